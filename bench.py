@@ -18,7 +18,12 @@ Workloads
 N > 1: every rank owns an independent block of frames / ensembles (dabgpu.shard.shard_range), no collective in the data path;
 torch.distributed (RCCL) carries only the timing barrier and the max over ranks -> "scaling": "weak".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload demod|full]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload demod|full] [--full] [--dump-outputs DIR]
+A plain run does what the headline figure needs: set-up, tuning, warm-up, the K timed steps, the result line.  `--full` adds
+everything else: the correctness check, the symbols-per-block candidates, the 4096-frame roofline and `extra.*` (demod, N = 1), the
+stage-by-stage rooflines (full), `cpu_baseline` / `cpu_baseline_full`.  `--dump-outputs DIR` (demod) writes what the last timed step
+computed as DIR/<name>.npy (float32): soft bits of a fixed seeded sample of frames, cyclic-prefix correlations, total phases and
+fine-frequency words; the fine-frequency state is zeroed before the timed steps, so equal arguments give equal files.
 `python bench.py --gpus N` started plainly (no RANK in the environment) launches N ranks itself through
 torch.distributed.run -- as a child process, before this process touches the GPU -- and exits with the child's status.
 
@@ -62,6 +67,8 @@ VIT_ALGO_PEAK_GSTEPS = N_SIMD * CLOCK_HZ * 64.0 / (VIT_ALGO_INSTR_PER_64_STEPS *
 # expected at LEAD and found within +-100 samples of it
 SLICE_LEAD = 1024
 SLICE_SAMPLES = SLICE_LEAD + 1544 + 196608
+# --dump-outputs: the soft bits of this many frames (a fixed seeded sample; all 1024 would be 943 MB as float32)
+DUMP_FRAMES, DUMP_SEED = 32, 1234
 
 
 def parse_args():
@@ -91,11 +98,18 @@ def parse_args():
     ap.add_argument("--aligned", action="store_true",
                     help="full / extras: frame-aligned input with synchronisation bypassed (what rounds 1-3 timed) instead of the sync-enabled path")
     ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: check, symbols-per-block candidates, 4096-frame roofline, extra.* (demod, N = 1), "
+                         "stage-by-stage rooflines (full workload), CPU baselines; the --no-* options select within it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="demod: after the timed steps, write what the last one computed as DIR/<name>.npy (float32, %d seeded frames' soft bits)" % DUMP_FRAMES)
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / sharding plumbing only, on CPU with gloo (tests/test_bench_launcher.py); no kernels, value = null")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="with --dry-run: this rank exits 3 (exit-status propagation test)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "demod":
+        ap.error("--dump-outputs: demod workload only (the full workload's state depends on the number of untimed prewarm steps)")
     if args.steps is None:
         args.steps = 400 if args.workload == "demod" else 10
     if args.warmup is None:
@@ -722,6 +736,22 @@ def cpu_baseline_full(sample, seconds_target=14.0):
                       f"{cores} pinned worker threads (one per physical core) x {per_thread} frames of the receivers the GPU decoded (incl. {warm} settling frames each), {dt:.1f} s wall"}
 
 
+def dump_outputs(dirname, torch, F, d_bits, d_corr, d_total, d_fine):
+    """--dump-outputs (demod): what the last timed step handed its caller, as DIR/<name>.npy in float32 -- the soft bits of DUMP_FRAMES
+    frames drawn with a fixed seed (all 1024 would be 943 MB), the cyclic-prefix correlations, total phase and fine-frequency word of
+    every frame (of 16384 seeded ones beyond that many): 31 MB at the default size, never more than 40 MB"""
+    import numpy as np
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = lambda n: torch.from_numpy(np.sort(rng.choice(F, size=min(F, n), replace=False))).to(d_bits.device)      # noqa: E731
+    rows = pick(DUMP_FRAMES)
+    per_frame = pick(16384) if F > 16384 else torch.arange(F, device=d_bits.device)
+    out = {"soft_bits_sampled_frames": d_bits[rows], "cp_corr": d_corr[per_frame], "total_phase": d_total[per_frame], "fine_freq": d_fine[per_frame]}
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def dry_run(args, rank, world):
     """the multi-rank plumbing of main() without a GPU: rendezvous (gloo), shard ranges, barrier, max over ranks, one line from rank 0"""
     import torch
@@ -809,12 +839,13 @@ def main():
         # symbols per workgroup: --spb 0 (default) leaves the choice to the library: dabgpu_ofdm_tune (called here, in the warm-up) times
         # a whole frame (75: one round of workgroups on a full chip, phase tail inside the kernel), two and three runs per frame (38, 25)
         # and records the fastest for this call shape (include/dabgpu.h; which one wins depends on the box); the data path
-        # only looks the record up.  The three are timed here once more (untimed region) only to put the numbers in the line
+        # only looks the record up.  With --full the three are timed here once more (untimed region) only to put the numbers in the line
         spb_timing = None
         if args.spb == 0 and F >= 512 and not args.dry_run:
             # explicit, blocking calibration (dabgpu_ofdm_tune), outside every timed region; symbols_per_block = 0 below then resolves to it
             ctx.ofdm_tune(iq_f, fmt_f32, F, d_bits, with_phase_tail=True)
             torch.cuda.synchronize()
+        if args.spb == 0 and F >= 512 and not args.dry_run and args.full:
             spb_timing = {}
             for rep in range(2):                                       # interleaved, the last pass counts: all see the same clock state
                 for cand in (25, 38, 75):
@@ -862,6 +893,8 @@ def main():
         torch.cuda.synchronize()
     for k in range(args.warmup):
         step(k)
+    if args.workload == "demod":
+        d_fine.zero_()        # the fine-frequency words walk on with every call: the timed steps start from zero whatever the prewarm ran
     barrier()
     region = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.workload == "demod" and not args.dry_run else None
     t0 = time.perf_counter()
@@ -883,9 +916,12 @@ def main():
     else:
         k_ms = sum(a.elapsed_time(b) for a, b in evs) / max(1, len(evs))  # mean demod launch duration inside the timed loop
 
-    # ---- correctness of what was just timed (untimed) ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, F, d_bits, d_corr, d_total, d_fine)
+
+    # ---- correctness of what was just timed (untimed, --full) ----
     check = {}
-    if args.workload == "demod" and not args.no_check:
+    if args.full and args.workload == "demod" and not args.no_check:
         hard = (d_bits.view(F, 75, 3072) >= 0).to(torch.uint8)
         err = (hard != tx_bits)
         check["hard_bit_errors_vs_transmitted"] = int(err.sum().item())
@@ -899,7 +935,7 @@ def main():
                 exp = O.demod_frame(iq[kk].cpu().numpy(), float(freq[kk].item()))
                 mism += int((exp["bits"] != d_bits[kk].cpu().numpy()).sum())
             check["soft_bit_mismatches_vs_oracle_3_frames"] = mism
-    elif args.workload == "full" and not args.no_check:
+    elif args.full and args.workload == "full" and not args.no_check:
         check = pipe.check(dabgpu)
 
     if rank == 0:
@@ -935,11 +971,16 @@ def main():
             "x_realtime": value / REALTIME_FRAMES_PER_S,
             "ms_per_step_per_rank": per_rank_ms,
             "roofline": hbm_roofline("ofdm_demod_kernel", k_ms, units),
-            "check": check,
         }
+        if args.full:
+            line["check"] = check
         if region:
             line["roofline"]["timing"] = (f"one pair of HIP events around the {args.steps} back-to-back launches of the timed loop, on their stream: "
                                           f"{k_ms_events:.4f} ms per launch" + ("" if (args.spb or ctx.ofdm_tuned_symbols_per_block(fmt_f32, units, with_phase_tail=True)) == 75 else " (incl. the 5 us phase-tail launch of each step)"))
+        elif not args.full:
+            line["roofline"] = hbm_roofline("ofdm_demod_kernel" if args.aligned else "ofdm_sync_kernel + ofdm_demod_kernel", k_ms, units)
+            line["roofline"]["timing"] = (f"HIP events around the demodulation launches inside the timed loop, overlapped with the other frame's trellis "
+                                          f"kernel: {k_ms_events:.4f} ms, mean of {len(evs)} launches (--full times the stages one at a time)")
         else:
             # configs[4]: inside the timed loop the demodulation of frame j + 1 runs BESIDE the trellis kernel of frame j (two frames in
             # flight), so its launches last longer than the kernel needs; the rooflines are taken one stage at a time after the loop
@@ -966,8 +1007,8 @@ def main():
             # 256 CUs x 4: the tail of the round is idle time the figure above includes).  Not under --no-extras: the profile passes (rocprofv3 kernel
             # stats, PMC) of that command must see launches of ONE shape only
             try:
-                if args.no_extras:
-                    raise RuntimeError("skipped (--no-extras)")
+                if args.no_extras or not args.full:
+                    raise RuntimeError("skipped (--no-extras)" if args.full else "skipped (runs with --full)")
                 F4 = 4 * units
                 big_iq = iq_f.repeat(4, 1, 1).contiguous()
                 big_bits = torch.empty((F4, 230400), dtype=torch.int8, device=device)
@@ -1007,7 +1048,7 @@ def main():
         except Exception:
             pass
         host_sample = None
-        if world == 1 and args.workload == "demod" and not args.no_extras:
+        if args.full and world == 1 and args.workload == "demod" and not args.no_extras:
             del iq, iq_f, tx_bits, d_bits
             torch.cuda.empty_cache()
             c2, c3, host_sample = extras_configs23(ctx, dabgpu, torch, device, args.extra_ensembles, args.distinct, layout=int(args.hist_layout == "classed"),
@@ -1040,7 +1081,7 @@ def main():
                 import bench_chain
                 line["extra"]["chain"] = bench_chain.run_chain(ctx, dabgpu, torch, device, args.extra_ensembles, args.distinct,
                                                                layout=int(args.hist_layout == "classed"))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
             if host_sample is not None:
                 line["cpu_baseline_full"] = cpu_baseline_full(host_sample)

@@ -41,3 +41,9 @@ def test_full_workload_shards_8192_ensembles_per_rank():
 def test_failing_rank_gives_nonzero_exit_status():
     res = run(["--gpus", "2", "--dry-run-fail-rank", "1"])
     assert res.returncode != 0
+
+
+def test_dump_outputs_is_refused_for_the_full_workload():
+    # the full workload's ring and synchroniser state depend on how many untimed prewarm steps ran: no reproducible dump
+    res = run(["--workload", "full", "--dump-outputs", "unused"])
+    assert res.returncode == 2 and "--dump-outputs" in res.stderr

@@ -2,7 +2,8 @@
 same programs the measurements come from:
 configs[1] (1024 frames of the demodulator: hard bits == transmitted bits for every frame, soft bits == oracle on sampled frames) and
 configs[2]/[3] (4096 ensembles x 18 sub-channels, two frames in flight: every FIB CRC passes, every decoded byte equals the transmitted
-payload) through bench.py's default line; configs[4] per GPU (8192 ensembles, bench.py --workload full) with the same checks."""
+payload) through bench.py --full; configs[4] per GPU (8192 ensembles, bench.py --workload full --full) with the same checks; and the
+plain line (no checks, no extras) with what --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def run_json(args):
 
 
 def test_bench_line_contract_and_full_size_checks():
-    d = run_json(["bench.py", "--steps", "20", "--warmup", "3", "--prewarm-ms", "50", "--no-cpu-baseline"])
+    d = run_json(["bench.py", "--full", "--steps", "20", "--warmup", "3", "--prewarm-ms", "50", "--no-cpu-baseline"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "extra"):
         assert key in d, key
@@ -47,12 +48,37 @@ def test_bench_line_contract_and_full_size_checks():
 
 
 def test_full_workload_of_configs4_per_gpu():
-    d = run_json(["bench.py", "--workload", "full", "--steps", "4", "--warmup", "1", "--prewarm-ms", "0", "--no-cpu-baseline"])
+    d = run_json(["bench.py", "--workload", "full", "--full", "--steps", "4", "--warmup", "1", "--prewarm-ms", "0", "--no-cpu-baseline"])
     assert d["config"]["ensembles_per_gpu"] == 8192 and d["n_gpus"] == 1 and d["scaling"] == "weak"
     c = d["check"]
     assert c["ensembles_checked"] == 8192 and c["fib_crc_pass"] == c["fib_crc_expected"]
     assert c["fib_bytes_equal_transmitted"] is True and c["msc_bytes_equal_transmitted"] is True
     assert d["value"] > 2.0e5
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run carries the headline keys and nothing that takes runs of its own; two runs with the same arguments dump equal arrays"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = run_json(["bench.py", "--steps", "7", "--warmup", "2", "--prewarm-ms", "50", "--dump-outputs", str(out)])
+        assert d["metric"] == "dab_mode1_frames_per_sec" and d["unit"] == "frames/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0.0 and d["value"] > 1.0e6
+        assert abs(d["value"] - 1024 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        for key in ("extra", "cpu_baseline", "cpu_baseline_full", "check"):
+            assert key not in d, key
+        files = sorted(out.glob("*.npy"))
+        assert [f.name for f in files] == ["cp_corr.npy", "fine_freq.npy", "soft_bits_sampled_frames.npy", "total_phase.npy"]
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs["soft_bits_sampled_frames"].shape == (32, 230400) and arrs["cp_corr"].shape == (1024, 76, 2)
+        assert arrs["total_phase"].shape == arrs["fine_freq"].shape == (1024,)
+        assert np.abs(arrs["soft_bits_sampled_frames"]).max() > 0 and np.isfinite(arrs["cp_corr"]).all()
+        dumps.append(arrs)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_stage_by_stage_tool_at_1024_ensembles():

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out
 mkdir -p $OUT
 BENCH_ARGS="--no-cpu-baseline --no-check --no-extras"
-python3 bench.py > $OUT/bench_n1_$TAG.json 2> $OUT/bench_n1_$TAG.err
+python3 bench.py --full > $OUT/bench_n1_$TAG.json 2> $OUT/bench_n1_$TAG.err
 # (symbols_per_block = 0 resolves to what dabgpu_ofdm_tune records in each process's warm-up)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python3 bench.py --steps 20 --warmup 3 $BENCH_ARGS > $OUT/prof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python3 bench.py --steps 3 --warmup 1 $BENCH_ARGS > $OUT/pmc_fetch.log 2>&1
@@ -22,7 +22,7 @@ cp $(find $OUT/prof_sync -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_chain -o trace -- python3 tools/bench_chain.py --ensembles 4096 --steps 8 > $OUT/bench_chain_profiled_$TAG.json 2> $OUT/prof_chain.log
 cp $(find $OUT/prof_chain -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats_chain4096_$TAG.csv; rm -rf $OUT/prof_chain
 python3 tools/bench_chain.py --ensembles 4096 > $OUT/bench_chain_$TAG.json 2> $OUT/bench_chain_$TAG.err
-python3 bench.py --workload full --no-cpu-baseline > $OUT/bench_full_$TAG.json 2> $OUT/bench_full_$TAG.err
+python3 bench.py --workload full --full --no-cpu-baseline > $OUT/bench_full_$TAG.json 2> $OUT/bench_full_$TAG.err
 python3 tools/bench_decode.py --ensembles 4096 --steps 6 > $OUT/bench_decode_4096_$TAG.json 2> $OUT/bench_decode_4096_$TAG.err
 python3 tools/bench_mirror.py > $OUT/bench_mirror_$TAG.json 2> $OUT/bench_mirror_$TAG.err
 # several receivers in one process: private pipelines, all in the receiver bank, and the classes' AUTO rule (the second and later ones banked)
