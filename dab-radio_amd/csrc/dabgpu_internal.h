@@ -108,6 +108,14 @@ int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int
                                   int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
                                   size_t block_stride, hipStream_t s);
 
+// the inverse carrier mapper of modes II-IV on the device (carrier c carries soft bit inv[c]), built on the context at first use (ofdm_wave512.hip)
+int dabgpu_mode_inv_map(dabgpu_ctx* c, int mode, const int** out);
+
+// OFDM transmitter (ofdm_mod.hip): n_frames frames of `mode` from their payloads (layout DABGPU_TX_PAYLOAD_*) into d_out (format
+// DABGPU_IQ_RAW_F32L / _U8), NULL first; d_prs = the PRS spectrum (nb_fft complex float) on the device; arguments checked by the caller
+int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int layout, size_t n_frames, const float* d_prs, float freq_norm,
+                           void* d_out, int out_format, hipStream_t s);
+
 // ---- channel decode ----
 typedef dabgpu_codeword dabgpu_cw_desc;
 typedef dabgpu_codeword_result dabgpu_cw_result;

@@ -443,14 +443,12 @@ void ofdm_demod_wave3_kernel(const f2* __restrict__ iq, const float* __restrict_
 
 using namespace dabgpu;
 
-// modes II, III and IV without the GUI views; frame = stream when d_desc != nullptr (stream bank rounds)
-int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                  int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
-                                  size_t block_stride, hipStream_t s) {
+// inverse of the frequency interleaver of modes II-IV on the device, built on first use: carrier c carries soft bit inv[c]
+// (get_DAB_mapper_ref); the transmitter (ofdm_mod.hip) reads the same table
+int dabgpu_mode_inv_map(dabgpu_ctx* c, int mode, const int** out) {
     ModeGeom g;
-    if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_wave: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
+    if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("mode inverse mapper: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
     int st;
-    // inverse of the frequency interleaver on the device, built on first use: carrier c carries soft bit inv[c] (get_DAB_mapper_ref)
     if (!c->d_mode_inv_map[mode]) {
         std::vector<int> m((size_t)g.n_carriers), inv((size_t)g.n_carriers);
         if ((st = dabgpu_get_carrier_mapper(mode, m.data()))) return st;
@@ -461,13 +459,26 @@ int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int
         if ((st = dabgpu_check_hip(hipMemcpy(d_inv, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(mode inverse mapper)"))) { (void)hipFree(d_inv); return st; }
         c->d_mode_inv_map[mode] = d_inv;
     }
+    *out = c->d_mode_inv_map[mode];
+    return DABGPU_OK;
+}
+
+// modes II, III and IV without the GUI views; frame = stream when d_desc != nullptr (stream bank rounds)
+int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
+                                  int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
+                                  size_t block_stride, hipStream_t s) {
+    ModeGeom g;
+    if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_wave: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
+    int st;
+    const int* d_inv = nullptr;
+    if ((st = dabgpu_mode_inv_map(c, mode, &d_inv))) return st;
     if (symbols_per_block <= 0 || symbols_per_block > g.n_sym - 1) symbols_per_block = 19;
     const int chunks = (g.n_sym - 1 + symbols_per_block - 1) / symbols_per_block;
     const size_t units = (size_t)n_frames * chunks;
     const dim3 grid((unsigned)((units + 3) / 4));
 #define WAVE_GO(MODE, SRC, BANK)                                                                                                   \
     hipLaunchKernelGGL((ofdm_demod_wave_kernel<MODE, SRC, BANK>), grid, dim3(256), 0, s, reinterpret_cast<const f2*>(d_iq), d_freq, d_bits, \
-                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), c->d_mode_inv_map[mode], n_frames,    \
+                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), d_inv, n_frames,                      \
                        symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride)
 #define WAVE_MODE(MODE)                                          \
     do {                                                         \
@@ -479,7 +490,7 @@ int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int
     } while (0)
 #define WAVE3_GO(SRC, BANK)                                                                                                          \
     hipLaunchKernelGGL((ofdm_demod_wave3_kernel<SRC, BANK>), grid, dim3(256), 0, s, reinterpret_cast<const f2*>(d_iq), d_freq, d_bits,    \
-                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), c->d_mode_inv_map[mode], n_frames,     \
+                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), d_inv, n_frames,                       \
                        symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride)
     if (mode == 2) WAVE_MODE(2);
     else if (mode == 4) WAVE_MODE(4);

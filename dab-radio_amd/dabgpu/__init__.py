@@ -69,7 +69,12 @@ ABI_SYMBOLS = [
     "dabgpu_receiver_reset", "dabgpu_receiver_submit_sync", "dabgpu_receiver_wait_sync", "dabgpu_receiver_submit_frame", "dabgpu_receiver_wait_frame",
     "dabgpu_receiver_submit_demod", "dabgpu_receiver_submit_decode",
     "dabgpu_ingest_create", "dabgpu_ingest_destroy", "dabgpu_ingest_acquire", "dabgpu_ingest_submit", "dabgpu_ingest_wait", "dabgpu_ingest_consumed",
+    "dabgpu_ofdm_modulate_frames", "dabgpu_ofdm_modulate_frames_host_sync",
 ]
+
+# OFDM transmitter payload layouts (include/dabgpu.h)
+TX_PAYLOAD_REFERENCE = 0
+TX_PAYLOAD_FRAME_BITS = 1
 
 IQ_FORMATS = ["raw_u8", "raw_s8", "raw_s16l", "raw_s16b", "raw_u16l", "raw_u16b", "raw_s32l", "raw_s32b", "raw_u32l", "raw_u32b",
               "raw_f32l", "raw_f32b", "raw_f64l", "raw_f64b",
@@ -263,6 +268,10 @@ def lib():
         L.dabgpu_ingest_submit.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.dabgpu_ingest_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_ingest_consumed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_ofdm_modulate_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_float,
+                                                  C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_ofdm_modulate_frames_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_float,
+                                                            C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -537,6 +546,26 @@ class Context:
         n = raw.size // sb
         out = np.empty(2 * n, np.float32)
         check(lib().dabgpu_iq_convert_host_sync(self._h, _ptr(raw), int(fmt), n, _ptr(out)), "dabgpu_iq_convert_host_sync")
+        return out
+
+    def ofdm_modulate_frames(self, mode, payload, n_frames, out, layout=TX_PAYLOAD_REFERENCE, out_format=None, prs_fft_ref=None,
+                             freq_norm=0.0, stream=None):
+        """OFDM transmitter (asynchronous): n_frames payloads on the device -> NULL-first frames in `out` (device, 16-byte aligned);
+        out_format = IQ_FORMATS.index("raw_f32l") (default) or IQ_FORMATS.index("raw_u8"); prs_fft_ref = device spectrum or None"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_ofdm_modulate_frames(self._h, int(mode), _ptr(payload), int(layout), n_frames, _ptr(prs_fft_ref), float(freq_norm),
+                                                _ptr(out), fmt, self._stream(stream)), "dabgpu_ofdm_modulate_frames")
+
+    def ofdm_modulate_frames_host(self, mode, payload, n_frames, layout=TX_PAYLOAD_REFERENCE, out_format=None, prs_fft_ref=None, freq_norm=0.0):
+        """numpy form: returns [n_frames][samples per frame] complex64 (raw_f32l) or [n_frames][2 * samples] uint8 (raw_u8)"""
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        n_samp = ofdm_params(mode)["nb_frame_samples"]
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        prs = None if prs_fft_ref is None else np.ascontiguousarray(prs_fft_ref, dtype=np.complex64)
+        out = np.empty((n_frames, n_samp), np.complex64) if fmt == IQ_FORMATS.index("raw_f32l") else np.empty((n_frames, 2 * n_samp), np.uint8)
+        check(lib().dabgpu_ofdm_modulate_frames_host_sync(self._h, int(mode), _ptr(payload), int(layout), n_frames, _ptr(prs), float(freq_norm),
+                                                          _ptr(out), fmt), "dabgpu_ofdm_modulate_frames_host_sync")
         return out
 
     def soft_bits_to_hard_bytes(self, bits, n_bytes, out, stream=None):

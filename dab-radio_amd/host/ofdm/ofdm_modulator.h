@@ -1,0 +1,35 @@
+// ofdm/ofdm_modulator.h -- OFDM_Modulator with the reference's public interface (src/ofdm/ofdm_modulator.h), re-implemented over the
+// MI355X C ABI (include/dabgpu.h, dabgpu_ofdm_modulate_frames_host_sync): the DQPSK chain, the inverse transforms and the cyclic
+// prefixes of a frame run on the device, in one call per ProcessBlock.
+//   params        one of the four DAB geometries (get_DAB_OFDM_params); anything else has no device path and throws std::runtime_error
+//   prs_fft_ref   the PRS spectrum (nb_fft bins) the frame starts from -- the caller's, as given
+//   ProcessBlock  frame_out_buf = nb_null_period + nb_symbol_period * nb_frame_symbols samples, NULL first; data_in_buf =
+//                 (nb_frame_symbols - 1) * nb_data_carriers / 4 bytes, 2 bits per carrier in natural carrier order.  Wrong sizes return
+//                 false and write nothing (ofdm_modulator.cpp:54-63); a device failure throws std::runtime_error.
+// Every ProcessBlock starts the chain from the PRS again (ofdm_modulator.cpp:73-76): the object keeps no state between frames.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+#include <complex>
+#include <vector>
+#include "utility/span.h"
+#include "./ofdm_params.h"
+
+class OFDM_Modulator
+{
+private:
+    const OFDM_Params m_params;
+    int m_mode = 0;
+    const size_t m_frame_out_size;
+    const size_t m_data_in_size;
+    std::vector<std::complex<float>> m_prs_fft_ref;
+public:
+    OFDM_Modulator(
+        const OFDM_Params& params,
+        tcb::span<const std::complex<float>> prs_fft_ref);
+    ~OFDM_Modulator();
+    bool ProcessBlock(
+        tcb::span<std::complex<float>> frame_out_buf,
+        tcb::span<const uint8_t> data_in_buf);
+};

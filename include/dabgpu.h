@@ -825,6 +825,33 @@ int dabgpu_soft_bits_to_hard_bytes_host_sync(dabgpu_ctx *ctx, const int8_t *h_bi
 int dabgpu_hard_bytes_to_soft_bits_host_sync(dabgpu_ctx *ctx, const uint8_t *h_bytes, size_t n_bytes, int8_t *h_bits);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * OFDM transmitter (src/ofdm/ofdm_modulator.cpp:49-156; examples/simulate_transmitter.cpp:167-178 for the u8 form).
+ * n_frames independent frames of `transmission_mode` (1..4), each NULL first in transmission order: nb_null_period +
+ * nb_symbol_period * nb_frame_symbols samples (dabgpu_get_ofdm_params(mode)[6]), exactly OFDM_Modulator::ProcessBlock's output.
+ * Every frame starts its DQPSK chain from the PRS (ofdm_modulator.cpp:73-76).
+ *   d_payload  [n_frames][(nb_frame_symbols - 1) * nb_data_carriers / 4] bytes in layout `payload_layout`:
+ *     DABGPU_TX_PAYLOAD_REFERENCE   OFDM_Modulator's input: natural carrier order, 2 bits per carrier LSB first, PHASE_MAP
+ *                                   {(-A,-A), (A,-A), (A,A), (-A,A)}, A = 1/sqrt(2) (ofdm_modulator.cpp:95-156)
+ *     DABGPU_TX_PAYLOAD_FRAME_BITS  the frame's hard bits as dabgpu_soft_bits_to_hard_bytes writes them (bit i -> byte i/8, bit i%8), in the
+ *                                   demodulator's de-interleaved order: bit n of a symbol sets the real part of carrier mapper[n], bit n + NC
+ *                                   its imaginary part, z = ((1 - 2 b_n) + j (1 - 2 b_{n+NC})) * A.  Demodulating the result gives back
+ *                                   the same hard bits.  Mode I uses the context's carrier mapper.
+ *   d_prs_fft_ref  nb_fft complex float on the device (8-byte aligned), or NULL for the mode's table (mode I: the context's)
+ *   freq_norm  != 0: apply_pll(frame, freq_norm) with its phase at 0 on each frame's first sample (both output formats)
+ *   d_out      [n_frames][samples per frame] in out_format, 16-byte aligned:
+ *     DABGPU_IQ_RAW_F32L  complex float
+ *     DABGPU_IQ_RAW_U8    QuantisedIQ<uint8_t>::from_iq(I * scale, Q * scale), scale = (1.0f / NC * 4.0f) * 127.5f
+ * Asynchronous on `stream`.  A bad context, mode, layout or format, or a NULL payload / output with n_frames > 0, returns
+ * DABGPU_ERR_INVALID_ARG before any device call. */
+enum { DABGPU_TX_PAYLOAD_REFERENCE = 0, DABGPU_TX_PAYLOAD_FRAME_BITS = 1 };
+int dabgpu_ofdm_modulate_frames(dabgpu_ctx *ctx, int transmission_mode, const uint8_t *d_payload, int payload_layout,
+                                size_t n_frames, const float *d_prs_fft_ref, float freq_norm,
+                                void *d_out, int out_format, void *stream);
+/* the same from and to host memory (h_prs_fft_ref may be NULL), on the context's stream; returns when h_out is written */
+int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx *ctx, int transmission_mode, const uint8_t *h_payload, int payload_layout,
+                                          size_t n_frames, const float *h_prs_fft_ref, float freq_norm, void *h_out, int out_format);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Ingest pipe: the host -> device hand-over of capture bytes.  Replaces the reader thread -> OFDM_Demod::Process hand-over
  * of examples/app_helpers/app_ofdm_blocks.h:45-58 and the memcpy of OFDM_Demod::ReadSymbols (src/ofdm/ofdm_demodulator.cpp:550-577).
  * A ring of `depth` PINNED host buffers with device twins and a copy stream of its own:
