@@ -52,6 +52,42 @@ int dabgpu_device_count(void) {
 }
 
 // ---- context ----
+// the device tables of `mode` from its PRS spectrum and carrier mapper (nullptr: the built-in ones, get_DAB_mapper_ref,
+// src/ofdm/dab_mapper_ref.cpp:10-51), in one allocation (t.prs) that is complete or not made (ofdm_demodulator.cpp:128-140)
+static int build_mode_tables(dabgpu_ctx* c, int mode, const float* prs, const int* mapper, dabgpu_mode_tables* out) {
+    dabgpu::ModeGeom g;
+    dabgpu::mode_geometry(mode, g);
+    const int nc = g.n_carriers;
+    const size_t prs_bytes = sizeof(float) * 2 * (size_t)g.n_fft, map_bytes = sizeof(int) * (size_t)nc;
+    // PRS | coarse-sync reference | mapper | its inverse | the inverse as uint16_t (every part a multiple of 16 bytes but the last)
+    std::vector<unsigned char> h(2 * prs_bytes + 2 * map_bytes + sizeof(uint16_t) * (size_t)nc);
+    float* h_prs = reinterpret_cast<float*>(h.data());
+    int* h_map = reinterpret_cast<int*>(h.data() + 2 * prs_bytes);
+    int* inv = h_map + nc;
+    uint16_t* inv16 = reinterpret_cast<uint16_t*>(h.data() + 2 * prs_bytes + 2 * map_bytes);
+    if (prs) memcpy(h_prs, prs, prs_bytes); else dabgpu_get_prs_fft_ref(mode, h_prs);
+    if (mapper) memcpy(h_map, mapper, map_bytes); else dabgpu_get_carrier_mapper(mode, h_map);
+    memset(inv, 0xFF, map_bytes);
+    for (int n = 0; n < nc; n++) {                // carrier -> soft bit: the inverse of the mapper, which must be a permutation
+        const int cidx = h_map[n];
+        if (cidx < 0 || cidx >= nc || inv[cidx] >= 0) {
+            dabgpu_set_error("carrier_mapper is not a permutation of 0..%d (entry %d = %d)", nc - 1, n, cidx);
+            return DABGPU_ERR_INVALID_ARG;
+        }
+        inv[cidx] = n; inv16[cidx] = (uint16_t)n;
+    }
+    unsigned char* d = nullptr;
+    int st = dabgpu_check_hip(hipMalloc(&d, h.size()), "hipMalloc(mode tables)");
+    if (!st) st = dabgpu_check_hip(hipMemcpy(d, h.data(), h.size(), hipMemcpyHostToDevice), "hipMemcpy(mode tables)");
+    const dabgpu_mode_tables t = {reinterpret_cast<float*>(d), reinterpret_cast<float*>(d + prs_bytes), reinterpret_cast<int*>(d + 2 * prs_bytes),
+                                  reinterpret_cast<int*>(d + 2 * prs_bytes + map_bytes), reinterpret_cast<uint16_t*>(d + 2 * prs_bytes + 2 * map_bytes)};
+    if (!st) st = dabgpu_check_hip(dabgpu_launch_sync_init(t.prs, c->d_tw, t.prs_time_ref, g.n_fft, c->stream), "sync_init_kernel launch");
+    if (!st) st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    if (st) { if (d) (void)hipFree(d); return st; }
+    *out = t;
+    return DABGPU_OK;
+}
+
 int dabgpu_create(dabgpu_ctx** out, int device, const float* h_prs, const int* h_mapper) {
     if (!out) return DABGPU_ERR_INVALID_ARG;
     *out = nullptr;
@@ -74,37 +110,15 @@ int dabgpu_create(dabgpu_ctx** out, int device, const float* h_prs, const int* h
 
     dabgpu_ctx* c = new dabgpu_ctx();
     c->device = device;
-    c->prs.resize(2 * DABGPU_NB_FFT);
-    c->mapper.resize(DABGPU_NB_DATA_CARRIERS);
-    if (h_prs) memcpy(c->prs.data(), h_prs, sizeof(float) * 2 * DABGPU_NB_FFT); else dabgpu_get_prs_fft_ref(1, c->prs.data());
-    if (h_mapper) memcpy(c->mapper.data(), h_mapper, sizeof(int) * DABGPU_NB_DATA_CARRIERS); else dabgpu_get_carrier_mapper(1, c->mapper.data());
-
-    // inverse of the frequency de-interleaver: output position n of carrier c (mapper[n] = c)
-    std::vector<uint16_t> inv(DABGPU_NB_DATA_CARRIERS, 0xFFFF);
-    for (int i = 0; i < DABGPU_NB_DATA_CARRIERS; i++) {
-        const int cidx = c->mapper[i];
-        if (cidx < 0 || cidx >= DABGPU_NB_DATA_CARRIERS || inv[cidx] != 0xFFFF) {
-            dabgpu_set_error("carrier_mapper is not a permutation of 0..1535 (entry %d = %d)", i, cidx);
-            delete c;
-            return DABGPU_ERR_INVALID_ARG;
-        }
-        inv[cidx] = (uint16_t)i;
-    }
     std::vector<float> tw(2 * DABGPU_NB_FFT);
     dabgpu_get_fft_twiddles(tw.data());
 
 #define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) { dabgpu_destroy(c); return st; } } while (0)
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CK(hipMalloc(&c->d_tw, sizeof(float) * tw.size()));
-    CK(hipMalloc(&c->d_inv_map, sizeof(uint16_t) * inv.size()));
-    CK(hipMalloc(&c->d_prs, sizeof(float) * c->prs.size()));
     CK(hipMemcpy(c->d_tw, tw.data(), sizeof(float) * tw.size(), hipMemcpyHostToDevice));
-    CK(hipMemcpy(c->d_inv_map, inv.data(), sizeof(uint16_t) * inv.size(), hipMemcpyHostToDevice));
-    CK(hipMemcpy(c->d_prs, c->prs.data(), sizeof(float) * c->prs.size(), hipMemcpyHostToDevice));
-    CK(hipMalloc(&c->d_prs_time_ref, sizeof(float) * 2 * DABGPU_NB_FFT));
-    CK(dabgpu_launch_sync_init(c->d_prs, c->d_tw, c->d_prs_time_ref, DABGPU_NB_FFT, c->stream));     // ofdm_demodulator.cpp:134-140
-    CK(hipStreamSynchronize(c->stream));
 #undef CK
+    if ((st = build_mode_tables(c, 1, h_prs, h_mapper, &c->modes[1]))) { dabgpu_destroy(c); return st; }
     *out = c;
     return DABGPU_OK;
 }
@@ -113,14 +127,8 @@ void dabgpu_destroy(dabgpu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->d_tw) (void)hipFree(c->d_tw);
-    if (c->d_inv_map) (void)hipFree(c->d_inv_map);
-    if (c->d_prs) (void)hipFree(c->d_prs);
-    if (c->d_prs_time_ref) (void)hipFree(c->d_prs_time_ref);
     if (c->d_vit_tables) (void)hipFree(c->d_vit_tables);
-    for (int* p : c->d_mode_mapper) if (p) (void)hipFree(p);
-    for (int* p : c->d_mode_inv_map) if (p) (void)hipFree(p);
-    for (float* p : c->d_mode_prs) if (p) (void)hipFree(p);
-    for (float* p : c->d_mode_prs_time_ref) if (p) (void)hipFree(p);
+    for (const dabgpu_mode_tables& t : c->modes) if (t.prs) (void)hipFree(t.prs);
     for (void* p : c->scratch) if (p) (void)hipFree(p);
     for (void* p : c->parked) if (p) (void)hipFree(p);
     for (auto& sl : c->stage) {
@@ -247,27 +255,21 @@ extern "C" int dabgpu_ofdm_auto_symbols_per_block(dabgpu_ctx* c, size_t n_frames
 static int ofdm_demod_any(dabgpu_ctx* c, const void* d_iq, int src, size_t n_frames, const float* d_freq, int8_t* d_bits,
                          float* d_cp_corr, float* d_fft, float* d_dqpsk, int symbols_per_block, size_t bits_frame_stride, void* stream,
                          int bits_layout = DABGPU_BITS_NATURAL, float* d_total_phase = nullptr, float* d_fine_freq = nullptr, float beta = 0.0f) {
-    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) {
-        dabgpu_set_error("ofdm_demod_frames: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG;
-    }
+    int st = dabgpu_check_bits_layout("ofdm_demod_frames", bits_layout);
+    if (st) return st;
     if (!c || !d_iq || !d_bits) { dabgpu_set_error("ofdm_demod_frames: null ctx/iq/bits"); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0) return DABGPU_OK;
     if (n_frames > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_demod_frames: n_frames too large"); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_frame_stride != 0 && (bits_frame_stride < DABGPU_NB_FRAME_BITS || (bits_frame_stride & 15))) {
-        dabgpu_set_error("ofdm_demod_frames: bits_frame_stride must be 0 or a multiple of 16 >= 230400"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_iq & 15) || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("ofdm_demod_frames: d_iq and d_bits must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if ((st = dabgpu_check_bits_buffers("ofdm_demod_frames", bits_frame_stride, "d_iq", d_iq, 16, d_bits))) return st;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;      // NULL = the HIP default (null) stream
     float* corr = d_cp_corr;
-    if (!corr) {     // the kernel always produces the correlation; park it in context scratch when unwanted
-        int st = dabgpu_scratch(c, 0, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr, s);
-        if (st) return st;
-    }
+    // the kernel always produces the correlation; park it in context scratch when unwanted
+    if (!corr && (st = dabgpu_scratch(c, SCR_DEMOD_CORR, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr, s))) return st;
     if (symbols_per_block <= 0)
         symbols_per_block = (d_fft || d_dqpsk) ? dabgpu_host_small_batch_spb(n_frames)      /* display views: three workgroups per CU, not tuned */
                                                : demod_cached_spb(c, n_frames, dabgpu_host_spb_variant(src, bits_layout, d_total_phase || d_fine_freq));
-    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, src, d_freq, d_bits, corr, d_fft, d_dqpsk, c->d_tw, c->d_inv_map,
+    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, src, d_freq, d_bits, corr, d_fft, d_dqpsk, c->d_tw, c->modes[1].inv_map16,
                                                      (int)n_frames, symbols_per_block, bits_frame_stride, nullptr, nullptr, 0,
                                                      bits_layout == DABGPU_BITS_MSC_CLASSED, s, d_total_phase, d_fine_freq, beta),
                             "ofdm_demod_kernel launch");
@@ -278,27 +280,16 @@ int dabgpu_ofdm_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_frames, 
     return ofdm_demod_any(c, d_iq, 0, n_frames, d_freq, d_bits, d_cp_corr, d_fft, d_dqpsk, symbols_per_block, bits_frame_stride, stream);
 }
 
-// capture formats the demodulator's loader dequantises itself (iq_decode.h): 0 = complex float, 1 = u8, 2 = s8, 3 = s16 little endian
-static int fused_loader_of(int format) {
-    switch (format) {
-    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32: return 0;
-    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8: return 1;
-    case DABGPU_IQ_RAW_S8: return 2;
-    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16: return 3;
-    default: return -1;
-    }
-}
-
 int dabgpu_ofdm_demod_frames_raw(dabgpu_ctx* c, const void* d_raw, int format, size_t n_frames, const float* d_freq, int8_t* d_bits,
                                  float* d_cp_corr, float* d_fft, float* d_dqpsk, int symbols_per_block, size_t bits_frame_stride, void* stream) {
-    const int src = fused_loader_of(format);
+    const int src = dabgpu_fused_loader(format);
     if (src >= 0) return ofdm_demod_any(c, d_raw, src, n_frames, d_freq, d_bits, d_cp_corr, d_fft, d_dqpsk, symbols_per_block, bits_frame_stride, stream);
     // formats without a fused loader: convert into context scratch on the same stream, then demodulate
     if (!c) { dabgpu_set_error("ofdm_demod_frames_raw: null context"); return DABGPU_ERR_INVALID_ARG; }
     if (dabgpu_iq_format_sample_bytes(format) == 0) { dabgpu_set_error("ofdm_demod_frames_raw: unknown format %d", format); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0) return DABGPU_OK;
     float* d_iq;
-    int st = dabgpu_scratch(c, 22, n_frames * DABGPU_NB_FRAME_SAMPLES * 2 * sizeof(float), (void**)&d_iq);
+    int st = dabgpu_scratch(c, SCR_RAW_IQ, n_frames * DABGPU_NB_FRAME_SAMPLES * 2 * sizeof(float), (void**)&d_iq);
     if (st) return st;
     if ((st = dabgpu_iq_convert(c, d_raw, format, n_frames * DABGPU_NB_FRAME_SAMPLES, d_iq, stream))) return st;
     return ofdm_demod_any(c, d_iq, 0, n_frames, d_freq, d_bits, d_cp_corr, d_fft, d_dqpsk, symbols_per_block, bits_frame_stride, stream);
@@ -307,16 +298,16 @@ int dabgpu_ofdm_demod_frames_raw(dabgpu_ctx* c, const void* d_raw, int format, s
 int dabgpu_ofdm_demod_phase_frames(dabgpu_ctx* c, const void* d_raw, int format, size_t n_frames, const float* d_freq, int8_t* d_bits,
                                    float* d_cp_corr, int symbols_per_block, size_t bits_frame_stride, int bits_layout,
                                    float fine_freq_update_beta, float* d_total_phase, float* d_fine_freq, void* stream) {
-    const int src = fused_loader_of(format);
-    if (src < 0) { dabgpu_set_error("ofdm_demod_phase_frames: format %d has no fused loader (float32, u8, s8, s16 little endian do)", format); return DABGPU_ERR_INVALID_ARG; }
+    const int src = dabgpu_fused_loader(format, "ofdm_demod_phase_frames");
+    if (src < 0) return DABGPU_ERR_INVALID_ARG;
     return ofdm_demod_any(c, d_raw, src, n_frames, d_freq, d_bits, d_cp_corr, nullptr, nullptr, symbols_per_block, bits_frame_stride, stream, bits_layout,
                           d_total_phase, d_fine_freq, fine_freq_update_beta);
 }
 
 int dabgpu_ofdm_demod_frames_history(dabgpu_ctx* c, const void* d_raw, int format, size_t n_frames, const float* d_freq, int8_t* d_bits,
                                      float* d_cp_corr, int symbols_per_block, size_t bits_frame_stride, int bits_layout, void* stream) {
-    const int src = fused_loader_of(format);
-    if (src < 0) { dabgpu_set_error("ofdm_demod_frames_history: format %d has no fused loader (float32, u8, s8, s16 little endian do)", format); return DABGPU_ERR_INVALID_ARG; }
+    const int src = dabgpu_fused_loader(format, "ofdm_demod_frames_history");
+    if (src < 0) return DABGPU_ERR_INVALID_ARG;
     return ofdm_demod_any(c, d_raw, src, n_frames, d_freq, d_bits, d_cp_corr, nullptr, nullptr, symbols_per_block, bits_frame_stride, stream, bits_layout);
 }
 
@@ -327,16 +318,14 @@ int dabgpu_ofdm_demod_frames_history(dabgpu_ctx* c, const void* d_raw, int forma
 // at 25 / 38) on context scratch, not on the caller's fine-frequency state.  d_bits receives valid soft bits (identical for every run length).
 int dabgpu_ofdm_tune(dabgpu_ctx* c, const void* d_raw, int format, size_t n_frames, int8_t* d_bits, size_t bits_frame_stride, int bits_layout,
                      int with_phase_tail, void* stream, int* chosen) {
-    const int src = fused_loader_of(format);
     if (chosen) *chosen = 0;
-    if (src < 0) { dabgpu_set_error("ofdm_tune: format %d has no fused loader (float32, u8, s8, s16 little endian do)", format); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) { dabgpu_set_error("ofdm_tune: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG; }
+    const int src = dabgpu_fused_loader(format, "ofdm_tune");
+    if (src < 0) return DABGPU_ERR_INVALID_ARG;
+    int st = dabgpu_check_bits_layout("ofdm_tune", bits_layout);
+    if (st) return st;
     if (!c || !d_raw || !d_bits) { dabgpu_set_error("ofdm_tune: null ctx/iq/bits"); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0 || n_frames > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_tune: n_frames out of range"); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_frame_stride != 0 && (bits_frame_stride < DABGPU_NB_FRAME_BITS || (bits_frame_stride & 15))) {
-        dabgpu_set_error("ofdm_tune: bits_frame_stride must be 0 or a multiple of 16 >= 230400"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_raw & 15) || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("ofdm_tune: d_raw and d_bits must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if ((st = dabgpu_check_bits_buffers("ofdm_tune", bits_frame_stride, "d_raw", d_raw, 16, d_bits))) return st;
     if (n_frames < 512) { if (chosen) *chosen = dabgpu_host_small_batch_spb(n_frames); return DABGPU_OK; }      // nothing to measure: the small-batch rule
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
@@ -345,14 +334,14 @@ int dabgpu_ofdm_tune(dabgpu_ctx* c, const void* d_raw, int format, size_t n_fram
         (void)hipGetLastError(); dabgpu_set_error("ofdm_tune: the stream is capturing"); return DABGPU_ERR_INVALID_ARG;
     }
     float *corr, *tail = nullptr;
-    int st = dabgpu_scratch(c, 0, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr);
+    st = dabgpu_scratch(c, SCR_DEMOD_CORR, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr);
     if (st) return st;
     if (with_phase_tail) {
-        if ((st = dabgpu_scratch(c, 23, 2 * n_frames * sizeof(float), (void**)&tail))) return st;
+        if ((st = dabgpu_scratch(c, SCR_TUNE_TAIL, 2 * n_frames * sizeof(float), (void**)&tail))) return st;
         if ((st = dabgpu_check_hip(hipMemsetAsync(tail, 0, 2 * n_frames * sizeof(float), s), "hipMemsetAsync(tune)"))) return st;
     }
     auto launch = [&](int spb) {
-        return dabgpu_launch_ofdm_demod(d_raw, src, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, c->d_inv_map, (int)n_frames, spb, bits_frame_stride,
+        return dabgpu_launch_ofdm_demod(d_raw, src, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, c->modes[1].inv_map16, (int)n_frames, spb, bits_frame_stride,
                                         nullptr, nullptr, 0, bits_layout == DABGPU_BITS_MSC_CLASSED, s, tail, tail ? tail + n_frames : nullptr, 0.9f);
     };
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -390,7 +379,7 @@ int dabgpu_ofdm_tune(dabgpu_ctx* c, const void* d_raw, int format, size_t n_fram
 }
 
 int dabgpu_ofdm_tuned_symbols_per_block(dabgpu_ctx* c, int format, size_t n_frames, int bits_layout, int with_phase_tail) {
-    const int src = fused_loader_of(format);
+    const int src = dabgpu_fused_loader(format);
     if (!c || src < 0 || n_frames == 0) return 0;
     return demod_cached_spb(c, n_frames, dabgpu_host_spb_variant(src, bits_layout, with_phase_tail != 0));
 }
@@ -402,7 +391,8 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_str
                                   const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
                                   size_t bits_frame_stride, int bits_layout, float* d_total_phase, void* stream) {
     if (!c || !d_iq || !cfg || !d_states || !d_bits) { dabgpu_set_error("ofdm_sync_demod_frames: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) { dabgpu_set_error("ofdm_sync_demod_frames: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG; }
+    int st = dabgpu_check_bits_layout("ofdm_sync_demod_frames", bits_layout);
+    if (st) return st;
     if (n_streams == 0) return DABGPU_OK;
     if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_sync_demod_frames: n_streams too large"); return DABGPU_ERR_INVALID_ARG; }
     // the impulse peak lies in [0, 2048): the frame starts between 504 samples before and 1543 after the expected position
@@ -411,44 +401,41 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_str
         dabgpu_set_error("ofdm_sync_demod_frames: needs prs_offset_samples >= 504 and stream_stride_samples >= prs_offset_samples + 1544 + 76 * 2552");
         return DABGPU_ERR_INVALID_ARG;
     }
-    if (bits_frame_stride != 0 && (bits_frame_stride < DABGPU_NB_FRAME_BITS || (bits_frame_stride & 15))) {
-        dabgpu_set_error("ofdm_sync_demod_frames: bits_frame_stride must be 0 or a multiple of 16 >= 230400"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_iq & 7) || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("ofdm_sync_demod_frames: d_iq must be 8-byte, d_bits 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if ((st = dabgpu_check_bits_buffers("ofdm_sync_demod_frames", bits_frame_stride, "d_iq", d_iq, 8, d_bits))) return st;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
+    const dabgpu_mode_tables& t = c->modes[1];
     float* corr = d_cp_corr;
-    int st;
-    if (!corr && (st = dabgpu_scratch(c, 0, n_streams * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr, s))) return st;
+    if (!corr && (st = dabgpu_scratch(c, SCR_DEMOD_CORR, n_streams * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr, s))) return st;
     if ((st = dabgpu_check_hip(dabgpu_launch_sync(d_iq + 2 * prs_offset_samples, stream_stride_samples, (int)n_streams, cfg, d_states, nullptr, nullptr,
-                                                 c->d_tw, c->d_prs, c->d_prs_time_ref, nullptr, 1, s), "ofdm_sync_kernel launch"))) return st;
+                                                 c->d_tw, t.prs, t.prs_time_ref, nullptr, 1, s), "ofdm_sync_kernel launch"))) return st;
     if (symbols_per_block <= 0) symbols_per_block = demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
-    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, 0, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, c->d_inv_map, (int)n_streams, symbols_per_block,
+    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, 0, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, t.inv_map16, (int)n_streams, symbols_per_block,
                                                      bits_frame_stride, nullptr, nullptr, 0, bits_layout == DABGPU_BITS_MSC_CLASSED, s, d_total_phase, nullptr,
                                                      cfg->fine_freq_update_beta, nullptr, stream_stride_samples, d_states, (int)prs_offset_samples),
                             "ofdm_demod_kernel launch (synchronised frames)");
 }
 
-int dabgpu_ofdm_phase_update_mode(dabgpu_ctx* c, int mode, const float* d_cp_corr, size_t n_frames, float beta, float* d_total_phase,
-                                  float* d_fine_freq, void* stream) {
-    int geom[9];
-    if (!c || !d_cp_corr) { dabgpu_set_error("ofdm_phase_update_mode: null ctx/corr"); return DABGPU_ERR_INVALID_ARG; }
-    if (dabgpu_get_ofdm_params(mode, geom)) return DABGPU_ERR_INVALID_ARG;
+// ---- one body per operation for every transmission mode: the mode I entry points are the mode forms with mode = 1 ----
+static int phase_update(dabgpu_ctx* c, int mode, const float* d_cp_corr, size_t n_frames, float beta, float* d_total_phase, float* d_fine_freq,
+                        void* stream, const char* who) {
+    dabgpu::ModeGeom g;
+    if (!c || !d_cp_corr) { dabgpu_set_error("%s: null ctx/corr", who); return DABGPU_ERR_INVALID_ARG; }
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("%s: invalid transmission mode %d", who, mode); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0) return DABGPU_OK;
     DABGPU_BIND(c);
-    return dabgpu_check_hip(dabgpu_launch_ofdm_phase(d_cp_corr, (int)n_frames, beta, d_total_phase, d_fine_freq, 1, nullptr, geom[0], geom[3],
+    return dabgpu_check_hip(dabgpu_launch_ofdm_phase(d_cp_corr, (int)n_frames, beta, d_total_phase, d_fine_freq, 1, nullptr, g.n_sym, g.n_fft,
                                                      (hipStream_t)stream), "ofdm_phase_kernel launch");
+}
+
+int dabgpu_ofdm_phase_update_mode(dabgpu_ctx* c, int mode, const float* d_cp_corr, size_t n_frames, float beta, float* d_total_phase,
+                                  float* d_fine_freq, void* stream) {
+    return phase_update(c, mode, d_cp_corr, n_frames, beta, d_total_phase, d_fine_freq, stream, "ofdm_phase_update_mode");
 }
 
 int dabgpu_ofdm_phase_update(dabgpu_ctx* c, const float* d_cp_corr, size_t n_frames, float beta, float* d_total_phase,
                              float* d_fine_freq, void* stream) {
-    if (!c || !d_cp_corr) { dabgpu_set_error("ofdm_phase_update: null ctx/corr"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0) return DABGPU_OK;
-    DABGPU_BIND(c);
-    hipStream_t s = (hipStream_t)stream;
-    return dabgpu_check_hip(dabgpu_launch_ofdm_phase(d_cp_corr, (int)n_frames, beta, d_total_phase, d_fine_freq, 1, nullptr, DABGPU_NB_FRAME_SYMBOLS,
-                                                     DABGPU_NB_FFT, s),
-                            "ofdm_phase_kernel launch");
+    return phase_update(c, 1, d_cp_corr, n_frames, beta, d_total_phase, d_fine_freq, stream, "ofdm_phase_update");
 }
 
 int dabgpu_ofdm_demod_frames_host_sync(dabgpu_ctx* c, const float* h_iq, size_t n_frames, const float* h_freq,
@@ -462,131 +449,139 @@ int dabgpu_ofdm_demod_frames_host_sync(dabgpu_ctx* c, const float* h_iq, size_t 
     const size_t bits_bytes = n_frames * DABGPU_NB_FRAME_BITS;
     const size_t fft_bytes = n_frames * 77 * DABGPU_NB_FFT * 2 * sizeof(float);
     float *d_iq, *d_freq, *d_corr, *d_total, *d_fft = nullptr; int8_t* d_bits;
-    if ((st = dabgpu_scratch(c, 1, iq_bytes, (void**)&d_iq))) return st;
-    if ((st = dabgpu_scratch(c, 2, bits_bytes, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, 3, n_frames * sizeof(float), (void**)&d_freq))) return st;
-    if ((st = dabgpu_scratch(c, 4, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&d_corr))) return st;
-    if ((st = dabgpu_scratch(c, 5, n_frames * sizeof(float), (void**)&d_total))) return st;
-    if (h_fft && (st = dabgpu_scratch(c, 6, fft_bytes, (void**)&d_fft))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_IQ, iq_bytes, (void**)&d_iq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, bits_bytes, (void**)&d_bits))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, n_frames * sizeof(float), (void**)&d_freq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_CORR, n_frames * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&d_corr))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_PHASE, n_frames * sizeof(float), (void**)&d_total))) return st;
+    if (h_fft && (st = dabgpu_scratch(c, SCR_HOST_FFT, fft_bytes, (void**)&d_fft))) return st;
     hipStream_t s = c->stream;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemcpyAsync(d_iq, h_iq, iq_bytes, hipMemcpyHostToDevice, s));
-    if (h_freq) CK(hipMemcpyAsync(d_freq, h_freq, n_frames * sizeof(float), hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_iq, h_iq, iq_bytes, hipMemcpyHostToDevice, s));
+    if (h_freq) DABGPU_CK(hipMemcpyAsync(d_freq, h_freq, n_frames * sizeof(float), hipMemcpyHostToDevice, s));
     if ((st = dabgpu_ofdm_demod_frames(c, d_iq, n_frames, h_freq ? d_freq : nullptr, d_bits, d_corr, d_fft, nullptr, 0, 0, s))) return st;
     if ((st = dabgpu_ofdm_phase_update(c, d_corr, n_frames, 0.0f, d_total, nullptr, s))) return st;
-    CK(hipMemcpyAsync(h_bits, d_bits, bits_bytes, hipMemcpyDeviceToHost, s));
-    if (h_total_phase) CK(hipMemcpyAsync(h_total_phase, d_total, n_frames * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (h_fft) CK(hipMemcpyAsync(h_fft, d_fft, fft_bytes, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-#undef CK
+    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, bits_bytes, hipMemcpyDeviceToHost, s));
+    if (h_total_phase) DABGPU_CK(hipMemcpyAsync(h_total_phase, d_total, n_frames * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (h_fft) DABGPU_CK(hipMemcpyAsync(h_fft, d_fft, fft_bytes, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     return DABGPU_OK;
 }
 
-int dabgpu_ofdm_demod_stream_frame_sync(dabgpu_ctx* c, const float* h_iq, float freq_coarse, float* h_freq_fine, float beta,
-                                        int8_t* h_bits, float* h_total_phase, float* h_fft, float* h_dqpsk) {
-    if (!c || !h_iq || !h_bits || !h_freq_fine) { dabgpu_set_error("ofdm_demod_stream_frame_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
+// one frame of the OFDM_Demod mirror class from host memory; mode I runs the mode I demodulator and may return its DQPSK view
+static int stream_frame_sync(dabgpu_ctx* c, int mode, const float* h_iq, float freq_coarse, float* h_freq_fine, float beta, int8_t* h_bits,
+                             float* h_total_phase, float* h_fft, float* h_dqpsk, const char* who) {
+    dabgpu::ModeGeom g;
+    if (!c || !h_iq || !h_bits || !h_freq_fine) { dabgpu_set_error("%s: null argument", who); return DABGPU_ERR_INVALID_ARG; }
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("%s: invalid transmission mode %d", who, mode); return DABGPU_ERR_INVALID_ARG; }
     int st;
     DABGPU_BIND(c);
     DABGPU_HOST_LOCK(c);
-    const size_t iq_bytes = (size_t)DABGPU_NB_FRAME_SAMPLES * 2 * sizeof(float);
-    const size_t fft_bytes = (size_t)77 * DABGPU_NB_FFT * 2 * sizeof(float);
-    const size_t dq_bytes = (size_t)75 * DABGPU_NB_DATA_CARRIERS * 2 * sizeof(float);
+    const size_t iq_bytes = (size_t)g.frame_samples * 2 * sizeof(float);
+    const size_t fft_bytes = (size_t)(g.n_sym + 1) * g.n_fft * 2 * sizeof(float);
+    const size_t dq_bytes = (size_t)(g.n_sym - 1) * g.n_carriers * 2 * sizeof(float);
     float *d_iq, *d_small, *d_corr, *d_fft = nullptr, *d_dq = nullptr; int8_t* d_bits;
-    if ((st = dabgpu_scratch(c, 1, iq_bytes, (void**)&d_iq))) return st;
-    if ((st = dabgpu_scratch(c, 2, DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, 3, 4 * sizeof(float), (void**)&d_small))) return st;       // [0] net freq, [1] fine, [2] total phase
-    if ((st = dabgpu_scratch(c, 4, DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&d_corr))) return st;
-    if (h_fft && (st = dabgpu_scratch(c, 6, fft_bytes, (void**)&d_fft))) return st;
-    if (h_dqpsk && (st = dabgpu_scratch(c, 13, dq_bytes, (void**)&d_dq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_IQ, iq_bytes, (void**)&d_iq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)g.frame_bits, (void**)&d_bits))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, 4 * sizeof(float), (void**)&d_small))) return st;       // [0] net freq, [1] fine, [2] total phase
+    if ((st = dabgpu_scratch(c, SCR_HOST_CORR, (size_t)g.n_sym * 2 * sizeof(float), (void**)&d_corr))) return st;
+    if (h_fft && (st = dabgpu_scratch(c, SCR_HOST_FFT, fft_bytes, (void**)&d_fft))) return st;
+    if (h_dqpsk && (st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes, (void**)&d_dq))) return st;
     hipStream_t s = c->stream;
     const float h_small[2] = { freq_coarse + *h_freq_fine, *h_freq_fine };               // :672 net offset of this frame
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemcpyAsync(d_iq, h_iq, iq_bytes, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(d_small, h_small, sizeof(h_small), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_ofdm_demod_frames(c, d_iq, 1, d_small, d_bits, d_corr, d_fft, d_dq, 0, 0, s))) return st;
-    if ((st = dabgpu_ofdm_phase_update(c, d_corr, 1, beta, d_small + 2, d_small + 1, s))) return st;
-    CK(hipMemcpyAsync(h_bits, d_bits, DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(d_iq, h_iq, iq_bytes, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_small, h_small, sizeof(h_small), hipMemcpyHostToDevice, s));
+    st = (mode == 1) ? dabgpu_ofdm_demod_frames(c, d_iq, 1, d_small, d_bits, d_corr, d_fft, d_dq, 0, 0, s)
+                     : dabgpu_ofdm_demod_frames_mode(c, mode, d_iq, 1, d_small, d_bits, d_corr, d_fft, 0, s);
+    if (st || (st = dabgpu_ofdm_phase_update_mode(c, mode, d_corr, 1, beta, d_small + 2, d_small + 1, s))) return st;
+    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)g.frame_bits, hipMemcpyDeviceToHost, s));
     float back[2];
-    CK(hipMemcpyAsync(back, d_small + 1, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (h_fft) CK(hipMemcpyAsync(h_fft, d_fft, fft_bytes, hipMemcpyDeviceToHost, s));
-    if (h_dqpsk) CK(hipMemcpyAsync(h_dqpsk, d_dq, dq_bytes, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-#undef CK
+    DABGPU_CK(hipMemcpyAsync(back, d_small + 1, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (h_fft) DABGPU_CK(hipMemcpyAsync(h_fft, d_fft, fft_bytes, hipMemcpyDeviceToHost, s));
+    if (h_dqpsk) DABGPU_CK(hipMemcpyAsync(h_dqpsk, d_dq, dq_bytes, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     *h_freq_fine = back[0];
     if (h_total_phase) *h_total_phase = back[1];
     return DABGPU_OK;
 }
 
+int dabgpu_ofdm_demod_stream_frame_sync(dabgpu_ctx* c, const float* h_iq, float freq_coarse, float* h_freq_fine, float beta,
+                                        int8_t* h_bits, float* h_total_phase, float* h_fft, float* h_dqpsk) {
+    return stream_frame_sync(c, 1, h_iq, freq_coarse, h_freq_fine, beta, h_bits, h_total_phase, h_fft, h_dqpsk, "ofdm_demod_stream_frame_sync");
+}
+
+int dabgpu_ofdm_demod_stream_frame_sync_mode(dabgpu_ctx* c, int mode, const float* h_iq, float freq_coarse, float* h_freq_fine, float beta,
+                                             int8_t* h_bits, float* h_total_phase, float* h_fft) {
+    return stream_frame_sync(c, mode, h_iq, freq_coarse, h_freq_fine, beta, h_bits, h_total_phase, h_fft, nullptr, "ofdm_demod_stream_frame_sync_mode");
+}
+
 // ---- sync ----
+static int ofdm_sync(dabgpu_ctx* c, int mode, const float* d_prs_syms, size_t n_streams, size_t stride_samples, const dabgpu_sync_cfg* cfg,
+                     dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, void* stream, const char* who) {
+    if (!c || !d_prs_syms || !cfg || !d_states) { dabgpu_set_error("%s: null argument", who); return DABGPU_ERR_INVALID_ARG; }
+    if (n_streams == 0) return DABGPU_OK;
+    if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("%s: n_streams too large", who); return DABGPU_ERR_INVALID_ARG; }
+    DABGPU_BIND(c);
+    const dabgpu_mode_tables* t;
+    int st = dabgpu_mode_tables_of(c, mode, &t, who);
+    if (st) return st;
+    return dabgpu_check_hip(dabgpu_launch_sync(d_prs_syms, stride_samples, (int)n_streams, cfg, d_states, d_impulse, d_freq,
+                                               c->d_tw, t->prs, t->prs_time_ref, nullptr, mode, (hipStream_t)stream), "ofdm_sync_kernel launch");
+}
+
 int dabgpu_ofdm_sync(dabgpu_ctx* c, const float* d_prs_syms, size_t n_streams, size_t stride_samples, const dabgpu_sync_cfg* cfg,
                      dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, void* stream) {
-    if (!c || !d_prs_syms || !cfg || !d_states) { dabgpu_set_error("ofdm_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_streams == 0) return DABGPU_OK;
-    if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_sync: n_streams too large"); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(c);
-    return dabgpu_check_hip(dabgpu_launch_sync(d_prs_syms, stride_samples, (int)n_streams, cfg, d_states, d_impulse, d_freq,
-                                               c->d_tw, c->d_prs, c->d_prs_time_ref, nullptr, 1, (hipStream_t)stream), "ofdm_sync_kernel launch");
+    return ofdm_sync(c, 1, d_prs_syms, n_streams, stride_samples, cfg, d_states, d_impulse, d_freq, stream, "ofdm_sync");
 }
 
 int dabgpu_ofdm_sync_mode(dabgpu_ctx* c, int mode, const float* d_prs_syms, size_t n_streams, size_t stride_samples, const dabgpu_sync_cfg* cfg,
                           dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, void* stream) {
-    if (!c || !d_prs_syms || !cfg || !d_states) { dabgpu_set_error("ofdm_sync_mode: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_streams == 0) return DABGPU_OK;
-    if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_sync_mode: n_streams too large"); return DABGPU_ERR_INVALID_ARG; }
+    return ofdm_sync(c, mode, d_prs_syms, n_streams, stride_samples, cfg, d_states, d_impulse, d_freq, stream, "ofdm_sync_mode");
+}
+
+static int sync_host_sync(dabgpu_ctx* c, int mode, const float* h_prs_sym, const dabgpu_sync_cfg* cfg, dabgpu_sync_state* h_state,
+                          float* h_impulse, float* h_freq, const char* who) {
+    dabgpu::ModeGeom g;
+    if (!c || !h_prs_sym || !cfg || !h_state) { dabgpu_set_error("%s: null argument", who); return DABGPU_ERR_INVALID_ARG; }
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("%s: invalid transmission mode %d", who, mode); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(c);
-    const float *d_prs, *d_ref;
-    int st = dabgpu_mode_sync_tables(c, mode, &d_prs, &d_ref);
-    if (st) return st;
-    return dabgpu_check_hip(dabgpu_launch_sync(d_prs_syms, stride_samples, (int)n_streams, cfg, d_states, d_impulse, d_freq,
-                                               c->d_tw, d_prs, d_ref, nullptr, mode, (hipStream_t)stream), "ofdm_sync_kernel launch");
+    DABGPU_HOST_LOCK(c);
+    int st;
+    const size_t N = (size_t)g.n_fft;
+    float *d_sym, *d_imp, *d_frq; dabgpu_sync_state* d_st;
+    if ((st = dabgpu_scratch(c, SCR_SYNC_SYM, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_sym))) return st;
+    if ((st = dabgpu_scratch(c, SCR_SYNC_STATE, sizeof(dabgpu_sync_state), (void**)&d_st))) return st;
+    if ((st = dabgpu_scratch(c, SCR_SYNC_RESP, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_imp))) return st;
+    d_frq = d_imp + DABGPU_NB_FFT;
+    hipStream_t s = c->stream;
+    DABGPU_CK(hipMemcpyAsync(d_sym, h_prs_sym, sizeof(float) * 2 * N, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_st, h_state, sizeof(dabgpu_sync_state), hipMemcpyHostToDevice, s));
+    if ((st = ofdm_sync(c, mode, d_sym, 1, N, cfg, d_st, d_imp, d_frq, s, mode == 1 ? "ofdm_sync" : "ofdm_sync_mode"))) return st;
+    DABGPU_CK(hipMemcpyAsync(h_state, d_st, sizeof(dabgpu_sync_state), hipMemcpyDeviceToHost, s));
+    if (h_impulse) DABGPU_CK(hipMemcpyAsync(h_impulse, d_imp, sizeof(float) * N, hipMemcpyDeviceToHost, s));
+    if (h_freq) DABGPU_CK(hipMemcpyAsync(h_freq, d_frq, sizeof(float) * N, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
+    return DABGPU_OK;
 }
 
 int dabgpu_ofdm_sync_host_sync(dabgpu_ctx* c, const float* h_prs_sym, const dabgpu_sync_cfg* cfg, dabgpu_sync_state* h_state,
                                float* h_impulse, float* h_freq) {
-    if (!c || !h_prs_sym || !cfg || !h_state) { dabgpu_set_error("ofdm_sync_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st;
-    float *d_sym, *d_imp, *d_frq; dabgpu_sync_state* d_st;
-    if ((st = dabgpu_scratch(c, 7, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_sym))) return st;
-    if ((st = dabgpu_scratch(c, 8, sizeof(dabgpu_sync_state), (void**)&d_st))) return st;
-    if ((st = dabgpu_scratch(c, 9, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_imp))) return st;
-    d_frq = d_imp + DABGPU_NB_FFT;
-    hipStream_t s = c->stream;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemcpyAsync(d_sym, h_prs_sym, sizeof(float) * 2 * DABGPU_NB_FFT, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(d_st, h_state, sizeof(dabgpu_sync_state), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_ofdm_sync(c, d_sym, 1, DABGPU_NB_FFT, cfg, d_st, d_imp, d_frq, s))) return st;
-    CK(hipMemcpyAsync(h_state, d_st, sizeof(dabgpu_sync_state), hipMemcpyDeviceToHost, s));
-    if (h_impulse) CK(hipMemcpyAsync(h_impulse, d_imp, sizeof(float) * DABGPU_NB_FFT, hipMemcpyDeviceToHost, s));
-    if (h_freq) CK(hipMemcpyAsync(h_freq, d_frq, sizeof(float) * DABGPU_NB_FFT, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-#undef CK
-    return DABGPU_OK;
+    return sync_host_sync(c, 1, h_prs_sym, cfg, h_state, h_impulse, h_freq, "ofdm_sync_host_sync");
+}
+
+int dabgpu_ofdm_sync_host_sync_mode(dabgpu_ctx* c, int mode, const float* h_prs_sym, const dabgpu_sync_cfg* cfg, dabgpu_sync_state* h_state,
+                                    float* h_impulse, float* h_freq) {
+    return sync_host_sync(c, mode, h_prs_sym, cfg, h_state, h_impulse, h_freq, "ofdm_sync_host_sync_mode");
 }
 
 }  // extern "C"
 
-// PRS spectrum and coarse-sync reference of modes II-IV on the device, built on first use (ofdm_demodulator.cpp:128-140)
-int dabgpu_mode_sync_tables(dabgpu_ctx* c, int mode, const float** d_prs, const float** d_prs_time_ref) {
-    int geom[9];
-    if (dabgpu_get_ofdm_params(mode, geom)) return DABGPU_ERR_INVALID_ARG;
-    if (mode == 1) { *d_prs = c->d_prs; *d_prs_time_ref = c->d_prs_time_ref; return DABGPU_OK; }
-    if (!c->d_mode_prs[mode]) {
-        const size_t bytes = sizeof(float) * 2 * (size_t)geom[3];
-        std::vector<float> prs(2 * (size_t)geom[3]);
-        int st = dabgpu_get_prs_fft_ref(mode, prs.data());
-        if (st) return st;
-        DABGPU_BIND(c);
-        float *dp = nullptr, *dr = nullptr;
-        if ((st = dabgpu_check_hip(hipMalloc(&dp, bytes), "hipMalloc(mode prs)"))) return st;
-        if ((st = dabgpu_check_hip(hipMalloc(&dr, bytes), "hipMalloc(mode prs ref)"))) { (void)hipFree(dp); return st; }
-        if ((st = dabgpu_check_hip(hipMemcpy(dp, prs.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(mode prs)")) ||
-            (st = dabgpu_check_hip(dabgpu_launch_sync_init(dp, c->d_tw, dr, geom[3], c->stream), "sync_init_kernel launch")) ||
-            (st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize"))) { (void)hipFree(dp); (void)hipFree(dr); return st; }
-        c->d_mode_prs[mode] = dp; c->d_mode_prs_time_ref[mode] = dr;
-    }
-    *d_prs = c->d_mode_prs[mode]; *d_prs_time_ref = c->d_mode_prs_time_ref[mode];
+int dabgpu_mode_tables_of(dabgpu_ctx* c, int mode, const dabgpu_mode_tables** out, const char* who) {
+    dabgpu::ModeGeom g;
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("%s: invalid transmission mode %d", who, mode); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu_mode_tables* t = &c->modes[mode];
+    int st;
+    if (!t->prs && (st = build_mode_tables(c, mode, nullptr, nullptr, t))) return st;     // (modes II-IV: the built-in tables)
+    *out = t;
     return DABGPU_OK;
 }
 
@@ -595,8 +590,7 @@ int dabgpu_mode_sync_tables(dabgpu_ctx* c, int mode, const float** d_prs, const 
 //   * growth needed while `user` is capturing -> DABGPU_ERR_INVALID_ARG (hipMalloc would invalidate the capture with an obscure error);
 //   * once a call of this context has run under capture, a slot that grows later (a larger eager call) PARKS its old buffer until
 //     dabgpu_destroy instead of freeing it: a replay of the earlier graph then still reads and writes memory the context owns.
-int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out, hipStream_t user, bool user_given) {
-    if ((size_t)slot >= c->scratch.size()) { c->scratch.resize(slot + 1, nullptr); c->scratch_bytes.resize(slot + 1, 0); }
+static int scratch_any(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out, hipStream_t user, bool user_given) {
     bool capturing = false;
     if (user_given) {
         if (!tl_capture.valid || tl_capture.stream != user) {
@@ -609,7 +603,7 @@ int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out, hipStream_
     }
     if (c->scratch_bytes[slot] < bytes) {
         if (capturing) {
-            dabgpu_set_error("this call needs more device scratch than the context holds (slot %d: %zu -> %zu bytes): run it once with these shapes before capturing", slot,
+            dabgpu_set_error("this call needs more device scratch than the context holds (slot %d: %zu -> %zu bytes): run it once with these shapes before capturing", (int)slot,
                              c->scratch_bytes[slot], bytes);
             return DABGPU_ERR_INVALID_ARG;
         }
@@ -625,5 +619,5 @@ int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out, hipStream_
     *out = c->scratch[slot];
     return DABGPU_OK;
 }
-int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out) { return dabgpu_scratch(c, slot, bytes, out, nullptr, false); }
-int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out, hipStream_t user) { return dabgpu_scratch(c, slot, bytes, out, user, true); }
+int dabgpu_scratch(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out) { return scratch_any(c, slot, bytes, out, nullptr, false); }
+int dabgpu_scratch(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out, hipStream_t user) { return scratch_any(c, slot, bytes, out, user, true); }

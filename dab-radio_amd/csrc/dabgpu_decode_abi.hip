@@ -29,18 +29,16 @@ static int ensure_vit_tables(dabgpu_ctx* c) {
     return dabgpu_check_hip(hipMemcpy(c->d_vit_tables, &T, sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(vit tables)");
 }
 
-// slot_off: the FIC entry points keep their device scratch in slots of their own (+ FIC_SLOTS), so that one context can decode the
-// FIC and the MSC of a batch concurrently on two streams
-static const int FIC_SLOTS = 20;
+// fic: the FIC entry points keep their device scratch in slots of their own (scratch_fic)
 static int run_viterbi(dabgpu_ctx* c, const dabgpu_cw_desc* d_descs, size_t n, uint32_t max_steps, uint32_t max_out_bytes,
-                       int tie_rule, dabgpu_codeword_result* d_results, hipStream_t s, int slot_off = 0, size_t n_first = 0,
+                       int tie_rule, dabgpu_codeword_result* d_results, hipStream_t s, bool fic = false, size_t n_first = 0,
                        dabgpu_codeword_result* d_results_rest = nullptr) {
     int st0 = ensure_vit_tables(c);
     if (st0) return st0;
     const int n_waves = (int)std::min<size_t>(n, (size_t)device_waves(c));
     const size_t words = ((size_t)max_steps + 63) & ~(size_t)63;
     uint64_t* d_scratch = nullptr;
-    int st = dabgpu_scratch(c, 11 + slot_off, (size_t)n_waves * words * sizeof(uint64_t), (void**)&d_scratch, s);
+    int st = dabgpu_scratch(c, scratch_fic<SCR_VIT_WAVE>(fic), (size_t)n_waves * words * sizeof(uint64_t), (void**)&d_scratch, s);
     if (st) return st;
     return dabgpu_check_hip(dabgpu_launch_viterbi(d_descs, (int)n, d_scratch, words, n_waves, (int)max_out_bytes, d_results,
                                                   tie_rule ? 1 : 0, c->d_vit_tables, s, (int)n_first, d_results_rest), "viterbi_kernel launch");
@@ -78,11 +76,11 @@ static size_t lanes_max_rows() {
 // sym_rows / dec_rows: rows of 64 dwords (kept soft bits, 4 per lane and row) and of 128 dwords (decisions, one row per step)
 static int run_viterbi_lanes(dabgpu_ctx* c, const dabgpu_cw_desc* d_descs, const dabgpu_vit_group* d_groups, size_t n_groups,
                              size_t sym_rows, size_t dec_rows, uint32_t max_in_rows, int tie_rule, int ring4, const uint2* d_sched,
-                             int octet, dabgpu_codeword_result* d_results, hipStream_t s, int slot_off = 0, uint32_t groups_per_sub = 0) {
+                             int octet, dabgpu_codeword_result* d_results, hipStream_t s, bool fic = false, uint32_t groups_per_sub = 0) {
     int st;
     uint32_t *d_sym = nullptr, *d_dec = nullptr;
-    if ((st = dabgpu_scratch(c, 18 + slot_off, sym_rows * 64 * sizeof(uint32_t), (void**)&d_sym, s))) return st;
-    if ((st = dabgpu_scratch(c, 19 + slot_off, dec_rows * 128 * sizeof(uint32_t), (void**)&d_dec, s))) return st;
+    if ((st = dabgpu_scratch(c, scratch_fic<SCR_VIT_SYM>(fic), sym_rows * 64 * sizeof(uint32_t), (void**)&d_sym, s))) return st;
+    if ((st = dabgpu_scratch(c, scratch_fic<SCR_VIT_DEC>(fic), dec_rows * 128 * sizeof(uint32_t), (void**)&d_dec, s))) return st;
     return dabgpu_check_hip(dabgpu_launch_viterbi_lanes(d_groups, n_groups, max_in_rows, d_descs, d_sym, d_dec, d_results,
                                                         tie_rule ? 1 : 0, ring4, c->d_vit_tables, d_sched, octet, device_waves(c) / 32, groups_per_sub, s),
                             "vit_lanes_kernel launch");
@@ -91,21 +89,21 @@ static int run_viterbi_lanes(dabgpu_ctx* c, const dabgpu_cw_desc* d_descs, const
 // one puncturing schedule for a whole batch (FIC, uniform codeword batches): groups of 64 consecutive codewords, in bounded slices
 static int run_lanes_uniform(dabgpu_ctx* c, const dabgpu_cw_desc* d_descs, size_t n, uint32_t n_steps, const uint32_t* seg_pi,
                              const uint32_t* seg_steps, int tie_rule, int ring4, int octet, dabgpu_codeword_result* d_results, hipStream_t s,
-                             int slot_off) {
+                             bool fic) {
     int st = ensure_vit_tables(c);
     if (st) return st;
     const uint32_t dec_rows = dabgpu_vit_alloc_steps(n_steps), in_rows = dabgpu_vit_in_rows(dabgpu_vit_in_bytes(seg_pi, seg_steps));
     uint2* d_sched = nullptr;
-    if ((st = dabgpu_scratch(c, 25 + slot_off, (size_t)dec_rows * sizeof(uint2), (void**)&d_sched, s))) return st;
+    if ((st = dabgpu_scratch(c, scratch_fic<SCR_VIT_SCHED>(fic), (size_t)dec_rows * sizeof(uint2), (void**)&d_sched, s))) return st;
     if ((st = dabgpu_check_hip(dabgpu_launch_vit_sched_uniform(d_sched, dec_rows, seg_pi, seg_steps, c->d_vit_tables, s), "vit_sched launch"))) return st;
     const size_t slice_groups = std::max<size_t>(1, lanes_max_rows() / dec_rows);
     for (size_t cw0 = 0; cw0 < n; cw0 += slice_groups * 64) {
         const size_t n_cw = std::min(n - cw0, slice_groups * 64), n_groups = (n_cw + 63) / 64;
         dabgpu_vit_group* d_groups = nullptr;
-        if ((st = dabgpu_scratch(c, 17 + slot_off, n_groups * sizeof(dabgpu_vit_group), (void**)&d_groups, s))) return st;
+        if ((st = dabgpu_scratch(c, scratch_fic<SCR_VIT_GROUPS>(fic), n_groups * sizeof(dabgpu_vit_group), (void**)&d_groups, s))) return st;
         if ((st = dabgpu_check_hip(dabgpu_launch_vit_groups_uniform(d_groups, n_cw, n_steps, seg_pi, seg_steps, s), "vit_groups launch"))) return st;
         if ((st = run_viterbi_lanes(c, d_descs + cw0, d_groups, n_groups, n_groups * in_rows, n_groups * dec_rows, in_rows, tie_rule, ring4,
-                                    d_sched, octet, d_results + cw0, s, slot_off))) return st;
+                                    d_sched, octet, d_results + cw0, s, fic))) return st;
     }
     return DABGPU_OK;
 }
@@ -123,7 +121,7 @@ extern "C" int dabgpu_viterbi_decode_batch(dabgpu_ctx* c, const dabgpu_codeword*
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
     dabgpu_cw_desc* d_descs = nullptr;
-    int st = dabgpu_scratch(c, 10, n * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
+    int st = dabgpu_scratch(c, SCR_CW_DESCS, n * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
     if (st) return st;
     if ((st = dabgpu_stage_h2d(c, d_descs, h_cw, n * sizeof(dabgpu_cw_desc), s))) return st;
     // (h_cw is consumed when this returns, the caller may reuse it: small tables go through the pinned staging ring, large ones through
@@ -139,7 +137,7 @@ extern "C" int dabgpu_viterbi_decode_batch(dabgpu_ctx* c, const dabgpu_codeword*
     const int map = uniform ? choose_mapping(c, n, (n + 63) / 64, (double)n * max_steps, (double)((n + 63) / 64) * max_steps, (double)max_steps, false)
                             : DABGPU_VIT_MAP_WAVE;
     if (map != DABGPU_VIT_MAP_WAVE)
-        return run_lanes_uniform(c, d_descs, n, max_steps, h_cw[0].seg_pi, h_cw[0].seg_steps, tie_rule, 0, map == DABGPU_VIT_MAP_OCTET, d_results, s, 0);
+        return run_lanes_uniform(c, d_descs, n, max_steps, h_cw[0].seg_pi, h_cw[0].seg_steps, tie_rule, 0, map == DABGPU_VIT_MAP_OCTET, d_results, s, false);
     return run_viterbi(c, d_descs, n, max_steps, max_steps > 6 ? (max_steps - 6) / 8 : 0, tie_rule, d_results, s);
 }
 
@@ -152,7 +150,7 @@ static int fic_decode_any(dabgpu_ctx* c, const int8_t* d_bits, size_t n_frames, 
     hipStream_t s = (hipStream_t)stream;
     const size_t n = n_frames * 4;
     dabgpu_cw_desc* d_descs = nullptr;
-    int st = dabgpu_scratch(c, 10 + FIC_SLOTS, n * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
+    int st = dabgpu_scratch(c, scratch_fic<SCR_CW_DESCS>(true), n * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
     if (st) return st;
     st = dabgpu_check_hip(dabgpu_launch_fic_build(d_descs, d_bits, n_frames, frame_stride, d_fib_bytes, d_slots, s), "fic_build_descs launch");
     if (st) return st;
@@ -162,9 +160,9 @@ static int fic_decode_any(dabgpu_ctx* c, const int8_t* d_bits, size_t n_frames, 
     if (map != DABGPU_VIT_MAP_WAVE) {
         // one schedule for every FIB group
         const uint32_t seg_pi[4] = {16, 15, 0, 0}, seg_steps[4] = {32 * 21, 32 * 3, 0, 0};
-        return run_lanes_uniform(c, d_descs, n, 774, seg_pi, seg_steps, tie_rule, fic_direct, map == DABGPU_VIT_MAP_OCTET, d_results, s, FIC_SLOTS);
+        return run_lanes_uniform(c, d_descs, n, 774, seg_pi, seg_steps, tie_rule, fic_direct, map == DABGPU_VIT_MAP_OCTET, d_results, s, true);
     }
-    return run_viterbi(c, d_descs, n, 774, 96, tie_rule, d_results, s, FIC_SLOTS);
+    return run_viterbi(c, d_descs, n, 774, 96, tie_rule, d_results, s, true);
 }
 
 extern "C" int dabgpu_fic_decode_frames(dabgpu_ctx* c, const int8_t* d_bits, size_t n_frames, size_t frame_stride,
@@ -188,9 +186,7 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
                           size_t out_ens_stride, dabgpu_codeword_result* d_results, int tie_rule, void* stream,
                           int bits_layout = DABGPU_BITS_NATURAL, const fic_request* fic = nullptr) {
     if (!c || !d_hist || !h_sub || !d_out || !d_results) { dabgpu_set_error("msc_decode_frames: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) {
-        dabgpu_set_error("msc_decode_frames: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG;
-    }
+    if (dabgpu_check_bits_layout("msc_decode_frames", bits_layout)) return DABGPU_ERR_INVALID_ARG;
     const int classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
     if (n_ens == 0 || n_sub == 0) return DABGPU_OK;
     if (hist_frames < 5 || newest_frame_slot < 0 || newest_frame_slot >= hist_frames || n_sub < 0) {
@@ -211,9 +207,9 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
     const int8_t* fic_bits = d_slots ? d_hist : d_hist + (size_t)newest_frame_slot * DABGPU_NB_FRAME_BITS;
     dabgpu_cw_desc* d_descs = nullptr;
     dabgpu_msc_plan* d_plans = nullptr;
-    int st = dabgpu_scratch(c, 10, (n + n_fic) * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
+    int st = dabgpu_scratch(c, SCR_CW_DESCS, (n + n_fic) * sizeof(dabgpu_cw_desc), (void**)&d_descs, s);
     if (st) return st;
-    if ((st = dabgpu_scratch(c, 12, plans.size() * sizeof(dabgpu_msc_plan), (void**)&d_plans, s))) return st;
+    if ((st = dabgpu_scratch(c, SCR_MSC_PLANS, plans.size() * sizeof(dabgpu_msc_plan), (void**)&d_plans, s))) return st;
     // (the plans are staged and the descriptors built once the mapping of every sub-channel is known, below)
     // Which sub-channels go to the lane-per-codeword kernel?  The k longest can be left to viterbi_kernel (one wavefront per
     // codeword) and the rest given to vit_lanes_kernel in the same call; AUTO only compares the two pure choices k = 0 and
@@ -283,14 +279,14 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
         const size_t max_gq = std::max<size_t>(1, lanes_max_rows() / dec_rows_per_gq);
         const size_t ens_per_slice = max_gq * 16;                       // 16 ensembles x 4 CIFs = one group per sub-channel
         uint64_t* d_lane_subs = nullptr;
-        if ((st = dabgpu_scratch(c, 24, lane_subs.size() * sizeof(uint64_t), (void**)&d_lane_subs, s))) return st;
+        if ((st = dabgpu_scratch(c, SCR_LANE_SUBS, lane_subs.size() * sizeof(uint64_t), (void**)&d_lane_subs, s))) return st;
         if ((st = dabgpu_stage_h2d_cached(c, 1, d_lane_subs, lane_subs.data(), lane_subs.size() * sizeof(uint64_t), s))) return st;
         // the schedule table of every lane-mapped sub-channel, once per call
         const uint32_t sched_stride = dabgpu_vit_alloc_steps(lane_max_steps);
         const uint32_t fic_pi[4] = {16, 15, 0, 0}, fic_steps[4] = {32 * 21, 32 * 3, 0, 0};
         const uint32_t fic_dec_rows = dabgpu_vit_alloc_steps(774), fic_in_rows = dabgpu_vit_in_rows(dabgpu_vit_in_bytes(fic_pi, fic_steps));
         uint2* d_sched = nullptr;
-        if ((st = dabgpu_scratch(c, 25, ((size_t)n_lane * sched_stride + (fic_inside ? fic_dec_rows : 0)) * sizeof(uint2), (void**)&d_sched, s))) return st;
+        if ((st = dabgpu_scratch(c, SCR_VIT_SCHED, ((size_t)n_lane * sched_stride + (fic_inside ? fic_dec_rows : 0)) * sizeof(uint2), (void**)&d_sched, s))) return st;
         if ((st = dabgpu_check_hip(dabgpu_launch_vit_sched_msc(d_sched, sched_stride, d_plans, d_lane_subs, n_lane, c->d_vit_tables, s), "vit_sched launch"))) return st;
         for (size_t e0 = 0; e0 < n_ens; e0 += ens_per_slice) {
             const size_t ne = std::min(n_ens - e0, ens_per_slice);
@@ -298,7 +294,7 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
             const size_t n_groups = (size_t)n_lane * gps;
             const size_t n_fic_groups = fic_inside ? (n_fic + 63) / 64 : 0;
             dabgpu_vit_group* d_groups = nullptr;
-            if ((st = dabgpu_scratch(c, 17, (n_groups + n_fic_groups) * sizeof(dabgpu_vit_group), (void**)&d_groups, s))) return st;
+            if ((st = dabgpu_scratch(c, SCR_VIT_GROUPS, (n_groups + n_fic_groups) * sizeof(dabgpu_vit_group), (void**)&d_groups, s))) return st;
             if ((st = dabgpu_check_hip(dabgpu_launch_vit_groups_msc(d_groups, d_plans, d_lane_subs, n_lane, n_sub, ne, gps, sched_stride, s), "vit_groups launch"))) return st;
             const size_t cw0 = e0 * 4 * (size_t)n_sub;
             // the staged gathers read the ring rows in aligned 16-byte chunks (natural order) / aligned 64-byte lines (class order)
@@ -308,7 +304,7 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
                                       : ((((uintptr_t)d_hist % 16 == 0) && (ens_stride % 16 == 0)) ? 1 : 0);
             if (!fic_inside) {
                 if ((st = run_viterbi_lanes(c, d_descs + cw0, d_groups, n_groups, sym_rows_per_gq * gps, dec_rows_per_gq * gps, lane_max_in_rows,
-                                            tie_rule, ring4, d_sched, octet, d_results + cw0, s, 0, gps))) return st;
+                                            tie_rule, ring4, d_sched, octet, d_results + cw0, s, false, gps))) return st;
                 continue;
             }
             // one slice (e0 = 0): the FIB groups of the newest frames behind the MSC's groups -- descriptors n .., schedule, symbol and
@@ -324,8 +320,8 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
             base.res_delta = (int64_t)(reinterpret_cast<const char*>(fic->d_results) - reinterpret_cast<const char*>(d_results + n));
             if ((st = dabgpu_check_hip(dabgpu_launch_vit_groups_uniform_at(d_groups + n_groups, n_fic, 774, fic_pi, fic_steps, base, s), "vit_groups launch"))) return st;
             uint32_t *d_sym = nullptr, *d_dec = nullptr;
-            if ((st = dabgpu_scratch(c, 18, (sym_rows + n_fic_groups * fic_in_rows) * 64 * sizeof(uint32_t), (void**)&d_sym, s))) return st;
-            if ((st = dabgpu_scratch(c, 19, (dec_rows + n_fic_groups * fic_dec_rows) * 128 * sizeof(uint32_t), (void**)&d_dec, s))) return st;
+            if ((st = dabgpu_scratch(c, SCR_VIT_SYM, (sym_rows + n_fic_groups * fic_in_rows) * 64 * sizeof(uint32_t), (void**)&d_sym, s))) return st;
+            if ((st = dabgpu_scratch(c, SCR_VIT_DEC, (dec_rows + n_fic_groups * fic_dec_rows) * 128 * sizeof(uint32_t), (void**)&d_dec, s))) return st;
             // FIB groups are contiguous runs of 2304 soft bits; with 16-byte aligned frames the staged gather applies
             const int fic_kind = (((uintptr_t)fic_bits % 16 == 0) && (ens_stride % 16 == 0)) ? 3 : 0;
             if ((st = dabgpu_check_hip(dabgpu_launch_vit_prep(ring4, d_groups, n_groups, lane_max_in_rows, d_descs, d_sym, gps, s), "vit_prep launch"))) return st;
@@ -336,7 +332,7 @@ static int msc_decode_any(dabgpu_ctx* c, const int8_t* d_hist, size_t n_ens, siz
         if (k_wave == 0) return DABGPU_OK;
     }
     if (fic_with_wave)
-        return run_viterbi(c, d_descs, n + n_fic, std::max(max_steps, 774u), std::max(max_out, 96u), tie_rule, d_results, s, 0, n, fic->d_results);
+        return run_viterbi(c, d_descs, n + n_fic, std::max(max_steps, 774u), std::max(max_out, 96u), tie_rule, d_results, s, false, n, fic->d_results);
     return run_viterbi(c, d_descs, n, max_steps, max_out, tie_rule, d_results, s);
 }
 
@@ -424,24 +420,22 @@ static int decode_one_sync(dabgpu_ctx* c, dabgpu_cw_desc D, const int8_t* h_src,
     DABGPU_BIND(c);
     int st;
     int8_t* d_src = nullptr; uint8_t* d_out; dabgpu_codeword_result* d_res; dabgpu_cw_desc* d_desc;
-    if (h_src && (st = dabgpu_scratch(c, 14, n_src, (void**)&d_src))) return st;
+    if (h_src && (st = dabgpu_scratch(c, SCR_CW_SRC, n_src, (void**)&d_src))) return st;
     // (the kernel writes (n_steps - 6) / 8 bytes whatever part of them the caller wants back)
     const size_t kernel_out = D.n_steps > 6 ? (size_t)(D.n_steps - 6) / 8 : 0;
-    if ((st = dabgpu_scratch(c, 15, std::max<size_t>(std::max(n_out, kernel_out), 16), (void**)&d_out))) return st;
-    if ((st = dabgpu_scratch(c, 16, sizeof(dabgpu_codeword_result), (void**)&d_res))) return st;
-    if ((st = dabgpu_scratch(c, 10, sizeof(dabgpu_cw_desc), (void**)&d_desc))) return st;
+    if ((st = dabgpu_scratch(c, SCR_CW_OUT, std::max<size_t>(std::max(n_out, kernel_out), 16), (void**)&d_out))) return st;
+    if ((st = dabgpu_scratch(c, SCR_CW_RESULT, sizeof(dabgpu_codeword_result), (void**)&d_res))) return st;
+    if ((st = dabgpu_scratch(c, SCR_CW_DESCS, sizeof(dabgpu_cw_desc), (void**)&d_desc))) return st;
     hipStream_t s = c->stream;
     if (h_src) D.d_src = (uint64_t)(uintptr_t)d_src;
     D.d_out = (uint64_t)(uintptr_t)d_out;
     if ((st = dabgpu_host_validate_codeword(D, 0))) return st;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    if (h_src) CK(hipMemcpyAsync(d_src, h_src, n_src, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(d_desc, &D, sizeof(D), hipMemcpyHostToDevice, s));
+    if (h_src) DABGPU_CK(hipMemcpyAsync(d_src, h_src, n_src, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_desc, &D, sizeof(D), hipMemcpyHostToDevice, s));
     if ((st = run_viterbi(c, d_desc, 1, D.n_steps, D.n_steps > 6 ? (D.n_steps - 6) / 8 : 0, tie_rule, d_res, s))) return st;
-    if (n_out) CK(hipMemcpyAsync(h_out, d_out, n_out, hipMemcpyDeviceToHost, s));
-    CK(hipMemcpyAsync(h_res, d_res, sizeof(*h_res), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-#undef CK
+    if (n_out) DABGPU_CK(hipMemcpyAsync(h_out, d_out, n_out, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(h_res, d_res, sizeof(*h_res), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     return DABGPU_OK;
 }
 
@@ -762,7 +756,6 @@ static int session_decode(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_se
     int st;
     sl.fic = decode_fic != 0;
     sl.subs = s->subs; sl.sub_off = s->sub_off; sl.sub_n = s->sub_n; sl.cif_out = s->cif_out;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
     if ((st = slot_block(s, sl))) return st;
     if (decode_fic && !n_sub) {
         if ((st = dabgpu_fic_decode_frames(c, d_frame, 1, DABGPU_NB_FRAME_BITS, s->d_fib, s->d_fres, tie_rule, q))) return st;
@@ -778,8 +771,7 @@ static int session_decode(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_se
     }
     // one copy: the whole block with sub-channels, its FIC head without
     if (n_sub || decode_fic)
-        CK(hipMemcpyAsync(sl.h_block, s->d_block, n_sub ? session_block_bytes((size_t)n_sub, s->cif_out) : session_block_bytes(0, 0), hipMemcpyDeviceToHost, q));
-#undef CK
+        DABGPU_CK(hipMemcpyAsync(sl.h_block, s->d_block, n_sub ? session_block_bytes((size_t)n_sub, s->cif_out) : session_block_bytes(0, 0), hipMemcpyDeviceToHost, q));
     return DABGPU_OK;
 }
 

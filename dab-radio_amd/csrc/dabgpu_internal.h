@@ -9,28 +9,55 @@
 #include "dabgpu.h"
 #include "dabgpu_host_logic.h"
 
+// device tables of one transmission mode, one allocation (starting at prs)
+struct dabgpu_mode_tables {
+    float* prs;                      // PRS spectrum, n_fft complex
+    float* prs_time_ref;             // conj(IFFT(relative_phase(PRS))), coarse-sync reference
+    int* mapper;                     // carrier mapper: soft bit n sits on carrier mapper[n]
+    int* inv_map;                    // its inverse: carrier c carries soft bit inv_map[c]
+    uint16_t* inv_map16;             // the same as uint16_t (the mode I demodulator and transmitter read it)
+};
+
+// Device scratch slots of a context (dabgpu_scratch), numbered in this order: one grow-only buffer each (a captured graph holds their
+// addresses).  Entry points that never run inside one another share slots.
+enum dabgpu_scratch_slot : int {
+    SCR_DEMOD_CORR,            // 0: cyclic-prefix correlations the caller of a mode I demodulation did not ask for
+    // 1-6: single-frame host forms (*_host_sync, *_stream_frame_sync): IQ in, soft bits out, frequency words (or [net, fine, total phase]),
+    // correlations, total phases, FFT view; the transmitter's host form: IQ out, payload in BITS, the caller's PRS in FFT
+    SCR_HOST_IQ, SCR_HOST_BITS, SCR_HOST_FREQ, SCR_HOST_CORR, SCR_HOST_PHASE, SCR_HOST_FFT,
+    SCR_SYNC_SYM, SCR_SYNC_STATE, SCR_SYNC_RESP,     // 7-9: ofdm_sync_host_sync: PRS symbol, record, responses
+    SCR_CW_DESCS, SCR_VIT_WAVE, SCR_MSC_PLANS,       // 10-12: codeword descriptors, wave Viterbi state, MSC plans
+    SCR_HOST_DQPSK,                                  // 13: DQPSK view of the single-frame host form
+    SCR_CW_SRC, SCR_CW_OUT, SCR_CW_RESULT,           // 14-16: one codeword from host memory
+    SCR_VIT_GROUPS, SCR_VIT_SYM, SCR_VIT_DEC,        // 17-19: lane / octet Viterbi: groups, kept soft bits, decisions
+    SCR_CONVERT_IN, SCR_CONVERT_OUT, SCR_RAW_IQ,     // 20-22: host-buffer format conversion; ofdm_demod_frames_raw's converted block
+    SCR_MODE_CORR, SCR_TUNE_TAIL = SCR_MODE_CORR,    // 23, shared: ofdm_demod_frames_mode's unwanted correlations, ofdm_tune's phase tail
+    SCR_LANE_SUBS, SCR_VIT_SCHED,                    // 24-25: MSC lane -> sub-channel table, puncturing schedules
+    SCR_NAMED,
+    // the FIC decoders' own copies of the decoder slots (scratch_fic): one context decodes the FIC and the MSC on two streams at once
+    SCR_FIC_OFFSET = 20,
+    SCR_COUNT = SCR_NAMED + SCR_FIC_OFFSET,
+};
+template <dabgpu_scratch_slot S> constexpr dabgpu_scratch_slot scratch_fic(bool fic) {
+    static_assert(S + SCR_FIC_OFFSET >= SCR_NAMED && S < SCR_NAMED, "the FIC copy of this slot would overlap another slot");
+    return fic ? dabgpu_scratch_slot(S + SCR_FIC_OFFSET) : S;
+}
+
 struct dabgpu_ctx {
     int device = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;
-    std::vector<float> prs;          // host copy, 2*2048
-    std::vector<int> mapper;         // host copy, 1536
     float* d_tw = nullptr;           // 2048 x (cos, -sin)
-    uint16_t* d_inv_map = nullptr;   // carrier -> de-interleaved position
-    float* d_prs = nullptr;          // PRS spectrum
-    float* d_prs_time_ref = nullptr; // conj(IFFT(relative_phase(PRS))), coarse-sync reference
+    // [mode]: mode I from the context's PRS and mapper (dabgpu_create), modes II-IV built on first use (dabgpu_mode_tables_of)
+    dabgpu_mode_tables modes[5] = {};
     struct dabgpu_vit_tables* d_vit_tables = nullptr;
     int vit_mapping = 0;             // DABGPU_VIT_MAP_* (dabgpu_viterbi_set_mapping)
     // symbols_per_block = 0 of the mode I demodulator: what dabgpu_ofdm_tune measured on this device, per size bucket (ceil log2 of the
     // batch) and kernel variant (loader, soft-bit layout, phase tail); the data path only looks it up (dabgpu_abi.hip)
     struct spb_choice { int bucket; int variant; int spb; };
     std::vector<spb_choice> spb_cache;
-    int* d_mode_mapper[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // carrier mappers of modes II-IV, built on first use
-    int* d_mode_inv_map[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // their inverses (ofdm_wave512.hip)
-    float* d_mode_prs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};    // PRS spectra and coarse-sync references of modes II-IV
-    float* d_mode_prs_time_ref[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::vector<void*> scratch;      // grow-only device scratch slots
-    std::vector<size_t> scratch_bytes;
+    void* scratch[SCR_COUNT] = {};   // grow-only device scratch slots (dabgpu_scratch)
+    size_t scratch_bytes[SCR_COUNT] = {};
     std::vector<void*> parked;       // outgrown slots a captured graph may still address (dabgpu_scratch); freed with the context
     bool captured_once = false;      // a capturable entry point of this context has run under hipStreamBeginCapture
     // Host-side entry points (*_host_sync, msc_stream_*, dabplus_process_frame_host_sync) share the context's stream and scratch
@@ -53,6 +80,8 @@ struct dabgpu_ctx {
     std::mutex tables_mu;
 };
 #define DABGPU_HOST_LOCK(ctx) std::lock_guard<std::recursive_mutex> dabgpu_host_lock_(ctx->host_mu)
+// return the status of a HIP call that failed (needs an `int st` in scope)
+#define DABGPU_CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
 // asynchronous host -> device copy on `s` that has consumed h_src when it returns (h_src may be freed or overwritten at once)
 extern "C" int dabgpu_stage_h2d(dabgpu_ctx* c, void* d_dst, const void* h_src, size_t bytes, hipStream_t s);
 // the same for table `which` (0: sub-channel plans, 1: lane table) of the context, skipped when nothing changed (see dabgpu_ctx::tables)
@@ -67,11 +96,41 @@ int dabgpu_bind_device(const dabgpu_ctx* c);
 // instead of spinning -- threads that wait for the device then cost no CPU (a container's CPU quota is shared by every waiting thread of a many-receiver
 // process), at ~20-50 us more wake-up latency; =spin is the runtime's default.  Unset: `bank_default` for the receiver bank's events, spin elsewhere.
 unsigned dabgpu_wait_event_flags(bool bank_default_block);
-int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out);
+int dabgpu_scratch(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out);
 // the same from a capturable entry point launching on `user` (HIP graphs: see the definition)
-int dabgpu_scratch(dabgpu_ctx* c, int slot, size_t bytes, void** out, hipStream_t user);
-// device PRS spectrum / coarse-sync time reference of a transmission mode (mode I: the context's own tables)
-int dabgpu_mode_sync_tables(dabgpu_ctx* c, int mode, const float** d_prs, const float** d_prs_time_ref);
+int dabgpu_scratch(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out, hipStream_t user);
+// the device tables of a transmission mode (mode I: the context's own), built on first use; DABGPU_ERR_INVALID_ARG for no mode
+int dabgpu_mode_tables_of(dabgpu_ctx* c, int mode, const dabgpu_mode_tables** out, const char* who);
+
+// capture formats the demodulators' loaders dequantise themselves (iq_decode.h): 0 = complex float, 1 = u8, 2 = s8, 3 = s16 little
+// endian; -1 = none (with an error message naming `who`, when given)
+inline int dabgpu_fused_loader(int format, const char* who = nullptr) {
+    switch (format) {
+    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32: return 0;
+    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8: return 1;
+    case DABGPU_IQ_RAW_S8: return 2;
+    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16: return 3;
+    default:
+        if (who) dabgpu_set_error("%s: format %d has no fused loader (float32, u8, s8, s16 little endian do)", who, format);
+        return -1;
+    }
+}
+
+// argument checks of the entry points that demodulate into soft bits of mode I (who = the entry point's name in the message)
+inline int dabgpu_check_bits_layout(const char* who, int bits_layout) {
+    if (bits_layout == DABGPU_BITS_NATURAL || bits_layout == DABGPU_BITS_MSC_CLASSED) return DABGPU_OK;
+    dabgpu_set_error("%s: unknown bits_layout %d", who, bits_layout); return DABGPU_ERR_INVALID_ARG;
+}
+// soft-bit frame stride; IQ (`iq`) aligned to iq_align bytes, soft bits to 16
+inline int dabgpu_check_bits_buffers(const char* who, size_t bits_frame_stride, const char* iq, const void* d_iq, int iq_align, const void* d_bits) {
+    if (bits_frame_stride != 0 && (bits_frame_stride < DABGPU_NB_FRAME_BITS || (bits_frame_stride & 15))) {
+        dabgpu_set_error("%s: bits_frame_stride must be 0 or a multiple of 16 >= 230400", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_iq & (uintptr_t)(iq_align - 1)) || ((uintptr_t)d_bits & 15)) {
+        dabgpu_set_error("%s: %s must be %d-byte, d_bits 16-byte aligned", who, iq, iq_align); return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
+}
 
 // per-stream work item of a stream bank round (ofdm_stream.hip -> ofdm_demod.hip)
 struct dabgpu_frame_desc {
@@ -108,11 +167,9 @@ int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int
                                   int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
                                   size_t block_stride, hipStream_t s);
 
-// the inverse carrier mapper of modes II-IV on the device (carrier c carries soft bit inv[c]), built on the context at first use (ofdm_wave512.hip)
-int dabgpu_mode_inv_map(dabgpu_ctx* c, int mode, const int** out);
-
 // OFDM transmitter (ofdm_mod.hip): n_frames frames of `mode` from their payloads (layout DABGPU_TX_PAYLOAD_*) into d_out (format
-// DABGPU_IQ_RAW_F32L / _U8), NULL first; d_prs = the PRS spectrum (nb_fft complex float) on the device; arguments checked by the caller
+// DABGPU_IQ_RAW_F32L / _U8), NULL first; d_prs = the PRS spectrum (nb_fft complex float) on the device, nullptr = the mode's own;
+// arguments checked by the caller
 int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int layout, size_t n_frames, const float* d_prs, float freq_norm,
                            void* d_out, int out_format, hipStream_t s);
 

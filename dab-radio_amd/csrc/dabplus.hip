@@ -557,23 +557,21 @@ int dabgpu_dabplus_process_frame_host_sync(dabgpu_dabplus_bank* b, const uint8_t
     DABGPU_HOST_LOCK(b->ctx);
     hipStream_t s = c->stream;
     int st;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemcpyAsync(b->d_frame, h_frame, n_bytes, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(b->d_n, &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(b->d_frame, h_frame, n_bytes, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(b->d_n, &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if ((st = dabgpu_dabplus_bank_process(b, b->d_frame, reinterpret_cast<const uint64_t*>(b->d_off), 0, b->d_n, 1, b->d_sf, DP_MAX_SF, b->d_res, 1,
                                           b->d_counts, s))) return st;
     int32_t counts[4];
-    CK(hipMemcpyAsync(counts, b->d_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DABGPU_CK(hipMemcpyAsync(counts, b->d_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     *superframe_done = counts[0];
     *firecode_wait_failed = counts[1];
     if (firecode_wait_rx_calc) *firecode_wait_rx_calc = (uint32_t)counts[2];
     if (counts[0]) {
-        CK(hipMemcpyAsync(h_result, b->d_res, sizeof(dabgpu_superframe_result), hipMemcpyDeviceToHost, s));
-        CK(hipMemcpyAsync(h_superframe, b->d_sf, 5 * (size_t)n_bytes, hipMemcpyDeviceToHost, s));
-        CK(hipStreamSynchronize(s));
+        DABGPU_CK(hipMemcpyAsync(h_result, b->d_res, sizeof(dabgpu_superframe_result), hipMemcpyDeviceToHost, s));
+        DABGPU_CK(hipMemcpyAsync(h_superframe, b->d_sf, 5 * (size_t)n_bytes, hipMemcpyDeviceToHost, s));
+        DABGPU_CK(hipStreamSynchronize(s));
     }
-#undef CK
     return DABGPU_OK;
 }
 

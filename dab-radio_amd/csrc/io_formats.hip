@@ -182,22 +182,20 @@ int dabgpu_hard_bytes_to_soft_bits(dabgpu_ctx* c, const uint8_t* d_bytes, size_t
 }
 
 // ---- host-buffer forms ------------------------------------------------------------------------------------------
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
 static int round_trip(dabgpu_ctx* c, const void* h_in, size_t in_bytes, void* h_out, size_t out_bytes,
                       int (*run)(dabgpu_ctx*, const void*, void*, size_t, int, hipStream_t), size_t n, int arg) {
     int st;
     DABGPU_BIND(c);
     void *d_in, *d_out;
-    if ((st = dabgpu_scratch(c, 20, in_bytes + 16, &d_in))) return st;
-    if ((st = dabgpu_scratch(c, 21, out_bytes + 16, &d_out))) return st;
+    if ((st = dabgpu_scratch(c, SCR_CONVERT_IN, in_bytes + 16, &d_in))) return st;
+    if ((st = dabgpu_scratch(c, SCR_CONVERT_OUT, out_bytes + 16, &d_out))) return st;
     hipStream_t s = c->stream;
-    CK(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
     if ((st = run(c, d_in, d_out, n, arg, s))) return st;
-    CK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
+    DABGPU_CK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     return DABGPU_OK;
 }
-#undef CK
 
 int dabgpu_iq_convert_host_sync(dabgpu_ctx* c, const void* h_raw, int format, size_t n_samples, float* h_iq) {
     if (!c) { dabgpu_set_error("iq_convert_host_sync: null context"); return DABGPU_ERR_INVALID_ARG; }

@@ -264,22 +264,24 @@ int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, in
                            void* d_out, int out_format, hipStream_t s) {
     ModeGeom g;
     if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_modulate_frames: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    int st;
-    const int* d_inv = nullptr;
-    if (mode != 1 && layout == DABGPU_TX_PAYLOAD_FRAME_BITS && (st = dabgpu_mode_inv_map(c, mode, &d_inv))) return st;
+    // (modes II-IV: their tables are built only by a call that reads them)
+    const dabgpu_mode_tables* t = nullptr;
+    int st = DABGPU_OK;
+    if ((mode == 1 || !d_prs || layout == DABGPU_TX_PAYLOAD_FRAME_BITS) && (st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_modulate_frames"))) return st;
+    const int* d_inv = (t && layout == DABGPU_TX_PAYLOAD_FRAME_BITS) ? t->inv_map : nullptr;
     const int spb = tx_sym_per_run(c, n_frames, g.n_sym);
     const int runs = (g.n_sym + spb - 1) / spb;
     const size_t units = n_frames * (size_t)runs;
     if (units > 0x7FFFFFFFull) { dabgpu_set_error("ofdm_modulate_frames: n_frames too large"); return DABGPU_ERR_INVALID_ARG; }
     const float scale = (1.0f / (float)g.n_carriers * 4.0f) * 127.5f;          // simulate_transmitter.cpp:174 x QuantisedIQ<uint8_t>::MAX_AMPLITUDE
     const bool pll = freq_norm != 0.0f;
-    const f2* prs = reinterpret_cast<const f2*>(d_prs);
+    const f2* prs = reinterpret_cast<const f2*>(d_prs ? d_prs : t->prs);
     const f2* tw = reinterpret_cast<const f2*>(c->d_tw);
 #define TX_GO(OUT, LAYOUT, PLL)                                                                                                       \
     do {                                                                                                                              \
         if (mode == 1)                                                                                                                \
             hipLaunchKernelGGL((ofdm_mod_kernel<OUT, LAYOUT, PLL>), dim3((unsigned)units), dim3(256), 0, s, d_payload, prs, tw,       \
-                               c->d_inv_map, (int)n_frames, spb, runs, freq_norm, scale, d_out);                                      \
+                               t->inv_map16, (int)n_frames, spb, runs, freq_norm, scale, d_out);                                      \
         else                                                                                                                          \
             hipLaunchKernelGGL((ofdm_mod_mode_kernel<OUT, LAYOUT, PLL>), dim3((unsigned)units), dim3(256), 0, s, mode, d_payload, prs, \
                                tw, d_inv, (int)n_frames, spb, runs, freq_norm, scale, d_out);                                         \
@@ -320,12 +322,7 @@ int dabgpu_ofdm_modulate_frames(dabgpu_ctx* c, int mode, const uint8_t* d_payloa
     if ((uintptr_t)d_out & 15) { dabgpu_set_error("ofdm_modulate_frames: d_out must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
     if ((uintptr_t)d_prs_fft_ref & 7) { dabgpu_set_error("ofdm_modulate_frames: d_prs_fft_ref must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(c);
-    const float* d_prs = d_prs_fft_ref;
-    if (!d_prs) {
-        const float* d_ref;
-        if ((st = dabgpu_mode_sync_tables(c, mode, &d_prs, &d_ref))) return st;
-    }
-    return dabgpu_launch_ofdm_mod(c, mode, d_payload, payload_layout, n_frames, d_prs, freq_norm, d_out, out_format, (hipStream_t)stream);
+    return dabgpu_launch_ofdm_mod(c, mode, d_payload, payload_layout, n_frames, d_prs_fft_ref, freq_norm, d_out, out_format, (hipStream_t)stream);
 }
 
 int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx* c, int mode, const uint8_t* h_payload, int payload_layout, size_t n_frames,
@@ -341,18 +338,16 @@ int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx* c, int mode, const uint8_t
     const size_t prs_bytes = (size_t)g.n_fft * 2 * sizeof(float);
     uint8_t *d_in, *d_out;
     float* d_prs = nullptr;
-    // (slots of the single-frame host forms: 1 = IQ, 2 = bits, 6 = FFT views; a call of one of them never runs inside another)
-    if ((st = dabgpu_scratch(c, 2, in_bytes, (void**)&d_in))) return st;
-    if ((st = dabgpu_scratch(c, 1, out_bytes, (void**)&d_out))) return st;
-    if (h_prs_fft_ref && (st = dabgpu_scratch(c, 6, prs_bytes, (void**)&d_prs))) return st;
+    // (the slots of the single-frame host forms, in the roles of a transmitter: a call of one of them never runs inside another)
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, in_bytes, (void**)&d_in))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_IQ, out_bytes, (void**)&d_out))) return st;
+    if (h_prs_fft_ref && (st = dabgpu_scratch(c, SCR_HOST_FFT, prs_bytes, (void**)&d_prs))) return st;
     hipStream_t s = c->stream;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemcpyAsync(d_in, h_payload, in_bytes, hipMemcpyHostToDevice, s));
-    if (h_prs_fft_ref) CK(hipMemcpyAsync(d_prs, h_prs_fft_ref, prs_bytes, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(d_in, h_payload, in_bytes, hipMemcpyHostToDevice, s));
+    if (h_prs_fft_ref) DABGPU_CK(hipMemcpyAsync(d_prs, h_prs_fft_ref, prs_bytes, hipMemcpyHostToDevice, s));
     if ((st = dabgpu_ofdm_modulate_frames(c, mode, d_in, payload_layout, n_frames, d_prs, freq_norm, d_out, out_format, s))) return st;
-    CK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-#undef CK
+    DABGPU_CK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
     return DABGPU_OK;
 }
 

@@ -176,15 +176,8 @@ int dabgpu_launch_ofdm_demod_mode(dabgpu_ctx* c, int mode, const void* d_iq, int
     // DABGPU_MODE_GENERIC=1 keeps them on this file's kernel (the tests cross-check the two)
     if (mode != 1 && !d_fft && !getenv("DABGPU_MODE_GENERIC"))
         return dabgpu_launch_ofdm_demod_wave(c, mode, d_iq, src, d_freq, d_bits, d_cp_corr, n_frames, symbols_per_block, d_desc, d_block, block_stride, s);
-    // per-mode carrier mapper on the device, built on first use (get_DAB_mapper_ref, src/ofdm/dab_mapper_ref.cpp:10-51)
-    if (!c->d_mode_mapper[mode]) {
-        std::vector<int> m((size_t)g.n_carriers);
-        if ((st = dabgpu_get_carrier_mapper(mode, m.data()))) return st;
-        int* d_m = nullptr;
-        if ((st = dabgpu_check_hip(hipMalloc(&d_m, m.size() * sizeof(int)), "hipMalloc(mode mapper)"))) return st;
-        if ((st = dabgpu_check_hip(hipMemcpy(d_m, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(mode mapper)"))) { (void)hipFree(d_m); return st; }
-        c->d_mode_mapper[mode] = d_m;
-    }
+    const dabgpu_mode_tables* t;     // (mode I: the context's carrier mapper)
+    if ((st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_demod_mode"))) return st;
     if (symbols_per_block <= 0 || symbols_per_block > g.n_sym - 1) symbols_per_block = 19;
     const int chunks = (g.n_sym - 1 + symbols_per_block - 1) / symbols_per_block;
     const size_t lds = ((size_t)g.period + 3 * (size_t)g.n_fft) * sizeof(f2) + 512 * sizeof(float);
@@ -198,7 +191,7 @@ int dabgpu_launch_ofdm_demod_mode(dabgpu_ctx* c, int mode, const void* d_iq, int
                                                       "hipFuncSetAttribute(ofdm_demod_mode_kernel)"))) return st;                  \
         hipLaunchKernelGGL((ofdm_demod_mode_kernel<SRC, BANK>), dim3((unsigned)((size_t)n_frames * chunks)), dim3((unsigned)n_threads), lds, s, mode, \
                            reinterpret_cast<const f2*>(d_iq), d_freq, d_bits, reinterpret_cast<f2*>(d_cp_corr),                    \
-                           reinterpret_cast<f2*>(d_fft), reinterpret_cast<const f2*>(c->d_tw), c->d_mode_mapper[mode], n_frames,     \
+                           reinterpret_cast<f2*>(d_fft), reinterpret_cast<const f2*>(c->d_tw), t->mapper, n_frames,                \
                            symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride);                  \
     } while (0)
     if (!d_desc) MODE_GO(0, false);
@@ -219,76 +212,13 @@ int dabgpu_ofdm_demod_frames_mode(dabgpu_ctx* c, int mode, const float* d_iq, si
     if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_frames_mode: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0) return DABGPU_OK;
     if (n_frames > (size_t)(1 << 22)) { dabgpu_set_error("ofdm_demod_frames_mode: n_frames too large"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("ofdm_demod_frames_mode: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_bits & 15) { dabgpu_set_error("ofdm_demod_frames_mode: d_bits must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    int st = dabgpu_check_bits_buffers("ofdm_demod_frames_mode", 0, "d_iq", d_iq, 8, d_bits);
+    if (st) return st;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
-    int st;
     float* corr = d_cp_corr;
-    if (!corr && (st = dabgpu_scratch(c, 23, n_frames * (size_t)g.n_sym * 2 * sizeof(float), (void**)&corr))) return st;
+    if (!corr && (st = dabgpu_scratch(c, SCR_MODE_CORR, n_frames * (size_t)g.n_sym * 2 * sizeof(float), (void**)&corr))) return st;
     return dabgpu_launch_ofdm_demod_mode(c, mode, d_iq, 0, d_freq, d_bits, corr, d_fft, (int)n_frames, symbols_per_block, nullptr, nullptr, 0, s);
 }
-
-// ---- single-stream, host-buffer forms for the OFDM_Demod mirror class in modes II-IV ----
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-
-int dabgpu_ofdm_demod_stream_frame_sync_mode(dabgpu_ctx* c, int mode, const float* h_iq, float freq_coarse, float* h_freq_fine, float beta,
-                                             int8_t* h_bits, float* h_total_phase, float* h_fft) {
-    ModeGeom g;
-    if (!c || !h_iq || !h_bits || !h_freq_fine) { dabgpu_set_error("ofdm_demod_stream_frame_sync_mode: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_stream_frame_sync_mode: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    if (mode == 1) return dabgpu_ofdm_demod_stream_frame_sync(c, h_iq, freq_coarse, h_freq_fine, beta, h_bits, h_total_phase, h_fft, nullptr);
-    int st;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    const size_t iq_bytes = (size_t)g.frame_samples * 2 * sizeof(float);
-    const size_t fft_bytes = (size_t)(g.n_sym + 1) * g.n_fft * 2 * sizeof(float);
-    float *d_iq, *d_small, *d_corr, *d_fft = nullptr; int8_t* d_bits;
-    if ((st = dabgpu_scratch(c, 1, iq_bytes, (void**)&d_iq))) return st;
-    if ((st = dabgpu_scratch(c, 2, (size_t)g.frame_bits, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, 3, 4 * sizeof(float), (void**)&d_small))) return st;       // [0] net freq, [1] fine, [2] total phase
-    if ((st = dabgpu_scratch(c, 4, (size_t)g.n_sym * 2 * sizeof(float), (void**)&d_corr))) return st;
-    if (h_fft && (st = dabgpu_scratch(c, 6, fft_bytes, (void**)&d_fft))) return st;
-    hipStream_t s = c->stream;
-    const float h_small[2] = { freq_coarse + *h_freq_fine, *h_freq_fine };
-    CK(hipMemcpyAsync(d_iq, h_iq, iq_bytes, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(d_small, h_small, sizeof(h_small), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_ofdm_demod_frames_mode(c, mode, d_iq, 1, d_small, d_bits, d_corr, d_fft, 0, s))) return st;
-    if ((st = dabgpu_ofdm_phase_update_mode(c, mode, d_corr, 1, beta, d_small + 2, d_small + 1, s))) return st;
-    CK(hipMemcpyAsync(h_bits, d_bits, (size_t)g.frame_bits, hipMemcpyDeviceToHost, s));
-    float back[2];
-    CK(hipMemcpyAsync(back, d_small + 1, 2 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (h_fft) CK(hipMemcpyAsync(h_fft, d_fft, fft_bytes, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    *h_freq_fine = back[0];
-    if (h_total_phase) *h_total_phase = back[1];
-    return DABGPU_OK;
-}
-
-int dabgpu_ofdm_sync_host_sync_mode(dabgpu_ctx* c, int mode, const float* h_prs_sym, const dabgpu_sync_cfg* cfg, dabgpu_sync_state* h_state,
-                                    float* h_impulse, float* h_freq) {
-    ModeGeom g;
-    if (!c || !h_prs_sym || !cfg || !h_state) { dabgpu_set_error("ofdm_sync_host_sync_mode: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_sync_host_sync_mode: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st;
-    const size_t N = (size_t)g.n_fft;
-    float *d_sym, *d_imp, *d_frq; dabgpu_sync_state* d_st;
-    if ((st = dabgpu_scratch(c, 7, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_sym))) return st;
-    if ((st = dabgpu_scratch(c, 8, sizeof(dabgpu_sync_state), (void**)&d_st))) return st;
-    if ((st = dabgpu_scratch(c, 9, sizeof(float) * 2 * DABGPU_NB_FFT, (void**)&d_imp))) return st;
-    d_frq = d_imp + DABGPU_NB_FFT;
-    hipStream_t s = c->stream;
-    CK(hipMemcpyAsync(d_sym, h_prs_sym, sizeof(float) * 2 * N, hipMemcpyHostToDevice, s));
-    CK(hipMemcpyAsync(d_st, h_state, sizeof(dabgpu_sync_state), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_ofdm_sync_mode(c, mode, d_sym, 1, N, cfg, d_st, d_imp, d_frq, s))) return st;
-    CK(hipMemcpyAsync(h_state, d_st, sizeof(dabgpu_sync_state), hipMemcpyDeviceToHost, s));
-    if (h_impulse) CK(hipMemcpyAsync(h_impulse, d_imp, sizeof(float) * N, hipMemcpyDeviceToHost, s));
-    if (h_freq) CK(hipMemcpyAsync(h_freq, d_frq, sizeof(float) * N, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    return DABGPU_OK;
-}
-#undef CK
 
 }  // extern "C"

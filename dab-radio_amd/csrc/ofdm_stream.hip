@@ -443,16 +443,14 @@ int dabgpu_stream_bank_reset(dabgpu_stream_bank* b, void* stream) {
     DABGPU_BIND(b->ctx);
     hipStream_t s = (hipStream_t)stream;
     int st;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
-    CK(hipMemsetAsync(b->view.st, 0, b->n * sizeof(StreamState), s));
-    CK(hipMemsetAsync(b->view.sync, 0, b->n * sizeof(dabgpu_sync_state), s));
-    CK(hipMemsetAsync(b->view.sync_active, 0, b->n * sizeof(int), s));
-    CK(hipMemsetAsync(b->view.desc, 0xFF, b->n * sizeof(dabgpu_frame_desc), s));
-    CK(hipMemsetAsync(b->view.ring, 0, b->n * (size_t)b->view.g.null_period * sizeof(f2), s));
-    CK(hipMemsetAsync(b->view.corr, 0, b->n * (size_t)b->view.g.n_corr * sizeof(f2), s));
-    CK(hipMemsetAsync(b->view.copy_cnt, 0, b->n * sizeof(int), s));
-    CK(hipMemsetAsync(b->view.not_done, 0, 16 * sizeof(int), s));
-#undef CK
+    DABGPU_CK(hipMemsetAsync(b->view.st, 0, b->n * sizeof(StreamState), s));
+    DABGPU_CK(hipMemsetAsync(b->view.sync, 0, b->n * sizeof(dabgpu_sync_state), s));
+    DABGPU_CK(hipMemsetAsync(b->view.sync_active, 0, b->n * sizeof(int), s));
+    DABGPU_CK(hipMemsetAsync(b->view.desc, 0xFF, b->n * sizeof(dabgpu_frame_desc), s));
+    DABGPU_CK(hipMemsetAsync(b->view.ring, 0, b->n * (size_t)b->view.g.null_period * sizeof(f2), s));
+    DABGPU_CK(hipMemsetAsync(b->view.corr, 0, b->n * (size_t)b->view.g.n_corr * sizeof(f2), s));
+    DABGPU_CK(hipMemsetAsync(b->view.copy_cnt, 0, b->n * sizeof(int), s));
+    DABGPU_CK(hipMemsetAsync(b->view.not_done, 0, 16 * sizeof(int), s));
     b->carry_pending = false;
     return DABGPU_OK;
 }
@@ -538,7 +536,6 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     hipStream_t s = (hipStream_t)stream;
     const int n = (int)b->n;
     int st;
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
     // Retained blocks (mode I): the unfinished frame at the end of a block is not copied into the stream's frame buffer -- the next
     // call reads it where it is.  A frame may then lie in the frame buffer, the previous block and the current block.  With blocks of
     // a frame's length or more every pending frame completes inside the next block; with the ring form's blocks (at most a frame
@@ -549,7 +546,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     if (b->carry_pending && !prev_valid) {
         hipLaunchKernelGGL(stream_copy_kernel<SRC>, dim3(COPY_WGS, (unsigned)n), dim3(256), 0, s, b->view, 0, static_cast<const uint8_t*>(d_prev),
                            stream_stride_samples);
-        CK(hipGetLastError());
+        DABGPU_CK(hipGetLastError());
     }
     b->carry_pending = false;
     const uint8_t* prev_iq = prev_valid ? static_cast<const uint8_t*>(d_prev) : nullptr;
@@ -559,21 +556,21 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
         const long long stride = (long long)k * b->cfg.signal_l1_nb_decimate;
         const long long n_win = ((long long)n_samples - k + stride - 1) / stride;
         if (n_win > b->view.win_cap) {
-            CK(hipStreamSynchronize(s));
+            DABGPU_CK(hipStreamSynchronize(s));
             if (b->view.win) { (void)hipFree(b->view.win); b->allocs.erase(std::find(b->allocs.begin(), b->allocs.end(), (void*)b->view.win)); }
             b->view.win = nullptr; b->view.win_cap = 0;
-            CK(hipMalloc((void**)&b->view.win, (size_t)n * (size_t)n_win * sizeof(float)));
+            DABGPU_CK(hipMalloc((void**)&b->view.win, (size_t)n * (size_t)n_win * sizeof(float)));
             b->allocs.push_back(b->view.win);
             b->view.win_cap = n_win;
         }
         if (n_win > 0) {
             hipLaunchKernelGGL(stream_l1_kernel<SRC>, dim3((unsigned)((n_win + L1_WINDOWS - 1) / L1_WINDOWS), (unsigned)n), dim3(256), 0, s,
                                b->view, static_cast<const uint8_t*>(d_iq), stream_stride_samples, n_win, k, stride);
-            CK(hipGetLastError());
+            DABGPU_CK(hipGetLastError());
         }
     }
-    const float *d_prs = nullptr, *d_prs_time_ref = nullptr;               // PRS spectrum / coarse-sync reference of the bank's mode
-    if ((st = dabgpu_mode_sync_tables(c, G.mode, &d_prs, &d_prs_time_ref))) return st;
+    const dabgpu_mode_tables* T;                                            // PRS spectrum / coarse-sync reference of the bank's mode
+    if ((st = dabgpu_mode_tables_of(c, G.mode, &T, "stream_bank_process"))) return st;
     // rounds every locked stream needs: one per frame that can complete inside this block (the demodulation of frame k - 1 and the
     // synchronisation of frame k share a round) plus one for the partial frame at the end; a stream that needs more (re-acquisition)
     // is caught by the counter read back after these
@@ -586,8 +583,8 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     hipStream_t lane_stream[2] = {s, b->side};
     const int lane_lo[3] = {0, (n_lanes == 2) ? n / 2 : n, n};
     if (n_lanes == 2) {
-        CK(hipEventRecord(b->ev_fork, s));
-        CK(hipStreamWaitEvent(b->side, b->ev_fork, 0));
+        DABGPU_CK(hipEventRecord(b->ev_fork, s));
+        DABGPU_CK(hipStreamWaitEvent(b->side, b->ev_fork, 0));
     }
     // (an error inside the rounds must not leave work on the side stream unordered with the caller's stream: the caller may free the
     // block and the output buffers as soon as the call has returned)
@@ -610,7 +607,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
             float* corr_l = b->d_corr_out + (size_t)s0 * G.n_sym * 2;
             if (G.mode == 1) {
                 CKL(dabgpu_launch_ofdm_demod(b->view.frame + (size_t)s0 * G.frame_samples, SRC, b->view.freq + s0, d_bits, corr_l, nullptr, nullptr,
-                                            c->d_tw, c->d_inv_map, cnt, bank_spb, 0, b->view.desc + s0, iq_l, stream_stride_samples, classed, ls, nullptr, nullptr, 0.0f,
+                                            c->d_tw, T->inv_map16, cnt, bank_spb, 0, b->view.desc + s0, iq_l, stream_stride_samples, classed, ls, nullptr, nullptr, 0.0f,
                                             prev_iq ? prev_iq + (size_t)s0 * stream_stride_samples * sb : nullptr));
             } else if ((st = dabgpu_launch_ofdm_demod_mode(     /* (modes II-IV run in one lane: n_lanes == 1, s0 == 0, cnt == n) */c, G.mode, b->view.frame, SRC, b->view.freq, d_bits, b->d_corr_out, nullptr, n, 0,
                                                            b->view.desc, d_iq, stream_stride_samples, ls))) {
@@ -621,7 +618,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
                                         (int)(sizeof(dabgpu_sync_state) / sizeof(float)), b->view.desc + s0, G.n_sym, G.n_fft, ls));
             // (after the phase kernel: the synchroniser of frame k sees the fine frequency the phase of frame k - 1 left, as in the reference)
             CKL(dabgpu_launch_sync(reinterpret_cast<const float*>(b->view.corr + (size_t)s0 * NB_CORR + NB_NULL_PERIOD), NB_CORR, cnt, &b->cfg.sync,
-                                  b->view.sync + s0, nullptr, nullptr, c->d_tw, d_prs, d_prs_time_ref, b->view.sync_active + s0, G.mode, ls));
+                                  b->view.sync + s0, nullptr, nullptr, c->d_tw, T->prs, T->prs_time_ref, b->view.sync_active + s0, G.mode, ls));
         }
         if (round + 1 >= blind_rounds) {
             for (int l = 0; l < n_lanes; l++) CKL(hipMemcpyAsync(&h_not_done[l], b->view.not_done + 8 * l + (round & 7), sizeof(int), hipMemcpyDeviceToHost, lane_stream[l]));
@@ -636,27 +633,39 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     }
 #undef CKL
     if (n_lanes == 2) {
-        CK(hipEventRecord(b->ev_join, b->side));
-        CK(hipStreamWaitEvent(s, b->ev_join, 0));
+        DABGPU_CK(hipEventRecord(b->ev_join, b->side));
+        DABGPU_CK(hipStreamWaitEvent(s, b->ev_join, 0));
     }
     if (d_n_frames) {
         hipLaunchKernelGGL(stream_report_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, b->view, n, d_n_frames,
                            (dabgpu_stream_status*)nullptr, ring_mode ? (int)max_frames_per_stream : 0);
-        CK(hipGetLastError());
+        DABGPU_CK(hipGetLastError());
     }
-#undef CK
     if (use_retain) { b->carry_pending = true; b->carry_src = SRC; b->carry_stride = stream_stride_samples; }
     return DABGPU_OK;
 }
 
+// bank_process_impl for the loader src (0..3, dabgpu_fused_loader) of the block's capture format
+template <class... A>
+static int bank_process_src(int src, A... a) {
+    switch (src) {
+    case 0: return bank_process_impl<0>(a...);
+    case 1: return bank_process_impl<1>(a...);
+    case 2: return bank_process_impl<2>(a...);
+    case 3: return bank_process_impl<3>(a...);
+    default: dabgpu_set_error("stream_bank_process: no loader %d", src); return DABGPU_ERR_INVALID_ARG;
+    }
+}
+
 // dabgpu_stream_bank_release: copies what the last retained call left in its block into the frame buffers
-template <int SRC>
-static int bank_release_impl(dabgpu_stream_bank* b, const void* d_prev, size_t stream_stride_samples, void* stream) {
-    if (b->carry_src != SRC || b->carry_stride != stream_stride_samples) {
+static int bank_release_src(dabgpu_stream_bank* b, int src, const void* d_prev, size_t stream_stride_samples, void* stream) {
+    if (b->carry_src != src || b->carry_stride != stream_stride_samples) {        // (carry_src: the loader of a bank_process_impl<SRC>)
         dabgpu_set_error("stream_bank_release: not the format / stride of the retained block"); return DABGPU_ERR_INVALID_ARG;
     }
     DABGPU_BIND(b->ctx);
-    hipLaunchKernelGGL(stream_copy_kernel<SRC>, dim3(COPY_WGS, (unsigned)b->n), dim3(256), 0, (hipStream_t)stream, b->view, 0,
+    static void (*const copy[4])(BankView, int, const uint8_t*, size_t) = {stream_copy_kernel<0>, stream_copy_kernel<1>, stream_copy_kernel<2>,
+                                                                           stream_copy_kernel<3>};
+    hipLaunchKernelGGL(copy[src], dim3(COPY_WGS, (unsigned)b->n), dim3(256), 0, (hipStream_t)stream, b->view, 0,
                        static_cast<const uint8_t*>(d_prev), stream_stride_samples);
     const int st = dabgpu_check_hip(hipGetLastError(), "stream_copy_kernel launch");
     if (st) return st;
@@ -671,34 +680,21 @@ int dabgpu_stream_bank_process_retained(dabgpu_stream_bank* b, const void* d_raw
                                         const void* d_prev_raw, int8_t* d_bits, size_t max_frames_per_stream, int32_t* d_n_frames, void* stream) {
     if (!b || !d_raw) { dabgpu_set_error("stream_bank_process_retained: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (n_samples == 0) return DABGPU_OK;
-    switch (format) {
-    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32:
-        return bank_process_impl<0>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream, 0, 0, d_prev_raw, 1);
-    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8:
-        return bank_process_impl<1>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream, 0, 0, d_prev_raw, 1);
-    case DABGPU_IQ_RAW_S8:
-        return bank_process_impl<2>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream, 0, 0, d_prev_raw, 1);
-    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16:
-        return bank_process_impl<3>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream, 0, 0, d_prev_raw, 1);
-    default: break;
+    const int src = dabgpu_fused_loader(format);
+    if (src < 0) {
+        dabgpu_set_error("stream_bank_process_retained: format %d is not read by the bank's kernels directly (raw_f32l, raw_u8, raw_s8, raw_s16l, wav PCM8 / PCM16 / float32)", format);
+        return DABGPU_ERR_INVALID_ARG;
     }
-    dabgpu_set_error("stream_bank_process_retained: format %d is not read by the bank's kernels directly (raw_f32l, raw_u8, raw_s8, raw_s16l, wav PCM8 / PCM16 / float32)", format);
-    return DABGPU_ERR_INVALID_ARG;
+    return bank_process_src(src, b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream, 0, 0, d_prev_raw, 1);
 }
 
 int dabgpu_stream_bank_release(dabgpu_stream_bank* b, const void* d_prev_raw, int format, size_t stream_stride_samples, void* stream) {
     if (!b) { dabgpu_set_error("stream_bank_release: null bank"); return DABGPU_ERR_INVALID_ARG; }
     if (!b->carry_pending) return DABGPU_OK;
     if (!d_prev_raw) { dabgpu_set_error("stream_bank_release: null block"); return DABGPU_ERR_INVALID_ARG; }
-    switch (format) {
-    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32: return bank_release_impl<0>(b, d_prev_raw, stream_stride_samples, stream);
-    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8: return bank_release_impl<1>(b, d_prev_raw, stream_stride_samples, stream);
-    case DABGPU_IQ_RAW_S8: return bank_release_impl<2>(b, d_prev_raw, stream_stride_samples, stream);
-    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16: return bank_release_impl<3>(b, d_prev_raw, stream_stride_samples, stream);
-    default: break;
-    }
-    dabgpu_set_error("stream_bank_release: not the format of the retained block");
-    return DABGPU_ERR_INVALID_ARG;
+    const int src = dabgpu_fused_loader(format);
+    if (src < 0) { dabgpu_set_error("stream_bank_release: not the format of the retained block"); return DABGPU_ERR_INVALID_ARG; }
+    return bank_release_src(b, src, d_prev_raw, stream_stride_samples, stream);
 }
 
 int dabgpu_stream_bank_process(dabgpu_stream_bank* b, const float* d_iq, size_t stream_stride_samples, size_t n_samples,
@@ -715,17 +711,8 @@ int dabgpu_stream_bank_process_raw(dabgpu_stream_bank* b, const void* d_raw, int
     if (sb == 0) { dabgpu_set_error("stream_bank_process_raw: unknown format %d", format); return DABGPU_ERR_INVALID_ARG; }
     if (n_samples == 0) return DABGPU_OK;
     // formats the kernels read by themselves: no conversion pass, 2-4 bytes per sample from HBM instead of 8
-    switch (format) {
-    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32:
-        return bank_process_impl<0>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
-    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8:
-        return bank_process_impl<1>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
-    case DABGPU_IQ_RAW_S8:
-        return bank_process_impl<2>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
-    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16:
-        return bank_process_impl<3>(b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
-    default: break;
-    }
+    const int src = dabgpu_fused_loader(format);
+    if (src >= 0) return bank_process_src(src, b, d_raw, stream_stride_samples, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
     if (((stream_stride_samples * sb) & 15) != 0 && b->n > 1) {
         dabgpu_set_error("stream_bank_process_raw: the byte stride between streams must be a multiple of 16"); return DABGPU_ERR_INVALID_ARG;
     }
@@ -755,27 +742,19 @@ static int bank_process_ring_any(dabgpu_stream_bank* b, const void* d_raw, int f
                                  int8_t* d_hist, int hist_frames, int32_t* d_newest_slot, int bits_layout, void* stream, const void* d_prev, int retain) {
     if (!b || !d_raw || !d_hist || !d_newest_slot) { dabgpu_set_error("stream_bank_process_ring: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (hist_frames < 5) { dabgpu_set_error("stream_bank_process_ring: the ring needs at least 5 frames"); return DABGPU_ERR_INVALID_ARG; }
-    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) {
-        dabgpu_set_error("stream_bank_process_ring: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG;
-    }
+    const int st = dabgpu_check_bits_layout("stream_bank_process_ring", bits_layout);
+    if (st) return st;
     const int classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
     if (classed && b->view.g.mode != 1) {
         dabgpu_set_error("stream_bank_process_ring: class order is defined for transmission mode I (the DAB layer above the soft bits is mode I only)");
         return DABGPU_ERR_UNSUPPORTED;
     }
-    switch (format) {
-    case DABGPU_IQ_RAW_F32L: case DABGPU_IQ_WAV_F32:
-        return bank_process_impl<0>(b, d_raw, stream_stride_samples, n_samples, d_hist, (size_t)hist_frames, d_newest_slot, stream, 1, classed, d_prev, retain);
-    case DABGPU_IQ_RAW_U8: case DABGPU_IQ_WAV_PCM8:
-        return bank_process_impl<1>(b, d_raw, stream_stride_samples, n_samples, d_hist, (size_t)hist_frames, d_newest_slot, stream, 1, classed, d_prev, retain);
-    case DABGPU_IQ_RAW_S8:
-        return bank_process_impl<2>(b, d_raw, stream_stride_samples, n_samples, d_hist, (size_t)hist_frames, d_newest_slot, stream, 1, classed, d_prev, retain);
-    case DABGPU_IQ_RAW_S16L: case DABGPU_IQ_WAV_PCM16:
-        return bank_process_impl<3>(b, d_raw, stream_stride_samples, n_samples, d_hist, (size_t)hist_frames, d_newest_slot, stream, 1, classed, d_prev, retain);
-    default:
+    const int src = dabgpu_fused_loader(format);
+    if (src < 0) {
         dabgpu_set_error("stream_bank_process_ring: format %d is not read directly (use raw_f32l, raw_u8, raw_s8 or raw_s16l)", format);
         return DABGPU_ERR_UNSUPPORTED;
     }
+    return bank_process_src(src, b, d_raw, stream_stride_samples, n_samples, d_hist, (size_t)hist_frames, d_newest_slot, stream, 1, classed, d_prev, retain);
 }
 
 int dabgpu_stream_bank_process_ring_layout(dabgpu_stream_bank* b, const void* d_raw, int format, size_t stream_stride_samples, size_t n_samples,

@@ -443,35 +443,16 @@ void ofdm_demod_wave3_kernel(const f2* __restrict__ iq, const float* __restrict_
 
 using namespace dabgpu;
 
-// inverse of the frequency interleaver of modes II-IV on the device, built on first use: carrier c carries soft bit inv[c]
-// (get_DAB_mapper_ref); the transmitter (ofdm_mod.hip) reads the same table
-int dabgpu_mode_inv_map(dabgpu_ctx* c, int mode, const int** out) {
-    ModeGeom g;
-    if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("mode inverse mapper: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    int st;
-    if (!c->d_mode_inv_map[mode]) {
-        std::vector<int> m((size_t)g.n_carriers), inv((size_t)g.n_carriers);
-        if ((st = dabgpu_get_carrier_mapper(mode, m.data()))) return st;
-        for (int n = 0; n < g.n_carriers; n++) inv[(size_t)m[(size_t)n]] = n;
-        // (into a local first: a failed copy must not leave a non-null pointer to uninitialised indices on the context)
-        int* d_inv = nullptr;
-        if ((st = dabgpu_check_hip(hipMalloc(&d_inv, inv.size() * sizeof(int)), "hipMalloc(mode inverse mapper)"))) return st;
-        if ((st = dabgpu_check_hip(hipMemcpy(d_inv, inv.data(), inv.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy(mode inverse mapper)"))) { (void)hipFree(d_inv); return st; }
-        c->d_mode_inv_map[mode] = d_inv;
-    }
-    *out = c->d_mode_inv_map[mode];
-    return DABGPU_OK;
-}
-
 // modes II, III and IV without the GUI views; frame = stream when d_desc != nullptr (stream bank rounds)
 int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
                                   int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
                                   size_t block_stride, hipStream_t s) {
     ModeGeom g;
     if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_wave: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    int st;
-    const int* d_inv = nullptr;
-    if ((st = dabgpu_mode_inv_map(c, mode, &d_inv))) return st;
+    const dabgpu_mode_tables* t;
+    const int st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_demod_wave");
+    if (st) return st;
+    const int* d_inv = t->inv_map;            // carrier c carries soft bit d_inv[c]
     if (symbols_per_block <= 0 || symbols_per_block > g.n_sym - 1) symbols_per_block = 19;
     const int chunks = (g.n_sym - 1 + symbols_per_block - 1) / symbols_per_block;
     const size_t units = (size_t)n_frames * chunks;

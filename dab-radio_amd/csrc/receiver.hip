@@ -39,7 +39,7 @@ struct dabgpu_receiver {
                                              // host's frame position hangs on them; they must not queue behind another receiver's 0.2 ms trellis launch
     dabgpu_frame_session* ses = nullptr;     // history ring, decode, result slots + stream B
     int mode = 1;
-    int geom[9] = {0};
+    dabgpu::ModeGeom g{};
     size_t stage_cap = 0;                    // samples
     float* h_stage[STAGES] = {nullptr, nullptr, nullptr};
     hipEvent_t stage_free[STAGES] = {nullptr, nullptr, nullptr};
@@ -63,8 +63,6 @@ struct dabgpu_receiver {
     dabgpu_rx_member* member = nullptr;
     int device = 0;
 };
-
-#define CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
 
 extern "C" void dabgpu_receiver_destroy(dabgpu_receiver* rx) {
     if (!rx) return;
@@ -100,12 +98,12 @@ extern "C" void dabgpu_receiver_destroy(dabgpu_receiver* rx) {
 extern "C" int dabgpu_receiver_create(dabgpu_receiver** out, int device, int mode, const float* h_prs, const int* h_mapper) {
     if (!out) { dabgpu_set_error("receiver_create: null argument"); return DABGPU_ERR_INVALID_ARG; }
     *out = nullptr;
-    int geom[9];
-    if (dabgpu_get_ofdm_params(mode, geom) != DABGPU_OK) { dabgpu_set_error("receiver_create: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu::ModeGeom g;
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("receiver_create: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
     if (mode != 1 && (h_prs || h_mapper)) { dabgpu_set_error("receiver_create: custom PRS / carrier tables are only supported in transmission mode I"); return DABGPU_ERR_INVALID_ARG; }
     dabgpu_receiver* rx = new dabgpu_receiver();
     rx->mode = mode;
-    memcpy(rx->geom, geom, sizeof(geom));
+    rx->g = g;
     int st = dabgpu_create(&rx->ctx, device, h_prs, h_mapper);
     if (!st) st = dabgpu_frame_session_create(&rx->ses, device);
     if (!st) {
@@ -113,9 +111,9 @@ extern "C" int dabgpu_receiver_create(dabgpu_receiver** out, int device, int mod
         st = dabgpu_check_hip(hipDeviceGetStreamPriorityRange(&least, &greatest), "hipDeviceGetStreamPriorityRange");
         if (!st) st = dabgpu_check_hip(hipStreamCreateWithPriority(&rx->a, hipStreamNonBlocking, greatest), "hipStreamCreateWithPriority(receiver)");
     }
-    const size_t n_fft = (size_t)geom[3], n_sym = (size_t)geom[0], frame_samples = (size_t)geom[6];
+    const size_t n_fft = (size_t)g.n_fft, n_sym = (size_t)g.n_sym, frame_samples = (size_t)g.frame_samples;
     // NULL symbol | frame, the frame between nb_cyclic_prefix samples before and nb_fft - nb_cyclic_prefix - 1 after the expected position
-    rx->stage_cap = (size_t)geom[2] + (n_fft - (size_t)geom[4]) + frame_samples;
+    rx->stage_cap = (size_t)g.null_period + (n_fft - (size_t)g.n_cp) + frame_samples;
     for (int k = 0; k < STAGES && !st; k++) {
         st = dabgpu_check_hip(hipHostMalloc((void**)&rx->h_stage[k], rx->stage_cap * 2 * sizeof(float), hipHostMallocDefault), "hipHostMalloc(receiver stage)");
         if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&rx->stage_free[k], dabgpu_wait_event_flags(false)), "hipEventCreate(receiver)");
@@ -148,8 +146,8 @@ extern "C" int dabgpu_receiver_create(dabgpu_receiver** out, int device, int mod
 extern "C" int dabgpu_receiver_create_banked(dabgpu_receiver** out, int device) {
     if (!out) { dabgpu_set_error("receiver_create_banked: null argument"); return DABGPU_ERR_INVALID_ARG; }
     *out = nullptr;
-    int geom[9];
-    (void)dabgpu_get_ofdm_params(1, geom);
+    dabgpu::ModeGeom g;
+    dabgpu::mode_geometry(1, g);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); dabgpu_set_error("hipGetDeviceCount found no device"); return DABGPU_ERR_NO_DEVICE; }
     if (device < 0 || device >= n) { dabgpu_set_error("device %d out of range (%d devices)", device, n); return DABGPU_ERR_INVALID_ARG; }
@@ -158,9 +156,9 @@ extern "C" int dabgpu_receiver_create_banked(dabgpu_receiver** out, int device) 
     dabgpu_receiver* rx = new dabgpu_receiver();
     rx->mode = 1;
     rx->device = device;
-    memcpy(rx->geom, geom, sizeof(geom));
-    const size_t n_fft = (size_t)geom[3], frame_samples = (size_t)geom[6];
-    rx->stage_cap = (size_t)geom[2] + (n_fft - (size_t)geom[4]) + frame_samples;
+    rx->g = g;
+    const size_t n_fft = (size_t)g.n_fft, frame_samples = (size_t)g.frame_samples;
+    rx->stage_cap = (size_t)g.null_period + (n_fft - (size_t)g.n_cp) + frame_samples;
     for (int k = 0; k < STAGES && !st; k++)
         st = dabgpu_check_hip(hipHostMalloc((void**)&rx->h_stage[k], rx->stage_cap * 2 * sizeof(float), hipHostMallocDefault), "hipHostMalloc(receiver stage)");
     if (!st) st = dabgpu_rx_bank_join(device, rx->h_stage, &rx->member);
@@ -202,7 +200,7 @@ extern "C" int dabgpu_receiver_reset(dabgpu_receiver* rx) {
 
 extern "C" int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_sync_cfg* cfg, size_t prs_sample) {
     if (!rx || !cfg) { dabgpu_set_error("receiver_submit_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    const size_t n_fft = (size_t)rx->geom[3];
+    const size_t n_fft = (size_t)rx->g.n_fft;
     if (prs_sample + n_fft > rx->stage_cap) { dabgpu_set_error("receiver_submit_sync: the PRS slot lies outside the staging buffer"); return DABGPU_ERR_INVALID_ARG; }
     if (rx->member) return dabgpu_rx_bank_post_sync(rx->member, cfg, rx->cur, prs_sample);
     if (rx->sync_pending) { dabgpu_set_error("receiver_submit_sync: the previous record has not been collected (dabgpu_receiver_wait_sync)"); return DABGPU_ERR_INVALID_ARG; }
@@ -210,14 +208,14 @@ extern "C" int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_syn
     DABGPU_BIND(c);
     hipStream_t a = rx->a;
     int st;
-    CK(hipMemcpyAsync(rx->d_prs, rx->h_stage[rx->cur] + 2 * prs_sample, n_fft * 2 * sizeof(float), hipMemcpyHostToDevice, a));
+    DABGPU_CK(hipMemcpyAsync(rx->d_prs, rx->h_stage[rx->cur] + 2 * prs_sample, n_fft * 2 * sizeof(float), hipMemcpyHostToDevice, a));
     rx->sync_coarse = cfg->is_coarse_freq_correction != 0;
     if ((st = dabgpu_ofdm_sync_mode(c, rx->mode, rx->d_prs, 1, n_fft, cfg, rx->d_state, rx->d_imp, rx->sync_coarse ? rx->d_imp + n_fft : nullptr, a))) return st;
     // (two copies on purpose: head + responses in one is 48 bytes over 16 KiB, and a device-to-host copy above 16 KiB takes a slower path in the
     //  runtime -- +18 us until the record is on the host, tools/exp/ab_mirror.sh)
-    CK(hipMemcpyAsync(rx->h_rec, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
-    CK(hipMemcpyAsync(rx->h_rec + REC_HEAD, rx->d_imp, (rx->sync_coarse ? 2 : 1) * n_fft * sizeof(float), hipMemcpyDeviceToHost, a));
-    CK(hipEventRecord(rx->sync_done, a));
+    DABGPU_CK(hipMemcpyAsync(rx->h_rec, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipMemcpyAsync(rx->h_rec + REC_HEAD, rx->d_imp, (rx->sync_coarse ? 2 : 1) * n_fft * sizeof(float), hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipEventRecord(rx->sync_done, a));
     rx->sync_pending = true;
     return DABGPU_OK;
 }
@@ -228,11 +226,11 @@ extern "C" int dabgpu_receiver_wait_sync(dabgpu_receiver* rx, dabgpu_sync_state*
     if (!rx->sync_pending) { dabgpu_set_error("receiver_wait_sync: no synchronisation was submitted"); return DABGPU_ERR_NOT_READY; }
     DABGPU_BIND(rx->ctx);
     int st;
-    CK(hipEventSynchronize(rx->sync_done));
+    DABGPU_CK(hipEventSynchronize(rx->sync_done));
     rx->sync_pending = false;
     *out = *reinterpret_cast<const dabgpu_sync_state*>(rx->h_rec);
     const float* h_imp = reinterpret_cast<const float*>(rx->h_rec + REC_HEAD);
-    const size_t n_fft = (size_t)rx->geom[3];
+    const size_t n_fft = (size_t)rx->g.n_fft;
     if (h_impulse) memcpy(h_impulse, h_imp, n_fft * sizeof(float));
     if (h_freq_response && rx->sync_coarse) memcpy(h_freq_response, h_imp + n_fft, n_fft * sizeof(float));
     return DABGPU_OK;
@@ -243,7 +241,7 @@ extern "C" int dabgpu_receiver_wait_sync(dabgpu_receiver* rx, dabgpu_sync_state*
 static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, uint64_t gen, int8_t* d_bits, dabgpu_frame_session::slot* sl);
 
 static int submit_demod(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, uint64_t* generation, dabgpu_frame_session::slot** slot_out) {
-    const size_t frame_samples = (size_t)rx->geom[6];
+    const size_t frame_samples = (size_t)rx->g.frame_samples;
     if (frame_sample + frame_samples > rx->stage_cap) { dabgpu_set_error("receiver_submit_frame: the frame lies outside the staging buffer"); return DABGPU_ERR_INVALID_ARG; }
     if (rx->sync_pending) { dabgpu_set_error("receiver_submit_frame: collect the synchroniser's record first (dabgpu_receiver_wait_sync)"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(rx->ctx);
@@ -261,57 +259,53 @@ static int submit_demod(dabgpu_receiver* rx, size_t frame_sample, float beta, in
 }
 
 static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, uint64_t /*gen*/, int8_t* d_bits, dabgpu_frame_session::slot* sl) {
-    const size_t frame_samples = (size_t)rx->geom[6], n_fft = (size_t)rx->geom[3], n_sym = (size_t)rx->geom[0], frame_bits = (size_t)rx->geom[8];
+    const size_t frame_samples = (size_t)rx->g.frame_samples, n_fft = (size_t)rx->g.n_fft, n_sym = (size_t)rx->g.n_sym, frame_bits = (size_t)rx->g.frame_bits;
     dabgpu_ctx* c = rx->ctx;
     DABGPU_BIND(c);
     hipStream_t a = rx->a;
     int st;
-    const size_t fft_bytes = (n_sym + 1) * n_fft * 2 * sizeof(float), dq_bytes = (n_sym - 1) * (size_t)rx->geom[5] * 2 * sizeof(float);
+    const size_t fft_bytes = (n_sym + 1) * n_fft * 2 * sizeof(float), dq_bytes = (n_sym - 1) * (size_t)rx->g.n_carriers * 2 * sizeof(float);
     const bool want_dq = want_views && rx->mode == 1;
     if (want_views) {
-        if (!rx->d_fft) CK(hipMalloc((void**)&rx->d_fft, fft_bytes));
-        if (want_dq && !rx->d_dq) CK(hipMalloc((void**)&rx->d_dq, dq_bytes));
+        if (!rx->d_fft) DABGPU_CK(hipMalloc((void**)&rx->d_fft, fft_bytes));
+        if (want_dq && !rx->d_dq) DABGPU_CK(hipMalloc((void**)&rx->d_dq, dq_bytes));
         if (sl->h_fft_cap < fft_bytes) {
             if (sl->h_fft) (void)hipHostFree(sl->h_fft);
             sl->h_fft = nullptr; sl->h_fft_cap = 0;
-            CK(hipHostMalloc((void**)&sl->h_fft, fft_bytes, hipHostMallocDefault));
+            DABGPU_CK(hipHostMalloc((void**)&sl->h_fft, fft_bytes, hipHostMallocDefault));
             sl->h_fft_cap = fft_bytes;
         }
         if (want_dq && sl->h_dq_cap < dq_bytes) {
             if (sl->h_dq) (void)hipHostFree(sl->h_dq);
             sl->h_dq = nullptr; sl->h_dq_cap = 0;
-            CK(hipHostMalloc((void**)&sl->h_dq, dq_bytes, hipHostMallocDefault));
+            DABGPU_CK(hipHostMalloc((void**)&sl->h_dq, dq_bytes, hipHostMallocDefault));
             sl->h_dq_cap = dq_bytes;
         }
     }
-    if (!sl->h_aux) CK(hipHostMalloc((void**)&sl->h_aux, REC_HEAD, hipHostMallocDefault));
-    if (!sl->h_bits) CK(hipHostMalloc((void**)&sl->h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault));
-    CK(hipMemcpyAsync(rx->d_iq, rx->h_stage[rx->cur] + 2 * frame_sample, frame_samples * 2 * sizeof(float), hipMemcpyHostToDevice, a));
-    CK(hipEventRecord(rx->stage_free[rx->cur], a));
+    if (!sl->h_aux) DABGPU_CK(hipHostMalloc((void**)&sl->h_aux, REC_HEAD, hipHostMallocDefault));
+    if (!sl->h_bits) DABGPU_CK(hipHostMalloc((void**)&sl->h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault));
+    DABGPU_CK(hipMemcpyAsync(rx->d_iq, rx->h_stage[rx->cur] + 2 * frame_sample, frame_samples * 2 * sizeof(float), hipMemcpyHostToDevice, a));
+    DABGPU_CK(hipEventRecord(rx->stage_free[rx->cur], a));
     rx->stage_pending[rx->cur] = true;
     rx_net_freq_kernel<<<1, 64, 0, a>>>(rx->d_state, rx->d_small);
-    CK(hipGetLastError());
+    DABGPU_CK(hipGetLastError());
     float* d_fine = &rx->d_state->freq_fine;
-    if (rx->mode == 1) {
-        if ((st = dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a))) return st;
-        if ((st = dabgpu_ofdm_phase_update(c, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
-    } else {
-        if ((st = dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, 0, a))) return st;
-        if ((st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
-    }
+    st = (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a)
+                         : dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, 0, a);
+    if (st || (st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
     // the decode may start; what the host reads of this frame -- soft bits, h_aux (the head of the device record: the frequency state after this frame's update, the sum of
     // the cyclic-prefix angles), the display views -- is copied on THIS stream beside it (the 230 KB of soft bits used to sit on the session's
     // stream in front of every trellis launch); the slot's done event waits for both
-    CK(hipEventRecord(sl->ev_ready, a));
-    CK(hipMemcpyAsync(sl->h_bits, d_bits, frame_bits, hipMemcpyDeviceToHost, a));
-    CK(hipMemcpyAsync(sl->h_aux, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
-    if (want_views) CK(hipMemcpyAsync(sl->h_fft, rx->d_fft, fft_bytes, hipMemcpyDeviceToHost, a));
-    if (want_dq) CK(hipMemcpyAsync(sl->h_dq, rx->d_dq, dq_bytes, hipMemcpyDeviceToHost, a));
-    CK(hipEventRecord(sl->ev_copied, a));
+    DABGPU_CK(hipEventRecord(sl->ev_ready, a));
+    DABGPU_CK(hipMemcpyAsync(sl->h_bits, d_bits, frame_bits, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipMemcpyAsync(sl->h_aux, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
+    if (want_views) DABGPU_CK(hipMemcpyAsync(sl->h_fft, rx->d_fft, fft_bytes, hipMemcpyDeviceToHost, a));
+    if (want_dq) DABGPU_CK(hipMemcpyAsync(sl->h_dq, rx->d_dq, dq_bytes, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipEventRecord(sl->ev_copied, a));
     // the next frame is assembled in the next staging buffer; its last upload (STAGES frames ago) has long finished
     rx->cur = (rx->cur + 1) % STAGES;
     if (rx->stage_pending[rx->cur]) {
-        CK(hipEventSynchronize(rx->stage_free[rx->cur]));
+        DABGPU_CK(hipEventSynchronize(rx->stage_free[rx->cur]));
         rx->stage_pending[rx->cur] = false;
     }
     return DABGPU_OK;
@@ -319,7 +313,7 @@ static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float
 
 // banked: post the frame, move on to the next staging buffer (waiting until the bank has uploaded what it still holds)
 static int submit_banked(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, int tie_rule, uint64_t* generation) {
-    const size_t frame_samples = (size_t)rx->geom[6];
+    const size_t frame_samples = (size_t)rx->g.frame_samples;
     if (frame_sample + frame_samples > rx->stage_cap) { dabgpu_set_error("receiver_submit_frame: the frame lies outside the staging buffer"); return DABGPU_ERR_INVALID_ARG; }
     if (dabgpu_rx_bank_sync_pending(rx->member)) { dabgpu_set_error("receiver_submit_frame: collect the synchroniser's record first (dabgpu_receiver_wait_sync)"); return DABGPU_ERR_INVALID_ARG; }
     int st = dabgpu_rx_bank_post_frame(rx->member, rx->cur, frame_sample, beta, want_views, tie_rule, generation);
@@ -397,7 +391,7 @@ extern "C" int dabgpu_receiver_wait_frame(dabgpu_receiver* rx, uint64_t generati
     { int st = dabgpu_check_hip(hipEventSynchronize(sl->ev_copied), "hipEventSynchronize(receiver copies)"); if (st) return st; }
     out->generation = generation;
     out->bits = sl->h_bits;
-    out->n_bits = (size_t)rx->geom[8];
+    out->n_bits = (size_t)rx->g.frame_bits;
     out->freq_fine = reinterpret_cast<const dabgpu_sync_state*>(sl->h_aux)->freq_fine;
     out->total_phase = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux) + REC_SMALL)[2];
     out->fft = sl->h_fft;

@@ -288,9 +288,8 @@ int enqueue_tick(dabgpu_rx_bank* b, rx_bank_tick& t, uint64_t tick_no) {
         BK(hipMemcpyAsync(b->d_prs + (size_t)lo * NFFT * 2, b->h_prs + (size_t)lo * NFFT * 2, (size_t)(up - lo + 1) * NFFT * 2 * sizeof(float), hipMemcpyHostToDevice, a));
         const dabgpu_sync_cfg& cfg = t.sync_jobs[0].cfg;
         const bool coarse = cfg.is_coarse_freq_correction != 0;
-        const float *d_prs_ref, *d_time_ref;
-        if ((st = dabgpu_mode_sync_tables(c, 1, &d_prs_ref, &d_time_ref))) return st;
-        BK(dabgpu_launch_sync(b->d_prs, NFFT, t.n_ens, &cfg, b->d_states, b->d_imp, coarse ? b->d_frq : nullptr, c->d_tw, d_prs_ref, d_time_ref, d_tab->sync_active, 1, a));
+        const dabgpu_mode_tables& mode1 = c->modes[1];
+        BK(dabgpu_launch_sync(b->d_prs, NFFT, t.n_ens, &cfg, b->d_states, b->d_imp, coarse ? b->d_frq : nullptr, c->d_tw, mode1.prs, mode1.prs_time_ref, d_tab->sync_active, 1, a));
         BK(hipMemcpyAsync(t.h_states, b->d_states, (size_t)t.n_ens * sizeof(dabgpu_sync_state), hipMemcpyDeviceToHost, a));
         BK(hipMemcpyAsync(t.h_imp, b->d_imp, (size_t)t.n_ens * NFFT * sizeof(float), hipMemcpyDeviceToHost, a));
         if (coarse) BK(hipMemcpyAsync(t.h_frq, b->d_frq, (size_t)t.n_ens * NFFT * sizeof(float), hipMemcpyDeviceToHost, a));

@@ -88,6 +88,36 @@ def test_mode_1_through_the_generic_kernel_equals_the_mode_1_kernel(ctx, oracle)
     assert all(np.array_equal(a, b) for a, b in zip(outs[0], outs[1]))
 
 
+def test_mode_1_through_the_generic_kernel_uses_the_contexts_carrier_mapper(ctx, oracle):
+    """a context created with its own carrier permutation: the generic kernel in mode I de-interleaves with that permutation, as the
+    mode I kernel does, not with the built-in one"""
+    import dabgpu
+    import torch
+    rng = np.random.default_rng(4)
+    own = dabgpu.Context(0, carrier_mapper=rng.permutation(oracle.NB_CARRIERS).astype(np.int32))
+    try:
+        n = 2
+        frames = np.stack([oracle.tx_to_frame_buffer(oracle.apply_pll(np.concatenate([oracle.modulate_frame(
+            rng.integers(0, 2, oracle.NB_FRAME_BITS, dtype=np.uint8))] * 2), 3e-4 * (k + 1), 0.0)) for k in range(n)])
+        d_iq = torch.view_as_real(torch.from_numpy(frames).cuda())
+        d_freq = torch.tensor([-3e-4, -6e-4], dtype=torch.float32, device="cuda")
+        outs = []
+        for c, generic in ((own, False), (own, True), (ctx, True)):
+            d_bits = torch.zeros((n, oracle.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
+            d_corr = torch.zeros((n, 76, 2), dtype=torch.float32, device="cuda")
+            d_fft = torch.zeros((n, 77, 2048, 2), dtype=torch.float32, device="cuda")
+            if generic:
+                c.ofdm_demod_frames_mode(1, d_iq, n, d_bits, freq_offset=d_freq, cp_corr=d_corr, fft=d_fft)
+            else:
+                c.ofdm_demod_frames(d_iq, d_bits, freq_offset=d_freq, cp_corr=d_corr, fft=d_fft, n_frames=n)
+            torch.cuda.synchronize()
+            outs.append(d_bits.cpu().numpy())
+        assert np.array_equal(outs[0], outs[1])
+        assert not np.array_equal(outs[1], outs[2]), "the permutation must change the soft-bit order"
+    finally:
+        own.close()
+
+
 def test_invalid_mode_is_rejected(ctx):
     import dabgpu
     import torch
