@@ -1,7 +1,9 @@
 // fake_dabgpu_oracle.cpp -- TEST INFRASTRUCTURE ONLY, never linked into the product: the entry points of include/dabgpu.h that the
 // C++ mirror classes call (dab-radio_amd/host/**), implemented on the CPU oracle (oracle/*.c), so that the classes' own host logic --
 // the framing state machine, the process-wide frame batcher with its per-demodulator sessions, the shared context, the decoders'
-// bookkeeping -- can run under ThreadSanitizer / AddressSanitizer on a machine without a GPU (tests/test_host_sanitizers.py).
+// bookkeeping -- can run under ThreadSanitizer / AddressSanitizer on a machine without a GPU (tests/test_host_sanitizers.py).  A banked receiver here
+// is a member of a bank that the PRODUCT's scheduler drives (dab-radio_amd/csrc/receiver_bank_sched.cpp, linked next to this file) over a
+// device half that computes a round on the oracle the moment it is enqueued (oracle_bank below).
 // Results are the oracle's, i.e. the ones the device produces (that equality is what the -m gpu tests establish); here only the
 // threading and memory behaviour of the host code is under test.
 #include <cstdlib>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "dabgpu.h"
+#include "receiver_bank_sched.h"
 extern "C" {
 #include "dab_oracle.h"
 }
@@ -231,7 +234,102 @@ struct dabgpu_receiver {
     std::mutex mu;                                       // result slots: written by the reader thread, read by the delivery thread
     struct Slot { uint64_t gen = ~0ull; std::vector<int8_t> bits; float fine = 0, total = 0; std::vector<float> fft, dq; } slots[8];
     uint64_t next = 0;
+    dabgpu_rx_member* member = nullptr;                  // a banked receiver: only the staging buffers above are its own
+    float* h_stage[3] = {nullptr, nullptr, nullptr};
 };
+static int frame_out(dabgpu_receiver::Slot& sl, uint64_t gen, dabgpu_receiver_frame* out) {
+    if (sl.gen != gen) return DABGPU_ERR_NOT_READY;
+    out->generation = gen; out->bits = sl.bits.data(); out->n_bits = sl.bits.size(); out->freq_fine = sl.fine; out->total_phase = sl.total;
+    out->fft = sl.fft.empty() ? nullptr : sl.fft.data(); out->dqpsk = sl.dq.empty() ? nullptr : sl.dq.data();
+    return DABGPU_OK;
+}
+// one frame with the receiver's frequency state, as dabgpu_receiver_submit_demod computes it (mode I)
+static int demod_into(dabgpu_ctx* ctx, const float* iq, dabgpu_sync_state& state, float beta, int want_views, dabgpu_receiver::Slot& sl) {
+    sl.bits.resize(DABGPU_NB_FRAME_BITS);
+    sl.fft.assign(want_views ? (size_t)(DABGPU_NB_FRAME_SYMBOLS + 1) * DABGPU_NB_FFT * 2 : 0, 0.0f);
+    sl.dq.assign(want_views ? (size_t)(DABGPU_NB_FRAME_SYMBOLS - 1) * DABGPU_NB_DATA_CARRIERS * 2 : 0, 0.0f);
+    sl.fine = state.freq_fine;
+    const int st = dabgpu_ofdm_demod_stream_frame_sync(ctx, iq, state.freq_coarse, &sl.fine, beta, sl.bits.data(), &sl.total, want_views ? sl.fft.data() : nullptr, nullptr);
+    if (!st) state.freq_fine = sl.fine;
+    return st;
+}
+
+}  // extern "C"
+// ---- the device half of a receiver bank on the oracle: enqueue computes, the waits return at once, delivery fills the members' result slots ----
+struct rx_member_device {
+    dabgpu_sync_state state = {0, 0, 0, 0, 0, 0};        // (the worker thread's: rounds are enqueued one at a time)
+    std::vector<float> iq[RX_BANK_SLOTS];                // "uploaded" frames by generation: every frame post_frame accepts keeps its samples until its round
+    std::mutex mu;                                       // result slots: written by the frames' completer, read by the member's delivery thread
+    dabgpu_receiver::Slot slots[RX_BANK_SLOTS];
+};
+static std::mutex g_hold_mu;                             // fake_dabgpu_bank_hold(1): rounds stay in enqueue, as behind a busy device (tests/cpp/bank_sched_driver.cpp)
+static std::condition_variable g_hold_cv;
+static bool g_hold = false;
+extern "C" void fake_dabgpu_bank_hold(int on) { { std::lock_guard<std::mutex> g(g_hold_mu); g_hold = on != 0; } g_hold_cv.notify_all(); }
+struct oracle_bank final : rx_bank_device {
+    dabgpu_ctx* ctx = nullptr;
+    std::vector<float> prs = std::vector<float>((size_t)DABGPU_RX_BANK_MAX * DABGPU_NB_FFT * 2);
+    struct Tick { std::vector<dabgpu_sync_state> rec; std::vector<std::vector<float>> imp, frq; std::vector<dabgpu_receiver::Slot> frames; } ticks[RX_BANK_TICKS];
+    oracle_bank() { dabgpu_create(&ctx, 0, nullptr, nullptr); }
+    ~oracle_bank() override { dabgpu_destroy(ctx); }
+    void bind_thread() override {}
+    int member_open(dabgpu_rx_member* m) override { m->dev = new rx_member_device(); return dabgpu_frame_session_create(&m->ses, 0); }
+    void member_close(dabgpu_rx_member* m) override { dabgpu_frame_session_destroy(m->ses); delete m->dev; }
+    float* prs_row(int slot) override { return prs.data() + (size_t)slot * DABGPU_NB_FFT * 2; }
+    int enqueue(const rx_bank_round& r) override {                            // the product's order: resets, frames, synchronisers behind them
+        Tick& t = ticks[r.no % RX_BANK_TICKS];
+        { std::unique_lock<std::mutex> g(g_hold_mu); g_hold_cv.wait(g, [] { return !g_hold; }); }
+        for (const auto& j : r.resets) j.m->dev->state = {0, 0, 0, 0, 0, 0};
+        t.frames.assign(r.frame_jobs.size(), dabgpu_receiver::Slot());
+        for (size_t j = 0; j < r.frame_jobs.size(); j++) {
+            const rx_bank_job& f = r.frame_jobs[j];
+            int st = demod_into(ctx, f.d_iq, f.m->dev->state, f.beta, f.want_views, t.frames[j]);
+            if (!st) st = dabgpu_frame_session_set_subchannels(f.m->ses, r.subs.data(), (int)r.subs.size());
+            uint64_t sgen = 0;
+            if (!st && (dabgpu_frame_session_push_frame(f.m->ses, t.frames[j].bits.data(), r.fic, f.tie, &sgen) || sgen != f.gen)) st = DABGPU_ERR_HIP;
+            if (st) return st;
+            t.frames[j].gen = f.gen;
+        }
+        const size_t nS = r.sync_jobs.size();
+        t.rec.resize(nS); t.imp.assign(nS, std::vector<float>(DABGPU_NB_FFT)); t.frq.assign(nS, std::vector<float>(DABGPU_NB_FFT));
+        for (size_t k = 0; k < nS; k++) {
+            const rx_bank_job& j = r.sync_jobs[k];
+            const int st = dabgpu_ofdm_sync_host_sync_mode(ctx, 1, prs_row(j.m->slot), &j.cfg, &j.m->dev->state, t.imp[k].data(), j.cfg.is_coarse_freq_correction ? t.frq[k].data() : nullptr);
+            if (st) return st;
+            t.rec[k] = j.m->dev->state;
+        }
+        return DABGPU_OK;
+    }
+    int wait_sync(const rx_bank_round&) override { return DABGPU_OK; }
+    void hand_sync(const rx_bank_round& r, size_t k) override {
+        Tick& t = ticks[r.no % RX_BANK_TICKS];
+        dabgpu_rx_member* m = r.sync_jobs[k].m;
+        m->sync_rec = t.rec[k]; m->sync_coarse = r.sync_jobs[k].cfg.is_coarse_freq_correction != 0;
+        m->sync_imp = t.imp[k]; if (m->sync_coarse) m->sync_frq = t.frq[k];
+    }
+    int wait_frames(const rx_bank_round&) override { return DABGPU_OK; }
+    int deliver_frame(const rx_bank_round& r, size_t j, int st) override {
+        const rx_bank_job& f = r.frame_jobs[j];
+        std::lock_guard<std::mutex> g(f.m->dev->mu);
+        f.m->dev->slots[f.gen % RX_BANK_SLOTS] = std::move(ticks[r.no % RX_BANK_TICKS].frames[j]);
+        return st;
+    }
+    int upload(dabgpu_rx_member* m, int stage, size_t frame_sample, uint64_t gen, int, const float** d_iq) override {
+        std::vector<float>& v = m->dev->iq[gen % RX_BANK_SLOTS];
+        v.assign(m->h_stage[stage] + 2 * frame_sample, m->h_stage[stage] + 2 * (frame_sample + DABGPU_NB_FRAME_SAMPLES));
+        *d_iq = v.data();
+        return DABGPU_OK;
+    }
+    int wait_stage(dabgpu_rx_member*, int) override { return DABGPU_OK; }
+    void drain_uploads() override {}
+    int fetch_frame(dabgpu_rx_member* m, uint64_t gen, dabgpu_receiver_frame* out) override {
+        std::lock_guard<std::mutex> g(m->dev->mu);
+        return frame_out(m->dev->slots[gen % RX_BANK_SLOTS], gen, out);
+    }
+};
+int dabgpu_rx_bank_device_open(int, rx_bank_device** out) { *out = new oracle_bank(); return DABGPU_OK; }
+extern "C" {
+
 int dabgpu_receiver_create(dabgpu_receiver** out, int, int mode, const float*, const int* h_mapper) {
     if (!out) return DABGPU_ERR_INVALID_ARG;
     dabgpu_receiver* rx = new dabgpu_receiver();
@@ -245,11 +343,28 @@ int dabgpu_receiver_create(dabgpu_receiver** out, int, int mode, const float*, c
     *out = rx;
     return DABGPU_OK;
 }
-int dabgpu_receiver_create_banked(dabgpu_receiver** out, int device) { return dabgpu_receiver_create(out, device, 1, nullptr, nullptr); }   // (no streams to share here)
-void dabgpu_receiver_destroy(dabgpu_receiver* rx) { if (!rx) return; dabgpu_frame_session_destroy(rx->ses); dabgpu_destroy(rx->ctx); delete rx; }
-dabgpu_frame_session* dabgpu_receiver_session(dabgpu_receiver* rx) { return rx ? rx->ses : nullptr; }
+// a member of the bank (csrc/receiver.hip: the staging buffers are the receiver's, the calls below post jobs)
+int dabgpu_receiver_create_banked(dabgpu_receiver** out, int device) {
+    if (!out) return DABGPU_ERR_INVALID_ARG;
+    dabgpu_receiver* rx = new dabgpu_receiver();
+    dab_ofdm_geometry_get(1, &rx->g);
+    const size_t cap = (size_t)rx->g.nb_null_period + (size_t)(rx->g.nb_fft - rx->g.nb_cp) + (size_t)rx->g.nb_frame_symbols * rx->g.nb_symbol_period + rx->g.nb_null_period;
+    for (int k = 0; k < 3; k++) { rx->stage[k].assign(2 * cap, 0.0f); rx->h_stage[k] = rx->stage[k].data(); }
+    const int st = dabgpu_rx_bank_join(device, rx->h_stage, &rx->member);
+    if (st) { delete rx; return st; }
+    *out = rx;
+    return DABGPU_OK;
+}
+void dabgpu_receiver_destroy(dabgpu_receiver* rx) {
+    if (!rx) return;
+    if (rx->member) dabgpu_rx_bank_leave(rx->member);
+    else { dabgpu_frame_session_destroy(rx->ses); dabgpu_destroy(rx->ctx); }
+    delete rx;
+}
+dabgpu_frame_session* dabgpu_receiver_session(dabgpu_receiver* rx) { return !rx ? nullptr : (rx->member ? dabgpu_rx_bank_session(rx->member) : rx->ses); }
 int dabgpu_receiver_set_subchannels(dabgpu_receiver* rx, const dabgpu_subchannel* subs, int n, int decode_fic) {
     if (!rx) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return dabgpu_rx_bank_set_subchannels(rx->member, subs, n, decode_fic);
     const int st = dabgpu_frame_session_set_subchannels(rx->ses, subs, n);
     if (st) return st;
     rx->decode_fic = decode_fic;
@@ -261,8 +376,14 @@ int dabgpu_receiver_stage(dabgpu_receiver* rx, float** h, size_t* cap) {
     if (cap) *cap = rx->stage[rx->cur].size() / 2;
     return DABGPU_OK;
 }
-int dabgpu_receiver_reset(dabgpu_receiver* rx) { if (!rx) return DABGPU_ERR_INVALID_ARG; rx->state = {0, 0, 0, 0, 0, 0}; return DABGPU_OK; }
+int dabgpu_receiver_reset(dabgpu_receiver* rx) {
+    if (!rx) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return dabgpu_rx_bank_reset(rx->member);
+    rx->state = {0, 0, 0, 0, 0, 0};
+    return DABGPU_OK;
+}
 int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_sync_cfg* cfg, size_t prs_sample) {
+    if (rx && cfg && rx->member) return dabgpu_rx_bank_post_sync(rx->member, cfg, rx->cur, prs_sample);
     if (!rx || !cfg || rx->sync_pending) return DABGPU_ERR_INVALID_ARG;
     rx->sync_coarse = cfg->is_coarse_freq_correction != 0;
     const int st = dabgpu_ofdm_sync_host_sync_mode(rx->ctx, rx->mode, rx->stage[rx->cur].data() + 2 * prs_sample, cfg, &rx->state, rx->imp.data(),
@@ -273,6 +394,7 @@ int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_sync_cfg* cfg,
 }
 int dabgpu_receiver_wait_sync(dabgpu_receiver* rx, dabgpu_sync_state* out, float* imp, float* frq) {
     if (!rx || !out) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return dabgpu_rx_bank_wait_sync(rx->member, out, imp, frq);
     if (!rx->sync_pending) return DABGPU_ERR_NOT_READY;
     rx->sync_pending = false;
     *out = rx->record;
@@ -282,6 +404,7 @@ int dabgpu_receiver_wait_sync(dabgpu_receiver* rx, dabgpu_sync_state* out, float
 }
 int dabgpu_receiver_submit_demod(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, uint64_t* generation) {
     if (!rx || rx->sync_pending) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return DABGPU_ERR_UNSUPPORTED;       // (a banked receiver takes dabgpu_receiver_submit_frame, csrc/receiver.hip)
     const size_t n_bits = (size_t)(rx->g.nb_frame_symbols - 1) * 2 * rx->g.nb_carriers;
     std::vector<int8_t> bits(n_bits);
     std::vector<float> fft(want_views ? (size_t)(rx->g.nb_frame_symbols + 1) * rx->g.nb_fft * 2 : 0);
@@ -307,6 +430,7 @@ int dabgpu_receiver_submit_demod(dabgpu_receiver* rx, size_t frame_sample, float
 // the decode of a demodulated frame: the frame session's push (its generations count the same frames)
 int dabgpu_receiver_submit_decode(dabgpu_receiver* rx, uint64_t gen, int tie) {
     if (!rx) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return DABGPU_ERR_UNSUPPORTED;
     if (rx->mode != 1) return DABGPU_OK;
     std::vector<int8_t> bits;
     { std::lock_guard<std::mutex> g(rx->mu); if (rx->slots[gen % 8].gen != gen) return DABGPU_ERR_NOT_READY; bits = rx->slots[gen % 8].bits; }
@@ -315,6 +439,13 @@ int dabgpu_receiver_submit_decode(dabgpu_receiver* rx, uint64_t gen, int tie) {
     return DABGPU_OK;
 }
 int dabgpu_receiver_submit_frame(dabgpu_receiver* rx, size_t frame_sample, float beta, int want_views, int tie, uint64_t* generation) {
+    if (rx && rx->member) {                              // post the frame, move on to the next staging buffer (submit_banked, csrc/receiver.hip)
+        if (dabgpu_rx_bank_sync_pending(rx->member)) return DABGPU_ERR_INVALID_ARG;
+        const int st = dabgpu_rx_bank_post_frame(rx->member, rx->cur, frame_sample, beta, want_views, tie, generation);
+        if (st) return st;
+        rx->cur = (rx->cur + 1) % 3;
+        return dabgpu_rx_bank_wait_stage(rx->member, rx->cur);
+    }
     uint64_t gen = 0;
     int st = dabgpu_receiver_submit_demod(rx, frame_sample, beta, want_views, &gen);
     if (!st) st = dabgpu_receiver_submit_decode(rx, gen, tie);
@@ -323,12 +454,9 @@ int dabgpu_receiver_submit_frame(dabgpu_receiver* rx, size_t frame_sample, float
 }
 int dabgpu_receiver_wait_frame(dabgpu_receiver* rx, uint64_t gen, dabgpu_receiver_frame* out) {
     if (!rx || !out) return DABGPU_ERR_INVALID_ARG;
+    if (rx->member) return dabgpu_rx_bank_wait_frame(rx->member, gen, out);
     std::lock_guard<std::mutex> g(rx->mu);
-    auto& sl = rx->slots[gen % 8];
-    if (sl.gen != gen) return DABGPU_ERR_NOT_READY;
-    out->generation = gen; out->bits = sl.bits.data(); out->n_bits = sl.bits.size(); out->freq_fine = sl.fine; out->total_phase = sl.total;
-    out->fft = sl.fft.empty() ? nullptr : sl.fft.data(); out->dqpsk = sl.dq.empty() ? nullptr : sl.dq.data();
-    return DABGPU_OK;
+    return frame_out(rx->slots[gen % 8], gen, out);
 }
 
 }  // extern "C"

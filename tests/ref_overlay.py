@@ -80,7 +80,8 @@ class Overlay:
 
     def oracle_backend_objects(self):
         return [self.compile(os.path.join(ORACLE, s)) for s in ORACLE_SRCS] + \
-               [self.compile(os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"), opt="-O2"), self.compile(os.path.join(CSRC, "dabgpu_host_logic.cpp"), opt="-O2")]
+               [self.compile(os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"), opt="-O2"), self.compile(os.path.join(CSRC, "dabgpu_host_logic.cpp"), opt="-O2"),
+                self.compile(os.path.join(CSRC, "receiver_bank_sched.cpp"), opt="-O2")]
 
     def link(self, objs, name, backend="oracle"):
         exe = os.path.join(self.dir, name)

@@ -100,6 +100,6 @@ def test_replay_on_the_oracle_backed_abi(replay, tmp_path):
     exe = d / "mirror_lifecycle_fake"
     subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + T.HOST, "-I" + os.path.join(ROOT, "include"), "-I" + T.CSRC, "-I" + T.ORACLE,
                     os.path.join(ROOT, "tests", "cpp", "mirror_lifecycle_driver.cpp"), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
-                    os.path.join(T.CSRC, "dabgpu_host_logic.cpp")] + [os.path.join(T.HOST, s) for s in T.MIRROR_SRCS] + objs + ["-lm", "-o", str(exe)],
+                    os.path.join(T.CSRC, "dabgpu_host_logic.cpp"), os.path.join(T.CSRC, "receiver_bank_sched.cpp")] + [os.path.join(T.HOST, s) for s in T.MIRROR_SRCS] + objs + ["-lm", "-o", str(exe)],
                    check=True, timeout=900)
     run_replay(str(exe), replay, tmp_path / "out", dict(DABGPU_MIRROR_BATCH="1", DABGPU_MIRROR_DEPTH="3"))

@@ -9,7 +9,10 @@ AddressSanitizer preset, CMakePresets.json:47-53):
  (c) the C++ MIRROR CLASSES' host code (framing state machine, frame batcher with one session per demodulator, shared context,
      decoders) under ThreadSanitizer and under ASan + UBSan, two receivers in one process with reader / radio / worker threads
      (tests/cpp/mirror_threads_driver.cpp), linked against a TEST-ONLY implementation of the C ABI entry points on the oracle
-     (tests/cpp/fake_dabgpu_oracle.cpp -- under tests/, never part of the product)."""
+     (tests/cpp/fake_dabgpu_oracle.cpp -- under tests/, never part of the product);
+ (d) the RECEIVER BANK'S SCHEDULER (dab-radio_amd/csrc/receiver_bank_sched.cpp: job queue, worker and completer threads, round formation, join / leave /
+     shutdown), the product's file compiled into the same executables and run over the fake's oracle-backed device half: eight banked receivers behind
+     the classes, a backlog of posted frames and join / leave churn through the C entry points (tests/cpp/bank_sched_driver.cpp)."""
 import json
 import os
 import subprocess
@@ -66,18 +69,19 @@ MIRROR_SRCS = ["ofdm/ofdm_demodulator.cpp", "ofdm/dab_refs.cpp", "dab/dabgpu_sha
 ORACLE_SRCS = ["dab_oracle_ofdm.c", "dab_oracle_decode.c", "dab_oracle_io.c", "dab_oracle_dabplus.c", "dab_oracle_chain.c"]
 
 
-def build_driver(tmp_path, tag, san_flags):
+def build_driver(tmp_path, tag, san_flags, driver="mirror_threads_driver.cpp", mirror=True):
     """mirror classes + device-free library code + the fake ABI + the oracle, everything instrumented, into one executable"""
     objs = []
     for src in ORACLE_SRCS:
         o = tmp_path / f"{tag}_{src}.o"
         run(["gcc", "-O1", "-g", "-std=gnu11", "-ffp-contract=off", "-fno-fast-math", "-w", "-DDAB_ORACLE_NO_CLONES"] + san_flags + ["-c", os.path.join(ORACLE, src), "-o", str(o)], timeout=600)
         objs.append(str(o))
-    exe = tmp_path / f"mirror_threads_{tag}"
+    exe = tmp_path / f"{driver.split('.')[0]}_{tag}"
     run(["g++", "-O1", "-g", "-std=c++17", "-pthread"] + san_flags +
         ["-I" + HOST, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + ORACLE,
-         os.path.join(ROOT, "tests", "cpp", "mirror_threads_driver.cpp"), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
-         os.path.join(CSRC, "dabgpu_host_logic.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS] + objs + ["-lm", "-o", str(exe)], timeout=900)
+         os.path.join(ROOT, "tests", "cpp", driver), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
+         os.path.join(CSRC, "dabgpu_host_logic.cpp"), os.path.join(CSRC, "receiver_bank_sched.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS if mirror] + objs +
+        ["-lm", "-o", str(exe)], timeout=900)
     return exe
 
 
@@ -98,11 +102,14 @@ def two_receiver_streams(tmp_path_factory):
     return subs, paths
 
 
-@pytest.mark.parametrize("tag,flags,env", [
+SANITIZERS = [
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"}),
     ("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"],
      {"ASAN_OPTIONS": "abort_on_error=1:detect_leaks=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"}),
-])
+]
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
 def test_mirror_classes_with_two_receivers_and_decoder_threads(tmp_path, two_receiver_streams, tag, flags, env):
     lib_of("libtsan.so" if tag == "tsan" else "libasan.so")
     subs, paths = two_receiver_streams
@@ -118,6 +125,57 @@ def test_mirror_classes_with_two_receivers_and_decoder_threads(tmp_path, two_rec
         # logical frames from the 16th CIF on -- through the batcher's sessions where the decoders had caught up with them
         assert r["frames"] >= 5 and r["fib_bytes"] >= 30 * 12 * (r["frames"] - 2) and r["cifs_with_output"] >= 2 * (4 * r["frames"] - 15) and r["threaded_equals_serial"]
     assert out["per_receiver"][0]["digest"] != out["per_receiver"][1]["digest"]
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
+def test_eight_banked_receivers_equal_private_ones_under_sanitizers(tmp_path, two_receiver_streams, tag, flags, env):
+    """DABGPU_MIRROR_BANK=1: every OFDM_Demod of the driver is a member of one receiver bank, whose scheduler is the product's (receiver_bank_sched.cpp) over
+    the fake's oracle-backed device half.  Eight receivers (the two captures round-robin); the process ends through dabgpu_rx_bank_shutdown (atexit)."""
+    lib_of("libtsan.so" if tag == "tsan" else "libasan.so")
+    subs, paths = two_receiver_streams
+    exe = build_driver(tmp_path, tag, flags)
+    args = [str(exe), "65536"]
+    for s in subs:
+        args += [str(s.start_address), str(s.length), str(s.eep_prot_level), str(s.eep_type)]
+    outs = {}
+    for bank, captures in (("0", paths), ("1", [paths[k % 2] for k in range(8)])):
+        res = run(args + ["--"] + captures, env=dict(os.environ, DABGPU_MIRROR_BANK=bank, DABGPU_BANK_PROFILE="1", **env), timeout=1200)
+        assert "ThreadSanitizer" not in res.stderr and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
+        # (the shutdown line of DABGPU_BANK_PROFILE: the bank existed, ran rounds and was shut down -- in the banked process only)
+        assert ("receiver bank (device 0):" in res.stderr) == (bank == "1"), res.stderr[-2000:]
+        outs[bank] = json.loads(res.stdout.strip().splitlines()[-1])
+        assert outs[bank]["ok"] and outs[bank]["receivers"] == len(captures)
+        for r in outs[bank]["per_receiver"]:
+            assert r["frames"] >= 5 and r["fib_bytes"] >= 30 * 12 * (r["frames"] - 2) and r["cifs_with_output"] >= 2 * (4 * r["frames"] - 15) and r["threaded_equals_serial"]
+    private = [r["digest"] for r in outs["0"]["per_receiver"]]
+    assert private[0] != private[1]
+    assert [r["digest"] for r in outs["1"]["per_receiver"]] == [private[k % 2] for k in range(8)]
+
+
+def bank_driver(tmp_path, case, tag, flags, env):
+    lib_of("libtsan.so" if tag == "tsan" else "libasan.so")
+    import oracle as O
+    O.build()
+    exe = build_driver(tmp_path, tag, flags, driver="bank_sched_driver.cpp", mirror=False)
+    res = run([str(exe), case], env=dict(os.environ, **env), timeout=1200)
+    assert "ThreadSanitizer" not in res.stderr and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
+    return json.loads(res.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
+def test_bank_member_posts_frames_back_to_back_without_a_sync_in_between(tmp_path, tag, flags, env):
+    """A member posts a synchroniser, collects it, then -- while no round completes -- as many frames as post_frame accepts, and one more: 7 = R - 1 are
+    accepted (next_gen >= done_gen + R - 1 refuses), the eighth returns DABGPU_ERR_NOT_READY (4), and the seven generations come back from wait_frame in
+    order, each with the bits a private receiver computes for the same samples."""
+    out = bank_driver(tmp_path, "backlog", tag, flags, env)
+    assert out["accepted"] == 7 and out["one_more"] == 4 and out["in_order_with_own_bits"] and out["frames_distinct"] and out["ok"], out
+
+
+def test_bank_join_leave_churn_under_thread_sanitizer(tmp_path):
+    """8 threads each join the bank, run two frames (results checked against a private receiver's) and leave, 20 times, while the others keep running;
+    afterwards the bank's slot table is empty and its reference count 0."""
+    out = bank_driver(tmp_path, "churn", *SANITIZERS[0])
+    assert out == {"threads": 8, "joins": 160, "wrong_results": 0, "members_left": 0, "refs": 0, "ok": True}, out
 
 
 def test_decoders_created_and_dropped_on_the_delivery_thread_under_thread_sanitizer(tmp_path):
@@ -144,7 +202,7 @@ def test_decoders_created_and_dropped_on_the_delivery_thread_under_thread_saniti
     exe = tmp_path / "mirror_lifecycle_tsan"
     run(["g++", "-O1", "-g", "-std=c++17", "-pthread"] + san + ["-I" + HOST, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + ORACLE,
          os.path.join(ROOT, "tests", "cpp", "mirror_lifecycle_driver.cpp"), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
-         os.path.join(CSRC, "dabgpu_host_logic.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS + ["dab/msc/cif_deinterleaver.cpp", "dab/algorithms/dab_viterbi_decoder.cpp"]] +
+         os.path.join(CSRC, "dabgpu_host_logic.cpp"), os.path.join(CSRC, "receiver_bank_sched.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS + ["dab/msc/cif_deinterleaver.cpp", "dab/algorithms/dab_viterbi_decoder.cpp"]] +
         objs + ["-lm", "-o", str(exe)], timeout=900)
     out = tmp_path / "out"
     out.mkdir()

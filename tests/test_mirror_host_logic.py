@@ -33,7 +33,7 @@ def harness(tmp_path_factory):
     exe = d / "mirror_harness_fake"
     subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + HOST, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + ORACLE,
                     os.path.join(ROOT, "tests", "cpp", "mirror_harness.cpp"), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
-                    os.path.join(CSRC, "dabgpu_host_logic.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS] + objs + ["-lm", "-o", str(exe)],
+                    os.path.join(CSRC, "dabgpu_host_logic.cpp"), os.path.join(CSRC, "receiver_bank_sched.cpp")] + [os.path.join(HOST, s) for s in MIRROR_SRCS] + objs + ["-lm", "-o", str(exe)],
                    check=True, timeout=900)
     return str(exe)
 

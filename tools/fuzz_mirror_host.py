@@ -23,7 +23,7 @@ for src in T.ORACLE_SRCS:
 EXE = os.path.join(W, "mirror_harness_fake")
 subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + T.HOST, "-I" + os.path.join(ROOT, "include"), "-I" + T.CSRC, "-I" + T.ORACLE,
                 os.path.join(ROOT, "tests", "cpp", "mirror_harness.cpp"), os.path.join(ROOT, "tests", "cpp", "fake_dabgpu_oracle.cpp"),
-                os.path.join(T.CSRC, "dabgpu_host_logic.cpp")] + [os.path.join(T.HOST, s) for s in T.MIRROR_SRCS] + objs + ["-lm", "-o", EXE], check=True)
+                os.path.join(T.CSRC, "dabgpu_host_logic.cpp"), os.path.join(T.CSRC, "receiver_bank_sched.cpp")] + [os.path.join(T.HOST, s) for s in T.MIRROR_SRCS] + objs + ["-lm", "-o", EXE], check=True)
 subs = [O.subchannel(0, 48, eep_level=2, eep_type=0)]
 caps = {}
 for name, c in {"a": dict(n_frames=24, seed=11, dropouts=((5, -0.03, 14000), (12, -0.03, 60000), (17, 0.2, 30000))),
