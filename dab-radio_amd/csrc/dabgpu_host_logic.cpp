@@ -242,6 +242,15 @@ void dabgpu_host_fill_vit_tables(dabgpu_vit_tables* T) {
     }
 }
 
+// DABGPU_VIT_MAP_AUTO: a cost model of the three mappings on this part (profiles/r01/ab_notes.md, profiles/r03/ab_notes.md; microseconds).
+//   WAVE   one wavefront per codeword keeps every SIMD busy: t = sum over codewords of (0.0189 ns x steps + 0.038 us)
+//   LANE   a group of 64 codewords is one wavefront that needs 0.5 us per trellis step however many of its lanes are used, and
+//          a SIMD works through its groups at that same rate: t = 0.5 us x max(longest schedule, rounds x mean steps) with
+//          rounds = ceil(groups / SIMDs), + the gather pass (3.3e-3 / 8.5e-3 us per codeword-kilostep, staged / byte-wise)
+//   OCTET  a group is 8 wavefronts of ~57 instructions per step; two of them share a SIMD at 4 cycles per instruction (a lone one
+//          issues at half rate, so one costs what two cost): t = 0.095 us x max(2 x longest schedule, rounds8 x mean steps) with
+//          rounds8 = ceil(8 groups / SIMDs), + the same gather pass
+// n_cw codewords in n_groups groups; sums and maximum of their trellis steps.  Returns DABGPU_VIT_MAP_WAVE / _LANE / _OCTET
 int dabgpu_host_choose_mapping(int forced_mapping, double n_simd, size_t n_cw, size_t n_groups, double sum_cw_steps, double sum_group_steps, double max_steps,
                           bool staged_gather) {
     if (forced_mapping != DABGPU_VIT_MAP_AUTO) return forced_mapping;
@@ -354,6 +363,123 @@ int dabgpu_host_build_msc_plans(const dabgpu_subchannel* h_sub, int n_sub, std::
     if (max_steps_out) *max_steps_out = max_steps;
     if (max_out_bytes) *max_out_bytes = max_out;
     return DABGPU_OK;
+}
+
+// ---- decode planner ----
+static size_t mul_sat(size_t a, size_t b) { size_t r; return __builtin_mul_overflow(a, b, &r) ? SIZE_MAX : r; }
+static size_t add_sat(size_t a, size_t b) { size_t r; return __builtin_add_overflow(a, b, &r) ? SIZE_MAX : r; }
+
+dabgpu_uniform_plan dabgpu_host_plan_uniform(size_t n_cw, uint32_t n_steps, const uint32_t* seg_pi, const uint32_t* seg_steps, bool staged_gather,
+                                             const dabgpu_decode_limits& lim) {
+    dabgpu_uniform_plan u;
+    const size_t n_groups = n_cw / 64 + (n_cw % 64 != 0);
+    u.mapping = dabgpu_host_choose_mapping(lim.forced_mapping, lim.n_simd, n_cw, n_groups, (double)n_cw * n_steps, (double)n_groups * n_steps,
+                                           (double)n_steps, staged_gather);
+    u.dec_rows = dabgpu_vit_alloc_steps(n_steps);
+    u.in_rows = dabgpu_vit_in_rows(dabgpu_vit_in_bytes(seg_pi, seg_steps));
+    u.slice_groups = std::max<size_t>(1, lim.max_dec_rows / u.dec_rows);
+    return u;
+}
+
+// Which sub-channels go to the lane-per-codeword kernel?  The k longest can be left to viterbi_kernel and the rest given to vit_lanes_kernel in
+// the same call; AUTO only compares the pure choices k = 0 and k = n_sub -- a partial viterbi_kernel launch is a single lockstep round of
+// wavefronts and measured 2x its share of a full one, so hybrids did not pay (hybrid_k forces one, for the tests).  The lane mapping keeps
+// ring offsets in 32 bits: one ensemble's ring must stay below 4 GiB.  Fills mapping, model_us, k_wave, n_lane, octet and order[n_sub]
+// (sub-channels by descending trellis length).
+static void choose_lane_subchannels(dabgpu_decode_plan& p, int hist_frames, const dabgpu_decode_limits& lim, int* order) {
+    const int n_sub = p.n_sub;
+    uint32_t steps[64];
+    for (int j = 0; j < n_sub; j++) { order[j] = j; steps[j] = p.subs[(size_t)j].n_steps; }
+    std::sort(order, order + n_sub, [&](int a, int b) { return steps[a] > steps[b]; });
+    const int m = dabgpu_host_choose_msc_mapping(lim.forced_mapping, lim.n_simd, p.n_ens, steps, n_sub, p.model_us);
+    const bool lanes_allowed = (uint64_t)hist_frames * DABGPU_NB_FRAME_BITS < ((uint64_t)1 << 32) && lim.forced_mapping != DABGPU_VIT_MAP_WAVE;
+    p.mapping = lanes_allowed ? m : DABGPU_VIT_MAP_WAVE;
+    p.k_wave = p.mapping == DABGPU_VIT_MAP_WAVE ? n_sub : 0;
+    p.octet = p.mapping == DABGPU_VIT_MAP_OCTET;
+    if (lanes_allowed && lim.forced_mapping == DABGPU_VIT_MAP_AUTO && lim.hybrid_k >= 0 && lim.hybrid_k <= n_sub) p.k_wave = lim.hybrid_k;
+    p.n_lane = n_sub - p.k_wave;
+    for (int j = p.k_wave; j < n_sub; j++) p.subs[(size_t)order[j]].lane_mapped = 1;
+}
+
+// the lane table (sub-channel, decision rows before it, symbol rows before it) and what follows from it: rows per group quartet (16
+// ensembles x 4 CIFs = one group per lane-mapped sub-channel), ensembles per slice, the schedule tables' stride
+static void lay_out_lanes(dabgpu_decode_plan& p, const int* order, const dabgpu_decode_limits& lim) {
+    p.lane_subs.assign((size_t)3 * p.n_lane, 0);
+    for (int j = 0; j < p.n_lane; j++) {
+        const int sidx = order[p.k_wave + j];
+        const dabgpu_msc_plan& P = p.subs[(size_t)sidx];
+        const uint32_t in_rows = dabgpu_vit_in_rows(dabgpu_vit_in_bytes(P.seg_pi, P.seg_steps));
+        p.lane_subs[(size_t)3 * j] = (uint64_t)sidx;
+        p.lane_subs[(size_t)3 * j + 1] = p.dec_rows_per_gq;
+        p.lane_subs[(size_t)3 * j + 2] = p.sym_rows_per_gq;
+        p.dec_rows_per_gq += dabgpu_vit_alloc_steps(P.n_steps);
+        p.sym_rows_per_gq += in_rows;
+        p.lane_max_steps = std::max(p.lane_max_steps, P.n_steps);
+        p.lane_max_in_rows = std::max(p.lane_max_in_rows, in_rows);
+    }
+    if (p.n_lane == 0) return;
+    p.ens_per_slice = mul_sat(std::max<size_t>(1, lim.max_dec_rows / p.dec_rows_per_gq), 16);
+    p.sched_stride = dabgpu_vit_alloc_steps(p.lane_max_steps);
+}
+
+// Where the FIC of the newest frames is decoded.  Inside the lane launch when every sub-channel is lane-mapped and the call is one slice
+// with the FIB groups' rows counted in (16 ensembles = 64 FIB groups = one more group of codewords in the launch's scratch): the MSC's
+// groups rarely fill the last round of wavefront slots (4096 ensembles x 18 sub-channels = 4608 groups on 5120 slots), so the FIC then costs
+// its 20 us gather and nothing else.  In viterbi_kernel's launch when every sub-channel is there and the FIC alone would be too (a handful
+// of ensembles: one receiver behind the classes is 4 + 72 codewords, and the two launches used to run one after the other on the stream,
+// 109 + 213 us, for work that is independent).  Otherwise first, by the FIC entry point's own path.
+static dabgpu_fic_place place_fic(const dabgpu_decode_plan& p, const dabgpu_decode_limits& lim) {
+    if (p.k_wave == 0 && p.n_lane > 0 && p.n_cw <= UINT32_MAX &&
+        p.n_ens <= mul_sat(std::max<size_t>(1, lim.max_dec_rows / (p.dec_rows_per_gq + p.fic_dec_rows)), 16))
+        return DABGPU_FIC_IN_LANES;
+    if (p.k_wave == p.n_sub && dabgpu_host_plan_fic(p.n_fic_cw, true, lim).mapping == DABGPU_VIT_MAP_WAVE) return DABGPU_FIC_IN_WAVE;
+    return DABGPU_FIC_OWN_LAUNCH;
+}
+
+int dabgpu_host_plan_decode(const dabgpu_subchannel* subs, int n_sub, size_t n_ens, int hist_frames, bool want_fic, const dabgpu_decode_limits& lim,
+                            dabgpu_decode_plan* out) {
+    dabgpu_decode_plan& p = *out;
+    p = dabgpu_decode_plan{};
+    const int st = dabgpu_host_build_msc_plans(subs, n_sub, p.subs, &p.cif_out_bytes, &p.max_steps, &p.max_out_bytes);
+    if (st) return st;
+    const dabgpu_uniform_plan fic_group = dabgpu_host_plan_fic(0, true, lim);
+    p.n_sub = n_sub; p.n_ens = n_ens;
+    p.n_cw = mul_sat(mul_sat(n_ens, 4), (size_t)n_sub);
+    p.fic_dec_rows = fic_group.dec_rows; p.fic_in_rows = fic_group.in_rows;
+    int order[64];
+    choose_lane_subchannels(p, hist_frames, lim, order);
+    lay_out_lanes(p, order, lim);
+    if (want_fic) {
+        p.n_fic_cw = mul_sat(n_ens, 4);
+        p.fic = place_fic(p, lim);
+    }
+    if (p.fic == DABGPU_FIC_IN_WAVE) { p.max_steps = std::max(p.max_steps, DABGPU_FIC_STEPS); p.max_out_bytes = std::max(p.max_out_bytes, DABGPU_FIC_OUT_BYTES); }
+    p.descs_bytes = mul_sat(add_sat(p.n_cw, p.n_fic_cw), sizeof(dabgpu_codeword));
+    p.plans_bytes = p.subs.size() * sizeof(dabgpu_msc_plan);
+    p.lane_subs_bytes = p.lane_subs.size() * sizeof(uint64_t);
+    p.sched_bytes = ((size_t)p.n_lane * p.sched_stride + (p.fic == DABGPU_FIC_IN_LANES ? p.fic_dec_rows : 0)) * 2 * sizeof(uint32_t);
+    return DABGPU_OK;
+}
+
+dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t e0) {
+    dabgpu_decode_slice s = {};
+    s.ne = std::min(p.n_ens - e0, p.ens_per_slice);
+    s.cw0 = mul_sat(mul_sat(e0, 4), (size_t)p.n_sub);
+    s.gps = (uint32_t)((s.ne * 4 + 63) / 64);
+    s.n_groups = (size_t)p.n_lane * s.gps;
+    s.sym_rows = p.sym_rows_per_gq * s.gps;
+    s.dec_rows = p.dec_rows_per_gq * s.gps;
+    if (p.fic == DABGPU_FIC_IN_LANES) {         // one slice (e0 = 0): descriptors n_cw .., schedule, symbol and decision areas behind the MSC's
+        s.n_fic_groups = (p.n_fic_cw + 63) / 64;
+        s.fic_base.first = (uint32_t)p.n_cw;
+        s.fic_base.sched_off = (uint64_t)p.n_lane * p.sched_stride;
+        s.fic_base.sym_off = (uint64_t)s.sym_rows * 64;
+        s.fic_base.dec_off = (uint64_t)s.dec_rows * 128;
+        s.sym_rows += s.n_fic_groups * p.fic_in_rows;
+        s.dec_rows += s.n_fic_groups * p.fic_dec_rows;
+    }
+    s.groups_bytes = (s.n_groups + s.n_fic_groups) * sizeof(dabgpu_vit_group);
+    return s;
 }
 
 extern "C" {

@@ -68,6 +68,23 @@ DABGPU_HD static inline uint32_t dabgpu_vit_in_bytes(const uint32_t* seg_pi, con
 // symbol rows: 4 kept soft bits per row, + the row the last step's two-row window reaches into + one the prefetch may touch
 DABGPU_HD static inline uint32_t dabgpu_vit_in_rows(uint32_t n_in) { return (n_in + 3u) / 4u + 2u; }
 
+// a codeword's puncturing from "segments + tail": PI only where a segment has steps, n_steps = sum + the 6 tail steps
+DABGPU_HD static inline void dabgpu_cw_set_segments(dabgpu_codeword* D, const uint32_t* seg_pi, const uint32_t* seg_steps) {
+    D->n_steps = 6;
+    for (int k = 0; k < 4; k++) { D->seg_pi[k] = seg_steps[k] ? seg_pi[k] : 0u; D->seg_steps[k] = seg_steps[k]; D->n_steps += seg_steps[k]; }
+}
+// the FIB group's codeword (fic_decoder.cpp:53-84): PI_16 x 21 blocks, PI_15 x 3 blocks, tail; 3 FIBs of 32 bytes with a CRC each
+#define DABGPU_FIC_STEPS 774u
+#define DABGPU_FIC_SEG_PI {16u, 15u, 0u, 0u}
+#define DABGPU_FIC_SEG_STEPS {32u * 21u, 32u * 3u, 0u, 0u}
+#define DABGPU_FIC_OUT_BYTES 96u
+#define DABGPU_FIC_CRC_BLOCKS 3u
+DABGPU_HD static inline void dabgpu_cw_set_fic(dabgpu_codeword* D) {
+    const uint32_t pi[4] = DABGPU_FIC_SEG_PI, steps[4] = DABGPU_FIC_SEG_STEPS;
+    dabgpu_cw_set_segments(D, pi, steps);
+    D->n_crc_blocks = DABGPU_FIC_CRC_BLOCKS;
+}
+
 // symbols_per_block = 0 of the mode I demodulator
 int dabgpu_host_small_batch_spb(size_t n_frames);
 int dabgpu_host_spb_bucket(size_t n_frames);
@@ -85,3 +102,81 @@ int dabgpu_host_choose_msc_mapping(int forced_mapping, double n_simd, size_t n_e
 int dabgpu_host_build_msc_plans(const dabgpu_subchannel* subs, int n_sub, std::vector<dabgpu_msc_plan>& plans, uint32_t* cif_out_bytes,
                                 uint32_t* max_steps, uint32_t* max_out_bytes);
 void dabgpu_host_fill_vit_tables(dabgpu_vit_tables* T);
+
+// ---- decode planner: what a batch decode call will launch, from its arguments alone (no device address enters) ----
+// what the planner may not decide for itself: the device, the environment (read once per entry-point call), the context's setting
+struct dabgpu_decode_limits {
+    double n_simd;              // SIMDs of the device (cost model)
+    size_t max_dec_rows;        // decision rows one lane / octet launch may hold (DABGPU_VIT_SCRATCH_MB at 768 bytes per row), >= 1
+    int hybrid_k;               // DABGPU_VIT_HYBRID_K (tests): that many longest sub-channels stay with viterbi_kernel; -1: not given
+    int forced_mapping;         // DABGPU_VIT_MAP_* of the context (dabgpu_viterbi_set_mapping)
+};
+// one puncturing schedule for a whole batch (FIC, uniform codeword batches): groups of 64 consecutive codewords, in bounded slices
+struct dabgpu_uniform_plan {
+    int mapping;                // DABGPU_VIT_MAP_WAVE / _LANE / _OCTET
+    uint32_t dec_rows, in_rows; // decision / symbol rows of one group
+    size_t slice_groups;        // groups per launch
+};
+dabgpu_uniform_plan dabgpu_host_plan_uniform(size_t n_cw, uint32_t n_steps, const uint32_t* seg_pi, const uint32_t* seg_steps, bool staged_gather,
+                                             const dabgpu_decode_limits& lim);
+inline dabgpu_uniform_plan dabgpu_host_plan_fic(size_t n_cw, bool staged_gather, const dabgpu_decode_limits& lim) {
+    const uint32_t pi[4] = DABGPU_FIC_SEG_PI, steps[4] = DABGPU_FIC_SEG_STEPS;
+    return dabgpu_host_plan_uniform(n_cw, DABGPU_FIC_STEPS, pi, steps, staged_gather, lim);
+}
+
+// lane-per-codeword decoder (viterbi_lanes.hip): a GROUP = up to 64 codewords with one puncturing schedule.
+// Symbol area of a group: the codewords' KEPT soft bits only, transposed -- row j, lane L = input bytes 4 j .. 4 j + 3 of lane L's
+// codeword (after the time de-interleaver, -128 clamped to -127).  The trellis kernel de-punctures with wave-uniform selectors.
+struct dabgpu_vit_group {
+    uint32_t first, stride, count;  // lane L decodes descs[first + L * stride], L < count
+    uint32_t n_steps;               // trellis steps incl. tail
+    uint32_t alloc_steps;           // rows of the group's decision area (dabgpu_vit_alloc_steps)
+    uint32_t seg_pi[4];
+    uint32_t seg_steps[4];
+    uint32_t in_rows;               // rows of the group's symbol area (dabgpu_vit_in_rows)
+    uint64_t sched_off;             // entries into the schedule tables: (symbol row, v_perm_b32 selector) per trellis step
+    uint64_t sym_off;               // dwords into the symbol scratch   [in_rows][64]
+    uint64_t dec_off;               // dwords into the decision scratch [alloc_steps][64][2]
+    int64_t res_delta;              // bytes added to &results[first + L * stride]: groups of ONE launch may report into different arrays
+                                    // (the FIB groups of a frame decoded inside the MSC launch, dabgpu_decode_frames_layout)
+};
+// groups appended to another launch's: descriptor index, schedule entries, symbol / decision dwords and result bytes they start at
+struct dabgpu_vit_group_base { uint32_t first; uint64_t sched_off, sym_off, dec_off; int64_t res_delta; };
+
+// MSC (+ FIC of the newest frame) of n_ens ensembles sharing a multiplex.  Sub-channels in descending trellis length: the first k_wave go
+// to viterbi_kernel (one wavefront per codeword), the other n_lane to the lane / octet kernels, group (li, gq) = lane-mapped sub-channel
+// li of ensemble-CIFs 64 gq .. 64 gq + 63, ensembles sliced so that a launch stays inside max_dec_rows.
+enum dabgpu_fic_place {
+    DABGPU_FIC_NONE,            // not asked for
+    DABGPU_FIC_OWN_LAUNCH,      // decoded first, by the FIC entry point's own path
+    DABGPU_FIC_IN_LANES,        // every sub-channel lane-mapped and the call one slice: the FIB groups are further groups of the lane launch
+    DABGPU_FIC_IN_WAVE,         // every sub-channel in viterbi_kernel and the FIC alone would be too: codewords n_cw .. of that launch
+};
+struct dabgpu_decode_plan {
+    std::vector<dabgpu_msc_plan> subs;      // as staged (table 0), lane_mapped set
+    std::vector<uint64_t> lane_subs;        // as staged (table 1): [n_lane] x (sub-channel, decision rows before it, symbol rows before it)
+    int mapping;                            // the pure choice (forced, or the cost model's) and what the model expects of WAVE / LANE / OCTET
+    double model_us[3];
+    int n_sub, k_wave, n_lane, octet;
+    dabgpu_fic_place fic;
+    size_t n_ens, n_cw, n_fic_cw;           // codewords of the sub-channels / FIB groups (sizes saturate at SIZE_MAX instead of wrapping)
+    uint32_t cif_out_bytes;
+    uint32_t max_steps, max_out_bytes;      // of the viterbi_kernel launch (the FIB group's included under DABGPU_FIC_IN_WAVE)
+    uint32_t lane_max_steps, lane_max_in_rows, sched_stride;
+    uint32_t fic_dec_rows, fic_in_rows;     // rows of one group of FIB codewords
+    size_t dec_rows_per_gq, sym_rows_per_gq, ens_per_slice;
+    size_t descs_bytes, plans_bytes, lane_subs_bytes, sched_bytes;      // SCR_CW_DESCS, SCR_MSC_PLANS, SCR_LANE_SUBS, SCR_VIT_SCHED
+};
+// DABGPU_OK, or dabgpu_host_build_msc_plans's status
+int dabgpu_host_plan_decode(const dabgpu_subchannel* subs, int n_sub, size_t n_ens, int hist_frames, bool want_fic, const dabgpu_decode_limits& lim,
+                            dabgpu_decode_plan* out);
+// the lane launch over ensembles e0 .. e0 + ne - 1 (e0 a multiple of ens_per_slice)
+struct dabgpu_decode_slice {
+    size_t ne, cw0;                         // ensembles; first codeword (descriptor and result index)
+    uint32_t gps;                           // groups per lane-mapped sub-channel
+    size_t n_groups, n_fic_groups;          // MSC groups, appended FIB groups (DABGPU_FIC_IN_LANES)
+    size_t sym_rows, dec_rows;              // SCR_VIT_SYM / SCR_VIT_DEC, rows of 64 / 128 dwords, appended groups included
+    size_t groups_bytes;                    // SCR_VIT_GROUPS
+    dabgpu_vit_group_base fic_base;         // where the appended groups start behind the MSC's (res_delta: the executor's, two device addresses)
+};
+dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t e0);

@@ -177,29 +177,13 @@ int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, in
 typedef dabgpu_codeword dabgpu_cw_desc;
 typedef dabgpu_codeword_result dabgpu_cw_result;
 #define DABGPU_CW_LANE_MAPPED 0x80000000u      // internal flag bit of dabgpu_codeword.flags (set by msc_build_descs_kernel)
-// lane-per-codeword decoder (viterbi_lanes.hip): a GROUP = up to 64 codewords with one puncturing schedule.
-// Symbol area of a group: the codewords' KEPT soft bits only, transposed -- row j, lane L = input bytes 4 j .. 4 j + 3 of lane L's
-// codeword (after the time de-interleaver, -128 clamped to -127).  The trellis kernel de-punctures with wave-uniform selectors.
-struct dabgpu_vit_group {
-    uint32_t first, stride, count;  // lane L decodes descs[first + L * stride], L < count
-    uint32_t n_steps;               // trellis steps incl. tail
-    uint32_t alloc_steps;           // rows of the group's decision area (dabgpu_vit_alloc_steps)
-    uint32_t seg_pi[4];
-    uint32_t seg_steps[4];
-    uint32_t in_rows;               // rows of the group's symbol area (dabgpu_vit_in_rows)
-    uint64_t sched_off;             // entries into the schedule tables: (symbol row, v_perm_b32 selector) per trellis step
-    uint64_t sym_off;               // dwords into the symbol scratch   [in_rows][64]
-    uint64_t dec_off;               // dwords into the decision scratch [alloc_steps][64][2]
-    int64_t res_delta;              // bytes added to &results[first + L * stride]: groups of ONE launch may report into different arrays
-                                    // (the FIB groups of a frame decoded inside the MSC launch, dabgpu_decode_frames_layout)
-};
+// (struct dabgpu_vit_group, the lane-per-codeword decoder's unit of work: dabgpu_host_logic.h)
 extern "C" hipError_t dabgpu_launch_vit_groups_uniform(dabgpu_vit_group* d_groups, size_t n_cw, uint32_t n_steps,
                                                        const uint32_t* seg_pi, const uint32_t* seg_steps, hipStream_t stream);
-// the same groups appended to another launch's: descriptor index, schedule entries, symbol / decision dwords and result bytes they start at
-struct dabgpu_vit_group_base { uint32_t first; uint64_t sched_off, sym_off, dec_off; int64_t res_delta; };
+// the same groups appended to another launch's (dabgpu_vit_group_base: dabgpu_host_logic.h)
 extern "C" hipError_t dabgpu_launch_vit_groups_uniform_at(dabgpu_vit_group* d_groups, size_t n_cw, uint32_t n_steps, const uint32_t* seg_pi,
                                                           const uint32_t* seg_steps, dabgpu_vit_group_base base, hipStream_t stream);
-// the two halves of dabgpu_launch_viterbi_lanes: the gather of `kind` (0 general, 1 ring of 4 CIFs, 2 the same in class order, 3 direct)
+// the two halves of a lane / octet decode: the gather of `kind` (0 general, 1 ring of 4 CIFs, 2 the same in class order, 3 direct)
 // over some groups, and the trellis over groups that were gathered
 extern "C" hipError_t dabgpu_launch_vit_prep(int kind, const dabgpu_vit_group* d_groups, size_t n_groups, uint32_t max_in_rows,
                                              const dabgpu_cw_desc* d_descs, uint32_t* d_sym, uint32_t groups_per_sub, hipStream_t stream);
@@ -216,12 +200,6 @@ extern "C" hipError_t dabgpu_launch_vit_sched_uniform(uint2* d_sched, uint32_t s
                                                       const struct dabgpu_vit_tables* d_tables, hipStream_t stream);
 extern "C" hipError_t dabgpu_launch_vit_sched_msc(uint2* d_sched, uint32_t sched_stride, const struct dabgpu_msc_plan* d_plans,
                                                   const uint64_t* d_lane_subs, int n_lane_sub, const struct dabgpu_vit_tables* d_tables,
-                                                  hipStream_t stream);
-extern "C" hipError_t dabgpu_launch_viterbi_lanes(const dabgpu_vit_group* d_groups, size_t n_groups, uint32_t max_in_rows,
-                                                  const dabgpu_cw_desc* d_descs, uint32_t* d_sym, uint32_t* d_dec,
-                                                  dabgpu_cw_result* d_results, int tie_rule, int ring4,
-                                                  const struct dabgpu_vit_tables* d_tables, const uint2* d_sched, int octet, int n_cu,
-                                                  uint32_t groups_per_sub /* MSC: groups[li * groups_per_sub + gq]; 0 = any order */,
                                                   hipStream_t stream);
 // eight lanes per codeword over prepared groups and their symbol array (viterbi_octet.hip): one 512-thread workgroup per group
 extern "C" hipError_t dabgpu_launch_viterbi_octet(const dabgpu_vit_group* d_groups, size_t n_groups, const dabgpu_cw_desc* d_descs,
@@ -243,7 +221,13 @@ extern "C" hipError_t dabgpu_launch_msc_build(dabgpu_cw_desc* d_descs, const int
                                               uint8_t* d_out, size_t out_ens_stride, int cif_out_bytes, const int32_t* d_slots,
                                               int classed, hipStream_t stream);
 
-// ---- frame session (dabgpu_decode_abi.hip) ----
+// one wavefront per codeword over descriptors on the device (dabgpu_decode_abi.hip); fic: in the FIC decoders' copies of the scratch slots;
+// n_first > 0: codewords n_first .. n - 1 report into d_results_rest[0 ..]
+int dabgpu_run_viterbi(dabgpu_ctx* c, const dabgpu_cw_desc* d_descs, size_t n, uint32_t max_steps, uint32_t max_out_bytes, int tie_rule,
+                       dabgpu_codeword_result* d_results, hipStream_t s, bool fic = false, size_t n_first = 0,
+                       dabgpu_codeword_result* d_results_rest = nullptr);
+
+// ---- frame session (frame_session.hip) ----
 // One receiver's decode state behind the single-stream classes: an 8-frame history of soft bits on the device, the FIC + MSC decode of
 // every frame pushed, result slots in pinned host memory (include/dabgpu.h, "Frame session").  Frames arrive either from host memory
 // (dabgpu_frame_session_push_frame) or -- the receiver pipeline, receiver.hip -- are demodulated straight into the history slot by a

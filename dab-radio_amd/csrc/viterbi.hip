@@ -473,10 +473,7 @@ __device__ __forceinline__ void fic_build_one(size_t i, dabgpu_cw_desc* descs, c
     }
     D.d_src = (uint64_t)(uintptr_t)(base + g * 2304);
     D.d_out = (uint64_t)(uintptr_t)(out + i * 96);
-    D.n_steps = 768 + 6;
-    D.seg_pi[0] = 16; D.seg_steps[0] = 32 * 21;
-    D.seg_pi[1] = 15; D.seg_steps[1] = 32 * 3;
-    D.n_crc_blocks = 3;
+    dabgpu_cw_set_fic(&D);
     descs[i] = D;
 }
 

@@ -811,13 +811,3 @@ extern "C" hipError_t dabgpu_launch_vit_trellis(const dabgpu_vit_group* d_groups
 #undef VL_GO
     return hipGetLastError();
 }
-
-extern "C" hipError_t dabgpu_launch_viterbi_lanes(const dabgpu_vit_group* d_groups, size_t n_groups, uint32_t max_in_rows,
-                                                  const dabgpu_cw_desc* d_descs, uint32_t* d_sym, uint32_t* d_dec,
-                                                  dabgpu_cw_result* d_results, int tie_rule, int ring4, const dabgpu_vit_tables* d_tables,
-                                                  const uint2* d_sched, int octet, int n_cu, uint32_t groups_per_sub, hipStream_t stream)
-{
-    hipError_t e = dabgpu_launch_vit_prep(ring4, d_groups, n_groups, max_in_rows, d_descs, d_sym, groups_per_sub, stream);
-    if (e != hipSuccess) return e;
-    return dabgpu_launch_vit_trellis(d_groups, n_groups, d_descs, d_sym, d_dec, d_results, tie_rule, d_tables, d_sched, octet, n_cu, stream);
-}

@@ -4,8 +4,9 @@ AddressSanitizer preset, CMakePresets.json:47-53):
  (a) the CPU ORACLE -- the checker that grades everything -- built with -fsanitize=address,undefined (oracle/Makefile SAN=1) runs its
      own CPU tests clean;
  (b) the DEVICE-FREE PART OF libdabgpu.so (dab-radio_amd/csrc/dabgpu_host_logic.cpp: protection-profile plans, codeword validation,
-     mapping cost model, run-length rules, constant tables, capture-format and wav-header parsing), built on its own under ASan + UBSan
-     and fuzzed (tests/cpp/host_logic_fuzz.cpp): hostile sub-channel descriptors, wav images with lying chunk sizes, truncations;
+     mapping cost model, the decode planner, run-length rules, constant tables, capture-format and wav-header parsing), built on its own
+     under ASan + UBSan and fuzzed (tests/cpp/host_logic_fuzz.cpp): hostile sub-channel descriptors, decode plans of random multiplexes and a
+     table of hand-worked ones, wav images with lying chunk sizes, truncations;
  (c) the C++ MIRROR CLASSES' host code (framing state machine, frame batcher with one session per demodulator, shared context,
      decoders) under ThreadSanitizer and under ASan + UBSan, two receivers in one process with reader / radio / worker threads
      (tests/cpp/mirror_threads_driver.cpp), linked against a TEST-ONLY implementation of the C ABI entry points on the oracle
@@ -62,6 +63,7 @@ def test_device_free_library_code_fuzzed_under_asan_and_ubsan(tmp_path):
         assert out["failed_checks"] == 0
         # the fuzzer reached both sides of every decision: it saw accepted AND rejected inputs of each kind
         assert 0 < out["accepted_plans"] < out["iterations"] and 0 < out["accepted_wav"] < out["iterations"] and 0 < out["accepted_codewords"] < out["iterations"]
+        assert 0 < out["accepted_decode_plans"] < out["iterations"]
 
 
 MIRROR_SRCS = ["ofdm/ofdm_demodulator.cpp", "ofdm/dab_refs.cpp", "dab/dabgpu_shared_context.cpp", "dab/dabgpu_frame_batcher.cpp", "dab/fic/fic_decoder.cpp",

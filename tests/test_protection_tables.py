@@ -1,4 +1,4 @@
-"""The PRODUCT's sub-channel protection tables (csrc/dabgpu_decode_abi.hip: its own copy of EN 300 401 tables 7/8/9,
+"""The PRODUCT's sub-channel protection tables (csrc/dabgpu_host_logic.cpp: its own copy of EN 300 401 tables 7/8/9,
 subchannel_protection_tables.h:21-139) against the golden plans generated from the reference's tables
 (tests/golden/reference_vectors.npz:subchannel_plans, generator tests/golden/make_golden.py): all 64 UEP rows and the EEP grid.
 CPU half: dabgpu_subchannel_plan is host-only.  GPU half: one logical frame of every profile is encoded by the oracle, pushed through
