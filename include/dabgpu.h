@@ -837,7 +837,11 @@ int dabgpu_hard_bytes_to_soft_bits_host_sync(dabgpu_ctx *ctx, const uint8_t *h_b
  *                                   its imaginary part, z = ((1 - 2 b_n) + j (1 - 2 b_{n+NC})) * A.  Demodulating the result gives back
  *                                   the same hard bits.  Mode I uses the context's carrier mapper.
  *   d_prs_fft_ref  nb_fft complex float on the device (8-byte aligned), or NULL for the mode's table (mode I: the context's)
- *   freq_norm  != 0: apply_pll(frame, freq_norm) with its phase at 0 on each frame's first sample (both output formats)
+ *   freq_norm  != 0: apply_pll(frame, freq_norm) with its phase at 0 on each frame's first sample (both output formats).
+ *              Cycles per sample, |freq_norm| < 0.5 (tested from 1e-7 to 0.4999, both signs).  The result is apply_pll's bit for bit over
+ *              that whole range, and shares its float phase: sample n is rotated by 2 pi n freq_norm to within
+ *              2 pi * 2^-22 * (n |freq_norm| + 1) rad -- 2e-4 rad at the end of a mode I frame at 3 kHz, 0.07 rad at |freq_norm| = 0.4999
+ *              (measured there: 0.026 rad).  A caller that needs a large shift with a tighter phase shifts the frames itself.
  *   d_out      [n_frames][samples per frame] in out_format, 16-byte aligned:
  *     DABGPU_IQ_RAW_F32L  complex float
  *     DABGPU_IQ_RAW_U8    QuantisedIQ<uint8_t>::from_iq(I * scale, Q * scale), scale = (1.0f / NC * 4.0f) * 127.5f

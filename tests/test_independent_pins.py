@@ -10,6 +10,11 @@ vendor/viterbi_decoder, ofdm_demodulator.cpp needs <fftw3.h>).  Nothing below sh
 * PRS synchroniser (a5, a6): a float64 numpy model written from ofdm_demodulator.cpp:399-467 and :503-536 must make the same integer
   decisions (peak bin, fast / slow update, fine-time offset, reset) as the oracle over a CFO x timing x SNR grid.
 * FFT rounding (a11-a13): a float64 demodulator (numpy FFT) must give the oracle's hard bits on the 20 dB-SNR config-1 frame.
+* Transmitter (ofdm_modulator.cpp needs <fftw3.h> too): a float64 modulator written from ETSI EN 300 401 clause 14 (its own frequency
+  interleaver, carrier-to-bin rule and unit phasors, numpy's complex128 inverse transform) holds the expectations of the -m gpu transmitter
+  tests (oracle.modulate_frame_reference_payload, oracle.modulate_frame, tests/tx_model.py) in modes I-IV and both payload layouts: exact
+  structure (NULL, cyclic prefix, every payload bit back through a complex128 demodulator), a derived float32 error bound per symbol,
+  the u8 quantisation within one count at samples near an integer boundary only, and oracle.apply_pll against a float64 rotation.
 """
 import numpy as np
 import pytest
@@ -383,3 +388,210 @@ def test_float64_demodulator_gives_the_same_hard_bits_on_the_config1_frame(oracl
     assert np.array_equal(hard[safe], hard64[safe])
     assert safe.mean() > 0.98
     assert (hard != bits.astype(bool)).mean() < 5e-3                     # and both are the transmitted bits but for channel errors
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Transmitter: float64 model from ETSI EN 300 401 clause 14 (read beside ofdm_modulator.cpp:49-156 and simulate_transmitter.cpp:138-178)
+# ---------------------------------------------------------------------------------------------------------------------
+import tx_model as TX
+
+U32 = 2.0 ** -24                                # unit roundoff of binary32
+
+
+def tx64_interleaver(N, NC):
+    """clause 14.6: PI(0) = 0, PI(i) = (13 PI(i-1) + N/4 - 1) mod N; D = the values in [N/2 - NC/2, N/2 + NC/2] without N/2, in order of
+    appearance; QPSK symbol n of an OFDM symbol goes onto carrier k = D[n] - N/2  (k in -NC/2 .. NC/2, k != 0)"""
+    pi, ks = 0, []
+    for _ in range(N):
+        if N // 2 - NC // 2 <= pi <= N // 2 + NC // 2 and pi != N // 2:
+            ks.append(pi - N // 2)
+        pi = (13 * pi + N // 4 - 1) % N
+    ks = np.array(ks, dtype=np.int64)
+    assert ks.size == NC and np.unique(ks).size == NC
+    return ks
+
+
+def tx64_carriers(NC):
+    """carrier numbers in ascending frequency: -NC/2 .. -1, 1 .. NC/2 (clause 14.5: no DC carrier)"""
+    return np.concatenate([np.arange(-NC // 2, 0), np.arange(1, NC // 2 + 1)])
+
+
+def tx64_slot(k, NC):
+    """position of carrier number k in tx64_carriers"""
+    k = np.asarray(k)
+    return np.where(k < 0, k + NC // 2, k + NC // 2 - 1)
+
+
+# quarter q <-> phase (2q + 1) pi / 4.  Reference layout: 2 bits v per carrier, ascending frequency, low bits first in a byte;
+# PHASE_MAP[v] = (-A,-A), (A,-A), (A,A), (-A,A) (ofdm_modulator.cpp:102) = quarters 2, 3, 0, 1
+TX64_Q_OF_V = np.array([2, 3, 0, 1])
+TX64_V_OF_Q = np.array([2, 3, 0, 1])
+# Frame-bits layout: z = ((1 - 2 b_n) + j (1 - 2 b_{n+NC})) / sqrt(2) (clause 14.5): (b_re, b_im) -> quarter
+TX64_Q_OF_BITS = np.array([[0, 3], [1, 2]])
+
+
+def tx64_quarters(payload, layout, N, NC, L):
+    """[L-1][NC] quarter per data symbol and carrier slot (ascending frequency)"""
+    pay = np.ascontiguousarray(payload, np.uint8).reshape(L - 1, NC // 4)
+    if layout == TX.LAYOUT_REFERENCE:
+        c = np.arange(NC)
+        v = (pay[:, c // 4] >> (2 * (c % 4))) & 3
+        return TX64_Q_OF_V[v]
+    b = np.unpackbits(pay, axis=1, bitorder="little")                  # bit n of a symbol = bit (n & 7) of byte n >> 3
+    q = np.empty((L - 1, NC), np.int64)
+    q[:, tx64_slot(tx64_interleaver(N, NC), NC)] = TX64_Q_OF_BITS[b[:, :NC], b[:, NC:]]
+    return q
+
+
+def tx64_modulate(oracle, mode, payload, layout, prs=None):
+    """complex128 frame, NULL first; every phasor has modulus one (integer eighths of a turn accumulated exactly)"""
+    g = oracle.geometry(mode)
+    N, NC, L, P, CP = g.nb_fft, g.nb_carriers, g.nb_frame_symbols, g.nb_symbol_period, g.nb_cp
+    prs = (oracle.prs_fft_mode(mode) if prs is None else np.asarray(prs)).astype(np.complex128)
+    bins = tx64_carriers(NC) % N                                        # carrier k sits in bin k mod N
+    q = tx64_quarters(payload, layout, N, NC, L)
+    eighths = np.concatenate([np.zeros((1, NC), np.int64), np.cumsum(2 * q + 1, axis=0)]) % 8
+    spec = np.zeros((L, N), np.complex128)
+    spec[:, bins] = prs[bins][None, :] * np.exp(0.25j * np.pi * eighths)
+    spec[0] = prs                                                       # the PRS symbol is the whole spectrum as given
+    t = np.fft.ifft(spec, axis=1) * N                                   # FFTW_BACKWARD is unnormalised
+    out = np.zeros(g.nb_frame_samples, np.complex128)
+    out[g.nb_null_period:] = np.concatenate([t[:, N - CP:], t], axis=1).reshape(-1)
+    return out
+
+
+def tx64_demodulate(oracle, mode, frame, layout):
+    """complex128 differential demodulator of a NULL-first frame -> (payload bytes in `layout`, smallest |component| of
+    X_s conj(X_{s-1}) / N^2 over all data carriers; the ideal value is |PRS bin|^2 / sqrt(2) = 1 / sqrt(2))"""
+    g = oracle.geometry(mode)
+    N, NC, L, P, CP = g.nb_fft, g.nb_carriers, g.nb_frame_symbols, g.nb_symbol_period, g.nb_cp
+    syms = np.asarray(frame).astype(np.complex128)[g.nb_null_period:].reshape(L, P)[:, CP:]
+    X = np.fft.fft(syms, axis=1)[:, tx64_carriers(NC) % N] / N
+    d = X[1:] * np.conj(X[:-1])
+    margin = float(min(np.abs(d.real).min(), np.abs(d.imag).min()))
+    if layout == TX.LAYOUT_REFERENCE:
+        q = np.where(d.imag > 0, np.where(d.real > 0, 0, 1), np.where(d.real > 0, 3, 2))
+        v = TX64_V_OF_Q[q].astype(np.uint8).reshape(L - 1, NC // 4, 4)
+        return (v[..., 0] | (v[..., 1] << 2) | (v[..., 2] << 4) | (v[..., 3] << 6)).astype(np.uint8).reshape(-1), margin
+    dn = d[:, tx64_slot(tx64_interleaver(N, NC), NC)]                   # QPSK symbol n
+    b = np.concatenate([dn.real < 0, dn.imag < 0], axis=1).astype(np.uint8)
+    return np.packbits(b, axis=1, bitorder="little").reshape(-1), margin
+
+
+def tx_symbol_bound(s, N, A):
+    """relative L2 error of data symbol s (s = 0: the PRS) of the float32 transmitter against exact arithmetic, from first principles:
+      * the chain: s complex products X <- X z.  |z| = sqrt(2 A A) against the model's 1: a modulus factor |2 A A - 1| / 2 (first order) per
+        step; a float32 complex product by the 4-operation formula has relative error below sqrt(5) u < 3 u (Brent, Percival, Zimmermann,
+        "Error bounds on complex floating-point multiplication", Math. Comp. 76 (2007), Theorem 3.1).  The transform is unitary up to its
+        scale, so a relative L2 error of the spectrum is the same relative L2 error of the symbol.
+      * the transform: Higham, "Accuracy and Stability of Numerical Algorithms" (2nd ed.), Theorem 24.2 (Cooley-Tukey radix 2):
+        |y^ - y|_2 / |y|_2 <= log2(N) eta / (1 - log2(N) eta), eta = mu + gamma_4 (sqrt(2) + mu), gamma_4 = 4u / (1 - 4u), mu = the error
+        of the stored twiddles, here u (each component is a double-precision value rounded once).  A radix-4 / radix-8 pass is two / three
+        radix-2 butterfly levels with exact or once-rounded inner factors, so log2(N) levels in all: c = eta / u = 1 + 4 sqrt(2) ~ 6.66."""
+    gamma4 = 4 * U32 / (1 - 4 * U32)
+    eta = U32 + gamma4 * (np.sqrt(2.0) + U32)
+    t = np.log2(N) * eta
+    return s * (abs(2.0 * float(A) * float(A) - 1.0) / 2 + 3 * U32) + t / (1 - t)
+
+
+def tx_expectations(oracle, mode, payload, layout):
+    """what the -m gpu tests compare the device with: name -> float32 frame"""
+    out = {"tx_model": TX.modulate(oracle, mode, payload, layout)}
+    if mode == 1 and layout == TX.LAYOUT_REFERENCE:
+        out["oracle.modulate_frame_reference_payload"] = oracle.modulate_frame_reference_payload(payload)
+    if mode == 1 and layout == TX.LAYOUT_FRAME_BITS:
+        out["oracle.modulate_frame"] = oracle.modulate_frame(np.unpackbits(np.ascontiguousarray(payload, np.uint8), bitorder="little"))
+    return out
+
+
+@pytest.mark.parametrize("layout", [TX.LAYOUT_REFERENCE, TX.LAYOUT_FRAME_BITS])
+@pytest.mark.parametrize("mode", [1, 2, 3, 4])
+def test_transmitter_expectations_equal_a_float64_model(oracle, mode, layout):
+    g = oracle.geometry(mode)
+    N, NC, L, P, CP, NUL = g.nb_fft, g.nb_carriers, g.nb_frame_symbols, g.nb_symbol_period, g.nb_cp, g.nb_null_period
+    rng = np.random.default_rng(7100 + 10 * mode + layout)
+    payload = rng.integers(0, 256, TX.payload_bytes(oracle, mode), dtype=np.uint8)
+    A = TX.A_REF if layout == TX.LAYOUT_REFERENCE else TX.A_BITS
+    x64 = tx64_modulate(oracle, mode, payload, layout)
+    # the model demodulates to its own payload (the two halves of the model agree before anything is held to them)
+    back, margin = tx64_demodulate(oracle, mode, x64, layout)
+    assert np.array_equal(back, payload) and margin > 0.70
+    s64 = x64[NUL:].reshape(L, P)
+    norm64 = np.sqrt((np.abs(s64[:, CP:]) ** 2).sum(axis=1))
+    bound = np.array([tx_symbol_bound(s, N, A) for s in range(L)])
+    scale32 = (np.float32(1.0) / np.float32(NC) * np.float32(4.0)) * np.float32(127.5)
+    scale = float(scale32)
+    for name, x32 in tx_expectations(oracle, mode, payload, layout).items():
+        x32 = np.ascontiguousarray(x32, np.complex64)
+        assert x32.size == g.nb_frame_samples
+        # exact: NULL all zero bits, prefix = the symbol's last nb_cp samples as bit patterns, every payload bit back
+        assert not x32[:NUL].view(np.uint32).any(), name
+        s32 = x32[NUL:].reshape(L, P)
+        assert np.array_equal(s32[:, :CP].copy().view(np.uint32), s32[:, N:].copy().view(np.uint32)), name
+        back, margin = tx64_demodulate(oracle, mode, x32, layout)
+        assert np.array_equal(back, payload), name
+        assert margin > 0.5 / np.sqrt(2.0), (name, margin)
+        # numeric: per symbol, relative L2 error of the useful part against the float64 model
+        err = np.sqrt((np.abs(s32[:, CP:].astype(np.complex128) - s64[:, CP:]) ** 2).sum(axis=1)) / norm64
+        worst = int(np.argmax(err / bound))
+        print(f"mode {mode} layout {layout} {name}: max relative L2 error {err.max():.3e} (symbol {int(np.argmax(err))}); "
+              f"closest to its bound at symbol {worst}: {err[worst]:.3e} of {bound[worst]:.3e}; decision margin {margin:.4f}")
+        assert (err <= bound).all(), (name, worst, err[worst], bound[worst])
+        # u8: at most one count, and only where the float64 value is within the bound of an integer boundary (1 .. 255; below 0 and
+        # above 255 both sides clamp).  A sample's error is at most the symbol's L2 error; the float32 quantiser adds two roundings
+        # of values below 256 (x * scale, + 127.5)
+        q32 = TX.quantise_u8(oracle, x32, 0.0, NC).astype(np.int64)
+        v64 = np.stack([x64.real, x64.imag], -1).reshape(-1) * scale + 127.5
+        q64 = np.floor(np.clip(v64, 0.0, 255.0)).astype(np.int64)
+        delta = np.concatenate([np.zeros(NUL), np.repeat(bound * norm64, P)]) * scale + 2 * 256 * U32
+        delta = np.repeat(delta, 2)
+        nearest = np.rint(v64)
+        near = (np.abs(v64 - nearest) <= delta) & (nearest >= 1) & (nearest <= 255)
+        diff = q32 != q64
+        print(f"    u8: {int(diff.sum())} of {diff.size} samples differ by one count; {near.mean():.4%} lie within the bound of a boundary")
+        assert np.abs(q32 - q64).max() <= 1, name
+        assert not (diff & ~near).any(), (name, int((diff & ~near).sum()))
+        assert near.mean() < 0.1, name                                  # (the bound is tight enough to mean something)
+
+
+# chebyshev_sine.h:13-20: sin(2 pi x) ~ P(x) = (a0 + a1 z + ... + a5 z^5) (z - 1/4) x, z = x x, on [-1/2, 1/2]
+TX_CHEB = (-25.13274193, 64.83583069, -67.07687378, 38.50016403, -14.07150173, 3.20396066)
+
+
+def pll_sample_bound(n, f):
+    """|y^_n - x_n e^{2 pi j f n}| / |x_n| for the float32 PLL of DESIGN.md 3.1, sample n of a frame (phase 0 at n = 0):
+      * the phase: (float)(n & ~3) * f rounds once (<= u n|f| cycles), base + (k f [+ 1/4]) rounds a value of magnitude <= n|f| + 1 once
+        more, k f rounds below u |f| x 4 ... in all <= 2u (n|f| + 1) cycles; d - rint(d) is exact.  In radians: 2 pi 2u (n|f| + 1).
+      * the polynomial: its distance from sin(2 pi x) on [-1/2, 1/2] (computed below in float64 from the published coefficients) plus
+        Horner in float32: 5 steps of one rounding each (fused) on sum |a_k| z^k <= 46.2 at z = 1/4, times |z - 1/4| |x| <= 1/8, plus the
+        three roundings of the closing products on |P| <= 1:  (5 x 46.2 / 8 + 3) u < 32 u.  cos and sin each carry it: a factor sqrt(2).
+      * the complex product: < 3u (as in tx_symbol_bound)."""
+    x = np.linspace(-0.5, 0.5, 200001)
+    z = x * x
+    p = np.polyval(TX_CHEB[::-1], z) * (z - 0.25) * x
+    approx = float(np.abs(p - np.sin(2 * np.pi * x)).max())
+    return 2 * np.pi * 2 * U32 * (n * abs(float(f)) + 1.0) + np.sqrt(2.0) * (approx + 32 * U32) + 3 * U32
+
+
+@pytest.mark.parametrize("mode", [1, 3])
+def test_transmitter_shift_equals_a_float64_rotation(oracle, mode):
+    """oracle.apply_pll (what the device's shifted output is held to) against frame * exp(2 pi j f n) in complex128 at every freq_norm the
+    -m gpu transmitter tests use; the bound grows with n |f|: at |f| = 0.4999 the last samples of a mode I frame may be off by
+    2 pi 2u x 98,285 = 0.074 rad (include/dabgpu.h states this for freq_norm)"""
+    g = oracle.geometry(mode)
+    rng = np.random.default_rng(7200 + mode)
+    payload = rng.integers(0, 256, TX.payload_bytes(oracle, mode), dtype=np.uint8)
+    frame = TX.modulate(oracle, mode, payload, TX.LAYOUT_REFERENCE)
+    n = np.arange(frame.size)
+    mag = np.abs(frame.astype(np.complex128))
+    live = mag > 0
+    for f in TX.shift_cases():
+        got = oracle.apply_pll(frame, f).astype(np.complex128)
+        exp = frame.astype(np.complex128) * np.exp(2j * np.pi * float(f) * n)
+        assert not got[~live].any()                                     # the NULL period stays zero
+        rel = np.abs(got - exp)[live] / mag[live]
+        bound = pll_sample_bound(n, f)[live]
+        worst = int(np.argmax(rel / bound))
+        print(f"mode {mode} freq_norm {float(f):+.6e}: max relative error {rel.max():.3e}; closest to its bound: {rel[worst]:.3e} of "
+              f"{bound[worst]:.3e} (bound at the frame's last sample {bound[-1]:.3e})")
+        assert (rel <= bound).all(), (float(f), rel[worst], bound[worst])

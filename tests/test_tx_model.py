@@ -33,10 +33,12 @@ def test_model_shapes_all_modes(oracle):
         f = TX.modulate(oracle, mode, payload, TX.LAYOUT_REFERENCE)
         assert f.size == g.nb_frame_samples
         assert not f[:g.nb_null_period].any()
-        # the cyclic prefix repeats the end of each symbol
-        for s in (0, g.nb_frame_symbols - 1):
+        # the cyclic prefix repeats the end of each symbol: every symbol of the frame, and the symbols fill it to its last sample
+        assert g.nb_null_period + g.nb_frame_symbols * g.nb_symbol_period == f.size
+        for s in range(g.nb_frame_symbols):
             p = g.nb_null_period + s * g.nb_symbol_period
-            assert np.array_equal(bits(f[p:p + g.nb_cp]), bits(f[p + g.nb_fft:p + g.nb_symbol_period]))
+            assert np.array_equal(bits(f[p:p + g.nb_cp]), bits(f[p + g.nb_fft:p + g.nb_symbol_period])), (mode, s)
+            assert f[p + g.nb_cp:p + g.nb_symbol_period].any(), (mode, s)
 
 
 def test_quantise_u8_and_scrambler():

@@ -88,6 +88,19 @@ def freq_norm(hz):
     return np.float32(np.float32(hz) / np.float32(2.048e6))
 
 
+SERIES_SHIFT = freq_norm(3000.0)            # the shift of the run-length series (tests/tx_variants_child.py)
+
+
+def shift_cases():
+    """the freq_norm values the transmitter tests use (float32, as the ABI takes them): the CLI's Hz values, the run-length series' shift,
+    and the edges -- tiny, a quarter cycle per sample, just under half a cycle, both signs.  tests/test_independent_pins.py holds
+    oracle.apply_pll to a float64 rotation at every one of them; tests/test_gpu_ofdm_modulator_variants.py holds the device to
+    oracle.apply_pll."""
+    hz = [freq_norm(1000.0), freq_norm(-2500.0), SERIES_SHIFT]
+    edges = [np.float32(v) for v in (2.0 ** -20, 1e-7, 0.25, -0.25, 0.4999, -0.4999)]
+    return hz + edges
+
+
 def to_frame_buffer(oracle, mode, tx_frame):
     """a NULL-first frame -> the demodulator's frame-buffer layout (PRS first, the following frame's NULL -- zeros -- last)"""
     g = oracle.geometry(mode)
