@@ -590,3 +590,96 @@ extern "C" int dabgpu_subchannel_validate(const dabgpu_subchannel* sc) {
     std::vector<dabgpu_msc_plan> one;
     return dabgpu_host_build_msc_plans(sc, 1, one, nullptr, nullptr, nullptr);
 }
+
+// ---- channel encoder planner ----
+// keep mask of PI over one run of 32 mother bits (8 input bits x 4 generator outputs, bit 4 g + r = output r of input bit g): the
+// first cnt[g] outputs of each input bit survive (EN 300 401 table 13, in the order puncture_codes.h:42-67 lists them)
+static uint32_t tx_keep_mask(uint32_t pi) {
+    static const int order[8] = {0, 4, 2, 6, 1, 5, 3, 7};
+    int cnt[8];
+    for (int g = 0; g < 8; g++) cnt[g] = 1;
+    for (uint32_t e = 0; e < pi; e++) cnt[order[e % 8]]++;
+    uint32_t m = 0;
+    for (int g = 0; g < 8; g++) m |= ((1u << cnt[g]) - 1u) << (4 * g);
+    return m;
+}
+
+// schedule of a code word "segments + tail", appended to `sched` unless an equal one is there already; returns its first entry
+static uint32_t tx_add_schedule(dabgpu_tx_plan* P, std::vector<std::pair<std::vector<uint32_t>, uint32_t>>& known, const uint32_t* pi,
+                                const uint32_t* blocks, uint32_t* kept_bits) {
+    std::vector<uint32_t> key;
+    uint32_t kept = 12;
+    for (int k = 0; k < 4; k++) { key.push_back(blocks[k] ? pi[k] : 0u); key.push_back(blocks[k]); kept += 4u * blocks[k] * (8u + pi[k]); }
+    *kept_bits = kept;
+    for (const auto& kn : known) if (kn.first == key) return kn.second;
+    const uint32_t first = (uint32_t)P->sched.size();
+    uint32_t bit = 0;
+    for (int k = 0; k < 4; k++)
+        for (uint32_t b = 0; b < blocks[k]; b++) { P->sched.push_back({bit, tx_keep_mask(pi[k])}); bit += 4u * (8u + pi[k]); }
+    P->sched.push_back({bit, DABGPU_TX_TAIL_KEEP_MASK});
+    known.emplace_back(key, first);
+    return first;
+}
+
+int dabgpu_host_tx_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_plan* P) {
+    *P = dabgpu_tx_plan{};
+    if (n_sub < 0 || n_sub > 64 || (n_sub > 0 && !subs)) { dabgpu_set_error("tx_encode_plan: %d sub-channels (0..64 are accepted)", n_sub); return DABGPU_ERR_INVALID_ARG; }
+    std::vector<std::pair<std::vector<uint32_t>, uint32_t>> known;
+    unsigned char used[864];
+    memset(used, 0, sizeof(used));
+    P->subs.assign((size_t)n_sub + 1, dabgpu_tx_sub_plan{});
+    for (int s = 0; s < n_sub; s++) {
+        const dabgpu_subchannel& sc = subs[s];
+        int pi[4], lx[4], nb = 0;
+        // (ranges first: start + length of a hostile descriptor overflows int)
+        if (sc.length <= 0 || sc.length > 864 || sc.start_address < 0 || sc.start_address > 864 - sc.length) {
+            dabgpu_set_error("tx_encode_plan: sub-channel %d lies outside the 864 capacity units", s); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (dabgpu_subchannel_plan(&sc, pi, lx, &nb) < 0) { dabgpu_set_error("tx_encode_plan: sub-channel %d has an invalid protection profile", s); return DABGPU_ERR_INVALID_ARG; }
+        for (int cu = sc.start_address; cu < sc.start_address + sc.length; cu++) {
+            if (used[cu]) { dabgpu_set_error("tx_encode_plan: sub-channel %d overlaps another at capacity unit %d", s, cu); return DABGPU_ERR_INVALID_ARG; }
+            used[cu] = 1;
+        }
+        dabgpu_tx_sub_plan& D = P->subs[(size_t)s];
+        D.start_address = (uint32_t)sc.start_address; D.length = (uint32_t)sc.length;
+        for (int k = 0; k < 4; k++) { D.seg_blocks[k] = (uint32_t)lx[k]; D.seg_pi[k] = lx[k] ? (uint32_t)pi[k] : 0u; D.n_words += (uint32_t)lx[k]; }
+        if (D.n_words == 0) { dabgpu_set_error("tx_encode_plan: sub-channel %d carries no data", s); return DABGPU_ERR_INVALID_ARG; }
+        D.sched_offset = tx_add_schedule(P, known, D.seg_pi, D.seg_blocks, &D.kept_bits);
+        if (D.kept_bits > D.length * 64u) {
+            dabgpu_set_error("tx_encode_plan: sub-channel %d: its code word has %u bits, %u capacity units hold %u", s, D.kept_bits, D.length, D.length * 64u);
+            return DABGPU_ERR_INVALID_ARG;
+        }
+        D.in_offset = P->cif_in_bytes; D.in_bytes = (uint32_t)nb;
+        P->cif_in_bytes += (uint32_t)nb;
+        // ring slot: 16 class rows of ceil(length / 8) dwords (4 bits per capacity unit and class)
+        D.ring_offset = P->ring_slot_dwords; D.ring_row_dwords = (D.length + 7u) / 8u;
+        P->ring_slot_dwords += 16u * D.ring_row_dwords;
+        P->max_length = std::max(P->max_length, D.length);
+    }
+    dabgpu_tx_sub_plan& F = P->subs[(size_t)n_sub];
+    const uint32_t fpi[4] = DABGPU_FIC_SEG_PI, fsteps[4] = DABGPU_FIC_SEG_STEPS;
+    F.length = DABGPU_NB_FIB_GROUP_BITS / 64; F.in_bytes = DABGPU_FIC_OUT_BYTES;
+    for (int k = 0; k < 4; k++) { F.seg_pi[k] = fpi[k]; F.seg_blocks[k] = fsteps[k] / 32u; F.n_words += F.seg_blocks[k]; }
+    F.sched_offset = tx_add_schedule(P, known, F.seg_pi, F.seg_blocks, &F.kept_bits);
+    for (int cu = 0; cu < 864;) {
+        if (used[cu]) { cu++; continue; }
+        int e = cu;
+        while (e < 864 && !used[e]) e++;
+        P->gaps.push_back((uint32_t)cu); P->gaps.push_back((uint32_t)(e - cu));
+        cu = e;
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_tx_encode_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_sub_plan* plans, uint32_t* cif_in_bytes,
+                                     dabgpu_tx_sched_entry* sched, size_t sched_capacity, size_t* n_sched, uint32_t* ring_slot_dwords) {
+    dabgpu_tx_plan P;
+    const int st = dabgpu_host_tx_plan(subs, n_sub, &P);
+    if (st) return st;
+    if (plans) memcpy(plans, P.subs.data(), P.subs.size() * sizeof(dabgpu_tx_sub_plan));
+    if (cif_in_bytes) *cif_in_bytes = P.cif_in_bytes;
+    if (n_sched) *n_sched = P.sched.size();
+    if (ring_slot_dwords) *ring_slot_dwords = P.ring_slot_dwords;
+    if (sched && sched_capacity >= P.sched.size()) memcpy(sched, P.sched.data(), P.sched.size() * sizeof(dabgpu_tx_sched_entry));
+    return DABGPU_OK;
+}

@@ -180,3 +180,16 @@ struct dabgpu_decode_slice {
     dabgpu_vit_group_base fic_base;         // where the appended groups start behind the MSC's (res_delta: the executor's, two device addresses)
 };
 dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t e0);
+
+// ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
+#define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
+struct dabgpu_tx_plan {
+    std::vector<dabgpu_tx_sub_plan> subs;           // n_sub sub-channels in list order, then the FIB group
+    std::vector<dabgpu_tx_sched_entry> sched;       // kept-bit schedules, one per distinct (PI, L) list
+    std::vector<uint32_t> gaps;                     // (start, length) in capacity units of the ranges no sub-channel occupies, ascending
+    uint32_t cif_in_bytes = 0;
+    uint32_t ring_slot_dwords = 0;                  // one slot of an ensemble's time-interleaver ring (16 slots per ensemble)
+    uint32_t max_length = 0;                        // capacity units of the largest sub-channel
+};
+// DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason in dabgpu_last_error
+int dabgpu_host_tx_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_plan* out);

@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "dabgpu_receiver_submit_demod", "dabgpu_receiver_submit_decode",
     "dabgpu_ingest_create", "dabgpu_ingest_destroy", "dabgpu_ingest_acquire", "dabgpu_ingest_submit", "dabgpu_ingest_wait", "dabgpu_ingest_consumed",
     "dabgpu_ofdm_modulate_frames", "dabgpu_ofdm_modulate_frames_host_sync",
+    "dabgpu_tx_encode_plan", "dabgpu_tx_bank_create", "dabgpu_tx_bank_destroy", "dabgpu_tx_bank_reset", "dabgpu_tx_bank_encode_frames",
+    "dabgpu_tx_bank_transmit_frames", "dabgpu_tx_bank_encode_frames_host_sync", "dabgpu_tx_bank_transmit_frames_host_sync",
 ]
 
 # OFDM transmitter payload layouts (include/dabgpu.h)
@@ -107,6 +109,13 @@ class SubChannel(C.Structure):
     """dabgpu_subchannel"""
     _fields_ = [("start_address", C.c_int), ("length", C.c_int), ("is_uep", C.c_int),
                 ("uep_prot_index", C.c_int), ("eep_prot_level", C.c_int), ("eep_type", C.c_int)]
+
+
+class TxSubPlan(C.Structure):
+    """dabgpu_tx_sub_plan"""
+    _fields_ = [("start_address", C.c_uint32), ("length", C.c_uint32), ("in_offset", C.c_uint32), ("in_bytes", C.c_uint32),
+                ("seg_pi", C.c_uint32 * 4), ("seg_blocks", C.c_uint32 * 4), ("n_words", C.c_uint32), ("kept_bits", C.c_uint32),
+                ("sched_offset", C.c_uint32), ("ring_offset", C.c_uint32), ("ring_row_dwords", C.c_uint32)]
 
 
 class SyncCfg(C.Structure):
@@ -272,6 +281,15 @@ def lib():
                                                   C.c_void_p, C.c_int, C.c_void_p]
         L.dabgpu_ofdm_modulate_frames_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_float,
                                                             C.c_void_p, C.c_int]
+        L.dabgpu_tx_encode_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dabgpu_tx_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.dabgpu_tx_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_tx_bank_destroy.restype = None
+        L.dabgpu_tx_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_tx_bank_encode_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_tx_bank_transmit_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_tx_bank_encode_frames_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_tx_bank_transmit_frames_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -657,6 +675,64 @@ class StreamBank:
         return out
 
 
+class TxBank:
+    """dabgpu_tx_bank: the channel encoder of n ensembles sharing one multiplex (FIB bodies + sub-channel bytes -> frame bits -> IQ)"""
+
+    def __init__(self, ctx, n_ensembles, subchannels):
+        self._ctx = ctx
+        self.n = n_ensembles
+        self.plan = tx_encode_plan(subchannels)
+        self.cif_in_bytes = self.plan["cif_in_bytes"]
+        n = len(subchannels)
+        arr = (SubChannel * n)(*subchannels) if n else None
+        self._h = C.c_void_p()
+        check(lib().dabgpu_tx_bank_create(ctx._h, n_ensembles, arr, n, C.byref(self._h)), "dabgpu_tx_bank_create")
+
+    def close(self):
+        if self._h:
+            lib().dabgpu_tx_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().dabgpu_tx_bank_reset(self._h, Context._stream(stream)), "dabgpu_tx_bank_reset")
+
+    def encode_frames(self, fib_data, payload, n_frames, frame_bits, frame_stride=0, stream=None):
+        """fib_data [n][F][4][3][30], payload [n][F][4][cif_in_bytes] -> frame_bits [n][F] frames of 28800 bytes (device, asynchronous)"""
+        check(lib().dabgpu_tx_bank_encode_frames(self._h, _ptr(fib_data), _ptr(payload), n_frames, _ptr(frame_bits), frame_stride,
+                                                 Context._stream(stream)), "dabgpu_tx_bank_encode_frames")
+
+    def transmit_frames(self, fib_data, payload, n_frames, out, freq_norm=0.0, out_format=None, stream=None):
+        """the same on to NULL-first IQ frames: out [n][F][196608] complex float (default) or u8 pairs"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_tx_bank_transmit_frames(self._h, _ptr(fib_data), _ptr(payload), n_frames, float(freq_norm), _ptr(out), fmt,
+                                                   Context._stream(stream)), "dabgpu_tx_bank_transmit_frames")
+
+    def encode_frames_host(self, fib_data, payload, n_frames):
+        import numpy as np
+        fib = np.ascontiguousarray(fib_data, dtype=np.uint8)
+        pay = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint8)
+        out = np.empty((self.n, n_frames, NB_FRAME_BITS // 8), np.uint8)
+        check(lib().dabgpu_tx_bank_encode_frames_host_sync(self._h, _ptr(fib), _ptr(pay), n_frames, _ptr(out)), "dabgpu_tx_bank_encode_frames_host_sync")
+        return out
+
+    def transmit_frames_host(self, fib_data, payload, n_frames, freq_norm=0.0, out_format=None):
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        fib = np.ascontiguousarray(fib_data, dtype=np.uint8)
+        pay = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint8)
+        out = np.empty((self.n, n_frames, NB_FRAME_SAMPLES), np.complex64) if fmt == IQ_FORMATS.index("raw_f32l") else \
+            np.empty((self.n, n_frames, 2 * NB_FRAME_SAMPLES), np.uint8)
+        check(lib().dabgpu_tx_bank_transmit_frames_host_sync(self._h, _ptr(fib), _ptr(pay), n_frames, float(freq_norm), _ptr(out), fmt),
+              "dabgpu_tx_bank_transmit_frames_host_sync")
+        return out
+
+
 class IngestPipe:
     """dabgpu_ingest: ring of pinned host buffers + device twins + a copy stream (include/dabgpu.h)"""
 
@@ -860,3 +936,17 @@ def subchannel_plan(sc):
     if n < 0:
         raise DabGpuError("invalid sub-channel protection profile")
     return list(pi)[:n], list(lx)[:n], nb.value
+
+
+def tx_encode_plan(subchannels):
+    """dabgpu_tx_encode_plan (host only): dict with `subs` (TxSubPlan per sub-channel), `fic` (the FIB group's), `cif_in_bytes`,
+    `ring_slot_dwords` and `sched` = uint32 array [n][2] of (out_bit, keep_mask)"""
+    import numpy as np
+    n = len(subchannels)
+    arr = (SubChannel * n)(*subchannels) if n else None
+    plans = (TxSubPlan * (n + 1))()
+    cif_in, ring, n_sched = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    check(lib().dabgpu_tx_encode_plan(arr, n, plans, C.byref(cif_in), None, 0, C.byref(n_sched), C.byref(ring)), "dabgpu_tx_encode_plan")
+    sched = np.zeros((n_sched.value, 2), np.uint32)
+    check(lib().dabgpu_tx_encode_plan(arr, n, plans, None, _ptr(sched), n_sched.value, None, None), "dabgpu_tx_encode_plan")
+    return dict(subs=[plans[i] for i in range(n)], fic=plans[n], cif_in_bytes=cif_in.value, ring_slot_dwords=ring.value, sched=sched)

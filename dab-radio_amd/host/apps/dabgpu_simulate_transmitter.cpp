@@ -7,9 +7,16 @@
 //   -f, --frequency HZ             shift of the 8-bit IQ signal (default 0; f_norm = HZ / 2.048e6)
 //   -o, --output FILE              default stdout
 //   --frames N                     (not in the reference) stop after N frames
+// Channel-coded frames (not in the reference, mode I; include/dabgpu.h "Channel encoder"): with any of the options below every frame is
+// encoded from FIB bodies and sub-channel bytes (dabgpu_tx_bank_transmit_frames_host_sync) and a receiver decodes what was sent.
+//   --subchannel START:LENGTH:PROT repeatable; capacity units; PROT = eepL-A | eepL-B (L = 1..4) or uepROW (row 0..63 of table 8)
+//   --fib-file FILE                FIB bodies, 30 bytes each, 12 per frame, read cyclically (tools/dabfig.py writes them)
+//   --payload-file FILE            the CIFs' input records (the sub-channels' bytes back to back in list order), read cyclically
+//   --seed N                       random FIB bodies / payload where no file is given (default 1)
 #include <stdio.h>
 #include <stdlib.h>
 #include <complex>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -39,11 +46,81 @@ struct Args {
     float frequency = 0.0f;
     std::string output_filename;
     long long frames = -1;             // < 0: until a write fails
+    // channel-coded frames
+    bool coded = false;
+    std::vector<dabgpu_subchannel> subchannels;
+    std::string fib_filename, payload_filename;
+    unsigned long long seed = 1;
 };
+
+// START:LENGTH:PROT
+static dabgpu_subchannel parse_subchannel(const std::string& v) {
+    const size_t a = v.find(':'), b = v.find(':', a == std::string::npos ? a : a + 1);
+    if (a == std::string::npos || b == std::string::npos) throw std::runtime_error("--subchannel wants START:LENGTH:PROT, got " + v);
+    dabgpu_subchannel sc = {};
+    sc.start_address = std::stoi(v.substr(0, a));
+    sc.length = std::stoi(v.substr(a + 1, b - a - 1));
+    const std::string prot = v.substr(b + 1);
+    if (prot.rfind("uep", 0) == 0 && prot.size() > 3) { sc.is_uep = 1; sc.uep_prot_index = std::stoi(prot.substr(3)); }
+    else if (prot.size() == 6 && prot.rfind("eep", 0) == 0 && prot[4] == '-' && (prot[5] == 'A' || prot[5] == 'B') && prot[3] >= '1' && prot[3] <= '4') {
+        sc.eep_prot_level = prot[3] - '1'; sc.eep_type = prot[5] == 'B';
+    } else throw std::runtime_error("--subchannel: protection " + prot + " (eepL-A, eepL-B or uepROW)");
+    return sc;
+}
+
+// a file's bytes, or n random ones; read cyclically
+struct ByteSource {
+    std::vector<uint8_t> bytes;
+    size_t at = 0;
+    ByteSource(const std::string& filename, std::mt19937_64& rng, size_t n_random) {
+        if (filename.empty()) {
+            bytes.resize(n_random);
+            for (auto& b : bytes) b = (uint8_t)(rng() & 0xFF);
+            return;
+        }
+        FILE* fp = fopen(filename.c_str(), "rb");
+        if (!fp) throw std::runtime_error("Failed to open input file: '" + filename + "'");
+        uint8_t buf[65536];
+        for (size_t n; (n = fread(buf, 1, sizeof(buf), fp)) > 0;) bytes.insert(bytes.end(), buf, buf + n);
+        fclose(fp);
+        if (bytes.empty()) throw std::runtime_error("Input file is empty: '" + filename + "'");
+    }
+    void read(uint8_t* dst, size_t n) { for (size_t i = 0; i < n; i++) { dst[i] = bytes[at]; at = (at + 1) % bytes.size(); } }
+};
+
+// frames channel coded on the device from the FIB bodies and the payload; mode I
+static int run_coded(const Args& args, FILE* fp_out) {
+    if (args.transmission_mode != 1) throw std::runtime_error("channel-coded frames are transmission mode I only");
+    const int n_sub = (int)args.subchannels.size();
+    dabgpu_tx_bank* bank = nullptr;
+    int st = dabgpu_tx_bank_create(dabgpu_shared_context(), 1, n_sub ? args.subchannels.data() : nullptr, n_sub, &bank);
+    if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the channel encoder: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); return 1; }
+    std::vector<dabgpu_tx_sub_plan> plans((size_t)n_sub + 1);
+    uint32_t cif_in = 0;
+    dabgpu_tx_encode_plan(n_sub ? args.subchannels.data() : nullptr, n_sub, plans.data(), &cif_in, nullptr, 0, nullptr, nullptr);
+    std::mt19937_64 rng(args.seed);
+    // (random data: 64 frames' worth, then it repeats)
+    ByteSource fibs(args.fib_filename, rng, 64 * 360), payload(args.payload_filename, rng, 64 * 4 * (size_t)cif_in + 1);
+    const float frequency_norm = (args.frequency != 0.0f) ? args.frequency / 2.048e6f : 0.0f;
+    std::vector<uint8_t> fib(360), pay(4 * (size_t)cif_in + 4), quantised(2 * (size_t)DABGPU_NB_FRAME_SAMPLES);
+    int rc = 0;
+    for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
+        fibs.read(fib.data(), 360);
+        payload.read(pay.data(), 4 * (size_t)cif_in);
+        st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
+        if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); rc = 1; break; }
+        const size_t nb_write = fwrite(quantised.data(), 2, DABGPU_NB_FRAME_SAMPLES, fp_out);
+        if (nb_write != DABGPU_NB_FRAME_SAMPLES) { fprintf(stderr, "Failed to write out frame %zu/%d\n", nb_write, DABGPU_NB_FRAME_SAMPLES); break; }
+    }
+    dabgpu_tx_bank_destroy(bank);
+    return rc;
+}
 
 static void usage(const char* argv0) {
     fprintf(stderr, "usage: %s [-m|--transmission-mode 1..4] [-f|--frequency HZ] [-o|--output FILE] [--frames N]\n"
-                    "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout)\n", argv0);
+                    "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
+                    "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
+                    "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data\n", argv0);
 }
 
 static bool parse_args(int argc, char** argv, Args& args) {
@@ -57,6 +134,10 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "-f" || a == "--frequency") args.frequency = std::stof(value());
         else if (a == "-o" || a == "--output") args.output_filename = value();
         else if (a == "--frames") args.frames = std::stoll(value());
+        else if (a == "--subchannel") { args.subchannels.push_back(parse_subchannel(value())); args.coded = true; }
+        else if (a == "--fib-file") { args.fib_filename = value(); args.coded = true; }
+        else if (a == "--payload-file") { args.payload_filename = value(); args.coded = true; }
+        else if (a == "--seed") { args.seed = std::stoull(value()); args.coded = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
     }
@@ -84,6 +165,12 @@ int main(int argc, char** argv) {
     }
 
     try {
+        if (args.coded) {
+            const int rc = run_coded(args, fp_out);
+            if (fp_out != stdout) fclose(fp_out);
+            else fflush(fp_out);
+            return rc;
+        }
         const auto params = get_DAB_OFDM_params(args.transmission_mode);
         auto prs_fft_ref = std::vector<std::complex<float>>(params.nb_fft);
         get_DAB_PRS_reference(args.transmission_mode, prs_fft_ref);

@@ -856,6 +856,67 @@ int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx *ctx, int transmission_mode
                                           size_t n_frames, const float *h_prs_fft_ref, float freq_norm, void *h_out, int out_format);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Channel encoder (mode I): FIB bodies and sub-channel bytes -> the frame's hard bits (DABGPU_TX_PAYLOAD_FRAME_BITS) -> IQ.
+ * ETSI EN 300 401 in the transmit direction; the reference has no channel encoder, the results are pinned to oracle/ and to this
+ * library's own decoders (tests/test_gpu_tx_encode.py).
+ *
+ * dabgpu_tx_encode_plan (host only, no device): the encoding plan of a multiplex.  plans[0 .. n_sub - 1] describe the sub-channels in
+ * list order, plans[n_sub] the FIB group (clause 11.2: PI_16 x 21 blocks, PI_15 x 3 blocks, tail PI_X; 96 bytes in, 2304 bits out).
+ *   in_offset / in_bytes     the sub-channel's bytes inside one CIF's input record (back to back in list order, as
+ *                            dabgpu_decode_frames_layout returns them); *cif_in_bytes = their sum
+ *   seg_pi / seg_blocks      clause 11.3: blocks of 128 mother bits punctured with PI (tables 7, 9, 10 as dabgpu_subchannel_plan derives them)
+ *   n_words                  32-bit words of input = sum of seg_blocks; the code word's schedule has n_words + 1 entries, the last the tail
+ *   kept_bits                bits that survive puncturing (<= length * 64; the capacity units' remaining bits are 0)
+ *   sched_offset             first entry of the sub-channel's kept-bit schedule in sched[]; sub-channels with the same segments share one
+ *   ring_offset / ring_row_dwords   where the time interleaver's state of the sub-channel sits inside one ring slot (below)
+ * sched[k] = {out_bit, keep_mask}: input word w = k - sched_offset yields mother bits 128 w .. 128 w + 127 (4 per input bit, clause
+ * 11.1.1, generators 133 171 145 133); of each run of 32, those whose bit is set in keep_mask are kept in order and placed from bit
+ * out_bit + (run index) * popcount(keep_mask) of the code word on.  The tail entry covers the 24 mother bits of the six zero bits only.
+ * Call with sched = NULL (or too small a sched_capacity) to learn *n_sched; plans must hold n_sub + 1 entries.
+ * DABGPU_ERR_INVALID_ARG: a sub-channel outside 0..864 CU, two that overlap, more than 64, a bad protection index, a profile whose code
+ * word does not fit its capacity units (table 8's row 34 as listed).  n_sub = 0 is legal: FIC only. */
+typedef struct {
+    uint32_t start_address, length;       /* capacity units */
+    uint32_t in_offset, in_bytes;
+    uint32_t seg_pi[4], seg_blocks[4];
+    uint32_t n_words, kept_bits;
+    uint32_t sched_offset;
+    uint32_t ring_offset, ring_row_dwords;
+} dabgpu_tx_sub_plan;
+typedef struct { uint32_t out_bit, keep_mask; } dabgpu_tx_sched_entry;
+int dabgpu_tx_encode_plan(const dabgpu_subchannel *subs, int n_sub, dabgpu_tx_sub_plan *plans, uint32_t *cif_in_bytes,
+                          dabgpu_tx_sched_entry *sched, size_t sched_capacity, size_t *n_sched, uint32_t *ring_slot_dwords);
+
+/* Encoder bank: n_ensembles transmitters sharing one multiplex configuration, their time-interleaver state on the device.
+ *   FIB CRC16 (5.2.1) -> energy dispersal (10) -> K = 7 rate-1/4 convolutional code with zero tail (11.1) -> puncturing (11.2 FIC,
+ *   11.3 MSC) -> 16-CIF time interleaving (12) -> the frame's 230400 bits.
+ *   d_fib_data   [n_ensembles][F][4][3][30] FIB bodies; the encoder appends each CRC
+ *   d_payload    [n_ensembles][F][4][cif_in_bytes] (4-byte aligned; may be NULL when n_sub = 0)
+ *   d_frame_bits [n_ensembles][F] frames of 28800 bytes, frame_stride bytes apart (0 = 28800; a multiple of 16), 16-byte aligned: bit i
+ *                of the frame in byte i / 8, bit i % 8, as dabgpu_soft_bits_to_hard_bytes writes them and DABGPU_TX_PAYLOAD_FRAME_BITS reads
+ * Bit i of logical frame r of a sub-channel is sent in CIF r + {0,8,4,12,2,10,6,14,1,9,5,13,3,11,7,15}[i % 16]; bits whose logical
+ * frame lies before the bank's first frame (or its last reset) are 0, and so are capacity units no sub-channel occupies and a
+ * sub-channel's bits beyond its code word.  A call with F frames equals F calls with one.  The frame counter lives on the device:
+ * a steady-state call enqueues kernels only and may be captured in a HIP graph; replays continue the sequence.
+ * Arguments are checked before any device call.  One bank = one stream at a time. */
+typedef struct dabgpu_tx_bank dabgpu_tx_bank;
+int dabgpu_tx_bank_create(dabgpu_ctx *ctx, size_t n_ensembles, const dabgpu_subchannel *subs, int n_sub, dabgpu_tx_bank **out);
+void dabgpu_tx_bank_destroy(dabgpu_tx_bank *bank);
+int dabgpu_tx_bank_reset(dabgpu_tx_bank *bank, void *stream);
+int dabgpu_tx_bank_encode_frames(dabgpu_tx_bank *bank, const uint8_t *d_fib_data, const uint8_t *d_payload, size_t n_frames_per_ensemble,
+                                 uint8_t *d_frame_bits, size_t frame_stride, void *stream);
+/* the encoder followed by dabgpu_ofdm_modulate_frames(mode I, DABGPU_TX_PAYLOAD_FRAME_BITS) on the same stream, through frame bits the
+ * bank owns (sized at creation for one frame per ensemble; a call with more grows them, which a capture refuses): d_out
+ * [n_ensembles][F][196608] samples in out_format (DABGPU_IQ_RAW_F32L / _U8), identical to the two calls made separately */
+int dabgpu_tx_bank_transmit_frames(dabgpu_tx_bank *bank, const uint8_t *d_fib_data, const uint8_t *d_payload, size_t n_frames_per_ensemble,
+                                   float freq_norm, void *d_out, int out_format, void *stream);
+/* the same from and to host memory, on the context's stream; h_frame_bits [n_ensembles][F][28800] */
+int dabgpu_tx_bank_encode_frames_host_sync(dabgpu_tx_bank *bank, const uint8_t *h_fib_data, const uint8_t *h_payload,
+                                           size_t n_frames_per_ensemble, uint8_t *h_frame_bits);
+int dabgpu_tx_bank_transmit_frames_host_sync(dabgpu_tx_bank *bank, const uint8_t *h_fib_data, const uint8_t *h_payload,
+                                             size_t n_frames_per_ensemble, float freq_norm, void *h_out, int out_format);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Ingest pipe: the host -> device hand-over of capture bytes.  Replaces the reader thread -> OFDM_Demod::Process hand-over
  * of examples/app_helpers/app_ofdm_blocks.h:45-58 and the memcpy of OFDM_Demod::ReadSymbols (src/ofdm/ofdm_demodulator.cpp:550-577).
  * A ring of `depth` PINNED host buffers with device twins and a copy stream of its own:
