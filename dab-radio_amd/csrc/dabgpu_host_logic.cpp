@@ -683,3 +683,15 @@ extern "C" int dabgpu_tx_encode_plan(const dabgpu_subchannel* subs, int n_sub, d
     if (sched && sched_capacity >= P.sched.size()) memcpy(sched, P.sched.data(), P.sched.size() * sizeof(dabgpu_tx_sched_entry));
     return DABGPU_OK;
 }
+
+extern "C" int dabgpu_dabplus_superframe_layout(uint32_t frame_bytes, uint8_t descriptor, const uint16_t* au_len, uint16_t* au_start, int* num_aus,
+                                                uint32_t* n_rs) {
+    if (!au_len) return -1;
+    uint32_t start[7], nrs;
+    int na;
+    const int st = dabgpu_dabplus_layout(frame_bytes, descriptor, au_len, start, &na, &nrs);
+    if (num_aus) *num_aus = na;
+    if (n_rs) *n_rs = nrs;
+    if (st == 0 && au_start) for (int i = 0; i < 7; i++) au_start[i] = (uint16_t)start[i];       // <= 110 x 64 = 7040
+    return st;
+}

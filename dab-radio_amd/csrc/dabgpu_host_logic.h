@@ -193,3 +193,23 @@ struct dabgpu_tx_plan {
 };
 // DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason in dabgpu_last_error
 int dabgpu_host_tx_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_plan* out);
+
+// ---- DAB+ super-frame encoder (dabplus_tx.hip; include/dabgpu.h, dabgpu_dabplus_superframe_layout) ----
+// Where the access units of a super frame start (ETSI TS 102 563 5.2, as AAC_Frame_Processor reads it back, aac_frame_processor.cpp:266-283),
+// one body for the host entry point and the kernel.  au_len: the first num_aus entries are read; start[0 .. num_aus] are written, the rest
+// of start[7] zeroed.  0, or DABGPU_DABPLUS_TX_BAD_FRAME_SIZE / _BAD_FILL / _BAD_START (then start[] holds no layout).
+DABGPU_HD inline int dabgpu_dabplus_layout(uint32_t frame_bytes, uint32_t descriptor, const uint16_t* au_len, uint32_t* start, int* num_aus,
+                                           uint32_t* n_rs) {
+    *num_aus = 0; *n_rs = 0;
+    for (int i = 0; i < 7; i++) start[i] = 0;
+    if (frame_bytes < 24u || frame_bytes > 1536u || frame_bytes % 24u) return DABGPU_DABPLUS_TX_BAD_FRAME_SIZE;
+    const int dac_rate = (descriptor >> 6) & 1, sbr = (descriptor >> 5) & 1;
+    const int na = dac_rate ? (sbr ? 3 : 6) : (sbr ? 2 : 4);                     // :275-279
+    *num_aus = na; *n_rs = frame_bytes / 24u;
+    uint32_t s = 3u + (12u * (uint32_t)(na - 1) + 7u) / 8u;
+    start[0] = s;
+    for (int i = 0; i < 6; i++) if (i < na) { s += (uint32_t)au_len[i] + 2u; start[i + 1] = s; }      // at most 6 x 65537 + 11
+    if (s != 110u * *n_rs) return DABGPU_DABPLUS_TX_BAD_FILL;
+    for (int i = 1; i < 6; i++) if (i < na && start[i] > 4095u) return DABGPU_DABPLUS_TX_BAD_START;
+    return 0;
+}

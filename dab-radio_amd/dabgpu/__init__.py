@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "dabgpu_ofdm_modulate_frames", "dabgpu_ofdm_modulate_frames_host_sync",
     "dabgpu_tx_encode_plan", "dabgpu_tx_bank_create", "dabgpu_tx_bank_destroy", "dabgpu_tx_bank_reset", "dabgpu_tx_bank_encode_frames",
     "dabgpu_tx_bank_transmit_frames", "dabgpu_tx_bank_encode_frames_host_sync", "dabgpu_tx_bank_transmit_frames_host_sync",
+    "dabgpu_dabplus_superframe_layout", "dabgpu_dabplus_tx_encode", "dabgpu_dabplus_tx_encode_host_sync",
 ]
 
 # OFDM transmitter payload layouts (include/dabgpu.h)
@@ -290,6 +291,11 @@ def lib():
         L.dabgpu_tx_bank_transmit_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
         L.dabgpu_tx_bank_encode_frames_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.dabgpu_tx_bank_transmit_frames_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_int]
+        L.dabgpu_dabplus_superframe_layout.argtypes = [C.c_uint32, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_dabplus_tx_encode.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dabgpu_dabplus_tx_encode_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                         C.c_void_p]
         _lib = L
     return _lib
 
@@ -731,6 +737,64 @@ class TxBank:
         check(lib().dabgpu_tx_bank_transmit_frames_host_sync(self._h, _ptr(fib), _ptr(pay), n_frames, float(freq_norm), _ptr(out), fmt),
               "dabgpu_tx_bank_transmit_frames_host_sync")
         return out
+
+
+class DabPlusTx:
+    """the DAB+ super-frame encoder (dabgpu_dabplus_tx_*): access units -> the logical frames of DAB+ sub-channels; stateless"""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+
+    @staticmethod
+    def layout(frame_bytes, descriptor, au_len):
+        """dabgpu_dabplus_superframe_layout (host only) -> (status, au_start[7] or None, num_aus, n_rs)"""
+        import numpy as np
+        lens = np.zeros(6, np.uint16)
+        au_len = np.asarray(au_len, np.uint16).ravel()[:6]
+        lens[:au_len.size] = au_len
+        start = np.zeros(7, np.uint16)
+        na, n_rs = C.c_int(0), C.c_uint32(0)
+        st = lib().dabgpu_dabplus_superframe_layout(int(frame_bytes), int(descriptor) & 0xFF, _ptr(lens), _ptr(start), C.byref(na), C.byref(n_rs))
+        return st, (start if st == 0 else None), na.value, n_rs.value
+
+    def encode(self, n_streams, n_superframes, au_bytes, au_offsets, au_len, descriptor, frame_bytes, frames, stream_offsets, frame_stride,
+               status, stream=None):
+        """device buffers: au_offsets uint64 [S][K], au_len uint16 [S][K][6], descriptor uint8 [S][K], frame_bytes uint32 [S], stream_offsets
+        uint64 [S], status int32 [S][K]; logical frame 5 k + j of stream s -> frames + stream_offsets[s] + (5 k + j) frame_stride (asynchronous)"""
+        check(lib().dabgpu_dabplus_tx_encode(self._ctx._h, n_streams, n_superframes, _ptr(au_bytes), _ptr(au_offsets), _ptr(au_len), _ptr(descriptor),
+                                             _ptr(frame_bytes), _ptr(frames), _ptr(stream_offsets), frame_stride, _ptr(status),
+                                             Context._stream(stream)), "dabgpu_dabplus_tx_encode")
+
+    def encode_host(self, frame_bytes, superframes):
+        """one stream: superframes = [(descriptor, [access-unit payloads]), ...] -> (uint8 [5 K][frame_bytes], int32 status [K])"""
+        import numpy as np
+        K = len(superframes)
+        offs, lens, desc = np.zeros(K, np.uint64), np.zeros((K, 6), np.uint16), np.zeros(K, np.uint8)
+        blob, off = [np.zeros(0, np.uint8)], 0
+        for k, (d, aus) in enumerate(superframes):
+            desc[k], offs[k] = d, off
+            for a, p in enumerate(aus[:6]):
+                p = np.ascontiguousarray(p, dtype=np.uint8)
+                lens[k, a] = p.size
+                blob.append(p)
+                off += p.size
+        au = np.concatenate(blob + [np.zeros(1, np.uint8)])
+        frames = np.full((5 * K, int(frame_bytes)), 0xA5, np.uint8)
+        status = np.full(K, -1, np.int32)
+        check(lib().dabgpu_dabplus_tx_encode_host_sync(self._ctx._h, K, _ptr(au), _ptr(offs), _ptr(lens), _ptr(desc), int(frame_bytes), _ptr(frames),
+                                                       _ptr(status)), "dabgpu_dabplus_tx_encode_host_sync")
+        return frames, status
+
+
+def dabplus_tx_offsets(tx_bank, subchannel_indices, n_frames=5):
+    """where DabPlusTx.encode writes into a TxBank payload [n][n_frames][4][cif_in_bytes] so that the bank reads the sub-channels' logical frames:
+    (stream_offsets uint64 [n * len(subchannel_indices)], ensemble major, frame_stride, frame_bytes uint32 of the same shape).  4 n_frames is a
+    multiple of 5 when whole super frames fill the payload (n_frames = 5, n_superframes = 4)."""
+    import numpy as np
+    cif = tx_bank.cif_in_bytes
+    offs = [e * 4 * n_frames * cif + tx_bank.plan["subs"][i].in_offset for e in range(tx_bank.n) for i in subchannel_indices]
+    sizes = [tx_bank.plan["subs"][i].in_bytes for _ in range(tx_bank.n) for i in subchannel_indices]
+    return np.array(offs, np.uint64), cif, np.array(sizes, np.uint32)
 
 
 class IngestPipe:

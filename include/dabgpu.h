@@ -917,6 +917,53 @@ int dabgpu_tx_bank_transmit_frames_host_sync(dabgpu_tx_bank *bank, const uint8_t
                                              size_t n_frames_per_ensemble, float freq_norm, void *h_out, int out_format);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * DAB+ super-frame encoder: AAC access units -> the bytes of a DAB+ sub-channel, five logical frames per super frame.  ETSI TS 102 563
+ * clauses 5.2 and 6 in the transmit direction; the consumer is AAC_Frame_Processor (src/dab/audio/aac_frame_processor.cpp:201-320, on the
+ * device dabgpu_dabplus_bank_process), which hands the access units back.  Per super frame:
+ *   byte 2 = descriptor (rfa | dac_rate | sbr_flag | aac_channel_mode | ps_flag | mpeg_surround_config(3)), then the 12-bit au_start[1 ..
+ *   num_aus - 1] packed MSB first (5.2, table 2); the access units at their starts, each followed by its CRC-16-CCITT (start value 0xFFFF,
+ *   inverted, MSB first; 5.3.2); the fire code of bytes 2..10 in bytes 0..1; RS(120,110) parity over GF(2^8), p(x) = x^8+x^4+x^3+x^2+1,
+ *   roots alpha^0..alpha^9, shortened by 135: code word i = bytes i + j n_rs, j = 0..109, its parity at i + (110 + j) n_rs (6);
+ *   the 120 n_rs bytes cut into five logical frames of frame_bytes.
+ *
+ * dabgpu_dabplus_superframe_layout (host only, no device): where the access units go.  num_aus follows (dac_rate, sbr_flag) of the
+ * descriptor as aac_frame_processor.cpp:275-279 reads them (2, 3, 4 or 6), n_rs = frame_bytes / 24, au_start[0] = 3 + ceil(12 (num_aus - 1)
+ * / 8), au_start[i + 1] = au_start[i] + au_len[i] + 2; au_len[i] = 0 is legal (the reference's walk accepts it).  Returns 0 and writes
+ * au_start[0 .. num_aus] (the rest of au_start[7] zero), or, with au_start untouched,
+ *   DABGPU_DABPLUS_TX_BAD_FRAME_SIZE  frame_bytes is not a multiple of 24 in 24..1536 (*num_aus = *n_rs = 0)
+ *   DABGPU_DABPLUS_TX_BAD_FILL        au_start[num_aus] != 110 n_rs: the last unit's end is implied by the syntax (:282)
+ *   DABGPU_DABPLUS_TX_BAD_START       an au_start[1 .. num_aus - 1] above 4095 does not fit its 12-bit field (possible from n_rs = 38 on)
+ * in this order; -1 for a NULL au_len.  au_len holds at least num_aus lengths; au_start, num_aus, n_rs may be NULL. */
+enum { DABGPU_DABPLUS_TX_BAD_FRAME_SIZE = 1, DABGPU_DABPLUS_TX_BAD_FILL = 2, DABGPU_DABPLUS_TX_BAD_START = 3 };
+int dabgpu_dabplus_superframe_layout(uint32_t frame_bytes, uint8_t descriptor, const uint16_t *au_len, uint16_t *au_start, int *num_aus,
+                                     uint32_t *n_rs);
+/* n_superframes whole super frames for each of n_streams streams (a stream = an (ensemble, sub-channel) pair); stateless.
+ *   d_au_bytes     the payloads (without CRCs) of the access units of super frame k of stream s back to back from d_au_offsets[s][k] on
+ *   d_au_len       [n_streams][n_superframes][6] payload bytes; entries from num_aus on are ignored
+ *   d_descriptor   [n_streams][n_superframes];  d_frame_bytes [n_streams]
+ *   d_frames       logical frame 5 k + j of stream s goes to d_frames + d_stream_offsets[s] + (5 k + j) frame_stride_bytes -- the layout
+ *                  dabgpu_dabplus_bank_process reads.  d_frames, the stream offsets and the stride are multiples of 4, frame_stride_bytes >=
+ *                  the stream's frame bytes (a stream offset that is not, which the host cannot see, costs byte stores instead of dword
+ *                  stores and changes no result).  Only the stream's own frame_bytes bytes per frame are written.  With d_frames a dabgpu_tx_bank
+ *                  payload [ens][F][4][cif_in_bytes], d_stream_offsets[s] = e 4 F cif_in_bytes + plan.in_offset, frame_stride_bytes =
+ *                  cif_in_bytes, F = 5 and n_superframes = 4 (20 CIFs: the common period of super frames and transmission frames) the
+ *                  result is what dabgpu_tx_bank_encode_frames / _transmit_frames read.
+ *   d_status       [n_streams][n_superframes]: 0, or the code dabgpu_dabplus_superframe_layout returns for the super frame; a refused
+ *                  super frame's five logical frames are written as zeros (which give the receiver a header and no access unit) -- for
+ *                  DABGPU_DABPLUS_TX_BAD_FRAME_SIZE the first min(frame_bytes, 1536) bytes of each
+ * Asynchronous on `stream`; kernel launches only, so the call may be captured in a HIP graph.  A NULL context, n_superframes < 0, a stride
+ * or d_frames that is not a multiple of 4, more than 2^30 super frames, or a NULL pointer with n_streams n_superframes > 0 returns
+ * DABGPU_ERR_INVALID_ARG before any device call; n_streams = 0 and n_superframes = 0 are legal and do nothing. */
+int dabgpu_dabplus_tx_encode(dabgpu_ctx *ctx, size_t n_streams, int n_superframes, const uint8_t *d_au_bytes, const uint64_t *d_au_offsets,
+                             const uint16_t *d_au_len, const uint8_t *d_descriptor, const uint32_t *d_frame_bytes, uint8_t *d_frames,
+                             const uint64_t *d_stream_offsets, size_t frame_stride_bytes, int32_t *d_status, void *stream);
+/* one stream from and to host memory, on the context's stream: h_au_offsets [n_superframes], h_au_len [n_superframes][6], h_descriptor
+ * [n_superframes]; h_frames [5 n_superframes][frame_bytes] back to back; h_status [n_superframes].  Returns when they are written. */
+int dabgpu_dabplus_tx_encode_host_sync(dabgpu_ctx *ctx, int n_superframes, const uint8_t *h_au_bytes, const uint64_t *h_au_offsets,
+                                       const uint16_t *h_au_len, const uint8_t *h_descriptor, uint32_t frame_bytes, uint8_t *h_frames,
+                                       int32_t *h_status);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Ingest pipe: the host -> device hand-over of capture bytes.  Replaces the reader thread -> OFDM_Demod::Process hand-over
  * of examples/app_helpers/app_ofdm_blocks.h:45-58 and the memcpy of OFDM_Demod::ReadSymbols (src/ofdm/ofdm_demodulator.cpp:550-577).
  * A ring of `depth` PINNED host buffers with device twins and a copy stream of its own:
