@@ -695,3 +695,88 @@ extern "C" int dabgpu_dabplus_superframe_layout(uint32_t frame_bytes, uint8_t de
     if (st == 0 && au_start) for (int i = 0; i < 7; i++) au_start[i] = (uint16_t)start[i];       // <= 110 x 64 = 7040
     return st;
 }
+
+// ---- channel model (include/dabgpu.h, "Channel model") ----
+int dabgpu_host_channel_plan(const dabgpu_channel_stream* params, size_t n_streams, dabgpu_channel_geometry* out) {
+    if (out) *out = dabgpu_channel_geometry{0, DABGPU_CHANNEL_BLOCK, 0, 0};
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("channel_plan: %zu streams (1..1048576 are accepted)", n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (!params) { dabgpu_set_error("channel_plan: null parameters"); return DABGPU_ERR_INVALID_ARG; }
+    uint32_t halo = 0, staged = 0;
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_channel_stream& P = params[s];
+        if (P.n_taps < 1 || P.n_taps > DABGPU_CHANNEL_MAX_TAPS) {
+            dabgpu_set_error("channel_plan: stream %zu: %d taps (1..%d are accepted)", s, P.n_taps, DABGPU_CHANNEL_MAX_TAPS); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (!std::isfinite(P.gain)) { dabgpu_set_error("channel_plan: stream %zu: gain is not finite", s); return DABGPU_ERR_INVALID_ARG; }
+        if (!std::isfinite(P.noise_sigma)) { dabgpu_set_error("channel_plan: stream %zu: noise_sigma is not finite", s); return DABGPU_ERR_INVALID_ARG; }
+        if (P.noise_sigma < 0.0f) { dabgpu_set_error("channel_plan: stream %zu: noise_sigma is negative", s); return DABGPU_ERR_INVALID_ARG; }
+        if (P.start > DABGPU_CHANNEL_MAX_POSITION || P.start < -DABGPU_CHANNEL_MAX_POSITION) {
+            dabgpu_set_error("channel_plan: stream %zu: start outside +-2^62", s); return DABGPU_ERR_INVALID_ARG;
+        }
+        for (int k = 0; k < P.n_taps; k++) {
+            if (P.tap_delay[k] < 0 || P.tap_delay[k] > DABGPU_CHANNEL_MAX_DELAY) {
+                dabgpu_set_error("channel_plan: stream %zu: tap %d: delay %d (0..%d are accepted)", s, k, P.tap_delay[k], DABGPU_CHANNEL_MAX_DELAY);
+                return DABGPU_ERR_INVALID_ARG;
+            }
+            if (!std::isfinite(P.tap_re[k]) || !std::isfinite(P.tap_im[k])) {
+                dabgpu_set_error("channel_plan: stream %zu: tap %d is not finite", s, k); return DABGPU_ERR_INVALID_ARG;
+            }
+            halo = std::max(halo, ((uint32_t)P.tap_delay[k] + 1u) & ~1u);
+        }
+        if (!(P.n_taps == 1 && P.tap_delay[0] == 0)) staged = 1;
+    }
+    if (out) {
+        out->halo = halo; out->staged = staged;
+        out->lds_bytes = staged ? (DABGPU_CHANNEL_BLOCK + halo + 2u) * 8u : 0u;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_channel_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_in, size_t n_out,
+                                    const void* out, int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers) {
+    if (out_format != DABGPU_IQ_RAW_F32L && out_format != DABGPU_IQ_RAW_U8) {
+        dabgpu_set_error("%s: output format %d (DABGPU_IQ_RAW_F32L or DABGPU_IQ_RAW_U8 only)", who, out_format); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_in == 0 || n_in > ((size_t)1 << 40)) { dabgpu_set_error("%s: n_in = %zu (1..2^40 are accepted)", who, n_in); return DABGPU_ERR_INVALID_ARG; }
+    if (n_out > ((size_t)1 << 31)) { dabgpu_set_error("%s: n_out = %zu (up to 2^31 per call)", who, n_out); return DABGPU_ERR_INVALID_ARG; }
+    if (!in || (n_out > 0 && !out)) { dabgpu_set_error("%s: null input / output", who); return DABGPU_ERR_INVALID_ARG; }
+    if (in_stride_samples != 0 && (in_stride_samples < n_in || ((in_stride_samples & 1) && device_pointers))) {
+        dabgpu_set_error("%s: in_stride_samples must be 0 (one shared input) or an even count >= n_in", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    const size_t exact = n_out * (out_format == DABGPU_IQ_RAW_F32L ? 8u : 2u);
+    const size_t row = device_pointers ? (exact + 15u) & ~(size_t)15 : exact;
+    if (*out_stride_bytes == 0) *out_stride_bytes = row;
+    if ((device_pointers && (*out_stride_bytes & 15)) || *out_stride_bytes < row) {
+        dabgpu_set_error("%s: out_stride_bytes must be 0 or a multiple of 16 that holds n_out samples", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (device_pointers && (((uintptr_t)in & 15) || ((uintptr_t)out & 15))) { dabgpu_set_error("%s: input and output must be 16-byte aligned", who); return DABGPU_ERR_INVALID_ARG; }
+    if (out_format == DABGPU_IQ_RAW_U8 && !std::isfinite(u8_scale)) { dabgpu_set_error("%s: u8_scale is not finite", who); return DABGPU_ERR_INVALID_ARG; }
+    const size_t tiles = (n_out + 3 + DABGPU_CHANNEL_BLOCK - 1) / DABGPU_CHANNEL_BLOCK;
+    if (tiles * n_streams > 0x7FFFFFFFull) { dabgpu_set_error("%s: n_streams x n_out too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_channel_fits(const dabgpu_channel_geometry& created, const dabgpu_channel_geometry& wanted) {
+    if (wanted.staged && !created.staged) {
+        dabgpu_set_error("channel_bank_set_params: the bank was created for single zero-delay taps; these parameters need the staged kernel "
+                         "(create the bank with its widest parameters)");
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (wanted.halo > created.halo) {
+        dabgpu_set_error("channel_bank_set_params: largest delay needs a halo of %u samples, the bank was created with %u", wanted.halo, created.halo);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channel_plan(const dabgpu_channel_stream* params, size_t n_streams, dabgpu_channel_geometry* out) {
+    return dabgpu_host_channel_plan(params, n_streams, out);
+}
+
+extern "C" uint64_t dabgpu_channel_freq_q64(double cycles) {
+    if (!(cycles >= -0.5 && cycles <= 0.5)) return 0;                       // (NaN included)
+    const double scaled = std::nearbyint(std::ldexp(cycles, 64));            // in [-2^63, 2^63], exact scaling
+    return scaled < 0.0 ? (uint64_t)(int64_t)scaled : (uint64_t)scaled;     // two's complement: -f and 2^64 - f are one frequency
+}
+
+extern "C" double dabgpu_channel_freq_cycles(uint64_t freq_q64) { return std::ldexp((double)(int64_t)freq_q64, -64); }

@@ -194,6 +194,18 @@ struct dabgpu_tx_plan {
 // DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason in dabgpu_last_error
 int dabgpu_host_tx_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_plan* out);
 
+// ---- channel model planner (channel.hip launches from it; include/dabgpu.h, dabgpu_channel_plan) ----
+// DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream index, field) in dabgpu_last_error
+int dabgpu_host_channel_plan(const dabgpu_channel_stream* params, size_t n_streams, dabgpu_channel_geometry* out);
+// dabgpu_channel_bank_set_params: the launch geometry (kernel variant, LDS size) is the one of the bank's creation -- a captured call has it
+// baked in -- so new parameters must fit it: DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason
+int dabgpu_host_channel_fits(const dabgpu_channel_geometry& created, const dabgpu_channel_geometry& wanted);
+// the arguments of a dabgpu_channel_bank_apply call (no device address is dereferenced): `who` names the entry point in the message;
+// *out_stride_bytes = 0 is replaced by the default.  device_pointers = false (the host form): no alignment rule, rows of any length >= n_out
+// samples, the default stride is the row itself
+int dabgpu_host_channel_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_in, size_t n_out,
+                                    const void* out, int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers = true);
+
 // ---- DAB+ super-frame encoder (dabplus_tx.hip; include/dabgpu.h, dabgpu_dabplus_superframe_layout) ----
 // Where the access units of a super frame start (ETSI TS 102 563 5.2, as AAC_Frame_Processor reads it back, aac_frame_processor.cpp:266-283),
 // one body for the host entry point and the kernel.  au_len: the first num_aus entries are read; start[0 .. num_aus] are written, the rest

@@ -73,7 +73,14 @@ ABI_SYMBOLS = [
     "dabgpu_tx_encode_plan", "dabgpu_tx_bank_create", "dabgpu_tx_bank_destroy", "dabgpu_tx_bank_reset", "dabgpu_tx_bank_encode_frames",
     "dabgpu_tx_bank_transmit_frames", "dabgpu_tx_bank_encode_frames_host_sync", "dabgpu_tx_bank_transmit_frames_host_sync",
     "dabgpu_dabplus_superframe_layout", "dabgpu_dabplus_tx_encode", "dabgpu_dabplus_tx_encode_host_sync",
+    "dabgpu_channel_plan", "dabgpu_channel_freq_q64", "dabgpu_channel_freq_cycles", "dabgpu_channel_bank_create", "dabgpu_channel_bank_destroy",
+    "dabgpu_channel_bank_set_params", "dabgpu_channel_bank_seek", "dabgpu_channel_bank_apply", "dabgpu_channel_bank_apply_host_sync",
 ]
+
+# channel model (include/dabgpu.h)
+CHANNEL_MAX_TAPS = 8
+CHANNEL_MAX_DELAY = 2047
+CHANNEL_BLOCK = 1024
 
 # OFDM transmitter payload layouts (include/dabgpu.h)
 TX_PAYLOAD_REFERENCE = 0
@@ -117,6 +124,18 @@ class TxSubPlan(C.Structure):
     _fields_ = [("start_address", C.c_uint32), ("length", C.c_uint32), ("in_offset", C.c_uint32), ("in_bytes", C.c_uint32),
                 ("seg_pi", C.c_uint32 * 4), ("seg_blocks", C.c_uint32 * 4), ("n_words", C.c_uint32), ("kept_bits", C.c_uint32),
                 ("sched_offset", C.c_uint32), ("ring_offset", C.c_uint32), ("ring_row_dwords", C.c_uint32)]
+
+
+class ChannelStream(C.Structure):
+    """dabgpu_channel_stream"""
+    _fields_ = [("freq_q64", C.c_uint64), ("phase0_q64", C.c_uint64), ("start", C.c_int64), ("seed", C.c_uint64),
+                ("gain", C.c_float), ("noise_sigma", C.c_float), ("n_taps", C.c_int32), ("tap_delay", C.c_int32 * 8),
+                ("tap_re", C.c_float * 8), ("tap_im", C.c_float * 8), ("reserved", C.c_int32)]
+
+
+class ChannelGeometry(C.Structure):
+    """dabgpu_channel_geometry"""
+    _fields_ = [("halo", C.c_uint32), ("block_samples", C.c_uint32), ("lds_bytes", C.c_uint32), ("staged", C.c_uint32)]
 
 
 class SyncCfg(C.Structure):
@@ -296,6 +315,20 @@ def lib():
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.dabgpu_dabplus_tx_encode_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                          C.c_void_p]
+        L.dabgpu_channel_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_channel_freq_q64.argtypes = [C.c_double]
+        L.dabgpu_channel_freq_q64.restype = C.c_uint64
+        L.dabgpu_channel_freq_cycles.argtypes = [C.c_uint64]
+        L.dabgpu_channel_freq_cycles.restype = C.c_double
+        L.dabgpu_channel_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_channel_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_channel_bank_destroy.restype = None
+        L.dabgpu_channel_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_channel_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_channel_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t,
+                                                C.c_float, C.c_void_p]
+        L.dabgpu_channel_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                                                          C.c_size_t, C.c_float]
         _lib = L
     return _lib
 
@@ -737,6 +770,77 @@ class TxBank:
         check(lib().dabgpu_tx_bank_transmit_frames_host_sync(self._h, _ptr(fib), _ptr(pay), n_frames, float(freq_norm), _ptr(out), fmt),
               "dabgpu_tx_bank_transmit_frames_host_sync")
         return out
+
+
+def channel_stream(taps=((0, 1.0, 0.0),), cycles_per_sample=0.0, phase0_cycles=0.0, start=0, seed=0, gain=1.0, noise_sigma=0.0,
+                   freq_q64=None, phase0_q64=None):
+    """a ChannelStream from taps [(delay, re, im), ...] and a carrier offset in cycles per sample (Hz / 2.048e6 for DAB)"""
+    P = ChannelStream()
+    P.freq_q64 = lib().dabgpu_channel_freq_q64(float(cycles_per_sample)) if freq_q64 is None else int(freq_q64)
+    P.phase0_q64 = lib().dabgpu_channel_freq_q64(float(phase0_cycles)) if phase0_q64 is None else int(phase0_q64)
+    P.start, P.seed, P.gain, P.noise_sigma, P.n_taps = int(start), int(seed), float(gain), float(noise_sigma), len(taps)
+    for k, (d, re, im) in enumerate(taps[:8]):
+        P.tap_delay[k], P.tap_re[k], P.tap_im[k] = int(d), float(re), float(im)
+    return P
+
+
+def channel_plan(streams):
+    """dabgpu_channel_plan (host only): {"halo", "block_samples", "lds_bytes", "staged"} of a list of ChannelStream; raises DabGpuError"""
+    n = len(streams)
+    arr = (ChannelStream * n)(*streams) if n else None
+    g = ChannelGeometry()
+    check(lib().dabgpu_channel_plan(arr, n, C.byref(g)), "dabgpu_channel_plan")
+    return {"halo": g.halo, "block_samples": g.block_samples, "lds_bytes": g.lds_bytes, "staged": g.staged}
+
+
+class Channel:
+    """dabgpu_channel_bank: multipath, carrier offset, timing offset and noise for n streams; the stream position lives on the device"""
+
+    def __init__(self, ctx, streams):
+        self._ctx = ctx
+        self.n = len(streams)
+        self.plan = channel_plan(streams)
+        arr = (ChannelStream * self.n)(*streams)
+        self._h = C.c_void_p()
+        check(lib().dabgpu_channel_bank_create(ctx._h, self.n, arr, C.byref(self._h)), "dabgpu_channel_bank_create")
+
+    def close(self):
+        if self._h:
+            lib().dabgpu_channel_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, streams, stream=None):
+        assert len(streams) == self.n
+        arr = (ChannelStream * self.n)(*streams)
+        check(lib().dabgpu_channel_bank_set_params(self._h, arr, Context._stream(stream)), "dabgpu_channel_bank_set_params")
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_channel_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_channel_bank_seek")
+
+    def apply(self, d_in, n_in, n_out, d_out, in_stride_samples=0, wrap=False, out_format=None, out_stride_bytes=0, u8_scale=1.0, stream=None):
+        """d_in complex float (device) -> d_out rows of n_out samples, complex float (default) or u8 pairs; asynchronous"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_channel_bank_apply(self._h, _ptr(d_in), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(d_out), fmt, out_stride_bytes,
+                                              float(u8_scale), Context._stream(stream)), "dabgpu_channel_bank_apply")
+
+    def apply_host(self, h_in, n_out, in_stride_samples=0, wrap=False, out_format=None, u8_scale=1.0):
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        x = np.ascontiguousarray(h_in, dtype=np.complex64)
+        n_in = x.shape[-1]
+        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
+        stride = (n_out * sb + 15) & ~15
+        out = np.zeros((self.n, stride), np.uint8)
+        check(lib().dabgpu_channel_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
+                                                        float(u8_scale)), "dabgpu_channel_bank_apply_host_sync")
+        out = out[:, :n_out * sb]
+        return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
 
 
 class DabPlusTx:

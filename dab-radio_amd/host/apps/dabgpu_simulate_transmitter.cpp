@@ -13,6 +13,15 @@
 //   --fib-file FILE                FIB bodies, 30 bytes each, 12 per frame, read cyclically (tools/dabfig.py writes them)
 //   --payload-file FILE            the CIFs' input records (the sub-channels' bytes back to back in list order), read cyclically
 //   --seed N                       random FIB bodies / payload where no file is given (default 1)
+// Channel (not in the reference; include/dabgpu.h "Channel model", DAB_Channel_Model): with any of the options below the frames are
+// modulated to complex float, passed through the channel on the device and quantised there; without them the output is byte for byte
+// what it was.  The stream position runs on from frame to frame: the oscillator keeps its phase and the noise never repeats.
+//   --snr-db DB                    white Gaussian noise; noise_sigma = sqrt(P / (2 * 10^(DB / 10))) per component with
+//                                  P = nb_data_carriers * sum |tap|^2, the mean power of the modulator's symbols (NULL excluded) after the taps
+//   --cfo-hz HZ                    carrier offset from the channel's 64-bit oscillator (cycles per sample = HZ / 2.048e6)
+//   --timing-offset N              the signal N samples late (N >= 0 with channel-coded frames: they are produced one at a time)
+//   --tap DELAY:RE:IM              repeatable, up to 8; delay in samples 0..2047; default one tap 0:1:0
+//   --noise-seed N                 default 1
 #include <stdio.h>
 #include <stdlib.h>
 #include <complex>
@@ -21,7 +30,11 @@
 #include <string>
 #include <vector>
 
+#include <math.h>
+#include <memory>
+
 #include "dab/dabgpu_shared_context.h"
+#include "dab/tx/dab_channel_model.h"
 #include "dabgpu.h"
 #include "ofdm/dab_ofdm_params_ref.h"
 #include "ofdm/dab_prs_ref.h"
@@ -51,7 +64,42 @@ struct Args {
     std::vector<dabgpu_subchannel> subchannels;
     std::string fib_filename, payload_filename;
     unsigned long long seed = 1;
+    // channel
+    bool channel = false;
+    bool have_snr = false;
+    double snr_db = 0.0, cfo_hz = 0.0;
+    long long timing_offset = 0;
+    unsigned long long noise_seed = 1;
+    struct Tap { int delay; float re, im; };
+    std::vector<Tap> taps;
 };
+
+// the channel's parameters for a mode with nb_carriers data carriers
+static dabgpu_channel_stream channel_params(const Args& args, int nb_carriers) {
+    dabgpu_channel_stream P = {};
+    P.freq_q64 = DAB_Channel_Model::FrequencyWord(args.cfo_hz);
+    P.start = args.timing_offset;
+    P.seed = args.noise_seed;
+    P.gain = 1.0f;
+    std::vector<Args::Tap> taps = args.taps;
+    if (taps.empty()) taps.push_back({0, 1.0f, 0.0f});
+    if (taps.size() > DABGPU_CHANNEL_MAX_TAPS) throw std::runtime_error("--tap: at most 8 taps");
+    double h2 = 0.0;
+    P.n_taps = (int)taps.size();
+    for (size_t k = 0; k < taps.size(); k++) {
+        P.tap_delay[k] = taps[k].delay; P.tap_re[k] = taps[k].re; P.tap_im[k] = taps[k].im;
+        h2 += (double)taps[k].re * taps[k].re + (double)taps[k].im * taps[k].im;
+    }
+    P.noise_sigma = args.have_snr ? DAB_Channel_Model::NoiseSigma((double)nb_carriers * h2, args.snr_db) : 0.0f;
+    return P;
+}
+
+// DELAY:RE:IM
+static Args::Tap parse_tap(const std::string& v) {
+    const size_t a = v.find(':'), b = v.find(':', a == std::string::npos ? a : a + 1);
+    if (a == std::string::npos || b == std::string::npos) throw std::runtime_error("--tap wants DELAY:RE:IM, got " + v);
+    return {std::stoi(v.substr(0, a)), std::stof(v.substr(a + 1, b - a - 1)), std::stof(v.substr(b + 1))};
+}
 
 // START:LENGTH:PROT
 static dabgpu_subchannel parse_subchannel(const std::string& v) {
@@ -103,10 +151,32 @@ static int run_coded(const Args& args, FILE* fp_out) {
     ByteSource fibs(args.fib_filename, rng, 64 * 360), payload(args.payload_filename, rng, 64 * 4 * (size_t)cif_in + 1);
     const float frequency_norm = (args.frequency != 0.0f) ? args.frequency / 2.048e6f : 0.0f;
     std::vector<uint8_t> fib(360), pay(4 * (size_t)cif_in + 4), quantised(2 * (size_t)DABGPU_NB_FRAME_SAMPLES);
+    // channel: the frames come one at a time, so the channel sees a window of the previous and the current frame and `start` moves with it
+    const size_t S = DABGPU_NB_FRAME_SAMPLES;
+    std::unique_ptr<DAB_Channel_Model> channel;
+    dabgpu_channel_stream cp = {};
+    std::vector<std::complex<float>> window;
+    if (args.channel) {
+        if (args.timing_offset < 0) throw std::runtime_error("--timing-offset must be >= 0 with channel-coded frames");
+        cp = channel_params(args, 1536);
+        channel = std::make_unique<DAB_Channel_Model>(cp);
+        window.assign(2 * S, std::complex<float>(0.0f, 0.0f));
+    }
+    const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
     int rc = 0;
     for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
         fibs.read(fib.data(), 360);
         payload.read(pay.data(), 4 * (size_t)cif_in);
+        if (channel) {
+            std::copy(window.begin() + (long)S, window.end(), window.begin());
+            st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, window.data() + S, DABGPU_IQ_RAW_F32L);
+            if (st == DABGPU_OK) {
+                dabgpu_channel_stream now = cp;
+                now.start = cp.start + (k - 1) * (long long)S;             // window sample 0 = stream sample (k - 1) S
+                channel->SetParams(now);
+                channel->ApplyU8(quantised, window, false, u8_scale);
+            }
+        } else
         st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
         if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); rc = 1; break; }
         const size_t nb_write = fwrite(quantised.data(), 2, DABGPU_NB_FRAME_SAMPLES, fp_out);
@@ -119,8 +189,13 @@ static int run_coded(const Args& args, FILE* fp_out) {
 static void usage(const char* argv0) {
     fprintf(stderr, "usage: %s [-m|--transmission-mode 1..4] [-f|--frequency HZ] [-o|--output FILE] [--frames N]\n"
                     "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
+                    "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N]\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
-                    "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data\n", argv0);
+                    "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
+                    "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
+                    "quantised: taps (default 0:1:0, delays 0..2047 samples), carrier offset, delay, white Gaussian noise with\n"
+                    "  noise_sigma = sqrt(P / (2 * 10^(DB / 10))) per component, P = nb_data_carriers * sum |tap|^2\n"
+                    "(the mean power of the modulator's symbols after the taps; the NULL period is not counted)\n", argv0);
 }
 
 static bool parse_args(int argc, char** argv, Args& args) {
@@ -138,6 +213,11 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--fib-file") { args.fib_filename = value(); args.coded = true; }
         else if (a == "--payload-file") { args.payload_filename = value(); args.coded = true; }
         else if (a == "--seed") { args.seed = std::stoull(value()); args.coded = true; }
+        else if (a == "--snr-db") { args.snr_db = std::stod(value()); args.have_snr = true; args.channel = true; }
+        else if (a == "--cfo-hz") { args.cfo_hz = std::stod(value()); args.channel = true; }
+        else if (a == "--timing-offset") { args.timing_offset = std::stoll(value()); args.channel = true; }
+        else if (a == "--tap") { args.taps.push_back(parse_tap(value())); args.channel = true; }
+        else if (a == "--noise-seed") { args.noise_seed = std::stoull(value()); args.channel = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
     }
@@ -186,6 +266,30 @@ int main(int argc, char** argv) {
         // modulation, frequency shift (:167-171, only for a non-zero frequency) and quantisation on the device
         const float frequency_norm = (args.frequency != 0.0f) ? args.frequency / 2.048e6f : 0.0f;
         auto quantised = std::vector<uint8_t>(2 * frame_size);
+        if (args.channel) {
+            // the frame once as complex float; the channel reads it as a transmission that repeats
+            auto frame = std::vector<std::complex<float>>(frame_size);
+            const int st = dabgpu_ofdm_modulate_frames_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
+                                                                 DABGPU_TX_PAYLOAD_REFERENCE, 1, reinterpret_cast<const float*>(prs_fft_ref.data()),
+                                                                 frequency_norm, frame.data(), DABGPU_IQ_RAW_F32L);
+            if (st != DABGPU_OK) {
+                fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error());
+                return 1;
+            }
+            DAB_Channel_Model channel(channel_params(args, (int)params.nb_data_carriers));
+            const float u8_scale = (1.0f / (float)params.nb_data_carriers * 4.0f) * 127.5f;
+            for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
+                channel.ApplyU8(quantised, frame, true, u8_scale);
+                const size_t nb_write = fwrite(quantised.data(), 2, frame_size, fp_out);
+                if (nb_write != frame_size) {
+                    fprintf(stderr, "Failed to write out frame %zu/%zu\n", nb_write, frame_size);
+                    break;
+                }
+            }
+            if (fp_out != stdout) fclose(fp_out);
+            else fflush(fp_out);
+            return 0;
+        }
         const int st = dabgpu_ofdm_modulate_frames_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
                                                              DABGPU_TX_PAYLOAD_REFERENCE, 1, reinterpret_cast<const float*>(prs_fft_ref.data()),
                                                              frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);

@@ -1,0 +1,47 @@
+// dab/tx/dab_channel_model.cpp -- see dab_channel_model.h
+#include "./dab_channel_model.h"
+
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "dab/dabgpu_shared_context.h"
+
+static void check(int st, const char* what) {
+    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Channel_Model: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
+}
+
+DAB_Channel_Model::DAB_Channel_Model(const dabgpu_channel_stream& params) {
+    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
+        throw std::runtime_error("DAB_Channel_Model: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
+                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    check(dabgpu_channel_bank_create(dabgpu_shared_context(), 1, &params, &m_bank), "dabgpu_channel_bank_create");
+}
+
+DAB_Channel_Model::~DAB_Channel_Model() { dabgpu_channel_bank_destroy(m_bank); }
+
+float DAB_Channel_Model::NoiseSigma(double mean_power, double snr_db) { return (float)std::sqrt(mean_power / (2.0 * std::pow(10.0, snr_db / 10.0))); }
+
+void DAB_Channel_Model::SetParams(const dabgpu_channel_stream& params) {
+    check(dabgpu_channel_bank_set_params(m_bank, &params, nullptr), "dabgpu_channel_bank_set_params");
+    check(dabgpu_synchronize(dabgpu_shared_context(), nullptr), "dabgpu_synchronize");
+}
+
+void DAB_Channel_Model::Seek(uint64_t position) {
+    check(dabgpu_channel_bank_seek(m_bank, position, nullptr), "dabgpu_channel_bank_seek");
+    check(dabgpu_synchronize(dabgpu_shared_context(), nullptr), "dabgpu_synchronize");
+}
+
+bool DAB_Channel_Model::Apply(tcb::span<std::complex<float>> out, tcb::span<const std::complex<float>> in, bool wrap) {
+    if (in.empty()) return false;
+    check(dabgpu_channel_bank_apply_host_sync(m_bank, reinterpret_cast<const float*>(in.data()), 0, in.size(), wrap ? 1 : 0, out.size(), out.data(),
+                                              DABGPU_IQ_RAW_F32L, 0, 1.0f), "dabgpu_channel_bank_apply_host_sync");
+    return true;
+}
+
+bool DAB_Channel_Model::ApplyU8(tcb::span<uint8_t> out, tcb::span<const std::complex<float>> in, bool wrap, float u8_scale) {
+    if (in.empty() || (out.size() & 1)) return false;
+    check(dabgpu_channel_bank_apply_host_sync(m_bank, reinterpret_cast<const float*>(in.data()), 0, in.size(), wrap ? 1 : 0, out.size() / 2, out.data(),
+                                              DABGPU_IQ_RAW_U8, 0, u8_scale), "dabgpu_channel_bank_apply_host_sync");
+    return true;
+}

@@ -964,6 +964,90 @@ int dabgpu_dabplus_tx_encode_host_sync(dabgpu_ctx *ctx, int n_superframes, const
                                        int32_t *h_status);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Channel model: multipath inside the guard interval, carrier offset, timing offset and white Gaussian noise for n_streams
+ * independent streams of complex float samples.  The reference has no channel (only examples/apply_frequency_shift.cpp); the definition
+ * is this library's own, written once in dab-radio_amd/csrc/channel_core.h for the kernel (channel.hip) and for the host model the
+ * tests build from the same header, and pinned to an independent numpy model (tests/channel_model.py, tests/test_channel_model.py:
+ * Philox known answers, float output inside the derived bound of DESIGN.md 4.16, noise moments, u8 rounding) and on the device bit for
+ * bit to the host model (tests/test_gpu_channel.py).  Transmission-mode agnostic.
+ *
+ * For stream s, absolute output sample m (the bank's 64-bit position + the sample's index in the call) and input x[0 .. n_in):
+ *   z      = sum over the n_taps taps, in list order, of (tap_re[k] + j tap_im[k]) * x[m - start - tap_delay[k]]
+ *            wrap != 0: the index is taken modulo n_in (a transmission that repeats); wrap = 0: samples outside the input are 0
+ *   phase  = phase0_q64 + m * freq_q64 in unsigned 64-bit arithmetic, cycles as a fraction of 2^64; its top 24 bits are the angle.
+ *            Exact, periodic by itself and independent of where calls are split -- unlike the float phase of freq_norm above, which
+ *            stays as it is.  freq_q64 = phase0_q64 = 0 skips the rotation (an identity channel returns its input bit for bit).
+ *   y      = gain * z * e^(j 2 pi phase) + noise_sigma * (g0 + j g1)
+ *   g0, g1 = one Box-Muller pair of Philox4x32-10: key = seed, counter = (low word of m >> 1, high word of m >> 1, s, 0); sample m
+ *            takes words 2 (m & 1) and 2 (m & 1) + 1 of the four, uniforms ((w >> 8) + 0.5) * 2^-24 (never 0, |g| <= 5.89).
+ *            The noise of a sample depends on (seed, s, m) alone.  noise_sigma = 0 adds nothing and runs no generator.
+ * Input sample indices are absolute like m: a call at position p reads x[p - start - delay ...] of the d_in it is given, so a call with
+ * a + b samples equals a call with a and then one with b ON THE SAME d_in AND n_in, for any a (the position, on the device, carries the
+ * shift).  A caller that holds only the input from absolute sample W on passes that window as d_in and adds W to `start`
+ * (dabgpu_channel_bank_set_params); the window has to begin max(tap_delay) samples before the first sample the call needs.
+ *
+ * dabgpu_channel_plan (host only, no device): checks a parameter list and returns the launch geometry.  Refused with
+ * DABGPU_ERR_INVALID_ARG: n_streams outside 1..1048576, NULL params, n_taps outside 1..8, a tap_delay above
+ * DABGPU_CHANNEL_MAX_DELAY, gain, noise_sigma or a tap that is not finite, noise_sigma < 0, |start| above 2^62 (with positions up to
+ * 2^62, which dabgpu_channel_bank_seek enforces and 70,000 years of DAB samples do not reach, the index m - start - delay stays a plain
+ * signed 64-bit number: the kernel reduces a tile's first index modulo n_in once and steps from there).
+ *   halo           largest tap_delay of the list rounded up to an even count
+ *   block_samples  output samples one workgroup produces (DABGPU_CHANNEL_BLOCK)
+ *   lds_bytes      staged input of a workgroup: (block_samples + halo + 2) complex float; 0 when no stream needs staging
+ *                  (every stream one tap of delay 0: the kernel then reads the input directly)
+ * dabgpu_channel_freq_q64(cycles_per_sample): round(cycles * 2^64) modulo 2^64, for |cycles| <= 0.5 (a double carries 53 bits of it;
+ * NaN and values outside give 0).  From Hz: cycles = hz / sample rate (2.048e6 for DAB).  dabgpu_channel_freq_cycles is its inverse
+ * into [-0.5, 0.5) (tests/test_channel_plan.py: round trips, both signs, +-0.5). */
+#define DABGPU_CHANNEL_MAX_TAPS 8
+#define DABGPU_CHANNEL_MAX_DELAY 2047
+#define DABGPU_CHANNEL_BLOCK 1024
+#define DABGPU_CHANNEL_MAX_POSITION ((int64_t)1 << 62)      /* |start| and the stream position stay below: m - start - delay never wraps */
+typedef struct {
+    uint64_t freq_q64, phase0_q64;
+    int64_t start;
+    uint64_t seed;
+    float gain, noise_sigma;
+    int32_t n_taps;
+    int32_t tap_delay[DABGPU_CHANNEL_MAX_TAPS];
+    float tap_re[DABGPU_CHANNEL_MAX_TAPS], tap_im[DABGPU_CHANNEL_MAX_TAPS];
+    int32_t reserved;
+} dabgpu_channel_stream;
+typedef struct { uint32_t halo, block_samples, lds_bytes, staged; } dabgpu_channel_geometry;
+int dabgpu_channel_plan(const dabgpu_channel_stream *params, size_t n_streams, dabgpu_channel_geometry *out);
+uint64_t dabgpu_channel_freq_q64(double cycles_per_sample);
+double dabgpu_channel_freq_cycles(uint64_t freq_q64);
+
+/* Channel bank: the parameters of n_streams streams and their common position on the device.
+ *   d_in    stream s reads d_in + s * in_stride_samples complex float; in_stride_samples = 0: every stream reads the same input,
+ *           otherwise >= n_in and even.  16-byte aligned.  n_in >= 1.
+ *   d_out   stream s writes n_out samples from d_out + s * out_stride_bytes on: complex float (DABGPU_IQ_RAW_F32L) or the u8 pairs of
+ *           the modulator's quantiser, QuantisedIQ<uint8_t>::from_iq(I * u8_scale, Q * u8_scale) (DABGPU_IQ_RAW_U8).  16-byte aligned,
+ *           out_stride_bytes a multiple of 16 that holds n_out samples (0 = n_out samples rounded up to 16 bytes).  Nothing else is written.
+ * A call is two launches on `stream`: the channel kernel, then a one-thread kernel that adds n_out to the position.  No host state
+ * changes, so a call may be captured in a HIP graph; replays continue the stream, with new noise.  _seek sets the position (0 at
+ * creation), _set_params replaces all parameters; both are ordered on `stream` like the calls.  One bank = one stream at a time.
+ * The launch geometry (staged or direct kernel, LDS size) is fixed when the bank is created, because a captured call has it baked in:
+ * _set_params refuses (DABGPU_ERR_INVALID_ARG) parameters whose halo exceeds the creation's, or that need staging in a bank created with
+ * single zero-delay taps only.  Create the bank with the widest profile it will carry; narrower ones are accepted later.
+ * Arguments are checked before any device call: the rules are plain C++ (dabgpu_host_logic.cpp), exercised without a device by
+ * tests/test_channel_plan.py (null handles, the parameter list) and its fuzzer tests/cpp/channel_plan_fuzz.cpp (every rule of an apply
+ * call, both sides), and on the device by tests/test_gpu_channel.py (error strings, output untouched). */
+typedef struct dabgpu_channel_bank dabgpu_channel_bank;
+int dabgpu_channel_bank_create(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_channel_stream *h_params, dabgpu_channel_bank **out);
+void dabgpu_channel_bank_destroy(dabgpu_channel_bank *bank);
+int dabgpu_channel_bank_set_params(dabgpu_channel_bank *bank, const dabgpu_channel_stream *h_params, void *stream);
+int dabgpu_channel_bank_seek(dabgpu_channel_bank *bank, uint64_t position, void *stream);
+int dabgpu_channel_bank_apply(dabgpu_channel_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
+                              void *d_out, int out_format, size_t out_stride_bytes, float u8_scale, void *stream);
+/* the same from and to host memory on the context's stream: h_in [n_streams] rows in_stride_samples apart (any count >= n_in; 0 = one
+ * shared row), h_out [n_streams] rows out_stride_bytes apart (any count that holds n_out samples; 0 = back to back); no alignment rule;
+ * only the rows' n_out samples are written.  The bank keeps two grow-only device buffers for this form; a call that needs larger ones
+ * than any before it waits for the whole device (hipDeviceSynchronize) before it frees the old: a test and single-stream path, not a
+ * batch path.  Returns when h_out is written (tests/test_gpu_channel.py, tests/cpp/channel_model_harness.cpp) */
+int dabgpu_channel_bank_apply_host_sync(dabgpu_channel_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_in, int wrap,
+                                        size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Ingest pipe: the host -> device hand-over of capture bytes.  Replaces the reader thread -> OFDM_Demod::Process hand-over
  * of examples/app_helpers/app_ofdm_blocks.h:45-58 and the memcpy of OFDM_Demod::ReadSymbols (src/ofdm/ofdm_demodulator.cpp:550-577).
  * A ring of `depth` PINNED host buffers with device twins and a copy stream of its own:

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""First sensitivity figures of the receiver: FIB CRC pass rate and MSC byte-error rate per protection level against signal-to-noise
+ratio, on the device from end to end.  One mode I transmission (dabgpu.TxBank) feeds E channel streams (dabgpu.Channel, one shared
+input, a noise seed each); every stream is a receiver: dabgpu_ofdm_sync_demod_frames -> dabgpu_decode_frames_layout.  Two channels: white
+noise alone, then two paths (the second 200 samples late at -6 dB) with the same noise.  Multiplex: 48-CU sub-channels at EEP 1-A,
+2-A, 3-A (x 13, the canonical layout's profile) and 4-A plus a 52-CU UEP row (the full canonical 18 x 48 leaves no room for the other
+levels).  SNR = mean power of the modulator's symbols after the taps (1536 x sum |tap|^2) over 2 sigma^2, as the transmitter tool defines it.
+    python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md]"""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "dab-radio_amd")]
+
+S, NULL, P_LEAD = 196608, 2656, 700
+STRIDE = P_LEAD + 1544 + S
+LEVELS = [("EEP 1-A", [(624, 48, 0, 0, 0)]), ("EEP 2-A", [(672, 48, 0, 0, 1)]), ("EEP 3-A", [(48 * k, 48, 0, 0, 2) for k in range(13)]),
+          ("EEP 4-A", [(720, 48, 0, 0, 3)]), ("UEP row 20", [(768, 52, 1, 20, 0)])]
+PROFILES = [("white noise", [(0, 1.0, 0.0)]), ("two paths (second 200 samples late, -6 dB) + noise", [(0, 1.0, 0.0), (200, 0.5, 0.0)])]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--frames", type=int, default=6)
+    ap.add_argument("--snr", default="2:15:1")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tx", "waterfall.md"))
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import dabgpu
+    lo, hi, step = (float(v) for v in a.snr.split(":"))
+    snrs = [lo + i * step for i in range(int(round((hi - lo) / step)) + 1)]
+    E, F, H = a.streams, a.frames, 8
+    ctx = dabgpu.Context(0)
+    subs, owner = [], []
+    for li, (_, lst) in enumerate(LEVELS):
+        for (start, length, uep, row, lvl) in lst:
+            subs.append(dabgpu.SubChannel(start, length, uep, row, lvl, 0)); owner.append(li)
+    plan = dabgpu.tx_encode_plan(subs)
+    nb = plan["cif_in_bytes"]
+    spans = [(int(p.in_offset), int(p.in_bytes)) for p in plan["subs"]]
+    rng = np.random.default_rng(1)
+    fib = rng.integers(0, 256, (1, F, 4, 3, 30), dtype=np.uint8)
+    pay = rng.integers(0, 256, (1, F, 4, nb), dtype=np.uint8)
+    bank = dabgpu.TxBank(ctx, 1, subs)
+    d_iq = torch.zeros((F * S, 2), dtype=torch.float32, device="cuda")
+    bank.transmit_frames(torch.from_numpy(fib).cuda(), torch.from_numpy(pay).cuda(), F, d_iq)
+    n_out = F * S + 4096
+    d_rx = torch.zeros((E, n_out, 2), dtype=torch.float32, device="cuda")
+    sdt, rdt = np.dtype(dabgpu.SYNC_STATE_DTYPE), np.dtype(dabgpu.RESULT_DTYPE)
+    cifs = torch.from_numpy(pay.reshape(4 * F, nb)).cuda()
+    text = [f"# Receiver sensitivity: FIB CRC pass rate and MSC byte-error rate against SNR", "",
+            f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  {E} receivers x {F} mode I frames per point, one transmission, a noise seed per receiver; "
+            f"FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on "
+            f"(per point: {', '.join(f'{name} {E * (4 * F - 15) * sum(spans[i][1] for i in range(len(subs)) if owner[i] == li)}' for li, (name, _) in enumerate(LEVELS))} bytes).  "
+            "No carrier or timing offset.  `python tools/waterfall.py`.", ""]
+    verdicts = []
+    for pname, taps in PROFILES:
+        h2 = sum(re * re + im * im for _, re, im in taps)
+        rows = []
+        ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)])
+        for snr in snrs:
+            sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
+            ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(E)])
+            ch.seek(0)
+            ch.apply(d_iq, F * S, n_out, d_rx, in_stride_samples=0, out_stride_bytes=n_out * 8)
+            d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
+            hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
+            d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
+            msc = torch.zeros((E, 4, nb), dtype=torch.uint8, device="cuda"); mres = torch.zeros((E * 4 * len(subs), 16), dtype=torch.uint8, device="cuda")
+            crc_ok, crc_n = 0, 0
+            err = [0] * len(LEVELS); tot = [0] * len(LEVELS)
+            for j in range(F):
+                a0 = NULL + j * S - P_LEAD
+                sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
+                seg = d_rx[:, a0:a0 + STRIDE]
+                sl[:, :seg.shape[1]] = seg
+                ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                ctx.decode_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
+                torch.cuda.synchronize()
+                masks = fres.cpu().numpy().view(rdt)["crc_ok_mask"].reshape(-1)
+                crc_ok += int(sum(bin(int(m) & 7).count("1") for m in masks)); crc_n += 3 * masks.size
+                for c in range(4):
+                    if 4 * j + c < 15:
+                        continue
+                    bad = (msc[:, c] != cifs[4 * j + c - 15][None, :])
+                    for i, (off, n) in enumerate(spans):
+                        err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
+            rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
+        ch.close()
+        text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
+        text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
+        # acceptance: error-free at the top, non-increasing within counting error, required SNR ordered by level
+        top = rows[-1]
+        free = top[1] == 1.0 and all(r == 0 for r in top[2])
+        mono = True
+        for li in range(len(LEVELS)):
+            for (s0, _, b0, t0), (s1, _, b1, _) in zip(rows, rows[1:]):
+                slack = 3 * math.sqrt(max(b0[li], 1.0 / t0[li]) / t0[li] * 255)        # byte errors come in bursts of a decoder's error event
+                mono = mono and b1[li] <= b0[li] + slack
+        need = [next((snr for k, (snr, _, ber, _) in enumerate(rows) if all(r[2][li] == 0 for r in rows[k:])), float("inf")) for li in range(len(LEVELS))]
+        order = need[0] <= need[1] <= need[2] <= need[3]
+        text += ["", f"Error-free at {top[0]:g} dB: {'yes' if free else 'NO'}.  Non-increasing with SNR within the counting error: {'yes' if mono else 'NO'}.  "
+                 f"First SNR from which no byte error remains: " + ", ".join(f"{name} {n:g} dB" for (name, _), n in zip(LEVELS, need)) +
+                 f" -- ordered 1-A <= 2-A <= 3-A <= 4-A: {'yes' if order else 'NO'}.", ""]
+        verdicts.append(free and mono and order)
+    text = "\n".join(text) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    open(a.out, "w").write(text)
+    return 0 if all(verdicts) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
