@@ -269,10 +269,13 @@ static int ofdm_demod_any(dabgpu_ctx* c, const void* d_iq, int src, size_t n_fra
     if (symbols_per_block <= 0)
         symbols_per_block = (d_fft || d_dqpsk) ? dabgpu_host_small_batch_spb(n_frames)      /* display views: three workgroups per CU, not tuned */
                                                : demod_cached_spb(c, n_frames, dabgpu_host_spb_variant(src, bits_layout, d_total_phase || d_fine_freq));
-    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, src, d_freq, d_bits, corr, d_fft, d_dqpsk, c->d_tw, c->modes[1].inv_map16,
-                                                     (int)n_frames, symbols_per_block, bits_frame_stride, nullptr, nullptr, 0,
-                                                     bits_layout == DABGPU_BITS_MSC_CLASSED, s, d_total_phase, d_fine_freq, beta),
-                            "ofdm_demod_kernel launch");
+    dabgpu_demod_call call;
+    call.d_iq = d_iq; call.src = src; call.d_freq = d_freq;
+    call.d_bits = d_bits; call.bits_frame_stride = bits_frame_stride; call.classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
+    call.d_cp_corr = corr; call.d_fft = d_fft; call.d_dqpsk = d_dqpsk;
+    call.n_frames = (int)n_frames; call.symbols_per_block = symbols_per_block;
+    call.d_total_phase = d_total_phase; call.d_fine_freq = d_fine_freq; call.beta = beta;
+    return dabgpu_launch_demod(c, 1, call, s);
 }
 
 int dabgpu_ofdm_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_frames, const float* d_freq, int8_t* d_bits,
@@ -340,31 +343,34 @@ int dabgpu_ofdm_tune(dabgpu_ctx* c, const void* d_raw, int format, size_t n_fram
         if ((st = dabgpu_scratch(c, SCR_TUNE_TAIL, 2 * n_frames * sizeof(float), (void**)&tail))) return st;
         if ((st = dabgpu_check_hip(hipMemsetAsync(tail, 0, 2 * n_frames * sizeof(float), s), "hipMemsetAsync(tune)"))) return st;
     }
-    auto launch = [&](int spb) {
-        return dabgpu_launch_ofdm_demod(d_raw, src, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, c->modes[1].inv_map16, (int)n_frames, spb, bits_frame_stride,
-                                        nullptr, nullptr, 0, bits_layout == DABGPU_BITS_MSC_CLASSED, s, tail, tail ? tail + n_frames : nullptr, 0.9f);
-    };
+    dabgpu_demod_call call;
+    call.d_iq = d_raw; call.src = src;
+    call.d_bits = d_bits; call.bits_frame_stride = bits_frame_stride; call.classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
+    call.d_cp_corr = corr; call.n_frames = (int)n_frames;
+    call.d_total_phase = tail; call.d_fine_freq = tail ? tail + n_frames : nullptr; call.beta = 0.9f;
+    auto launch = [&](int spb) { call.symbols_per_block = spb; return dabgpu_launch_demod(c, 1, call, s, "ofdm_tune"); };
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if ((st = dabgpu_check_hip(hipEventCreate(&e0), "hipEventCreate(tune)"))) return st;
     if ((st = dabgpu_check_hip(hipEventCreate(&e1), "hipEventCreate(tune)"))) { (void)hipEventDestroy(e0); return st; }
     static const int cand[3] = {25, 38, 75};
     float sum_ms[3] = {0.0f, 0.0f, 0.0f}, warm_ms = 0.0f;
-    hipError_t err = hipSuccess;
-    for (int pass = 0, timed = 0; timed < 3 && pass < 16 && err == hipSuccess; pass++) {
+    auto ck = [](hipError_t e) { return dabgpu_check_hip(e, "ofdm_tune"); };
+    st = DABGPU_OK;
+    for (int pass = 0, timed = 0; timed < 3 && pass < 16 && !st; pass++) {
         const bool counts = warm_ms >= 40.0f || pass >= 12;
-        for (int k = 0; k < 3 && err == hipSuccess; k++) {
-            err = hipEventRecord(e0, s);
-            for (int r = 0; r < 2 && err == hipSuccess; r++) err = launch(cand[k]);
+        for (int k = 0; k < 3 && !st; k++) {
+            st = ck(hipEventRecord(e0, s));
+            for (int r = 0; r < 2 && !st; r++) st = launch(cand[k]);
             float ms = 0.0f;
-            if (err == hipSuccess) err = hipEventRecord(e1, s);
-            if (err == hipSuccess) err = hipEventSynchronize(e1);
-            if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+            if (!st) st = ck(hipEventRecord(e1, s));
+            if (!st) st = ck(hipEventSynchronize(e1));
+            if (!st) st = ck(hipEventElapsedTime(&ms, e0, e1));
             if (counts) sum_ms[k] += ms; else warm_ms += ms;
         }
         timed += counts;
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (err != hipSuccess) return dabgpu_check_hip(err, "ofdm_tune");
+    if (st) return st;
     int best = 0;
     for (int k = 1; k < 3; k++) if (sum_ms[k] < sum_ms[best]) best = k;
     const int bucket = dabgpu_host_spb_bucket(n_frames), variant = dabgpu_host_spb_variant(src, bits_layout, with_phase_tail != 0);
@@ -404,16 +410,17 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_str
     if ((st = dabgpu_check_bits_buffers("ofdm_sync_demod_frames", bits_frame_stride, "d_iq", d_iq, 8, d_bits))) return st;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
-    const dabgpu_mode_tables& t = c->modes[1];
     float* corr = d_cp_corr;
     if (!corr && (st = dabgpu_scratch(c, SCR_DEMOD_CORR, n_streams * DABGPU_NB_FRAME_SYMBOLS * 2 * sizeof(float), (void**)&corr, s))) return st;
-    if ((st = dabgpu_check_hip(dabgpu_launch_sync(d_iq + 2 * prs_offset_samples, stream_stride_samples, (int)n_streams, cfg, d_states, nullptr, nullptr,
-                                                 c->d_tw, t.prs, t.prs_time_ref, nullptr, 1, s), "ofdm_sync_kernel launch"))) return st;
-    if (symbols_per_block <= 0) symbols_per_block = demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
-    return dabgpu_check_hip(dabgpu_launch_ofdm_demod(d_iq, 0, nullptr, d_bits, corr, nullptr, nullptr, c->d_tw, t.inv_map16, (int)n_streams, symbols_per_block,
-                                                     bits_frame_stride, nullptr, nullptr, 0, bits_layout == DABGPU_BITS_MSC_CLASSED, s, d_total_phase, nullptr,
-                                                     cfg->fine_freq_update_beta, nullptr, stream_stride_samples, d_states, (int)prs_offset_samples),
-                            "ofdm_demod_kernel launch (synchronised frames)");
+    if ((st = dabgpu_launch_sync(c, 1, d_iq + 2 * prs_offset_samples, stream_stride_samples, (int)n_streams, cfg, d_states, nullptr, nullptr, nullptr, s))) return st;
+    dabgpu_demod_call call;
+    call.d_iq = d_iq; call.frame_stride_samples = stream_stride_samples;
+    call.d_bits = d_bits; call.bits_frame_stride = bits_frame_stride; call.classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
+    call.d_cp_corr = corr; call.n_frames = (int)n_streams;
+    call.symbols_per_block = symbols_per_block > 0 ? symbols_per_block : demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
+    call.d_sync = d_states; call.prs_offset = (int)prs_offset_samples;
+    call.d_total_phase = d_total_phase; call.beta = cfg->fine_freq_update_beta;
+    return dabgpu_launch_demod(c, 1, call, s, "ofdm_demod_kernel launch (synchronised frames)");
 }
 
 // ---- one body per operation for every transmission mode: the mode I entry points are the mode forms with mode = 1 ----
@@ -521,11 +528,9 @@ static int ofdm_sync(dabgpu_ctx* c, int mode, const float* d_prs_syms, size_t n_
     if (n_streams == 0) return DABGPU_OK;
     if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("%s: n_streams too large", who); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(c);
-    const dabgpu_mode_tables* t;
-    int st = dabgpu_mode_tables_of(c, mode, &t, who);
-    if (st) return st;
-    return dabgpu_check_hip(dabgpu_launch_sync(d_prs_syms, stride_samples, (int)n_streams, cfg, d_states, d_impulse, d_freq,
-                                               c->d_tw, t->prs, t->prs_time_ref, nullptr, mode, (hipStream_t)stream), "ofdm_sync_kernel launch");
+    dabgpu::ModeGeom g;
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("%s: invalid transmission mode %d", who, mode); return DABGPU_ERR_INVALID_ARG; }
+    return dabgpu_launch_sync(c, mode, d_prs_syms, stride_samples, (int)n_streams, cfg, d_states, d_impulse, d_freq, nullptr, (hipStream_t)stream);
 }
 
 int dabgpu_ofdm_sync(dabgpu_ctx* c, const float* d_prs_syms, size_t n_streams, size_t stride_samples, const dabgpu_sync_cfg* cfg,

@@ -161,6 +161,52 @@ int dabgpu_host_spb_bucket(size_t n_frames) {
 // kernel variant of a call: loader (0..3), soft-bit layout, whether the phase tail runs with it (fused at 75, a second launch otherwise)
 int dabgpu_host_spb_variant(int src, int bits_layout, bool tail) { return src * 4 + (bits_layout == DABGPU_BITS_MSC_CLASSED ? 2 : 0) + (tail ? 1 : 0); }
 
+dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f) {
+    dabgpu_demod_plan p = {};
+    p.status = DABGPU_ERR_INVALID_ARG;
+    dabgpu::ModeGeom g;
+    if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod: invalid transmission mode %d", mode); return p; }
+    const bool mode1 = mode == 1 && !f.generic_mode1;
+    const bool views = f.fft || f.dqpsk;
+    if (mode1) {
+        if (f.src < 0 || f.src > 3) { dabgpu_set_error("ofdm_demod: no loader %d", f.src); return p; }
+        if (f.classed && views) { dabgpu_set_error("ofdm_demod: soft bits in class order come without the display views"); return p; }
+        if (f.desc && (f.sync || f.frame_stride)) { dabgpu_set_error("ofdm_demod: a bank round takes neither sync records nor a frame stride"); return p; }
+        p.family = DABGPU_DEMOD_MODE1;
+        p.variant = (f.src * 2 + (f.desc ? 1 : 0)) * 3 + (f.classed ? 2 : views ? 1 : 0);
+    } else {
+        // modes II-IV run register-resident unless the FFT view, which only the size-generic kernel writes, is wanted
+        p.family = (mode == 1 || f.fft || f.switch_generic) ? DABGPU_DEMOD_GENERIC
+                   : (mode == 3 && !f.switch_mode3_single)   ? DABGPU_DEMOD_WAVE3
+                                                             : DABGPU_DEMOD_WAVE;
+        // (a loader these kernels do not know runs as s16, as it always has: the entry points check the format, dabgpu_fused_loader)
+        p.variant = !f.desc ? 0 : 1 + ((f.src >= 0 && f.src <= 2) ? f.src : 3);
+    }
+    // mode I default: three runs per frame (one extra FFT per run).  A whole frame per workgroup (75) is 1 % faster when 1024 frames are
+    // exactly one round of a 256-CU chip (and lets the phase tail run inside the kernel) but 25 % slower on boxes whose CUs do not
+    // all run at one speed (workgroup lifetimes 0.33 .. 0.53 ms in one static round: 0.536 against 0.427 ms): callers that care
+    // time both (bench.py does) and pass it.  The other modes: 19 symbols.
+    const int n_out = g.n_sym - 1;
+    p.symbols_per_block = (f.symbols_per_block <= 0 || f.symbols_per_block > n_out) ? (mode1 ? 25 : 19) : f.symbols_per_block;
+    p.chunks = (n_out + p.symbols_per_block - 1) / p.symbols_per_block;
+    const uint64_t units = (uint64_t)(f.n_frames > 0 ? f.n_frames : 0) * (uint64_t)p.chunks;
+    const bool wave = p.family == DABGPU_DEMOD_WAVE || p.family == DABGPU_DEMOD_WAVE3;      // four runs, one per wavefront, to a workgroup
+    p.grid = (uint32_t)(wave ? (units + 3) / 4 : units);
+    // size-generic kernel, measured (tools/bench_io.py, 2048 frames): FFT 512 / 256 run best with 128 threads (0.94 / 1.01 ms; 256 threads
+    // 1.03 / 1.47, 64 threads 1.19 / 1.01), FFT 1024 with 256 (1.93 ms; 128 threads 2.58): fewer idle butterfly lanes against fewer resident wavefronts
+    p.threads = (p.family == DABGPU_DEMOD_GENERIC && (mode == 2 || mode == 3)) ? 128 : 256;
+    // size-generic kernel: one PLL-corrected symbol, three transform buffers, 2 x 256 reduction leaves
+    p.lds_bytes = p.family == DABGPU_DEMOD_GENERIC ? (uint32_t)((g.period + 3 * g.n_fft) * 8 + 2048) : 0;
+    p.raise_lds_limit = p.lds_bytes > 48u * 1024u;
+    // the phase tail (mode I): inside the kernel when one workgroup walks the whole frame, else a launch of its own; a bank round runs its
+    // own phase kernel over the descriptors.  With sync records the fine-frequency word is the record's.
+    p.fine_stride = f.sync ? (int)(sizeof(dabgpu_sync_state) / sizeof(float)) : 1;
+    const bool want_tail = mode1 && !f.desc && (f.total_phase || f.fine_freq || f.sync);
+    p.tail = !want_tail ? DABGPU_DEMOD_TAIL_NONE : (p.chunks == 1 && !views) ? DABGPU_DEMOD_TAIL_FUSED : DABGPU_DEMOD_TAIL_LAUNCH;
+    p.status = DABGPU_OK;
+    return p;
+}
+
 
 // ETSI EN 300 401 tables 8 + 15: {size CU, kbps, level, L1..L4, PI1..PI4, padding bits}; row order (and the two
 // exchanged size fields of rows 33/34) as the reference lists them, src/dab/constants/subchannel_protection_tables.h:21-86,

@@ -1,5 +1,6 @@
 // dabgpu_host_logic.h -- the part of libdabgpu.so that never touches the device: constant tables, protection-profile plans, codeword
-// validation, the mapping cost model, run-length rules, capture-format and wav-header parsing, error text.  Plain C++ (no HIP headers):
+// validation, the mapping cost model, run-length rules, the planners (decode, demodulation, channel encoder, channel model: what a call will
+// launch, decided before any device header enters), capture-format and wav-header parsing, error text.  Plain C++ (no HIP headers):
 // compiled into the library by the same Makefile, and on its own with -fsanitize=address,undefined by tests/test_host_sanitizers.py,
 // which fuzzes it (tests/cpp/host_logic_fuzz.cpp).
 #pragma once
@@ -180,6 +181,42 @@ struct dabgpu_decode_slice {
     dabgpu_vit_group_base fic_base;         // where the appended groups start behind the MSC's (res_delta: the executor's, two device addresses)
 };
 dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t e0);
+
+// ---- demodulation planner: which kernel one demodulator launch runs and over what grid (dabgpu_launch_demod launches from it) ----
+// Four kernel families: the register-resident mode I kernel (ofdm_demod.hip), the size-generic kernel (ofdm_modes.hip), one wavefront per
+// run of symbols for modes II-IV, and two symbols per wavefront for mode III (ofdm_wave512.hip).  Each keeps a table of its kernels,
+// indexed by `variant`:
+//   mode I:        ((src * 2 + bank) * 3 + layout), layout 0 = soft bits, 1 = + display views, 2 = soft bits in class order
+//   other families: 0 without descriptors (complex float only), 1 + src with them
+enum dabgpu_demod_family { DABGPU_DEMOD_MODE1, DABGPU_DEMOD_GENERIC, DABGPU_DEMOD_WAVE, DABGPU_DEMOD_WAVE3 };
+enum dabgpu_demod_tail { DABGPU_DEMOD_TAIL_NONE, DABGPU_DEMOD_TAIL_FUSED, DABGPU_DEMOD_TAIL_LAUNCH };
+constexpr int DABGPU_DEMOD_MODE1_VARIANTS = 4 * 2 * 3, DABGPU_DEMOD_LOADER_VARIANTS = 1 + 4;
+// the facts of a call that are not addresses.  The views, class order, sync records, frame stride and phase outputs are the mode I kernel's:
+// the other families have none of them (the FFT view apart, which only the size-generic kernel writes) and do not look at these facts.
+struct dabgpu_demod_facts {
+    int src = 0;                            // loader: 0 complex float, 1 u8, 2 s8, 3 s16 (dabgpu_fused_loader)
+    bool desc = false;                      // bank round: frame descriptors
+    bool fft = false, dqpsk = false;        // display views
+    bool sync = false, frame_stride = false;
+    bool total_phase = false, fine_freq = false;
+    bool classed = false;
+    int symbols_per_block = 0, n_frames = 0;
+    bool generic_mode1 = false;             // mode I runs on the size-generic kernel too (dabgpu_ofdm_demod_frames_mode: the tests cross-check the two)
+    bool switch_generic = false;            // DABGPU_MODE_GENERIC: modes II-IV stay on the size-generic kernel
+    bool switch_mode3_single = false;       // DABGPU_MODE3_SINGLE: mode III, one symbol per wavefront
+};
+struct dabgpu_demod_plan {
+    int status;                             // DABGPU_OK, or DABGPU_ERR_INVALID_ARG (reason in dabgpu_last_error): nothing else is set then
+    dabgpu_demod_family family;
+    int variant;
+    int symbols_per_block, chunks;          // run length as resolved, runs per frame
+    uint32_t grid, threads;
+    uint32_t lds_bytes;                     // dynamic LDS; 0 for mode I: its kernel's own constant
+    bool raise_lds_limit;                   // more than 48 KB: the kernel's attribute is set first (the size-generic kernel in mode I only)
+    dabgpu_demod_tail tail;
+    int fine_stride;                        // floats between the fine-frequency words of two frames
+};
+dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f);
 
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps

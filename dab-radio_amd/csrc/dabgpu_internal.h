@@ -143,29 +143,54 @@ struct dabgpu_frame_desc {
     long long carry_off;
 };
 
-extern "C" hipError_t dabgpu_launch_ofdm_demod(const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                               float* d_fft, float* d_dqpsk, const float* d_tw, const uint16_t* d_inv_map,
-                                               int n_frames, int sym_per_chunk, size_t bits_frame_stride,
-                                               const dabgpu_frame_desc* d_desc, const void* d_tail, size_t tail_stride,
-                                               int classed, hipStream_t stream, float* d_total_phase = nullptr, float* d_fine_freq = nullptr,
-                                               float beta = 0.0f, const void* d_prev_tail = nullptr /* stream banks, retained blocks */,
-                                               size_t frame_stride_samples = 0 /* 0 = 196608, frame after frame */,
-                                               dabgpu_sync_state* d_sync = nullptr /* frame k starts prs_offset + d_sync[k].fine_time_offset samples into its
-                                                                                      slice, PLL offset and fine-frequency word are the record's */,
-                                               int prs_offset = 0);
+// one demodulator launch (dabgpu_launch_demod): every field at the value that leaves it out.  The tables are the launcher's to find.
+struct dabgpu_demod_call {
+    // input: frames one after the other unless a stride is given; src = the loader (dabgpu_fused_loader)
+    const void* d_iq = nullptr;
+    int src = 0;
+    size_t frame_stride_samples = 0;            // 0 = the mode's frame, frame after frame
+    const float* d_freq = nullptr;              // per frame, nullptr = 0
+    // outputs
+    int8_t* d_bits = nullptr;
+    size_t bits_frame_stride = 0;               // 0 = 230400
+    int classed = 0;                            // MSC symbols in time-interleaver class order (soft bits only)
+    float* d_cp_corr = nullptr;
+    float* d_fft = nullptr;                     // display views (modes II-IV: d_fft only, from the size-generic kernel)
+    float* d_dqpsk = nullptr;
+    // batch
+    int n_frames = 0;
+    int symbols_per_block = 0;                  // 0 = the mode's default run length
+    bool generic_mode1 = false;                 // mode I on the size-generic kernel (dabgpu_ofdm_demod_frames_mode)
+    // stream bank round: frame = stream, samples [0, split) from d_iq (the frame buffers), the rest from the caller's block(s) in format src
+    const dabgpu_frame_desc* d_desc = nullptr;
+    const void* d_block = nullptr;
+    size_t block_stride = 0;
+    const void* d_prev_block = nullptr;         // retained blocks
+    // sync records: frame k starts prs_offset + d_sync[k].fine_time_offset samples into its slice, PLL offset and fine-frequency word are the record's
+    dabgpu_sync_state* d_sync = nullptr;
+    int prs_offset = 0;
+    // phase tail: total phase error and fine-frequency update of every frame (either may be null)
+    float* d_total_phase = nullptr;
+    float* d_fine_freq = nullptr;
+    float beta = 0.0f;
+};
+// plans the call (dabgpu_host_plan_demod) and launches the demodulation kernel of the mode's family, then the phase kernel if the plan asks for it;
+// what = how a HIP failure of the mode I launch is reported (the entry points' own wording)
+int dabgpu_launch_demod(dabgpu_ctx* c, int mode, const dabgpu_demod_call& a, hipStream_t stream, const char* what = "ofdm_demod_kernel launch");
+// the families outside ofdm_demod.hip: a launch from the plan through the table beside the kernels (ofdm_modes.hip, ofdm_wave512.hip)
+int dabgpu_enqueue_demod_generic(int mode, const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t,
+                                 hipStream_t stream);
+int dabgpu_enqueue_demod_wave(int mode, const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t,
+                              hipStream_t stream);
+// a kernel table has an entry in every place (an initialiser that is too short leaves null pointers behind)
+template <class K, size_t N> constexpr bool dabgpu_kernels_all_set(const K (&table)[N]) {
+    for (size_t i = 0; i < N; i++) if (table[i] == nullptr) return false;
+    return true;
+}
+
 extern "C" hipError_t dabgpu_launch_ofdm_phase(const float* d_cp_corr, int n_frames, float beta, float* d_total_phase,
                                                float* d_fine_freq, int fine_freq_stride, const dabgpu_frame_desc* d_desc, int n_sym, int n_fft,
                                                hipStream_t stream);
-
-// size-generic demodulation (ofdm_modes.hip); d_desc != nullptr = stream bank round (frame = stream, split input)
-int dabgpu_launch_ofdm_demod_mode(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                  float* d_fft, int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
-                                  size_t block_stride, hipStream_t s);
-
-// register-resident demodulation of modes II / IV (ofdm_wave512.hip), same arguments
-int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                  int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
-                                  size_t block_stride, hipStream_t s);
 
 // OFDM transmitter (ofdm_mod.hip): n_frames frames of `mode` from their payloads (layout DABGPU_TX_PAYLOAD_*) into d_out (format
 // DABGPU_IQ_RAW_F32L / _U8), NULL first; d_prs = the PRS spectrum (nb_fft complex float) on the device, nullptr = the mode's own;
@@ -278,9 +303,8 @@ int dabgpu_session_slot(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_sess
 
 // ---- sync ----
 extern "C" hipError_t dabgpu_launch_sync_init(const float* d_prs, const float* d_tw, float* d_prs_time_ref, int n_fft, hipStream_t stream);
-extern "C" hipError_t dabgpu_launch_sync(const float* d_prs_syms, size_t stride_samples, int n_streams, const dabgpu_sync_cfg* cfg,
-                                         dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, const float* d_tw,
-                                         const float* d_prs, const float* d_prs_time_ref, const int* d_active, int mode,
-                                         hipStream_t stream);
+// PRS synchronisation of n_streams symbols against the mode's PRS tables (built on first use)
+int dabgpu_launch_sync(dabgpu_ctx* c, int mode, const float* d_prs_syms, size_t stride_samples, int n_streams, const dabgpu_sync_cfg* cfg,
+                       dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, const int* d_active, hipStream_t stream);
 extern "C" hipError_t dabgpu_launch_cif_deinterleave(const int8_t* d_ring, int n_bits, int n_slots, int newest_slot,
                                                      int8_t* d_out, hipStream_t stream);

@@ -20,6 +20,9 @@
 // hazard nops (A/B: 0.51 ms packed vs 0.46 ms scalar per 1024 frames, profiles/r01/README.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <array>
+#include <utility>
 
 #include "dabgpu_internal.h"
 #include "iq_decode.h"
@@ -541,64 +544,57 @@ void ofdm_phase_kernel(const f2* __restrict__ cp_corr, int n_frames, float beta,
 
 }  // namespace dabgpu
 
-// ---- launchers (called from dabgpu_abi.hip) ----
-// src: 0 interleaved complex float, 1 raw_u8 / wav pcm8, 2 raw_s8, 3 raw_s16l / wav pcm16
-extern "C" hipError_t dabgpu_launch_ofdm_demod(const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                               float* d_fft, float* d_dqpsk, const float* d_tw, const uint16_t* d_inv_map,
-                                               int n_frames, int sym_per_chunk, size_t bits_frame_stride,
-                                               const dabgpu_frame_desc* d_desc, const void* d_tail, size_t tail_stride,
-                                               int classed, hipStream_t stream, float* d_total_phase, float* d_fine_freq, float beta,
-                                               const void* d_prev_tail, size_t frame_stride_samples, dabgpu_sync_state* d_sync, int prs_offset)
-{
-    using namespace dabgpu;
-    if (classed && (d_fft != nullptr || d_dqpsk != nullptr)) return hipErrorInvalidValue;   // soft bits only
-    if (bits_frame_stride == 0) bits_frame_stride = NB_FRAME_BITS;
-    // default: three runs per frame (one extra FFT per run).  A whole frame per workgroup (75) is 1 % faster when 1024 frames are
-    // exactly one round of a 256-CU chip (and lets the phase tail run inside the kernel) but 25 % slower on boxes whose CUs do not
-    // all run at one speed (workgroup lifetimes 0.33 .. 0.53 ms in one static round: 0.536 against 0.427 ms): callers that care
-    // time both (bench.py does) and pass it
-    if (sym_per_chunk <= 0 || sym_per_chunk > 75) sym_per_chunk = 25;
-    const int chunks = (75 + sym_per_chunk - 1) / sym_per_chunk;
-    const size_t lds = DEMOD_LDS_BYTES;
-    const bool views_ = (d_fft != nullptr) || (d_dqpsk != nullptr);
-    // the phase tail runs inside the kernel when one workgroup walks the whole frame; otherwise as its own launch below
-    // frames one after the other unless the caller gives a stride; with sync records the fine-frequency words are theirs
-    if (d_desc != nullptr && (d_sync != nullptr || frame_stride_samples != 0)) return hipErrorInvalidValue;
-    const demod_frame_src fs = {frame_stride_samples ? frame_stride_samples : (size_t)NB_FRAME_SAMPLES, d_sync, prs_offset};
-    int fine_stride = 1;
-    if (d_sync != nullptr) { d_fine_freq = &d_sync->freq_fine; fine_stride = (int)(sizeof(dabgpu_sync_state) / sizeof(float)); }
-    const bool fuse = (d_total_phase != nullptr || d_fine_freq != nullptr) && chunks == 1 && d_desc == nullptr && !views_;
-    const demod_phase_tail pt = {fuse ? d_total_phase : nullptr, fuse ? d_fine_freq : nullptr, beta, fine_stride};
-    const dim3 grid((unsigned)(n_frames * chunks));
-#define DABGPU_LAUNCH_V(SRC, BANK, VIEWS) hipLaunchKernelGGL((ofdm_demod_kernel<SRC, BANK, VIEWS>), grid, dim3(256), lds, stream, \
-                       d_iq, d_freq, d_bits, reinterpret_cast<f2*>(d_cp_corr), \
-                       reinterpret_cast<f2*>(d_fft), reinterpret_cast<f2*>(d_dqpsk), reinterpret_cast<const f2*>(d_tw), d_inv_map, \
-                       n_frames, sym_per_chunk, chunks, bits_frame_stride, d_desc, d_tail, tail_stride, pt, d_prev_tail, fs)
-    const bool views = (d_fft != nullptr) || (d_dqpsk != nullptr);
-#define DABGPU_LAUNCH(SRC, BANK) do { if (views) DABGPU_LAUNCH_V(SRC, BANK, true); else DABGPU_LAUNCH_V(SRC, BANK, false); } while (0)
-#define DABGPU_LAUNCH_CB(SRC, BANK) hipLaunchKernelGGL((ofdm_demod_kernel<SRC, BANK, false, true>), grid, dim3(256), lds, stream, \
-                       d_iq, d_freq, d_bits, reinterpret_cast<f2*>(d_cp_corr), static_cast<f2*>(nullptr), static_cast<f2*>(nullptr), \
-                       reinterpret_cast<const f2*>(d_tw), d_inv_map, n_frames, sym_per_chunk, chunks, bits_frame_stride, d_desc, d_tail, tail_stride, pt, d_prev_tail, fs)
-#define DABGPU_LAUNCH_C(SRC) do { if (d_desc != nullptr) DABGPU_LAUNCH_CB(SRC, true); else DABGPU_LAUNCH_CB(SRC, false); } while (0)
-    switch (src) {
-    case SRC_C32: if (classed) DABGPU_LAUNCH_C(SRC_C32); else if (d_desc != nullptr) DABGPU_LAUNCH(SRC_C32, true); else DABGPU_LAUNCH(SRC_C32, false); break;
-    case SRC_U8: if (classed) DABGPU_LAUNCH_C(SRC_U8); else if (d_desc != nullptr) DABGPU_LAUNCH(SRC_U8, true); else DABGPU_LAUNCH(SRC_U8, false); break;
-    case SRC_S8: if (classed) DABGPU_LAUNCH_C(SRC_S8); else if (d_desc != nullptr) DABGPU_LAUNCH(SRC_S8, true); else DABGPU_LAUNCH(SRC_S8, false); break;
-    case SRC_S16: if (classed) DABGPU_LAUNCH_C(SRC_S16); else if (d_desc != nullptr) DABGPU_LAUNCH(SRC_S16, true); else DABGPU_LAUNCH(SRC_S16, false); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef DABGPU_LAUNCH_C
-#undef DABGPU_LAUNCH_CB
-#undef DABGPU_LAUNCH
-#undef DABGPU_LAUNCH_V
+// ---- launchers ----
+namespace {
+using namespace dabgpu;
+// variant -> kernel, the planner's numbering (dabgpu_host_logic.h): ((loader * 2 + bank) * 3 + layout), layout 1 = display views, 2 = class order
+using demod_kernel_t = decltype(&ofdm_demod_kernel<SRC_C32, false>);
+template <int... V>
+constexpr std::array<demod_kernel_t, sizeof...(V)> mode1_kernels(std::integer_sequence<int, V...>) {
+    return {{ofdm_demod_kernel<V / 6, (V / 3) % 2 == 1, V % 3 == 1, V % 3 == 2>...}};
+}
+constexpr auto MODE1_KERNELS = mode1_kernels(std::make_integer_sequence<int, DABGPU_DEMOD_MODE1_VARIANTS>{});
+static_assert(DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3, "the planner's variants are (loader, bank, layout): the formula above instantiates nothing else");
+static_assert(SRC_C32 == 0 && SRC_U8 == 1 && SRC_S8 == 2 && SRC_S16 == 3, "the planner's loader numbers");
+
+hipError_t enqueue_demod_mode1(const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t, hipStream_t stream) {
+    const bool fuse = p.tail == DABGPU_DEMOD_TAIL_FUSED;
+    float* const d_fine_freq = a.d_sync ? &a.d_sync->freq_fine : a.d_fine_freq;        // with sync records the fine-frequency words are theirs
+    const demod_frame_src fs = {a.frame_stride_samples ? a.frame_stride_samples : (size_t)NB_FRAME_SAMPLES, a.d_sync, a.prs_offset};
+    const demod_phase_tail pt = {fuse ? a.d_total_phase : nullptr, fuse ? d_fine_freq : nullptr, a.beta, p.fine_stride};
+    hipLaunchKernelGGL(MODE1_KERNELS[p.variant], dim3(p.grid), dim3(p.threads), DEMOD_LDS_BYTES, stream, a.d_iq, a.d_freq, a.d_bits,
+                       reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<f2*>(a.d_fft), reinterpret_cast<f2*>(a.d_dqpsk), reinterpret_cast<const f2*>(d_tw),
+                       t.inv_map16, a.n_frames, p.symbols_per_block, p.chunks, a.bits_frame_stride ? a.bits_frame_stride : (size_t)NB_FRAME_BITS, a.d_desc,
+                       a.d_block, a.block_stride, pt, a.d_prev_block, fs);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !fuse && (d_total_phase != nullptr || d_fine_freq != nullptr) && d_desc == nullptr) {
-        hipLaunchKernelGGL(ofdm_phase_kernel, dim3((unsigned)n_frames), dim3(64), 0, stream, reinterpret_cast<const f2*>(d_cp_corr), n_frames, beta,
-                           d_total_phase, d_fine_freq, fine_stride, static_cast<const dabgpu_frame_desc*>(nullptr), NB_FRAME_SYMBOLS, NB_FFT,
-                           static_cast<const dabgpu_sync_state*>(d_sync));
+    if (e == hipSuccess && p.tail == DABGPU_DEMOD_TAIL_LAUNCH) {
+        hipLaunchKernelGGL(ofdm_phase_kernel, dim3((unsigned)a.n_frames), dim3(64), 0, stream, reinterpret_cast<const f2*>(a.d_cp_corr), a.n_frames, a.beta,
+                           a.d_total_phase, d_fine_freq, p.fine_stride, static_cast<const dabgpu_frame_desc*>(nullptr), NB_FRAME_SYMBOLS, NB_FFT,
+                           static_cast<const dabgpu_sync_state*>(a.d_sync));
         e = hipGetLastError();
     }
     return e;
+}
+}  // namespace
+
+int dabgpu_launch_demod(dabgpu_ctx* c, int mode, const dabgpu_demod_call& a, hipStream_t stream, const char* what) {
+    dabgpu_demod_facts f;
+    f.src = a.src; f.desc = a.d_desc != nullptr; f.fft = a.d_fft != nullptr; f.dqpsk = a.d_dqpsk != nullptr; f.sync = a.d_sync != nullptr;
+    f.frame_stride = a.frame_stride_samples != 0; f.total_phase = a.d_total_phase != nullptr; f.fine_freq = a.d_fine_freq != nullptr;
+    f.classed = a.classed != 0; f.symbols_per_block = a.symbols_per_block; f.n_frames = a.n_frames; f.generic_mode1 = a.generic_mode1;
+    // development switches of modes II-IV (the tests cross-check the kernels of a mode with them)
+    f.switch_generic = mode != 1 && getenv("DABGPU_MODE_GENERIC");
+    f.switch_mode3_single = mode == 3 && getenv("DABGPU_MODE3_SINGLE");
+    const dabgpu_demod_plan p = dabgpu_host_plan_demod(mode, f);
+    if (p.status) return p.status;
+    const dabgpu_mode_tables* t;
+    const int st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_demod");
+    if (st) return st;
+    switch (p.family) {
+    case DABGPU_DEMOD_MODE1: return dabgpu_check_hip(enqueue_demod_mode1(p, a, c->d_tw, *t, stream), what);
+    case DABGPU_DEMOD_GENERIC: return dabgpu_enqueue_demod_generic(mode, p, a, c->d_tw, *t, stream);
+    default: return dabgpu_enqueue_demod_wave(mode, p, a, c->d_tw, *t, stream);
+    }
 }
 
 extern "C" hipError_t dabgpu_launch_ofdm_phase(const float* d_cp_corr, int n_frames, float beta, float* d_total_phase,

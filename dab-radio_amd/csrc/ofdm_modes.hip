@@ -9,9 +9,6 @@
 // the soft bits here as they do there.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <algorithm>
-#include <vector>
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -164,42 +161,21 @@ void ofdm_demod_mode_kernel(int mode, const f2* __restrict__ iq, const float* __
 
 using namespace dabgpu;
 
-// size-generic demodulation launch shared by dabgpu_ofdm_demod_frames_mode and the stream bank (d_desc != nullptr: bank round,
-// frame = stream, input split between the bank's frame buffers d_iq and the caller's block d_block in capture format src)
-int dabgpu_launch_ofdm_demod_mode(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                  float* d_fft, int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
-                                  size_t block_stride, hipStream_t s) {
-    ModeGeom g;
-    if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_mode: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
+// variant -> kernel (dabgpu_host_logic.h): complex float without descriptors, loader 0..3 with a bank's
+static constexpr decltype(&ofdm_demod_mode_kernel<0, false>) MODE_KERNELS[] = {ofdm_demod_mode_kernel<0, false>, ofdm_demod_mode_kernel<0, true>,
+                                                                               ofdm_demod_mode_kernel<1, true>, ofdm_demod_mode_kernel<2, true>,
+                                                                               ofdm_demod_mode_kernel<3, true>};
+static_assert(sizeof(MODE_KERNELS) / sizeof(MODE_KERNELS[0]) == DABGPU_DEMOD_LOADER_VARIANTS, "one kernel per variant the planner may choose");
+
+int dabgpu_enqueue_demod_generic(int mode, const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t,
+                                 hipStream_t stream) {
+    const auto kernel = MODE_KERNELS[p.variant];
     int st;
-    // modes II-IV without the GUI view run register-resident, one wavefront per run of symbols (ofdm_wave512.hip);
-    // DABGPU_MODE_GENERIC=1 keeps them on this file's kernel (the tests cross-check the two)
-    if (mode != 1 && !d_fft && !getenv("DABGPU_MODE_GENERIC"))
-        return dabgpu_launch_ofdm_demod_wave(c, mode, d_iq, src, d_freq, d_bits, d_cp_corr, n_frames, symbols_per_block, d_desc, d_block, block_stride, s);
-    const dabgpu_mode_tables* t;     // (mode I: the context's carrier mapper)
-    if ((st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_demod_mode"))) return st;
-    if (symbols_per_block <= 0 || symbols_per_block > g.n_sym - 1) symbols_per_block = 19;
-    const int chunks = (g.n_sym - 1 + symbols_per_block - 1) / symbols_per_block;
-    const size_t lds = ((size_t)g.period + 3 * (size_t)g.n_fft) * sizeof(f2) + 512 * sizeof(float);
-    // measured (tools/bench_io.py, 2048 frames): FFT 512 / 256 run best with 128 threads (0.94 / 1.01 ms; 256 threads 1.03 / 1.47, 64 threads
-    // 1.19 / 1.01), FFT 1024 with 256 (1.93 ms; 128 threads 2.58): fewer idle butterfly lanes against fewer resident wavefronts
-    const int n_threads = (mode == 2 || mode == 3) ? 128 : 256;
-#define MODE_GO(SRC, BANK)                                                                                                          \
-    do {                                                                                                                            \
-        if (lds > 48 * 1024 && (st = dabgpu_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(ofdm_demod_mode_kernel<SRC, BANK>), \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),                   \
-                                                      "hipFuncSetAttribute(ofdm_demod_mode_kernel)"))) return st;                  \
-        hipLaunchKernelGGL((ofdm_demod_mode_kernel<SRC, BANK>), dim3((unsigned)((size_t)n_frames * chunks)), dim3((unsigned)n_threads), lds, s, mode, \
-                           reinterpret_cast<const f2*>(d_iq), d_freq, d_bits, reinterpret_cast<f2*>(d_cp_corr),                    \
-                           reinterpret_cast<f2*>(d_fft), reinterpret_cast<const f2*>(c->d_tw), t->mapper, n_frames,                \
-                           symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride);                  \
-    } while (0)
-    if (!d_desc) MODE_GO(0, false);
-    else if (src == 0) MODE_GO(0, true);
-    else if (src == 1) MODE_GO(1, true);
-    else if (src == 2) MODE_GO(2, true);
-    else MODE_GO(3, true);
-#undef MODE_GO
+    if (p.raise_lds_limit && (st = dabgpu_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                                      (int)p.lds_bytes), "hipFuncSetAttribute(ofdm_demod_mode_kernel)"))) return st;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds_bytes, stream, mode, reinterpret_cast<const f2*>(a.d_iq), a.d_freq, a.d_bits,
+                       reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<f2*>(a.d_fft), reinterpret_cast<const f2*>(d_tw), t.mapper, a.n_frames,
+                       p.symbols_per_block, p.chunks, a.d_desc, static_cast<const uint8_t*>(a.d_block), a.block_stride);
     return dabgpu_check_hip(hipGetLastError(), "ofdm_demod_mode_kernel launch");
 }
 
@@ -218,7 +194,11 @@ int dabgpu_ofdm_demod_frames_mode(dabgpu_ctx* c, int mode, const float* d_iq, si
     hipStream_t s = (hipStream_t)stream;
     float* corr = d_cp_corr;
     if (!corr && (st = dabgpu_scratch(c, SCR_MODE_CORR, n_frames * (size_t)g.n_sym * 2 * sizeof(float), (void**)&corr))) return st;
-    return dabgpu_launch_ofdm_demod_mode(c, mode, d_iq, 0, d_freq, d_bits, corr, d_fft, (int)n_frames, symbols_per_block, nullptr, nullptr, 0, s);
+    dabgpu_demod_call call;
+    call.d_iq = d_iq; call.d_freq = d_freq; call.d_bits = d_bits; call.d_cp_corr = corr; call.d_fft = d_fft;
+    call.n_frames = (int)n_frames; call.symbols_per_block = symbols_per_block;
+    call.generic_mode1 = true;          // (mode I: this entry point is the size-generic kernel's, the tests cross-check it with ofdm_demod_kernel)
+    return dabgpu_launch_demod(c, mode, call, s);
 }
 
 }  // extern "C"

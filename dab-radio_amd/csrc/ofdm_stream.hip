@@ -569,8 +569,6 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
             DABGPU_CK(hipGetLastError());
         }
     }
-    const dabgpu_mode_tables* T;                                            // PRS spectrum / coarse-sync reference of the bank's mode
-    if ((st = dabgpu_mode_tables_of(c, G.mode, &T, "stream_bank_process"))) return st;
     // rounds every locked stream needs: one per frame that can complete inside this block (the demodulation of frame k - 1 and the
     // synchronisation of frame k share a round) plus one for the partial frame at the end; a stream that needs more (re-acquisition)
     // is caught by the counter read back after these
@@ -588,7 +586,8 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     }
     // (an error inside the rounds must not leave work on the side stream unordered with the caller's stream: the caller may free the
     // block and the output buffers as soon as the call has returned)
-#define CKL(call) do { st = dabgpu_check_hip((call), #call); if (st) { if (n_lanes == 2) (void)hipStreamSynchronize(b->side); return st; } } while (0)
+#define CKS(status) do { st = (status); if (st) { if (n_lanes == 2) (void)hipStreamSynchronize(b->side); return st; } } while (0)
+#define CKL(call) CKS(dabgpu_check_hip((call), #call))
     const size_t sb = src_sample_bytes<SRC>::value;
     // run length of the bank's demodulation: four workgroups per frame (19 + 19 + 19 + 18 symbols).  Shorter-lived workgroups hand
     // their slots to the round's small kernels sooner: 256 streams +8 % against three per frame, 1024 streams +1 %; six per frame loses again
@@ -605,20 +604,19 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
                                b->view.not_done + 8 * l + (round & 7), b->view.not_done + 8 * l + ((round + 1) & 7), prev_iq, use_retain ? 1 : 0);
             CKL(hipGetLastError());
             float* corr_l = b->d_corr_out + (size_t)s0 * G.n_sym * 2;
-            if (G.mode == 1) {
-                CKL(dabgpu_launch_ofdm_demod(b->view.frame + (size_t)s0 * G.frame_samples, SRC, b->view.freq + s0, d_bits, corr_l, nullptr, nullptr,
-                                            c->d_tw, T->inv_map16, cnt, bank_spb, 0, b->view.desc + s0, iq_l, stream_stride_samples, classed, ls, nullptr, nullptr, 0.0f,
-                                            prev_iq ? prev_iq + (size_t)s0 * stream_stride_samples * sb : nullptr));
-            } else if ((st = dabgpu_launch_ofdm_demod_mode(     /* (modes II-IV run in one lane: n_lanes == 1, s0 == 0, cnt == n) */c, G.mode, b->view.frame, SRC, b->view.freq, d_bits, b->d_corr_out, nullptr, n, 0,
-                                                           b->view.desc, d_iq, stream_stride_samples, ls))) {
-                if (n_lanes == 2) (void)hipStreamSynchronize(b->side);
-                return st;
-            }
+            // (modes II-IV run in one lane: n_lanes == 1, s0 == 0, cnt == n)
+            dabgpu_demod_call call;
+            call.d_iq = b->view.frame + (size_t)s0 * G.frame_samples; call.src = SRC; call.d_freq = b->view.freq + s0;
+            call.d_bits = d_bits; call.classed = classed; call.d_cp_corr = corr_l;
+            call.n_frames = cnt; call.symbols_per_block = bank_spb;
+            call.d_desc = b->view.desc + s0; call.d_block = iq_l; call.block_stride = stream_stride_samples;
+            call.d_prev_block = prev_iq ? prev_iq + (size_t)s0 * stream_stride_samples * sb : nullptr;
+            CKS(dabgpu_launch_demod(c, G.mode, call, ls));
             CKL(dabgpu_launch_ofdm_phase(corr_l, cnt, b->cfg.sync.fine_freq_update_beta, nullptr, &b->view.sync[s0].freq_fine,
                                         (int)(sizeof(dabgpu_sync_state) / sizeof(float)), b->view.desc + s0, G.n_sym, G.n_fft, ls));
             // (after the phase kernel: the synchroniser of frame k sees the fine frequency the phase of frame k - 1 left, as in the reference)
-            CKL(dabgpu_launch_sync(reinterpret_cast<const float*>(b->view.corr + (size_t)s0 * NB_CORR + NB_NULL_PERIOD), NB_CORR, cnt, &b->cfg.sync,
-                                  b->view.sync + s0, nullptr, nullptr, c->d_tw, T->prs, T->prs_time_ref, b->view.sync_active + s0, G.mode, ls));
+            CKS(dabgpu_launch_sync(c, G.mode, reinterpret_cast<const float*>(b->view.corr + (size_t)s0 * NB_CORR + NB_NULL_PERIOD), NB_CORR, cnt, &b->cfg.sync,
+                                   b->view.sync + s0, nullptr, nullptr, b->view.sync_active + s0, ls));
         }
         if (round + 1 >= blind_rounds) {
             for (int l = 0; l < n_lanes; l++) CKL(hipMemcpyAsync(&h_not_done[l], b->view.not_done + 8 * l + (round & 7), sizeof(int), hipMemcpyDeviceToHost, lane_stream[l]));
@@ -632,6 +630,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
         CKL(hipGetLastError());
     }
 #undef CKL
+#undef CKS
     if (n_lanes == 2) {
         DABGPU_CK(hipEventRecord(b->ev_join, b->side));
         DABGPU_CK(hipStreamWaitEvent(s, b->ev_join, 0));

@@ -299,15 +299,16 @@ extern "C" hipError_t dabgpu_launch_sync_init(const float* d_prs, const float* d
     return hipGetLastError();
 }
 
-extern "C" hipError_t dabgpu_launch_sync(const float* d_prs_syms, size_t stride_samples, int n_streams, const dabgpu_sync_cfg* cfg,
-                                         dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, const float* d_tw,
-                                         const float* d_prs, const float* d_prs_time_ref, const int* d_active, int mode,
-                                         hipStream_t stream) {
+int dabgpu_launch_sync(dabgpu_ctx* c, int mode, const float* d_prs_syms, size_t stride_samples, int n_streams, const dabgpu_sync_cfg* cfg,
+                       dabgpu_sync_state* d_states, float* d_impulse, float* d_freq, const int* d_active, hipStream_t stream) {
     using namespace dabgpu;
     ModeGeom g;
-    if (!mode_geometry(mode, g)) return hipErrorInvalidValue;
+    const dabgpu_mode_tables* t;
+    const int st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_sync");
+    if (st) return st;
+    mode_geometry(mode, g);
     hipLaunchKernelGGL(ofdm_sync_kernel, dim3((unsigned)n_streams), dim3(256), dabgpu_sync_lds_bytes(g.n_fft), stream,
                        reinterpret_cast<const f2*>(d_prs_syms), stride_samples, n_streams, *cfg, d_states, d_impulse, d_freq,
-                       reinterpret_cast<const f2*>(d_tw), reinterpret_cast<const f2*>(d_prs), reinterpret_cast<const f2*>(d_prs_time_ref), d_active, g);
-    return hipGetLastError();
+                       reinterpret_cast<const f2*>(c->d_tw), reinterpret_cast<const f2*>(t->prs), reinterpret_cast<const f2*>(t->prs_time_ref), d_active, g);
+    return dabgpu_check_hip(hipGetLastError(), "ofdm_sync_kernel launch");
 }

@@ -15,8 +15,6 @@
 // (1 TB/s, barrier-bound) remains for the GUI views (fft_out) and as the cross-check of this one in the tests.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <vector>
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -443,46 +441,29 @@ void ofdm_demod_wave3_kernel(const f2* __restrict__ iq, const float* __restrict_
 
 using namespace dabgpu;
 
-// modes II, III and IV without the GUI views; frame = stream when d_desc != nullptr (stream bank rounds)
-int dabgpu_launch_ofdm_demod_wave(dabgpu_ctx* c, int mode, const void* d_iq, int src, const float* d_freq, int8_t* d_bits, float* d_cp_corr,
-                                  int n_frames, int symbols_per_block, const dabgpu_frame_desc* d_desc, const void* d_block,
-                                  size_t block_stride, hipStream_t s) {
-    ModeGeom g;
-    if ((mode != 2 && mode != 3 && mode != 4) || !mode_geometry(mode, g)) { dabgpu_set_error("ofdm_demod_wave: mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
-    const dabgpu_mode_tables* t;
-    const int st = dabgpu_mode_tables_of(c, mode, &t, "ofdm_demod_wave");
-    if (st) return st;
-    const int* d_inv = t->inv_map;            // carrier c carries soft bit d_inv[c]
-    if (symbols_per_block <= 0 || symbols_per_block > g.n_sym - 1) symbols_per_block = 19;
-    const int chunks = (g.n_sym - 1 + symbols_per_block - 1) / symbols_per_block;
-    const size_t units = (size_t)n_frames * chunks;
-    const dim3 grid((unsigned)((units + 3) / 4));
-#define WAVE_GO(MODE, SRC, BANK)                                                                                                   \
-    hipLaunchKernelGGL((ofdm_demod_wave_kernel<MODE, SRC, BANK>), grid, dim3(256), 0, s, reinterpret_cast<const f2*>(d_iq), d_freq, d_bits, \
-                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), d_inv, n_frames,                      \
-                       symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride)
-#define WAVE_MODE(MODE)                                          \
-    do {                                                         \
-        if (!d_desc) WAVE_GO(MODE, 0, false);                    \
-        else if (src == 0) WAVE_GO(MODE, 0, true);               \
-        else if (src == 1) WAVE_GO(MODE, 1, true);               \
-        else if (src == 2) WAVE_GO(MODE, 2, true);               \
-        else WAVE_GO(MODE, 3, true);                             \
-    } while (0)
-#define WAVE3_GO(SRC, BANK)                                                                                                          \
-    hipLaunchKernelGGL((ofdm_demod_wave3_kernel<SRC, BANK>), grid, dim3(256), 0, s, reinterpret_cast<const f2*>(d_iq), d_freq, d_bits,    \
-                       reinterpret_cast<f2*>(d_cp_corr), reinterpret_cast<const f2*>(c->d_tw), d_inv, n_frames,                       \
-                       symbols_per_block, chunks, d_desc, static_cast<const uint8_t*>(d_block), block_stride)
-    if (mode == 2) WAVE_MODE(2);
-    else if (mode == 4) WAVE_MODE(4);
-    else if (getenv("DABGPU_MODE3_SINGLE")) WAVE_MODE(3);          // development: one symbol per wavefront (the cross-check of the tests)
-    else if (!d_desc) WAVE3_GO(0, false);
-    else if (src == 0) WAVE3_GO(0, true);
-    else if (src == 1) WAVE3_GO(1, true);
-    else if (src == 2) WAVE3_GO(2, true);
-    else WAVE3_GO(3, true);
-#undef WAVE3_GO
-#undef WAVE_MODE
-#undef WAVE_GO
+// modes II, III and IV without the GUI views; frame = stream when a.d_desc != nullptr (stream bank rounds)
+// [row][variant] -> kernel (dabgpu_host_logic.h): rows = modes II, III, IV one symbol per wavefront, then mode III two symbols per wavefront;
+// variant = complex float without descriptors, loader 0..3 with a bank's
+using wave_kernel_t = decltype(&ofdm_demod_wave3_kernel<0, false>);
+static constexpr wave_kernel_t WAVE_KERNELS[][DABGPU_DEMOD_LOADER_VARIANTS] = {
+    {ofdm_demod_wave_kernel<2, 0, false>, ofdm_demod_wave_kernel<2, 0, true>, ofdm_demod_wave_kernel<2, 1, true>, ofdm_demod_wave_kernel<2, 2, true>,
+     ofdm_demod_wave_kernel<2, 3, true>},
+    {ofdm_demod_wave_kernel<3, 0, false>, ofdm_demod_wave_kernel<3, 0, true>, ofdm_demod_wave_kernel<3, 1, true>, ofdm_demod_wave_kernel<3, 2, true>,
+     ofdm_demod_wave_kernel<3, 3, true>},
+    {ofdm_demod_wave_kernel<4, 0, false>, ofdm_demod_wave_kernel<4, 0, true>, ofdm_demod_wave_kernel<4, 1, true>, ofdm_demod_wave_kernel<4, 2, true>,
+     ofdm_demod_wave_kernel<4, 3, true>},
+    {ofdm_demod_wave3_kernel<0, false>, ofdm_demod_wave3_kernel<0, true>, ofdm_demod_wave3_kernel<1, true>, ofdm_demod_wave3_kernel<2, true>,
+     ofdm_demod_wave3_kernel<3, true>},
+};
+static_assert(sizeof(WAVE_KERNELS) / sizeof(WAVE_KERNELS[0]) == 4 && dabgpu_kernels_all_set(WAVE_KERNELS[0]) && dabgpu_kernels_all_set(WAVE_KERNELS[1]) &&
+                  dabgpu_kernels_all_set(WAVE_KERNELS[2]) && dabgpu_kernels_all_set(WAVE_KERNELS[3]),
+              "four rows, and in each one kernel per variant the planner may choose");
+
+int dabgpu_enqueue_demod_wave(int mode, const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(WAVE_KERNELS[p.family == DABGPU_DEMOD_WAVE3 ? 3 : mode - 2][p.variant], dim3(p.grid), dim3(p.threads), 0, stream,
+                       reinterpret_cast<const f2*>(a.d_iq), a.d_freq, a.d_bits, reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<const f2*>(d_tw),
+                       t.inv_map /* carrier c carries soft bit inv_map[c] */, a.n_frames, p.symbols_per_block, p.chunks, a.d_desc,
+                       static_cast<const uint8_t*>(a.d_block), a.block_stride);
     return dabgpu_check_hip(hipGetLastError(), "ofdm_demod_wave_kernel launch");
 }

@@ -253,8 +253,7 @@ int hip_bank::enqueue_tick(const rx_bank_round& r) {
         BK(hipMemcpyAsync(d_prs + (size_t)lo * NFFT * 2, h_prs + (size_t)lo * NFFT * 2, (size_t)(up - lo + 1) * NFFT * 2 * sizeof(float), hipMemcpyHostToDevice, a));
         const dabgpu_sync_cfg& cfg = r.sync_jobs[0].cfg;
         const bool coarse = cfg.is_coarse_freq_correction != 0;
-        const dabgpu_mode_tables& mode1 = c->modes[1];
-        BK(dabgpu_launch_sync(d_prs, NFFT, t.n_ens, &cfg, d_states, d_imp, coarse ? d_frq : nullptr, c->d_tw, mode1.prs, mode1.prs_time_ref, dtab->sync_active, 1, a));
+        if ((st = dabgpu_launch_sync(c, 1, d_prs, NFFT, t.n_ens, &cfg, d_states, d_imp, coarse ? d_frq : nullptr, dtab->sync_active, a))) return st;
         BK(hipMemcpyAsync(t.h_states, d_states, (size_t)t.n_ens * sizeof(dabgpu_sync_state), hipMemcpyDeviceToHost, a));
         BK(hipMemcpyAsync(t.h_imp, d_imp, (size_t)t.n_ens * NFFT * sizeof(float), hipMemcpyDeviceToHost, a));
         if (coarse) BK(hipMemcpyAsync(t.h_frq, d_frq, (size_t)t.n_ens * NFFT * sizeof(float), hipMemcpyDeviceToHost, a));

@@ -4,7 +4,7 @@ AddressSanitizer preset, CMakePresets.json:47-53):
  (a) the CPU ORACLE -- the checker that grades everything -- built with -fsanitize=address,undefined (oracle/Makefile SAN=1) runs its
      own CPU tests clean;
  (b) the DEVICE-FREE PART OF libdabgpu.so (dab-radio_amd/csrc/dabgpu_host_logic.cpp: protection-profile plans, codeword validation,
-     mapping cost model, the decode planner, run-length rules, constant tables, capture-format and wav-header parsing), built on its own
+     mapping cost model, the decode and demodulation planners, run-length rules, constant tables, capture-format and wav-header parsing), built on its own
      under ASan + UBSan and fuzzed (tests/cpp/host_logic_fuzz.cpp): hostile sub-channel descriptors, decode plans of random multiplexes and a
      table of hand-worked ones, wav images with lying chunk sizes, truncations;
  (c) the C++ MIRROR CLASSES' host code (framing state machine, frame batcher with one session per demodulator, shared context,
@@ -64,6 +64,14 @@ def test_device_free_library_code_fuzzed_under_asan_and_ubsan(tmp_path):
         # the fuzzer reached both sides of every decision: it saw accepted AND rejected inputs of each kind
         assert 0 < out["accepted_plans"] < out["iterations"] and 0 < out["accepted_wav"] < out["iterations"] and 0 < out["accepted_codewords"] < out["iterations"]
         assert 0 < out["accepted_decode_plans"] < out["iterations"]
+
+
+def test_demodulation_planner_over_every_combination_under_asan_and_ubsan(tmp_path):
+    """tests/cpp/demod_plan_driver.cpp (tests/test_demod_plan.py runs it plain): every combination of the facts of a demodulator launch, instrumented"""
+    lib_of("libasan.so")
+    import test_demod_plan as P
+    exe = P.build_driver(tmp_path, ("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"))
+    P.check_every_combination(exe, env=dict(os.environ, ASAN_OPTIONS="abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1"))
 
 
 MIRROR_SRCS = ["ofdm/ofdm_demodulator.cpp", "ofdm/dab_refs.cpp", "dab/dabgpu_shared_context.cpp", "dab/dabgpu_frame_batcher.cpp", "dab/fic/fic_decoder.cpp",
