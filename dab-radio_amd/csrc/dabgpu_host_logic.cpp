@@ -826,3 +826,41 @@ extern "C" uint64_t dabgpu_channel_freq_q64(double cycles) {
 }
 
 extern "C" double dabgpu_channel_freq_cycles(uint64_t freq_q64) { return std::ldexp((double)(int64_t)freq_q64, -64); }
+
+// ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
+#include "tii_core.h"
+
+extern "C" void dabgpu_tii_cfg_default(dabgpu_tii_cfg* cfg) {
+    if (!cfg) return;
+    cfg->threshold = DABGPU_TII_DEFAULT_THRESHOLD;
+    cfg->reserved = 0;
+}
+extern "C" int dabgpu_tii_pattern(int main_id) { return (main_id < 0 || main_id >= DABGPU_TII_NB_MAIN) ? -1 : (int)dabgpu::tii_pattern(main_id); }
+extern "C" int dabgpu_tii_main_id(uint32_t mask) { return dabgpu::tii_main_id(mask); }
+extern "C" int dabgpu_tii_carriers(int main_id, int sub_id, int out[32]) {
+    if (!out) { dabgpu_set_error("tii_carriers: null output"); return DABGPU_ERR_INVALID_ARG; }
+    if (main_id < 0 || main_id >= DABGPU_TII_NB_MAIN) { dabgpu_set_error("tii_carriers: main id %d outside 0..69", main_id); return DABGPU_ERR_INVALID_ARG; }
+    if (sub_id < 0 || sub_id >= DABGPU_TII_COMBS) { dabgpu_set_error("tii_carriers: sub id %d outside 0..23", sub_id); return DABGPU_ERR_INVALID_ARG; }
+    for (int q = 0; q < 32; q++) { int k0; out[q] = dabgpu::tii_carrier(main_id, sub_id, q, &k0); }
+    return DABGPU_OK;
+}
+extern "C" int dabgpu_tii_validate(const dabgpu_tii_tx* tii, const uint8_t* tii_count, size_t n_frames) {
+    if (!tii_count || n_frames == 0) return DABGPU_OK;
+    if (!tii) { dabgpu_set_error("tii: counts without a transmitter list"); return DABGPU_ERR_INVALID_ARG; }
+    for (size_t f = 0; f < n_frames; f++) {
+        if (tii_count[f] > DABGPU_TII_MAX_TX) {
+            dabgpu_set_error("tii: frame %zu: %u transmitters (at most %d)", f, (unsigned)tii_count[f], DABGPU_TII_MAX_TX); return DABGPU_ERR_INVALID_ARG;
+        }
+        for (unsigned i = 0; i < tii_count[f]; i++) {
+            const dabgpu_tii_tx& t = tii[f * DABGPU_TII_MAX_TX + i];
+            if (t.main_id >= DABGPU_TII_NB_MAIN) {
+                dabgpu_set_error("tii: frame %zu: transmitter %u: main id %u outside 0..69", f, i, (unsigned)t.main_id); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (t.sub_id >= DABGPU_TII_COMBS) {
+                dabgpu_set_error("tii: frame %zu: transmitter %u: sub id %u outside 0..23", f, i, (unsigned)t.sub_id); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (!std::isfinite(t.amp)) { dabgpu_set_error("tii: frame %zu: transmitter %u: amp is not finite", f, i); return DABGPU_ERR_INVALID_ARG; }
+        }
+    }
+    return DABGPU_OK;
+}

@@ -25,7 +25,9 @@ enum dabgpu_scratch_slot : int {
     // 1-6: single-frame host forms (*_host_sync, *_stream_frame_sync): IQ in, soft bits out, frequency words (or [net, fine, total phase]),
     // correlations, total phases, FFT view; the transmitter's host form: IQ out, payload in BITS, the caller's PRS in FFT
     SCR_HOST_IQ, SCR_HOST_BITS, SCR_HOST_FREQ, SCR_HOST_CORR, SCR_HOST_PHASE, SCR_HOST_FFT,
-    SCR_SYNC_SYM, SCR_SYNC_STATE, SCR_SYNC_RESP,     // 7-9: ofdm_sync_host_sync: PRS symbol, record, responses
+    // shared, as SCR_TUNE_TAIL below: the transmitter's host form has neither correlations nor frequency words, its TII lists and counts live there
+    SCR_HOST_TII_LIST = SCR_HOST_CORR, SCR_HOST_TII_COUNT = SCR_HOST_FREQ,
+    SCR_SYNC_SYM = SCR_HOST_FFT + 1, SCR_SYNC_STATE, SCR_SYNC_RESP,     // 7-9: ofdm_sync_host_sync: PRS symbol, record, responses
     SCR_CW_DESCS, SCR_VIT_WAVE, SCR_MSC_PLANS,       // 10-12: codeword descriptors, wave Viterbi state, MSC plans
     SCR_HOST_DQPSK,                                  // 13: DQPSK view of the single-frame host form
     SCR_CW_SRC, SCR_CW_OUT, SCR_CW_RESULT,           // 14-16: one codeword from host memory
@@ -194,9 +196,10 @@ extern "C" hipError_t dabgpu_launch_ofdm_phase(const float* d_cp_corr, int n_fra
 
 // OFDM transmitter (ofdm_mod.hip): n_frames frames of `mode` from their payloads (layout DABGPU_TX_PAYLOAD_*) into d_out (format
 // DABGPU_IQ_RAW_F32L / _U8), NULL first; d_prs = the PRS spectrum (nb_fft complex float) on the device, nullptr = the mode's own;
-// arguments checked by the caller
+// arguments checked by the caller.  d_tii [n_frames][DABGPU_TII_MAX_TX] and d_tii_count [n_frames] (mode I, both or neither): the TII
+// symbol in the NULL period of the frames that name transmitters
 int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int layout, size_t n_frames, const float* d_prs, float freq_norm,
-                           void* d_out, int out_format, hipStream_t s);
+                           void* d_out, int out_format, hipStream_t s, const dabgpu_tii_tx* d_tii = nullptr, const uint8_t* d_tii_count = nullptr);
 
 // ---- channel decode ----
 typedef dabgpu_codeword dabgpu_cw_desc;

@@ -1,7 +1,8 @@
 // ofdm_mod.hip -- the OFDM transmitter on the device: OFDM_Modulator::ProcessBlock (src/ofdm/ofdm_modulator.cpp:49-156) for a batch of
 // independent frames, optionally followed by the frequency shift and 8-bit quantisation of examples/simulate_transmitter.cpp:167-178.
 // Per frame, NULL first (transmission order):
-//   NULL period            zeros
+//   NULL period            zeros, or (dabgpu_ofdm_modulate_frames_tii, mode I) the frame's TII symbol: the inverse transform of the comb
+//                          spectrum of its transmitters (tii_core.h) behind its last 608 samples
 //   PRS symbol             IFFT(PRS spectrum), cyclic prefix = its last nb_cyclic_prefix samples
 //   data symbols 1..L-1    X_s = X_{s-1} * z_s per carrier (X_0 = the PRS bin; re = x.re*z.re - x.im*z.im, im = x.re*z.im + x.im*z.re,
 //                          no fused operations), IFFT, cyclic prefix
@@ -27,6 +28,7 @@
 #include "dabgpu_internal.h"
 #include "ofdm_device.h"
 #include "ofdm_fft_lds.h"
+#include "tii_core.h"
 
 namespace dabgpu {
 
@@ -109,12 +111,40 @@ __device__ __forceinline__ void tx_step_mode1(f2 (&X)[TX_CPT], const TxRaw<LAYOU
     }
 }
 
+// the TII symbol of a frame with n_tx > 0 transmitters in the NULL period (include/dabgpu.h, "TII"): the spectra add in list order, one
+// carrier per thread and transmitter (a transmitter's 32 carriers are distinct; two transmitters may meet on one, hence the barrier)
+template <int OUT, bool PLL>
+__device__ __forceinline__ void tx_null_tii(f2* A, const Fft2048Tw& w, const f2* __restrict__ prs, const dabgpu_tii_tx* __restrict__ list, int n_tx,
+                                            size_t o_frame, float f, float scale, void* __restrict__ out) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int r = 0; r < 8; r++) A[t + 256 * r] = mk2(0.0f, 0.0f);
+    __syncthreads();
+    for (int i = 0; i < n_tx; i++) {
+        const dabgpu_tii_tx tx = list[i];
+        if (t < 32 && tx.main_id < TII_NB_MAIN && tx.sub_id < TII_COMBS) {
+            int k0;
+            const int k = tii_carrier(tx.main_id, tx.sub_id, t, &k0);
+            const f2 ph = prs[tii_bin(k0)], z = A[tii_bin(k)];
+            A[tii_bin(k)] = mk2(z.x + tx.amp * ph.x, z.y + tx.amp * ph.y);
+        }
+        __syncthreads();
+    }
+    fft2048_lds(A, w, true);
+    for (int q = t; q < TX_NULL / 2; q += 256) {
+        const int n = 2 * q, i = (n < TII_PREFIX) ? n + (NB_FFT - TII_PREFIX) : n - TII_PREFIX;   // prefix = the transform's last 608 samples
+        tx_store_pair<OUT, PLL>(A[i], A[i + 1], n, o_frame + n, f, scale, out);
+    }
+    __syncthreads();                                                   // every sample read before the PRS spectrum goes in
+}
+
 // mode I: one 256-thread workgroup per (frame, run of symbols [s0, s1)); symbol 0 is the PRS, the run holding it also writes the NULL
-template <int OUT, int LAYOUT, bool PLL>
+// (TII: tii [n_frames][4] and tii_count [n_frames] say what the NULL carries; !TII: neither is read)
+template <int OUT, int LAYOUT, bool PLL, bool TII>
 __global__ __launch_bounds__(256)
 void ofdm_mod_kernel(const uint8_t* __restrict__ payload, const f2* __restrict__ prs, const f2* __restrict__ tw,
                      const uint16_t* __restrict__ inv_map, int n_frames, int sym_per_run, int runs_per_frame, float f, float scale,
-                     void* __restrict__ out)
+                     void* __restrict__ out, const dabgpu_tii_tx* __restrict__ tii, const uint8_t* __restrict__ tii_count)
 {
     __shared__ __attribute__((aligned(16))) f2 A[4 * WAVE_PATCH];
     const int t = threadIdx.x;
@@ -137,8 +167,13 @@ void ofdm_mod_kernel(const uint8_t* __restrict__ payload, const f2* __restrict__
     // replay the carrier chain up to the run's first symbol
     for (int s = 1; s < s0; s++) tx_step_mode1<LAYOUT>(X, tx_load_mode1<LAYOUT>(pl + (size_t)(s - 1) * TX_SYM_BYTES, t, nbit), t, nbit);
 
-    if (s0 == 0)                                                       // the NULL period: zeros through the same shift and conversion
-        for (int q = t; q < TX_NULL / 2; q += 256) tx_store_pair<OUT, PLL>(mk2(0.0f, 0.0f), mk2(0.0f, 0.0f), 2 * q, o_frame + 2 * q, f, scale, out);
+    if (s0 == 0) {
+        int n_tx = 0;
+        if constexpr (TII) n_tx = min((int)tii_count[frame], DABGPU_TII_MAX_TX);
+        if (n_tx > 0) tx_null_tii<OUT, PLL>(A, w, prs, tii + (size_t)frame * DABGPU_TII_MAX_TX, n_tx, o_frame, f, scale, out);
+        else                                                           // the NULL period: zeros through the same shift and conversion
+            for (int q = t; q < TX_NULL / 2; q += 256) tx_store_pair<OUT, PLL>(mk2(0.0f, 0.0f), mk2(0.0f, 0.0f), 2 * q, o_frame + 2 * q, f, scale, out);
+    }
 
     TxRaw<LAYOUT> raw = {};
     if (s0 >= 1) raw = tx_load_mode1<LAYOUT>(pl + (size_t)(s0 - 1) * TX_SYM_BYTES, t, nbit);
@@ -261,9 +296,11 @@ static int tx_sym_per_run(dabgpu_ctx* c, size_t n_frames, int n_sym) {
 }
 
 int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int layout, size_t n_frames, const float* d_prs, float freq_norm,
-                           void* d_out, int out_format, hipStream_t s) {
+                           void* d_out, int out_format, hipStream_t s, const dabgpu_tii_tx* d_tii, const uint8_t* d_tii_count) {
     ModeGeom g;
     if (!mode_geometry(mode, g)) { dabgpu_set_error("ofdm_modulate_frames: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
+    const bool tii = d_tii && d_tii_count;
+    if (tii && mode != 1) { dabgpu_set_error("ofdm_modulate_frames_tii: TII is defined for transmission mode I only (mode %d)", mode); return DABGPU_ERR_INVALID_ARG; }
     // (modes II-IV: their tables are built only by a call that reads them)
     const dabgpu_mode_tables* t = nullptr;
     int st = DABGPU_OK;
@@ -279,9 +316,13 @@ int dabgpu_launch_ofdm_mod(dabgpu_ctx* c, int mode, const uint8_t* d_payload, in
     const f2* tw = reinterpret_cast<const f2*>(c->d_tw);
 #define TX_GO(OUT, LAYOUT, PLL)                                                                                                       \
     do {                                                                                                                              \
-        if (mode == 1)                                                                                                                \
-            hipLaunchKernelGGL((ofdm_mod_kernel<OUT, LAYOUT, PLL>), dim3((unsigned)units), dim3(256), 0, s, d_payload, prs, tw,       \
-                               t->inv_map16, (int)n_frames, spb, runs, freq_norm, scale, d_out);                                      \
+        if (mode == 1 && tii)                                                                                                         \
+            hipLaunchKernelGGL((ofdm_mod_kernel<OUT, LAYOUT, PLL, true>), dim3((unsigned)units), dim3(256), 0, s, d_payload, prs, tw, \
+                               t->inv_map16, (int)n_frames, spb, runs, freq_norm, scale, d_out, d_tii, d_tii_count);                  \
+        else if (mode == 1)                                                                                                           \
+            hipLaunchKernelGGL((ofdm_mod_kernel<OUT, LAYOUT, PLL, false>), dim3((unsigned)units), dim3(256), 0, s, d_payload, prs, tw, \
+                               t->inv_map16, (int)n_frames, spb, runs, freq_norm, scale, d_out, (const dabgpu_tii_tx*)nullptr,        \
+                               (const uint8_t*)nullptr);                                                                              \
         else                                                                                                                          \
             hipLaunchKernelGGL((ofdm_mod_mode_kernel<OUT, LAYOUT, PLL>), dim3((unsigned)units), dim3(256), 0, s, mode, d_payload, prs, \
                                tw, d_inv, (int)n_frames, spb, runs, freq_norm, scale, d_out);                                         \
@@ -315,20 +356,41 @@ static int tx_check(dabgpu_ctx* c, int mode, const void* payload, int layout, si
     return DABGPU_OK;
 }
 
-int dabgpu_ofdm_modulate_frames(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int payload_layout, size_t n_frames, const float* d_prs_fft_ref,
-                                float freq_norm, void* d_out, int out_format, void* stream) {
-    int st = tx_check(c, mode, d_payload, payload_layout, n_frames, d_out, out_format, "ofdm_modulate_frames");
-    if (st || n_frames == 0) return st;
-    if ((uintptr_t)d_out & 15) { dabgpu_set_error("ofdm_modulate_frames: d_out must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_prs_fft_ref & 7) { dabgpu_set_error("ofdm_modulate_frames: d_prs_fft_ref must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+// both device forms; d_tii / d_tii_count = nullptr: no TII
+static int tx_modulate(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int payload_layout, size_t n_frames, const float* d_prs_fft_ref, float freq_norm,
+                       void* d_out, int out_format, void* stream, const dabgpu_tii_tx* d_tii, const uint8_t* d_tii_count, const char* who) {
+    int st = tx_check(c, mode, d_payload, payload_layout, n_frames, d_out, out_format, who);
+    if (st) return st;
+    if (d_tii && d_tii_count && mode != 1) { dabgpu_set_error("%s: TII is defined for transmission mode I only (mode %d)", who, mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0) return st;
+    if ((uintptr_t)d_out & 15) { dabgpu_set_error("%s: d_out must be 16-byte aligned", who); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_prs_fft_ref & 7) { dabgpu_set_error("%s: d_prs_fft_ref must be 8-byte aligned", who); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_tii & 3) { dabgpu_set_error("%s: d_tii must be 4-byte aligned", who); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(c);
-    return dabgpu_launch_ofdm_mod(c, mode, d_payload, payload_layout, n_frames, d_prs_fft_ref, freq_norm, d_out, out_format, (hipStream_t)stream);
+    return dabgpu_launch_ofdm_mod(c, mode, d_payload, payload_layout, n_frames, d_prs_fft_ref, freq_norm, d_out, out_format, (hipStream_t)stream, d_tii,
+                                  d_tii_count);
 }
 
-int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx* c, int mode, const uint8_t* h_payload, int payload_layout, size_t n_frames,
-                                          const float* h_prs_fft_ref, float freq_norm, void* h_out, int out_format) {
-    int st = tx_check(c, mode, h_payload, payload_layout, n_frames, h_out, out_format, "ofdm_modulate_frames_host_sync");
-    if (st || n_frames == 0) return st;
+int dabgpu_ofdm_modulate_frames(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int payload_layout, size_t n_frames, const float* d_prs_fft_ref,
+                                float freq_norm, void* d_out, int out_format, void* stream) {
+    return tx_modulate(c, mode, d_payload, payload_layout, n_frames, d_prs_fft_ref, freq_norm, d_out, out_format, stream, nullptr, nullptr,
+                       "ofdm_modulate_frames");
+}
+
+int dabgpu_ofdm_modulate_frames_tii(dabgpu_ctx* c, int mode, const uint8_t* d_payload, int payload_layout, size_t n_frames, const float* d_prs_fft_ref,
+                                    float freq_norm, void* d_out, int out_format, void* stream, const dabgpu_tii_tx* d_tii, const uint8_t* d_tii_count) {
+    return tx_modulate(c, mode, d_payload, payload_layout, n_frames, d_prs_fft_ref, freq_norm, d_out, out_format, stream, d_tii, d_tii_count,
+                       "ofdm_modulate_frames_tii");
+}
+
+static int tx_modulate_host(dabgpu_ctx* c, int mode, const uint8_t* h_payload, int payload_layout, size_t n_frames, const float* h_prs_fft_ref,
+                            float freq_norm, void* h_out, int out_format, const dabgpu_tii_tx* h_tii, const uint8_t* h_tii_count, const char* who) {
+    int st = tx_check(c, mode, h_payload, payload_layout, n_frames, h_out, out_format, who);
+    if (st) return st;
+    const bool tii = h_tii && h_tii_count;
+    if (tii && mode != 1) { dabgpu_set_error("%s: TII is defined for transmission mode I only (mode %d)", who, mode); return DABGPU_ERR_INVALID_ARG; }
+    if (tii && (st = dabgpu_tii_validate(h_tii, h_tii_count, n_frames))) return st;
+    if (n_frames == 0) return st;
     ModeGeom g;
     mode_geometry(mode, g);
     DABGPU_BIND(c);
@@ -342,13 +404,34 @@ int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx* c, int mode, const uint8_t
     if ((st = dabgpu_scratch(c, SCR_HOST_BITS, in_bytes, (void**)&d_in))) return st;
     if ((st = dabgpu_scratch(c, SCR_HOST_IQ, out_bytes, (void**)&d_out))) return st;
     if (h_prs_fft_ref && (st = dabgpu_scratch(c, SCR_HOST_FFT, prs_bytes, (void**)&d_prs))) return st;
+    dabgpu_tii_tx* d_tii = nullptr;
+    uint8_t* d_cnt = nullptr;
+    if (tii && (st = dabgpu_scratch(c, SCR_HOST_TII_LIST, n_frames * DABGPU_TII_MAX_TX * sizeof(dabgpu_tii_tx), (void**)&d_tii))) return st;
+    if (tii && (st = dabgpu_scratch(c, SCR_HOST_TII_COUNT, n_frames, (void**)&d_cnt))) return st;
     hipStream_t s = c->stream;
     DABGPU_CK(hipMemcpyAsync(d_in, h_payload, in_bytes, hipMemcpyHostToDevice, s));
     if (h_prs_fft_ref) DABGPU_CK(hipMemcpyAsync(d_prs, h_prs_fft_ref, prs_bytes, hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_ofdm_modulate_frames(c, mode, d_in, payload_layout, n_frames, d_prs, freq_norm, d_out, out_format, s))) return st;
+    if (tii) {
+        DABGPU_CK(hipMemcpyAsync(d_tii, h_tii, n_frames * DABGPU_TII_MAX_TX * sizeof(dabgpu_tii_tx), hipMemcpyHostToDevice, s));
+        DABGPU_CK(hipMemcpyAsync(d_cnt, h_tii_count, n_frames, hipMemcpyHostToDevice, s));
+    }
+    if ((st = tx_modulate(c, mode, d_in, payload_layout, n_frames, d_prs, freq_norm, d_out, out_format, s, d_tii, d_cnt, who))) return st;
     DABGPU_CK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipStreamSynchronize(s));
     return DABGPU_OK;
+}
+
+int dabgpu_ofdm_modulate_frames_host_sync(dabgpu_ctx* c, int mode, const uint8_t* h_payload, int payload_layout, size_t n_frames,
+                                          const float* h_prs_fft_ref, float freq_norm, void* h_out, int out_format) {
+    return tx_modulate_host(c, mode, h_payload, payload_layout, n_frames, h_prs_fft_ref, freq_norm, h_out, out_format, nullptr, nullptr,
+                            "ofdm_modulate_frames_host_sync");
+}
+
+int dabgpu_ofdm_modulate_frames_tii_host_sync(dabgpu_ctx* c, int mode, const uint8_t* h_payload, int payload_layout, size_t n_frames,
+                                              const float* h_prs_fft_ref, float freq_norm, void* h_out, int out_format, const dabgpu_tii_tx* h_tii,
+                                              const uint8_t* h_tii_count) {
+    return tx_modulate_host(c, mode, h_payload, payload_layout, n_frames, h_prs_fft_ref, freq_norm, h_out, out_format, h_tii, h_tii_count,
+                            "ofdm_modulate_frames_tii_host_sync");
 }
 
 }  // extern "C"

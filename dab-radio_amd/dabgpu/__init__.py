@@ -75,12 +75,26 @@ ABI_SYMBOLS = [
     "dabgpu_dabplus_superframe_layout", "dabgpu_dabplus_tx_encode", "dabgpu_dabplus_tx_encode_host_sync",
     "dabgpu_channel_plan", "dabgpu_channel_freq_q64", "dabgpu_channel_freq_cycles", "dabgpu_channel_bank_create", "dabgpu_channel_bank_destroy",
     "dabgpu_channel_bank_set_params", "dabgpu_channel_bank_seek", "dabgpu_channel_bank_apply", "dabgpu_channel_bank_apply_host_sync",
+    "dabgpu_tii_cfg_default", "dabgpu_tii_pattern", "dabgpu_tii_main_id", "dabgpu_tii_carriers", "dabgpu_tii_validate",
+    "dabgpu_ofdm_modulate_frames_tii", "dabgpu_ofdm_modulate_frames_tii_host_sync",
+    "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
+    "dabgpu_tii_bank_read",
 ]
 
 # channel model (include/dabgpu.h)
 CHANNEL_MAX_TAPS = 8
 CHANNEL_MAX_DELAY = 2047
 CHANNEL_BLOCK = 1024
+
+# TII (include/dabgpu.h)
+TII_MAX_TX = 4
+TII_NB_MAIN = 70
+TII_COMBS = 24
+TII_GROUPS = 8
+TII_DEFAULT_THRESHOLD = 2.16
+TII_SETTLE_FRAMES = 1          # frames after an acquisition whose sync record is still up to half a carrier spacing off (dabgpu.h, "TII")
+TII_TX_DTYPE = [("main_id", "u1"), ("sub_id", "u1"), ("pad", "<u2"), ("amp", "<f4")]                 # dabgpu_tii_tx
+TII_RECORD_DTYPE = [("sub_id", "<i4"), ("main_id", "<i4"), ("mask", "<u4"), ("strength", "<f4")]   # dabgpu_tii_record
 
 # OFDM transmitter payload layouts (include/dabgpu.h)
 TX_PAYLOAD_REFERENCE = 0
@@ -329,6 +343,25 @@ def lib():
                                                 C.c_float, C.c_void_p]
         L.dabgpu_channel_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
                                                           C.c_size_t, C.c_float]
+        L.dabgpu_tii_cfg_default.argtypes = [C.c_void_p]
+        L.dabgpu_tii_cfg_default.restype = None
+        L.dabgpu_tii_pattern.argtypes = [C.c_int]
+        L.dabgpu_tii_main_id.argtypes = [C.c_uint32]
+        L.dabgpu_tii_carriers.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.dabgpu_tii_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabgpu_ofdm_modulate_frames_tii.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_float,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_ofdm_modulate_frames_tii_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_float,
+                                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.dabgpu_tii_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_tii_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_tii_bank_destroy.restype = None
+        L.dabgpu_tii_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_tii_bank_process.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.dabgpu_tii_bank_process_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                                        C.c_void_p]
+        L.dabgpu_tii_bank_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -625,6 +658,29 @@ class Context:
                                                           _ptr(out), fmt), "dabgpu_ofdm_modulate_frames_host_sync")
         return out
 
+    def ofdm_modulate_frames_tii(self, mode, payload, n_frames, out, tii, tii_count, layout=TX_PAYLOAD_REFERENCE, out_format=None,
+                                 prs_fft_ref=None, freq_norm=0.0, stream=None):
+        """ofdm_modulate_frames with the TII symbol in the NULL period: tii = device [n_frames][4] TII_TX_DTYPE, tii_count = device
+        [n_frames] uint8 (either None: no TII)"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_ofdm_modulate_frames_tii(self._h, int(mode), _ptr(payload), int(layout), n_frames, _ptr(prs_fft_ref), float(freq_norm),
+                                                    _ptr(out), fmt, self._stream(stream), _ptr(tii), _ptr(tii_count)),
+              "dabgpu_ofdm_modulate_frames_tii")
+
+    def ofdm_modulate_frames_tii_host(self, mode, payload, n_frames, tii, layout=TX_PAYLOAD_REFERENCE, out_format=None, prs_fft_ref=None,
+                                      freq_norm=0.0):
+        """numpy form: tii = per frame a list of (main_id, sub_id, amp), at most TII_MAX_TX each (tii_lists packs them)"""
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        n_samp = ofdm_params(mode)["nb_frame_samples"]
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        prs = None if prs_fft_ref is None else np.ascontiguousarray(prs_fft_ref, dtype=np.complex64)
+        lists, counts = tii_lists(tii, n_frames)
+        out = np.empty((n_frames, n_samp), np.complex64) if fmt == IQ_FORMATS.index("raw_f32l") else np.empty((n_frames, 2 * n_samp), np.uint8)
+        check(lib().dabgpu_ofdm_modulate_frames_tii_host_sync(self._h, int(mode), _ptr(payload), int(layout), n_frames, _ptr(prs), float(freq_norm),
+                                                              _ptr(out), fmt, _ptr(lists), _ptr(counts)), "dabgpu_ofdm_modulate_frames_tii_host_sync")
+        return out
+
     def soft_bits_to_hard_bytes(self, bits, n_bytes, out, stream=None):
         check(lib().dabgpu_soft_bits_to_hard_bytes(self._h, _ptr(bits), n_bytes, _ptr(out), self._stream(stream)),
               "dabgpu_soft_bits_to_hard_bytes")
@@ -841,6 +897,90 @@ class Channel:
                                                         float(u8_scale)), "dabgpu_channel_bank_apply_host_sync")
         out = out[:, :n_out * sb]
         return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+
+
+def tii_pattern(main_id):
+    """T[main_id]: the byte whose bit 7 - b says whether group b carries the transmitter; -1 outside 0..69"""
+    return lib().dabgpu_tii_pattern(int(main_id))
+
+
+def tii_carriers(main_id, sub_id):
+    """the 32 carriers (-768 .. 768) of a transmitter, in adjacent pairs"""
+    import numpy as np
+    out = np.zeros(32, np.int32)
+    check(lib().dabgpu_tii_carriers(int(main_id), int(sub_id), _ptr(out)), "dabgpu_tii_carriers")
+    return out
+
+
+def tii_lists(per_frame, n_frames=None):
+    """per frame a list of (main_id, sub_id, amp) -> ([n_frames][4] TII_TX_DTYPE, [n_frames] uint8) as the modulator reads them; a list
+    longer than TII_MAX_TX keeps its count (and is refused by the library), its first four entries are packed"""
+    import numpy as np
+    n = len(per_frame) if n_frames is None else n_frames
+    lists = np.zeros((n, TII_MAX_TX), np.dtype(TII_TX_DTYPE))
+    counts = np.zeros(n, np.uint8)
+    for f, txs in enumerate(per_frame):
+        counts[f] = len(txs)
+        for i, (p, c, amp) in enumerate(txs[:TII_MAX_TX]):
+            lists[f, i] = (p, c, 0, amp)
+    return lists, counts
+
+
+def tii_validate(lists, counts):
+    check(lib().dabgpu_tii_validate(_ptr(lists), _ptr(counts), len(counts)), "dabgpu_tii_validate")
+
+
+class TiiBank:
+    """dabgpu_tii_bank: the TII detector of n receivers; accumulators and frame counts live on the device"""
+
+    def __init__(self, ctx, n, threshold=None):
+        self._ctx = ctx
+        self.n = int(n)
+        cfg = (C.c_float * 2)()
+        lib().dabgpu_tii_cfg_default(cfg)
+        if threshold is not None:
+            cfg[0] = float(threshold)
+        self.threshold = cfg[0]
+        self._h = C.c_void_p()
+        check(lib().dabgpu_tii_bank_create(ctx._h, self.n, cfg, C.byref(self._h)), "dabgpu_tii_bank_create")
+
+    def close(self):
+        if self._h:
+            lib().dabgpu_tii_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None):
+        check(lib().dabgpu_tii_bank_reset(self._h, Context._stream(stream)), "dabgpu_tii_bank_reset")
+
+    def process(self, d_iq, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, decide=False, results=None, counts=None,
+                stream=None):
+        """one frame of every receiver (asynchronous): results = device [n][24] TII_RECORD_DTYPE, counts = device [n] uint32"""
+        check(lib().dabgpu_tii_bank_process(self._h, _ptr(d_iq), stream_stride_samples, null_offset_samples, _ptr(states), _ptr(freq_offset),
+                                            int(bool(decide)), _ptr(results), _ptr(counts), Context._stream(stream)), "dabgpu_tii_bank_process")
+
+    def process_host(self, h_iq, null_offset_samples, freq_offset=0.0, fine_time_offset=0, decide=True):
+        """one receiver from host memory; returns the records of the decision (None without one)"""
+        import numpy as np
+        x = np.ascontiguousarray(h_iq, dtype=np.complex64)
+        rec = np.zeros(TII_COMBS, np.dtype(TII_RECORD_DTYPE))
+        cnt = np.zeros(1, np.uint32)
+        check(lib().dabgpu_tii_bank_process_host_sync(self._h, _ptr(x), x.size, null_offset_samples, float(freq_offset), int(fine_time_offset),
+                                                      int(bool(decide)), _ptr(rec), _ptr(cnt)), "dabgpu_tii_bank_process_host_sync")
+        return rec[:int(cnt[0])] if decide else None
+
+    def read(self, stream=None):
+        """(accumulators [n][24][8] float32, frame counts [n]) behind everything queued on the stream"""
+        import numpy as np
+        acc = np.zeros((self.n, TII_COMBS, TII_GROUPS), np.float32)
+        frames = np.zeros(self.n, np.uint32)
+        check(lib().dabgpu_tii_bank_read(self._h, _ptr(acc), _ptr(frames), Context._stream(stream)), "dabgpu_tii_bank_read")
+        return acc, frames
 
 
 class DabPlusTx:

@@ -10,6 +10,15 @@
 // BasicRadio's first stage produces (basic_radio.cpp:41-65): the CRC-checked FIBs and, for sub-channels given
 // explicitly with --radio-subchannel, the decoded logical frames.
 //
+// --tii (not in the reference; include/dabgpu.h "TII"): a TII_Decoder is fed inside the frame observer from the head of
+// GetCorrelationTimeBuffer() -- the NULL period that follows the delivered frame, cut with that frame's timing, so the fine time offset it
+// is given is 0 -- and GetNetFrequencyOffset(); GetFineTimeOffset() and GetTotalFramesDesync() go into the printed line and the reset rule.
+// It skips the first frame after every acquisition (DABGPU_TII_SETTLE_FRAMES), accumulates, and every --tii-frames accumulated frames
+// (default 8) prints one line on stdout:
+//   tii frames=N fine_time=T net_freq=F: P:C/STRENGTH ...          (?:C/0xMASK/STRENGTH for a comb whose mask is no pattern)
+// The reader must not overwrite the buffer's head while the observer reads it, so with --tii every Process() call is followed by
+// Synchronize() and --ofdm-block-size may not exceed one frame less a NULL period.
+//
 // Output files are byte-for-byte what the reference writes with the same options (frame bits: 230400 int8 per frame,
 // or 28800 bytes per frame with --ofdm-output-hard-bytes, LSB first).
 #include <stdio.h>
@@ -27,6 +36,7 @@
 #include "dab/fic/fic_decoder.h"
 #include "dab/msc/msc_decoder.h"
 #include "ofdm/ofdm_helpers.h"
+#include "ofdm/tii_decoder.h"
 
 struct Args {
     std::string input_file;
@@ -43,6 +53,8 @@ struct Args {
     std::string radio_fib_output;
     std::string radio_msc_output = "subchannel_";
     std::vector<Subchannel> subchannels;
+    bool tii = false;
+    int tii_frames = 8;
 };
 
 static void usage(const char* argv0) {
@@ -52,7 +64,7 @@ static void usage(const char* argv0) {
         "  [--ofdm-enable-output] [--ofdm-output FILE] [--ofdm-output-hard-bytes]\n"
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
-        "  [--radio-msc-output PREFIX]\n"
+        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -113,9 +125,14 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--radio-fib-output") args.radio_fib_output = value();
         else if (a == "--radio-msc-output") args.radio_msc_output = value();
         else if (a == "--radio-subchannel") { const auto v = value(); args.subchannels.push_back(parse_subchannel(v, args.subchannels.size())); }
+        else if (a == "--tii") args.tii = true;
+        else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
+    if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
+    if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
+    if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
     if (args.transmission_mode != 1) throw std::runtime_error("only transmission mode I is implemented");
     if (args.ofdm_block_size == 0) throw std::runtime_error("--ofdm-block-size must be positive");
     return true;
@@ -207,7 +224,24 @@ static int run(const Args& args) {
         auto demod = Create_OFDM_Demodulator(args.transmission_mode);
         demod->GetConfig().sync.is_coarse_freq_correction = !args.ofdm_disable_coarse_freq;
         std::vector<uint8_t> hard;
+        std::unique_ptr<TII_Decoder> tii;
+        if (args.tii) tii = std::make_unique<TII_Decoder>(args.transmission_mode);
+        int tii_desync = 0;
         demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> bits) {
+            if (tii) {
+                if (demod->GetTotalFramesDesync() != tii_desync) { tii_desync = demod->GetTotalFramesDesync(); tii->Reset(); }
+                const auto null_region = demod->GetCorrelationTimeBuffer().first(2656);
+                const float net = demod->GetNetFrequencyOffset();
+                const bool decide = (tii->GetTotalFrames() + 1) % args.tii_frames == 0;
+                if (tii->Process(null_region, net, 0, decide) && decide) {
+                    printf("tii frames=%d fine_time=%d net_freq=%.6g:", tii->GetTotalFrames(), demod->GetFineTimeOffset(), (double)net);
+                    for (const auto& r : tii->GetRecords()) {
+                        if (r.main_id >= 0) printf(" %d:%d/%.1f", r.main_id, r.sub_id, (double)r.strength);
+                        else printf(" ?:%d/0x%02X/%.1f", r.sub_id, r.mask, (double)r.strength);
+                    }
+                    printf("\n");
+                }
+            }
             if (fp_ofdm_out) {
                 if (args.ofdm_output_hard_bytes) {
                     hard.resize(bits.size() / 8);
@@ -224,6 +258,7 @@ static int run(const Args& args) {
             const size_t length = reader->read(block);
             if (length == 0) break;
             demod->Process(tcb::span<const std::complex<float>>(block.data(), length));
+            if (tii) demod->Synchronize();                                          // the observer reads the head of the correlation buffer
             if (length != block.size()) break;
         }
         demod->Synchronize();

@@ -22,6 +22,10 @@
 //   --timing-offset N              the signal N samples late (N >= 0 with channel-coded frames: they are produced one at a time)
 //   --tap DELAY:RE:IM              repeatable, up to 8; delay in samples 0..2047; default one tap 0:1:0
 //   --noise-seed N                 default 1
+// TII (not in the reference, mode I; include/dabgpu.h "TII"):
+//   --tii P:C[:AMP]                repeatable, up to 4: a transmitter with main id P (0..69), sub id C (0..23) and amplitude AMP (default 1 =
+//                                  the power of a data carrier) fills the NULL period of every other frame, the first one included; the
+//                                  frames between keep their zeros.  Not with channel-coded frames.
 #include <stdio.h>
 #include <stdlib.h>
 #include <complex>
@@ -72,6 +76,7 @@ struct Args {
     unsigned long long noise_seed = 1;
     struct Tap { int delay; float re, im; };
     std::vector<Tap> taps;
+    std::vector<dabgpu_tii_tx> tii;
 };
 
 // the channel's parameters for a mode with nb_carriers data carriers
@@ -99,6 +104,15 @@ static Args::Tap parse_tap(const std::string& v) {
     const size_t a = v.find(':'), b = v.find(':', a == std::string::npos ? a : a + 1);
     if (a == std::string::npos || b == std::string::npos) throw std::runtime_error("--tap wants DELAY:RE:IM, got " + v);
     return {std::stoi(v.substr(0, a)), std::stof(v.substr(a + 1, b - a - 1)), std::stof(v.substr(b + 1))};
+}
+
+// P:C[:AMP]
+static dabgpu_tii_tx parse_tii(const std::string& v) {
+    const size_t a = v.find(':'), b = v.find(':', a == std::string::npos ? a : a + 1);
+    if (a == std::string::npos) throw std::runtime_error("--tii wants P:C[:AMP], got " + v);
+    const int p = std::stoi(v.substr(0, a)), c = std::stoi(v.substr(a + 1, b == std::string::npos ? b : b - a - 1));
+    if (p < 0 || p >= DABGPU_TII_NB_MAIN || c < 0 || c >= DABGPU_TII_COMBS) throw std::runtime_error("--tii: main id 0..69 and sub id 0..23, got " + v);
+    return {(uint8_t)p, (uint8_t)c, b == std::string::npos ? 1.0f : std::stof(v.substr(b + 1))};
 }
 
 // START:LENGTH:PROT
@@ -189,13 +203,14 @@ static int run_coded(const Args& args, FILE* fp_out) {
 static void usage(const char* argv0) {
     fprintf(stderr, "usage: %s [-m|--transmission-mode 1..4] [-f|--frequency HZ] [-o|--output FILE] [--frames N]\n"
                     "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
-                    "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N]\n"
+                    "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N] [--tii P:C[:AMP]]...\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
                     "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
                     "quantised: taps (default 0:1:0, delays 0..2047 samples), carrier offset, delay, white Gaussian noise with\n"
                     "  noise_sigma = sqrt(P / (2 * 10^(DB / 10))) per component, P = nb_data_carriers * sum |tap|^2\n"
-                    "(the mean power of the modulator's symbols after the taps; the NULL period is not counted)\n", argv0);
+                    "(the mean power of the modulator's symbols after the taps; the NULL period is not counted);\n"
+                    "with --tii (mode I, up to 4) the NULL period of every other frame carries those transmitters' identification\n", argv0);
 }
 
 static bool parse_args(int argc, char** argv, Args& args) {
@@ -218,9 +233,12 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--timing-offset") { args.timing_offset = std::stoll(value()); args.channel = true; }
         else if (a == "--tap") { args.taps.push_back(parse_tap(value())); args.channel = true; }
         else if (a == "--noise-seed") { args.noise_seed = std::stoull(value()); args.channel = true; }
+        else if (a == "--tii") args.tii.push_back(parse_tii(value()));
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
     }
+    if (args.tii.size() > DABGPU_TII_MAX_TX) throw std::runtime_error("--tii: at most 4 transmitters");
+    if (!args.tii.empty() && args.coded) throw std::runtime_error("--tii is not available with channel-coded frames");
     if (args.transmission_mode < 1 || args.transmission_mode > 4) throw std::runtime_error("--transmission-mode must be one of 1,2,3,4");
     return true;
 }
@@ -265,13 +283,27 @@ int main(int argc, char** argv) {
 
         // modulation, frequency shift (:167-171, only for a non-zero frequency) and quantisation on the device
         const float frequency_norm = (args.frequency != 0.0f) ? args.frequency / 2.048e6f : 0.0f;
-        auto quantised = std::vector<uint8_t>(2 * frame_size);
+        // with TII the transmission is two frames long: the payload twice, the comb in the first NULL period only
+        const size_t n_tx = args.tii.empty() ? 1 : 2;
+        if (n_tx == 2) frame_bytes_buf.insert(frame_bytes_buf.end(), frame_bytes_buf.begin(), frame_bytes_buf.begin() + (long)nb_frame_bytes);
+        dabgpu_tii_tx tii_list[2 * DABGPU_TII_MAX_TX] = {};
+        std::copy(args.tii.begin(), args.tii.end(), tii_list);
+        const uint8_t tii_count[2] = {(uint8_t)args.tii.size(), 0};
+        auto modulate = [&](void* out, int format) {
+            if (n_tx == 2)
+                return dabgpu_ofdm_modulate_frames_tii_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
+                                                                 DABGPU_TX_PAYLOAD_REFERENCE, 2, reinterpret_cast<const float*>(prs_fft_ref.data()),
+                                                                 frequency_norm, out, format, tii_list, tii_count);
+            return dabgpu_ofdm_modulate_frames_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
+                                                         DABGPU_TX_PAYLOAD_REFERENCE, 1, reinterpret_cast<const float*>(prs_fft_ref.data()),
+                                                         frequency_norm, out, format);
+        };
+        auto quantised = std::vector<uint8_t>(2 * frame_size * n_tx);
         if (args.channel) {
-            // the frame once as complex float; the channel reads it as a transmission that repeats
-            auto frame = std::vector<std::complex<float>>(frame_size);
-            const int st = dabgpu_ofdm_modulate_frames_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
-                                                                 DABGPU_TX_PAYLOAD_REFERENCE, 1, reinterpret_cast<const float*>(prs_fft_ref.data()),
-                                                                 frequency_norm, frame.data(), DABGPU_IQ_RAW_F32L);
+            // the transmission once as complex float; the channel reads it as one that repeats
+            auto frame = std::vector<std::complex<float>>(frame_size * n_tx);
+            quantised.resize(2 * frame_size);
+            const int st = modulate(frame.data(), DABGPU_IQ_RAW_F32L);
             if (st != DABGPU_OK) {
                 fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error());
                 return 1;
@@ -290,15 +322,13 @@ int main(int argc, char** argv) {
             else fflush(fp_out);
             return 0;
         }
-        const int st = dabgpu_ofdm_modulate_frames_host_sync(dabgpu_shared_context(), args.transmission_mode, frame_bytes_buf.data(),
-                                                             DABGPU_TX_PAYLOAD_REFERENCE, 1, reinterpret_cast<const float*>(prs_fft_ref.data()),
-                                                             frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
+        const int st = modulate(quantised.data(), DABGPU_IQ_RAW_U8);
         if (st != DABGPU_OK) {
             fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error());
             return 1;
         }
         for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
-            const size_t nb_write = fwrite(quantised.data(), 2, frame_size, fp_out);
+            const size_t nb_write = fwrite(quantised.data() + 2 * frame_size * ((size_t)k % n_tx), 2, frame_size, fp_out);
             if (nb_write != frame_size) {
                 fprintf(stderr, "Failed to write out frame %zu/%zu\n", nb_write, frame_size);
                 break;

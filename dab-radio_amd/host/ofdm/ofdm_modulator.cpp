@@ -40,6 +40,18 @@ bool OFDM_Modulator::ProcessBlock(
     // invalid buffer sizes (ofdm_modulator.cpp:54-63)
     if (data_in_buf.size() != m_data_in_size) return false;
     if (frame_out_buf.size() != m_frame_out_size) return false;
+    if (!m_tii.empty()) {
+        dabgpu_tii_tx list[DABGPU_TII_MAX_TX] = {};
+        std::copy(m_tii.begin(), m_tii.end(), list);
+        const uint8_t count = (uint8_t)m_tii.size();
+        const int st = dabgpu_ofdm_modulate_frames_tii_host_sync(
+            dabgpu_shared_context(), m_mode, data_in_buf.data(), DABGPU_TX_PAYLOAD_REFERENCE, 1,
+            reinterpret_cast<const float*>(m_prs_fft_ref.data()), 0.0f,
+            reinterpret_cast<float*>(frame_out_buf.data()), DABGPU_IQ_RAW_F32L, list, &count);
+        if (st != DABGPU_OK)
+            throw std::runtime_error(std::string("OFDM_Modulator: dabgpu_ofdm_modulate_frames_tii_host_sync: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
+        return true;
+    }
     const int st = dabgpu_ofdm_modulate_frames_host_sync(
         dabgpu_shared_context(), m_mode, data_in_buf.data(), DABGPU_TX_PAYLOAD_REFERENCE, 1,
         reinterpret_cast<const float*>(m_prs_fft_ref.data()), 0.0f,
@@ -47,4 +59,17 @@ bool OFDM_Modulator::ProcessBlock(
     if (st != DABGPU_OK)
         throw std::runtime_error(std::string("OFDM_Modulator: dabgpu_ofdm_modulate_frames_host_sync: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
     return true;
+}
+
+void OFDM_Modulator::SetTII(tcb::span<const dabgpu_tii_tx> transmitters)
+{
+    if (transmitters.empty()) { m_tii.clear(); return; }
+    if (m_mode != 1) throw std::runtime_error("OFDM_Modulator: TII is defined for transmission mode I only");
+    if (transmitters.size() > DABGPU_TII_MAX_TX) throw std::runtime_error("OFDM_Modulator: " + std::to_string(transmitters.size()) + " transmitters (at most 4)");
+    dabgpu_tii_tx list[DABGPU_TII_MAX_TX] = {};
+    std::copy(transmitters.begin(), transmitters.end(), list);
+    const uint8_t count = (uint8_t)transmitters.size();
+    const int st = dabgpu_tii_validate(list, &count, 1);
+    if (st != DABGPU_OK) throw std::runtime_error(std::string("OFDM_Modulator: dabgpu_tii_validate: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
+    m_tii.assign(transmitters.begin(), transmitters.end());
 }

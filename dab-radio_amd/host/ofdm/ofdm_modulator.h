@@ -7,6 +7,10 @@
 //                 (nb_frame_symbols - 1) * nb_data_carriers / 4 bytes, 2 bits per carrier in natural carrier order.  Wrong sizes return
 //                 false and write nothing (ofdm_modulator.cpp:54-63); a device failure throws std::runtime_error.
 // Every ProcessBlock starts the chain from the PRS again (ofdm_modulator.cpp:73-76): the object keeps no state between frames.
+//   SetTII        (not in the reference; mode I; include/dabgpu.h "TII") the transmitters whose comb fills the NULL period of every frame
+//                 modulated from now on, at most DABGPU_TII_MAX_TX; an empty list (the default) keeps the zeros.  TII is sent in alternate
+//                 frames: the caller sets and clears the list between ProcessBlock calls.  A list the library refuses (main id >= 70,
+//                 sub id >= 24, an amplitude that is not finite, another mode) throws std::runtime_error and leaves the list as it was.
 #pragma once
 
 #include <stddef.h>
@@ -15,6 +19,7 @@
 #include <vector>
 #include "utility/span.h"
 #include "./ofdm_params.h"
+#include "dabgpu.h"
 
 class OFDM_Modulator
 {
@@ -24,6 +29,7 @@ private:
     const size_t m_frame_out_size;
     const size_t m_data_in_size;
     std::vector<std::complex<float>> m_prs_fft_ref;
+    std::vector<dabgpu_tii_tx> m_tii;
 public:
     OFDM_Modulator(
         const OFDM_Params& params,
@@ -32,4 +38,5 @@ public:
     bool ProcessBlock(
         tcb::span<std::complex<float>> frame_out_buf,
         tcb::span<const uint8_t> data_in_buf);
+    void SetTII(tcb::span<const dabgpu_tii_tx> transmitters);
 };

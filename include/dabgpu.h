@@ -1048,6 +1048,102 @@ int dabgpu_channel_bank_apply_host_sync(dabgpu_channel_bank *bank, const float *
                                         size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * TII: transmitter identification information in the NULL symbol of mode I, both directions (every other mode returns
+ * DABGPU_ERR_INVALID_ARG).  The reference has no TII code; this section is the definition.  It is EN 300 401 clause 14.8.1 as recalled:
+ * THE NUMBERING OF p FOLLOWS THE TABLE BELOW AND HAS NOT BEEN CHECKED AGAINST TABLE 38 of the standard.
+ *
+ * Pattern table: T[0 .. 69] = the 70 bytes with exactly four bits set in ascending numeric order (T[0] = 0x0F, T[1] = 0x17, T[2] = 0x1B,
+ * ..., T[69] = 0xF0); a_b(p) = bit 7 - b of T[p], b = 0 .. 7.  dabgpu_tii_pattern(p) = T[p], -1 outside [0, 70).
+ * Carriers of the transmitter with main id p in [0, 70) and sub id c in [0, 24): for every b with a_b(p) = 1 and every block start
+ * B in {-768, -384, +1, +385} the pair k0 = B + 2 c + 48 b and k0 + 1: 32 carriers in [-768, 768], none of them 0; carrier k sits in
+ * bin k mod 2048.  dabgpu_tii_carriers writes them (b ascending, B ascending, k0 then k0 + 1).
+ *
+ * Transmit: the NULL spectrum is z[k0] += amp * PRS[k0], z[k0 + 1] += amp * PRS[k0] (both carriers of a pair carry the phase of k0; PRS =
+ * the modulator's PRS spectrum, amp a real float, amp = 1 the power of a data carrier) for up to DABGPU_TII_MAX_TX transmitters, whose
+ * spectra add in list order.  The NULL period is the inverse transform of z behind its last 608 samples, through the inverse transform,
+ * frequency shift and quantiser of a data symbol.  A frame with no transmitter keeps its zeros: TII is sent in alternate frames, the
+ * caller says per frame.
+ *   dabgpu_ofdm_modulate_frames_tii: dabgpu_ofdm_modulate_frames plus d_tii [n_frames][DABGPU_TII_MAX_TX] and d_tii_count [n_frames] on
+ *   the device (either NULL, or every count 0: the output of dabgpu_ofdm_modulate_frames bit for bit).  The lists are device memory, so
+ *   the call cannot refuse their content: the kernel reads min(count, 4) entries and passes over an entry that dabgpu_tii_validate
+ *   would refuse.  The _host_sync form validates its lists (main_id >= 70, sub_id >= 24, a count above 4, an amp that is not finite)
+ *   and, like a mode other than I, refuses before any device call.
+ *
+ * Detect, per receiver and frame (dabgpu_tii_bank_process; one 256-thread workgroup per receiver, kernel launches only: asynchronous,
+ * no host state changes, so a call may be captured in a HIP graph and replayed on the next frame's samples):
+ *   1 window      the 2048 samples that begin 608 samples after the NULL's first sample; the NULL begins at null_offset_samples +
+ *                 fine_time_offset of the receiver's dabgpu_sync_state (0 without records).  A record with sync_valid = 0 (or a
+ *                 fine_time_offset outside [-504, 1543]) skips the receiver: accumulator, frame count and results untouched.
+ *   2 offset      apply_pll with the record's freq_coarse + freq_fine (or d_freq_offset[k]; neither: 0), phase 0 at the window's first sample
+ *   3 transform   forward, 2048 points, the demodulator's butterflies
+ *   4 power       P[k] = fma(re, re, im * im)
+ *   5 fold        for c < 24, b < 8, q_B = P[B + 2 c + 48 b] + P[B + 2 c + 48 b + 1]:  E[c][b] = (q_-768 + q_-384) + (q_+1 + q_+385)
+ *   6 accumulate  acc[c][b] += E[c][b] (192 floats per receiver on the device), frames += 1
+ *   7 decision    (decide != 0) every comb's eight values sorted; N = the mean over the 24 combs, in order of c, of the mean of each
+ *                 comb's four smallest -- any transmitter leaves four of its comb's eight groups empty, so N is a noise floor whatever is
+ *                 on the air.  A comb is active when its fourth largest value is >= threshold * N; its mask (bit 7 - b for group b) holds
+ *                 the groups >= threshold * N.  A mask of four bits gives main_id by the table, any other main_id = -1 with the mask (two
+ *                 main ids on one comb).  strength = mean of the masked groups / N.  N = 0 (no energy at all): no record.
+ *                 d_results [n][24] records in ascending sub_id, d_counts [n].
+ * Default threshold 2.16: under noise alone an accumulated group is a sum of 8 * frames unit exponentials, a Gamma(8 * frames, 1)
+ * variable.  Splitting a comb's event by which four groups are its smallest gives P(comb active) = 70 E[S(max(t, max a))^4] with
+ * t = threshold * (23 N' + mean a) / 24, a = four independent Gamma draws, N' the floor of the other 23 combs, S the Gamma survival
+ * function; P(any of 24 combs) = 24 P to within 1e-12.  At frames = 2 this is 1.20e-6 at 2.15 and 0.93e-6 at 2.16 (root 2.157): 2.16 is
+ * the smallest threshold, in steps of 0.01, with fewer than 1e-6 false decisions (tests/tii_model.py, asserted by tests/test_tii_model.py).
+ * More frames only lower the probability.
+ * The decision needs a noise floor: on a signal without noise N is the float32 rounding of the transforms, which is not flat, and what
+ * is reported beside the transmitters is then undefined.
+ * Records of a synchroniser: the record of the first frame after an acquisition is up to half a carrier spacing off (the coarse estimate
+ * is a weighted mean of three bins and freq_fine takes its remainder through fmodf(., 0.505 spacings), the reference's arithmetic); half
+ * a spacing off, a third of every pair's power falls into the combs c - 1 and c + 1.  The fine-frequency update has the record within
+ * 0.05 spacings after that frame.  So do not feed the detector a receiver's first DABGPU_TII_SETTLE_FRAMES frames after sync_valid
+ * turned 1 (or reset the bank after them); tests/test_tii_closed_loop.py pins both the exact settled loop and the unsettled frame.
+ * Beyond the issue's list, kept deliberately: dabgpu_tii_main_id (the table look-up of step 7, shared with the kernel),
+ * dabgpu_tii_validate (the refusal of the _host_sync modulator, callable before a device list is uploaded) and dabgpu_tii_bank_read
+ * (a synchronous read-back of accumulators and frame counts for tests and diagnosis; no call on the hot path). */
+#define DABGPU_TII_MAX_TX 4
+#define DABGPU_TII_SETTLE_FRAMES 1
+#define DABGPU_TII_NB_MAIN 70
+#define DABGPU_TII_COMBS 24
+#define DABGPU_TII_GROUPS 8
+#define DABGPU_TII_DEFAULT_THRESHOLD 2.16f
+typedef struct { uint8_t main_id, sub_id; float amp; } dabgpu_tii_tx;
+typedef struct { float threshold; int32_t reserved; } dabgpu_tii_cfg;
+typedef struct { int32_t sub_id, main_id; uint32_t mask; float strength; } dabgpu_tii_record;
+void dabgpu_tii_cfg_default(dabgpu_tii_cfg *cfg);
+int dabgpu_tii_pattern(int main_id);
+int dabgpu_tii_main_id(uint32_t mask);                        /* inverse of dabgpu_tii_pattern, -1 for a mask that is no pattern */
+int dabgpu_tii_carriers(int main_id, int sub_id, int out[32]);
+/* n_frames lists of DABGPU_TII_MAX_TX entries and their counts, in host memory (counts NULL: no list is read) */
+int dabgpu_tii_validate(const dabgpu_tii_tx *tii, const uint8_t *tii_count, size_t n_frames);
+int dabgpu_ofdm_modulate_frames_tii(dabgpu_ctx *ctx, int transmission_mode, const uint8_t *d_payload, int payload_layout, size_t n_frames,
+                                    const float *d_prs_fft_ref, float freq_norm, void *d_out, int out_format, void *stream,
+                                    const dabgpu_tii_tx *d_tii, const uint8_t *d_tii_count);
+int dabgpu_ofdm_modulate_frames_tii_host_sync(dabgpu_ctx *ctx, int transmission_mode, const uint8_t *h_payload, int payload_layout,
+                                              size_t n_frames, const float *h_prs_fft_ref, float freq_norm, void *h_out, int out_format,
+                                              const dabgpu_tii_tx *h_tii, const uint8_t *h_tii_count);
+/* Detector bank: accumulators and frame counts of n_receivers receivers on the device (cfg NULL = the default).
+ *   d_iq      receiver k's samples: complex float at d_iq + 2 * k * stream_stride_samples, 8-byte aligned (16-byte aligned windows are
+ *             read with 16-byte loads); stream_stride_samples >= null_offset_samples + 2656, + 1543 more when d_states is given
+ *   d_states  [n] the records dabgpu_ofdm_sync / dabgpu_ofdm_sync_demod_frames left (read only), or NULL
+ *   d_freq_offset  [n] cycles per sample, or NULL: receiver k is rotated by d_freq_offset[k] instead of its record's sum unless that
+ *             value is NaN (position and validity stay the record's); without records it is the only offset
+ *   d_results, d_counts  required when decide != 0
+ * _reset clears accumulators and frame counts on `stream`; _read copies them to host memory behind everything queued on `stream` and
+ * waits (h_acc [n][192], h_frames [n], either may be NULL).  The _host_sync form serves a bank of one receiver from host memory:
+ * h_iq holds n_samples samples, the NULL begins at null_offset_samples + fine_time_offset, which must leave the window inside them. */
+typedef struct dabgpu_tii_bank dabgpu_tii_bank;
+int dabgpu_tii_bank_create(dabgpu_ctx *ctx, size_t n_receivers, const dabgpu_tii_cfg *cfg, dabgpu_tii_bank **out);
+void dabgpu_tii_bank_destroy(dabgpu_tii_bank *bank);
+int dabgpu_tii_bank_reset(dabgpu_tii_bank *bank, void *stream);
+int dabgpu_tii_bank_process(dabgpu_tii_bank *bank, const float *d_iq, size_t stream_stride_samples, size_t null_offset_samples,
+                            const dabgpu_sync_state *d_states, const float *d_freq_offset, int decide, dabgpu_tii_record *d_results,
+                            uint32_t *d_counts, void *stream);
+int dabgpu_tii_bank_process_host_sync(dabgpu_tii_bank *bank, const float *h_iq, size_t n_samples, size_t null_offset_samples,
+                                      float freq_offset, int fine_time_offset, int decide, dabgpu_tii_record *h_results, uint32_t *h_count);
+int dabgpu_tii_bank_read(dabgpu_tii_bank *bank, float *h_acc, uint32_t *h_frames, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Ingest pipe: the host -> device hand-over of capture bytes.  Replaces the reader thread -> OFDM_Demod::Process hand-over
  * of examples/app_helpers/app_ofdm_blocks.h:45-58 and the memcpy of OFDM_Demod::ReadSymbols (src/ofdm/ofdm_demodulator.cpp:550-577).
  * A ring of `depth` PINNED host buffers with device twins and a copy stream of its own:
