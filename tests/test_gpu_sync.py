@@ -83,14 +83,18 @@ def test_sync_batch_and_coarse_disabled(ctx, oracle):
     d_st = torch.from_numpy(st0.view(np.uint8)).cuda()
     cfg = dabgpu.sync_cfg_default()
     cfg.is_coarse_freq_correction = 0
-    ctx.ofdm_sync(d_syms, n, 2048, d_st, cfg=cfg)
+    d_imp = torch.zeros((n, 2048), dtype=torch.float32, device="cuda")
+    ctx.ofdm_sync(d_syms, n, 2048, d_st, cfg=cfg, impulse=d_imp)
     torch.cuda.synchronize()
     got = d_st.cpu().numpy().view(np.dtype(dabgpu.SYNC_STATE_DTYPE))
+    imp = d_imp.cpu().numpy()
     conj_ref, _ = oracle.sync_refs()
     cfg_o = oracle.sync_cfg_default()
     cfg_o.is_coarse_freq_correction = 0
     for k in range(n):
-        ok_o, off_o, _ = oracle.fine_time_sync(syms[k], st0["freq_fine"][k], cfg_o, conj_ref)      # coarse forced to 0 (:363-367)
+        ok_o, off_o, ir_o = oracle.fine_time_sync(syms[k], st0["freq_fine"][k], cfg_o, conj_ref)   # coarse forced to 0 (:363-367)
         assert got[k]["freq_coarse"] == 0.0 and bool(got[k]["sync_valid"]) == ok_o
+        assert u32(got[k]["freq_fine"]) == u32(st0["freq_fine"][k])                                # the fine offset passes through untouched
+        assert np.array_equal(u32(imp[k]), u32(ir_o)), k
         if ok_o:
             assert got[k]["fine_time_offset"] == off_o

@@ -260,54 +260,7 @@ def test_u16_candidate_sums_cannot_reach_65535():
 # ---------------------------------------------------------------------------------------------------------------------
 # PRS synchroniser: float64 model of ofdm_demodulator.cpp:360-548
 # ---------------------------------------------------------------------------------------------------------------------
-def f64_coarse(prs_sym, prs_fft, coarse, found, cfg):
-    n = 2048
-    X = np.fft.fft(prs_sym[:n].astype(np.complex128))
-    rel = np.conj(X) * np.roll(X, -1)                                   # CalculateRelativePhase :901-909: arg(conj(z0) z1)
-    rel[-1] = 0
-    ref_rel = np.conj(prs_fft.astype(np.complex128)) * np.roll(prs_fft.astype(np.complex128), -1)
-    ref_rel[-1] = 0
-    tref = np.conj(np.fft.ifft(ref_rel))                                # constructor :127-135
-    corr = np.fft.fft(np.fft.ifft(rel) * tref)
-    mag = 20.0 * np.log10(np.abs(np.fft.fftshift(corr)) + 1e-300)       # CalculateMagnitude :911-920 (fft-shifted)
-    M = n // 2
-    mco = min(max(int(cfg.max_coarse_freq_correction_norm * n), 0), M)
-    idx = [i for i in range(-mco, mco + 1) if i + M != n]
-    vals = np.array([mag[i + M] for i in idx])
-    k = int(np.argmax(vals))
-    srt = np.sort(vals)
-    margin = srt[-1] - srt[-2]
-    max_index = idx[k]
-
-    def peak(index):
-        index = min(max(index, -mco), mco)
-        fi = min(index + M, n - 1)
-        return fi - M, 10.0 ** (mag[fi] / 20.0)
-    pk = [peak(max_index - 1), peak(max_index), peak(max_index + 1)]
-    s = sum(p[1] for p in pk)
-    lerp = sum(p[0] * p[1] / s for p in pk)
-    pred = -lerp / n
-    err = pred - coarse
-    large = abs(err) > 1.5 / n
-    fast = large or not found
-    return max_index, fast, pred, margin, abs(abs(err) - 1.5 / n)
-
-
-def f64_fine(prs_sym, prs_fft, freq, cfg):
-    n, cp, period = 2048, 504, 2552
-    x = prs_sym[:n].astype(np.complex128) * np.exp(2j * np.pi * freq * np.arange(n))
-    imp = n * np.fft.ifft(np.fft.fft(x) * np.conj(prs_fft.astype(np.complex128)))   # FFTW's backward transform is unnormalised, and the
-    db = 20.0 * np.log10(np.abs(imp) + 1e-300)                                      # distance weighting below multiplies dB VALUES: scale matters
-    w = 1.0 - (1.0 - cfg.impulse_peak_distance_probability) * np.abs(cp - np.arange(n)) / period
-    weighted = w * db
-    best, bi = db[0], 0                                                  # :503 initialised with the UNWEIGHTED [0]
-    for i in range(n):
-        if weighted[i] > best:
-            best, bi = weighted[i], i
-    srt = np.sort(weighted)
-    avg = db.mean()
-    ok = (best - avg) >= cfg.impulse_peak_threshold_db
-    return ok, bi - cp, srt[-1] - srt[-2], abs((best - avg) - cfg.impulse_peak_threshold_db)
+from sync_cases import f64_coarse, f64_fine      # the model for any geometry (tests/sync_cases.py); the defaults are mode I's
 
 
 def test_sync_decisions_equal_a_float64_model(oracle):
