@@ -17,50 +17,9 @@
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
 #include "channel_core.h"
+#include "channel_device.h"
 
 namespace dabgpu {
-
-constexpr int CH_BLK = DABGPU_CHANNEL_BLOCK;
-typedef float ch_f4 __attribute__((ext_vector_type(4)));
-typedef float ch_f2v __attribute__((ext_vector_type(2)));
-
-// where a tile's input comes from: x[origin + off], off < span.  wrap: origin is already reduced into [0, n_in); otherwise it is the
-// plain index, clamped far enough outside the input that origin + off cannot overflow
-struct ChWindow { const chf2* x; int64_t n_in, origin; int span; bool wrap; };
-
-__device__ __forceinline__ chf2 ch_ld(const chf2* p) { const ch_f2v v = *reinterpret_cast<const ch_f2v*>(p); return chf2{v.x, v.y}; }
-
-// samples off and off + 1 of the window
-__device__ __forceinline__ void ch_load2(const ChWindow& W, int off, chf2& a, chf2& b) {
-    int64_t j = W.origin + off;
-    const chf2 zero = chf2{0.0f, 0.0f};
-    if (W.wrap) {
-        if (j >= W.n_in) j = (W.span <= W.n_in) ? j - W.n_in : j % W.n_in;
-        const int64_t j1 = (j + 1 == W.n_in) ? 0 : j + 1;
-        if (!(j & 1) && j1 == j + 1) {
-            const ch_f4 v = *reinterpret_cast<const ch_f4*>(W.x + j);
-            a = chf2{v.x, v.y}; b = chf2{v.z, v.w};
-        } else { a = ch_ld(W.x + j); b = ch_ld(W.x + j1); }
-    } else {
-        if (j >= 0 && j + 1 < W.n_in && !(j & 1)) {
-            const ch_f4 v = *reinterpret_cast<const ch_f4*>(W.x + j);
-            a = chf2{v.x, v.y}; b = chf2{v.z, v.w};
-        } else {
-            a = (j >= 0 && j < W.n_in) ? ch_ld(W.x + j) : zero;
-            b = (j + 1 >= 0 && j + 1 < W.n_in) ? ch_ld(W.x + j + 1) : zero;
-        }
-    }
-}
-
-__device__ __forceinline__ ChWindow ch_window(const chf2* x, int64_t n_in, bool wrap, uint64_t first, int span) {
-    ChWindow W;
-    W.x = x; W.n_in = n_in; W.wrap = wrap; W.span = span;
-    int64_t o = (int64_t)first;
-    if (wrap) { o %= n_in; if (o < 0) o += n_in; }
-    else o = o < -((int64_t)1 << 41) ? -((int64_t)1 << 41) : (o > ((int64_t)1 << 41) ? ((int64_t)1 << 41) : o);
-    W.origin = o;
-    return W;
-}
 
 template <int OUT, bool STAGE>
 __global__ __launch_bounds__(256)
@@ -156,6 +115,11 @@ void channel_kernel(const dabgpu_channel_stream* __restrict__ params, const uint
 // behind the channel kernel on the same stream: the next call (or graph replay) continues where this one ended
 __global__ void channel_advance_kernel(uint64_t* pos, uint64_t n) { *pos += n; }
 
+// channel_fading.hip
+void ch_launch_fading(const dabgpu_channel_stream* d_params, const dabgpu_channel_fading_stream* d_tables, const uint64_t* d_pos,
+                      const dabgpu_channel_geometry& geom, int tiles, unsigned grid, const float* d_in, size_t in_stride, size_t n_in, int wrap, size_t n_out,
+                      void* d_out, int out_format, size_t out_stride_bytes, float u8_scale, hipStream_t s);
+
 }  // namespace dabgpu
 
 using namespace dabgpu;
@@ -167,6 +131,9 @@ struct dabgpu_channel_bank {
     void* d_mem = nullptr;                      // one allocation: position (16 bytes) | parameters
     uint64_t* d_pos = nullptr;
     dabgpu_channel_stream* d_params = nullptr;
+    dabgpu_channel_fading_stream* d_fading = nullptr;   // a fading bank's tables (its own allocation); null: a plain bank
+    std::vector<dabgpu_channel_stream> h_params;        // a fading bank keeps its parameters and tables on the host: _set_fading and
+    std::vector<dabgpu_channel_fading_stream> h_tables; // _set_params check the one against the other (n_taps may grow past checked kinds)
     void* buf[2] = {};                          // host form: [0] input, [1] output (grow only)
     size_t buf_bytes[2] = {};
 };
@@ -189,6 +156,11 @@ static int ch_launch(dabgpu_channel_bank* b, const float* d_in, size_t in_stride
     const bool stage = b->geom.staged != 0;
     const size_t lds = stage ? (size_t)(CH_BLK + b->geom.halo + 2) * 8 : 0;
     const chf2* in = reinterpret_cast<const chf2*>(d_in);
+    if (b->d_fading) {
+        ch_launch_fading(b->d_params, b->d_fading, b->d_pos, b->geom, tiles, grid, d_in, in_stride, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, s);
+        hipLaunchKernelGGL(channel_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
+        return dabgpu_check_hip(hipGetLastError(), "channel_fading_kernel launch");
+    }
 #define CH_GO(OUT, STAGE)                                                                                                                     \
     hipLaunchKernelGGL((channel_kernel<OUT, STAGE>), dim3(grid), dim3(256), lds, s, b->d_params, b->d_pos, in, in_stride, (int64_t)n_in, wrap, \
                        (uint32_t)n_out, tiles, static_cast<uint8_t*>(d_out), out_stride_bytes, u8_scale)
@@ -199,18 +171,25 @@ static int ch_launch(dabgpu_channel_bank* b, const float* d_in, size_t in_stride
     return dabgpu_check_hip(hipGetLastError(), "channel_kernel launch");
 }
 
-extern "C" {
-
-int dabgpu_channel_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_channel_stream* h_params, dabgpu_channel_bank** out) {
-    if (!c || !out) { dabgpu_set_error("channel_bank_create: null context / result"); return DABGPU_ERR_INVALID_ARG; }
+static int ch_create(const char* who, dabgpu_ctx* c, size_t n_streams, const dabgpu_channel_stream* h_params, const dabgpu_channel_fading_stream* h_tables,
+                     bool fading, dabgpu_channel_bank** out) {
+    if (!c || !out) { dabgpu_set_error("%s: null context / result", who); return DABGPU_ERR_INVALID_ARG; }
     *out = nullptr;
     dabgpu_channel_geometry g;
     int st = dabgpu_host_channel_plan(h_params, n_streams, &g);
     if (st) return st;
+    if (fading && (st = dabgpu_host_channel_fading_check(who, h_params, h_tables, n_streams))) return st;
     dabgpu_channel_bank* b = new dabgpu_channel_bank;
-    b->ctx = c; b->n = n_streams; b->geom = g;
+    b->ctx = c; b->n = n_streams; b->geom = fading ? dabgpu_host_channel_fading_geometry(g) : g;
     auto fail = [&](int status) { dabgpu_channel_bank_destroy(b); return status; };
     if ((st = dabgpu_bind_device(c))) return fail(st);
+    if (fading) {
+        b->h_params.assign(h_params, h_params + n_streams);
+        b->h_tables.assign(h_tables, h_tables + n_streams);
+        const size_t table_bytes = n_streams * sizeof(dabgpu_channel_fading_stream);
+        if ((st = dabgpu_check_hip(hipMalloc((void**)&b->d_fading, table_bytes), "hipMalloc(channel fading tables)"))) return fail(st);
+        if ((st = dabgpu_stage_h2d(c, b->d_fading, h_tables, table_bytes, c->stream))) return fail(st);
+    }
     const size_t bytes = 16 + n_streams * sizeof(dabgpu_channel_stream);
     if ((st = dabgpu_check_hip(hipMalloc(&b->d_mem, bytes), "hipMalloc(channel bank)"))) return fail(st);
     b->d_pos = static_cast<uint64_t*>(b->d_mem);
@@ -222,12 +201,34 @@ int dabgpu_channel_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_cha
     return DABGPU_OK;
 }
 
+extern "C" {
+
+int dabgpu_channel_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_channel_stream* h_params, dabgpu_channel_bank** out) {
+    return ch_create("channel_bank_create", c, n_streams, h_params, nullptr, false, out);
+}
+
+int dabgpu_channel_bank_create_fading(dabgpu_ctx* c, size_t n_streams, const dabgpu_channel_stream* h_params, const dabgpu_channel_fading_stream* h_tables,
+                                      dabgpu_channel_bank** out) {
+    return ch_create("channel_bank_create_fading", c, n_streams, h_params, h_tables, true, out);
+}
+
+int dabgpu_channel_bank_set_fading(dabgpu_channel_bank* b, const dabgpu_channel_fading_stream* h_tables, void* stream) {
+    if (!b) { dabgpu_set_error("channel_bank_set_fading: null bank"); return DABGPU_ERR_INVALID_ARG; }
+    if (!b->d_fading) { dabgpu_set_error("channel_bank_set_fading: the bank was not created with dabgpu_channel_bank_create_fading"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_channel_fading_check("channel_bank_set_fading", b->h_params.data(), h_tables, b->n);
+    if (st) return st;
+    b->h_tables.assign(h_tables, h_tables + b->n);
+    DABGPU_BIND(b->ctx);
+    return dabgpu_stage_h2d(b->ctx, b->d_fading, h_tables, b->n * sizeof(dabgpu_channel_fading_stream), (hipStream_t)stream);
+}
+
 void dabgpu_channel_bank_destroy(dabgpu_channel_bank* b) {
     if (!b) return;
     if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
         (void)hipDeviceSynchronize();
         for (void* p : b->buf) if (p) (void)hipFree(p);
         if (b->d_mem) (void)hipFree(b->d_mem);
+        if (b->d_fading) (void)hipFree(b->d_fading);
     }
     delete b;
 }
@@ -237,6 +238,10 @@ int dabgpu_channel_bank_set_params(dabgpu_channel_bank* b, const dabgpu_channel_
     dabgpu_channel_geometry g;
     int st = dabgpu_host_channel_plan(h_params, b->n, &g);
     if (st || (st = dabgpu_host_channel_fits(b->geom, g))) return st;       // (b->geom stays: captured calls launch with it)
+    if (b->d_fading) {
+        if ((st = dabgpu_host_channel_fading_check("channel_bank_set_params", h_params, b->h_tables.data(), b->n))) return st;
+        b->h_params.assign(h_params, h_params + b->n);
+    }
     DABGPU_BIND(b->ctx);
     return dabgpu_stage_h2d(b->ctx, b->d_params, h_params, b->n * sizeof(dabgpu_channel_stream), (hipStream_t)stream);
 }

@@ -17,7 +17,9 @@ struct chf2 { float re, im; };
 
 // ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) ----
 DABGPU_HD inline void ch_philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out[4]) {
+#if defined(__HIPCC__)                 // (the planner's plain C++ build of this header does not know the pragma)
 #pragma unroll
+#endif
     for (int r = 0; r < 10; r++) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
         const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
@@ -155,6 +157,62 @@ DABGPU_HD inline chf2 ch_finish(const dabgpu_channel_stream& P, uint64_t m, chf2
         y = chf2{__builtin_fmaf(P.noise_sigma, g.re, y.re), __builtin_fmaf(P.noise_sigma, g.im, y.im)};
     }
     return y;
+}
+
+// ---- fading taps (include/dabgpu.h, "Channel model, fading taps"; bounds: DESIGN.md 4.18) ----
+constexpr int CH_FADE_GRID_SHIFT = 6;                                        // DABGPU_FADING_GRID = 64
+constexpr int CH_FADE_MAX_POINTS = 18;                                       // grid points a tile of 1024 samples aligned to 4 can touch
+static_assert((1 << CH_FADE_GRID_SHIFT) == DABGPU_FADING_GRID, "grid");
+
+// bit k set: tap k of the stream fades
+DABGPU_HD inline uint32_t ch_fading_mask(const dabgpu_channel_fading_stream& F, int n_taps) {
+    uint32_t mask = 0;
+    for (int k = 0; k < n_taps; k++) mask |= (F.kind[k] == DABGPU_TAP_FADING ? 1u : 0u) << k;
+    return mask;
+}
+// (cos, sin) of oscillator n of a tap at grid point j (absolute sample 64 j)
+DABGPU_HD inline chf2 ch_fading_osc(const dabgpu_channel_fading_tap& T, int n, uint64_t j) {
+    return ch_cos_sin(ch_osc_cycles(T.phase_q64[n], T.freq_q64[n], j << CH_FADE_GRID_SHIFT));
+}
+// the 16 diffuse terms as the fixed pairwise tree v[i] += v[i ^ 1], v[i ^ 2], v[i ^ 4], v[i ^ 8]: every level adds partners both ways
+// round (the sum of two floats does not depend on their order), which is what 16 lanes exchanging registers do; v[0] is the sum
+DABGPU_HD inline float ch_fading_tree16(float v[16]) {
+    for (int stride = 1; stride < 16; stride <<= 1) {
+        float t[16];
+        for (int i = 0; i < 16; i++) t[i] = v[i] + v[i ^ stride];
+        for (int i = 0; i < 16; i++) v[i] = t[i];
+    }
+    return v[0];
+}
+// G_j from the tree's sums and the line of sight (los is not read when amp_los == 0)
+DABGPU_HD inline chf2 ch_fading_combine(float amp_diffuse, float amp_los, chf2 sum, chf2 los) {
+    const chf2 d = chf2{amp_diffuse * sum.re, amp_diffuse * sum.im};
+    if (amp_los == 0.0f) return d;
+    return chf2{__builtin_fmaf(amp_los, los.re, d.re), __builtin_fmaf(amp_los, los.im, d.im)};
+}
+// G_j of one tap, one thread (the kernel spreads the same operations over 16 lanes)
+DABGPU_HD inline chf2 ch_fading_grid_gain(const dabgpu_channel_fading_tap& T, uint64_t j) {
+    float c[16], s[16];
+    for (int n = 0; n < 16; n++) { const chf2 cs = ch_fading_osc(T, n, j); c[n] = cs.re; s[n] = cs.im; }
+    const chf2 sum = chf2{ch_fading_tree16(c), ch_fading_tree16(s)};
+    const chf2 los = (T.amp_los != 0.0f) ? ch_fading_osc(T, 16, j) : chf2{0.0f, 0.0f};
+    return ch_fading_combine(T.amp_diffuse, T.amp_los, sum, los);
+}
+// g(m) between the grid points j = m >> 6 and j + 1
+DABGPU_HD inline chf2 ch_fading_interp(chf2 g0, chf2 g1, uint64_t m) {
+    const float w = (float)(uint32_t)(m & (uint64_t)(DABGPU_FADING_GRID - 1)) * 0x1p-6f;
+    return chf2{__builtin_fmaf(w, g1.re - g0.re, g0.re), __builtin_fmaf(w, g1.im - g0.im, g0.im)};
+}
+// the paths of one sample of a fading stream; gain(k) = g_k(m) (called for the taps of `mask` only), fetch(k) as in ch_paths
+template <class Gain, class Fetch>
+DABGPU_HD inline chf2 ch_paths_fading(const dabgpu_channel_stream& P, uint32_t mask, Gain gain, Fetch fetch) {
+    chf2 z = chf2{0.0f, 0.0f};
+    for (int k = 0; k < P.n_taps; k++) {
+        float hr = P.tap_re[k], hi = P.tap_im[k];
+        if ((mask >> k) & 1u) { const chf2 e = ch_tap_first(hr, hi, gain(k)); hr = e.re; hi = e.im; }
+        z = (k == 0) ? ch_tap_first(hr, hi, fetch(0)) : ch_tap_add(z, hr, hi, fetch(k));
+    }
+    return z;
 }
 
 // the modulator's quantiser (ofdm_mod.hip, tx_u8): x * scale + 127.5, clamped to [0, 255] (NaN -> 0), truncated

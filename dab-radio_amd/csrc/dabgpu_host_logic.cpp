@@ -827,6 +827,140 @@ extern "C" uint64_t dabgpu_channel_freq_q64(double cycles) {
 
 extern "C" double dabgpu_channel_freq_cycles(uint64_t freq_q64) { return std::ldexp((double)(int64_t)freq_q64, -64); }
 
+// ---- channel model, fading taps (include/dabgpu.h, "Channel model, fading taps"; the arithmetic is channel_core.h's, shared with the kernel) ----
+#include "channel_core.h"
+
+extern "C" int dabgpu_channel_fading_plan(const dabgpu_channel_stream* params, const dabgpu_channel_fading_spec* specs, size_t n_streams,
+                                          dabgpu_channel_fading_stream* out) {
+    if (!params || !specs || !out) { dabgpu_set_error("channel_fading_plan: null parameters / specs / result"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_channel_plan(params, n_streams, nullptr);
+    if (st) return st;
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_channel_fading_spec& S = specs[s];
+        if (!(S.doppler_cycles >= 0.0 && S.doppler_cycles <= DABGPU_FADING_MAX_DOPPLER_CYCLES)) {
+            dabgpu_set_error("channel_fading_plan: stream %zu: doppler_cycles %g (0..2^-11 are accepted)", s, S.doppler_cycles); return DABGPU_ERR_INVALID_ARG;
+        }
+        for (int k = 0; k < params[s].n_taps; k++) {
+            if (S.kind[k] != DABGPU_TAP_STATIC && S.kind[k] != DABGPU_TAP_FADING) {
+                dabgpu_set_error("channel_fading_plan: stream %zu: tap %d: kind %d (STATIC or FADING)", s, k, S.kind[k]); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (S.kind[k] == DABGPU_TAP_STATIC) continue;
+            if (!std::isfinite(S.rice_k[k]) || S.rice_k[k] < 0.0f) {
+                dabgpu_set_error("channel_fading_plan: stream %zu: tap %d: rice_k is negative or not finite", s, k); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (!(S.los_cos[k] >= -1.0f && S.los_cos[k] <= 1.0f)) {
+                dabgpu_set_error("channel_fading_plan: stream %zu: tap %d: los_cos outside [-1, 1] or not finite", s, k); return DABGPU_ERR_INVALID_ARG;
+            }
+        }
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_channel_fading_spec& S = specs[s];
+        dabgpu_channel_fading_stream& F = out[s];
+        memset(&F, 0, sizeof(F));
+        for (int k = 0; k < params[s].n_taps; k++) {
+            if (S.kind[k] != DABGPU_TAP_FADING) continue;
+            dabgpu_channel_fading_tap& T = F.tap[k];
+            F.kind[k] = DABGPU_TAP_FADING;
+            for (int n = 0; n < DABGPU_FADING_OSC; n++) {
+                uint32_t w[4];
+                dabgpu::ch_philox4x32_10((uint32_t)S.seed, (uint32_t)(S.seed >> 32), (uint32_t)n, (uint32_t)k, (uint32_t)s, 1u, w);
+                const double c = (n < 16) ? std::cos(two_pi * ((double)n + ((double)w[0] + 0.5) * 0x1p-32) / 16.0) : (double)S.los_cos[k];
+                T.freq_q64[n] = dabgpu_channel_freq_q64(S.doppler_cycles * c);
+                T.phase_q64[n] = ((uint64_t)w[2] << 32) | w[3];
+            }
+            const double K = (double)S.rice_k[k];
+            T.amp_diffuse = (float)std::sqrt(1.0 / (K + 1.0)) * 0.25f;
+            T.amp_los = (float)std::sqrt(K / (K + 1.0));
+        }
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channel_fading_gain_host(const dabgpu_channel_fading_stream* row, int tap, uint64_t m0, size_t count, float* out) {
+    if (!row || (count > 0 && !out)) { dabgpu_set_error("channel_fading_gain_host: null table / result"); return DABGPU_ERR_INVALID_ARG; }
+    if (tap < 0 || tap >= DABGPU_CHANNEL_MAX_TAPS) {
+        dabgpu_set_error("channel_fading_gain_host: tap %d (0..%d are accepted)", tap, DABGPU_CHANNEL_MAX_TAPS - 1); return DABGPU_ERR_INVALID_ARG;
+    }
+    const bool fades = row->kind[tap] == DABGPU_TAP_FADING;
+    const dabgpu_channel_fading_tap& T = row->tap[tap];
+    uint64_t j = 0;
+    dabgpu::chf2 g0 = {1.0f, 0.0f}, g1 = g0;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t m = m0 + i;
+        dabgpu::chf2 g = {1.0f, 0.0f};
+        if (fades) {
+            if (i == 0 || (m >> dabgpu::CH_FADE_GRID_SHIFT) != j) {
+                j = m >> dabgpu::CH_FADE_GRID_SHIFT;
+                g0 = dabgpu::ch_fading_grid_gain(T, j); g1 = dabgpu::ch_fading_grid_gain(T, j + 1);
+            }
+            g = dabgpu::ch_fading_interp(g0, g1, m);
+        }
+        out[2 * i] = g.re; out[2 * i + 1] = g.im;
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channel_profile(const char* name, dabgpu_channel_stream* params, dabgpu_channel_fading_spec* spec) {
+    if (!name || !params || !spec) { dabgpu_set_error("channel_profile: null name / parameters / spec"); return DABGPU_ERR_INVALID_ARG; }
+    struct Preset { const char* name; int n; double delay_us[6]; int delay_samples[6]; double db[6]; };
+    static const Preset presets[3] = {
+        {"tu6", 6, {0.0, 0.2, 0.5, 1.6, 2.3, 5.0}, {}, {-3.0, 0.0, -2.0, -6.0, -8.0, -10.0}},
+        {"ra6", 6, {0.0, 0.1, 0.2, 0.3, 0.4, 0.5}, {}, {0.0, -4.0, -8.0, -12.0, -16.0, -20.0}},
+        {"sfn2", 2, {}, {0, 200}, {0.0, -6.0}},
+    };
+    for (const Preset& p : presets) {
+        if (strcmp(name, p.name) != 0) continue;
+        const bool samples = p.delay_samples[p.n - 1] != 0;
+        double total = 0.0;
+        for (int k = 0; k < p.n; k++) total += std::pow(10.0, p.db[k] / 10.0);
+        params->n_taps = p.n;
+        for (int k = 0; k < DABGPU_CHANNEL_MAX_TAPS; k++) {
+            const bool on = k < p.n;
+            params->tap_delay[k] = !on ? 0 : samples ? p.delay_samples[k] : (int32_t)std::lround(p.delay_us[k] * 2.048);
+            params->tap_re[k] = on ? (float)std::sqrt(std::pow(10.0, p.db[k] / 10.0) / total) : 0.0f;
+            params->tap_im[k] = 0.0f;
+            spec->kind[k] = on ? DABGPU_TAP_FADING : DABGPU_TAP_STATIC;
+            spec->rice_k[k] = 0.0f;
+            spec->los_cos[k] = 0.0f;
+        }
+        if (&p == &presets[1]) { spec->rice_k[0] = (float)(0.91 / 0.41); spec->los_cos[0] = 0.7f; }
+        return DABGPU_OK;
+    }
+    dabgpu_set_error("channel_profile: unknown profile \"%.32s\" (tu6, ra6, sfn2)", name);
+    return DABGPU_ERR_INVALID_ARG;
+}
+
+int dabgpu_host_channel_fading_check(const char* who, const dabgpu_channel_stream* params, const dabgpu_channel_fading_stream* tables, size_t n_streams) {
+    if (!params || !tables) { dabgpu_set_error("%s: null parameters / fading tables", who); return DABGPU_ERR_INVALID_ARG; }
+    for (size_t s = 0; s < n_streams; s++) {
+        const int n_taps = std::min(std::max(params[s].n_taps, 0), DABGPU_CHANNEL_MAX_TAPS);
+        for (int k = 0; k < n_taps; k++) {
+            const int kind = tables[s].kind[k];
+            if (kind != DABGPU_TAP_STATIC && kind != DABGPU_TAP_FADING) {
+                dabgpu_set_error("%s: stream %zu: tap %d: kind %d (STATIC or FADING)", who, s, k, kind); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (kind == DABGPU_TAP_FADING && (!std::isfinite(tables[s].tap[k].amp_diffuse) || !std::isfinite(tables[s].tap[k].amp_los))) {
+                dabgpu_set_error("%s: stream %zu: tap %d: fading amplitudes are not finite", who, s, k); return DABGPU_ERR_INVALID_ARG;
+            }
+        }
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channel_plan_fading(const dabgpu_channel_stream* params, size_t n_streams, dabgpu_channel_geometry* out) {
+    dabgpu_channel_geometry g;
+    const int st = dabgpu_host_channel_plan(params, n_streams, &g);
+    if (out) *out = st ? g : dabgpu_host_channel_fading_geometry(g);
+    return st;
+}
+
+dabgpu_channel_geometry dabgpu_host_channel_fading_geometry(dabgpu_channel_geometry g) {
+    g.staged = 1;
+    g.lds_bytes = (DABGPU_CHANNEL_BLOCK + g.halo + 2u) * 8u + (uint32_t)(dabgpu::CH_FADE_MAX_POINTS * DABGPU_CHANNEL_MAX_TAPS * 8);
+    return g;
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

@@ -242,6 +242,11 @@ int dabgpu_host_channel_fits(const dabgpu_channel_geometry& created, const dabgp
 // samples, the default stride is the row itself
 int dabgpu_host_channel_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_in, size_t n_out,
                                     const void* out, int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers = true);
+// the fading tables of a bank (dabgpu_channel_bank_create_fading / _set_fading) against its parameters: kinds below n_taps STATIC or FADING,
+// the amplitudes of fading taps finite; `who` names the entry point
+int dabgpu_host_channel_fading_check(const char* who, const dabgpu_channel_stream* params, const dabgpu_channel_fading_stream* tables, size_t n_streams);
+// the geometry of a fading bank from the plain one: always staged, the tile's grid gains behind the staged input
+dabgpu_channel_geometry dabgpu_host_channel_fading_geometry(dabgpu_channel_geometry plain);
 
 // ---- DAB+ super-frame encoder (dabplus_tx.hip; include/dabgpu.h, dabgpu_dabplus_superframe_layout) ----
 // Where the access units of a super frame start (ETSI TS 102 563 5.2, as AAC_Frame_Processor reads it back, aac_frame_processor.cpp:266-283),

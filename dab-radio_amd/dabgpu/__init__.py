@@ -75,6 +75,8 @@ ABI_SYMBOLS = [
     "dabgpu_dabplus_superframe_layout", "dabgpu_dabplus_tx_encode", "dabgpu_dabplus_tx_encode_host_sync",
     "dabgpu_channel_plan", "dabgpu_channel_freq_q64", "dabgpu_channel_freq_cycles", "dabgpu_channel_bank_create", "dabgpu_channel_bank_destroy",
     "dabgpu_channel_bank_set_params", "dabgpu_channel_bank_seek", "dabgpu_channel_bank_apply", "dabgpu_channel_bank_apply_host_sync",
+    "dabgpu_channel_fading_plan", "dabgpu_channel_fading_gain_host", "dabgpu_channel_profile", "dabgpu_channel_bank_create_fading",
+    "dabgpu_channel_bank_set_fading", "dabgpu_channel_plan_fading",
     "dabgpu_tii_cfg_default", "dabgpu_tii_pattern", "dabgpu_tii_main_id", "dabgpu_tii_carriers", "dabgpu_tii_validate",
     "dabgpu_ofdm_modulate_frames_tii", "dabgpu_ofdm_modulate_frames_tii_host_sync",
     "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
@@ -145,6 +147,25 @@ class ChannelStream(C.Structure):
     _fields_ = [("freq_q64", C.c_uint64), ("phase0_q64", C.c_uint64), ("start", C.c_int64), ("seed", C.c_uint64),
                 ("gain", C.c_float), ("noise_sigma", C.c_float), ("n_taps", C.c_int32), ("tap_delay", C.c_int32 * 8),
                 ("tap_re", C.c_float * 8), ("tap_im", C.c_float * 8), ("reserved", C.c_int32)]
+
+
+class ChannelFadingTap(C.Structure):
+    """dabgpu_channel_fading_tap"""
+    _fields_ = [("freq_q64", C.c_uint64 * 17), ("phase_q64", C.c_uint64 * 17), ("amp_diffuse", C.c_float), ("amp_los", C.c_float)]
+
+
+class ChannelFadingStream(C.Structure):
+    """dabgpu_channel_fading_stream"""
+    _fields_ = [("kind", C.c_int32 * 8), ("tap", ChannelFadingTap * 8)]
+
+
+class ChannelFadingSpec(C.Structure):
+    """dabgpu_channel_fading_spec"""
+    _fields_ = [("doppler_cycles", C.c_double), ("seed", C.c_uint64), ("kind", C.c_int32 * 8), ("rice_k", C.c_float * 8), ("los_cos", C.c_float * 8)]
+
+
+TAP_STATIC, TAP_FADING = 0, 1
+FADING_OSC, FADING_GRID, FADING_MAX_DOPPLER_CYCLES = 17, 64, 2.0 ** -11
 
 
 class ChannelGeometry(C.Structure):
@@ -341,6 +362,12 @@ def lib():
         L.dabgpu_channel_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.dabgpu_channel_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t,
                                                 C.c_float, C.c_void_p]
+        L.dabgpu_channel_plan_fading.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_channel_fading_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_channel_fading_gain_host.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_void_p]
+        L.dabgpu_channel_profile.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_channel_bank_create_fading.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_channel_bank_set_fading.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_channel_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
                                                           C.c_size_t, C.c_float]
         L.dabgpu_tii_cfg_default.argtypes = [C.c_void_p]
@@ -840,25 +867,85 @@ def channel_stream(taps=((0, 1.0, 0.0),), cycles_per_sample=0.0, phase0_cycles=0
     return P
 
 
-def channel_plan(streams):
-    """dabgpu_channel_plan (host only): {"halo", "block_samples", "lds_bytes", "staged"} of a list of ChannelStream; raises DabGpuError"""
+def channel_plan(streams, fading=False):
+    """dabgpu_channel_plan (host only): {"halo", "block_samples", "lds_bytes", "staged"} of a list of ChannelStream; raises DabGpuError.
+    fading: the geometry of a fading bank (dabgpu_channel_plan_fading: always staged, the grid gains in LDS)"""
     n = len(streams)
     arr = (ChannelStream * n)(*streams) if n else None
     g = ChannelGeometry()
-    check(lib().dabgpu_channel_plan(arr, n, C.byref(g)), "dabgpu_channel_plan")
+    if fading:
+        check(lib().dabgpu_channel_plan_fading(arr, n, C.byref(g)), "dabgpu_channel_plan_fading")
+    else:
+        check(lib().dabgpu_channel_plan(arr, n, C.byref(g)), "dabgpu_channel_plan")
     return {"halo": g.halo, "block_samples": g.block_samples, "lds_bytes": g.lds_bytes, "staged": g.staged}
 
 
-class Channel:
-    """dabgpu_channel_bank: multipath, carrier offset, timing offset and noise for n streams; the stream position lives on the device"""
+def channel_fading_spec(doppler_cycles=0.0, seed=0, kinds=(), rice_k=(), los_cos=()):
+    """a ChannelFadingSpec: doppler_cycles = f_D / sample rate (Hz / 2.048e6 for DAB), kinds TAP_STATIC / TAP_FADING per tap, rice_k linear"""
+    S = ChannelFadingSpec()
+    S.doppler_cycles, S.seed = float(doppler_cycles), int(seed)
+    for k, v in enumerate(kinds):
+        S.kind[k] = int(v)
+    for k, v in enumerate(rice_k):
+        S.rice_k[k] = float(v)
+    for k, v in enumerate(los_cos):
+        S.los_cos[k] = float(v)
+    return S
 
-    def __init__(self, ctx, streams):
+
+def channel_fading_plan(streams, specs):
+    """dabgpu_channel_fading_plan (host only): the fading tables (a ctypes array of ChannelFadingStream) of ChannelStream and
+    ChannelFadingSpec lists of one length; raises DabGpuError"""
+    n = len(streams)
+    assert len(specs) == n
+    arr = (ChannelStream * n)(*streams) if n else None
+    sp = (ChannelFadingSpec * n)(*specs) if n else None
+    out = (ChannelFadingStream * max(n, 1))()
+    check(lib().dabgpu_channel_fading_plan(arr, sp, n, out), "dabgpu_channel_fading_plan")
+    return out
+
+
+def channel_fading_gain(table, tap, m0, count):
+    """dabgpu_channel_fading_gain_host: g(m) of one tap of a ChannelFadingStream for m0 .. m0 + count - 1, complex64"""
+    import numpy as np
+    out = np.zeros(count, np.complex64)
+    check(lib().dabgpu_channel_fading_gain_host(C.byref(table), int(tap), int(m0), count, _ptr(out)), "dabgpu_channel_fading_gain_host")
+    return out
+
+
+def channel_profile(name):
+    """dabgpu_channel_profile: {"taps": [(delay, re, im), ...], "kinds", "rice_k", "los_cos"} of "tu6", "ra6" or "sfn2" (as recalled from
+    COST 207, delays in samples at 2.048 MHz); the lists feed channel_stream(taps=...) and channel_fading_spec(...)"""
+    P, S = ChannelStream(), ChannelFadingSpec()
+    check(lib().dabgpu_channel_profile(name.encode(), C.byref(P), C.byref(S)), "dabgpu_channel_profile")
+    n = P.n_taps
+    return {"taps": [(P.tap_delay[k], P.tap_re[k], P.tap_im[k]) for k in range(n)], "kinds": list(S.kind[:n]), "rice_k": list(S.rice_k[:n]),
+            "los_cos": list(S.los_cos[:n])}
+
+
+class Channel:
+    """dabgpu_channel_bank: multipath, carrier offset, timing offset and noise for n streams; the stream position lives on the device.
+    fading = the tables of channel_fading_plan: a fading bank (Rayleigh / Rice taps with Doppler)"""
+
+    def __init__(self, ctx, streams, fading=None):
         self._ctx = ctx
         self.n = len(streams)
-        self.plan = channel_plan(streams)
+        self.fading = fading is not None
+        self.plan = channel_plan(streams, fading=self.fading)
         arr = (ChannelStream * self.n)(*streams)
         self._h = C.c_void_p()
-        check(lib().dabgpu_channel_bank_create(ctx._h, self.n, arr, C.byref(self._h)), "dabgpu_channel_bank_create")
+        if self.fading:
+            tab = self._tables(fading)
+            check(lib().dabgpu_channel_bank_create_fading(ctx._h, self.n, arr, tab, C.byref(self._h)), "dabgpu_channel_bank_create_fading")
+        else:
+            check(lib().dabgpu_channel_bank_create(ctx._h, self.n, arr, C.byref(self._h)), "dabgpu_channel_bank_create")
+
+    def _tables(self, fading):
+        assert len(fading) >= self.n
+        return fading if isinstance(fading, C.Array) else (ChannelFadingStream * self.n)(*fading)
+
+    def set_fading(self, fading, stream=None):
+        check(lib().dabgpu_channel_bank_set_fading(self._h, self._tables(fading), Context._stream(stream)), "dabgpu_channel_bank_set_fading")
 
     def close(self):
         if self._h:

@@ -22,6 +22,13 @@
 //   --timing-offset N              the signal N samples late (N >= 0 with channel-coded frames: they are produced one at a time)
 //   --tap DELAY:RE:IM              repeatable, up to 8; delay in samples 0..2047; default one tap 0:1:0
 //   --noise-seed N                 default 1
+// Fading (include/dabgpu.h "Channel model, fading taps", DAB_Channel_Model::SetFading): taps with a Rayleigh or Rice gain and Doppler.
+//   --doppler-hz F                 maximum Doppler shift, 0..1000 Hz; with it every tap fades (Rayleigh) unless --tap-kind says otherwise
+//   --fading-seed S                default 1
+//   --profile tu6|ra6|sfn2         taps and kinds of a preset (as recalled from COST 207, delays rounded to samples); not with --tap
+//   --tap-kind K:static|rayleigh|rice:KDB   kind of tap K (list order, from 0); rice:KDB = Rice factor in dB, line of sight at cos 0.7
+// Without --doppler-hz, or with --doppler-hz 0 and every tap static, no fading bank is made: the code path and the bytes are those of the
+// channel options above.
 // TII (not in the reference, mode I; include/dabgpu.h "TII"):
 //   --tii P:C[:AMP]                repeatable, up to 4: a transmitter with main id P (0..69), sub id C (0..23) and amplitude AMP (default 1 =
 //                                  the power of a data carrier) fills the NULL period of every other frame, the first one included; the
@@ -35,6 +42,7 @@
 #include <vector>
 
 #include <math.h>
+#include <cmath>
 #include <memory>
 
 #include "dab/dabgpu_shared_context.h"
@@ -76,6 +84,13 @@ struct Args {
     unsigned long long noise_seed = 1;
     struct Tap { int delay; float re, im; };
     std::vector<Tap> taps;
+    // fading
+    bool have_doppler = false;
+    double doppler_hz = 0.0;
+    unsigned long long fading_seed = 1;
+    std::string profile;
+    struct TapKind { int tap; int kind; float rice_k; };
+    std::vector<TapKind> tap_kinds;
     std::vector<dabgpu_tii_tx> tii;
 };
 
@@ -87,6 +102,12 @@ static dabgpu_channel_stream channel_params(const Args& args, int nb_carriers) {
     P.seed = args.noise_seed;
     P.gain = 1.0f;
     std::vector<Args::Tap> taps = args.taps;
+    if (!args.profile.empty()) {
+        dabgpu_channel_stream pp = {};
+        dabgpu_channel_fading_spec ps = {};
+        if (dabgpu_channel_profile(args.profile.c_str(), &pp, &ps) != DABGPU_OK) throw std::runtime_error(std::string("--profile: ") + dabgpu_last_error());
+        for (int k = 0; k < pp.n_taps; k++) taps.push_back({pp.tap_delay[k], pp.tap_re[k], pp.tap_im[k]});
+    }
     if (taps.empty()) taps.push_back({0, 1.0f, 0.0f});
     if (taps.size() > DABGPU_CHANNEL_MAX_TAPS) throw std::runtime_error("--tap: at most 8 taps");
     double h2 = 0.0;
@@ -97,6 +118,42 @@ static dabgpu_channel_stream channel_params(const Args& args, int nb_carriers) {
     }
     P.noise_sigma = args.have_snr ? DAB_Channel_Model::NoiseSigma((double)nb_carriers * h2, args.snr_db) : 0.0f;
     return P;
+}
+
+// the fading spec of the options; false: no tap fades (no fading bank is made)
+static bool fading_spec(const Args& args, const dabgpu_channel_stream& P, dabgpu_channel_fading_spec& S) {
+    S = dabgpu_channel_fading_spec{};
+    if (!args.have_doppler) {
+        if (!args.tap_kinds.empty() || !args.profile.empty()) throw std::runtime_error("--profile and --tap-kind want --doppler-hz");
+        return false;
+    }
+    S.doppler_cycles = args.doppler_hz / 2.048e6;
+    S.seed = args.fading_seed;
+    if (!args.profile.empty()) {
+        dabgpu_channel_stream pp = {};
+        dabgpu_channel_profile(args.profile.c_str(), &pp, &S);             // (kinds, rice_k, los_cos; the name was checked with the taps)
+        S.doppler_cycles = args.doppler_hz / 2.048e6; S.seed = args.fading_seed;
+    } else
+        for (int k = 0; k < P.n_taps; k++) S.kind[k] = DABGPU_TAP_FADING;
+    for (const auto& t : args.tap_kinds) {
+        if (t.tap < 0 || t.tap >= P.n_taps) throw std::runtime_error("--tap-kind: tap " + std::to_string(t.tap) + " of " + std::to_string(P.n_taps));
+        S.kind[t.tap] = t.kind; S.rice_k[t.tap] = t.rice_k; S.los_cos[t.tap] = t.rice_k > 0.0f ? 0.7f : 0.0f;
+    }
+    bool any = false;
+    for (int k = 0; k < P.n_taps; k++) any = any || S.kind[k] == DABGPU_TAP_FADING;
+    return any;
+}
+
+// K:static | K:rayleigh | K:rice:KDB
+static Args::TapKind parse_tap_kind(const std::string& v) {
+    const size_t a = v.find(':');
+    if (a == std::string::npos) throw std::runtime_error("--tap-kind wants K:static|rayleigh|rice:KDB, got " + v);
+    const int tap = std::stoi(v.substr(0, a));
+    const std::string kind = v.substr(a + 1);
+    if (kind == "static") return {tap, DABGPU_TAP_STATIC, 0.0f};
+    if (kind == "rayleigh") return {tap, DABGPU_TAP_FADING, 0.0f};
+    if (kind.rfind("rice:", 0) == 0) return {tap, DABGPU_TAP_FADING, (float)std::pow(10.0, std::stod(kind.substr(5)) / 10.0)};
+    throw std::runtime_error("--tap-kind wants K:static|rayleigh|rice:KDB, got " + v);
 }
 
 // DELAY:RE:IM
@@ -174,6 +231,8 @@ static int run_coded(const Args& args, FILE* fp_out) {
         if (args.timing_offset < 0) throw std::runtime_error("--timing-offset must be >= 0 with channel-coded frames");
         cp = channel_params(args, 1536);
         channel = std::make_unique<DAB_Channel_Model>(cp);
+        dabgpu_channel_fading_spec spec;
+        if (fading_spec(args, cp, spec)) channel->SetFading(spec);
         window.assign(2 * S, std::complex<float>(0.0f, 0.0f));
     }
     const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
@@ -204,12 +263,15 @@ static void usage(const char* argv0) {
     fprintf(stderr, "usage: %s [-m|--transmission-mode 1..4] [-f|--frequency HZ] [-o|--output FILE] [--frames N]\n"
                     "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
                     "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N] [--tii P:C[:AMP]]...\n"
+                    "          [--doppler-hz F] [--fading-seed S] [--profile tu6|ra6|sfn2] [--tap-kind K:static|rayleigh|rice:KDB]...\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
                     "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
                     "quantised: taps (default 0:1:0, delays 0..2047 samples), carrier offset, delay, white Gaussian noise with\n"
                     "  noise_sigma = sqrt(P / (2 * 10^(DB / 10))) per component, P = nb_data_carriers * sum |tap|^2\n"
                     "(the mean power of the modulator's symbols after the taps; the NULL period is not counted);\n"
+                    "with --doppler-hz F (0..1000) the taps fade (Rayleigh; --tap-kind sets single taps static or Rice with a factor in dB,\n"
+                    "--profile takes taps and kinds from a preset as recalled from COST 207), unit mean power each, seeded by --fading-seed;\n"
                     "with --tii (mode I, up to 4) the NULL period of every other frame carries those transmitters' identification\n", argv0);
 }
 
@@ -233,10 +295,15 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--timing-offset") { args.timing_offset = std::stoll(value()); args.channel = true; }
         else if (a == "--tap") { args.taps.push_back(parse_tap(value())); args.channel = true; }
         else if (a == "--noise-seed") { args.noise_seed = std::stoull(value()); args.channel = true; }
+        else if (a == "--doppler-hz") { args.doppler_hz = std::stod(value()); args.have_doppler = true; args.channel = true; }
+        else if (a == "--fading-seed") { args.fading_seed = std::stoull(value()); args.channel = true; }
+        else if (a == "--profile") { args.profile = value(); args.channel = true; }
+        else if (a == "--tap-kind") { args.tap_kinds.push_back(parse_tap_kind(value())); args.channel = true; }
         else if (a == "--tii") args.tii.push_back(parse_tii(value()));
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
     }
+    if (!args.profile.empty() && !args.taps.empty()) throw std::runtime_error("--profile is not available with --tap");
     if (args.tii.size() > DABGPU_TII_MAX_TX) throw std::runtime_error("--tii: at most 4 transmitters");
     if (!args.tii.empty() && args.coded) throw std::runtime_error("--tii is not available with channel-coded frames");
     if (args.transmission_mode < 1 || args.transmission_mode > 4) throw std::runtime_error("--transmission-mode must be one of 1,2,3,4");
@@ -308,7 +375,10 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error());
                 return 1;
             }
-            DAB_Channel_Model channel(channel_params(args, (int)params.nb_data_carriers));
+            const dabgpu_channel_stream cp = channel_params(args, (int)params.nb_data_carriers);
+            DAB_Channel_Model channel(cp);
+            dabgpu_channel_fading_spec spec;
+            if (fading_spec(args, cp, spec)) channel.SetFading(spec);
             const float u8_scale = (1.0f / (float)params.nb_data_carriers * 4.0f) * 127.5f;
             for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
                 channel.ApplyU8(quantised, frame, true, u8_scale);

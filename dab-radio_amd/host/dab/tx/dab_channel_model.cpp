@@ -11,7 +11,7 @@ static void check(int st, const char* what) {
     if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Channel_Model: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
 }
 
-DAB_Channel_Model::DAB_Channel_Model(const dabgpu_channel_stream& params) {
+DAB_Channel_Model::DAB_Channel_Model(const dabgpu_channel_stream& params) : m_created(params), m_params(params) {
     if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
         throw std::runtime_error("DAB_Channel_Model: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
                                  ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
@@ -23,19 +23,45 @@ DAB_Channel_Model::~DAB_Channel_Model() { dabgpu_channel_bank_destroy(m_bank); }
 float DAB_Channel_Model::NoiseSigma(double mean_power, double snr_db) { return (float)std::sqrt(mean_power / (2.0 * std::pow(10.0, snr_db / 10.0))); }
 
 void DAB_Channel_Model::SetParams(const dabgpu_channel_stream& params) {
+    dabgpu_channel_fading_stream table;
+    if (m_fading) check(dabgpu_channel_fading_plan(&params, &m_spec, 1, &table), "dabgpu_channel_fading_plan");
     check(dabgpu_channel_bank_set_params(m_bank, &params, nullptr), "dabgpu_channel_bank_set_params");
+    if (m_fading) check(dabgpu_channel_bank_set_fading(m_bank, &table, nullptr), "dabgpu_channel_bank_set_fading");
     check(dabgpu_synchronize(dabgpu_shared_context(), nullptr), "dabgpu_synchronize");
+    m_params = params;
+}
+
+void DAB_Channel_Model::SetFading(const dabgpu_channel_fading_spec& spec) {
+    dabgpu_channel_fading_stream table;
+    check(dabgpu_channel_fading_plan(&m_params, &spec, 1, &table), "dabgpu_channel_fading_plan");
+    if (m_fading) {
+        check(dabgpu_channel_bank_set_fading(m_bank, &table, nullptr), "dabgpu_channel_bank_set_fading");
+    } else {
+        // the kernel and the LDS size of a bank are fixed when it is created: a fading bank takes the plain one's place and position
+        dabgpu_channel_bank* bank = nullptr;
+        check(dabgpu_channel_bank_create_fading(dabgpu_shared_context(), 1, &m_created, &table, &bank), "dabgpu_channel_bank_create_fading");
+        dabgpu_channel_bank_destroy(m_bank);
+        m_bank = bank;
+        check(dabgpu_channel_bank_set_params(m_bank, &m_params, nullptr), "dabgpu_channel_bank_set_params");
+        check(dabgpu_channel_bank_set_fading(m_bank, &table, nullptr), "dabgpu_channel_bank_set_fading");
+        check(dabgpu_channel_bank_seek(m_bank, m_position, nullptr), "dabgpu_channel_bank_seek");
+    }
+    check(dabgpu_synchronize(dabgpu_shared_context(), nullptr), "dabgpu_synchronize");
+    m_spec = spec;
+    m_fading = true;
 }
 
 void DAB_Channel_Model::Seek(uint64_t position) {
     check(dabgpu_channel_bank_seek(m_bank, position, nullptr), "dabgpu_channel_bank_seek");
     check(dabgpu_synchronize(dabgpu_shared_context(), nullptr), "dabgpu_synchronize");
+    m_position = position;
 }
 
 bool DAB_Channel_Model::Apply(tcb::span<std::complex<float>> out, tcb::span<const std::complex<float>> in, bool wrap) {
     if (in.empty()) return false;
     check(dabgpu_channel_bank_apply_host_sync(m_bank, reinterpret_cast<const float*>(in.data()), 0, in.size(), wrap ? 1 : 0, out.size(), out.data(),
                                               DABGPU_IQ_RAW_F32L, 0, 1.0f), "dabgpu_channel_bank_apply_host_sync");
+    m_position += out.size();
     return true;
 }
 
@@ -43,5 +69,6 @@ bool DAB_Channel_Model::ApplyU8(tcb::span<uint8_t> out, tcb::span<const std::com
     if (in.empty() || (out.size() & 1)) return false;
     check(dabgpu_channel_bank_apply_host_sync(m_bank, reinterpret_cast<const float*>(in.data()), 0, in.size(), wrap ? 1 : 0, out.size() / 2, out.data(),
                                               DABGPU_IQ_RAW_U8, 0, u8_scale), "dabgpu_channel_bank_apply_host_sync");
+    m_position += out.size() / 2;
     return true;
 }

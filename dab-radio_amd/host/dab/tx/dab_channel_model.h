@@ -23,6 +23,10 @@ public:
     // noise_sigma for a signal-to-noise ratio in dB and the mean power of the channel's noiseless output
     static float NoiseSigma(double mean_power, double snr_db);
     void SetParams(const dabgpu_channel_stream& params);
+    // Rayleigh / Rice taps with Doppler (include/dabgpu.h, "Channel model, fading taps"): the tables are planned from `spec` for the
+    // parameters in force (stream 0) and planned again by every later SetParams.  The first call turns the object into a fading bank at
+    // the position it has reached; a model that never calls it is the class of before.
+    void SetFading(const dabgpu_channel_fading_spec& spec);
     void Seek(uint64_t position);
     // out.size() samples from the current position; false for an empty input
     bool Apply(tcb::span<std::complex<float>> out, tcb::span<const std::complex<float>> in, bool wrap);
@@ -30,4 +34,8 @@ public:
     bool ApplyU8(tcb::span<uint8_t> out, tcb::span<const std::complex<float>> in, bool wrap, float u8_scale);
 private:
     dabgpu_channel_bank* m_bank = nullptr;
+    dabgpu_channel_stream m_created, m_params;   // of the constructor (the widest), and in force
+    dabgpu_channel_fading_spec m_spec = {};
+    bool m_fading = false;
+    uint64_t m_position = 0;                 // the bank's position, followed on the host: SetFading recreates the bank there
 };

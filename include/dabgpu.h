@@ -1048,6 +1048,81 @@ int dabgpu_channel_bank_apply_host_sync(dabgpu_channel_bank *bank, const float *
                                         size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Channel model, fading taps: Rayleigh and Rice taps with Doppler beside the constant taps above.  A fading stream keeps its
+ * dabgpu_channel_stream and adds one dabgpu_channel_fading_stream: per tap k a kind,
+ *   DABGPU_TAP_STATIC  the tap is the constant h_k = tap_re[k] + j tap_im[k], exactly as above
+ *   DABGPU_TAP_FADING  the tap is h_k * g_k(m) with a complex gain g_k(m) of unit mean power
+ * and, for a fading tap, DABGPU_FADING_OSC = 17 exact 64-bit integer oscillators (freq_q64[n], phase_q64[n]) -- n = 0 .. 15 the diffuse
+ * part, n = 16 the line of sight -- and two floats amp_diffuse = sqrt(1 / (K + 1)) / 4, amp_los = sqrt(K / (K + 1)) (Rayleigh: K = 0).
+ * The gain depends on (table, absolute sample m) alone: a + b samples equal a and then b, at any split.
+ *   grid      at the absolute samples 64 j (DABGPU_FADING_GRID = 64): (c_n, s_n) = (cos, sin) of oscillator n's angle at sample 64 j (its
+ *             top 24 bits, as for the carrier); S = the sum of the 16 diffuse (c_n, s_n) as a fixed pairwise tree -- level by level
+ *             v[i] += v[i ^ 1], v[i ^ 2], v[i ^ 4], v[i ^ 8] -- and G_j = fmaf(amp_los, (c_16, s_16), amp_diffuse * S) per component;
+ *             amp_los = 0 evaluates no line of sight and G_j = amp_diffuse * S
+ *   between   w = (m & 63) / 64 (exact), j = m >> 6: g(m) = fmaf(w, G_{j+1} - G_j, G_j) per component.  The interpolated form IS the
+ *             definition (tests/channel_fading_model.py interpolates as well): at the largest Doppler accepted, 2^-11 cycles per sample
+ *             (1000 Hz at 2.048 MHz; L band at 200 km/h stays below 300 Hz), an oscillator turns phi = 0.196 rad per interval and the
+ *             chord of a unit phasor is off by at most phi^2 / 8 = 4.8e-3 (4.8e-5 at 100 Hz)
+ *   tap       e_k = h_k * g_k(m): (fmaf(-h_im, g_im, h_re * g_re), fmaf(h_im, g_re, h_re * g_im)); z then sums e_k * x[...] over the taps
+ *             in list order as above (a static tap enters with h_k itself, no product); gain, rotation, noise and the u8 quantiser are
+ *             unchanged.  Written once in dab-radio_amd/csrc/channel_core.h; error bound and measurements: DESIGN.md 4.18.
+ *
+ * dabgpu_channel_fading_plan (host only, no device): the tables of n_streams streams from their specs.  For stream s, tap k, oscillator
+ * n < 16 the four words are Philox4x32-10(key = seed, counter = (n, k, s, 1)) -- the last word keeps them apart from the noise, which
+ * counts with 0 --, the arrival angle alpha = 2 pi (n + (w0 + 0.5) 2^-32) / 16 (stratified: the mean over seeds of the time-averaged
+ * autocorrelation is J0(2 pi f_D tau)), freq_q64 = dabgpu_channel_freq_q64(doppler_cycles * cos alpha), phase_q64 = (w2 << 32) | w3.
+ * The line of sight is n = 16: freq_q64 = dabgpu_channel_freq_q64(doppler_cycles * los_cos[k]), its phase from its own call
+ * (counter (16, k, s, 1)).  Static taps and taps past n_taps get kind STATIC and zeroed oscillators.  Refused with
+ * DABGPU_ERR_INVALID_ARG: a null pointer, everything dabgpu_channel_plan refuses, doppler_cycles outside [0, 2^-11] (NaN included), a
+ * kind that is neither STATIC nor FADING, rice_k negative or not finite, los_cos outside [-1, 1] or not finite (of the taps below
+ * n_taps; rice_k and los_cos of static taps are not read).
+ * dabgpu_channel_fading_gain_host: g(m) of one tap for m = m0 .. m0 + count - 1 as (re, im) float pairs, computed on the host from the
+ * same header ((1, 0) for a static tap); for users who want the channel state, and for the tests.
+ * dabgpu_channel_profile: presets AS RECALLED FROM COST 207 AND NOT CHECKED AGAINST THE DOCUMENT, delays rounded to the nearest sample
+ * at 2.048 MHz, amplitudes real and normalised to unit total power; two taps that round to one delay stay two taps (they fade
+ * independently).  Fills n_taps, tap_delay, tap_re, tap_im of *params (its other fields stay) and kind, rice_k, los_cos of *spec:
+ *   "tu6"   0, 0.2, 0.5, 1.6, 2.3, 5.0 us at -3, 0, -2, -6, -8, -10 dB, all Rayleigh
+ *   "ra6"   0, 0.1, 0.2, 0.3, 0.4, 0.5 us at 0, -4, -8, -12, -16, -20 dB, the first tap Rice (K = 0.91 / 0.41, los_cos = 0.7), the rest Rayleigh
+ *   "sfn2"  0 and 200 samples at 0 and -6 dB, both Rayleigh
+ * Any other name: DABGPU_ERR_INVALID_ARG. */
+#define DABGPU_FADING_OSC 17
+#define DABGPU_FADING_GRID 64
+#define DABGPU_FADING_MAX_DOPPLER_CYCLES 0.00048828125       /* 2^-11 */
+enum { DABGPU_TAP_STATIC = 0, DABGPU_TAP_FADING = 1 };
+typedef struct {
+    uint64_t freq_q64[DABGPU_FADING_OSC], phase_q64[DABGPU_FADING_OSC];
+    float amp_diffuse, amp_los;
+} dabgpu_channel_fading_tap;
+typedef struct {
+    int32_t kind[DABGPU_CHANNEL_MAX_TAPS];
+    dabgpu_channel_fading_tap tap[DABGPU_CHANNEL_MAX_TAPS];
+} dabgpu_channel_fading_stream;
+typedef struct {
+    double doppler_cycles;                       /* maximum Doppler shift f_D over the sample rate */
+    uint64_t seed;
+    int32_t kind[DABGPU_CHANNEL_MAX_TAPS];
+    float rice_k[DABGPU_CHANNEL_MAX_TAPS];       /* linear power ratio line of sight / diffuse, >= 0 */
+    float los_cos[DABGPU_CHANNEL_MAX_TAPS];      /* cosine of the line of sight's arrival angle */
+} dabgpu_channel_fading_spec;
+int dabgpu_channel_fading_plan(const dabgpu_channel_stream *params, const dabgpu_channel_fading_spec *specs, size_t n_streams,
+                               dabgpu_channel_fading_stream *out);
+int dabgpu_channel_fading_gain_host(const dabgpu_channel_fading_stream *row, int tap, uint64_t m0, size_t count, float *out);
+int dabgpu_channel_profile(const char *name, dabgpu_channel_stream *params, dabgpu_channel_fading_spec *spec);
+
+/* A fading bank: dabgpu_channel_bank_create_fading uploads the tables beside the parameters; such a bank always launches the fading
+ * kernel (staged; its LDS holds the tile's grid gains, (halo + 1026 + 18 x 8) x 8 bytes), whatever the kinds say -- the geometry is fixed at
+ * creation for the reason given above: captured calls.  A table is accepted when every kind below n_taps is STATIC or FADING and the two
+ * amplitudes of its fading taps are finite.  dabgpu_channel_bank_set_fading replaces all tables, ordered on `stream` like _set_params,
+ * and is refused (DABGPU_ERR_INVALID_ARG) on a bank not created fading.  _apply, _apply_host_sync, _seek and _set_params work on a fading
+ * bank unchanged (the kinds are read against the n_taps of the parameters in force); a call stays two launches and capturable.  A fading
+ * bank whose kinds are all STATIC returns the plain bank's output bit for bit (tests/test_gpu_channel_fading.py). */
+/* dabgpu_channel_plan for a fading bank (host only): the same checks, `staged` = 1 and `lds_bytes` with the grid gains */
+int dabgpu_channel_plan_fading(const dabgpu_channel_stream *params, size_t n_streams, dabgpu_channel_geometry *out);
+int dabgpu_channel_bank_create_fading(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_channel_stream *h_params,
+                                      const dabgpu_channel_fading_stream *h_tables, dabgpu_channel_bank **out);
+int dabgpu_channel_bank_set_fading(dabgpu_channel_bank *bank, const dabgpu_channel_fading_stream *h_tables, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * TII: transmitter identification information in the NULL symbol of mode I, both directions (every other mode returns
  * DABGPU_ERR_INVALID_ARG).  The reference has no TII code; this section is the definition.  It is EN 300 401 clause 14.8.1 as recalled:
  * THE NUMBERING OF p FOLLOWS THE TABLE BELOW AND HAS NOT BEEN CHECKED AGAINST TABLE 38 of the standard.

@@ -1,0 +1,265 @@
+"""-m gpu: the fading kernel (dabgpu_channel_bank_create_fading, dab-radio_amd/csrc/channel_fading.hip) against the host model -- the same
+channel_core.h under g++ (tests/cpp/channel_fading_host_model.cpp) -- bit for bit, float and u8; the host model is tied to the float64
+model by tests/test_channel_fading_model.py.  Small shapes: 3400 output samples (three tiles and a part) from a wrapped 3077-sample
+input, positions that put a grid point inside the first partial tile, a tap at the largest delay; 4 KiB guards around every output."""
+import numpy as np
+import pytest
+
+import channel_fading_model as FM
+import channel_model as CM
+
+pytestmark = pytest.mark.gpu
+
+N_IN, N_OUT = 3077, 3400
+GUARD, GUARD_BYTES = 0xA5, 4096
+POSITIONS = (0, 1, 61, (1 << 33) - 1701)
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    return FM.build_host_model(tmp_path_factory.mktemp("channel_fading_host_model"))
+
+
+@pytest.fixture(scope="module")
+def static_host(tmp_path_factory):
+    return CM.build_host_model(tmp_path_factory.mktemp("channel_host_model"))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import dabgpu
+    c = dabgpu.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def x3():
+    rng = np.random.default_rng(7300)
+    return (rng.standard_normal((3, N_IN)) + 1j * rng.standard_normal((3, N_IN))).astype(np.complex64)
+
+
+def streams3(doppler=300 / 2.048e6, seed=0xfade):
+    """tu6 with a seventh Rayleigh echo at the largest delay, noise and a carrier offset; ra6 (a Rice tap) at another start, no noise; eight
+    static taps.  -> (parameter dicts, dabgpu tables)"""
+    import dabgpu
+    tu6, ra6 = dabgpu.channel_profile("tu6"), dabgpu.channel_profile("ra6")
+    plist = [
+        CM.params_dict(taps=tu6["taps"] + [(2047, 0.2, -0.1)], noise_sigma=0.25, seed=0x1234567890abcdef, freq_q64=int(0.00123 * 2 ** 64), phase0_q64=1 << 62,
+                       start=-41),
+        CM.params_dict(taps=ra6["taps"], freq_q64=(1 << 64) - int(3.3e-4 * 2 ** 64), start=N_IN + 100, gain=0.7),
+        CM.params_dict(taps=[(3, 0.5, 0.1), (0, -0.2, 0.9), (1, 0.3, 0.3), (1023, 0.1, 0.0), (1025, 0.0, -0.4), (2047, 0.25, 0.25), (77, -0.6, 0.2),
+                             (504, 0.2, -0.1)], noise_sigma=1.5, seed=99, freq_q64=int(0.4999 * 2 ** 64), gain=2.0),
+    ]
+    specs = [dabgpu.channel_fading_spec(doppler, seed, tu6["kinds"] + [1], tu6["rice_k"] + [0.0], tu6["los_cos"] + [0.0]),
+             dabgpu.channel_fading_spec(doppler, seed + 1, ra6["kinds"], ra6["rice_k"], ra6["los_cos"]),
+             dabgpu.channel_fading_spec(doppler, seed + 2, [0] * 8)]
+    return plist, dabgpu.channel_fading_plan(g_streams(plist), specs)
+
+
+def g_streams(plist):
+    import dabgpu
+    return [CM.to_struct(P, dabgpu.ChannelStream) for P in plist]
+
+
+def host_tables(tables, n):
+    """the library's tables as the host model's ctypes array (one layout)"""
+    import ctypes as C
+    arr = (FM.FadingStream * n)()
+    C.memmove(arr, tables, n * C.sizeof(FM.FadingStream))
+    return arr
+
+
+def run_device(ch, x, n_out, wrap=True, fmt=CM.F32, scale=1.0):
+    """one apply into rows with 4 KiB of guard bytes before and behind d_out (and 32 between the rows) -> (rows, guards intact)"""
+    import torch
+    sb = 8 if fmt == CM.F32 else 2
+    stride = ((n_out * sb + 15) & ~15) + 32
+    whole = torch.full((GUARD_BYTES + ch.n * stride + GUARD_BYTES,), GUARD, dtype=torch.uint8, device="cuda")
+    view = whole[GUARD_BYTES:GUARD_BYTES + ch.n * stride]
+    n_in = x.shape[-1]
+    pad = np.zeros(x.shape[:-1] + (n_in + (n_in & 1),), np.complex64)        # rows an even count apart
+    pad[..., :n_in] = x
+    d_in = torch.from_numpy(pad).cuda()
+    ch.apply(d_in, n_in, n_out, view, in_stride_samples=0 if x.ndim == 1 else pad.shape[-1], wrap=wrap, out_format=fmt, out_stride_bytes=stride, u8_scale=scale)
+    torch.cuda.synchronize()
+    h = whole.cpu().numpy()
+    rows = h[GUARD_BYTES:GUARD_BYTES + ch.n * stride].reshape(ch.n, stride)
+    ok = bool(np.all(h[:GUARD_BYTES] == GUARD) and np.all(h[-GUARD_BYTES:] == GUARD) and np.all(rows[:, n_out * sb:] == GUARD))
+    data = np.ascontiguousarray(rows[:, :n_out * sb])
+    return (data.view(np.complex64) if fmt == CM.F32 else data.reshape(ch.n, n_out, 2)), ok
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+@pytest.mark.parametrize("fmt", [CM.F32, CM.U8])
+def test_three_streams_equal_the_host_model(host, ctx, x3, fmt):
+    """positions 0, 1 (odd: the sample-by-sample stores), 61 (a grid point inside the first partial tile), 2^33 - 1701"""
+    import dabgpu
+    plist, tables = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    ht = host_tables(tables, 3)
+    for pos in POSITIONS:
+        ch.seek(pos)
+        got, ok = run_device(ch, x3, N_OUT, True, fmt, scale=9.0)
+        exp = FM.host_apply(host, plist, ht, x3, pos, N_OUT, True, fmt, scale=9.0)
+        assert ok, "guard bytes before, between or behind the rows were written"
+        assert same_bits(got, exp), f"position {pos}"
+    ch.seek(5)
+    got, ok = run_device(ch, x3, N_OUT, False, fmt, scale=9.0)               # no wrap: zeros outside the input
+    assert ok and same_bits(got, FM.host_apply(host, plist, ht, x3, 5, N_OUT, False, fmt, scale=9.0))
+    ch.close()
+
+
+@pytest.mark.parametrize("pos", [0, (1 << 33) - 1701])
+def test_gains_read_directly(ctx, pos):
+    """input = (1, 0), one tap h = 1, no rotation, no noise: the output IS g(m) and equals dabgpu_channel_fading_gain_host as bit patterns
+    (Rayleigh at the largest Doppler, Rice, and no Doppler at all: a constant)"""
+    import dabgpu
+    plist = [CM.params_dict()] * 3
+    specs = [dabgpu.channel_fading_spec(2.0 ** -11, 11, [1]), dabgpu.channel_fading_spec(100 / 2.048e6, 12, [1], [4.0], [0.7]),
+             dabgpu.channel_fading_spec(0.0, 13, [1], [1.0], [-1.0])]
+    tables = dabgpu.channel_fading_plan(g_streams(plist), specs)
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    ch.seek(pos)
+    got, ok = run_device(ch, np.ones(2, np.complex64), N_OUT)
+    assert ok
+    for s in range(3):
+        assert same_bits(got[s], dabgpu.channel_fading_gain(tables[s], 0, pos, N_OUT)), f"stream {s}"
+    assert not same_bits(got[0, :-1], got[0, 1:]) and 0.05 < np.abs(got[0]).mean() < 4.0
+    assert np.all(got[2] == got[2, 0]) and abs(got[2, 0]) > 0                                 # doppler_cycles = 0: constant over the call
+    ch.close()
+
+
+@pytest.mark.parametrize("fmt", [CM.F32, CM.U8])
+def test_split_calls_equal_one_call(ctx, x3, fmt):
+    """a + b samples equal a and then b for a in {1, 63, 64, 1023, 1025}"""
+    import dabgpu
+    plist, tables = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    ch.seek(3)
+    whole, ok = run_device(ch, x3, N_OUT, True, fmt, scale=9.0)
+    assert ok
+    for a in (1, 63, 64, 1023, 1025):
+        ch.seek(3)
+        first, ok1 = run_device(ch, x3, a, True, fmt, scale=9.0)
+        rest, ok2 = run_device(ch, x3, N_OUT - a, True, fmt, scale=9.0)
+        assert ok1 and ok2 and same_bits(first, whole[:, :a]) and same_bits(rest, whole[:, a:]), f"a = {a}"
+    ch.close()
+
+
+@pytest.mark.parametrize("fmt", [CM.F32, CM.U8])
+def test_all_static_fading_bank_equals_a_plain_bank(static_host, ctx, x3, fmt):
+    import dabgpu
+    plist, _ = streams3()
+    tables = dabgpu.channel_fading_plan(g_streams(plist), [dabgpu.channel_fading_spec(1e-4, 5, [0] * 8)] * 3)
+    fading, plain = dabgpu.Channel(ctx, g_streams(plist), fading=tables), dabgpu.Channel(ctx, g_streams(plist))
+    for pos in (0, 61):
+        fading.seek(pos); plain.seek(pos)
+        a, ok1 = run_device(fading, x3, N_OUT, True, fmt, scale=9.0)
+        b, ok2 = run_device(plain, x3, N_OUT, True, fmt, scale=9.0)
+        assert ok1 and ok2 and same_bits(a, b)
+        assert same_bits(a, CM.host_apply(static_host, plist, x3, pos, N_OUT, True, fmt, scale=9.0))
+    # single zero-delay taps: the plain bank reads its input directly, the fading bank stages it; one result
+    direct = [CM.params_dict(taps=[(0, 0.6, 0.8)], noise_sigma=0.1, seed=1)] * 3
+    tables = dabgpu.channel_fading_plan(g_streams(direct), [dabgpu.channel_fading_spec()] * 3)
+    f2, p2 = dabgpu.Channel(ctx, g_streams(direct), fading=tables), dabgpu.Channel(ctx, g_streams(direct))
+    assert p2.plan["staged"] == 0
+    a, ok1 = run_device(f2, x3, N_OUT, False, fmt, scale=9.0)
+    b, ok2 = run_device(p2, x3, N_OUT, False, fmt, scale=9.0)
+    assert ok1 and ok2 and same_bits(a, b)
+    for c in (fading, plain, f2, p2):
+        c.close()
+
+
+def test_set_fading_and_set_params_on_a_fading_bank(host, ctx, x3):
+    import dabgpu
+    plist, tables = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    first, ok = run_device(ch, x3, N_OUT)
+    assert ok
+    _, other = streams3(doppler=2.0 ** -11, seed=77)
+    ch.set_fading(other)
+    ch.seek(0)
+    got, ok = run_device(ch, x3, N_OUT)
+    assert ok and same_bits(got, FM.host_apply(host, plist, host_tables(other, 3), x3, 0, N_OUT, True))
+    assert not same_bits(got[0], first[0]) and same_bits(got[2], first[2])                   # (stream 2 is static)
+    narrow = [dict(P, taps=P["taps"][:2], gain=0.5) for P in plist]
+    ch.set_params(g_streams(narrow))
+    ch.seek(61)
+    got, ok = run_device(ch, x3, N_OUT)
+    assert ok and same_bits(got, FM.host_apply(host, narrow, host_tables(other, 3), x3, 61, N_OUT, True))
+    ch.close()
+
+
+def test_graph_replays_continue_the_stream(host, ctx, x3):
+    """one call, then the same call captured and replayed twice: three times the length of one call"""
+    import dabgpu
+    import torch
+    plist, tables = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    n = 1029
+    pad = np.zeros((3, N_IN + 1), np.complex64)
+    pad[:, :-1] = x3
+    d_in = torch.from_numpy(pad).cuda()
+    stride = (n * 8 + 15) & ~15
+    out = torch.zeros(3 * stride, dtype=torch.uint8, device="cuda")
+    exp = FM.host_apply(host, plist, host_tables(tables, 3), x3, 0, 3 * n, True)
+
+    def rows():
+        torch.cuda.synchronize()
+        return out.cpu().numpy().reshape(3, stride)[:, :n * 8].copy().view(np.complex64)
+
+    ch.apply(d_in, N_IN, n, out, in_stride_samples=N_IN + 1, wrap=True, out_stride_bytes=stride)
+    assert same_bits(rows(), exp[:, :n])
+    side = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g, stream=side):
+        ch.apply(d_in, N_IN, n, out, in_stride_samples=N_IN + 1, wrap=True, out_stride_bytes=stride, stream=side.cuda_stream)
+    for r in (1, 2):                                                         # (capturing enqueued nothing: the position is still n)
+        g.replay()
+        assert same_bits(rows(), exp[:, r * n:(r + 1) * n]), f"replay {r}"
+    ch.close()
+
+
+def test_refusals_leave_the_output_untouched(host, ctx, x3):
+    import dabgpu
+    import torch
+    plist, tables = streams3()
+    plain = dabgpu.Channel(ctx, g_streams(plist))
+    with pytest.raises(dabgpu.DabGpuError) as err:
+        plain.set_fading(tables)
+    assert "not created with dabgpu_channel_bank_create_fading" in str(err.value)
+    plain.close()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    bad = dabgpu.channel_fading_plan(g_streams(plist), [dabgpu.channel_fading_spec(1e-4, 5, [1] * 8)] * 3)
+    bad[1].kind[2] = 7
+    with pytest.raises(dabgpu.DabGpuError) as err:
+        ch.set_fading(bad)
+    assert "stream 1: tap 2: kind 7" in str(err.value)
+    with pytest.raises(dabgpu.DabGpuError) as err:
+        dabgpu.Channel(ctx, g_streams(plist), fading=bad)
+    assert "channel_bank_create_fading: stream 1: tap 2: kind 7" in str(err.value)
+    with pytest.raises(dabgpu.DabGpuError) as err:
+        ch.set_params(g_streams([dict(P, taps=[(0, 1.0, 0.0), (2047, 1.0, 0.0)]) for P in plist][:2] + [CM.params_dict(taps=[(2048, 1.0, 0.0)])]))
+    assert "delay 2048" in str(err.value)
+    pad = np.zeros((3, N_IN + 1), np.complex64)
+    pad[:, :-1] = x3
+    d_in = torch.from_numpy(pad).cuda()
+    d_out = torch.full((3 * 1040 * 8,), GUARD, dtype=torch.uint8, device="cuda")
+    for change, text in ((dict(out_format=3), "output format"), (dict(n_in=0), "n_in = 0"), (dict(in_stride_samples=N_IN), "in_stride_samples"),
+                         (dict(out_stride_bytes=1029 * 8 - 8), "out_stride_bytes"), (dict(d_out=d_out[8:]), "16-byte aligned"), (dict(d_in=None), "null input")):
+        a = dict(d_in=d_in, n_in=N_IN, n_out=1029, d_out=d_out, in_stride_samples=N_IN + 1, wrap=True, out_stride_bytes=1040 * 8)
+        a.update(change)
+        with pytest.raises(dabgpu.DabGpuError) as err:
+            ch.apply(**a)
+        assert text in str(err.value), (change, str(err.value))
+    torch.cuda.synchronize()
+    assert bool((d_out == GUARD).all())
+    # nothing moved: the refused tables and parameters are not in force, the position is 0
+    got, ok = run_device(ch, x3, 100)
+    assert ok and same_bits(got, FM.host_apply(host, plist, host_tables(tables, 3), x3, 0, 100, True))
+    ch.close()

@@ -2,8 +2,11 @@
 """Rate of the channel model (dabgpu_channel_bank_apply, dab-radio_amd/csrc/channel.hip) on one MI355X: N streams x one mode I frame,
 complex float and u8 output, one tap without noise / one tap with noise / four taps with noise, the median of --reps calls timed with
 HIP events; the modulator (dabgpu_ofdm_modulate_frames) on the same number of frames in the same process for comparison.  Algorithmic
-bytes: 16 per sample for complex float out (8 read, 8 written), 10 for u8; shares are of 8 TB/s.
-    python tools/bench_channel.py [--streams 4096] [--reps 30] [--out profiles/tx/bench_channel.md]"""
+bytes: 16 per sample for complex float out (8 read, 8 written), 10 for u8; shares are of 8 TB/s.  Behind them, in the same process, the
+fading kernel (channel_fading.hip): the same four taps all Rayleigh, and two of the four, against the static four-tap rows just measured
+(--fading-out; the ratio is against those rows, never against figures from another machine).
+    python tools/bench_channel.py [--streams 4096] [--reps 30] [--out profiles/tx/bench_channel.md]
+                                  [--fading-out profiles/tx/bench_channel_fading.md] [--doppler-hz 100]"""
 import argparse
 import os
 import sys
@@ -30,6 +33,8 @@ def main():
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tx", "bench_channel.md"))
+    ap.add_argument("--fading-out", default=os.path.join(ROOT, "profiles", "tx", "bench_channel_fading.md"))
+    ap.add_argument("--doppler-hz", type=float, default=100.0)
     a = ap.parse_args()
     import torch
     import dabgpu
@@ -60,6 +65,22 @@ def main():
             gbs = N * S * bps / ms / 1e6
             rows.append((name, label, ms, gbs, gbs / 8000 * 100, ms / t_mod[fmt]))
         ch.close()
+    static4 = {l: ms for n, l, ms, _, _, _ in rows if n == "4 taps, noise"}
+    frows = []
+    streams = [dabgpu.channel_stream(seed=s + 1, **cases[2][1]) for s in range(N)]
+    for name, kinds in (("4 taps, all static kinds, noise", [0, 0, 0, 0]), ("4 taps, 2 Rayleigh, noise", [0, 1, 0, 1]), ("4 taps, 4 Rayleigh, noise", [1, 1, 1, 1])):
+        tables = dabgpu.channel_fading_plan(streams, [dabgpu.channel_fading_spec(a.doppler_hz / 2.048e6, s + 1, kinds) for s in range(N)])
+        ch = dabgpu.Channel(ctx, streams, fading=tables)
+        for fmt, label, bps in ((F32, "f32", 16), (U8, "u8", 10)):
+            ms = median_ms(lambda: ch.apply(frames, S, S, out, in_stride_samples=S, wrap=True, out_format=fmt, u8_scale=scale), a.reps)
+            frows.append((name, label, ms, N * S * bps / ms / 1e6, ms / static4[label]))
+        ch.close()
+    ftext = [f"# Fading channel: {N} streams x one mode I frame ({S} samples), Doppler {a.doppler_hz:g} Hz, median of {a.reps} calls (HIP events)", "",
+             f"Device: {torch.cuda.get_device_properties(0).gcnArchName} ({torch.cuda.get_device_name(0)}).  The yardstick, measured in the same process on "
+             f"the same card: the plain bank's \"4 taps, noise\" rows, {static4['f32']:.3f} ms (f32) and {static4['u8']:.3f} ms (u8).", "",
+             "| case (fading bank) | out | ms / call | GB/s (algorithmic) | x static 4 taps |", "|---|---|---|---|---|"]
+    ftext += [f"| {n} | {l} | {ms:.3f} | {g:.0f} | {r:.2f} |" for n, l, ms, g, r in frows]
+    ftext = "\n".join(ftext) + "\n"
     text = [f"# Channel model: {N} streams x one mode I frame ({S} samples), median of {a.reps} calls (HIP events)", "",
             f"Device: {torch.cuda.get_device_properties(0).gcnArchName} ({torch.cuda.get_device_name(0)}).  Modulator on the same {N} frames: "
             f"{t_mod[F32]:.3f} ms (f32, {N * S * 8 / t_mod[F32] / 1e6 / 80:.1f} % of 8 TB/s written), {t_mod[U8]:.3f} ms (u8).", "",
@@ -69,6 +90,9 @@ def main():
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     open(a.out, "w").write(text)
+    print(ftext)
+    os.makedirs(os.path.dirname(a.fading_out), exist_ok=True)
+    open(a.fading_out, "w").write(ftext)
 
 
 if __name__ == "__main__":

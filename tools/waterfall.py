@@ -5,7 +5,10 @@ input, a noise seed each); every stream is a receiver: dabgpu_ofdm_sync_demod_fr
 noise alone, then two paths (the second 200 samples late at -6 dB) with the same noise.  Multiplex: 48-CU sub-channels at EEP 1-A,
 2-A, 3-A (x 13, the canonical layout's profile) and 4-A plus a 52-CU UEP row (the full canonical 18 x 48 leaves no room for the other
 levels).  SNR = mean power of the modulator's symbols after the taps (1536 x sum |tap|^2) over 2 sigma^2, as the transmitter tool defines it.
-    python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md]"""
+With --doppler-hz (and optionally --profile tu6|ra6|sfn2; default tu6) the channels are replaced by ONE fading channel: the preset's taps
+on a fading bank (dabgpu.Channel(..., fading=)), a fading seed per receiver, SNR against the taps' mean power; give such a run its own --out
+(profiles/tx/waterfall_fading.md).  Without those options the run and its output are the ones of before.
+    python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]"""
 import argparse
 import math
 import os
@@ -27,7 +30,11 @@ def main():
     ap.add_argument("--frames", type=int, default=6)
     ap.add_argument("--snr", default="2:15:1")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tx", "waterfall.md"))
+    ap.add_argument("--doppler-hz", type=float, default=None)
+    ap.add_argument("--profile", default=None)
     a = ap.parse_args()
+    if a.profile is not None and a.doppler_hz is None:
+        ap.error("--profile wants --doppler-hz")
     import numpy as np
     import torch
     import dabgpu
@@ -58,10 +65,17 @@ def main():
             f"(per point: {', '.join(f'{name} {E * (4 * F - 15) * sum(spans[i][1] for i in range(len(subs)) if owner[i] == li)}' for li, (name, _) in enumerate(LEVELS))} bytes).  "
             "No carrier or timing offset.  `python tools/waterfall.py`.", ""]
     verdicts = []
-    for pname, taps in PROFILES:
+    profiles, fading = PROFILES, None
+    if a.doppler_hz is not None:
+        prof = dabgpu.channel_profile(a.profile or "tu6")
+        profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"])]
+        fading = dabgpu.channel_fading_plan([dabgpu.channel_stream(taps=prof["taps"]) for _ in range(E)],
+                                            [dabgpu.channel_fading_spec(a.doppler_hz / 2.048e6, 5000 + e, prof["kinds"], prof["rice_k"], prof["los_cos"])
+                                             for e in range(E)])
+    for pname, taps in profiles:
         h2 = sum(re * re + im * im for _, re, im in taps)
         rows = []
-        ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)])
+        ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
             ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(E)])
