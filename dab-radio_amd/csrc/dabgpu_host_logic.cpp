@@ -961,6 +961,182 @@ dabgpu_channel_geometry dabgpu_host_channel_fading_geometry(dabgpu_channel_geome
     return g;
 }
 
+// ---- resampler (include/dabgpu.h, "Resampler"; the time arithmetic is resample_core.h's, shared with the kernel) ----
+#include "resample_core.h"
+
+namespace {
+
+constexpr double RS_PI = 3.14159265358979323846;
+constexpr double RS_BETA = 9.25;
+
+// I0(x) by its series sum_k ((x / 2)^k / k!)^2
+double rs_bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+// the prototype: sinc(t / M) / M under a Kaiser window of `taps` input samples, zero from the window's edge on
+double rs_prototype(double t, double M, double i0_beta) {
+    const double u = 2.0 * t / (double)DABGPU_RESAMPLE_TAPS;
+    if (!(std::fabs(u) < 1.0)) return 0.0;
+    const double win = rs_bessel_i0(RS_BETA * std::sqrt(1.0 - u * u)) / i0_beta;
+    const double a = RS_PI * t / M;
+    const double sinc = (a == 0.0) ? 1.0 : std::sin(a) / a;
+    return sinc / M * win;
+}
+
+// worst |sum_j c_j e^(2 pi i f (j - taps / 2 + 1 - frac)) - target| over n_f frequencies in [f_lo, f_hi], every phase and three weights
+double rs_table_deviation(const float* table, double f_lo, double f_hi, int n_f, double target) {
+    constexpr int L = DABGPU_RESAMPLE_PHASES, T = DABGPU_RESAMPLE_TAPS;
+    const double weights[3] = {0.0, 0.5, 32767.0 / 32768.0};
+    double worst = 0.0;
+    for (int fi = 0; fi < n_f; fi++) {
+        const double f = f_lo + (f_hi - f_lo) * (double)fi / (double)(n_f - 1);
+        const double step_re = std::cos(2.0 * RS_PI * f), step_im = std::sin(2.0 * RS_PI * f);
+        for (int wi = 0; wi < 3; wi++) {
+            for (int p = 0; p < L; p++) {
+                const double frac = ((double)p + weights[wi]) / (double)L;
+                const double a0 = 2.0 * RS_PI * f * ((double)(1 - T / 2) - frac);
+                double er = std::cos(a0), ei = std::sin(a0), sr = 0.0, si = 0.0;
+                const float* h0 = table + (size_t)p * T;
+                for (int j = 0; j < T; j++) {
+                    const double c = (double)h0[j] + weights[wi] * ((double)h0[T + j] - (double)h0[j]);
+                    sr += c * er; si += c * ei;
+                    const double nr = er * step_re - ei * step_im;
+                    ei = er * step_im + ei * step_re; er = nr;
+                }
+                worst = std::max(worst, std::hypot(sr - target, si));
+            }
+        }
+    }
+    return worst;
+}
+
+int rs_check_stream(const char* who, const dabgpu_resample_stream& P, size_t s, uint64_t max_step_q62) {
+    if (P.step_q62 < (dabgpu::RS_ONE >> 1) || P.step_q62 > (dabgpu::RS_ONE << 1)) {
+        dabgpu_set_error("%s: stream %zu: step %.9g outside [0.5, 2]", who, s, std::ldexp((double)P.step_q62, -62)); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (P.step_q62 > max_step_q62) {
+        dabgpu_set_error("%s: stream %zu: step %.9g above the design's max_step %.9g", who, s, std::ldexp((double)P.step_q62, -62),
+                         std::ldexp((double)max_step_q62, -62));
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite(P.gain)) { dabgpu_set_error("%s: stream %zu: gain is not finite", who, s); return DABGPU_ERR_INVALID_ARG; }
+    if (P.offset_samples > DABGPU_CHANNEL_MAX_POSITION || P.offset_samples < -DABGPU_CHANNEL_MAX_POSITION) {
+        dabgpu_set_error("%s: stream %zu: offset_samples outside +-2^62", who, s); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (P.offset_frac_q62 >= dabgpu::RS_ONE) { dabgpu_set_error("%s: stream %zu: offset_frac_q62 is 2^62 or more", who, s); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+}  // namespace
+
+uint64_t dabgpu_host_resample_max_step_q62(double max_step) {
+    if (!(max_step >= 0.5 && max_step <= 2.0)) return 0;                    // (NaN included)
+    return (uint64_t)std::ceil(std::ldexp(max_step, 62));                   // exact scaling; <= 2^63
+}
+
+extern "C" int dabgpu_resample_design(double max_step, double passband_cycles, dabgpu_resample_filter* out) {
+    constexpr int L = DABGPU_RESAMPLE_PHASES, T = DABGPU_RESAMPLE_TAPS;
+    if (!out) { dabgpu_set_error("resample_design: null result"); return DABGPU_ERR_INVALID_ARG; }
+    if (!(max_step >= 0.5 && max_step <= 2.0)) { dabgpu_set_error("resample_design: max_step %g outside [0.5, 2]", max_step); return DABGPU_ERR_INVALID_ARG; }
+    if (passband_cycles == 0.0) passband_cycles = DABGPU_RESAMPLE_DEFAULT_PASSBAND;
+    if (!(passband_cycles > 0.0 && passband_cycles <= 0.45)) {
+        dabgpu_set_error("resample_design: passband %g cycles outside (0, 0.45]", passband_cycles); return DABGPU_ERR_INVALID_ARG;
+    }
+    const double M = std::max(max_step, 1.0), i0_beta = rs_bessel_i0(RS_BETA);
+    for (int p = 0; p < L; p++) {
+        double row[T], sum = 0.0;
+        for (int j = 0; j < T; j++) { row[j] = rs_prototype((double)p / (double)L + (double)(T / 2 - 1 - j), M, i0_beta); sum += row[j]; }
+        for (int j = 0; j < T; j++) out->table[(size_t)p * T + j] = (float)(row[j] / sum);
+    }
+    out->table[(size_t)L * T] = 0.0f;
+    for (int j = 1; j < T; j++) out->table[(size_t)L * T + j] = out->table[j - 1];
+    out->max_step = max_step; out->passband_cycles = passband_cycles; out->beta = RS_BETA;
+    const double f_pass = passband_cycles / M, f_alias = (1.0 - passband_cycles) / M;
+    out->passband_error = rs_table_deviation(out->table, 0.0, f_pass, 65, 1.0);
+    out->alias_leakage = (f_alias < 0.5) ? rs_table_deviation(out->table, f_alias, 0.5, 65, 0.0) : 0.0;
+    out->error = out->passband_error + out->alias_leakage;
+    return DABGPU_OK;
+}
+
+int dabgpu_host_resample_plan(const char* who, const dabgpu_resample_stream* params, size_t n_streams, uint64_t max_step_q62,
+                              dabgpu_resample_geometry* out) {
+    if (out) *out = dabgpu_resample_geometry{DABGPU_RESAMPLE_BLOCK, 0, 0, 0};
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("%s: %zu streams (1..1048576 are accepted)", who, n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (!params) { dabgpu_set_error("%s: null parameters", who); return DABGPU_ERR_INVALID_ARG; }
+    if (max_step_q62 == 0) { dabgpu_set_error("%s: the design's max_step is outside [0.5, 2]", who); return DABGPU_ERR_INVALID_ARG; }
+    uint64_t step = 0;
+    uint32_t rows = 0;
+    for (size_t s = 0; s < n_streams; s++) {
+        const int st = rs_check_stream(who, params[s], s, max_step_q62);
+        if (st) return st;
+        step = std::max(step, params[s].step_q62);
+        if (!dabgpu::rs_identity(params[s])) rows = std::max(rows, dabgpu::rs_rows_needed(params[s]));
+    }
+    if (out) {
+        out->window_samples = (uint32_t)((step + (((uint64_t)1 << 52) - 1)) >> 52) + DABGPU_RESAMPLE_TAPS + 2u;       // ceil(1024 step) + taps + 2
+        out->table_rows = rows;
+        out->lds_bytes = ((out->window_samples + 1u) & ~1u) * 8u + rows * (DABGPU_RESAMPLE_TAPS + 1u) * 4u;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_resample_fits(const dabgpu_resample_geometry& created, const dabgpu_resample_geometry& wanted) {
+    if (wanted.window_samples > created.window_samples) {
+        dabgpu_set_error("resample_bank_set_params: largest step needs a window of %u samples, the bank was created with %u", wanted.window_samples,
+                         created.window_samples);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (wanted.table_rows > created.table_rows) {
+        dabgpu_set_error("resample_bank_set_params: these steps touch %u table rows per block, the bank was created for %u (create the bank with "
+                         "its widest parameters)", wanted.table_rows, created.table_rows);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_resample_plan(const dabgpu_resample_stream* params, size_t n_streams, const dabgpu_resample_filter* design,
+                                    dabgpu_resample_geometry* out) {
+    if (out) *out = dabgpu_resample_geometry{DABGPU_RESAMPLE_BLOCK, 0, 0, 0};
+    if (!design) { dabgpu_set_error("resample_plan: null design"); return DABGPU_ERR_INVALID_ARG; }
+    return dabgpu_host_resample_plan("resample_plan", params, n_streams, dabgpu_host_resample_max_step_q62(design->max_step), out);
+}
+
+extern "C" uint64_t dabgpu_resample_step_q62(double in_rate_hz, double out_rate_hz, double ppm) {
+    if (!(in_rate_hz > 0.0) || !(out_rate_hz > 0.0) || !std::isfinite(ppm)) return 0;
+    const double step = in_rate_hz / out_rate_hz * (1.0 + ppm * 1e-6);
+    if (!(step > 0.0 && step < 4.0)) return 0;
+    return (uint64_t)std::nearbyint(std::ldexp(step, 62));                  // exact scaling, below 2^64
+}
+
+extern "C" double dabgpu_resample_step(uint64_t step_q62) { return std::ldexp((double)step_q62, -62); }
+
+extern "C" int dabgpu_resample_input_needed(const dabgpu_resample_stream* params, uint64_t position, size_t n_out, int64_t* first, uint64_t* count) {
+    if (!params || !first || !count) { dabgpu_set_error("resample_input_needed: null parameters / result"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = rs_check_stream("resample_input_needed", *params, 0, dabgpu::RS_ONE << 1);
+    if (st) return st;
+    if (position > (uint64_t)DABGPU_CHANNEL_MAX_POSITION || n_out > ((size_t)1 << 31)) {
+        dabgpu_set_error("resample_input_needed: position above 2^62 or more than 2^31 samples"); return DABGPU_ERR_INVALID_ARG;
+    }
+    *first = 0; *count = 0;
+    if (n_out == 0) return DABGPU_OK;
+    const bool ident = dabgpu::rs_identity(*params);
+    const uint64_t before = ident ? 0u : (uint64_t)(DABGPU_RESAMPLE_TAPS / 2 - 1), after = ident ? 0u : (uint64_t)(DABGPU_RESAMPLE_TAPS / 2);
+    const dabgpu::RsIndex a = dabgpu::rs_before(dabgpu::rs_index(dabgpu::rs_time(*params, position)), before);
+    const dabgpu::RsIndex b = dabgpu::rs_after(dabgpu::rs_index(dabgpu::rs_time(*params, position + (n_out - 1))), after);
+    if (!b.neg && (b.n >> 63)) { dabgpu_set_error("resample_input_needed: the span ends above 2^63"); return DABGPU_ERR_INVALID_ARG; }
+    *first = (int64_t)a.n;
+    *count = b.n - a.n + 1;
+    return DABGPU_OK;
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

@@ -248,6 +248,15 @@ int dabgpu_host_channel_fading_check(const char* who, const dabgpu_channel_strea
 // the geometry of a fading bank from the plain one: always staged, the tile's grid gains behind the staged input
 dabgpu_channel_geometry dabgpu_host_channel_fading_geometry(dabgpu_channel_geometry plain);
 
+// ---- resampler planner (resample.hip launches from it; include/dabgpu.h, dabgpu_resample_plan) ----
+// DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream index, field); `who` names the entry point.
+// max_step_q62: the largest step the bank's design serves (dabgpu_host_resample_max_step_q62 of its max_step)
+int dabgpu_host_resample_plan(const char* who, const dabgpu_resample_stream* params, size_t n_streams, uint64_t max_step_q62,
+                              dabgpu_resample_geometry* out);
+uint64_t dabgpu_host_resample_max_step_q62(double max_step);       // max_step rounded UP to Q2.62, within [2^61, 2^63]; 0: not a valid max_step
+// dabgpu_resample_bank_set_params: new parameters must fit the window and the table rows of the bank's creation
+int dabgpu_host_resample_fits(const dabgpu_resample_geometry& created, const dabgpu_resample_geometry& wanted);
+
 // ---- DAB+ super-frame encoder (dabplus_tx.hip; include/dabgpu.h, dabgpu_dabplus_superframe_layout) ----
 // Where the access units of a super frame start (ETSI TS 102 563 5.2, as AAC_Frame_Processor reads it back, aac_frame_processor.cpp:266-283),
 // one body for the host entry point and the kernel.  au_len: the first num_aus entries are read; start[0 .. num_aus] are written, the rest

@@ -77,6 +77,9 @@ ABI_SYMBOLS = [
     "dabgpu_channel_bank_set_params", "dabgpu_channel_bank_seek", "dabgpu_channel_bank_apply", "dabgpu_channel_bank_apply_host_sync",
     "dabgpu_channel_fading_plan", "dabgpu_channel_fading_gain_host", "dabgpu_channel_profile", "dabgpu_channel_bank_create_fading",
     "dabgpu_channel_bank_set_fading", "dabgpu_channel_plan_fading",
+    "dabgpu_resample_design", "dabgpu_resample_plan", "dabgpu_resample_step_q62", "dabgpu_resample_step", "dabgpu_resample_input_needed",
+    "dabgpu_resample_bank_create", "dabgpu_resample_bank_destroy", "dabgpu_resample_bank_set_params", "dabgpu_resample_bank_seek",
+    "dabgpu_resample_bank_apply", "dabgpu_resample_bank_apply_host_sync",
     "dabgpu_tii_cfg_default", "dabgpu_tii_pattern", "dabgpu_tii_main_id", "dabgpu_tii_carriers", "dabgpu_tii_validate",
     "dabgpu_ofdm_modulate_frames_tii", "dabgpu_ofdm_modulate_frames_tii_host_sync",
     "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
@@ -87,6 +90,12 @@ ABI_SYMBOLS = [
 CHANNEL_MAX_TAPS = 8
 CHANNEL_MAX_DELAY = 2047
 CHANNEL_BLOCK = 1024
+
+# resampler (include/dabgpu.h)
+RESAMPLE_PHASES = 256
+RESAMPLE_TAPS = 48
+RESAMPLE_BLOCK = 1024
+RESAMPLE_DEFAULT_PASSBAND = 0.375
 
 # TII (include/dabgpu.h)
 TII_MAX_TX = 4
@@ -171,6 +180,23 @@ FADING_OSC, FADING_GRID, FADING_MAX_DOPPLER_CYCLES = 17, 64, 2.0 ** -11
 class ChannelGeometry(C.Structure):
     """dabgpu_channel_geometry"""
     _fields_ = [("halo", C.c_uint32), ("block_samples", C.c_uint32), ("lds_bytes", C.c_uint32), ("staged", C.c_uint32)]
+
+
+class ResampleStream(C.Structure):
+    """dabgpu_resample_stream"""
+    _fields_ = [("step_q62", C.c_uint64), ("offset_samples", C.c_int64), ("offset_frac_q62", C.c_uint64), ("gain", C.c_float), ("reserved", C.c_int32)]
+
+
+class ResampleFilter(C.Structure):
+    """dabgpu_resample_filter: the design record (its error figures) and the (L + 1) x taps table"""
+    _fields_ = [("max_step", C.c_double), ("passband_cycles", C.c_double), ("beta", C.c_double),
+                ("passband_error", C.c_double), ("alias_leakage", C.c_double), ("error", C.c_double),
+                ("table", C.c_float * ((RESAMPLE_PHASES + 1) * RESAMPLE_TAPS))]
+
+
+class ResampleGeometry(C.Structure):
+    """dabgpu_resample_geometry"""
+    _fields_ = [("block_samples", C.c_uint32), ("window_samples", C.c_uint32), ("table_rows", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
 class SyncCfg(C.Structure):
@@ -368,6 +394,22 @@ def lib():
         L.dabgpu_channel_profile.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
         L.dabgpu_channel_bank_create_fading.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.dabgpu_channel_bank_set_fading.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_resample_design.argtypes = [C.c_double, C.c_double, C.c_void_p]
+        L.dabgpu_resample_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dabgpu_resample_step_q62.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.dabgpu_resample_step_q62.restype = C.c_uint64
+        L.dabgpu_resample_step.argtypes = [C.c_uint64]
+        L.dabgpu_resample_step.restype = C.c_double
+        L.dabgpu_resample_input_needed.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.dabgpu_resample_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_resample_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_resample_bank_destroy.restype = None
+        L.dabgpu_resample_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_resample_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_resample_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t,
+                                                 C.c_float, C.c_void_p]
+        L.dabgpu_resample_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                                                           C.c_size_t, C.c_float]
         L.dabgpu_channel_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
                                                           C.c_size_t, C.c_float]
         L.dabgpu_tii_cfg_default.argtypes = [C.c_void_p]
@@ -982,6 +1024,105 @@ class Channel:
         out = np.zeros((self.n, stride), np.uint8)
         check(lib().dabgpu_channel_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
                                                         float(u8_scale)), "dabgpu_channel_bank_apply_host_sync")
+        out = out[:, :n_out * sb]
+        return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+
+
+def resample_step(in_rate_hz=2048000.0, out_rate_hz=2048000.0, ppm=0.0):
+    """dabgpu_resample_step_q62: in / out * (1 + ppm * 1e-6) as the nearest Q2.62 word (input samples per output sample); 0: not representable"""
+    return int(lib().dabgpu_resample_step_q62(float(in_rate_hz), float(out_rate_hz), float(ppm)))
+
+
+def resample_stream(step_q62=1 << 62, offset=0.0, offset_samples=0, offset_frac_q62=None, gain=1.0):
+    """a ResampleStream: step_q62 from resample_step; the offset as offset_samples + a fraction (`offset`, a float in input samples, is split
+    into floor and fraction) or as the exact word offset_frac_q62"""
+    import math
+    P = ResampleStream()
+    whole = math.floor(offset)
+    P.step_q62 = int(step_q62)
+    P.offset_samples = int(offset_samples) + whole
+    P.offset_frac_q62 = min(int(round((offset - whole) * 2.0 ** 62)), (1 << 62) - 1) if offset_frac_q62 is None else int(offset_frac_q62)
+    P.gain = gain
+    return P
+
+
+def resample_design(max_step=1.0, passband_cycles=0.0):
+    """dabgpu_resample_design (host only): a ResampleFilter -- the table for steps up to max_step and the error figures it was found to have"""
+    D = ResampleFilter()
+    check(lib().dabgpu_resample_design(float(max_step), float(passband_cycles), C.byref(D)), "dabgpu_resample_design")
+    return D
+
+
+def resample_plan(streams, design):
+    """dabgpu_resample_plan (host only): {"block_samples", "window_samples", "table_rows", "lds_bytes"}; raises DabGpuError"""
+    n = len(streams)
+    arr = (ResampleStream * n)(*streams) if n else None
+    g = ResampleGeometry()
+    check(lib().dabgpu_resample_plan(arr, n, C.byref(design) if design is not None else None, C.byref(g)), "dabgpu_resample_plan")
+    return {"block_samples": g.block_samples, "window_samples": g.window_samples, "table_rows": g.table_rows, "lds_bytes": g.lds_bytes}
+
+
+def resample_input_needed(stream, position, n_out):
+    """dabgpu_resample_input_needed: (first, count) of the input indices a call of n_out samples at `position` reads for one stream"""
+    first, count = C.c_int64(), C.c_uint64()
+    check(lib().dabgpu_resample_input_needed(C.byref(stream), int(position), int(n_out), C.byref(first), C.byref(count)), "dabgpu_resample_input_needed")
+    return first.value, count.value
+
+
+class Resampler:
+    """dabgpu_resample_bank: arbitrary-ratio, fractional-delay resampling of n streams (a sampling-clock error, a capture rate); the stream
+    position lives on the device.  design = None: a table for the largest step of `params` (at least 1), default passband"""
+
+    def __init__(self, ctx, params, design=None):
+        self._ctx = ctx
+        self.n = len(params)
+        if design is None:
+            import math
+            widest = max([1.0] + [p.step_q62 * 2.0 ** -62 for p in params])               # (a double holds 53 of the word's bits: round up)
+            design = resample_design(min(math.nextafter(widest, 4.0), 2.0) if widest > 1.0 else 1.0)
+        self.design = design
+        self.plan = resample_plan(params, design)
+        arr = (ResampleStream * self.n)(*params)
+        self._h = C.c_void_p()
+        check(lib().dabgpu_resample_bank_create(ctx._h, self.n, arr, C.byref(design), C.byref(self._h)), "dabgpu_resample_bank_create")
+
+    def close(self):
+        if self._h:
+            lib().dabgpu_resample_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, params, stream=None):
+        assert len(params) == self.n
+        arr = (ResampleStream * self.n)(*params)
+        check(lib().dabgpu_resample_bank_set_params(self._h, arr, Context._stream(stream)), "dabgpu_resample_bank_set_params")
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_resample_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_resample_bank_seek")
+
+    def apply(self, d_in, n_in, n_out, d_out, in_stride_samples=0, wrap=False, out_format=None, out_stride_bytes=0, u8_scale=1.0, stream=None):
+        """d_in complex float (device) -> d_out rows of n_out samples, complex float (default) or u8 pairs; asynchronous"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_resample_bank_apply(self._h, _ptr(d_in), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(d_out), fmt, out_stride_bytes,
+                                               float(u8_scale), Context._stream(stream)), "dabgpu_resample_bank_apply")
+
+    def apply_host(self, h_in, n_out, in_stride_samples=0, wrap=False, out_format=None, u8_scale=1.0):
+        """dabgpu_resample_bank_apply_host_sync: h_in complex64 [n_in] (shared, in_stride_samples = 0) or [n][n_in] with in_stride_samples =
+        n_in, on the host -> [n][n_out] complex64, or [n][n_out][2] uint8 for the u8 format; returns when the output is there"""
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        x = np.ascontiguousarray(h_in, dtype=np.complex64)
+        n_in = x.shape[-1]
+        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
+        stride = (n_out * sb + 15) & ~15
+        out = np.zeros((self.n, stride), np.uint8)
+        check(lib().dabgpu_resample_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
+                                                         float(u8_scale)), "dabgpu_resample_bank_apply_host_sync")
         out = out[:, :n_out * sb]
         return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
 

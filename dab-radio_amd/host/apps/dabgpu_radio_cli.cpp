@@ -19,6 +19,10 @@
 // The reader must not overwrite the buffer's head while the observer reads it, so with --tii every Process() call is followed by
 // Synchronize() and --ofdm-block-size may not exceed one frame less a NULL period.
 //
+// --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
+// Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
+// not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
+//
 // Output files are byte-for-byte what the reference writes with the same options (frame bits: 230400 int8 per frame,
 // or 28800 bytes per frame with --ofdm-output-hard-bytes, LSB first).
 #include <stdio.h>
@@ -35,6 +39,7 @@
 #include "dab/constants/dab_parameters.h"
 #include "dab/fic/fic_decoder.h"
 #include "dab/msc/msc_decoder.h"
+#include "dab/tx/dab_resampler.h"
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
 
@@ -55,6 +60,7 @@ struct Args {
     std::vector<Subchannel> subchannels;
     bool tii = false;
     int tii_frames = 8;
+    double input_rate = 2.048e6;
 };
 
 static void usage(const char* argv0) {
@@ -64,7 +70,7 @@ static void usage(const char* argv0) {
         "  [--ofdm-enable-output] [--ofdm-output FILE] [--ofdm-output-hard-bytes]\n"
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
-        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N]\n"
+        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -127,12 +133,16 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--radio-subchannel") { const auto v = value(); args.subchannels.push_back(parse_subchannel(v, args.subchannels.size())); }
         else if (a == "--tii") args.tii = true;
         else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
+        else if (a == "--input-rate") args.input_rate = std::stod(value());
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
+    if (!(args.input_rate >= 1.024e6 && args.input_rate <= 4.096e6)) throw std::runtime_error("--input-rate: 1024000 .. 4096000 samples per second");
+    if (args.input_rate != 2.048e6 && !args.is_ofdm_used) throw std::runtime_error("--input-rate needs the OFDM stage");
+    if (args.input_rate != 2.048e6 && args.tii) throw std::runtime_error("--input-rate is not available with --tii (resampled blocks may exceed --ofdm-block-size)");
     if (args.transmission_mode != 1) throw std::runtime_error("only transmission mode I is implemented");
     if (args.ofdm_block_size == 0) throw std::runtime_error("--ofdm-block-size must be positive");
     return true;
@@ -254,9 +264,17 @@ static int run(const Args& args) {
             if (radio) radio->Process(bits);
         });
         std::vector<std::complex<float>> block(args.ofdm_block_size);               // OFDM_Block::run, app_ofdm_blocks.h:45-57
+        std::unique_ptr<DAB_Stream_Resampler> resampler;
+        std::vector<std::complex<float>> resampled;
+        if (args.input_rate != 2.048e6) resampler = std::make_unique<DAB_Stream_Resampler>(DAB_Resampler::StepWord(args.input_rate, 2.048e6));
         for (;;) {
             const size_t length = reader->read(block);
             if (length == 0) break;
+            if (resampler) {
+                resampled.clear();
+                resampler->Process(tcb::span<const std::complex<float>>(block.data(), length), resampled);
+                if (!resampled.empty()) demod->Process(resampled);
+            } else
             demod->Process(tcb::span<const std::complex<float>>(block.data(), length));
             if (tii) demod->Synchronize();                                          // the observer reads the head of the correlation buffer
             if (length != block.size()) break;

@@ -22,6 +22,11 @@
 //   --timing-offset N              the signal N samples late (N >= 0 with channel-coded frames: they are produced one at a time)
 //   --tap DELAY:RE:IM              repeatable, up to 8; delay in samples 0..2047; default one tap 0:1:0
 //   --noise-seed N                 default 1
+// Resampler (include/dabgpu.h "Resampler", DAB_Stream_Resampler): behind the channel, so that the noise is resampled too, as at a receiver's ADC.
+//   --output-rate HZ               samples per second of the output (default 2048000; 1024000 .. 4096000), e.g. 2400000 for a tuner's capture
+//   --clock-ppm X                  the ADC's sample period X ppm longer than nominal: step = 2048000 / HZ * (1 + X 1e-6) input samples per output
+//   --frac-delay D                 the samples taken D of a 2.048 MHz sample late, 0 <= D < 1
+// With any of them a frame's worth of input gives about 196608 / step samples; the last taps of a frame's last samples come with the next frame.
 // Fading (include/dabgpu.h "Channel model, fading taps", DAB_Channel_Model::SetFading): taps with a Rayleigh or Rice gain and Doppler.
 //   --doppler-hz F                 maximum Doppler shift, 0..1000 Hz; with it every tap fades (Rayleigh) unless --tap-kind says otherwise
 //   --fading-seed S                default 1
@@ -47,6 +52,7 @@
 
 #include "dab/dabgpu_shared_context.h"
 #include "dab/tx/dab_channel_model.h"
+#include "dab/tx/dab_resampler.h"
 #include "dabgpu.h"
 #include "ofdm/dab_ofdm_params_ref.h"
 #include "ofdm/dab_prs_ref.h"
@@ -92,7 +98,27 @@ struct Args {
     struct TapKind { int tap; int kind; float rice_k; };
     std::vector<TapKind> tap_kinds;
     std::vector<dabgpu_tii_tx> tii;
+    // resampler: behind the channel
+    bool resample = false;
+    double clock_ppm = 0.0, frac_delay = 0.0, output_rate = 2.048e6;
 };
+
+// the receiver's ADC behind the channel (include/dabgpu.h "Resampler"): --output-rate HZ samples per second, its sample period --clock-ppm
+// longer than nominal, the samples taken --frac-delay of a 2.048 MHz sample late
+static std::unique_ptr<DAB_Stream_Resampler> make_resampler(const Args& args) {
+    if (!args.resample) return nullptr;
+    const uint64_t step = DAB_Resampler::StepWord(2.048e6, args.output_rate, args.clock_ppm);
+    if (step == 0) throw std::runtime_error("--output-rate / --clock-ppm: not a sample rate");
+    return std::make_unique<DAB_Stream_Resampler>(step, args.frac_delay);
+}
+// one frame of the 2.048 MHz stream through the resampler to the file; false when a write fails
+static bool write_resampled(DAB_Stream_Resampler& rs, tcb::span<const std::complex<float>> frame, float u8_scale, std::vector<uint8_t>& bytes, FILE* fp_out) {
+    bytes.clear();
+    rs.ProcessU8(frame, bytes, u8_scale);
+    const size_t nb_write = fwrite(bytes.data(), 2, bytes.size() / 2, fp_out);
+    if (nb_write != bytes.size() / 2) { fprintf(stderr, "Failed to write out frame %zu/%zu\n", nb_write, bytes.size() / 2); return false; }
+    return true;
+}
 
 // the channel's parameters for a mode with nb_carriers data carriers
 static dabgpu_channel_stream channel_params(const Args& args, int nb_carriers) {
@@ -235,6 +261,8 @@ static int run_coded(const Args& args, FILE* fp_out) {
         if (fading_spec(args, cp, spec)) channel->SetFading(spec);
         window.assign(2 * S, std::complex<float>(0.0f, 0.0f));
     }
+    auto resampler = make_resampler(args);
+    std::vector<std::complex<float>> impaired(resampler ? S : 0);
     const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
     int rc = 0;
     for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
@@ -247,11 +275,16 @@ static int run_coded(const Args& args, FILE* fp_out) {
                 dabgpu_channel_stream now = cp;
                 now.start = cp.start + (k - 1) * (long long)S;             // window sample 0 = stream sample (k - 1) S
                 channel->SetParams(now);
-                channel->ApplyU8(quantised, window, false, u8_scale);
+                if (resampler) channel->Apply(impaired, window, false);
+                else channel->ApplyU8(quantised, window, false, u8_scale);
             }
         } else
         st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
         if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); rc = 1; break; }
+        if (resampler) {
+            if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
+            continue;
+        }
         const size_t nb_write = fwrite(quantised.data(), 2, DABGPU_NB_FRAME_SAMPLES, fp_out);
         if (nb_write != DABGPU_NB_FRAME_SAMPLES) { fprintf(stderr, "Failed to write out frame %zu/%d\n", nb_write, DABGPU_NB_FRAME_SAMPLES); break; }
     }
@@ -264,6 +297,7 @@ static void usage(const char* argv0) {
                     "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
                     "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N] [--tii P:C[:AMP]]...\n"
                     "          [--doppler-hz F] [--fading-seed S] [--profile tu6|ra6|sfn2] [--tap-kind K:static|rayleigh|rice:KDB]...\n"
+                    "          [--clock-ppm X] [--frac-delay D] [--output-rate HZ]\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
                     "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
@@ -272,6 +306,8 @@ static void usage(const char* argv0) {
                     "(the mean power of the modulator's symbols after the taps; the NULL period is not counted);\n"
                     "with --doppler-hz F (0..1000) the taps fade (Rayleigh; --tap-kind sets single taps static or Rice with a factor in dB,\n"
                     "--profile takes taps and kinds from a preset as recalled from COST 207), unit mean power each, seeded by --fading-seed;\n"
+                    "with --clock-ppm X / --frac-delay D / --output-rate HZ the signal is resampled behind the channel (the noise too, as at a\n"
+                    "receiver's ADC): HZ samples per second (default 2048000), every sample period X ppm longer, D of a sample late;\n"
                     "with --tii (mode I, up to 4) the NULL period of every other frame carries those transmitters' identification\n", argv0);
 }
 
@@ -300,8 +336,18 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--profile") { args.profile = value(); args.channel = true; }
         else if (a == "--tap-kind") { args.tap_kinds.push_back(parse_tap_kind(value())); args.channel = true; }
         else if (a == "--tii") args.tii.push_back(parse_tii(value()));
+        else if (a == "--clock-ppm") { args.clock_ppm = std::stod(value()); args.resample = true; }
+        else if (a == "--frac-delay") { args.frac_delay = std::stod(value()); args.resample = true; }
+        else if (a == "--output-rate") { args.output_rate = std::stod(value()); args.resample = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
+    }
+    if (args.resample) {
+        // the resampler stands behind the channel: without channel options that is the identity channel, which returns its input bit for bit
+        args.channel = true;
+        if (!(args.frac_delay >= 0.0 && args.frac_delay < 1.0)) throw std::runtime_error("--frac-delay is a fraction of a sample: 0 <= D < 1");
+        if (!(args.output_rate >= 1.024e6 && args.output_rate <= 4.096e6)) throw std::runtime_error("--output-rate: 1024000 .. 4096000");
+        if (!(std::fabs(args.clock_ppm) <= 1000.0)) throw std::runtime_error("--clock-ppm: -1000 .. 1000");
     }
     if (!args.profile.empty() && !args.taps.empty()) throw std::runtime_error("--profile is not available with --tap");
     if (args.tii.size() > DABGPU_TII_MAX_TX) throw std::runtime_error("--tii: at most 4 transmitters");
@@ -380,7 +426,14 @@ int main(int argc, char** argv) {
             dabgpu_channel_fading_spec spec;
             if (fading_spec(args, cp, spec)) channel.SetFading(spec);
             const float u8_scale = (1.0f / (float)params.nb_data_carriers * 4.0f) * 127.5f;
+            auto resampler = make_resampler(args);
+            std::vector<std::complex<float>> impaired(resampler ? frame_size : 0);
             for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
+                if (resampler) {
+                    channel.Apply(impaired, frame, true);
+                    if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
+                    continue;
+                }
                 channel.ApplyU8(quantised, frame, true, u8_scale);
                 const size_t nb_write = fwrite(quantised.data(), 2, frame_size, fp_out);
                 if (nb_write != frame_size) {

@@ -1123,6 +1123,100 @@ int dabgpu_channel_bank_create_fading(dabgpu_ctx *ctx, size_t n_streams, const d
 int dabgpu_channel_bank_set_fading(dabgpu_channel_bank *bank, const dabgpu_channel_fading_stream *h_tables, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Resampler: arbitrary-ratio, fractional-delay resampling of n_streams independent streams of complex float samples -- a receiver's
+ * sampling-clock error and fractional delay behind the channel model, and captures at 2.4, 2.56, 3.072 or 4.096 MS/s brought to the 2.048 MHz
+ * grid in front of the demodulator.  The reference has nothing comparable; the definition is this library's own, written once in
+ * dab-radio_amd/csrc/resample_core.h for the kernel (resample.hip) and for the host model the tests build from the same header, pinned to
+ * an independent numpy model (tests/resample_model.py, tests/test_resample_model.py) and on the device bit for bit to the host model
+ * (tests/test_gpu_resample.py).  Error bounds and measurements: DESIGN.md 4.19.
+ *
+ * For stream s, absolute output sample m (the bank's 64-bit position + the sample's index in the call) and input x[0 .. n_in):
+ *   T(m)   = offset_q62 + m * step_q62 in exact integer arithmetic, in units of 2^-62 input samples; step_q62 is unsigned Q2.62 (input
+ *            samples per output sample, 0.5 .. 2), offset_q62 = offset_samples * 2^62 + offset_frac_q62 is signed: offset_samples any
+ *            integer up to +-2^62, offset_frac_q62 in [0, 2^62).  The value is 128 bits wide and depends on (parameters, m) alone: a call
+ *            with a + b samples equals a call with a and then one with b on the same d_in and n_in, at any split.
+ *   n, p, w  n = floor(T / 2^62); the phase row p = the top 8 bits of the fraction (DABGPU_RESAMPLE_PHASES = 256 rows); w = the next 15
+ *            bits over 2^15
+ *   c_j    = fmaf(w, H[p + 1][j] - H[p][j], H[p][j]), j = 0 .. DABGPU_RESAMPLE_TAPS - 1: H is the design's table of L + 1 rows, row L
+ *            being row 0 advanced by one input sample.  The interpolated form IS the definition.
+ *   y      = gain * sum_j c_j * x[n - taps / 2 + 1 + j], re and im separate, each one chain in ascending j that starts from the product
+ *            c_0 * x and continues with fmaf(c_j, x, sum).  wrap != 0: the index is taken modulo n_in (a transmission that repeats);
+ *            wrap = 0: samples outside the input are 0.  The output is complex float or the u8 pairs of the modulator's quantiser.
+ *   identity  step_q62 = 2^62 with offset_frac_q62 = 0 takes no filter: y = gain * x[n], the shifted input bit for bit at gain 1.
+ *
+ * dabgpu_resample_design (host only): the (L + 1) x taps float table of a Kaiser-windowed sinc (beta = 9.25, I0 by its series, everything
+ * in double) for steps up to max_step (0.5 .. 2).  With M = max(max_step, 1): h(t) = sinc(t / M) / M * kaiser(t), zero for |t| >= taps / 2,
+ * H[p][j] = h(p / L + taps / 2 - 1 - j), every row p < L divided by its sum (DC gain 1 per phase), H[L][j] = H[0][j - 1], H[L][0] = 0.
+ * passband_cycles (0 = the default 0.375, the +-768 kHz of a DAB block at 2.048 MHz; accepted: (0, 0.45]) is the passband edge in cycles
+ * per sample of the SLOWER of the two rates: per output sample for max_step >= 1, per input sample below (where 0.375 cycles per output
+ * sample would lie above the input's own Nyquist frequency).  In cycles per input sample the passband ends at passband / M, the first alias
+ * of it begins at (1 - passband) / M and the cutoff 0.5 / M lies half way.  The function RETURNS the table's own error, evaluated in double
+ * over frequencies x all phases x w in {0, 1/2, 1 - 2^-15}:
+ *   passband_error   worst |sum_j c_j e^(2 pi i f (j - taps / 2 + 1 - frac)) - 1| over 65 frequencies f in [0, passband / M]
+ *   alias_leakage    worst |the same sum| over 65 frequencies in [(1 - passband) / M, 0.5] (0 where that interval is empty: M <= 1.25)
+ *   error            their sum; 1e-4 (-80 dB) or better for every max_step in [0.5, 2] at the default passband
+ * A bank has one table; a stream may use it when its step does not exceed the design's max_step (a smaller step keeps the passband in
+ * input cycles, which is narrower in its own output cycles).
+ *
+ * dabgpu_resample_plan (host only): checks a parameter list against a design and returns the launch geometry.  Refused with
+ * DABGPU_ERR_INVALID_ARG: a null pointer, n_streams outside 1..1048576, a step outside [0.5, 2] or above the design's max_step (rounded up
+ * to Q2.62), gain not finite, |offset_samples| above DABGPU_CHANNEL_MAX_POSITION, offset_frac_q62 >= 2^62.
+ *   block_samples   output samples one workgroup produces (DABGPU_RESAMPLE_BLOCK)
+ *   window_samples  input window of a workgroup: ceil(block_samples * largest step) + taps + 2
+ *   table_rows      table rows a workgroup stages: what a block of the fastest-drifting stream can touch, at most L + 1 (the whole table);
+ *                   a step within a few hundred ppm of 1 needs a handful
+ *   lds_bytes       (window_samples rounded up to even) * 8 + table_rows * (taps + 1) * 4
+ * dabgpu_resample_step_q62(in_rate_hz, out_rate_hz, ppm): in / out * (1 + ppm * 1e-6) rounded to the nearest Q2.62 value (0 for NaN,
+ * rates that are not positive, or a result outside (0, 4)); dabgpu_resample_step is its inverse as a double.
+ * dabgpu_resample_input_needed: the span [*first, *first + *count) of input indices that a call of n_out samples at `position` reads for
+ * ONE stream (before wrap or zero-fill; *first may be negative), so that callers can size windows; *count = 0 for n_out = 0. */
+#define DABGPU_RESAMPLE_PHASES 256
+#define DABGPU_RESAMPLE_PHASE_BITS 8
+#define DABGPU_RESAMPLE_TAPS 48
+#define DABGPU_RESAMPLE_BLOCK 1024
+#define DABGPU_RESAMPLE_DEFAULT_PASSBAND 0.375
+typedef struct {
+    uint64_t step_q62;
+    int64_t offset_samples;
+    uint64_t offset_frac_q62;
+    float gain;
+    int32_t reserved;
+} dabgpu_resample_stream;
+typedef struct {
+    double max_step, passband_cycles, beta;
+    double passband_error, alias_leakage, error;
+    float table[(DABGPU_RESAMPLE_PHASES + 1) * DABGPU_RESAMPLE_TAPS];
+} dabgpu_resample_filter;
+typedef struct { uint32_t block_samples, window_samples, table_rows, lds_bytes; } dabgpu_resample_geometry;
+int dabgpu_resample_design(double max_step, double passband_cycles, dabgpu_resample_filter *out);
+int dabgpu_resample_plan(const dabgpu_resample_stream *params, size_t n_streams, const dabgpu_resample_filter *design,
+                         dabgpu_resample_geometry *out);
+uint64_t dabgpu_resample_step_q62(double in_rate_hz, double out_rate_hz, double ppm);
+double dabgpu_resample_step(uint64_t step_q62);
+int dabgpu_resample_input_needed(const dabgpu_resample_stream *params, uint64_t position, size_t n_out, int64_t *first, uint64_t *count);
+
+/* Resampler bank: the parameters of n_streams streams, the design's table and the streams' common position on the device.  The contract
+ * is the channel bank's, point for point: d_in with a stride (even, >= n_in) or shared (0), d_in and d_out 16-byte aligned, out_stride_bytes
+ * 0 or a multiple of 16 that holds n_out samples, complex float (DABGPU_IQ_RAW_F32L) or u8 pairs with u8_scale (DABGPU_IQ_RAW_U8); nothing
+ * else is written.  A call is two launches on `stream` -- the resampling kernel, then a one-thread kernel that adds n_out to the position
+ * -- and changes no host state, so it may be captured in a HIP graph; replays continue the stream.  _seek sets the position (0 at
+ * creation, at most DABGPU_CHANNEL_MAX_POSITION), _set_params replaces all parameters; both are ordered on `stream`.  The geometry is
+ * fixed when the bank is created: _set_params refuses (DABGPU_ERR_INVALID_ARG) parameters that need a larger window or more table rows, or
+ * a step above the design's max_step.  Streams of one launch may have different steps.  Arguments are checked before any device call
+ * (dabgpu_host_logic.cpp; tests/test_resample_plan.py, tests/cpp/resample_plan_fuzz.cpp, tests/test_gpu_resample.py). */
+typedef struct dabgpu_resample_bank dabgpu_resample_bank;
+int dabgpu_resample_bank_create(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_resample_stream *h_params,
+                                const dabgpu_resample_filter *design, dabgpu_resample_bank **out);
+void dabgpu_resample_bank_destroy(dabgpu_resample_bank *bank);
+int dabgpu_resample_bank_set_params(dabgpu_resample_bank *bank, const dabgpu_resample_stream *h_params, void *stream);
+int dabgpu_resample_bank_seek(dabgpu_resample_bank *bank, uint64_t position, void *stream);
+int dabgpu_resample_bank_apply(dabgpu_resample_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
+                               void *d_out, int out_format, size_t out_stride_bytes, float u8_scale, void *stream);
+/* the same from and to host memory on the context's stream, with the rules of dabgpu_channel_bank_apply_host_sync */
+int dabgpu_resample_bank_apply_host_sync(dabgpu_resample_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_in, int wrap,
+                                         size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * TII: transmitter identification information in the NULL symbol of mode I, both directions (every other mode returns
  * DABGPU_ERR_INVALID_ARG).  The reference has no TII code; this section is the definition.  It is EN 300 401 clause 14.8.1 as recalled:
  * THE NUMBERING OF p FOLLOWS THE TABLE BELOW AND HAS NOT BEEN CHECKED AGAINST TABLE 38 of the standard.

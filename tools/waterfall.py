@@ -8,7 +8,11 @@ levels).  SNR = mean power of the modulator's symbols after the taps (1536 x sum
 With --doppler-hz (and optionally --profile tu6|ra6|sfn2; default tu6) the channels are replaced by ONE fading channel: the preset's taps
 on a fading bank (dabgpu.Channel(..., fading=)), a fading seed per receiver, SNR against the taps' mean power; give such a run its own --out
 (profiles/tx/waterfall_fading.md).  Without those options the run and its output are the ones of before.
-    python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]"""
+With --clock-ppm X[,Y...] the run is the white-noise channel followed by the resampler (dabgpu.Resampler behind dabgpu.Channel: the noise is
+resampled too, as at a receiver's ADC) at a sampling-clock error of X ppm (step 1 + X 1e-6), one table per error, and the tables are
+APPENDED to --out: the clock error's place in the sensitivity record.
+    python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
+                              [--clock-ppm X[,Y...]]"""
 import argparse
 import math
 import os
@@ -32,7 +36,11 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tx", "waterfall.md"))
     ap.add_argument("--doppler-hz", type=float, default=None)
     ap.add_argument("--profile", default=None)
+    ap.add_argument("--clock-ppm", default=None)
     a = ap.parse_args()
+    if a.clock_ppm is not None and a.doppler_hz is not None:
+        ap.error("--clock-ppm is not available with --doppler-hz")
+    clock_ppm = [float(v) for v in a.clock_ppm.split(",")] if a.clock_ppm is not None else []
     if a.profile is not None and a.doppler_hz is None:
         ap.error("--profile wants --doppler-hz")
     import numpy as np
@@ -56,7 +64,9 @@ def main():
     d_iq = torch.zeros((F * S, 2), dtype=torch.float32, device="cuda")
     bank.transmit_frames(torch.from_numpy(fib).cuda(), torch.from_numpy(pay).cuda(), F, d_iq)
     n_out = F * S + 4096
-    d_rx = torch.zeros((E, n_out, 2), dtype=torch.float32, device="cuda")
+    n_rx = n_out + (256 if clock_ppm else 0)                                  # (the resampler reads ahead of its output)
+    d_rx = torch.zeros((E, n_rx, 2), dtype=torch.float32, device="cuda")
+    d_rs = torch.zeros((E, n_out, 2), dtype=torch.float32, device="cuda") if clock_ppm else None
     sdt, rdt = np.dtype(dabgpu.SYNC_STATE_DTYPE), np.dtype(dabgpu.RESULT_DTYPE)
     cifs = torch.from_numpy(pay.reshape(4 * F, nb)).cuda()
     text = [f"# Receiver sensitivity: FIB CRC pass rate and MSC byte-error rate against SNR", "",
@@ -65,14 +75,21 @@ def main():
             f"(per point: {', '.join(f'{name} {E * (4 * F - 15) * sum(spans[i][1] for i in range(len(subs)) if owner[i] == li)}' for li, (name, _) in enumerate(LEVELS))} bytes).  "
             "No carrier or timing offset.  `python tools/waterfall.py`.", ""]
     verdicts = []
-    profiles, fading = PROFILES, None
+    profiles, fading = [(n, t, None) for n, t in PROFILES], None
+    if clock_ppm:
+        text = [f"# Sampling-clock error (appended by `python tools/waterfall.py --clock-ppm {a.clock_ppm}`)", "",
+                f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The white-noise channel of the first table followed by the resampler "
+                f"(step 1 + ppm 1e-6, the noise resampled too): {E} receivers x {F} mode I frames per point, byte counts per point as above.  The frame start drifts "
+                "by ppm 1e-6 x 196608 samples per frame; every frame is synchronised from a slice at its nominal position.", ""]
+        profiles = [(f"white noise, sampling clock {ppm:g} ppm off", PROFILES[0][1], ppm) for ppm in clock_ppm]
     if a.doppler_hz is not None:
         prof = dabgpu.channel_profile(a.profile or "tu6")
-        profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"])]
+        profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"], None)]
         fading = dabgpu.channel_fading_plan([dabgpu.channel_stream(taps=prof["taps"]) for _ in range(E)],
                                             [dabgpu.channel_fading_spec(a.doppler_hz / 2.048e6, 5000 + e, prof["kinds"], prof["rice_k"], prof["los_cos"])
                                              for e in range(E)])
-    for pname, taps in profiles:
+    for pname, taps, ppm in profiles:
+        rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
         rows = []
         ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)], fading=fading)
@@ -80,7 +97,12 @@ def main():
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
             ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(E)])
             ch.seek(0)
-            ch.apply(d_iq, F * S, n_out, d_rx, in_stride_samples=0, out_stride_bytes=n_out * 8)
+            ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rx * 8)
+            d_use = d_rx
+            if rs is not None:
+                rs.seek(0)
+                rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
+                d_use = d_rs
             d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
             hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
             d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
@@ -90,7 +112,7 @@ def main():
             for j in range(F):
                 a0 = NULL + j * S - P_LEAD
                 sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
-                seg = d_rx[:, a0:a0 + STRIDE]
+                seg = d_use[:, a0:a0 + STRIDE]
                 sl[:, :seg.shape[1]] = seg
                 ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
                 ctx.decode_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
@@ -105,6 +127,8 @@ def main():
                         err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
             rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
         ch.close()
+        if rs is not None:
+            rs.close()
         text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
         text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
         # acceptance: error-free at the top, non-increasing within counting error, required SNR ordered by level
@@ -124,7 +148,7 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    open(a.out, "w").write(text)
+    open(a.out, "a" if clock_ppm else "w").write(("\n" if clock_ppm else "") + text)
     return 0 if all(verdicts) else 1
 
 
