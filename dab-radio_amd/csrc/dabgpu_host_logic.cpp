@@ -1137,6 +1137,163 @@ extern "C" int dabgpu_resample_input_needed(const dabgpu_resample_stream* params
     return DABGPU_OK;
 }
 
+// ---- channeliser (include/dabgpu.h, "Channeliser"; the index arithmetic is channelise_core.h's, shared with the kernels) ----
+#include "channelise_core.h"
+
+namespace {
+
+// worst |sum_j h[j] e^(-2 pi i f (j - peak)) - target| over n_f frequencies in [f_lo, f_hi]
+double cs_table_deviation(const float* h, int K, int peak, double f_lo, double f_hi, int n_f, double target) {
+    double worst = 0.0;
+    for (int fi = 0; fi < n_f; fi++) {
+        const double f = f_lo + (f_hi - f_lo) * (double)fi / (double)(n_f - 1);
+        const double step_re = std::cos(2.0 * RS_PI * f), step_im = -std::sin(2.0 * RS_PI * f), a0 = 2.0 * RS_PI * f * (double)peak;
+        double er = std::cos(a0), ei = std::sin(a0), sr = 0.0, si = 0.0;    // e^(-2 pi i f (j - peak)), stepped from j = 0
+        for (int j = 0; j < K; j++) {
+            sr += (double)h[j] * er; si += (double)h[j] * ei;
+            const double nr = er * step_re - ei * step_im;
+            ei = er * step_im + ei * step_re; er = nr;
+        }
+        worst = std::max(worst, std::hypot(sr - target, si));
+    }
+    return worst;
+}
+
+}  // namespace
+
+extern "C" int dabgpu_channeliser_design(int decim, double passband_cycles, double stopband_cycles, dabgpu_channeliser_filter* out) {
+    if (!out) { dabgpu_set_error("channeliser_design: null result"); return DABGPU_ERR_INVALID_ARG; }
+    if (decim < 1 || decim > DABGPU_CHANNELISER_MAX_DECIM) {
+        dabgpu_set_error("channeliser_design: decimation %d (1..%d are accepted)", decim, DABGPU_CHANNELISER_MAX_DECIM); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (passband_cycles == 0.0) passband_cycles = DABGPU_CHANNELISER_DEFAULT_PASSBAND;
+    if (stopband_cycles == 0.0) stopband_cycles = DABGPU_CHANNELISER_DEFAULT_STOPBAND;
+    if (!(passband_cycles > 0.0) || !(stopband_cycles > 0.0)) {             // (NaN included)
+        dabgpu_set_error("channeliser_design: edges %g / %g cycles: both must be positive numbers", passband_cycles, stopband_cycles);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!(passband_cycles < stopband_cycles)) {
+        dabgpu_set_error("channeliser_design: passband %g and stopband %g cycles leave no transition", passband_cycles, stopband_cycles);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!(stopband_cycles <= 0.5 * (double)decim)) {
+        dabgpu_set_error("channeliser_design: stopband %g cycles per block sample lies beyond what the wideband stream holds (0.5 x %d)", stopband_cycles,
+                         decim);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    const int D = decim, K = dabgpu::cs_taps(D), peak = dabgpu::cs_peak(D);
+    const double fc = 0.5 * (passband_cycles + stopband_cycles);
+    for (float& v : out->table) v = 0.0f;
+    if (D == 1) out->table[0] = 1.0f;
+    else {
+        double h[DABGPU_CHANNELISER_TAPS_PER_PHASE * DABGPU_CHANNELISER_MAX_DECIM], sum = 0.0;
+        const double i0_beta = rs_bessel_i0(RS_BETA);
+        for (int j = 0; j < K; j++) {
+            const double t = (double)(j - peak), u = 2.0 * t / (double)K;
+            double win = 0.0;
+            if (std::fabs(u) < 1.0) win = rs_bessel_i0(RS_BETA * std::sqrt(1.0 - u * u)) / i0_beta;
+            const double a = RS_PI * 2.0 * fc * t / (double)D;
+            h[j] = 2.0 * fc / (double)D * ((a == 0.0) ? 1.0 : std::sin(a) / a) * win;
+            sum += h[j];
+        }
+        for (int j = 0; j < K; j++) out->table[j] = (float)(h[j] / sum);
+    }
+    out->decim = D; out->taps = K;
+    out->passband_cycles = passband_cycles; out->stopband_cycles = stopband_cycles; out->cutoff_cycles = fc; out->beta = RS_BETA;
+    if (D == 1) { out->passband_error = out->stopband_level = out->error = 0.0; return DABGPU_OK; }
+    const int n_f = 16 * K + 1;
+    out->passband_error = cs_table_deviation(out->table, K, peak, 0.0, passband_cycles / (double)D, n_f, 1.0);
+    out->stopband_level = cs_table_deviation(out->table, K, peak, stopband_cycles / (double)D, 0.5, n_f, 0.0);
+    out->error = out->passband_error + out->stopband_level;
+    return DABGPU_OK;
+}
+
+int dabgpu_host_channeliser_plan(const char* who, const dabgpu_channeliser_channel* channels, size_t n_channels, size_t n_streams, int64_t start,
+                                 int decim, dabgpu_channeliser_geometry* out, uint32_t* first) {
+    if (out) *out = dabgpu_channeliser_geometry{};
+    if (decim < 1 || decim > DABGPU_CHANNELISER_MAX_DECIM) { dabgpu_set_error("%s: the design's decimation is %d (1..8)", who, decim); return DABGPU_ERR_INVALID_ARG; }
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("%s: %zu streams (1..1048576 are accepted)", who, n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (n_channels == 0 || n_channels > n_streams * DABGPU_CHANNELISER_MAX_CHANNELS) {
+        dabgpu_set_error("%s: %zu channels on %zu streams (1..8 per stream are accepted)", who, n_channels, n_streams); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!channels) { dabgpu_set_error("%s: null channel list", who); return DABGPU_ERR_INVALID_ARG; }
+    if (start > DABGPU_CHANNELISER_MAX_START || start < -DABGPU_CHANNELISER_MAX_START) { dabgpu_set_error("%s: start outside +-2^61", who); return DABGPU_ERR_INVALID_ARG; }
+    size_t run = 0;
+    for (size_t c = 0; c < n_channels; c++) {
+        const dabgpu_channeliser_channel& C = channels[c];
+        if (C.stream >= n_streams) { dabgpu_set_error("%s: channel %zu: stream %u of %zu", who, c, C.stream, n_streams); return DABGPU_ERR_INVALID_ARG; }
+        if (c > 0 && C.stream < channels[c - 1].stream) {
+            dabgpu_set_error("%s: channel %zu: stream %u behind stream %u (the list is sorted by stream)", who, c, C.stream, channels[c - 1].stream);
+            return DABGPU_ERR_INVALID_ARG;
+        }
+        run = (c > 0 && C.stream == channels[c - 1].stream) ? run + 1 : 1;
+        if (run > DABGPU_CHANNELISER_MAX_CHANNELS) {
+            dabgpu_set_error("%s: channel %zu: more than %d channels on stream %u", who, c, DABGPU_CHANNELISER_MAX_CHANNELS, C.stream); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (!std::isfinite(C.gain)) { dabgpu_set_error("%s: channel %zu: gain is not finite", who, c); return DABGPU_ERR_INVALID_ARG; }
+    }
+    if (first) {
+        size_t c = 0;
+        for (size_t s = 0; s <= n_streams; s++) {
+            while (c < n_channels && channels[c].stream < s) c++;
+            first[s] = (uint32_t)c;
+        }
+    }
+    if (out) {
+        const uint32_t D = (uint32_t)decim, nt = (uint32_t)dabgpu::cs_phase_taps(decim);
+        out->decim = D; out->taps = (uint32_t)dabgpu::cs_taps(decim);
+        out->split_tile = DABGPU_CHANNELISER_SPLIT_TILE;
+        // D = 1 reads the input directly.  Otherwise (tile + 72) block-rate positions of D samples, the raw window and the rotated one, each
+        // as 4 D planes of tile / 4 + 18 + 1 samples (channelise.hip)
+        out->split_window = (D == 1) ? 0u : (DABGPU_CHANNELISER_SPLIT_TILE + DABGPU_CHANNELISER_TAPS_PER_PHASE) * D;
+        out->split_lds_bytes = (D == 1) ? 0u : 2u * 4u * D * ((DABGPU_CHANNELISER_SPLIT_TILE + DABGPU_CHANNELISER_TAPS_PER_PHASE) / 4u + 1u) * 8u;
+        out->combine_tile = DABGPU_CHANNELISER_COMBINE_ROWS * D;
+        out->combine_window = DABGPU_CHANNELISER_COMBINE_ROWS + nt - 1u;
+        out->combine_lds_bytes = ((out->combine_window + 1u) & ~1u) * 8u;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_channeliser_tiles(const char* who, size_t n_out, uint32_t tile, size_t rows, uint32_t* tiles) {
+    const size_t t = (n_out + tile - 1) / tile + 1;                         // (+ 1: a combine call may begin inside a tile)
+    if (t * rows > 0x7FFFFFFFull) { dabgpu_set_error("%s: streams x n_out too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    *tiles = (uint32_t)(t - 1);
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channeliser_plan(const dabgpu_channeliser_channel* channels, size_t n_channels, size_t n_streams, int64_t start,
+                                       const dabgpu_channeliser_filter* design, dabgpu_channeliser_geometry* out) {
+    if (out) *out = dabgpu_channeliser_geometry{};
+    if (!design) { dabgpu_set_error("channeliser_plan: null design"); return DABGPU_ERR_INVALID_ARG; }
+    return dabgpu_host_channeliser_plan("channeliser_plan", channels, n_channels, n_streams, start, design->decim, out, nullptr);
+}
+
+extern "C" uint64_t dabgpu_channeliser_freq_q64(double offset_hz, double rate_hz) {
+    if (!(rate_hz > 0.0) || !std::isfinite(rate_hz)) return 0;
+    return dabgpu_channel_freq_q64(offset_hz / rate_hz);                    // (0 for NaN and outside +-0.5)
+}
+
+extern "C" int dabgpu_channeliser_input_needed(int decim, uint64_t position, int64_t start, size_t n_out, int64_t* first, uint64_t* count) {
+    if (!first || !count) { dabgpu_set_error("channeliser_input_needed: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *first = 0; *count = 0;
+    if (decim < 1 || decim > DABGPU_CHANNELISER_MAX_DECIM) { dabgpu_set_error("channeliser_input_needed: decimation %d (1..8)", decim); return DABGPU_ERR_INVALID_ARG; }
+    if (position > (uint64_t)DABGPU_CHANNELISER_MAX_POSITION || n_out > ((size_t)1 << 31)) {
+        dabgpu_set_error("channeliser_input_needed: position above 2^58 or more than 2^31 samples"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (start > DABGPU_CHANNELISER_MAX_START || start < -DABGPU_CHANNELISER_MAX_START) {
+        dabgpu_set_error("channeliser_input_needed: start outside +-2^61"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_out == 0) return DABGPU_OK;
+    *first = dabgpu::cs_split_first(decim, position, start);
+    *count = (uint64_t)(n_out - 1) * (uint64_t)decim + (uint64_t)dabgpu::cs_taps(decim);
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_channeliser_decim_for(double rate_hz) {
+    for (int d = DABGPU_CHANNELISER_MAX_DECIM; d >= 1; d--) if (rate_hz / (double)d >= 2048000.0) return d;
+    return 0;                                                                // (NaN included)
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

@@ -257,6 +257,14 @@ uint64_t dabgpu_host_resample_max_step_q62(double max_step);       // max_step r
 // dabgpu_resample_bank_set_params: new parameters must fit the window and the table rows of the bank's creation
 int dabgpu_host_resample_fits(const dabgpu_resample_geometry& created, const dabgpu_resample_geometry& wanted);
 
+// ---- channeliser planner (channelise.hip launches from it; include/dabgpu.h, dabgpu_channeliser_plan) ----
+// DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (channel index, field); `who` names the entry point.
+// first (NULL, or n_streams + 1 words): first[s] .. first[s + 1] are the channels of stream s in the sorted list
+int dabgpu_host_channeliser_plan(const char* who, const dabgpu_channeliser_channel* channels, size_t n_channels, size_t n_streams, int64_t start,
+                                 int decim, dabgpu_channeliser_geometry* out, uint32_t* first);
+// the workgroups of a call: DABGPU_OK and *tiles, or DABGPU_ERR_INVALID_ARG when tiles x rows does not fit one grid
+int dabgpu_host_channeliser_tiles(const char* who, size_t n_out, uint32_t tile, size_t rows, uint32_t* tiles);
+
 // ---- DAB+ super-frame encoder (dabplus_tx.hip; include/dabgpu.h, dabgpu_dabplus_superframe_layout) ----
 // Where the access units of a super frame start (ETSI TS 102 563 5.2, as AAC_Frame_Processor reads it back, aac_frame_processor.cpp:266-283),
 // one body for the host entry point and the kernel.  au_len: the first num_aus entries are read; start[0 .. num_aus] are written, the rest

@@ -80,6 +80,10 @@ ABI_SYMBOLS = [
     "dabgpu_resample_design", "dabgpu_resample_plan", "dabgpu_resample_step_q62", "dabgpu_resample_step", "dabgpu_resample_input_needed",
     "dabgpu_resample_bank_create", "dabgpu_resample_bank_destroy", "dabgpu_resample_bank_set_params", "dabgpu_resample_bank_seek",
     "dabgpu_resample_bank_apply", "dabgpu_resample_bank_apply_host_sync",
+    "dabgpu_channeliser_design", "dabgpu_channeliser_plan", "dabgpu_channeliser_freq_q64", "dabgpu_channeliser_input_needed",
+    "dabgpu_channeliser_decim_for", "dabgpu_channeliser_bank_create", "dabgpu_channeliser_bank_destroy", "dabgpu_channeliser_bank_set_params",
+    "dabgpu_channeliser_bank_seek", "dabgpu_channeliser_bank_split", "dabgpu_channeliser_bank_split_host_sync",
+    "dabgpu_channeliser_bank_combine", "dabgpu_channeliser_bank_combine_host_sync",
     "dabgpu_tii_cfg_default", "dabgpu_tii_pattern", "dabgpu_tii_main_id", "dabgpu_tii_carriers", "dabgpu_tii_validate",
     "dabgpu_ofdm_modulate_frames_tii", "dabgpu_ofdm_modulate_frames_tii_host_sync",
     "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
@@ -96,6 +100,17 @@ RESAMPLE_PHASES = 256
 RESAMPLE_TAPS = 48
 RESAMPLE_BLOCK = 1024
 RESAMPLE_DEFAULT_PASSBAND = 0.375
+
+# channeliser (include/dabgpu.h)
+CHANNELISER_TAPS_PER_PHASE = 72
+CHANNELISER_MAX_DECIM = 8
+CHANNELISER_MAX_CHANNELS = 8
+CHANNELISER_SPLIT_TILE = 512
+CHANNELISER_COMBINE_ROWS = 128
+CHANNELISER_DEFAULT_PASSBAND = 0.375
+CHANNELISER_DEFAULT_STOPBAND = 0.4609375
+CHANNELISER_MAX_POSITION = 1 << 58
+CHANNELISER_MAX_START = 1 << 61
 
 # TII (include/dabgpu.h)
 TII_MAX_TX = 4
@@ -197,6 +212,24 @@ class ResampleFilter(C.Structure):
 class ResampleGeometry(C.Structure):
     """dabgpu_resample_geometry"""
     _fields_ = [("block_samples", C.c_uint32), ("window_samples", C.c_uint32), ("table_rows", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
+class ChanneliserChannel(C.Structure):
+    """dabgpu_channeliser_channel"""
+    _fields_ = [("freq_q64", C.c_uint64), ("phase0_q64", C.c_uint64), ("gain", C.c_float), ("stream", C.c_uint32)]
+
+
+class ChanneliserFilter(C.Structure):
+    """dabgpu_channeliser_filter: the design record (its error figures) and the table of 72 x decim taps"""
+    _fields_ = [("decim", C.c_int32), ("taps", C.c_int32), ("passband_cycles", C.c_double), ("stopband_cycles", C.c_double),
+                ("cutoff_cycles", C.c_double), ("beta", C.c_double), ("passband_error", C.c_double), ("stopband_level", C.c_double),
+                ("error", C.c_double), ("table", C.c_float * (CHANNELISER_TAPS_PER_PHASE * CHANNELISER_MAX_DECIM))]
+
+
+class ChanneliserGeometry(C.Structure):
+    """dabgpu_channeliser_geometry"""
+    _fields_ = [(name, C.c_uint32) for name in ("decim", "taps", "split_tile", "split_window", "split_lds_bytes", "combine_tile", "combine_window",
+                                                "combine_lds_bytes")]
 
 
 class SyncCfg(C.Structure):
@@ -401,6 +434,23 @@ def lib():
         L.dabgpu_resample_step.argtypes = [C.c_uint64]
         L.dabgpu_resample_step.restype = C.c_double
         L.dabgpu_resample_input_needed.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.dabgpu_channeliser_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_void_p]
+        L.dabgpu_channeliser_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p]
+        L.dabgpu_channeliser_freq_q64.argtypes = [C.c_double, C.c_double]
+        L.dabgpu_channeliser_freq_q64.restype = C.c_uint64
+        L.dabgpu_channeliser_input_needed.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.dabgpu_channeliser_decim_for.argtypes = [C.c_double]
+        L.dabgpu_channeliser_bank_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_channeliser_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_channeliser_bank_destroy.restype = None
+        L.dabgpu_channeliser_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p]
+        L.dabgpu_channeliser_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_channeliser_bank_split.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_channeliser_bank_split_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.dabgpu_channeliser_bank_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t,
+                                                      C.c_float, C.c_void_p]
+        L.dabgpu_channeliser_bank_combine_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                                                                C.c_size_t, C.c_float]
         L.dabgpu_resample_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.dabgpu_resample_bank_destroy.argtypes = [C.c_void_p]
         L.dabgpu_resample_bank_destroy.restype = None
@@ -1125,6 +1175,126 @@ class Resampler:
                                                          float(u8_scale)), "dabgpu_resample_bank_apply_host_sync")
         out = out[:, :n_out * sb]
         return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+
+
+def channeliser_freq(offset_hz, rate_hz):
+    """dabgpu_channeliser_freq_q64: offset / rate (cycles per wideband sample) as the nearest Q64 word; 0 for NaN or outside +- half the rate"""
+    return int(lib().dabgpu_channeliser_freq_q64(float(offset_hz), float(rate_hz)))
+
+
+def channeliser_decim_for(rate_hz):
+    """dabgpu_channeliser_decim_for: the largest D <= 8 with rate / D >= 2.048 MHz; 0: none"""
+    return int(lib().dabgpu_channeliser_decim_for(float(rate_hz)))
+
+
+def channeliser_channel(freq_q64=0, phase0_q64=0, gain=1.0, stream=0):
+    """a ChanneliserChannel: freq_q64 from channeliser_freq"""
+    ch = ChanneliserChannel()
+    ch.freq_q64, ch.phase0_q64, ch.gain, ch.stream = int(freq_q64) & ((1 << 64) - 1), int(phase0_q64) & ((1 << 64) - 1), gain, int(stream)
+    return ch
+
+
+def channeliser_design(decim, passband_cycles=0.0, stopband_cycles=0.0):
+    """dabgpu_channeliser_design (host only): a ChanneliserFilter -- 72 x decim taps and the error figures the table was found to have"""
+    D = ChanneliserFilter()
+    check(lib().dabgpu_channeliser_design(int(decim), float(passband_cycles), float(stopband_cycles), C.byref(D)), "dabgpu_channeliser_design")
+    return D
+
+
+def channeliser_plan(channels, n_streams, design, start=0):
+    """dabgpu_channeliser_plan (host only): the geometry as a dict; raises DabGpuError"""
+    n = len(channels)
+    arr = (ChanneliserChannel * n)(*channels) if n else None
+    g = ChanneliserGeometry()
+    check(lib().dabgpu_channeliser_plan(arr, n, int(n_streams), int(start), C.byref(design) if design is not None else None, C.byref(g)),
+          "dabgpu_channeliser_plan")
+    return {name: getattr(g, name) for name, _ in ChanneliserGeometry._fields_}
+
+
+def channeliser_input_needed(decim, position, start, n_out):
+    """dabgpu_channeliser_input_needed: (first, count) of the wideband indices a split of n_out samples at `position` reads"""
+    first, count = C.c_int64(), C.c_uint64()
+    check(lib().dabgpu_channeliser_input_needed(int(decim), int(position), int(start), int(n_out), C.byref(first), C.byref(count)),
+          "dabgpu_channeliser_input_needed")
+    return first.value, count.value
+
+
+class Channeliser:
+    """dabgpu_channeliser_bank: split (wideband streams -> block streams, one row per channel of the list) and combine (block streams -> wideband
+    streams); the list is sorted by stream, at most 8 channels per stream; the position lives on the device.  design: a ChanneliserFilter, or
+    the decimation (default edges)"""
+
+    def __init__(self, ctx, channels, n_streams, design, start=0):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.n_channels, self.n_streams = len(channels), int(n_streams)
+        if not isinstance(design, ChanneliserFilter):
+            design = channeliser_design(design)
+        self.design, self.decim = design, design.decim
+        self.plan = channeliser_plan(channels, n_streams, design, start)
+        self.start = int(start)
+        arr = (ChanneliserChannel * self.n_channels)(*channels)
+        check(lib().dabgpu_channeliser_bank_create(ctx._h, arr, self.n_channels, self.n_streams, int(start), C.byref(design), C.byref(self._h)),
+              "dabgpu_channeliser_bank_create")
+
+    def close(self):
+        if self._h:
+            lib().dabgpu_channeliser_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, channels, start=None, stream=None):
+        """replaces the channel list; start = None keeps the bank's `start` (the one of its creation or of the last set_params)"""
+        start = self.start if start is None else int(start)
+        n = len(channels)
+        arr = (ChanneliserChannel * n)(*channels) if n else None
+        check(lib().dabgpu_channeliser_bank_set_params(self._h, arr, n, int(start), Context._stream(stream)), "dabgpu_channeliser_bank_set_params")
+        self.n_channels, self.start = n, start
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_channeliser_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_channeliser_bank_seek")
+
+    def split(self, d_in, n_in, n_out, d_out, in_stride_samples=0, wrap=False, out_stride_bytes=0, stream=None):
+        """d_in wideband complex float (device) -> d_out [n_channels] rows of n_out block samples; asynchronous"""
+        check(lib().dabgpu_channeliser_bank_split(self._h, _ptr(d_in), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(d_out), out_stride_bytes,
+                                                  Context._stream(stream)), "dabgpu_channeliser_bank_split")
+
+    def combine(self, d_in, n_in, n_out, d_out, in_stride_samples=0, wrap=False, out_format=None, out_stride_bytes=0, u8_scale=1.0, stream=None):
+        """d_in [n_channels] block rows (device) -> d_out [n_streams] rows of n_out wideband samples, complex float or u8 pairs; asynchronous"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_channeliser_bank_combine(self._h, _ptr(d_in), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(d_out), fmt,
+                                                    out_stride_bytes, float(u8_scale), Context._stream(stream)), "dabgpu_channeliser_bank_combine")
+
+    def _host(self, split, h_in, n_out, in_stride_samples, wrap, fmt, u8_scale):
+        import numpy as np
+        x = np.ascontiguousarray(h_in, dtype=np.complex64)
+        n_in = x.shape[-1]
+        rows = self.n_channels if split else self.n_streams
+        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
+        stride = (n_out * sb + 15) & ~15
+        out = np.zeros((rows, stride), np.uint8)
+        if split:
+            check(lib().dabgpu_channeliser_bank_split_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), stride),
+                  "dabgpu_channeliser_bank_split_host_sync")
+        else:
+            check(lib().dabgpu_channeliser_bank_combine_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
+                                                                  float(u8_scale)), "dabgpu_channeliser_bank_combine_host_sync")
+        out = out[:, :n_out * sb]
+        return out.copy().view(np.complex64) if sb == 8 else out.reshape(rows, n_out, 2).copy()
+
+    def split_host(self, h_in, n_out, in_stride_samples=0, wrap=False):
+        """h_in complex64 [n_in] (shared) or [n_streams][n_in] with in_stride_samples = n_in -> [n_channels][n_out] complex64; returns when done"""
+        return self._host(True, h_in, n_out, in_stride_samples, wrap, IQ_FORMATS.index("raw_f32l"), 1.0)
+
+    def combine_host(self, h_in, n_out, in_stride_samples=0, wrap=False, out_format=None, u8_scale=1.0):
+        """h_in complex64 [n_channels][n_in] with in_stride_samples = n_in (or one shared row) -> [n_streams][n_out] complex64 / [..][n_out][2] uint8"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        return self._host(False, h_in, n_out, in_stride_samples, wrap, fmt, u8_scale)
 
 
 def tii_pattern(main_id):

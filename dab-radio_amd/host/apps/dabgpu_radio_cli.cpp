@@ -23,6 +23,13 @@
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
 //
+// --channel-offset-hz F, together with --input-rate HZ (include/dabgpu.h "Channeliser"): the capture is a wideband one, HZ from 2048000 to
+// 32768000, and the block to receive lies F Hz from its centre.  Every block is split by D = dabgpu_channeliser_decim_for(HZ) at offset F
+// (DAB_Stream_Channeliser) between the format conversion and the resampler, which then takes HZ / D to 2.048 MHz and is absent where HZ / D
+// is 2.048 MHz already (8192000: D = 4, no resampler; 10000000: D = 4, then 2.5 -> 2.048 MS/s).  The filter's edges are the block's own
+// (768 kHz) and its neighbour's (944 kHz) at the rate the split leaves.  With F = 0 and HZ below 4096000 no channeliser is made: the
+// resampler alone, as without the option.
+//
 // Output files are byte-for-byte what the reference writes with the same options (frame bits: 230400 int8 per frame,
 // or 28800 bytes per frame with --ofdm-output-hard-bytes, LSB first).
 #include <stdio.h>
@@ -39,6 +46,7 @@
 #include "dab/constants/dab_parameters.h"
 #include "dab/fic/fic_decoder.h"
 #include "dab/msc/msc_decoder.h"
+#include "dab/tx/dab_channeliser.h"
 #include "dab/tx/dab_resampler.h"
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
@@ -61,6 +69,8 @@ struct Args {
     bool tii = false;
     int tii_frames = 8;
     double input_rate = 2.048e6;
+    bool channelise = false;
+    double channel_offset_hz = 0.0;
 };
 
 static void usage(const char* argv0) {
@@ -70,7 +80,7 @@ static void usage(const char* argv0) {
         "  [--ofdm-enable-output] [--ofdm-output FILE] [--ofdm-output-hard-bytes]\n"
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
-        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ]\n"
+        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ] [--channel-offset-hz F]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -134,13 +144,22 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--tii") args.tii = true;
         else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
         else if (a == "--input-rate") args.input_rate = std::stod(value());
+        else if (a == "--channel-offset-hz") { args.channel_offset_hz = std::stod(value()); args.channelise = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
-    if (!(args.input_rate >= 1.024e6 && args.input_rate <= 4.096e6)) throw std::runtime_error("--input-rate: 1024000 .. 4096000 samples per second");
+    if (args.channelise) {
+        if (!(args.input_rate >= 2.048e6 && args.input_rate <= 8 * 4.096e6)) throw std::runtime_error("--channel-offset-hz: --input-rate 2048000 .. 32768000 samples per second");
+        if (!(std::fabs(args.channel_offset_hz) <= 0.5 * args.input_rate)) throw std::runtime_error("--channel-offset-hz: within half of --input-rate either way");
+        if (!args.is_ofdm_used) throw std::runtime_error("--channel-offset-hz needs the OFDM stage");
+        if (args.tii) throw std::runtime_error("--channel-offset-hz is not available with --tii");
+        if (args.channel_offset_hz == 0.0 && args.input_rate < 4.096e6) args.channelise = false;       // the resampler alone
+    }
+    if (!args.channelise && !(args.input_rate >= 1.024e6 && args.input_rate <= 4.096e6))
+        throw std::runtime_error("--input-rate: 1024000 .. 4096000 samples per second");
     if (args.input_rate != 2.048e6 && !args.is_ofdm_used) throw std::runtime_error("--input-rate needs the OFDM stage");
     if (args.input_rate != 2.048e6 && args.tii) throw std::runtime_error("--input-rate is not available with --tii (resampled blocks may exceed --ofdm-block-size)");
     if (args.transmission_mode != 1) throw std::runtime_error("only transmission mode I is implemented");
@@ -266,11 +285,35 @@ static int run(const Args& args) {
         std::vector<std::complex<float>> block(args.ofdm_block_size);               // OFDM_Block::run, app_ofdm_blocks.h:45-57
         std::unique_ptr<DAB_Stream_Resampler> resampler;
         std::vector<std::complex<float>> resampled;
-        if (args.input_rate != 2.048e6) resampler = std::make_unique<DAB_Stream_Resampler>(DAB_Resampler::StepWord(args.input_rate, 2.048e6));
+        std::unique_ptr<DAB_Stream_Channeliser> channeliser;
+        std::vector<std::vector<std::complex<float>>> split;
+        double block_rate = args.input_rate;
+        if (args.channelise) {
+            const int decim = DAB_Channeliser::DecimFor(args.input_rate);
+            block_rate = args.input_rate / (double)decim;
+            // the block's edge (768 kHz) and its neighbour's (944 kHz) in cycles per sample of the rate the split leaves: 0.375 / 0.4609375 at 2.048 MS/s
+            channeliser = std::make_unique<DAB_Stream_Channeliser>(decim, std::vector<dabgpu_channeliser_channel>{DAB_Channeliser::Channel(args.channel_offset_hz, args.input_rate)},
+                                                                   768000.0 / block_rate, 944000.0 / block_rate);
+            fprintf(stderr, "channeliser: decimation %d, %.0f samples per second per block, design error %.3g\n", decim, block_rate, channeliser->DesignError());
+            if (channeliser->DesignError() > 1e-4)
+                fprintf(stderr, "warning: that is above the 1e-4 the design holds at 2048000 samples per second per block (the transition between the "
+                                "block's edge and its neighbour's is narrower at this rate)\n");
+        }
+        if (block_rate != 2.048e6) resampler = std::make_unique<DAB_Stream_Resampler>(DAB_Resampler::StepWord(block_rate, 2.048e6));
         for (;;) {
             const size_t length = reader->read(block);
             if (length == 0) break;
-            if (resampler) {
+            if (channeliser) {
+                split.clear();
+                channeliser->Process(tcb::span<const std::complex<float>>(block.data(), length), split);
+                if (!split.empty() && !split[0].empty()) {
+                    if (resampler) {
+                        resampled.clear();
+                        resampler->Process(split[0], resampled);
+                        if (!resampled.empty()) demod->Process(resampled);
+                    } else demod->Process(split[0]);
+                }
+            } else if (resampler) {
                 resampled.clear();
                 resampler->Process(tcb::span<const std::complex<float>>(block.data(), length), resampled);
                 if (!resampled.empty()) demod->Process(resampled);

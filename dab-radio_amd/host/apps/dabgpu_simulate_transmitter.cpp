@@ -27,6 +27,18 @@
 //   --clock-ppm X                  the ADC's sample period X ppm longer than nominal: step = 2048000 / HZ * (1 + X 1e-6) input samples per output
 //   --frac-delay D                 the samples taken D of a 2.048 MHz sample late, 0 <= D < 1
 // With any of them a frame's worth of input gives about 196608 / step samples; the last taps of a frame's last samples come with the next frame.
+// Wideband capture (include/dabgpu.h "Channeliser", DAB_Stream_Combiner): behind the channel and the resampler, the combiner puts the block
+// and up to 7 neighbours onto one stream at D times the output rate, as a wideband tuner would write them.
+//   --wideband D                   1..8; the output has D x the samples (D x 2048000 per second, or D x --output-rate)
+//   --centre-offset-hz F           the block lies F Hz above the centre of the capture (default 0)
+//   --neighbour OFFSET_HZ:LEVEL_DB repeatable, up to 7: a block OFFSET_HZ from the wanted one, LEVEL_DB above it.  Neighbour k carries the
+//                                  wanted block's own stream 50001 + 70006 k samples late (zeros before): the same frames, other content
+//                                  at every instant
+// The u8 scale leaves the sum of the blocks four standard deviations of head room, 127.5 / (4 sqrt(carriers / 2 x (1 + sum 10^(LEVEL_DB / 10)))),
+// and is never above the single block's scale (no neighbour: the single block's bytes).  The quantiser truncates, as the modulator's does:
+// its mean of half a step is a carrier at the CAPTURE's centre, which lies inside a block unless --centre-offset-hz puts it between two;
+// the head room rule keeps it 13 dB under a block 20 dB below its neighbours.  The last 72 D / 2 - 1 samples of a frame's worth come with
+// the next frame.
 // Fading (include/dabgpu.h "Channel model, fading taps", DAB_Channel_Model::SetFading): taps with a Rayleigh or Rice gain and Doppler.
 //   --doppler-hz F                 maximum Doppler shift, 0..1000 Hz; with it every tap fades (Rayleigh) unless --tap-kind says otherwise
 //   --fading-seed S                default 1
@@ -52,6 +64,7 @@
 
 #include "dab/dabgpu_shared_context.h"
 #include "dab/tx/dab_channel_model.h"
+#include "dab/tx/dab_channeliser.h"
 #include "dab/tx/dab_resampler.h"
 #include "dabgpu.h"
 #include "ofdm/dab_ofdm_params_ref.h"
@@ -101,7 +114,64 @@ struct Args {
     // resampler: behind the channel
     bool resample = false;
     double clock_ppm = 0.0, frac_delay = 0.0, output_rate = 2.048e6;
+    // combiner: behind the channel and the resampler
+    int wideband = 0;
+    double centre_offset_hz = 0.0;
+    struct Neighbour { double offset_hz, level_db; };
+    std::vector<Neighbour> neighbours;
 };
+
+// the wideband capture behind the channel and the resampler (include/dabgpu.h "Channeliser"): the block at --centre-offset-hz and its
+// --neighbour blocks, which carry the block's own stream a fixed count of samples late, combined at --wideband times the block rate
+struct Wideband {
+    std::unique_ptr<DAB_Stream_Combiner> combiner;
+    std::vector<size_t> delay;                                 // per row, in block samples (row 0: the wanted block, 0)
+    std::vector<std::complex<float>> history, rows;            // the last max(delay) samples of the stream; the rows of one call
+    std::vector<uint8_t> bytes;
+    float u8_scale = 1.0f;
+    Wideband(const Args& args, float block_u8_scale, int nb_carriers) {
+        const double block_rate = args.output_rate, rate = block_rate * args.wideband;
+        std::vector<dabgpu_channeliser_channel> channels{DAB_Channeliser::Channel(args.centre_offset_hz, rate)};
+        delay.push_back(0);
+        double power = 1.0;
+        for (size_t k = 0; k < args.neighbours.size(); k++) {
+            channels.push_back(DAB_Channeliser::Channel(args.centre_offset_hz + args.neighbours[k].offset_hz, rate, args.neighbours[k].level_db));
+            delay.push_back(50001 + 70006 * k);
+            power += std::pow(10.0, args.neighbours[k].level_db / 10.0);
+        }
+        // the block's edge (768 kHz) and its neighbour's (944 kHz) in cycles per sample of the block rate: 0.375 / 0.4609375 at 2.048 MS/s
+        combiner = std::make_unique<DAB_Stream_Combiner>(args.wideband, channels, 768000.0 / block_rate, 944000.0 / block_rate);
+        if (combiner->DesignError() > 1e-4)
+            fprintf(stderr, "warning: at %.0f samples per second per block the combiner's 72 x %d taps reach %.3g (passband deviation + stopband level), "
+                            "above the 1e-4 the design holds at 2048000\n", block_rate, args.wideband, combiner->DesignError());
+        history.assign(delay.back(), std::complex<float>(0.0f, 0.0f));
+        u8_scale = (float)std::min((double)block_u8_scale, 127.5 / (4.0 * std::sqrt(0.5 * (double)nb_carriers * power)));
+    }
+    // the next samples of the block stream through the combiner to the file; false when a write fails
+    bool Write(tcb::span<const std::complex<float>> block, FILE* fp_out) {
+        const size_t n = block.size(), H = history.size();
+        history.insert(history.end(), block.begin(), block.end());          // stream samples (now - H) .. (now + n)
+        rows.resize(delay.size() * n);
+        for (size_t k = 0; k < delay.size(); k++) std::copy(history.begin() + (long)(H - delay[k]), history.begin() + (long)(H - delay[k] + n), rows.begin() + (long)(k * n));
+        history.erase(history.begin(), history.begin() + (long)n);
+        bytes.clear();
+        combiner->ProcessU8(rows, bytes, u8_scale);
+        const size_t nb_write = fwrite(bytes.data(), 2, bytes.size() / 2, fp_out);
+        if (nb_write != bytes.size() / 2) { fprintf(stderr, "Failed to write out frame %zu/%zu\n", nb_write, bytes.size() / 2); return false; }
+        return true;
+    }
+};
+static std::unique_ptr<Wideband> make_wideband(const Args& args, float block_u8_scale, int nb_carriers) {
+    if (args.wideband == 0) return nullptr;
+    return std::make_unique<Wideband>(args, block_u8_scale, nb_carriers);
+}
+// one frame of the channel's output on its way out: through the resampler where there is one, then the combiner
+static bool write_wideband(Wideband& wide, DAB_Stream_Resampler* rs, tcb::span<const std::complex<float>> frame, std::vector<std::complex<float>>& resampled, FILE* fp_out) {
+    if (!rs) return wide.Write(frame, fp_out);
+    resampled.clear();
+    rs->Process(frame, resampled);
+    return resampled.empty() ? true : wide.Write(resampled, fp_out);
+}
 
 // the receiver's ADC behind the channel (include/dabgpu.h "Resampler"): --output-rate HZ samples per second, its sample period --clock-ppm
 // longer than nominal, the samples taken --frac-delay of a 2.048 MHz sample late
@@ -262,8 +332,9 @@ static int run_coded(const Args& args, FILE* fp_out) {
         window.assign(2 * S, std::complex<float>(0.0f, 0.0f));
     }
     auto resampler = make_resampler(args);
-    std::vector<std::complex<float>> impaired(resampler ? S : 0);
     const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
+    auto wide = make_wideband(args, u8_scale, 1536);
+    std::vector<std::complex<float>> impaired((resampler || wide) ? S : 0), resampled;
     int rc = 0;
     for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
         fibs.read(fib.data(), 360);
@@ -275,12 +346,16 @@ static int run_coded(const Args& args, FILE* fp_out) {
                 dabgpu_channel_stream now = cp;
                 now.start = cp.start + (k - 1) * (long long)S;             // window sample 0 = stream sample (k - 1) S
                 channel->SetParams(now);
-                if (resampler) channel->Apply(impaired, window, false);
+                if (resampler || wide) channel->Apply(impaired, window, false);
                 else channel->ApplyU8(quantised, window, false, u8_scale);
             }
         } else
         st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
         if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); rc = 1; break; }
+        if (wide) {
+            if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out)) break;
+            continue;
+        }
         if (resampler) {
             if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
             continue;
@@ -298,6 +373,7 @@ static void usage(const char* argv0) {
                     "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N] [--tii P:C[:AMP]]...\n"
                     "          [--doppler-hz F] [--fading-seed S] [--profile tu6|ra6|sfn2] [--tap-kind K:static|rayleigh|rice:KDB]...\n"
                     "          [--clock-ppm X] [--frac-delay D] [--output-rate HZ]\n"
+                    "          [--wideband D] [--centre-offset-hz F] [--neighbour OFFSET_HZ:LEVEL_DB]...\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
                     "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
@@ -308,10 +384,13 @@ static void usage(const char* argv0) {
                     "--profile takes taps and kinds from a preset as recalled from COST 207), unit mean power each, seeded by --fading-seed;\n"
                     "with --clock-ppm X / --frac-delay D / --output-rate HZ the signal is resampled behind the channel (the noise too, as at a\n"
                     "receiver's ADC): HZ samples per second (default 2048000), every sample period X ppm longer, D of a sample late;\n"
+                    "with --wideband D (1..8) the block goes onto a capture at D times the rate, --centre-offset-hz F above its centre, with up to 7\n"
+                    "--neighbour blocks OFFSET_HZ from it and LEVEL_DB above it (the block's own stream, a fixed count of samples late);\n"
                     "with --tii (mode I, up to 4) the NULL period of every other frame carries those transmitters' identification\n", argv0);
 }
 
 static bool parse_args(int argc, char** argv, Args& args) {
+    bool have_wide_option = false, have_wideband = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> std::string {
@@ -339,8 +418,33 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--clock-ppm") { args.clock_ppm = std::stod(value()); args.resample = true; }
         else if (a == "--frac-delay") { args.frac_delay = std::stod(value()); args.resample = true; }
         else if (a == "--output-rate") { args.output_rate = std::stod(value()); args.resample = true; }
+        else if (a == "--wideband") { args.wideband = std::stoi(value()); have_wideband = true; }
+        else if (a == "--centre-offset-hz") { args.centre_offset_hz = std::stod(value()); have_wide_option = true; }
+        else if (a == "--neighbour") {
+            const std::string v = value();
+            const size_t colon = v.find(':');
+            if (colon == std::string::npos) throw std::runtime_error("--neighbour expects OFFSET_HZ:LEVEL_DB: '" + v + "'");
+            args.neighbours.push_back({std::stod(v.substr(0, colon)), std::stod(v.substr(colon + 1))});
+            have_wide_option = true;
+        }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument: " + a);
+    }
+    if (have_wide_option && !have_wideband) throw std::runtime_error("--centre-offset-hz / --neighbour need --wideband D");
+    if (have_wideband) {
+        // the combiner stands behind the channel (and the resampler): without channel options that is the identity channel
+        args.channel = true;
+        if (args.wideband < 1 || args.wideband > DABGPU_CHANNELISER_MAX_DECIM) throw std::runtime_error("--wideband: 1 .. 8");
+        if (args.neighbours.size() > DABGPU_CHANNELISER_MAX_CHANNELS - 1) throw std::runtime_error("--neighbour: at most 7");
+        // the filter's edges are the block's (768 kHz) and its neighbour's (944 kHz) over the block rate: the stopband has to fit 0.5 x D
+        if (!(944000.0 / args.output_rate <= 0.5 * args.wideband))
+            throw std::runtime_error("--wideband: the capture's rate (D x --output-rate) does not hold a block and its neighbour's edge: at least 1888000 samples per second");
+        const double half = 0.5 * args.output_rate * args.wideband;
+        if (!(std::fabs(args.centre_offset_hz) <= half)) throw std::runtime_error("--centre-offset-hz: within half of the capture's rate either way");
+        for (const auto& nb : args.neighbours) {
+            if (!(std::fabs(args.centre_offset_hz + nb.offset_hz) <= half)) throw std::runtime_error("--neighbour: the block lies outside the capture");
+            if (!(std::fabs(nb.level_db) <= 100.0)) throw std::runtime_error("--neighbour: level -100 .. 100 dB");
+        }
     }
     if (args.resample) {
         // the resampler stands behind the channel: without channel options that is the identity channel, which returns its input bit for bit
@@ -427,8 +531,14 @@ int main(int argc, char** argv) {
             if (fading_spec(args, cp, spec)) channel.SetFading(spec);
             const float u8_scale = (1.0f / (float)params.nb_data_carriers * 4.0f) * 127.5f;
             auto resampler = make_resampler(args);
-            std::vector<std::complex<float>> impaired(resampler ? frame_size : 0);
+            auto wide = make_wideband(args, u8_scale, (int)params.nb_data_carriers);
+            std::vector<std::complex<float>> impaired((resampler || wide) ? frame_size : 0), resampled;
             for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
+                if (wide) {
+                    channel.Apply(impaired, frame, true);
+                    if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out)) break;
+                    continue;
+                }
                 if (resampler) {
                     channel.Apply(impaired, frame, true);
                     if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;

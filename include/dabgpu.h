@@ -1217,6 +1217,117 @@ int dabgpu_resample_bank_apply_host_sync(dabgpu_resample_bank *bank, const float
                                          size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Channeliser: wideband captures to DAB blocks and back.  A wideband tuner writes several Band III blocks, 1.712 MHz apart, into one
+ * 8.192 / 10.24 / 16.384 MS/s capture; SPLIT is a frequency-translating, integer-decimating bank that turns one such stream into up to
+ * DABGPU_CHANNELISER_MAX_CHANNELS block streams, COMBINE is its transpose (block streams at their offsets and levels onto one wideband
+ * stream, for the simulator).  A rate that is no integer multiple of the block rate is left to the resampler behind the channeliser
+ * (10 MS/s -> split by 4 -> 2.5 MS/s -> resampler -> 2.048 MS/s).  The reference has nothing comparable; the definition is this library's
+ * own, written once in dab-radio_amd/csrc/channelise_core.h for the kernels (channelise.hip) and for the host model of the tests
+ * (tests/cpp/channelise_host_model.cpp), pinned to an independent numpy model (tests/channelise_model.py) and on the device bit for bit to
+ * the host model (tests/test_gpu_channelise.py).  Design table, error bound and measurements: DESIGN.md 4.20.
+ *
+ * Table.  dabgpu_channeliser_design(decim, passband_cycles, stopband_cycles, *out), host only, double throughout: D = decim in 1..8,
+ * K = DABGPU_CHANNELISER_TAPS_PER_PHASE * D taps.  h[j] = 2 f_c / D * sinc(2 f_c t / D) * kaiser(t), t = j - P in wideband samples, under the
+ * resampler's Kaiser window (beta = 9.25, I0 by its series, argument 2 t / K, zero from |2 t / K| = 1 on); f_c lies half way between the
+ * two edges, which are given in cycles per sample of the BLOCK rate (0 = the defaults 0.375, the 768 kHz edge of a block at 2.048 MS/s,
+ * and 0.4609375, the 944 kHz edge of the next block); the table is divided by its sum (DC gain 1).  The peak sits on tap P = K / 2 - 1 as in
+ * the resampler: block sample m is time-aligned with wideband sample m * D, so frame positions divide exactly.  D = 1: K = 1, h = {1}, P = 0:
+ * mixing only.  The function returns the table's own error on a grid of 16 K + 1 frequencies per band, in cycles per wideband sample:
+ *   passband_error   worst |H(f) - 1| over [0, passband / D],  H(f) = sum_j h[j] e^(-2 pi i f (j - P))
+ *   stopband_level   worst |H(f)| over [stopband / D, 0.5]
+ *   error            their sum: 5.3e-5 for D = 2..8 at the default edges, inside the resampler's 1e-4 (-80 dB) target; 0 for D = 1
+ * Refused with DABGPU_ERR_INVALID_ARG: a null result, D outside 1..8, an edge that is NaN or negative, passband >= stopband (no
+ * transition), stopband above 0.5 * D (beyond what the wideband stream can hold).
+ *
+ * Split.  Channel c of input stream s has freq_q64 (cycles per WIDEBAND sample, two's complement), phase0_q64 and gain.  With the bank's
+ * 64-bit output position pos, the bank's `start` and wideband input x_s[0 .. n_in):
+ *   v_c[n] = x_s[n] rotated by (cos, sin)(-(phase0 + n * freq)): the 64-bit phase is exact, its angle the top 24 bits (ch_osc_cycles,
+ *            ch_cos_sin of the channel model), the product order the channel model's; both words 0 skip the rotation
+ *   y_c[m] = gain * sum_{j < K} h[j] * v_c[(pos + m) * D + start - P + j], re and im one chain each in ascending j, the first term the plain
+ *            product and every later one fmaf, the gain last
+ * Samples outside the input are zero, or (wrap) the index is taken modulo n_in; the oscillator always sees the absolute index n, so a + b
+ * outputs equal a and then b at any split and replays of a captured call continue the stream.  D = 1 with both words 0 and gain 1 returns
+ * the input shifted by `start`, bit for bit.  Mix-then-filter is the definition on purpose: the table stays real and bank-wide, and a
+ * channel is three words that _set_params can replace under a captured graph.
+ *
+ * Combine, the transpose over the same table: block streams x_c[0 .. n_in), wideband output sample n = pos + i:
+ *   u_c[n] = D * sum_m h[n - start - m * D + P] * x_c[m] over the m whose tap index lies in [0, K): K / D taps, ascending m, chained as above
+ *   y[n]   = sum_c rot(gain_c * u_c[n], +(phase0_c + n * freq_c)), channels in list order, the first term starts the sum, every later one
+ *            is added (re and im each one plain addition)
+ * as complex float or the u8 pairs of the modulator's quantiser.  Position, splitting and wrap rules are those of the split.
+ *
+ * dabgpu_channeliser_plan (host only): a channel list against a design.  Refused with DABGPU_ERR_INVALID_ARG: a null pointer, n_streams
+ * outside 1..1048576, n_channels outside 1..8 n_streams, a channel whose `stream` is >= n_streams or below its predecessor's (the list is
+ * sorted by stream), more than 8 channels on one stream, a gain that is not finite, |start| above DABGPU_CHANNELISER_MAX_START.  Geometry:
+ *   split_tile / combine_tile       output samples one workgroup produces (combine: DABGPU_CHANNELISER_COMBINE_ROWS * D)
+ *   split_window / combine_window   input samples it stages per stream / per channel
+ *   split_lds_bytes / combine_lds_bytes
+ * dabgpu_channeliser_freq_q64(offset_hz, rate_hz): offset / rate as the nearest Q64 word; 0 for NaN, a rate that is not positive, or an
+ * offset outside +- half the rate (+- half itself is accepted: both are the word 2^63).
+ * dabgpu_channeliser_input_needed(decim, position, start, n_out, *first, *count): the span of wideband indices that a split of n_out
+ * samples at `position` reads (before wrap or zero-fill; *first may be negative; *count = 0 for n_out = 0).
+ * dabgpu_channeliser_decim_for(rate_hz): the largest D <= 8 with rate / D >= 2.048 MHz; 0 when there is none (NaN, below 2.048 MHz). */
+#define DABGPU_CHANNELISER_TAPS_PER_PHASE 72
+#define DABGPU_CHANNELISER_MAX_DECIM 8
+#define DABGPU_CHANNELISER_MAX_CHANNELS 8                     /* per stream */
+#define DABGPU_CHANNELISER_SPLIT_TILE 512
+#define DABGPU_CHANNELISER_COMBINE_ROWS 128                   /* block-rate positions per workgroup: a tile is 128 D wideband samples */
+#define DABGPU_CHANNELISER_DEFAULT_PASSBAND 0.375
+#define DABGPU_CHANNELISER_DEFAULT_STOPBAND 0.4609375
+#define DABGPU_CHANNELISER_MAX_POSITION ((int64_t)1 << 58)    /* outputs; (position + n_out) * 8 + start stays a signed 64-bit number */
+#define DABGPU_CHANNELISER_MAX_START ((int64_t)1 << 61)
+typedef struct {
+    uint64_t freq_q64, phase0_q64;
+    float gain;
+    uint32_t stream;                                          /* split: the input stream it reads; combine: the output stream it joins */
+} dabgpu_channeliser_channel;
+typedef struct {
+    int32_t decim, taps;
+    double passband_cycles, stopband_cycles, cutoff_cycles, beta;
+    double passband_error, stopband_level, error;
+    float table[DABGPU_CHANNELISER_TAPS_PER_PHASE * DABGPU_CHANNELISER_MAX_DECIM];
+} dabgpu_channeliser_filter;
+typedef struct {
+    uint32_t decim, taps, split_tile, split_window, split_lds_bytes, combine_tile, combine_window, combine_lds_bytes;
+} dabgpu_channeliser_geometry;
+int dabgpu_channeliser_design(int decim, double passband_cycles, double stopband_cycles, dabgpu_channeliser_filter *out);
+int dabgpu_channeliser_plan(const dabgpu_channeliser_channel *channels, size_t n_channels, size_t n_streams, int64_t start,
+                            const dabgpu_channeliser_filter *design, dabgpu_channeliser_geometry *out);
+uint64_t dabgpu_channeliser_freq_q64(double offset_hz, double rate_hz);
+int dabgpu_channeliser_input_needed(int decim, uint64_t position, int64_t start, size_t n_out, int64_t *first, uint64_t *count);
+int dabgpu_channeliser_decim_for(double rate_hz);
+
+/* Channeliser bank: the design's table, n_channels channels on n_streams wideband streams, `start` and the position on the device.  The
+ * buffer rules are the channel bank's.  Split: d_in holds n_streams wideband rows (in_stride_samples even and >= n_in, or 0 = one shared
+ * row), d_out n_channels rows of n_out complex float, row c = channel c of the list.  Combine: d_in holds n_channels block rows, d_out
+ * n_streams rows of n_out wideband samples, complex float or u8 pairs; a stream with no channel is written as zeros.  d_in and d_out
+ * 16-byte aligned, out_stride_bytes 0 or a multiple of 16 that holds n_out samples; nothing else is written.  A call is two launches on
+ * `stream` -- the kernel, then a one-thread kernel that adds n_out to the position -- and changes no host state: it may be captured in a
+ * HIP graph and replays continue the stream.  The position counts output samples of the calls made (block samples for a split, wideband
+ * samples for a combine; one bank serves one direction at a time), 0 at creation; _seek sets it (at most
+ * DABGPU_CHANNELISER_MAX_POSITION).  _set_params replaces every channel and `start`, ordered on `stream`; the tile, window and LDS bytes
+ * and the room for the list are fixed at creation, so it refuses (DABGPU_ERR_INVALID_ARG) a list with more channels than the bank was
+ * created with (fewer are accepted: the rows of the channels left out are not written) and whatever dabgpu_channeliser_plan refuses.
+ * The decimation is the design's and cannot change in a bank: tile, window and LDS bytes depend on it alone, so the channel count is
+ * all of the plan that a new list can exceed.
+ * Above 48 KB of LDS (split, D >= 6) the kernel's limit is raised once at creation. */
+typedef struct dabgpu_channeliser_bank dabgpu_channeliser_bank;
+int dabgpu_channeliser_bank_create(dabgpu_ctx *ctx, const dabgpu_channeliser_channel *h_channels, size_t n_channels, size_t n_streams,
+                                   int64_t start, const dabgpu_channeliser_filter *design, dabgpu_channeliser_bank **out);
+void dabgpu_channeliser_bank_destroy(dabgpu_channeliser_bank *bank);
+int dabgpu_channeliser_bank_set_params(dabgpu_channeliser_bank *bank, const dabgpu_channeliser_channel *h_channels, size_t n_channels,
+                                       int64_t start, void *stream);
+int dabgpu_channeliser_bank_seek(dabgpu_channeliser_bank *bank, uint64_t position, void *stream);
+int dabgpu_channeliser_bank_split(dabgpu_channeliser_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_in, int wrap,
+                                  size_t n_out, float *d_out, size_t out_stride_bytes, void *stream);
+int dabgpu_channeliser_bank_split_host_sync(dabgpu_channeliser_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_in, int wrap,
+                                            size_t n_out, float *h_out, size_t out_stride_bytes);
+int dabgpu_channeliser_bank_combine(dabgpu_channeliser_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_in, int wrap,
+                                    size_t n_out, void *d_out, int out_format, size_t out_stride_bytes, float u8_scale, void *stream);
+int dabgpu_channeliser_bank_combine_host_sync(dabgpu_channeliser_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_in,
+                                              int wrap, size_t n_out, void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * TII: transmitter identification information in the NULL symbol of mode I, both directions (every other mode returns
  * DABGPU_ERR_INVALID_ARG).  The reference has no TII code; this section is the definition.  It is EN 300 401 clause 14.8.1 as recalled:
  * THE NUMBERING OF p FOLLOWS THE TABLE BELOW AND HAS NOT BEEN CHECKED AGAINST TABLE 38 of the standard.

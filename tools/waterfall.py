@@ -11,8 +11,12 @@ on a fading bank (dabgpu.Channel(..., fading=)), a fading seed per receiver, SNR
 With --clock-ppm X[,Y...] the run is the white-noise channel followed by the resampler (dabgpu.Resampler behind dabgpu.Channel: the noise is
 resampled too, as at a receiver's ADC) at a sampling-clock error of X ppm (step 1 + X 1e-6), one table per error, and the tables are
 APPENDED to --out: the clock error's place in the sensitivity record.
+With --adjacent-db A[,B...] [--adjacent-sides 1|2] the run is the white-noise channel followed by the combiner and the channeliser
+(dabgpu.Channeliser, D = 4): the block 300 kHz above the centre of an 8.192 MS/s capture with a neighbour 1.712 MHz above it (sides = 1) or
+to either side (2, the default), A dB above the wanted block's signal power -- the clean transmission rolled by 50001 and 120007 samples --,
+then split back out; one table per level, APPENDED to --out: the adjacent block's place in the sensitivity record.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
-                              [--clock-ppm X[,Y...]]"""
+                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2]"""
 import argparse
 import math
 import os
@@ -37,7 +41,12 @@ def main():
     ap.add_argument("--doppler-hz", type=float, default=None)
     ap.add_argument("--profile", default=None)
     ap.add_argument("--clock-ppm", default=None)
+    ap.add_argument("--adjacent-db", default=None)
+    ap.add_argument("--adjacent-sides", type=int, default=2, choices=(1, 2))
     a = ap.parse_args()
+    if a.adjacent_db is not None and (a.doppler_hz is not None or a.clock_ppm is not None):
+        ap.error("--adjacent-db is not available with --doppler-hz or --clock-ppm")
+    adjacent_db = [float(v) for v in a.adjacent_db.split(",")] if a.adjacent_db is not None else []
     if a.clock_ppm is not None and a.doppler_hz is not None:
         ap.error("--clock-ppm is not available with --doppler-hz")
     clock_ppm = [float(v) for v in a.clock_ppm.split(",")] if a.clock_ppm is not None else []
@@ -64,8 +73,17 @@ def main():
     d_iq = torch.zeros((F * S, 2), dtype=torch.float32, device="cuda")
     bank.transmit_frames(torch.from_numpy(fib).cuda(), torch.from_numpy(pay).cuda(), F, d_iq)
     n_out = F * S + 4096
-    n_rx = n_out + (256 if clock_ppm else 0)                                  # (the resampler reads ahead of its output)
-    d_rx = torch.zeros((E, n_rx, 2), dtype=torch.float32, device="cuda")
+    n_rx = n_out + (256 if clock_ppm or adjacent_db else 0)                   # (the resampler and the combiner read ahead of their output)
+    ADJ_D, ADJ_RATE, ADJ_OFFSET, ADJ_SPACING, ADJ_ROLLS = 4, 8192000.0, 300000.0, 1712000.0, (50001, 120007)
+    n_rows = 1 + (a.adjacent_sides if adjacent_db else 0)
+    n_wide = n_out * ADJ_D + 72 * ADJ_D
+    # with neighbours a receiver has n_rows block rows: the channel writes row 0, the others hold the clean transmission rolled
+    d_rows = torch.zeros((E, n_rows, n_rx, 2), dtype=torch.float32, device="cuda")
+    d_rx = d_rows[:, 0]
+    for k, roll in enumerate(ADJ_ROLLS[2 - a.adjacent_sides:] if adjacent_db else ()):
+        d_rows[:, 1 + k, :F * S] = torch.roll(d_iq, roll, 0)
+    d_wide = torch.zeros((E, n_wide, 2), dtype=torch.float32, device="cuda") if adjacent_db else None
+    d_back = torch.zeros((E, n_out, 2), dtype=torch.float32, device="cuda") if adjacent_db else None
     d_rs = torch.zeros((E, n_out, 2), dtype=torch.float32, device="cuda") if clock_ppm else None
     sdt, rdt = np.dtype(dabgpu.SYNC_STATE_DTYPE), np.dtype(dabgpu.RESULT_DTYPE)
     cifs = torch.from_numpy(pay.reshape(4 * F, nb)).cuda()
@@ -75,20 +93,33 @@ def main():
             f"(per point: {', '.join(f'{name} {E * (4 * F - 15) * sum(spans[i][1] for i in range(len(subs)) if owner[i] == li)}' for li, (name, _) in enumerate(LEVELS))} bytes).  "
             "No carrier or timing offset.  `python tools/waterfall.py`.", ""]
     verdicts = []
-    profiles, fading = [(n, t, None) for n, t in PROFILES], None
+    profiles, fading = [(n, t, None, None) for n, t in PROFILES], None
+    if adjacent_db:
+        text = [f"# Adjacent blocks (appended by `python tools/waterfall.py --adjacent-db {a.adjacent_db} --adjacent-sides {a.adjacent_sides}`)", "",
+                f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The white-noise channel of the first table followed by the combiner and the "
+                f"channeliser (D = 4): the block {ADJ_OFFSET / 1e3:g} kHz above the centre of an 8.192 MS/s capture, a neighbour 1.712 MHz "
+                f"{'to either side' if a.adjacent_sides == 2 else 'above it'} (the clean transmission rolled by {' and '.join(str(r) for r in ADJ_ROLLS[2 - a.adjacent_sides:])} samples), "
+                f"each the given level above the wanted block's signal power; {E} receivers x {F} mode I frames per point, byte counts per point as above.", ""]
+        profiles = [(f"white noise, neighbour{'s' if a.adjacent_sides == 2 else ''} {adb:+g} dB", PROFILES[0][1], None, adb) for adb in adjacent_db]
     if clock_ppm:
         text = [f"# Sampling-clock error (appended by `python tools/waterfall.py --clock-ppm {a.clock_ppm}`)", "",
                 f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The white-noise channel of the first table followed by the resampler "
                 f"(step 1 + ppm 1e-6, the noise resampled too): {E} receivers x {F} mode I frames per point, byte counts per point as above.  The frame start drifts "
                 "by ppm 1e-6 x 196608 samples per frame; every frame is synchronised from a slice at its nominal position.", ""]
-        profiles = [(f"white noise, sampling clock {ppm:g} ppm off", PROFILES[0][1], ppm) for ppm in clock_ppm]
+        profiles = [(f"white noise, sampling clock {ppm:g} ppm off", PROFILES[0][1], ppm, None) for ppm in clock_ppm]
     if a.doppler_hz is not None:
         prof = dabgpu.channel_profile(a.profile or "tu6")
-        profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"], None)]
+        profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"], None, None)]
         fading = dabgpu.channel_fading_plan([dabgpu.channel_stream(taps=prof["taps"]) for _ in range(E)],
                                             [dabgpu.channel_fading_spec(a.doppler_hz / 2.048e6, 5000 + e, prof["kinds"], prof["rice_k"], prof["los_cos"])
                                              for e in range(E)])
-    for pname, taps, ppm in profiles:
+    for pname, taps, ppm, adb in profiles:
+        comb = spl = None
+        if adb is not None:
+            offs = ([ADJ_OFFSET - ADJ_SPACING] if a.adjacent_sides == 2 else []) + [ADJ_OFFSET + ADJ_SPACING]
+            wanted = [dabgpu.channeliser_channel(dabgpu.channeliser_freq(ADJ_OFFSET, ADJ_RATE), 0, 1.0, e) for e in range(E)]
+            both = [c for e in range(E) for c in [wanted[e]] + [dabgpu.channeliser_channel(dabgpu.channeliser_freq(o, ADJ_RATE), 0, 10.0 ** (adb / 20.0), e) for o in offs]]
+            comb, spl = dabgpu.Channeliser(ctx, both, E, ADJ_D), dabgpu.Channeliser(ctx, wanted, E, ADJ_D)
         rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
         rows = []
@@ -97,8 +128,13 @@ def main():
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
             ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(E)])
             ch.seek(0)
-            ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rx * 8)
+            ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rows * n_rx * 8)
             d_use = d_rx
+            if comb is not None:
+                comb.seek(0); spl.seek(0)
+                comb.combine(d_rows, n_rx, n_wide, d_wide, in_stride_samples=n_rx, out_stride_bytes=n_wide * 8)
+                spl.split(d_wide, n_wide, n_out, d_back, in_stride_samples=n_wide, out_stride_bytes=n_out * 8)
+                d_use = d_back
             if rs is not None:
                 rs.seek(0)
                 rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
@@ -129,6 +165,8 @@ def main():
         ch.close()
         if rs is not None:
             rs.close()
+        if comb is not None:
+            comb.close(); spl.close()
         text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
         text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
         # acceptance: error-free at the top, non-increasing within counting error, required SNR ordered by level
@@ -148,7 +186,7 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    open(a.out, "a" if clock_ppm else "w").write(("\n" if clock_ppm else "") + text)
+    open(a.out, "a" if clock_ppm or adjacent_db else "w").write(("\n" if clock_ppm or adjacent_db else "") + text)
     return 0 if all(verdicts) else 1
 
 
