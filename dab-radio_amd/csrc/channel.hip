@@ -18,6 +18,7 @@
 #include "dabgpu_internal.h"
 #include "channel_core.h"
 #include "channel_device.h"
+#include "signal_bank.h"
 
 namespace dabgpu {
 
@@ -112,9 +113,6 @@ void channel_kernel(const dabgpu_channel_stream* __restrict__ params, const uint
     }
 }
 
-// behind the channel kernel on the same stream: the next call (or graph replay) continues where this one ended
-__global__ void channel_advance_kernel(uint64_t* pos, uint64_t n) { *pos += n; }
-
 // channel_fading.hip
 void ch_launch_fading(const dabgpu_channel_stream* d_params, const dabgpu_channel_fading_stream* d_tables, const uint64_t* d_pos,
                       const dabgpu_channel_geometry& geom, int tiles, unsigned grid, const float* d_in, size_t in_stride, size_t n_in, int wrap, size_t n_out,
@@ -124,30 +122,14 @@ void ch_launch_fading(const dabgpu_channel_stream* d_params, const dabgpu_channe
 
 using namespace dabgpu;
 
-struct dabgpu_channel_bank {
-    dabgpu_ctx* ctx = nullptr;
+struct dabgpu_channel_bank : SignalBank {         // d_mem: position (16 bytes) | parameters
     size_t n = 0;
     dabgpu_channel_geometry geom = {};
-    void* d_mem = nullptr;                      // one allocation: position (16 bytes) | parameters
-    uint64_t* d_pos = nullptr;
     dabgpu_channel_stream* d_params = nullptr;
     dabgpu_channel_fading_stream* d_fading = nullptr;   // a fading bank's tables (its own allocation); null: a plain bank
     std::vector<dabgpu_channel_stream> h_params;        // a fading bank keeps its parameters and tables on the host: _set_fading and
     std::vector<dabgpu_channel_fading_stream> h_tables; // _set_params check the one against the other (n_taps may grow past checked kinds)
-    void* buf[2] = {};                          // host form: [0] input, [1] output (grow only)
-    size_t buf_bytes[2] = {};
 };
-
-static int ch_buffer(dabgpu_channel_bank* b, int which, size_t bytes, void** out) {
-    int st = DABGPU_OK;
-    if (b->buf_bytes[which] < bytes) {
-        if (b->buf[which]) { DABGPU_CK(hipDeviceSynchronize()); DABGPU_CK(hipFree(b->buf[which])); b->buf[which] = nullptr; b->buf_bytes[which] = 0; }
-        DABGPU_CK(hipMalloc(&b->buf[which], bytes));
-        b->buf_bytes[which] = bytes;
-    }
-    *out = b->buf[which];
-    return st;
-}
 
 static int ch_launch(dabgpu_channel_bank* b, const float* d_in, size_t in_stride, size_t n_in, int wrap, size_t n_out, void* d_out, int out_format,
                      size_t out_stride_bytes, float u8_scale, hipStream_t s) {
@@ -156,19 +138,16 @@ static int ch_launch(dabgpu_channel_bank* b, const float* d_in, size_t in_stride
     const bool stage = b->geom.staged != 0;
     const size_t lds = stage ? (size_t)(CH_BLK + b->geom.halo + 2) * 8 : 0;
     const chf2* in = reinterpret_cast<const chf2*>(d_in);
-    if (b->d_fading) {
-        ch_launch_fading(b->d_params, b->d_fading, b->d_pos, b->geom, tiles, grid, d_in, in_stride, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, s);
-        hipLaunchKernelGGL(channel_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
-        return dabgpu_check_hip(hipGetLastError(), "channel_fading_kernel launch");
-    }
 #define CH_GO(OUT, STAGE)                                                                                                                     \
     hipLaunchKernelGGL((channel_kernel<OUT, STAGE>), dim3(grid), dim3(256), lds, s, b->d_params, b->d_pos, in, in_stride, (int64_t)n_in, wrap, \
                        (uint32_t)n_out, tiles, static_cast<uint8_t*>(d_out), out_stride_bytes, u8_scale)
-    if (out_format == DABGPU_IQ_RAW_F32L) { if (stage) CH_GO(DABGPU_IQ_RAW_F32L, true); else CH_GO(DABGPU_IQ_RAW_F32L, false); }
+    if (b->d_fading)
+        ch_launch_fading(b->d_params, b->d_fading, b->d_pos, b->geom, tiles, grid, d_in, in_stride, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, s);
+    else if (out_format == DABGPU_IQ_RAW_F32L) { if (stage) CH_GO(DABGPU_IQ_RAW_F32L, true); else CH_GO(DABGPU_IQ_RAW_F32L, false); }
     else { if (stage) CH_GO(DABGPU_IQ_RAW_U8, true); else CH_GO(DABGPU_IQ_RAW_U8, false); }
 #undef CH_GO
-    hipLaunchKernelGGL(channel_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
-    return dabgpu_check_hip(hipGetLastError(), "channel_kernel launch");
+    sb_enqueue_advance(b->d_pos, n_out, s);
+    return dabgpu_check_hip(hipGetLastError(), b->d_fading ? "channel_fading_kernel launch" : "channel_kernel launch");
 }
 
 static int ch_create(const char* who, dabgpu_ctx* c, size_t n_streams, const dabgpu_channel_stream* h_params, const dabgpu_channel_fading_stream* h_tables,
@@ -190,11 +169,9 @@ static int ch_create(const char* who, dabgpu_ctx* c, size_t n_streams, const dab
         if ((st = dabgpu_check_hip(hipMalloc((void**)&b->d_fading, table_bytes), "hipMalloc(channel fading tables)"))) return fail(st);
         if ((st = dabgpu_stage_h2d(c, b->d_fading, h_tables, table_bytes, c->stream))) return fail(st);
     }
-    const size_t bytes = 16 + n_streams * sizeof(dabgpu_channel_stream);
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_mem, bytes), "hipMalloc(channel bank)"))) return fail(st);
-    b->d_pos = static_cast<uint64_t*>(b->d_mem);
-    b->d_params = reinterpret_cast<dabgpu_channel_stream*>(static_cast<uint8_t*>(b->d_mem) + 16);
-    if ((st = dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, 16, c->stream), "hipMemsetAsync(channel position)"))) return fail(st);
+    uint8_t* payload;
+    if ((st = sb_alloc(b, n_streams * sizeof(dabgpu_channel_stream), "channel", &payload))) return fail(st);
+    b->d_params = reinterpret_cast<dabgpu_channel_stream*>(payload);
     if ((st = dabgpu_stage_h2d(c, b->d_params, h_params, n_streams * sizeof(dabgpu_channel_stream), c->stream))) return fail(st);
     if ((st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(channel_bank_create)"))) return fail(st);
     *out = b;
@@ -224,12 +201,7 @@ int dabgpu_channel_bank_set_fading(dabgpu_channel_bank* b, const dabgpu_channel_
 
 void dabgpu_channel_bank_destroy(dabgpu_channel_bank* b) {
     if (!b) return;
-    if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
-        (void)hipDeviceSynchronize();
-        for (void* p : b->buf) if (p) (void)hipFree(p);
-        if (b->d_mem) (void)hipFree(b->d_mem);
-        if (b->d_fading) (void)hipFree(b->d_fading);
-    }
+    if (sb_release(b) && b->d_fading) (void)hipFree(b->d_fading);
     delete b;
 }
 
@@ -247,10 +219,7 @@ int dabgpu_channel_bank_set_params(dabgpu_channel_bank* b, const dabgpu_channel_
 }
 
 int dabgpu_channel_bank_seek(dabgpu_channel_bank* b, uint64_t position, void* stream) {
-    if (!b) { dabgpu_set_error("channel_bank_seek: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    if (position > (uint64_t)DABGPU_CHANNEL_MAX_POSITION) { dabgpu_set_error("channel_bank_seek: position above 2^62"); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(b->ctx);
-    return dabgpu_stage_h2d(b->ctx, b->d_pos, &position, sizeof(position), (hipStream_t)stream);
+    return sb_seek(b, "channel_bank_seek", position, (uint64_t)DABGPU_CHANNEL_MAX_POSITION, "2^62", stream);
 }
 
 int dabgpu_channel_bank_apply(dabgpu_channel_bank* b, const float* d_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out, void* d_out,
@@ -266,25 +235,13 @@ int dabgpu_channel_bank_apply(dabgpu_channel_bank* b, const float* d_in, size_t 
 int dabgpu_channel_bank_apply_host_sync(dabgpu_channel_bank* b, const float* h_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
                                         void* h_out, int out_format, size_t out_stride_bytes, float u8_scale) {
     if (!b) { dabgpu_set_error("channel_bank_apply_host_sync: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    int st = dabgpu_host_channel_check_apply("channel_bank_apply_host_sync", b->n, h_in, in_stride_samples, n_in, n_out, h_out, out_format,
-                                             &out_stride_bytes, u8_scale, false);
+    const int st = dabgpu_host_channel_check_apply("channel_bank_apply_host_sync", b->n, h_in, in_stride_samples, n_in, n_out, h_out, out_format,
+                                                   &out_stride_bytes, u8_scale, false);
     if (st || n_out == 0) return st;
-    dabgpu_ctx* c = b->ctx;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    hipStream_t s = c->stream;
-    // on the device: input rows an even count apart, output rows a multiple of 16 bytes apart
-    const size_t row_bytes = n_out * (out_format == DABGPU_IQ_RAW_F32L ? 8 : 2), d_out_stride = (row_bytes + 15) & ~(size_t)15;
-    const size_t d_in_stride = in_stride_samples ? (n_in + 1) & ~(size_t)1 : 0, n_rows = in_stride_samples ? b->n : 1;
-    void *d_in, *d_out;
-    if ((st = ch_buffer(b, 0, (n_rows * (d_in_stride ? d_in_stride : n_in)) * 8, &d_in))) return st;
-    if ((st = ch_buffer(b, 1, b->n * d_out_stride, &d_out))) return st;
-    DABGPU_CK(hipMemcpy2DAsync(d_in, (d_in_stride ? d_in_stride : n_in) * 8, h_in, (in_stride_samples ? in_stride_samples : n_in) * 8, n_in * 8, n_rows,
-                               hipMemcpyHostToDevice, s));
-    if ((st = ch_launch(b, static_cast<const float*>(d_in), d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s))) return st;
-    DABGPU_CK(hipMemcpy2DAsync(h_out, out_stride_bytes, d_out, d_out_stride, row_bytes, b->n, hipMemcpyDeviceToHost, s));   // the rows only
-    DABGPU_CK(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    return sb_host_round_trip(b, b->n, b->n, false, h_in, in_stride_samples, n_in, n_out, h_out, out_format, out_stride_bytes,
+                              [&](const float* d_in, size_t d_in_stride, void* d_out, size_t d_out_stride, hipStream_t s) {
+                                  return ch_launch(b, d_in, d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s);
+                              });
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 #include "dabgpu_internal.h"
 #include "channelise_core.h"
 #include "channel_device.h"
+#include "signal_bank.h"
 
 namespace dabgpu {
 
@@ -202,39 +203,20 @@ void channelise_combine_kernel(const dabgpu_channeliser_channel* __restrict__ ch
     }
 }
 
-// behind the kernel on the same stream: the next call (or graph replay) continues where this one ended
-__global__ void channelise_advance_kernel(uint64_t* pos, uint64_t n) { *pos += n; }
-
 }  // namespace dabgpu
 
 using namespace dabgpu;
 
-struct dabgpu_channeliser_bank {
-    dabgpu_ctx* ctx = nullptr;
+struct dabgpu_channeliser_bank : SignalBank {     // d_mem: position (16 bytes) | table | start (16 bytes) | first_of | channels
     size_t n_streams = 0, capacity = 0, n_channels = 0;                      // channels the bank has room for / of the list in force
     int decim = 1;
     dabgpu_channeliser_geometry geom = {};
-    void* d_mem = nullptr;                      // one allocation: position (16 bytes) | table | start (16 bytes) | first_of | channels
-    uint64_t* d_pos = nullptr;
     float* d_table = nullptr;
     int64_t* d_start = nullptr;
     uint32_t* d_first = nullptr;
     dabgpu_channeliser_channel* d_channels = nullptr;
     size_t first_bytes = 0;
-    void* buf[2] = {};                          // host form: [0] input, [1] output (grow only)
-    size_t buf_bytes[2] = {};
 };
-
-static int cs_buffer(dabgpu_channeliser_bank* b, int which, size_t bytes, void** out) {
-    int st = DABGPU_OK;
-    if (b->buf_bytes[which] < bytes) {
-        if (b->buf[which]) { DABGPU_CK(hipDeviceSynchronize()); DABGPU_CK(hipFree(b->buf[which])); b->buf[which] = nullptr; b->buf_bytes[which] = 0; }
-        DABGPU_CK(hipMalloc(&b->buf[which], bytes));
-        b->buf_bytes[which] = bytes;
-    }
-    *out = b->buf[which];
-    return st;
-}
 
 // start | first_of | channels as one block, as it lies on the device
 static int cs_upload(dabgpu_channeliser_bank* b, const char* who, const dabgpu_channeliser_channel* h_channels, size_t n_channels, int64_t start,
@@ -267,7 +249,7 @@ static int cs_launch_split(dabgpu_channeliser_bank* b, const float* d_in, size_t
         CS_EACH_D(CS_GO)
 #undef CS_GO
     }
-    hipLaunchKernelGGL(channelise_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
+    sb_enqueue_advance(b->d_pos, n_out, s);
     return dabgpu_check_hip(hipGetLastError(), "channelise_split_kernel launch");
 }
 
@@ -289,7 +271,7 @@ static int cs_launch_combine(dabgpu_channeliser_bank* b, const float* d_in, size
 #undef CS_GO
 #undef CS_GO2
     }
-    hipLaunchKernelGGL(channelise_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
+    sb_enqueue_advance(b->d_pos, n_out, s);
     return dabgpu_check_hip(hipGetLastError(), "channelise_combine_kernel launch");
 }
 
@@ -321,14 +303,12 @@ int dabgpu_channeliser_bank_create(dabgpu_ctx* c, const dabgpu_channeliser_chann
     }
     const size_t table_bytes = sizeof(design->table), params_bytes = 16 + b->first_bytes + n_channels * sizeof(dabgpu_channeliser_channel);
     static_assert(sizeof(dabgpu_channeliser_filter::table) % 16 == 0 && sizeof(dabgpu_channeliser_channel) == 24, "the layout of the bank's block");
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_mem, 16 + table_bytes + params_bytes), "hipMalloc(channeliser bank)"))) return fail(st);
-    uint8_t* base = static_cast<uint8_t*>(b->d_mem);
-    b->d_pos = reinterpret_cast<uint64_t*>(base);
-    b->d_table = reinterpret_cast<float*>(base + 16);
-    b->d_start = reinterpret_cast<int64_t*>(base + 16 + table_bytes);
-    b->d_first = reinterpret_cast<uint32_t*>(base + 16 + table_bytes + 16);
-    b->d_channels = reinterpret_cast<dabgpu_channeliser_channel*>(base + 16 + table_bytes + 16 + b->first_bytes);
-    if ((st = dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, 16, c->stream), "hipMemsetAsync(channeliser position)"))) return fail(st);
+    uint8_t* payload;
+    if ((st = sb_alloc(b, table_bytes + params_bytes, "channeliser", &payload))) return fail(st);
+    b->d_table = reinterpret_cast<float*>(payload);
+    b->d_start = reinterpret_cast<int64_t*>(payload + table_bytes);
+    b->d_first = reinterpret_cast<uint32_t*>(payload + table_bytes + 16);
+    b->d_channels = reinterpret_cast<dabgpu_channeliser_channel*>(payload + table_bytes + 16 + b->first_bytes);
     if ((st = dabgpu_stage_h2d(c, b->d_table, design->table, table_bytes, c->stream))) return fail(st);
     if ((st = cs_upload(b, "channeliser_bank_create", h_channels, n_channels, start, c->stream))) return fail(st);
     if ((st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(channeliser_bank_create)"))) return fail(st);
@@ -338,11 +318,7 @@ int dabgpu_channeliser_bank_create(dabgpu_ctx* c, const dabgpu_channeliser_chann
 
 void dabgpu_channeliser_bank_destroy(dabgpu_channeliser_bank* b) {
     if (!b) return;
-    if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
-        (void)hipDeviceSynchronize();
-        for (void* p : b->buf) if (p) (void)hipFree(p);
-        if (b->d_mem) (void)hipFree(b->d_mem);
-    }
+    sb_release(b);
     delete b;
 }
 
@@ -357,10 +333,7 @@ int dabgpu_channeliser_bank_set_params(dabgpu_channeliser_bank* b, const dabgpu_
 }
 
 int dabgpu_channeliser_bank_seek(dabgpu_channeliser_bank* b, uint64_t position, void* stream) {
-    if (!b) { dabgpu_set_error("channeliser_bank_seek: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    if (position > (uint64_t)DABGPU_CHANNELISER_MAX_POSITION) { dabgpu_set_error("channeliser_bank_seek: position above 2^58"); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(b->ctx);
-    return dabgpu_stage_h2d(b->ctx, b->d_pos, &position, sizeof(position), (hipStream_t)stream);
+    return sb_seek(b, "channeliser_bank_seek", position, (uint64_t)DABGPU_CHANNELISER_MAX_POSITION, "2^58", stream);
 }
 
 int dabgpu_channeliser_bank_split(dabgpu_channeliser_bank* b, const float* d_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
@@ -384,44 +357,31 @@ int dabgpu_channeliser_bank_combine(dabgpu_channeliser_bank* b, const float* d_i
     return cs_launch_combine(b, d_in, in_stride_samples, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, (hipStream_t)stream);
 }
 
-// the host forms: rows to the device (input rows an even count apart, output rows a multiple of 16 bytes apart), the call, the rows back
-static int cs_host_call(dabgpu_channeliser_bank* b, bool split, const char* who, const float* h_in, size_t in_stride_samples, size_t n_in, int wrap,
-                        size_t n_out, void* h_out, int out_format, size_t out_stride_bytes, float u8_scale) {
-    const size_t in_rows = split ? b->n_streams : b->n_channels, out_rows = split ? b->n_channels : b->n_streams;
-    int st = dabgpu_host_channel_check_apply(who, 1, h_in, in_stride_samples, n_in, n_out, h_out, out_format, &out_stride_bytes, u8_scale, false);   // (the grid: cs_launch_*)
-    if (st || n_out == 0) return st;
-    dabgpu_ctx* c = b->ctx;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    hipStream_t s = c->stream;
-    const size_t row_bytes = n_out * (out_format == DABGPU_IQ_RAW_F32L ? 8 : 2), d_out_stride = (row_bytes + 15) & ~(size_t)15;
-    const size_t d_in_stride = in_stride_samples ? (n_in + 1) & ~(size_t)1 : 0, n_rows = in_stride_samples ? in_rows : 1;
-    void *d_in, *d_out;
-    if ((st = cs_buffer(b, 0, (n_rows * (d_in_stride ? d_in_stride : n_in)) * 8, &d_in))) return st;
-    if ((st = cs_buffer(b, 1, out_rows * d_out_stride, &d_out))) return st;
-    DABGPU_CK(hipMemcpy2DAsync(d_in, (d_in_stride ? d_in_stride : n_in) * 8, h_in, (in_stride_samples ? in_stride_samples : n_in) * 8, n_in * 8, n_rows,
-                               hipMemcpyHostToDevice, s));
-    DABGPU_CK(hipMemsetAsync(d_out, 0, out_rows * d_out_stride, s));         // (split: the rows of streams without a channel)
-    st = split ? cs_launch_split(b, static_cast<const float*>(d_in), d_in_stride, n_in, wrap, n_out, static_cast<float*>(d_out), d_out_stride, s)
-               : cs_launch_combine(b, static_cast<const float*>(d_in), d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s);
-    if (st) return st;
-    DABGPU_CK(hipMemcpy2DAsync(h_out, out_stride_bytes, d_out, d_out_stride, row_bytes, out_rows, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    return DABGPU_OK;
-}
-
+// the host forms zero the output rows first (split: the rows of streams without a channel)
 int dabgpu_channeliser_bank_split_host_sync(dabgpu_channeliser_bank* b, const float* h_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
                                             float* h_out, size_t out_stride_bytes) {
     if (!b) { dabgpu_set_error("channeliser_bank_split_host_sync: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    return cs_host_call(b, true, "channeliser_bank_split_host_sync", h_in, in_stride_samples, n_in, wrap, n_out, h_out, DABGPU_IQ_RAW_F32L, out_stride_bytes,
-                        1.0f);
+    // (the grid: cs_launch_split)
+    const int st = dabgpu_host_channel_check_apply("channeliser_bank_split_host_sync", 1, h_in, in_stride_samples, n_in, n_out, h_out, DABGPU_IQ_RAW_F32L,
+                                                   &out_stride_bytes, 1.0f, false);
+    if (st || n_out == 0) return st;
+    return sb_host_round_trip(b, b->n_streams, b->n_channels, true, h_in, in_stride_samples, n_in, n_out, h_out, DABGPU_IQ_RAW_F32L, out_stride_bytes,
+                              [&](const float* d_in, size_t d_in_stride, void* d_out, size_t d_out_stride, hipStream_t s) {
+                                  return cs_launch_split(b, d_in, d_in_stride, n_in, wrap, n_out, static_cast<float*>(d_out), d_out_stride, s);
+                              });
 }
 
 int dabgpu_channeliser_bank_combine_host_sync(dabgpu_channeliser_bank* b, const float* h_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
                                               void* h_out, int out_format, size_t out_stride_bytes, float u8_scale) {
     if (!b) { dabgpu_set_error("channeliser_bank_combine_host_sync: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    return cs_host_call(b, false, "channeliser_bank_combine_host_sync", h_in, in_stride_samples, n_in, wrap, n_out, h_out, out_format, out_stride_bytes,
-                        u8_scale);
+    // (the grid: cs_launch_combine)
+    const int st = dabgpu_host_channel_check_apply("channeliser_bank_combine_host_sync", 1, h_in, in_stride_samples, n_in, n_out, h_out, out_format,
+                                                   &out_stride_bytes, u8_scale, false);
+    if (st || n_out == 0) return st;
+    return sb_host_round_trip(b, b->n_channels, b->n_streams, true, h_in, in_stride_samples, n_in, n_out, h_out, out_format, out_stride_bytes,
+                              [&](const float* d_in, size_t d_in_stride, void* d_out, size_t d_out_stride, hipStream_t s) {
+                                  return cs_launch_combine(b, d_in, d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s);
+                              });
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "dabgpu_internal.h"
 #include "resample_core.h"
 #include "channel_device.h"
+#include "signal_bank.h"
 
 namespace dabgpu {
 
@@ -107,36 +108,17 @@ void resample_kernel(const dabgpu_resample_stream* __restrict__ params, const fl
     }
 }
 
-// behind the resampling kernel on the same stream: the next call (or graph replay) continues where this one ended
-__global__ void resample_advance_kernel(uint64_t* pos, uint64_t n) { *pos += n; }
-
 }  // namespace dabgpu
 
 using namespace dabgpu;
 
-struct dabgpu_resample_bank {
-    dabgpu_ctx* ctx = nullptr;
+struct dabgpu_resample_bank : SignalBank {        // d_mem: position (16 bytes) | table | parameters
     size_t n = 0;
     dabgpu_resample_geometry geom = {};
     uint64_t max_step_q62 = 0;
-    void* d_mem = nullptr;                      // one allocation: position (16 bytes) | table | parameters
-    uint64_t* d_pos = nullptr;
     float* d_table = nullptr;
     dabgpu_resample_stream* d_params = nullptr;
-    void* buf[2] = {};                          // host form: [0] input, [1] output (grow only)
-    size_t buf_bytes[2] = {};
 };
-
-static int rs_buffer(dabgpu_resample_bank* b, int which, size_t bytes, void** out) {
-    int st = DABGPU_OK;
-    if (b->buf_bytes[which] < bytes) {
-        if (b->buf[which]) { DABGPU_CK(hipDeviceSynchronize()); DABGPU_CK(hipFree(b->buf[which])); b->buf[which] = nullptr; b->buf_bytes[which] = 0; }
-        DABGPU_CK(hipMalloc(&b->buf[which], bytes));
-        b->buf_bytes[which] = bytes;
-    }
-    *out = b->buf[which];
-    return st;
-}
 
 static int rs_launch(dabgpu_resample_bank* b, const float* d_in, size_t in_stride, size_t n_in, int wrap, size_t n_out, void* d_out, int out_format,
                      size_t out_stride_bytes, float u8_scale, hipStream_t s) {
@@ -149,7 +131,7 @@ static int rs_launch(dabgpu_resample_bank* b, const float* d_in, size_t in_strid
                        (int64_t)n_in, wrap, (uint32_t)n_out, tiles, static_cast<uint8_t*>(d_out), out_stride_bytes, u8_scale, window_pairs)
     if (out_format == DABGPU_IQ_RAW_F32L) RS_GO(DABGPU_IQ_RAW_F32L); else RS_GO(DABGPU_IQ_RAW_U8);
 #undef RS_GO
-    hipLaunchKernelGGL(resample_advance_kernel, dim3(1), dim3(1), 0, s, b->d_pos, (uint64_t)n_out);
+    sb_enqueue_advance(b->d_pos, n_out, s);
     return dabgpu_check_hip(hipGetLastError(), "resample_kernel launch");
 }
 
@@ -176,13 +158,12 @@ int dabgpu_resample_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_re
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, most), "hipFuncSetAttribute(resample_kernel)")))
             return fail(st);
     }
-    const size_t table_bytes = sizeof(design->table), bytes = 16 + table_bytes + n_streams * sizeof(dabgpu_resample_stream);
+    const size_t table_bytes = sizeof(design->table);
     static_assert(sizeof(dabgpu_resample_filter::table) % 16 == 0, "the parameters behind the table stay 8-byte aligned");
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_mem, bytes), "hipMalloc(resample bank)"))) return fail(st);
-    b->d_pos = static_cast<uint64_t*>(b->d_mem);
-    b->d_table = reinterpret_cast<float*>(static_cast<uint8_t*>(b->d_mem) + 16);
-    b->d_params = reinterpret_cast<dabgpu_resample_stream*>(static_cast<uint8_t*>(b->d_mem) + 16 + table_bytes);
-    if ((st = dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, 16, c->stream), "hipMemsetAsync(resample position)"))) return fail(st);
+    uint8_t* payload;
+    if ((st = sb_alloc(b, table_bytes + n_streams * sizeof(dabgpu_resample_stream), "resample", &payload))) return fail(st);
+    b->d_table = reinterpret_cast<float*>(payload);
+    b->d_params = reinterpret_cast<dabgpu_resample_stream*>(payload + table_bytes);
     if ((st = dabgpu_stage_h2d(c, b->d_table, design->table, table_bytes, c->stream))) return fail(st);
     if ((st = dabgpu_stage_h2d(c, b->d_params, h_params, n_streams * sizeof(dabgpu_resample_stream), c->stream))) return fail(st);
     if ((st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(resample_bank_create)"))) return fail(st);
@@ -192,11 +173,7 @@ int dabgpu_resample_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_re
 
 void dabgpu_resample_bank_destroy(dabgpu_resample_bank* b) {
     if (!b) return;
-    if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
-        (void)hipDeviceSynchronize();
-        for (void* p : b->buf) if (p) (void)hipFree(p);
-        if (b->d_mem) (void)hipFree(b->d_mem);
-    }
+    sb_release(b);
     delete b;
 }
 
@@ -210,10 +187,7 @@ int dabgpu_resample_bank_set_params(dabgpu_resample_bank* b, const dabgpu_resamp
 }
 
 int dabgpu_resample_bank_seek(dabgpu_resample_bank* b, uint64_t position, void* stream) {
-    if (!b) { dabgpu_set_error("resample_bank_seek: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    if (position > (uint64_t)DABGPU_CHANNEL_MAX_POSITION) { dabgpu_set_error("resample_bank_seek: position above 2^62"); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(b->ctx);
-    return dabgpu_stage_h2d(b->ctx, b->d_pos, &position, sizeof(position), (hipStream_t)stream);
+    return sb_seek(b, "resample_bank_seek", position, (uint64_t)DABGPU_CHANNEL_MAX_POSITION, "2^62", stream);
 }
 
 int dabgpu_resample_bank_apply(dabgpu_resample_bank* b, const float* d_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out, void* d_out,
@@ -229,25 +203,13 @@ int dabgpu_resample_bank_apply(dabgpu_resample_bank* b, const float* d_in, size_
 int dabgpu_resample_bank_apply_host_sync(dabgpu_resample_bank* b, const float* h_in, size_t in_stride_samples, size_t n_in, int wrap, size_t n_out,
                                          void* h_out, int out_format, size_t out_stride_bytes, float u8_scale) {
     if (!b) { dabgpu_set_error("resample_bank_apply_host_sync: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    int st = dabgpu_host_channel_check_apply("resample_bank_apply_host_sync", b->n, h_in, in_stride_samples, n_in, n_out, h_out, out_format,
-                                             &out_stride_bytes, u8_scale, false);
+    const int st = dabgpu_host_channel_check_apply("resample_bank_apply_host_sync", b->n, h_in, in_stride_samples, n_in, n_out, h_out, out_format,
+                                                   &out_stride_bytes, u8_scale, false);
     if (st || n_out == 0) return st;
-    dabgpu_ctx* c = b->ctx;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    hipStream_t s = c->stream;
-    // on the device: input rows an even count apart, output rows a multiple of 16 bytes apart
-    const size_t row_bytes = n_out * (out_format == DABGPU_IQ_RAW_F32L ? 8 : 2), d_out_stride = (row_bytes + 15) & ~(size_t)15;
-    const size_t d_in_stride = in_stride_samples ? (n_in + 1) & ~(size_t)1 : 0, n_rows = in_stride_samples ? b->n : 1;
-    void *d_in, *d_out;
-    if ((st = rs_buffer(b, 0, (n_rows * (d_in_stride ? d_in_stride : n_in)) * 8, &d_in))) return st;
-    if ((st = rs_buffer(b, 1, b->n * d_out_stride, &d_out))) return st;
-    DABGPU_CK(hipMemcpy2DAsync(d_in, (d_in_stride ? d_in_stride : n_in) * 8, h_in, (in_stride_samples ? in_stride_samples : n_in) * 8, n_in * 8, n_rows,
-                               hipMemcpyHostToDevice, s));
-    if ((st = rs_launch(b, static_cast<const float*>(d_in), d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s))) return st;
-    DABGPU_CK(hipMemcpy2DAsync(h_out, out_stride_bytes, d_out, d_out_stride, row_bytes, b->n, hipMemcpyDeviceToHost, s));   // the rows only
-    DABGPU_CK(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    return sb_host_round_trip(b, b->n, b->n, false, h_in, in_stride_samples, n_in, n_out, h_out, out_format, out_stride_bytes,
+                              [&](const float* d_in, size_t d_in_stride, void* d_out, size_t d_out_stride, hipStream_t s) {
+                                  return rs_launch(b, d_in, d_in_stride, n_in, wrap, n_out, d_out, out_format, d_out_stride, u8_scale, s);
+                              });
 }
 
 }  // extern "C"

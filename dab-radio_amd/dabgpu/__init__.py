@@ -520,6 +520,34 @@ def host_tables():
     return prs, mapper, tw
 
 
+class _Handle:
+    """owns one handle of the library, `_h`; `_destroy` names the function that releases it"""
+    _destroy = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _host_form(call, h_in, rows, n_out, fmt):
+    """a *_host_sync call into `rows` padded output rows: call(x, n_in, out, stride); -> [rows][n_out] complex64, or [rows][n_out][2] uint8"""
+    import numpy as np
+    x = np.ascontiguousarray(h_in, dtype=np.complex64)
+    sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
+    stride = (n_out * sb + 15) & ~15
+    out = np.zeros((rows, stride), np.uint8)
+    call(x, x.shape[-1], out, stride)
+    out = out[:, :n_out * sb]
+    return out.copy().view(np.complex64) if sb == 8 else out.reshape(rows, n_out, 2).copy()
+
+
 class Context:
     """One device + constant tables (dabgpu_create / dabgpu_destroy)."""
 
@@ -823,8 +851,9 @@ class Context:
         return out
 
 
-class StreamBank:
+class StreamBank(_Handle):
     """dabgpu_stream_bank: n unsynchronised receivers resident on the device (one OFDM_Demod each)"""
+    _destroy = "dabgpu_stream_bank_destroy"
 
     def __init__(self, ctx, n_streams, cfg=None, mode=1):
         self._ctx = ctx
@@ -833,17 +862,6 @@ class StreamBank:
         self._h = C.c_void_p()
         check(lib().dabgpu_stream_bank_create_mode(ctx._h, int(mode), n_streams, C.byref(cfg) if cfg is not None else None, C.byref(self._h)),
               "dabgpu_stream_bank_create_mode")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_stream_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, stream=None):
         check(lib().dabgpu_stream_bank_reset(self._h, Context._stream(stream)), "dabgpu_stream_bank_reset")
@@ -889,8 +907,9 @@ class StreamBank:
         return out
 
 
-class TxBank:
+class TxBank(_Handle):
     """dabgpu_tx_bank: the channel encoder of n ensembles sharing one multiplex (FIB bodies + sub-channel bytes -> frame bits -> IQ)"""
+    _destroy = "dabgpu_tx_bank_destroy"
 
     def __init__(self, ctx, n_ensembles, subchannels):
         self._ctx = ctx
@@ -901,17 +920,6 @@ class TxBank:
         arr = (SubChannel * n)(*subchannels) if n else None
         self._h = C.c_void_p()
         check(lib().dabgpu_tx_bank_create(ctx._h, n_ensembles, arr, n, C.byref(self._h)), "dabgpu_tx_bank_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_tx_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, stream=None):
         check(lib().dabgpu_tx_bank_reset(self._h, Context._stream(stream)), "dabgpu_tx_bank_reset")
@@ -1015,9 +1023,10 @@ def channel_profile(name):
             "los_cos": list(S.los_cos[:n])}
 
 
-class Channel:
+class Channel(_Handle):
     """dabgpu_channel_bank: multipath, carrier offset, timing offset and noise for n streams; the stream position lives on the device.
     fading = the tables of channel_fading_plan: a fading bank (Rayleigh / Rice taps with Doppler)"""
+    _destroy = "dabgpu_channel_bank_destroy"
 
     def __init__(self, ctx, streams, fading=None):
         self._ctx = ctx
@@ -1039,17 +1048,6 @@ class Channel:
     def set_fading(self, fading, stream=None):
         check(lib().dabgpu_channel_bank_set_fading(self._h, self._tables(fading), Context._stream(stream)), "dabgpu_channel_bank_set_fading")
 
-    def close(self):
-        if self._h:
-            lib().dabgpu_channel_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_params(self, streams, stream=None):
         assert len(streams) == self.n
         arr = (ChannelStream * self.n)(*streams)
@@ -1065,17 +1063,10 @@ class Channel:
                                               float(u8_scale), Context._stream(stream)), "dabgpu_channel_bank_apply")
 
     def apply_host(self, h_in, n_out, in_stride_samples=0, wrap=False, out_format=None, u8_scale=1.0):
-        import numpy as np
         fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
-        x = np.ascontiguousarray(h_in, dtype=np.complex64)
-        n_in = x.shape[-1]
-        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
-        stride = (n_out * sb + 15) & ~15
-        out = np.zeros((self.n, stride), np.uint8)
-        check(lib().dabgpu_channel_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
-                                                        float(u8_scale)), "dabgpu_channel_bank_apply_host_sync")
-        out = out[:, :n_out * sb]
-        return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+        return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_channel_bank_apply_host_sync(
+            self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride, float(u8_scale)),
+            "dabgpu_channel_bank_apply_host_sync"), h_in, self.n, n_out, fmt)
 
 
 def resample_step(in_rate_hz=2048000.0, out_rate_hz=2048000.0, ppm=0.0):
@@ -1119,9 +1110,10 @@ def resample_input_needed(stream, position, n_out):
     return first.value, count.value
 
 
-class Resampler:
+class Resampler(_Handle):
     """dabgpu_resample_bank: arbitrary-ratio, fractional-delay resampling of n streams (a sampling-clock error, a capture rate); the stream
     position lives on the device.  design = None: a table for the largest step of `params` (at least 1), default passband"""
+    _destroy = "dabgpu_resample_bank_destroy"
 
     def __init__(self, ctx, params, design=None):
         self._ctx = ctx
@@ -1135,17 +1127,6 @@ class Resampler:
         arr = (ResampleStream * self.n)(*params)
         self._h = C.c_void_p()
         check(lib().dabgpu_resample_bank_create(ctx._h, self.n, arr, C.byref(design), C.byref(self._h)), "dabgpu_resample_bank_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_resample_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_params(self, params, stream=None):
         assert len(params) == self.n
@@ -1164,17 +1145,10 @@ class Resampler:
     def apply_host(self, h_in, n_out, in_stride_samples=0, wrap=False, out_format=None, u8_scale=1.0):
         """dabgpu_resample_bank_apply_host_sync: h_in complex64 [n_in] (shared, in_stride_samples = 0) or [n][n_in] with in_stride_samples =
         n_in, on the host -> [n][n_out] complex64, or [n][n_out][2] uint8 for the u8 format; returns when the output is there"""
-        import numpy as np
         fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
-        x = np.ascontiguousarray(h_in, dtype=np.complex64)
-        n_in = x.shape[-1]
-        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
-        stride = (n_out * sb + 15) & ~15
-        out = np.zeros((self.n, stride), np.uint8)
-        check(lib().dabgpu_resample_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
-                                                         float(u8_scale)), "dabgpu_resample_bank_apply_host_sync")
-        out = out[:, :n_out * sb]
-        return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+        return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_resample_bank_apply_host_sync(
+            self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride, float(u8_scale)),
+            "dabgpu_resample_bank_apply_host_sync"), h_in, self.n, n_out, fmt)
 
 
 def channeliser_freq(offset_hz, rate_hz):
@@ -1219,10 +1193,11 @@ def channeliser_input_needed(decim, position, start, n_out):
     return first.value, count.value
 
 
-class Channeliser:
+class Channeliser(_Handle):
     """dabgpu_channeliser_bank: split (wideband streams -> block streams, one row per channel of the list) and combine (block streams -> wideband
     streams); the list is sorted by stream, at most 8 channels per stream; the position lives on the device.  design: a ChanneliserFilter, or
     the decimation (default edges)"""
+    _destroy = "dabgpu_channeliser_bank_destroy"
 
     def __init__(self, ctx, channels, n_streams, design, start=0):
         self._ctx = ctx
@@ -1236,17 +1211,6 @@ class Channeliser:
         arr = (ChanneliserChannel * self.n_channels)(*channels)
         check(lib().dabgpu_channeliser_bank_create(ctx._h, arr, self.n_channels, self.n_streams, int(start), C.byref(design), C.byref(self._h)),
               "dabgpu_channeliser_bank_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_channeliser_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_params(self, channels, start=None, stream=None):
         """replaces the channel list; start = None keeps the bank's `start` (the one of its creation or of the last set_params)"""
@@ -1271,21 +1235,14 @@ class Channeliser:
                                                     out_stride_bytes, float(u8_scale), Context._stream(stream)), "dabgpu_channeliser_bank_combine")
 
     def _host(self, split, h_in, n_out, in_stride_samples, wrap, fmt, u8_scale):
-        import numpy as np
-        x = np.ascontiguousarray(h_in, dtype=np.complex64)
-        n_in = x.shape[-1]
-        rows = self.n_channels if split else self.n_streams
-        sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
-        stride = (n_out * sb + 15) & ~15
-        out = np.zeros((rows, stride), np.uint8)
-        if split:
-            check(lib().dabgpu_channeliser_bank_split_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), stride),
-                  "dabgpu_channeliser_bank_split_host_sync")
-        else:
-            check(lib().dabgpu_channeliser_bank_combine_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
-                                                                  float(u8_scale)), "dabgpu_channeliser_bank_combine_host_sync")
-        out = out[:, :n_out * sb]
-        return out.copy().view(np.complex64) if sb == 8 else out.reshape(rows, n_out, 2).copy()
+        def call(x, n_in, out, stride):
+            if split:
+                check(lib().dabgpu_channeliser_bank_split_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), stride),
+                      "dabgpu_channeliser_bank_split_host_sync")
+            else:
+                check(lib().dabgpu_channeliser_bank_combine_host_sync(self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride,
+                                                                      float(u8_scale)), "dabgpu_channeliser_bank_combine_host_sync")
+        return _host_form(call, h_in, self.n_channels if split else self.n_streams, n_out, fmt)
 
     def split_host(self, h_in, n_out, in_stride_samples=0, wrap=False):
         """h_in complex64 [n_in] (shared) or [n_streams][n_in] with in_stride_samples = n_in -> [n_channels][n_out] complex64; returns when done"""
@@ -1328,8 +1285,9 @@ def tii_validate(lists, counts):
     check(lib().dabgpu_tii_validate(_ptr(lists), _ptr(counts), len(counts)), "dabgpu_tii_validate")
 
 
-class TiiBank:
+class TiiBank(_Handle):
     """dabgpu_tii_bank: the TII detector of n receivers; accumulators and frame counts live on the device"""
+    _destroy = "dabgpu_tii_bank_destroy"
 
     def __init__(self, ctx, n, threshold=None):
         self._ctx = ctx
@@ -1341,17 +1299,6 @@ class TiiBank:
         self.threshold = cfg[0]
         self._h = C.c_void_p()
         check(lib().dabgpu_tii_bank_create(ctx._h, self.n, cfg, C.byref(self._h)), "dabgpu_tii_bank_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_tii_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, stream=None):
         check(lib().dabgpu_tii_bank_reset(self._h, Context._stream(stream)), "dabgpu_tii_bank_reset")
@@ -1439,25 +1386,15 @@ def dabplus_tx_offsets(tx_bank, subchannel_indices, n_frames=5):
     return np.array(offs, np.uint64), cif, np.array(sizes, np.uint32)
 
 
-class IngestPipe:
+class IngestPipe(_Handle):
     """dabgpu_ingest: ring of pinned host buffers + device twins + a copy stream (include/dabgpu.h)"""
+    _destroy = "dabgpu_ingest_destroy"
 
     def __init__(self, ctx, buffer_bytes, depth=2):
         self._ctx = ctx
         self.bytes = buffer_bytes
         self._h = C.c_void_p()
         check(lib().dabgpu_ingest_create(ctx._h, buffer_bytes, depth, C.byref(self._h)), "dabgpu_ingest_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_ingest_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def acquire(self):
         """-> numpy uint8 view of the next pinned buffer"""
@@ -1538,25 +1475,15 @@ class FrameSession:
         return out[:n.value].copy(), e.value
 
 
-class DabPlusBank:
+class DabPlusBank(_Handle):
     """dabgpu_dabplus_bank: n AAC_Frame_Processor states resident on the device"""
+    _destroy = "dabgpu_dabplus_bank_destroy"
 
     def __init__(self, ctx, n_streams):
         self._ctx = ctx
         self.n = n_streams
         self._h = C.c_void_p()
         check(lib().dabgpu_dabplus_bank_create(ctx._h, n_streams, C.byref(self._h)), "dabgpu_dabplus_bank_create")
-
-    def close(self):
-        if self._h:
-            lib().dabgpu_dabplus_bank_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, stream=None):
         check(lib().dabgpu_dabplus_bank_reset(self._h, Context._stream(stream)), "dabgpu_dabplus_bank_reset")

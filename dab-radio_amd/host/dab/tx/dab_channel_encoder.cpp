@@ -5,15 +5,12 @@
 #include <string>
 
 #include "dab/dabgpu_shared_context.h"
+#include "./dabgpu_tx_check.h"
 
-static void check(int st, const char* what) {
-    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Channel_Encoder: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
-}
+static void check(int st, const char* what) { dabgpu_tx_check("DAB_Channel_Encoder", st, what); }
 
 DAB_Channel_Encoder::DAB_Channel_Encoder(tcb::span<const dabgpu_subchannel> subchannels) {
-    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
-        throw std::runtime_error("DAB_Channel_Encoder: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
-                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    dabgpu_tx_check_abi("DAB_Channel_Encoder");
     const int n = (int)subchannels.size();
     std::vector<dabgpu_tx_sub_plan> plans((size_t)n + 1);
     uint32_t cif_in = 0;

@@ -6,15 +6,12 @@
 #include <string>
 
 #include "dab/dabgpu_shared_context.h"
+#include "./dabgpu_tx_check.h"
 
-static void check(int st, const char* what) {
-    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Channel_Model: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
-}
+static void check(int st, const char* what) { dabgpu_tx_check("DAB_Channel_Model", st, what); }
 
 DAB_Channel_Model::DAB_Channel_Model(const dabgpu_channel_stream& params) : m_created(params), m_params(params) {
-    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
-        throw std::runtime_error("DAB_Channel_Model: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
-                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    dabgpu_tx_check_abi("DAB_Channel_Model");
     check(dabgpu_channel_bank_create(dabgpu_shared_context(), 1, &params, &m_bank), "dabgpu_channel_bank_create");
 }
 

@@ -8,17 +8,14 @@
 #include <string>
 
 #include "dab/dabgpu_shared_context.h"
+#include "./dabgpu_tx_check.h"
 
-static void check(int st, const char* what) {
-    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Channeliser: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
-}
+static void check(int st, const char* what) { dabgpu_tx_check("DAB_Channeliser", st, what); }
 
 DAB_Channeliser::DAB_Channeliser(int decim, const std::vector<dabgpu_channeliser_channel>& channels, int64_t start, double passband_cycles,
                                  double stopband_cycles)
     : m_channels(channels), m_start(start), m_decim(decim) {
-    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
-        throw std::runtime_error("DAB_Channeliser: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
-                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    dabgpu_tx_check_abi("DAB_Channeliser");
     auto design = std::make_unique<dabgpu_channeliser_filter>();
     check(dabgpu_channeliser_design(decim, passband_cycles, stopband_cycles, design.get()), "dabgpu_channeliser_design");
     m_error = design->error;

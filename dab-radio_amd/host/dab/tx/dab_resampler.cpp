@@ -8,15 +8,12 @@
 #include <string>
 
 #include "dab/dabgpu_shared_context.h"
+#include "./dabgpu_tx_check.h"
 
-static void check(int st, const char* what) {
-    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Resampler: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
-}
+static void check(int st, const char* what) { dabgpu_tx_check("DAB_Resampler", st, what); }
 
 DAB_Resampler::DAB_Resampler(const dabgpu_resample_stream& params, double passband_cycles) : m_params(params) {
-    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
-        throw std::runtime_error("DAB_Resampler: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
-                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    dabgpu_tx_check_abi("DAB_Resampler");
     // max_step: the step as a double rounded up (the planner compares words), at least 1; a step outside [0.5, 2] is the planner's to refuse
     double max_step = std::nextafter(dabgpu_resample_step(params.step_q62), 4.0);
     max_step = max_step <= 1.0 ? 1.0 : (max_step > 2.0 ? 2.0 : max_step);

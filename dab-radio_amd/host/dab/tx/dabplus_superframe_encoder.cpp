@@ -6,15 +6,12 @@
 #include <string>
 
 #include "dab/dabgpu_shared_context.h"
+#include "./dabgpu_tx_check.h"
 
-static void check(int st, const char* what) {
-    if (st != DABGPU_OK) throw std::runtime_error(std::string("DABPlus_SuperFrame_Encoder: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
-}
+static void check(int st, const char* what) { dabgpu_tx_check("DABPlus_SuperFrame_Encoder", st, what); }
 
 DABPlus_SuperFrame_Encoder::DABPlus_SuperFrame_Encoder(uint32_t frame_bytes) : m_frame_bytes(frame_bytes) {
-    if (dabgpu_abi_version() != DABGPU_ABI_VERSION)
-        throw std::runtime_error("DABPlus_SuperFrame_Encoder: libdabgpu.so implements ABI version " + std::to_string(dabgpu_abi_version()) +
-                                 ", this class was built for " + std::to_string(DABGPU_ABI_VERSION));
+    dabgpu_tx_check_abi("DABPlus_SuperFrame_Encoder");
     if (frame_bytes < 24 || frame_bytes > 1536 || frame_bytes % 24)
         throw std::invalid_argument("DABPlus_SuperFrame_Encoder: " + std::to_string(frame_bytes) + " bytes per logical frame (a multiple of 24 in 24..1536)");
     (void)dabgpu_shared_context();                  // throws where there is no device

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import channel_model as CM
+import signal_bank_cases as SB
 
 pytestmark = pytest.mark.gpu
 
@@ -256,6 +257,31 @@ def test_host_form_and_invalid_arguments(host, ctx, x3):
         dabgpu.Channel(ctx, g_streams([CM.params_dict(taps=[(2048, 1.0, 0.0)])]))
     assert "delay 2048" in str(err.value)
     ch.close()
+
+
+def test_host_form_three_calls_regrow_the_buffers_of_one_bank(host, ctx, x3):
+    """7 samples out of 64 in, 2049 out of the whole input (both buffers grow), 101 (both larger than needed); then the device form goes on
+    from the summed position"""
+    import dabgpu
+    plist = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist))
+    L = dabgpu.lib()
+
+    def host_sync(x, n_out, wrap, fmt, out, stride):
+        n_in = x.shape[-1]
+        dabgpu.check(L.dabgpu_channel_bank_apply_host_sync(ch._h, x.ctypes.data, n_in, n_in, int(wrap), n_out, out.ctypes.data, fmt, stride, 9.0), "host form")
+
+    pos = SB.host_form_regrowth(host_sync, lambda x, pos, n_out, wrap, fmt: CM.host_apply(host, plist, x, pos, n_out, wrap, fmt, scale=9.0), x3, 3, CM.F32,
+                                CM.U8)
+    assert pos == SB.HOST_TOTAL
+    got, ok = run_device(ch, x3, 300, True)
+    assert ok and same_bits(got, CM.host_apply(host, plist, x3, pos, 300, True))
+    ch.close()
+
+
+def test_handle_closes_twice_and_goes_with_its_last_reference(ctx):
+    import dabgpu
+    SB.handle_lifecycle(lambda: dabgpu.Channel(ctx, g_streams(streams3())))
 
 
 def test_set_params_must_fit_the_geometry_of_creation(host, ctx, x3):

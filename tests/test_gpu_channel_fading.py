@@ -7,6 +7,7 @@ import pytest
 
 import channel_fading_model as FM
 import channel_model as CM
+import signal_bank_cases as SB
 
 pytestmark = pytest.mark.gpu
 
@@ -222,6 +223,27 @@ def test_graph_replays_continue_the_stream(host, ctx, x3):
     for r in (1, 2):                                                         # (capturing enqueued nothing: the position is still n)
         g.replay()
         assert same_bits(rows(), exp[:, r * n:(r + 1) * n]), f"replay {r}"
+    ch.close()
+
+
+def test_host_form_three_calls_regrow_the_buffers_of_one_bank(host, ctx, x3):
+    """7 samples out of 64 in, 2049 out of the whole input (both buffers grow), 101 (both larger than needed); then the device form goes on
+    from the summed position"""
+    import dabgpu
+    plist, tables = streams3()
+    ch = dabgpu.Channel(ctx, g_streams(plist), fading=tables)
+    ht = host_tables(tables, 3)
+    L = dabgpu.lib()
+
+    def host_sync(x, n_out, wrap, fmt, out, stride):
+        n_in = x.shape[-1]
+        dabgpu.check(L.dabgpu_channel_bank_apply_host_sync(ch._h, x.ctypes.data, n_in, n_in, int(wrap), n_out, out.ctypes.data, fmt, stride, 9.0), "host form")
+
+    pos = SB.host_form_regrowth(host_sync, lambda x, pos, n_out, wrap, fmt: FM.host_apply(host, plist, ht, x, pos, n_out, wrap, fmt, scale=9.0), x3, 3,
+                                CM.F32, CM.U8)
+    assert pos == SB.HOST_TOTAL
+    got, ok = run_device(ch, x3, 300)
+    assert ok and same_bits(got, FM.host_apply(host, plist, ht, x3, pos, 300, True))
     ch.close()
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import channelise_model as CM
+import signal_bank_cases as SB
 
 pytestmark = pytest.mark.gpu
 
@@ -267,6 +268,42 @@ def test_host_forms_and_refusals(host, ctx, x3, blocks12):
     cb.set_params([CM.to_struct(c, dabgpu.ChanneliserChannel) for c in fewer], 5)
     got, ok = run_device(cb, True, x3, 100, True, rows=12)                   # the stream goes on from where the host forms left it
     assert ok and same_bits(got[:4], CM.host_split(host, fewer, F, x3, 777, 5, 100, True)) and np.all(got[4:].view(np.uint8) == GUARD)
+    cb.close()
+
+
+@pytest.mark.parametrize("split", [True, False])
+def test_host_form_three_calls_regrow_the_buffers_of_one_bank(host, ctx, x3, blocks12, split):
+    """7 samples out of 64 in, 2049 out of the whole input (both buffers grow), 101 (both larger than needed); then the device form goes on
+    from the summed position.  Two wideband streams, the three channels all on stream 1: stream 0 has none and its combined row is zeros.
+    (The combine kernel stores those zeros itself and the split kernel writes every channel's row, so the host forms' zeroing of the
+    output buffer cannot be told from its absence here.)"""
+    import dabgpu
+    D = 4
+    chs = channels12(D)[1:4]
+    cb, F = bank(ctx, host, chs, 2, D, START)
+    x = np.ascontiguousarray(x3[:2, :4001]) if split else np.ascontiguousarray(blocks12[:3])
+    rows = 3 if split else 2
+    L = dabgpu.lib()
+
+    def host_sync(x, n_out, wrap, fmt, out, stride):
+        n_in = x.shape[-1]
+        if split:
+            dabgpu.check(L.dabgpu_channeliser_bank_split_host_sync(cb._h, x.ctypes.data, n_in, n_in, int(wrap), n_out, out.ctypes.data, stride), "host form")
+        else:
+            dabgpu.check(L.dabgpu_channeliser_bank_combine_host_sync(cb._h, x.ctypes.data, n_in, n_in, int(wrap), n_out, out.ctypes.data, fmt, stride, 25.0),
+                         "host form")
+
+    def model(x, pos, n_out, wrap, fmt=CM.F32):
+        if split:
+            return CM.host_split(host, chs, F, x, pos, START, n_out, wrap)
+        return CM.host_combine(host, chs, 2, F, x, pos, START, n_out, wrap, fmt, 25.0)
+
+    pos = SB.host_form_regrowth(host_sync, model, x, rows, CM.F32, None if split else CM.U8)  # (split has no u8 form)
+    assert pos == SB.HOST_TOTAL
+    got, ok = run_device(cb, split, x, 300, True)
+    assert ok and same_bits(got, model(x, pos, 300, True))
+    if not split:
+        assert not got[0].any() and got[1].any()
     cb.close()
 
 

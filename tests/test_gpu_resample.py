@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import resample_model as RM
+import signal_bank_cases as SB
 
 pytestmark = pytest.mark.gpu
 
@@ -226,6 +227,27 @@ def test_identity_bank_returns_its_input(host, ctx, x3):
     bad = ~np.isfinite(exp)
     assert ok and np.array_equal(~np.isfinite(got), bad) and 90 <= bad[0].sum() <= 100
     assert same_bits(got[~bad], exp[~bad])
+    rs.close()
+
+
+def test_host_form_three_calls_regrow_the_buffers_of_one_bank(host, ctx, x3):
+    """7 samples out of 64 in, 2049 out of the whole input (both buffers grow), 101 (both larger than needed); then the device form goes on
+    from the summed position"""
+    import dabgpu
+    plist = [RM.params_dict(RM.step_q62(2.4e6, 2.048e6, 20.0), -10, 1 << 60), RM.params_dict(RM.step_q62(1.0, 1.0, -200.0), 40, W_MAX, gain=0.25),
+             RM.params_dict(ONE, 3, 0)]                                         # all rows, a few rows, the copy
+    rs, D = bank(ctx, host, plist)
+    L = dabgpu.lib()
+
+    def host_sync(x, n_out, wrap, fmt, out, stride):
+        n_in = x.shape[-1]
+        dabgpu.check(L.dabgpu_resample_bank_apply_host_sync(rs._h, x.ctypes.data, n_in, n_in, int(wrap), n_out, out.ctypes.data, fmt, stride, 30.0), "host form")
+
+    pos = SB.host_form_regrowth(host_sync, lambda x, pos, n_out, wrap, fmt: RM.host_apply(host, plist, D, x, pos, n_out, wrap, fmt, 30.0), x3, 3, RM.F32,
+                                RM.U8)
+    assert pos == SB.HOST_TOTAL
+    got, ok = run_device(rs, x3, 300, True)
+    assert ok and same_bits(got, RM.host_apply(host, plist, D, x3, pos, 300, True))
     rs.close()
 
 

@@ -11,6 +11,7 @@ which would add a fifth bit to about 1 % of 1680 masks; after 6 frames the level
 import numpy as np
 import pytest
 
+import signal_bank_cases as SB
 import tii_model as M
 
 pytestmark = pytest.mark.gpu
@@ -251,6 +252,11 @@ def test_host_form_and_checks(ctx, oracle, host):
     with pytest.raises(dabgpu.DabGpuError):
         dabgpu.TiiBank(ctx, 1, threshold=0.5)
     bank.close()
+
+
+def test_handle_closes_twice_and_goes_with_its_last_reference(ctx):
+    import dabgpu
+    SB.handle_lifecycle(lambda: dabgpu.TiiBank(ctx, 2))
 
 
 def test_whole_chain_on_the_device(ctx):
