@@ -1,5 +1,6 @@
 // dabgpu_host_logic.cpp -- see dabgpu_host_logic.h.  No device code and no HIP call in this file.
 #include "dabgpu_host_logic.h"
+#include "packet_fec_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -740,6 +741,70 @@ extern "C" int dabgpu_dabplus_superframe_layout(uint32_t frame_bytes, uint8_t de
     if (n_rs) *n_rs = nrs;
     if (st == 0 && au_start) for (int i = 0; i < 7; i++) au_start[i] = (uint16_t)start[i];       // <= 110 x 64 = 7040
     return st;
+}
+
+// ---- packet mode, transmit direction (include/dabgpu.h, "MSC packet mode"; arithmetic in packet_fec_core.h) ----
+namespace {
+struct PacketLayoutState {
+    size_t n_entries;
+    uint32_t t, used, ci;            // FEC frame, bytes of its application table filled, continuity index of the next data packet
+};
+}
+extern "C" int dabgpu_packet_tx_layout(const uint32_t* group_len, size_t n_groups, uint32_t address, uint32_t packet_length, uint32_t frame_bytes,
+                                       uint64_t start_byte, uint32_t continuity_index, int n_fec_frames, dabgpu_packet_tx_entry* table,
+                                       size_t max_entries, uint32_t* frame_first, size_t* groups_consumed, uint64_t* end_start_byte,
+                                       uint32_t* end_continuity_index) {
+    using namespace dabgpu::pkt;
+    if (groups_consumed) *groups_consumed = 0;
+    if (address < 1 || address > (uint32_t)MAX_ADDRESS) return DABGPU_PACKET_TX_BAD_ADDRESS;
+    if (!length_valid((int)packet_length) || packet_length > 96u) return DABGPU_PACKET_TX_BAD_LENGTH;
+    if (frame_bytes == 0 || frame_bytes % 24u) return DABGPU_PACKET_TX_BAD_FRAME_BYTES;
+    if (frame_bytes < packet_length) return DABGPU_PACKET_TX_FRAME_TOO_SMALL;
+    if (n_groups && !group_len) return -1;
+    for (size_t g = 0; g < n_groups; g++) if (group_len[g] > (uint32_t)MAX_GROUP_BYTES) return DABGPU_PACKET_TX_BAD_GROUP;
+    if (start_byte % 24u) return DABGPU_PACKET_TX_BAD_START;
+    if (n_fec_frames < 0 || n_fec_frames > (1 << 20) || !table || !frame_first) return -1;
+    if (max_entries < (size_t)MAX_FRAME_PACKETS * (size_t)n_fec_frames) return -1;
+    const uint32_t K = (uint32_t)n_fec_frames, L = packet_length, room = L - 5;
+    PacketLayoutState S{0, 0, 0, continuity_index & 3u};
+    if (K) frame_first[0] = 0;
+    // one packet of `len` bytes at the current position; a full table closes its FEC frame
+    auto place = [&](int32_t group, uint32_t offset, uint32_t len, uint32_t useful, uint32_t flags, uint32_t ci) {
+        dabgpu_packet_tx_entry& e = table[S.n_entries++];
+        e.group = group; e.offset = offset; e.position = S.t * (uint32_t)RING_BYTES + S.used;
+        e.length = (uint8_t)len; e.useful = (uint8_t)useful; e.flags = (uint8_t)flags; e.continuity_index = (uint8_t)ci;
+        S.used += len;
+        if (S.used == (uint32_t)APP_TABLE_BYTES) { S.t++; S.used = 0; frame_first[S.t] = (uint32_t)S.n_entries; }
+    };
+    auto fits = [&](uint32_t len) {
+        const uint64_t at = start_byte + (uint64_t)S.t * RING_BYTES + S.used;
+        return S.used + len <= (uint32_t)APP_TABLE_BYTES && at % frame_bytes + len <= frame_bytes;
+    };
+    size_t g = 0;
+    for (; g < n_groups && S.t < K; g++) {
+        const PacketLayoutState before = S;
+        uint32_t done = 0;
+        bool first = true, whole = false;
+        while (S.t < K) {
+            if (!fits(L)) { place(-1, 0, 24, 0, 0, 0); continue; }
+            const uint32_t left = group_len[g] - done, take = std::min(left, room);
+            const bool last = (take == left);
+            place((int32_t)g, done, L, take, (first ? 2u : 0u) | (last ? 1u : 0u), S.ci);
+            S.ci = (S.ci + 1) & 3u;
+            done += take;
+            first = false;
+            if (last) { whole = true; break; }
+        }
+        if (!whole) {                                       // the group does not end inside this call: it is not begun
+            S = before;
+            break;
+        }
+    }
+    while (S.t < K) place(-1, 0, 24, 0, 0, 0);
+    if (groups_consumed) *groups_consumed = g;
+    if (end_start_byte) *end_start_byte = start_byte + (uint64_t)K * RING_BYTES;
+    if (end_continuity_index) *end_continuity_index = S.ci;
+    return 0;
 }
 
 // ---- channel model (include/dabgpu.h, "Channel model") ----

@@ -73,6 +73,9 @@ ABI_SYMBOLS = [
     "dabgpu_tx_encode_plan", "dabgpu_tx_bank_create", "dabgpu_tx_bank_destroy", "dabgpu_tx_bank_reset", "dabgpu_tx_bank_encode_frames",
     "dabgpu_tx_bank_transmit_frames", "dabgpu_tx_bank_encode_frames_host_sync", "dabgpu_tx_bank_transmit_frames_host_sync",
     "dabgpu_dabplus_superframe_layout", "dabgpu_dabplus_tx_encode", "dabgpu_dabplus_tx_encode_host_sync",
+    "dabgpu_packet_bank_create", "dabgpu_packet_bank_destroy", "dabgpu_packet_bank_reset", "dabgpu_packet_bank_process",
+    "dabgpu_packet_bank_process_masked", "dabgpu_packet_fec_read_host_sync",
+    "dabgpu_packet_tx_layout", "dabgpu_packet_tx_encode", "dabgpu_packet_tx_encode_host_sync",
     "dabgpu_channel_plan", "dabgpu_channel_freq_q64", "dabgpu_channel_freq_cycles", "dabgpu_channel_bank_create", "dabgpu_channel_bank_destroy",
     "dabgpu_channel_bank_set_params", "dabgpu_channel_bank_seek", "dabgpu_channel_bank_apply", "dabgpu_channel_bank_apply_host_sync",
     "dabgpu_channel_fading_plan", "dabgpu_channel_fading_gain_host", "dabgpu_channel_profile", "dabgpu_channel_bank_create_fading",
@@ -258,6 +261,15 @@ SUPERFRAME_RESULT_DTYPE = [("rs_failed_index", "<i4"), ("rs_corrected", "<i4"), 
                            ("descriptor", "<i4"), ("num_aus", "<i4"), ("au_start", "<i4", (8,)), ("au_walk_stopped_at", "<i4"),
                            ("au_crc_ok_mask", "<u4"), ("frame_index", "<i4"), ("firecode_rx_calc", "<u4"),
                            ("au_crc_calc", "<u2", (6,)), ("reserved", "<u2", (2,))]
+# MSC packet mode (include/dabgpu.h): dabgpu_packet_record, dabgpu_packet_fec_frame, dabgpu_packet_tx_entry
+PACKET_RECORD_DTYPE = [("offset", "<u4"), ("length", "<u2"), ("address", "<u2"), ("continuity_index", "u1"), ("first_last", "u1"), ("command", "u1"),
+                       ("useful_length", "u1"), ("is_corrected", "u1"), ("crc_ok", "u1"), ("reserved", "u1", (2,))]
+PACKET_FEC_FRAME_DTYPE = [("frame_index", "<i4"), ("first_record", "<i4"), ("rs_count", "i1", (12,))]
+PACKET_TX_ENTRY_DTYPE = [("group", "<i4"), ("offset", "<u4"), ("position", "<u4"), ("length", "u1"), ("useful", "u1"), ("flags", "u1"),
+                         ("continuity_index", "u1")]
+PACKET_RING_BYTES = 2472
+PACKET_APP_BYTES = 2256
+PACKET_MAX_FRAME_PACKETS = 94
 SYNC_STATE_DTYPE = [("freq_coarse", "<f4"), ("freq_fine", "<f4"), ("is_found_coarse", "<i4"),
                     ("fine_time_offset", "<i4"), ("sync_valid", "<i4"), ("reserved", "<i4")]
 RESULT_DTYPE = [("path_error", "<u8"), ("crc_ok_mask", "<u4"), ("n_out_bytes", "<u4")]
@@ -409,6 +421,21 @@ def lib():
                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.dabgpu_dabplus_tx_encode_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                          C.c_void_p]
+        L.dabgpu_packet_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.dabgpu_packet_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_packet_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_packet_bank_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.dabgpu_packet_bank_process_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_packet_fec_read_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                       C.c_void_p]
+        L.dabgpu_packet_tx_layout.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_packet_tx_encode.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dabgpu_packet_tx_encode_host_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                        C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         L.dabgpu_channel_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         L.dabgpu_channel_freq_q64.argtypes = [C.c_double]
         L.dabgpu_channel_freq_q64.restype = C.c_uint64
@@ -1513,6 +1540,112 @@ class DabPlusBank(_Handle):
         check(lib().dabgpu_dabplus_process_frame_host_sync(self._h, _ptr(frame), frame.size, C.byref(done), C.byref(wait), None, _ptr(res),
                                                            _ptr(sf)), "dabgpu_dabplus_process_frame_host_sync")
         return done.value, wait.value, res[0], (sf if done.value else None)
+
+
+class PacketBank(_Handle):
+    """dabgpu_packet_bank: n MSC_Reed_Solomon_Data_Packet_Processor states (packet mode with FEC) resident on the device"""
+    _destroy = "dabgpu_packet_bank_destroy"
+
+    def __init__(self, ctx, n_streams):
+        self._ctx = ctx
+        self.n = n_streams
+        self._h = C.c_void_p()
+        check(lib().dabgpu_packet_bank_create(ctx._h, n_streams, C.byref(self._h)), "dabgpu_packet_bank_create")
+
+    def reset(self, stream=None):
+        check(lib().dabgpu_packet_bank_reset(self._h, Context._stream(stream)), "dabgpu_packet_bank_reset")
+
+    def process(self, frames, stream_offsets, frame_stride, frame_bytes, n_frames, packets, packet_stride, records, max_records, fec_frames,
+                max_fec_frames, counts, stream=None):
+        """device buffers: stream_offsets uint64 [S], frame_bytes uint32 [S], packets uint8 [S][packet_stride], records PACKET_RECORD_DTYPE
+        [S][max_records], fec_frames PACKET_FEC_FRAME_DTYPE [S][max_fec_frames], counts int32 [S][4] (asynchronous)"""
+        check(lib().dabgpu_packet_bank_process(self._h, _ptr(frames), _ptr(stream_offsets), frame_stride, _ptr(frame_bytes), n_frames,
+                                               _ptr(packets), packet_stride, _ptr(records), max_records, _ptr(fec_frames), max_fec_frames,
+                                               _ptr(counts), Context._stream(stream)), "dabgpu_packet_bank_process")
+
+    def process_masked(self, frames, stream_offsets, frame_stride, frame_bytes, n_frames, packets, packet_stride, records, max_records,
+                       fec_frames, max_fec_frames, counts, active, streams_per_flag, stream=None):
+        check(lib().dabgpu_packet_bank_process_masked(self._h, _ptr(frames), _ptr(stream_offsets), frame_stride, _ptr(frame_bytes), n_frames,
+                                                      _ptr(packets), packet_stride, _ptr(records), max_records, _ptr(fec_frames),
+                                                      max_fec_frames, _ptr(counts), _ptr(active), streams_per_flag, Context._stream(stream)),
+              "dabgpu_packet_bank_process_masked")
+
+    def read_host(self, buf):
+        """one-stream bank, one buffer (a logical frame) -> (packets uint8, records, FEC frame records, counts int32 [4])"""
+        import numpy as np
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        cap = PACKET_RING_BYTES + buf.size
+        max_rec, max_fec = cap // 24 + 1, buf.size // 24 // 9 + 2
+        packets = np.zeros(cap, np.uint8)
+        rec = np.zeros(max_rec, np.dtype(PACKET_RECORD_DTYPE))
+        fec = np.zeros(max_fec, np.dtype(PACKET_FEC_FRAME_DTYPE))
+        counts = np.zeros(4, np.int32)
+        check(lib().dabgpu_packet_fec_read_host_sync(self._h, _ptr(buf), buf.size, _ptr(packets), _ptr(rec), max_rec, _ptr(fec), max_fec,
+                                                     _ptr(counts)), "dabgpu_packet_fec_read_host_sync")
+        return packets[:max(int(counts[1]), 0)], rec[:int(counts[0])], fec[:int(counts[2])], counts
+
+
+def packet_tx_layout(group_len, address, packet_length, frame_bytes, start_byte=0, continuity_index=0, n_fec_frames=1):
+    """dabgpu_packet_tx_layout (host only) -> (status, table PACKET_TX_ENTRY_DTYPE [n], frame_first uint32 [n_fec_frames + 1], groups consumed,
+    end start_byte, end continuity index); table and frame_first are None when the call is refused"""
+    import numpy as np
+    lens = np.ascontiguousarray(group_len, dtype=np.uint32).ravel()
+    K = max(int(n_fec_frames), 0)
+    table = np.zeros(max(PACKET_MAX_FRAME_PACKETS * K, 1), np.dtype(PACKET_TX_ENTRY_DTYPE))
+    first = np.zeros(K + 1, np.uint32)
+    consumed, end_start, end_ci = C.c_size_t(0), C.c_uint64(int(start_byte)), C.c_uint32(int(continuity_index))
+    st = lib().dabgpu_packet_tx_layout(_ptr(lens) if lens.size else None, lens.size, int(address), int(packet_length), int(frame_bytes),
+                                       int(start_byte), int(continuity_index), int(n_fec_frames), _ptr(table), PACKET_MAX_FRAME_PACKETS * K,
+                                       _ptr(first), C.byref(consumed), C.byref(end_start), C.byref(end_ci))
+    if st != 0:
+        return st, None, None, 0, int(start_byte), int(continuity_index)
+    return 0, table[:int(first[K])], first, consumed.value, end_start.value, end_ci.value
+
+
+class PacketTx:
+    """the packet-mode encoder with FEC (dabgpu_packet_tx_*): data groups -> the logical frames of packet-mode sub-channels; stateless"""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+
+    layout = staticmethod(packet_tx_layout)
+
+    def encode(self, n_streams, n_fec_frames, data, group_offsets, group_base, table, table_stride, frame_first, address, frame_bytes,
+               start_byte, frames, stream_offsets, frame_stride, status, stream=None):
+        """device buffers: group_offsets uint64 [groups + 1], group_base uint32 [S + 1], table PACKET_TX_ENTRY_DTYPE [S][table_stride],
+        frame_first uint32 [S][K + 1], address uint16 [S], frame_bytes uint32 [S], start_byte uint64 [S], stream_offsets uint64 [S], status
+        int32 [S][K] (asynchronous)"""
+        check(lib().dabgpu_packet_tx_encode(self._ctx._h, n_streams, n_fec_frames, _ptr(data), _ptr(group_offsets), _ptr(group_base), _ptr(table),
+                                            table_stride, _ptr(frame_first), _ptr(address), _ptr(frame_bytes), _ptr(start_byte), _ptr(frames),
+                                            _ptr(stream_offsets), frame_stride, _ptr(status), Context._stream(stream)), "dabgpu_packet_tx_encode")
+
+    def encode_host(self, groups, address, packet_length, frame_bytes, start_byte=0, continuity_index=0, n_fec_frames=1, fill=0):
+        """one stream: lays the groups out and encodes them -> (layout status, uint8 [n_logical_frames][frame_bytes], int32 status [K], groups
+        consumed, end start_byte, end continuity index)"""
+        import numpy as np
+        groups = [np.ascontiguousarray(g, dtype=np.uint8) for g in groups]
+        st, table, first, consumed, end_start, end_ci = packet_tx_layout([g.size for g in groups], address, packet_length, frame_bytes, start_byte,
+                                                                         continuity_index, n_fec_frames)
+        if st != 0:
+            return st, None, None, 0, end_start, end_ci
+        K = int(n_fec_frames)
+        offs = np.zeros(max(len(groups), 1), np.uint64)
+        offs[:len(groups)] = np.cumsum([0] + [g.size for g in groups])[:len(groups)]
+        data = np.concatenate(groups + [np.zeros(1, np.uint8)])
+        n_logical = (int(start_byte) % int(frame_bytes) + K * PACKET_RING_BYTES + int(frame_bytes) - 1) // int(frame_bytes)
+        frames = np.full((n_logical, int(frame_bytes)), fill, np.uint8)
+        status = np.full(max(K, 1), -1, np.int32)
+        check(lib().dabgpu_packet_tx_encode_host_sync(self._ctx._h, K, _ptr(data), data.size - 1, _ptr(offs), len(groups), _ptr(table), _ptr(first),
+                                                      int(address), int(frame_bytes), int(start_byte), _ptr(frames), _ptr(status)),
+              "dabgpu_packet_tx_encode_host_sync")
+        return 0, frames, status[:K], consumed, end_start, end_ci
+
+
+def packet_tx_offsets(tx_bank, subchannel_indices, n_frames=5):
+    """where PacketTx.encode writes into a TxBank payload [n][n_frames][4][cif_in_bytes] so that the bank reads the sub-channels' logical frames:
+    (stream_offsets uint64 [n * len(subchannel_indices)], ensemble major, frame_stride, frame_bytes uint32 of the same shape).  4 n_frames logical
+    frames of frame_bytes hold the call's FEC frames of 2472 bytes; a trailing partial frame belongs to the next payload."""
+    return dabplus_tx_offsets(tx_bank, subchannel_indices, n_frames)
 
 
 def stream_cfg_default():

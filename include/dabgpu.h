@@ -964,6 +964,140 @@ int dabgpu_dabplus_tx_encode_host_sync(dabgpu_ctx *ctx, int n_superframes, const
                                        int32_t *h_status);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * MSC packet mode with its FEC scheme (EN 300 401 clauses 5.3.2 and 5.3.5), both directions.
+ *
+ * Receive: MSC_Reed_Solomon_Data_Packet_Processor (src/dab/msc/msc_reed_solomon_data_packet_processor.cpp), the outer code
+ * Basic_Data_Packet_Channel runs for a sub-channel with fec_scheme = 1 (src/basic_radio/basic_data_packet_channel.cpp:29-34,74-80),
+ * for n_streams streams at once, one wavefront per stream:
+ *   walk     ReadPacket over every logical frame (:57-87): 2-byte header = length id (24/48/72/96) | counter | address; address 0x3FE is
+ *            a FEC packet whose length field is not believed (:72-75, :150-152); a remainder shorter than 2 bytes or than the packet its
+ *            header names is consumed without being stored (:58-61, :78-81)
+ *   ring     2472 bytes; a packet that does not fit discards whole packets from the head WITHOUT handing them out (:136-147)
+ *   FEC      packets count 0..8; a wrong counter hands out everything stored, FEC packets included, uncorrected (:89-105); counter 8 with a
+ *            ring of exactly 2472 bytes corrects the frame, any other fill hands it out uncorrected (:112-120)
+ *   correct  (:186-258) 12 rows of RS(204,188) over GF(2^8), p(x) = x^8+x^4+x^3+x^2+1, roots alpha^0..alpha^15, shortened by 51
+ *            (src/dab/algorithms/reed_solomon_decoder.cpp as (8, 0x11D, 0, 1, 16, 51)): row y = application bytes i*12 + y, i = 0..187, then
+ *            bytes i*12 + y, i = 0..15, of the nine 22-byte FEC data fields.  A row whose locator degree differs from its number of roots
+ *            (Decode returns -1) stays as received; otherwise positions 0..187 are written back, parity positions and positions inside the
+ *            padding (reported, never applied: reed_solomon_decoder.cpp:464) are not.  Then packets are popped from the corrected 2256 bytes
+ *            by their corrected headers until at least 2256 bytes are read -- a header an uncorrectable row left wrong makes this walk
+ *            differ from the one at push time and run up to 72 bytes into the FEC packets.  The FEC packets of a corrected frame are not
+ *            handed out.
+ * is_corrected means "went through the FEC path", not "an error was fixed"; a data packet whose length bits arrive damaged misaligns the
+ * walk before any correction can run.  Both are the reference's behaviour.
+ * Per packet handed out, the fields of the data-packet header and its CRC (src/dab/msc/msc_data_packet_processor.cpp:60-66, :23-32,
+ * :81-92: x^16+x^12+x^5+1, start 0xFFFF, inverted, over the first length - 2 bytes) are recorded; for FEC packets handed out uncorrected
+ * they are the same bit fields of those bytes.
+ */
+typedef struct {
+    uint32_t offset;                /* of the packet inside the stream's slot of d_packets */
+    uint16_t length;                /* 24 / 48 / 72 / 96 */
+    uint16_t address;
+    uint8_t continuity_index;
+    uint8_t first_last;             /* bit 1 first, bit 0 last (table 7) */
+    uint8_t command;
+    uint8_t useful_length;
+    uint8_t is_corrected;           /* the callback's flag */
+    uint8_t crc_ok;
+    uint8_t reserved[2];
+} dabgpu_packet_record;
+typedef struct {
+    int32_t frame_index;            /* index inside this call of the logical frame in which the ninth FEC packet arrived */
+    int32_t first_record;           /* index of the record of the frame's first packet */
+    int8_t rs_count[12];            /* Decode's return value per row: roots found, or -1 */
+} dabgpu_packet_fec_frame;
+
+typedef struct dabgpu_packet_bank dabgpu_packet_bank;
+int dabgpu_packet_bank_create(dabgpu_ctx *ctx, size_t n_streams, dabgpu_packet_bank **out);
+void dabgpu_packet_bank_destroy(dabgpu_packet_bank *bank);
+int dabgpu_packet_bank_reset(dabgpu_packet_bank *bank, void *stream);
+/* n_frames logical frames per stream, read where dabgpu_dabplus_bank_process reads them (frame f of stream s = d_frame_bytes[s] bytes at
+ * d_frames + d_stream_offsets[s] + f frame_stride_bytes); any frame size is accepted.  Ring, heads, fill, discard counters and the last FEC
+ * counter of every stream stay in device memory between calls.
+ *   d_packets    [n_streams][packet_stride_bytes]: the packets the callback receives, in its order, back to back
+ *   d_records    [n_streams][max_records]: one per packet; d_fec_frames [n_streams][max_fec_frames]: one per corrected FEC frame.  Packets
+ *                and frames beyond max_records / max_fec_frames are counted, their records are not written
+ *   d_counts     [n_streams][4]: packets handed out, bytes handed out, FEC frames corrected, packets discarded without callback
+ * A call hands out at most 2472 + n_frames * frame bytes; a stream whose slot is smaller is not processed and gets d_counts[s][1] = -2.
+ * Asynchronous on `stream`, one kernel launch, capturable in a HIP graph.  A NULL argument, n_frames < 0, negative max_records /
+ * max_fec_frames or streams_per_flag < 1 return DABGPU_ERR_INVALID_ARG before any device call; n_frames = 0 does nothing. */
+int dabgpu_packet_bank_process(dabgpu_packet_bank *bank, const uint8_t *d_frames, const uint64_t *d_stream_offsets, size_t frame_stride_bytes,
+                               const uint32_t *d_frame_bytes, int n_frames, uint8_t *d_packets, size_t packet_stride_bytes,
+                               dabgpu_packet_record *d_records, int max_records, dabgpu_packet_fec_frame *d_fec_frames, int max_fec_frames,
+                               int32_t *d_counts, void *stream);
+/* the same, skipping every stream whose flag d_active[s / streams_per_flag] is negative (its counts are written as zeros) */
+int dabgpu_packet_bank_process_masked(dabgpu_packet_bank *bank, const uint8_t *d_frames, const uint64_t *d_stream_offsets,
+                                      size_t frame_stride_bytes, const uint32_t *d_frame_bytes, int n_frames, uint8_t *d_packets,
+                                      size_t packet_stride_bytes, dabgpu_packet_record *d_records, int max_records,
+                                      dabgpu_packet_fec_frame *d_fec_frames, int max_fec_frames, int32_t *d_counts, const int32_t *d_active,
+                                      int streams_per_flag, void *stream);
+/* one buffer through a one-stream bank, from and to host memory (the mirror class's ReadPacket loop over one logical frame): h_packets
+ * [2472 + n_bytes], h_records [max_records], h_fec_frames [max_fec_frames], h_counts [4] */
+int dabgpu_packet_fec_read_host_sync(dabgpu_packet_bank *bank, const uint8_t *h_buf, uint32_t n_bytes, uint8_t *h_packets,
+                                     dabgpu_packet_record *h_records, int max_records, dabgpu_packet_fec_frame *h_fec_frames,
+                                     int max_fec_frames, int32_t *h_counts);
+
+/* Transmit: data groups -> packets -> FEC frames (2256 application bytes, then nine FEC packets with counter 0..8, address 0x3FE and 6
+ * zero padding bytes in the last) -> the bytes of a sub-channel.  The reference has no encoder; the definition is the inverse of the walk
+ * above and is pinned by the reference's decoder returning 0 for every row and handing every packet back.
+ *
+ * dabgpu_packet_tx_layout (host only, no device): cuts whole data groups into packets of packet_length bytes (3 header bytes, up to
+ * packet_length - 5 useful bytes, zero padding, CRC) for n_fec_frames FEC frames that begin at stream byte start_byte.  24-byte padding
+ * packets (address 0, useful length 0) are inserted so that no packet crosses a logical-frame boundary (5.3.2) and every application data
+ * table is exactly 2256 bytes.  A group that cannot end inside the call's frames is not begun; the rest is padding.  A group of 0 bytes is
+ * one packet with both flags and useful length 0.
+ *   table        [max_entries >= 94 n_fec_frames] one entry per packet, in stream order; frame_first [n_fec_frames + 1]: the first entry of
+ *                each FEC frame, and the total
+ *   position     of an entry: bytes from the start of the call (FEC frame t begins at 2472 t)
+ *   end state    *end_start_byte = start_byte + 2472 n_fec_frames, *end_continuity_index for the next call
+ * Returns 0, or in this order DABGPU_PACKET_TX_BAD_ADDRESS (not 1..1021), _BAD_LENGTH (not 24/48/72/96), _BAD_FRAME_BYTES (0 or no
+ * multiple of 24), _FRAME_TOO_SMALL (frame_bytes below the packet length), _BAD_GROUP (a group above 8191 bytes), _BAD_START (start_byte
+ * no multiple of 24); -1 for a NULL pointer, n_fec_frames outside 0..2^20 or a table that is too small. */
+enum { DABGPU_PACKET_TX_BAD_ADDRESS = 1, DABGPU_PACKET_TX_BAD_LENGTH = 2, DABGPU_PACKET_TX_BAD_FRAME_BYTES = 3,
+       DABGPU_PACKET_TX_FRAME_TOO_SMALL = 4, DABGPU_PACKET_TX_BAD_GROUP = 5, DABGPU_PACKET_TX_BAD_START = 6, DABGPU_PACKET_TX_BAD_TABLE = 7 };
+typedef struct {
+    int32_t group;                  /* index of the data group, -1 for a padding packet */
+    uint32_t offset;                /* of the packet's useful bytes inside the group */
+    uint32_t position;              /* of the packet, bytes from the start of the call */
+    uint8_t length;                 /* 24 / 48 / 72 / 96 */
+    uint8_t useful;                 /* useful data length, 0 .. length - 5 */
+    uint8_t flags;                  /* bit 1 first, bit 0 last */
+    uint8_t continuity_index;
+} dabgpu_packet_tx_entry;
+int dabgpu_packet_tx_layout(const uint32_t *group_len, size_t n_groups, uint32_t address, uint32_t packet_length, uint32_t frame_bytes,
+                            uint64_t start_byte, uint32_t continuity_index, int n_fec_frames, dabgpu_packet_tx_entry *table,
+                            size_t max_entries, uint32_t *frame_first, size_t *groups_consumed, uint64_t *end_start_byte,
+                            uint32_t *end_continuity_index);
+/* n_fec_frames FEC frames for each of n_streams streams, one wavefront per (stream, FEC frame); stateless.
+ *   d_data           the streams' data groups back to back; group g of stream s is bytes d_group_offsets[G] .. d_group_offsets[G + 1] of it,
+ *                    G = d_group_base[s] + g.  d_group_offsets [all groups + 1] uint64, d_group_base [n_streams + 1] uint32: stream s owns
+ *                    groups d_group_base[s] .. d_group_base[s + 1]
+ *   d_table          [n_streams][table_stride] entries, d_frame_first [n_streams][n_fec_frames + 1] as the layout writes them
+ *   d_address, d_frame_bytes [n_streams]; d_start_byte [n_streams] uint64
+ *   d_frames         byte k of the call (k = 2472 t + ...) goes to d_frames + d_stream_offsets[s] + F frame_stride_bytes + C with
+ *                    F = (start_byte + k) / frame_bytes - start_byte / frame_bytes and C = (start_byte + k) % frame_bytes: the layout
+ *                    dabgpu_packet_bank_process reads and a dabgpu_tx_bank payload holds.  A trailing partial logical frame is completed by
+ *                    the next call, which the caller points at that frame.
+ *   d_status         [n_streams][n_fec_frames]: 0, or DABGPU_PACKET_TX_BAD_ADDRESS / _BAD_FRAME_BYTES / _BAD_START / _BAD_TABLE (the frame's
+ *                    entries do not tile its 2256 bytes with valid packets inside logical frames and inside their groups); a refused frame
+ *                    is written as 94 padding packets and their FEC packets (nothing at all for frame_bytes = 0)
+ * Asynchronous on `stream`, one kernel launch, capturable.  A NULL context, n_fec_frames < 0, more than 2^30 frames, table_stride below 94
+ * n_fec_frames, or a NULL pointer with n_streams n_fec_frames > 0 return DABGPU_ERR_INVALID_ARG before any device call; n_streams = 0 and
+ * n_fec_frames = 0 are legal and do nothing. */
+int dabgpu_packet_tx_encode(dabgpu_ctx *ctx, size_t n_streams, int n_fec_frames, const uint8_t *d_data, const uint64_t *d_group_offsets,
+                            const uint32_t *d_group_base, const dabgpu_packet_tx_entry *d_table, size_t table_stride,
+                            const uint32_t *d_frame_first, const uint16_t *d_address, const uint32_t *d_frame_bytes,
+                            const uint64_t *d_start_byte, uint8_t *d_frames, const uint64_t *d_stream_offsets, size_t frame_stride_bytes,
+                            int32_t *d_status, void *stream);
+/* one stream from and to host memory: the groups back to back in h_data (h_group_offsets [n_groups]); h_frames [n_logical_frames]
+ * [frame_bytes] with n_logical_frames = (start_byte % frame_bytes + 2472 n_fec_frames + frame_bytes - 1) / frame_bytes; bytes the call
+ * does not write are left as they are.  h_status [n_fec_frames]. */
+int dabgpu_packet_tx_encode_host_sync(dabgpu_ctx *ctx, int n_fec_frames, const uint8_t *h_data, size_t n_data_bytes,
+                                      const uint64_t *h_group_offsets, size_t n_groups, const dabgpu_packet_tx_entry *h_table,
+                                      const uint32_t *h_frame_first, uint32_t address, uint32_t frame_bytes, uint64_t start_byte,
+                                      uint8_t *h_frames, int32_t *h_status);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Channel model: multipath inside the guard interval, carrier offset, timing offset and white Gaussian noise for n_streams
  * independent streams of complex float samples.  The reference has no channel (only examples/apply_frequency_shift.cpp); the definition
  * is this library's own, written once in dab-radio_amd/csrc/channel_core.h for the kernel (channel.hip) and for the host model the
