@@ -731,6 +731,54 @@ extern "C" int dabgpu_tx_encode_plan(const dabgpu_subchannel* subs, int n_sub, d
     return DABGPU_OK;
 }
 
+// ---- channel BER planner ----
+int dabgpu_host_ber_plan(const dabgpu_subchannel* subs, int n_sub, size_t n_ens, int hist_frames, size_t ens_stride, size_t out_ens_stride,
+                         int bits_layout, dabgpu_ber_launch* L) {
+    *L = dabgpu_ber_launch{};
+    if (n_sub < 0 || n_sub > 64 || (n_sub > 0 && !subs)) { dabgpu_set_error("ber_plan: %d sub-channels (0..64 are accepted)", n_sub); return DABGPU_ERR_INVALID_ARG; }
+    int st;
+    for (int s = 0; s < n_sub; s++)
+        if ((st = dabgpu_subchannel_validate(&subs[s]))) return st;
+    if ((st = dabgpu_host_tx_plan(subs, n_sub, &L->tx))) return st;
+    if (n_ens == 0 || n_ens > (size_t)(1 << 20)) { dabgpu_set_error("ber_plan: %zu ensembles (1..1048576 are accepted)", n_ens); return DABGPU_ERR_INVALID_ARG; }
+    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) {
+        dabgpu_set_error("ber_plan: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (hist_frames < 5) { dabgpu_set_error("ber_plan: history_frames %d (>= 5: 16 CIFs of delay + the 4 new ones)", hist_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (ens_stride / DABGPU_NB_FRAME_BITS < (size_t)hist_frames || (ens_stride & 15)) {
+        dabgpu_set_error("ber_plan: ensemble_stride %zu must be a multiple of 16 >= %d x 230400", ens_stride, hist_frames); return DABGPU_ERR_INVALID_ARG;
+    }
+    const dabgpu_tx_plan& P = L->tx;
+    if (n_sub > 0 && (out_ens_stride < (size_t)4 * P.cif_in_bytes || (out_ens_stride & 3))) {
+        dabgpu_set_error("ber_plan: out_ensemble_stride %zu must be a multiple of 4 >= 4 x %u", out_ens_stride, P.cif_in_bytes); return DABGPU_ERR_INVALID_ARG;
+    }
+    dabgpu_ber_geometry& G = L->geo;
+    G.n_sub = (uint32_t)n_sub;
+    G.codewords_per_ensemble = 4u * (uint32_t)n_sub + 4u;
+    G.cif_bytes = P.cif_in_bytes;
+    G.n_sched = (uint32_t)P.sched.size();
+    uint32_t max_length = 0;
+    for (size_t s = 0; s < P.subs.size(); s++) {
+        G.sched_offset[s] = P.subs[s].sched_offset;
+        G.max_kept_bits = std::max(G.max_kept_bits, P.subs[s].kept_bits);
+        max_length = std::max(max_length, P.subs[s].length);
+    }
+    G.lds_bytes = 4u * dabgpu_ber_cw_dwords(max_length);
+    G.waves_per_block = DABGPU_BER_WAVES; G.block_threads = 64u * DABGPU_BER_WAVES;
+    G.grid = (uint32_t)((n_ens * G.codewords_per_ensemble + DABGPU_BER_WAVES - 1u) / DABGPU_BER_WAVES);      // <= 2^20 x 260 / 4
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_ber_plan(const dabgpu_subchannel* subs, int n_sub, size_t n_ens, int hist_frames, size_t ens_stride, size_t out_ens_stride,
+                               int bits_layout, dabgpu_ber_geometry* out) {
+    if (!out) { dabgpu_set_error("ber_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu_ber_launch L;
+    const int st = dabgpu_host_ber_plan(subs, n_sub, n_ens, hist_frames, ens_stride, out_ens_stride, bits_layout, &L);
+    if (st) return st;
+    *out = L.geo;
+    return DABGPU_OK;
+}
+
 extern "C" int dabgpu_dabplus_superframe_layout(uint32_t frame_bytes, uint8_t descriptor, const uint16_t* au_len, uint16_t* au_start, int* num_aus,
                                                 uint32_t* n_rs) {
     if (!au_len) return -1;

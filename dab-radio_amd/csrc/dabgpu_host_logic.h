@@ -231,6 +231,18 @@ struct dabgpu_tx_plan {
 // DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason in dabgpu_last_error
 int dabgpu_host_tx_plan(const dabgpu_subchannel* subs, int n_sub, dabgpu_tx_plan* out);
 
+// ---- channel BER planner (channel_ber.hip launches from it; include/dabgpu.h, dabgpu_ber_plan) ----
+#define DABGPU_BER_WAVES 4u                         // wavefronts (code words) per workgroup
+struct dabgpu_ber_launch {
+    dabgpu_tx_plan tx;                              // the encoder's plan of the multiplex: sub-channels, FIB group, schedules
+    dabgpu_ber_geometry geo;
+};
+// DABGPU_OK, or DABGPU_ERR_INVALID_ARG with the reason in dabgpu_last_error (the order of the checks: include/dabgpu.h)
+int dabgpu_host_ber_plan(const dabgpu_subchannel* subs, int n_sub, size_t n_ens, int hist_frames, size_t ens_stride, size_t out_ens_stride,
+                         int bits_layout, dabgpu_ber_launch* out);
+// LDS dwords one wavefront holds a code word of `length` capacity units in (whole blocks of 512 bits)
+DABGPU_HD static inline uint32_t dabgpu_ber_cw_dwords(uint32_t length) { return 16u * ((length + 7u) / 8u); }
+
 // ---- channel model planner (channel.hip launches from it; include/dabgpu.h, dabgpu_channel_plan) ----
 // DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream index, field) in dabgpu_last_error
 int dabgpu_host_channel_plan(const dabgpu_channel_stream* params, size_t n_streams, dabgpu_channel_geometry* out);

@@ -35,6 +35,7 @@ enum dabgpu_scratch_slot : int {
     SCR_CONVERT_IN, SCR_CONVERT_OUT, SCR_RAW_IQ,     // 20-22: host-buffer format conversion; ofdm_demod_frames_raw's converted block
     SCR_MODE_CORR, SCR_TUNE_TAIL = SCR_MODE_CORR,    // 23, shared: ofdm_demod_frames_mode's unwanted correlations, ofdm_tune's phase tail
     SCR_LANE_SUBS, SCR_VIT_SCHED,                    // 24-25: MSC lane -> sub-channel table, puncturing schedules
+    SCR_BER_TABLES, SCR_BER_HOST,                    // 26-27: channel BER: a multiplex's encoder tables; the single-code-word host forms' block
     SCR_NAMED,
     // the FIC decoders' own copies of the decoder slots (scratch_fic): one context decodes the FIC and the MSC on two streams at once
     SCR_FIC_OFFSET = 20,
@@ -78,7 +79,7 @@ struct dabgpu_ctx {
     // (dabgpu_stage_h2d_cached).  Steady-state decode calls then contain kernel launches only, which is what lets a caller capture them
     // in a HIP graph.
     struct table_copy { void* d = nullptr; hipStream_t s = nullptr; std::vector<unsigned char> bytes; };
-    table_copy tables[2];
+    table_copy tables[3];
     std::mutex tables_mu;
 };
 #define DABGPU_HOST_LOCK(ctx) std::lock_guard<std::recursive_mutex> dabgpu_host_lock_(ctx->host_mu)
@@ -86,7 +87,7 @@ struct dabgpu_ctx {
 #define DABGPU_CK(call) do { st = dabgpu_check_hip((call), #call); if (st) return st; } while (0)
 // asynchronous host -> device copy on `s` that has consumed h_src when it returns (h_src may be freed or overwritten at once)
 extern "C" int dabgpu_stage_h2d(dabgpu_ctx* c, void* d_dst, const void* h_src, size_t bytes, hipStream_t s);
-// the same for table `which` (0: sub-channel plans, 1: lane table) of the context, skipped when nothing changed (see dabgpu_ctx::tables)
+// the same for table `which` (0: sub-channel plans, 1: lane table, 2: channel BER tables) of the context, skipped when nothing changed (see dabgpu_ctx::tables)
 extern "C" int dabgpu_stage_h2d_cached(dabgpu_ctx* c, int which, void* d_dst, const void* h_src, size_t bytes, hipStream_t s);
 
 int dabgpu_check_hip(hipError_t e, const char* what);

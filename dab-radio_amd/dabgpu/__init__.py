@@ -91,6 +91,7 @@ ABI_SYMBOLS = [
     "dabgpu_ofdm_modulate_frames_tii", "dabgpu_ofdm_modulate_frames_tii_host_sync",
     "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
     "dabgpu_tii_bank_read",
+    "dabgpu_ber_plan", "dabgpu_ber_frames_layout", "dabgpu_ber_ring_layout", "dabgpu_ber_fib_group_host_sync", "dabgpu_ber_codeword_host_sync",
 ]
 
 # channel model (include/dabgpu.h)
@@ -167,6 +168,13 @@ class TxSubPlan(C.Structure):
     _fields_ = [("start_address", C.c_uint32), ("length", C.c_uint32), ("in_offset", C.c_uint32), ("in_bytes", C.c_uint32),
                 ("seg_pi", C.c_uint32 * 4), ("seg_blocks", C.c_uint32 * 4), ("n_words", C.c_uint32), ("kept_bits", C.c_uint32),
                 ("sched_offset", C.c_uint32), ("ring_offset", C.c_uint32), ("ring_row_dwords", C.c_uint32)]
+
+
+class BerGeometry(C.Structure):
+    """dabgpu_ber_geometry"""
+    _fields_ = [("n_sub", C.c_uint32), ("codewords_per_ensemble", C.c_uint32), ("cif_bytes", C.c_uint32), ("n_sched", C.c_uint32),
+                ("sched_offset", C.c_uint32 * 65), ("max_kept_bits", C.c_uint32), ("lds_bytes", C.c_uint32), ("waves_per_block", C.c_uint32),
+                ("block_threads", C.c_uint32), ("grid", C.c_uint32)]
 
 
 class ChannelStream(C.Structure):
@@ -273,6 +281,7 @@ PACKET_MAX_FRAME_PACKETS = 94
 SYNC_STATE_DTYPE = [("freq_coarse", "<f4"), ("freq_fine", "<f4"), ("is_found_coarse", "<i4"),
                     ("fine_time_offset", "<i4"), ("sync_valid", "<i4"), ("reserved", "<i4")]
 RESULT_DTYPE = [("path_error", "<u8"), ("crc_ok_mask", "<u4"), ("n_out_bytes", "<u4")]
+BER_RESULT_DTYPE = [("n_bits", "<u4"), ("n_errors", "<u4"), ("error_weight", "<u4"), ("total_weight", "<u4")]      # dabgpu_ber_result
 
 
 class DabGpuError(RuntimeError):
@@ -508,6 +517,13 @@ def lib():
         L.dabgpu_tii_bank_process_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                                         C.c_void_p]
         L.dabgpu_tii_bank_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_ber_plan.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
+        L.dabgpu_ber_frames_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_ber_ring_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_ber_fib_group_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_ber_codeword_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -796,6 +812,45 @@ class Context:
                                              newest_frame_slot, arr, n, _ptr(out), out_ensemble_stride, _ptr(results),
                                              tie_rule, self._stream(stream)), "dabgpu_msc_decode_frames")
 
+    def ber_frames(self, history, n_ensembles, ensemble_stride, history_frames, newest_frame_slot, subchannels, fib_bytes, msc_out,
+                   out_ensemble_stride, fic_ber, msc_ber, stream=None, bits_layout=BITS_NATURAL):
+        """channel BER of the code words decode_frames decoded (dabgpu_ber_frames_layout): fib_bytes / msc_out as that call left them,
+        fic_ber [n][4] and msc_ber [n][4][n_sub] device buffers of BER_RESULT_DTYPE; a half whose bytes or records are None is skipped"""
+        n = len(subchannels)
+        arr = (SubChannel * n)(*subchannels) if n else None
+        check(lib().dabgpu_ber_frames_layout(self._h, _ptr(history), n_ensembles, ensemble_stride, history_frames, newest_frame_slot, arr, n,
+                                             _ptr(fib_bytes), _ptr(msc_out), out_ensemble_stride, _ptr(fic_ber), _ptr(msc_ber), int(bits_layout),
+                                             self._stream(stream)), "dabgpu_ber_frames_layout")
+
+    def ber_ring(self, history, n_ensembles, ensemble_stride, history_frames, newest_slot, subchannels, fib_bytes, msc_out, out_ensemble_stride,
+                 fic_ber, msc_ber, stream=None, bits_layout=BITS_NATURAL):
+        """ber_frames for rings: newest_slot = device int32 [n], a negative slot yields all-zero records (dabgpu_ber_ring_layout)"""
+        n = len(subchannels)
+        arr = (SubChannel * n)(*subchannels) if n else None
+        check(lib().dabgpu_ber_ring_layout(self._h, _ptr(history), n_ensembles, ensemble_stride, history_frames, _ptr(newest_slot), arr, n,
+                                           _ptr(fib_bytes), _ptr(msc_out), out_ensemble_stride, _ptr(fic_ber), _ptr(msc_ber), int(bits_layout),
+                                           self._stream(stream)), "dabgpu_ber_ring_layout")
+
+    def ber_fib_group(self, bits, fib_bytes):
+        """one FIB group from host memory: 2304 soft bits, 96 decoded bytes -> record of BER_RESULT_DTYPE (dabgpu_ber_fib_group_host_sync)"""
+        import numpy as np
+        b = np.ascontiguousarray(bits, dtype=np.int8)
+        d = np.ascontiguousarray(fib_bytes, dtype=np.uint8)
+        assert b.size == NB_FIB_GROUP_BITS and d.size == 96
+        res = np.zeros(1, np.dtype(BER_RESULT_DTYPE))
+        check(lib().dabgpu_ber_fib_group_host_sync(self._h, _ptr(b), _ptr(d), _ptr(res)), "dabgpu_ber_fib_group_host_sync")
+        return res[0]
+
+    def ber_codeword(self, subchannel, deinterleaved_bits, decoded_bytes):
+        """one sub-channel code word from host memory: its de-interleaved CIF and decoded bytes (dabgpu_ber_codeword_host_sync)"""
+        import numpy as np
+        b = np.ascontiguousarray(deinterleaved_bits, dtype=np.int8)
+        d = np.ascontiguousarray(decoded_bytes, dtype=np.uint8)
+        _, _, nb = subchannel_plan(subchannel)
+        assert b.size == subchannel.length * 64 and d.size == nb
+        res = np.zeros(1, np.dtype(BER_RESULT_DTYPE))
+        check(lib().dabgpu_ber_codeword_host_sync(self._h, C.byref(subchannel), _ptr(b), _ptr(d), _ptr(res)), "dabgpu_ber_codeword_host_sync")
+        return res[0]
 
     def iq_convert(self, raw, fmt, n_samples, iq, stream=None):
         """device raw samples in format number `fmt` -> device interleaved float IQ (asynchronous)"""
@@ -1702,6 +1757,16 @@ def subchannel_plan(sc):
     if n < 0:
         raise DabGpuError("invalid sub-channel protection profile")
     return list(pi)[:n], list(lx)[:n], nb.value
+
+
+def ber_plan(subchannels, n_ensembles, history_frames, ensemble_stride, out_ensemble_stride, bits_layout=BITS_NATURAL):
+    """dabgpu_ber_plan (host only): the BerGeometry of a ber_frames call with these arguments; DabGpuError with the reason when refused"""
+    n = len(subchannels)
+    arr = (SubChannel * n)(*subchannels) if n else None
+    g = BerGeometry()
+    check(lib().dabgpu_ber_plan(arr, n, n_ensembles, history_frames, ensemble_stride, out_ensemble_stride, int(bits_layout), C.byref(g)),
+          "dabgpu_ber_plan")
+    return g
 
 
 def tx_encode_plan(subchannels):

@@ -19,6 +19,12 @@
 // The reader must not overwrite the buffer's head while the observer reads it, so with --tii every Process() call is followed by
 // Synchronize() and --ofdm-block-size may not exceed one frame less a NULL period.
 //
+// --ber (not in the reference; include/dabgpu.h "Channel BER"): the channel decode stage prints one line per frame to stdout,
+//   ber frame=N fic=ERRORS/BITS sub0=ERRORS/BITS ...
+// the channel bit errors of the frame's four FIB groups and of each sub-channel's CIFs that were decoded (0/0 while the time
+// de-interleaver fills).  The decoder classes stay as they are: the stage decodes each FIB group once more for its 96 bytes with the received
+// CRCs, keeps the last 16 CIFs of every sub-channel on the host, de-interleaves by index and hands both to DAB_Channel_BER.
+//
 // --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
@@ -46,6 +52,8 @@
 #include "dab/constants/dab_parameters.h"
 #include "dab/fic/fic_decoder.h"
 #include "dab/msc/msc_decoder.h"
+#include "dab/dabgpu_shared_context.h"
+#include "dab/quality/dab_channel_ber.h"
 #include "dab/tx/dab_channeliser.h"
 #include "dab/tx/dab_resampler.h"
 #include "ofdm/ofdm_helpers.h"
@@ -71,6 +79,7 @@ struct Args {
     double input_rate = 2.048e6;
     bool channelise = false;
     double channel_offset_hz = 0.0;
+    bool ber = false;
 };
 
 static void usage(const char* argv0) {
@@ -80,7 +89,7 @@ static void usage(const char* argv0) {
         "  [--ofdm-enable-output] [--ofdm-output FILE] [--ofdm-output-hard-bytes]\n"
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
-        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ] [--channel-offset-hz F]\n"
+        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -143,11 +152,13 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--radio-subchannel") { const auto v = value(); args.subchannels.push_back(parse_subchannel(v, args.subchannels.size())); }
         else if (a == "--tii") args.tii = true;
         else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
+        else if (a == "--ber") args.ber = true;
         else if (a == "--input-rate") args.input_rate = std::stod(value());
         else if (a == "--channel-offset-hz") { args.channel_offset_hz = std::stod(value()); args.channelise = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
+    if (args.ber && !args.is_dab_used) throw std::runtime_error("--ber needs the channel decode stage");
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
@@ -175,6 +186,19 @@ private:
     std::vector<std::unique_ptr<MSC_Decoder>> m_msc;
     FILE* m_fib_out = nullptr;
     std::vector<FILE*> m_msc_out;
+    // --ber: the meter, each sub-channel as the C ABI describes it and its last 16 CIFs (slot = CIF count mod 16)
+    std::unique_ptr<DAB_Channel_BER> m_ber;
+    std::vector<dabgpu_subchannel> m_ber_sc;
+    std::vector<std::vector<viterbi_bit_t>> m_ber_ring;
+    std::vector<viterbi_bit_t> m_ber_bits;
+    size_t m_ber_cifs = 0;
+    // what CIF_Deinterleaver delivers for the CIF filed last: bit i from the CIF that is 15 - bitrev4(i mod 16) CIFs older
+    void BerDeinterleave(size_t k, size_t newest) {
+        static const int delay[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
+        const size_t n = (size_t)m_ber_sc[k].length * 64;
+        m_ber_bits.resize(n);
+        for (size_t i = 0; i < n; i++) m_ber_bits[i] = m_ber_ring[k][((newest + 16 - (size_t)(15 - delay[i & 15])) & 15) * n + i];
+    }
 public:
     size_t total_frames = 0, total_fibs = 0, total_fib_groups_failed = 0;
     std::vector<size_t> total_msc_bytes;
@@ -197,6 +221,14 @@ public:
             m_msc_out.push_back(f);
             total_msc_bytes.push_back(0);
         }
+        if (args.ber) {
+            m_ber = std::make_unique<DAB_Channel_BER>();
+            for (const Subchannel& s : args.subchannels) {
+                m_ber_sc.push_back({(int)s.start_address, (int)s.length, s.is_uep ? 1 : 0, (int)s.uep_prot_index, (int)s.eep_prot_level,
+                                    s.eep_type == EEP_Type::TYPE_B ? 1 : 0});
+                m_ber_ring.emplace_back((size_t)16 * (size_t)s.length * 64);
+            }
+        }
     }
     ~ChannelDecodeStage() {
         if (m_fib_out) fclose(m_fib_out);
@@ -213,14 +245,43 @@ public:
             m_fic.DecodeFIBGroup(fic_bits.subspan((size_t)c * m_params.nb_fib_cif_bits, (size_t)m_params.nb_fib_cif_bits), (size_t)c);
             if (total_fibs - before != (size_t)m_params.nb_fibs_per_cif) total_fib_groups_failed++;
         }
+        uint64_t fic_err = 0, fic_n = 0;
+        std::vector<uint64_t> sub_err(m_msc.size(), 0), sub_n(m_msc.size(), 0);
+        if (m_ber && m_params.nb_fib_cif_bits == DABGPU_NB_FIB_GROUP_BITS) {
+            for (int c = 0; c < m_params.nb_cifs; c++) {
+                const auto group = fic_bits.subspan((size_t)c * DABGPU_NB_FIB_GROUP_BITS, DABGPU_NB_FIB_GROUP_BITS);
+                uint8_t bytes[96]; uint32_t mask = 0; uint64_t path = 0;
+                const int st = dabgpu_fic_decode_group_host_sync(dabgpu_shared_context(), group.data(), bytes, &mask, &path, dabgpu_tie_rule_from_env());
+                if (st != DABGPU_OK) throw std::runtime_error(std::string("--ber: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
+                dabgpu_ber_result r;
+                if (m_ber->MeasureFIBGroup(group, tcb::span<const uint8_t>(bytes, 96), r)) { fic_err += r.n_errors; fic_n += r.n_bits; }
+            }
+        }
         for (int c = 0; c < m_params.nb_cifs; c++) {
             auto cif = msc_bits.subspan((size_t)c * m_params.nb_cif_bits, (size_t)m_params.nb_cif_bits);
             for (size_t k = 0; k < m_msc.size(); k++) {
                 auto bytes = m_msc[k]->DecodeCIF(cif);
+                if (m_ber) {
+                    const size_t n = (size_t)m_ber_sc[k].length * 64, slot = m_ber_cifs & 15;
+                    memcpy(&m_ber_ring[k][slot * n], cif.data() + (size_t)m_ber_sc[k].start_address * 64, n);
+                    if (!bytes.empty() && m_ber_cifs >= 15) {
+                        BerDeinterleave(k, slot);
+                        dabgpu_ber_result r;
+                        if (m_ber->MeasureSubchannel(m_ber_sc[k], m_ber_bits, tcb::span<const uint8_t>(bytes.data(), bytes.size()), r)) {
+                            sub_err[k] += r.n_errors; sub_n[k] += r.n_bits;
+                        }
+                    }
+                }
                 if (bytes.empty()) continue;                                            // time de-interleaver still filling
                 fwrite(bytes.data(), 1, bytes.size(), m_msc_out[k]);
                 total_msc_bytes[k] += bytes.size();
             }
+            m_ber_cifs++;
+        }
+        if (m_ber) {
+            printf("ber frame=%zu fic=%llu/%llu", total_frames - 1, (unsigned long long)fic_err, (unsigned long long)fic_n);
+            for (size_t k = 0; k < m_msc.size(); k++) printf(" sub%zu=%llu/%llu", k, (unsigned long long)sub_err[k], (unsigned long long)sub_n[k]);
+            printf("\n");
         }
     }
 };

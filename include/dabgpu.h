@@ -1576,6 +1576,65 @@ int dabgpu_ingest_submit(dabgpu_ingest *pipe, size_t bytes, void **d_buffer);
 int dabgpu_ingest_wait(dabgpu_ingest *pipe, const void *d_buffer, void *compute_stream);
 int dabgpu_ingest_consumed(dabgpu_ingest *pipe, const void *d_buffer, void *compute_stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Channel BER: the channel ("pre-Viterbi") bit error rate of every code word a decode call has decoded, without knowing what was sent.
+ * The decoded bytes are encoded again and compared with the hard decisions of the soft bits the decoder consumed.  For one code word of
+ * K = kept_bits of its dabgpu_tx_encode_plan entry (a FIB group: 2304):
+ *   s_i   the soft bit the decoder consumed at position i < K: FIC, soft bit i of the FIB group; MSC, what CIF_Deinterleaver delivers
+ *         for that CIF (bit i of the sub-channel comes from the CIF that is 15 - bitrev4(i mod 16) CIFs older, read from the same ring
+ *         and in the same layout as dabgpu_msc_decode_frames_layout reads it)
+ *   e_i   bit i of the code word the channel encoder makes of the decoder's output bytes AS THEY STAND (the 96 bytes of a FIB group with
+ *         the received CRC bytes, or the sub-channel's bytes of that CIF): energy dispersal, K = 7 rate-1/4 code with zero tail,
+ *         puncturing -- the schedule of dabgpu_tx_encode_plan; nothing is corrected or recomputed
+ *   h_i   = (s_i >= 0), as dabgpu_soft_bits_to_hard_bytes decides; |s_i| in integer arithmetic, |-128| = 128
+ * Soft bits of the capacity units beyond K are not read.  Every field is an integer: the results have no tolerance. */
+typedef struct {
+    uint32_t n_bits;        /* positions i < K with s_i != 0 (a 0 is an erasure: not compared) */
+    uint32_t n_errors;      /* of those, h_i != e_i */
+    uint32_t error_weight;  /* sum of |s_i| over the error positions */
+    uint32_t total_weight;  /* sum of |s_i| over all i < K */
+} dabgpu_ber_result;
+
+/* dabgpu_ber_plan (host only, no device): the launch a dabgpu_ber_frames_layout call with these arguments makes, FIC and MSC both.
+ * Refuses with DABGPU_ERR_INVALID_ARG and the reason in dabgpu_last_error(), in this order: a sub-channel count outside 0..64 (or a null
+ * list); a descriptor dabgpu_subchannel_validate refuses, in list order; a multiplex dabgpu_tx_encode_plan refuses (two sub-channels that
+ * overlap); n_ensembles outside 1..1048576; an unknown bits_layout; history_frames < 5; ensemble_stride < history_frames x 230400 or not
+ * a multiple of 16; out_ensemble_stride < 4 x the CIF's decoded bytes or not a multiple of 4 (n_sub > 0 only).  n_sub = 0 is legal: FIC
+ * only. */
+typedef struct {
+    uint32_t n_sub;
+    uint32_t codewords_per_ensemble;    /* 4 x n_sub sub-channel code words + 4 FIB groups: one wavefront each */
+    uint32_t cif_bytes;                 /* decoded bytes of one CIF of all sub-channels (dabgpu_tx_encode_plan's cif_in_bytes) */
+    uint32_t n_sched;                   /* entries of the multiplex's kept-bit schedules */
+    uint32_t sched_offset[65];          /* first schedule entry of sub-channel s; [n_sub] = the FIB group's */
+    uint32_t max_kept_bits;             /* K of the longest code word */
+    uint32_t lds_bytes;                 /* LDS one wavefront holds its code word in: whole blocks of 512 bits */
+    uint32_t waves_per_block, block_threads;
+    uint32_t grid;                      /* workgroups */
+} dabgpu_ber_geometry;
+int dabgpu_ber_plan(const dabgpu_subchannel *subs, int n_sub, size_t n_ensembles, int history_frames, size_t ensemble_stride,
+                    size_t out_ensemble_stride, int bits_layout, dabgpu_ber_geometry *out);
+
+/* The batch forms.  The arguments are those of dabgpu_decode_frames_layout / dabgpu_decode_ring_layout, whose outputs d_fib_bytes
+ * [n_ensembles][4][96] and d_msc_out are inputs here; d_fic_ber [n_ensembles][4], d_msc_ber [n_ensembles][4][n_sub].  A half whose bytes
+ * or records are NULL is skipped (and the MSC half when n_subchannels = 0).  d_bits_history 16-byte aligned, the byte and record
+ * pointers 4- and 16-byte aligned.  Ring form: an ensemble with a negative slot gets all-zero records.  One launch, one pass over the
+ * soft bits, nothing intermediate in device memory; a steady-state call enqueues that kernel only and may be captured in a HIP graph
+ * (the first call with a multiplex uploads its tables, as the decoders do: run once before capturing). */
+int dabgpu_ber_frames_layout(dabgpu_ctx *ctx, const int8_t *d_bits_history, size_t n_ensembles, size_t ensemble_stride, int history_frames,
+                             int newest_frame_slot, const dabgpu_subchannel *h_subchannels, int n_subchannels, const uint8_t *d_fib_bytes,
+                             const uint8_t *d_msc_out, size_t out_ensemble_stride, dabgpu_ber_result *d_fic_ber,
+                             dabgpu_ber_result *d_msc_ber, int bits_layout, void *stream);
+int dabgpu_ber_ring_layout(dabgpu_ctx *ctx, const int8_t *d_hist, size_t n_ensembles, size_t ensemble_stride, int history_frames,
+                           const int32_t *d_newest_slot, const dabgpu_subchannel *h_subchannels, int n_subchannels,
+                           const uint8_t *d_fib_bytes, const uint8_t *d_msc_out, size_t out_ensemble_stride, dabgpu_ber_result *d_fic_ber,
+                           dabgpu_ber_result *d_msc_ber, int bits_layout, void *stream);
+/* One code word from and to host memory, synchronous, on the context's stream (the mirror layer's forms): a FIB group's 2304 soft bits
+ * and 96 decoded bytes; a sub-channel's de-interleaved CIF (length x 64 soft bits, of which the first K are read) and its decoded bytes */
+int dabgpu_ber_fib_group_host_sync(dabgpu_ctx *ctx, const int8_t *h_bits /*[2304]*/, const uint8_t *h_bytes /*[96]*/, dabgpu_ber_result *result);
+int dabgpu_ber_codeword_host_sync(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, const int8_t *h_deinterleaved_bits, const uint8_t *h_bytes,
+                                  dabgpu_ber_result *result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,12 @@ With --adjacent-db A[,B...] [--adjacent-sides 1|2] the run is the white-noise ch
 (dabgpu.Channeliser, D = 4): the block 300 kHz above the centre of an 8.192 MS/s capture with a neighbour 1.712 MHz above it (sides = 1) or
 to either side (2, the default), A dB above the wanted block's signal power -- the clean transmission rolled by 50001 and 120007 samples --,
 then split back out; one table per level, APPENDED to --out: the adjacent block's place in the sensitivity record.
+With --ber every table gains two columns: the channel BER the receiver MEASURES (dabgpu_ber_frames_layout on what it decoded: errors / bits over the
+FIB groups of every frame and the sub-channel code words from CIF 15 on) and the TRUE channel BER of the same soft bits against the transmitted
+bits (a second TxBank keeps the frame bits).  The two agree while the decoders deliver; below the waterfall the measured figure falls short of
+the true one, because a wrongly decoded code word is re-encoded into a neighbour of what was received.  Without the flag the output is unchanged.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
-                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2]"""
+                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber]"""
 import argparse
 import math
 import os
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--clock-ppm", default=None)
     ap.add_argument("--adjacent-db", default=None)
     ap.add_argument("--adjacent-sides", type=int, default=2, choices=(1, 2))
+    ap.add_argument("--ber", action="store_true")
     a = ap.parse_args()
     if a.adjacent_db is not None and (a.doppler_hz is not None or a.clock_ppm is not None):
         ap.error("--adjacent-db is not available with --doppler-hz or --clock-ppm")
@@ -72,6 +77,28 @@ def main():
     bank = dabgpu.TxBank(ctx, 1, subs)
     d_iq = torch.zeros((F * S, 2), dtype=torch.float32, device="cuda")
     bank.transmit_frames(torch.from_numpy(fib).cuda(), torch.from_numpy(pay).cuda(), F, d_iq)
+    if a.ber:
+        # the transmitted frame bits (a bank of its own: transmit_frames above has advanced the first one's time interleaver) and, per frame, where
+        # the decoders' soft bits come from: (ring slot, frame bit) of the FIC and of every sub-channel code word from CIF 15 on
+        bank2 = dabgpu.TxBank(ctx, 1, subs)
+        d_sent = torch.zeros((F, dabgpu.NB_FRAME_BITS // 8), dtype=torch.uint8, device="cuda")
+        bank2.encode_frames(torch.from_numpy(fib).cuda(), torch.from_numpy(pay).cuda(), F, d_sent)
+        torch.cuda.synchronize()
+        bank2.close()
+        sent = torch.from_numpy(np.unpackbits(d_sent.cpu().numpy(), axis=1, bitorder="little").astype(np.bool_)).cuda()
+        delay = np.array([0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15])
+        consumed = []
+        for j in range(F):
+            fr, pos = [np.full(dabgpu.NB_FIC_BITS, j)], [np.arange(dabgpu.NB_FIC_BITS)]
+            for c in range(4):
+                if 4 * j + c < 15:
+                    continue
+                for p in plan["subs"]:
+                    i = np.arange(int(p.kept_bits))
+                    cif = 4 * j + c - (15 - delay[i % 16])
+                    fr.append(cif // 4); pos.append(dabgpu.NB_FIC_BITS + dabgpu.NB_CIF_BITS * (cif % 4) + 64 * int(p.start_address) + i)
+            consumed.append((torch.from_numpy(np.concatenate(fr)).cuda(), torch.from_numpy(np.concatenate(pos)).cuda()))
+        bdt = np.dtype(dabgpu.BER_RESULT_DTYPE)
     n_out = F * S + 4096
     n_rx = n_out + (256 if clock_ppm or adjacent_db else 0)                   # (the resampler and the combiner read ahead of their output)
     ADJ_D, ADJ_RATE, ADJ_OFFSET, ADJ_SPACING, ADJ_ROLLS = 4, 8192000.0, 300000.0, 1712000.0, (50001, 120007)
@@ -122,7 +149,7 @@ def main():
             comb, spl = dabgpu.Channeliser(ctx, both, E, ADJ_D), dabgpu.Channeliser(ctx, wanted, E, ADJ_D)
         rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
-        rows = []
+        rows, chan = [], []
         ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
@@ -144,6 +171,9 @@ def main():
             d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
             msc = torch.zeros((E, 4, nb), dtype=torch.uint8, device="cuda"); mres = torch.zeros((E * 4 * len(subs), 16), dtype=torch.uint8, device="cuda")
             crc_ok, crc_n = 0, 0
+            if a.ber:
+                fic_ber = torch.zeros((E, 4, 16), dtype=torch.uint8, device="cuda"); msc_ber = torch.zeros((E, 4, len(subs), 16), dtype=torch.uint8, device="cuda")
+                m_err = m_bits = t_err = t_bits = 0
             err = [0] * len(LEVELS); tot = [0] * len(LEVELS)
             for j in range(F):
                 a0 = NULL + j * S - P_LEAD
@@ -152,6 +182,15 @@ def main():
                 sl[:, :seg.shape[1]] = seg
                 ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
                 ctx.decode_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
+                if a.ber:
+                    ctx.ber_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, msc, 4 * nb, fic_ber, msc_ber)
+                    torch.cuda.synchronize()
+                    recs = [fic_ber.cpu().numpy().view(bdt).reshape(E, 4)] + [msc_ber.cpu().numpy().view(bdt).reshape(E, 4, len(subs))[:, c]
+                                                                              for c in range(4) if 4 * j + c >= 15]
+                    m_err += sum(int(r["n_errors"].sum()) for r in recs); m_bits += sum(int(r["n_bits"].sum()) for r in recs)
+                    fr, pos = consumed[j]
+                    soft = hist[:, fr % H, pos]
+                    t_err += int(((soft != 0) & ((soft >= 0) != sent[fr, pos][None, :])).sum()); t_bits += int((soft != 0).sum())
                 torch.cuda.synchronize()
                 masks = fres.cpu().numpy().view(rdt)["crc_ok_mask"].reshape(-1)
                 crc_ok += int(sum(bin(int(m) & 7).count("1") for m in masks)); crc_n += 3 * masks.size
@@ -162,6 +201,9 @@ def main():
                     for i, (off, n) in enumerate(spans):
                         err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
             rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
+            if a.ber:
+                assert m_bits == t_bits
+                chan.append((m_err / m_bits, t_err / t_bits))
         ch.close()
         if rs is not None:
             rs.close()
@@ -169,6 +211,11 @@ def main():
             comb.close(); spl.close()
         text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
         text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
+        if a.ber:
+            n0 = len(text) - len(rows) - 2
+            text[n0] += " channel BER measured | channel BER true |"; text[n0 + 1] += "---|---|"
+            for k, (m, tr) in enumerate(chan):
+                text[n0 + 2 + k] += f" {m:.3e} | {tr:.3e} |"
         # acceptance: error-free at the top, non-increasing within counting error, required SNR ordered by level
         top = rows[-1]
         free = top[1] == 1.0 and all(r == 0 for r in top[2])
