@@ -254,9 +254,11 @@ extern "C" int dabgpu_ofdm_auto_symbols_per_block(dabgpu_ctx* c, size_t n_frames
 
 static int ofdm_demod_any(dabgpu_ctx* c, const void* d_iq, int src, size_t n_frames, const float* d_freq, int8_t* d_bits,
                          float* d_cp_corr, float* d_fft, float* d_dqpsk, int symbols_per_block, size_t bits_frame_stride, void* stream,
-                         int bits_layout = DABGPU_BITS_NATURAL, float* d_total_phase = nullptr, float* d_fine_freq = nullptr, float beta = 0.0f) {
+                         int bits_layout = DABGPU_BITS_NATURAL, float* d_total_phase = nullptr, float* d_fine_freq = nullptr, float beta = 0.0f,
+                         const dabgpu_soft_cfg* soft = nullptr, float* d_soft_scale = nullptr) {
     int st = dabgpu_check_bits_layout("ofdm_demod_frames", bits_layout);
     if (st) return st;
+    if (soft && (st = dabgpu_host_check_soft_cfg("ofdm_demod_frames_soft", soft))) return st;
     if (!c || !d_iq || !d_bits) { dabgpu_set_error("ofdm_demod_frames: null ctx/iq/bits"); return DABGPU_ERR_INVALID_ARG; }
     if (n_frames == 0) return DABGPU_OK;
     if (n_frames > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_demod_frames: n_frames too large"); return DABGPU_ERR_INVALID_ARG; }
@@ -275,7 +277,19 @@ static int ofdm_demod_any(dabgpu_ctx* c, const void* d_iq, int src, size_t n_fra
     call.d_cp_corr = corr; call.d_fft = d_fft; call.d_dqpsk = d_dqpsk;
     call.n_frames = (int)n_frames; call.symbols_per_block = symbols_per_block;
     call.d_total_phase = d_total_phase; call.d_fine_freq = d_fine_freq; call.beta = beta;
+    if (soft && soft->policy != DABGPU_SOFT_NORMALISED) { call.soft_policy = soft->policy; call.soft_level = soft->level; call.d_soft_scale = d_soft_scale; }
     return dabgpu_launch_demod(c, 1, call, s);
+}
+
+int dabgpu_ofdm_demod_frames_soft(dabgpu_ctx* c, const void* d_raw, int format, size_t n_frames, const float* d_freq, int8_t* d_bits,
+                                  float* d_cp_corr, float* d_fft, float* d_dqpsk, int symbols_per_block, size_t bits_frame_stride, int bits_layout,
+                                  const dabgpu_soft_cfg* cfg, float* d_soft_scale, void* stream) {
+    if (!cfg) { dabgpu_set_error("ofdm_demod_frames_soft: null soft-decision configuration"); return DABGPU_ERR_INVALID_ARG; }
+    const int src = dabgpu_fused_loader(format, "ofdm_demod_frames_soft");
+    if (src < 0) return DABGPU_ERR_INVALID_ARG;
+    // (the display views with the class order are refused by the planner, as for every caller)
+    return ofdm_demod_any(c, d_raw, src, n_frames, d_freq, d_bits, d_cp_corr, d_fft, d_dqpsk, symbols_per_block, bits_frame_stride, stream, bits_layout,
+                          nullptr, nullptr, 0.0f, cfg, d_soft_scale);
 }
 
 int dabgpu_ofdm_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_frames, const float* d_freq, int8_t* d_bits,
@@ -393,12 +407,13 @@ int dabgpu_ofdm_tuned_symbols_per_block(dabgpu_ctx* c, int format, size_t n_fram
 // One steady-state frame of n receivers: PRS synchronisation, then the demodulation it positions and corrects, then the fine-frequency
 // update -- three dependent steps of OFDM_Demod per frame (ofdm_demodulator.cpp:360-548, :650-766, :606-618) with the records of the
 // first read by the second and third on the device.
-int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
-                                  const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
-                                  size_t bits_frame_stride, int bits_layout, float* d_total_phase, void* stream) {
+static int sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
+                             const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
+                             size_t bits_frame_stride, int bits_layout, float* d_total_phase, const dabgpu_soft_cfg* soft, float* d_soft_scale, void* stream) {
     if (!c || !d_iq || !cfg || !d_states || !d_bits) { dabgpu_set_error("ofdm_sync_demod_frames: null argument"); return DABGPU_ERR_INVALID_ARG; }
     int st = dabgpu_check_bits_layout("ofdm_sync_demod_frames", bits_layout);
     if (st) return st;
+    if (soft && (st = dabgpu_host_check_soft_cfg("ofdm_sync_demod_frames_soft", soft))) return st;
     if (n_streams == 0) return DABGPU_OK;
     if (n_streams > (size_t)(1 << 24)) { dabgpu_set_error("ofdm_sync_demod_frames: n_streams too large"); return DABGPU_ERR_INVALID_ARG; }
     // the impulse peak lies in [0, 2048): the frame starts between 504 samples before and 1543 after the expected position
@@ -420,7 +435,24 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_str
     call.symbols_per_block = symbols_per_block > 0 ? symbols_per_block : demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
     call.d_sync = d_states; call.prs_offset = (int)prs_offset_samples;
     call.d_total_phase = d_total_phase; call.beta = cfg->fine_freq_update_beta;
+    if (soft && soft->policy != DABGPU_SOFT_NORMALISED) { call.soft_policy = soft->policy; call.soft_level = soft->level; call.d_soft_scale = d_soft_scale; }
     return dabgpu_launch_demod(c, 1, call, s, "ofdm_demod_kernel launch (synchronised frames)");
+}
+
+int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
+                                  const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
+                                  size_t bits_frame_stride, int bits_layout, float* d_total_phase, void* stream) {
+    return sync_demod_frames(c, d_iq, n_streams, stream_stride_samples, prs_offset_samples, cfg, d_states, d_bits, d_cp_corr, symbols_per_block,
+                             bits_frame_stride, bits_layout, d_total_phase, nullptr, nullptr, stream);
+}
+
+int dabgpu_ofdm_sync_demod_frames_soft(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
+                                       const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
+                                       size_t bits_frame_stride, int bits_layout, float* d_total_phase, const dabgpu_soft_cfg* soft, float* d_soft_scale,
+                                       void* stream) {
+    if (!soft) { dabgpu_set_error("ofdm_sync_demod_frames_soft: null soft-decision configuration"); return DABGPU_ERR_INVALID_ARG; }
+    return sync_demod_frames(c, d_iq, n_streams, stream_stride_samples, prs_offset_samples, cfg, d_states, d_bits, d_cp_corr, symbols_per_block,
+                             bits_frame_stride, bits_layout, d_total_phase, soft, d_soft_scale, stream);
 }
 
 // ---- one body per operation for every transmission mode: the mode I entry points are the mode forms with mode = 1 ----

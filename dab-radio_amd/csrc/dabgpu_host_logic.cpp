@@ -1,6 +1,7 @@
 // dabgpu_host_logic.cpp -- see dabgpu_host_logic.h.  No device code and no HIP call in this file.
 #include "dabgpu_host_logic.h"
 #include "packet_fec_core.h"
+#include "softbit_csi_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -112,6 +113,17 @@ void dabgpu_sync_cfg_default(dabgpu_sync_cfg* cfg) {          // ofdm_demodulato
     cfg->impulse_peak_distance_probability = 0.15f;
 }
 
+void dabgpu_soft_cfg_default(dabgpu_soft_cfg* cfg) {
+    if (!cfg) return;
+    cfg->policy = DABGPU_SOFT_NORMALISED;
+    cfg->level = 64.0f;
+}
+
+float dabgpu_soft_scale_host(const float* h_prs_useful, float level) {
+    if (!h_prs_useful || !dabgpu::sb_level_ok(level)) return 0.0f;
+    return dabgpu::sb_scale(level, dabgpu::sb_frame_power(h_prs_useful));
+}
+
 void dabgpu_stream_cfg_default(dabgpu_stream_cfg* c) {
     if (!c) return;
     c->signal_l1_update_beta = 0.95f; c->signal_l1_nb_samples = 100; c->signal_l1_nb_decimate = 5;      // ofdm_demodulator.h:25-29
@@ -162,6 +174,15 @@ int dabgpu_host_spb_bucket(size_t n_frames) {
 // kernel variant of a call: loader (0..3), soft-bit layout, whether the phase tail runs with it (fused at 75, a second launch otherwise)
 int dabgpu_host_spb_variant(int src, int bits_layout, bool tail) { return src * 4 + (bits_layout == DABGPU_BITS_MSC_CLASSED ? 2 : 0) + (tail ? 1 : 0); }
 
+int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg) {
+    if (!cfg) { dabgpu_set_error("%s: null soft-decision configuration", who); return DABGPU_ERR_INVALID_ARG; }
+    if (cfg->policy != DABGPU_SOFT_NORMALISED && cfg->policy != DABGPU_SOFT_CSI) {
+        dabgpu_set_error("%s: no soft-decision policy %d", who, cfg->policy); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!dabgpu::sb_level_ok(cfg->level)) { dabgpu_set_error("%s: soft level %g outside [1, 127]", who, (double)cfg->level); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
 dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f) {
     dabgpu_demod_plan p = {};
     p.status = DABGPU_ERR_INVALID_ARG;
@@ -175,7 +196,15 @@ dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f) 
         if (f.desc && (f.sync || f.frame_stride)) { dabgpu_set_error("ofdm_demod: a bank round takes neither sync records nor a frame stride"); return p; }
         p.family = DABGPU_DEMOD_MODE1;
         p.variant = (f.src * 2 + (f.desc ? 1 : 0)) * 3 + (f.classed ? 2 : views ? 1 : 0);
-    } else {
+    }
+    if (f.soft_policy != DABGPU_SOFT_NORMALISED) {
+        if (f.soft_policy != DABGPU_SOFT_CSI) { dabgpu_set_error("ofdm_demod: no soft-decision policy %d", f.soft_policy); return p; }
+        if (!mode1) { dabgpu_set_error("ofdm_demod: the weighted soft bits exist for the transmission mode I kernel only (mode %d)", mode); return p; }
+        if (f.desc) { dabgpu_set_error("ofdm_demod: the weighted soft bits have no stream-bank loader (frame descriptors)"); return p; }
+        if (!dabgpu::sb_level_ok(f.soft_level)) { dabgpu_set_error("ofdm_demod: soft level %g outside [1, 127]", (double)f.soft_level); return p; }
+        p.variant = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + f.src * 3 + (f.classed ? 2 : views ? 1 : 0);
+    }
+    if (!mode1) {
         // modes II-IV run register-resident unless the FFT view, which only the size-generic kernel writes, is wanted
         p.family = (mode == 1 || f.fft || f.switch_generic) ? DABGPU_DEMOD_GENERIC
                    : (mode == 3 && !f.switch_mode3_single)   ? DABGPU_DEMOD_WAVE3

@@ -186,11 +186,13 @@ dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t
 // Four kernel families: the register-resident mode I kernel (ofdm_demod.hip), the size-generic kernel (ofdm_modes.hip), one wavefront per
 // run of symbols for modes II-IV, and two symbols per wavefront for mode III (ofdm_wave512.hip).  Each keeps a table of its kernels,
 // indexed by `variant`:
-//   mode I:        ((src * 2 + bank) * 3 + layout), layout 0 = soft bits, 1 = + display views, 2 = soft bits in class order
+//   mode I:        ((src * 2 + bank) * 3 + layout), layout 0 = soft bits, 1 = + display views, 2 = soft bits in class order;
+//                  weighted soft bits (DABGPU_SOFT_CSI) follow as 24 + src * 3 + layout: they have no bank loader
 //   other families: 0 without descriptors (complex float only), 1 + src with them
 enum dabgpu_demod_family { DABGPU_DEMOD_MODE1, DABGPU_DEMOD_GENERIC, DABGPU_DEMOD_WAVE, DABGPU_DEMOD_WAVE3 };
 enum dabgpu_demod_tail { DABGPU_DEMOD_TAIL_NONE, DABGPU_DEMOD_TAIL_FUSED, DABGPU_DEMOD_TAIL_LAUNCH };
-constexpr int DABGPU_DEMOD_MODE1_VARIANTS = 4 * 2 * 3, DABGPU_DEMOD_LOADER_VARIANTS = 1 + 4;
+constexpr int DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS = 4 * 2 * 3, DABGPU_DEMOD_MODE1_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + 4 * 3;
+constexpr int DABGPU_DEMOD_LOADER_VARIANTS = 1 + 4;
 // the facts of a call that are not addresses.  The views, class order, sync records, frame stride and phase outputs are the mode I kernel's:
 // the other families have none of them (the FFT view apart, which only the size-generic kernel writes) and do not look at these facts.
 struct dabgpu_demod_facts {
@@ -204,6 +206,8 @@ struct dabgpu_demod_facts {
     bool generic_mode1 = false;             // mode I runs on the size-generic kernel too (dabgpu_ofdm_demod_frames_mode: the tests cross-check the two)
     bool switch_generic = false;            // DABGPU_MODE_GENERIC: modes II-IV stay on the size-generic kernel
     bool switch_mode3_single = false;       // DABGPU_MODE3_SINGLE: mode III, one symbol per wavefront
+    int soft_policy = DABGPU_SOFT_NORMALISED;   // DABGPU_SOFT_CSI: the mode I kernel without descriptors only
+    float soft_level = 64.0f;               // [1, 127], looked at under DABGPU_SOFT_CSI
 };
 struct dabgpu_demod_plan {
     int status;                             // DABGPU_OK, or DABGPU_ERR_INVALID_ARG (reason in dabgpu_last_error): nothing else is set then
@@ -217,6 +221,8 @@ struct dabgpu_demod_plan {
     int fine_stride;                        // floats between the fine-frequency words of two frames
 };
 dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f);
+// a dabgpu_soft_cfg as an entry point receives it (`who` names it in the message): a policy that exists, a level in [1, 127]
+int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg);
 
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps

@@ -176,6 +176,10 @@ struct dabgpu_demod_call {
     float* d_total_phase = nullptr;
     float* d_fine_freq = nullptr;
     float beta = 0.0f;
+    // soft-decision policy (dabgpu_soft_cfg); DABGPU_SOFT_CSI: d_soft_scale [n_frames] receives the scale of every frame (may be null)
+    int soft_policy = DABGPU_SOFT_NORMALISED;
+    float soft_level = 64.0f;
+    float* d_soft_scale = nullptr;
 };
 // plans the call (dabgpu_host_plan_demod) and launches the demodulation kernel of the mode's family, then the phase kernel if the plan asks for it;
 // what = how a HIP failure of the mode I launch is reported (the entry points' own wording)

@@ -27,6 +27,7 @@
 #include "dabgpu_internal.h"
 #include "iq_decode.h"
 #include "ofdm_device.h"
+#include "softbit_csi_core.h"
 
 // wave priority by phase of the symbol loop, one hex digit per point (F = leave as it is): start of symbol, before the
 // correlation, after barrier 1, after barrier 2, after the last radix-8 pass, end of the demapper
@@ -125,6 +126,9 @@ struct demod_phase_tail { float* total_phase; float* fine_freq; float beta; int 
 // and is corrected by freq_coarse + freq_fine (:672) -- the record ofdm_sync_kernel has just written, read on the device
 struct demod_frame_src { size_t stride; const dabgpu_sync_state* sync; int prs_offset; };
 
+// weighted soft bits (CSI instantiations): the level, and where frame k's scale is reported as scale[k] (may be null)
+struct demod_soft { float level; float* scale; };
+
 // LDS of one workgroup (float2 elements unless noted)
 constexpr int LDS_TW1 = 6 * 256;           // pass-1 twiddles [thread][6]: a private 48-byte slot per thread (registers parked in LDS)
 constexpr int LDS_TW3 = 7 * 8;             // pass-3 twiddles [k][lane & 7] (stream-bank and class-order instantiations only: they need the registers)
@@ -146,7 +150,13 @@ constexpr size_t DEMOD_LDS_BYTES = (4 * WAVE_PATCH) * sizeof(f2) + NB_SYM_BITS +
 // output CIF the bits of class c from the CIF that is 15 - bitrev4(c) CIFs old (cif_deinterleaver.cpp:57-68), reads each history row
 // in contiguous pieces instead of one byte in sixteen.  The permutation rides on the frequency de-interleave scatter (a second
 // set of LDS positions) and on the row store's addresses: no extra pass, no extra instructions.  The FIC symbols stay as they are.
-template <int SRC, bool BANK, bool VIEWS = true, bool CLASSED = false>
+//
+// CSI = true (DABGPU_SOFT_CSI; arithmetic: softbit_csi_core.h): the soft bits keep the amplitude of the DQPSK product and are scaled by
+// one factor per frame, k = level * 1536 / (2048 P), P = the power of the 2048 useful samples of the frame's symbol 0 as the loader
+// delivers them.  Every workgroup forms P once, before its first symbol, by the header's tree: a run that starts at symbol 0 has the
+// samples in registers already, any other reads them in addition; the four wavefront sums meet in LDS at the barrier the set-up has
+// anyway.  The demapper is then one multiplication per component: no quotient, no range test.
+template <int SRC, bool BANK, bool VIEWS = true, bool CLASSED = false, bool CSI = false>
 __global__ __launch_bounds__(256, (VIEWS || (BANK && CLASSED)) ? 3 : 4)      // (the display views, and the stream-bank loader with the
                                                                             // second position set, need a few more registers: 3 workgroups per CU instead of spills)
 void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ freq_offset,
@@ -154,8 +164,9 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
                        f2* __restrict__ dqpsk_out_, const f2* __restrict__ tw, const uint16_t* __restrict__ inv_map,
                        int n_frames, int sym_per_chunk, int chunks_per_frame, size_t bits_frame_stride,
                        const dabgpu_frame_desc* __restrict__ desc, const void* __restrict__ tail, size_t tail_stride, demod_phase_tail pt,
-                       const void* __restrict__ prev_tail, demod_frame_src fs)
+                       const void* __restrict__ prev_tail, demod_frame_src fs, demod_soft soft)
 {
+    static_assert(!(CSI && BANK), "the weighted soft bits have no stream-bank loader");
     f2* const fft_out = VIEWS ? fft_out_ : nullptr;
     f2* const dqpsk_out = VIEWS ? dqpsk_out_ : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -256,6 +267,24 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
     // they are on their way (they were issued behind them: two memory latencies in series at the start of every workgroup)
     f4 v[4], h = f4{0.0f, 0.0f, 0.0f, 0.0f};
     load_symbol(out0, v, h);
+    // weighted soft bits: this lane's share of the frame power, from the first symbol's samples where the run starts there
+    float* const sb_sums = reinterpret_cast<float*>(ph_corr + 80) + NB_FRAME_SYMBOLS;      // the four floats behind the 76 angles
+    if constexpr (CSI) {
+        f4 q[4];
+        if (out0 == 0) {                                                 // (uniform)
+#pragma unroll
+            for (int k = 0; k < 4; k++) q[k] = v[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) q[k] = load_pair_buf<SRC>(iq_rs, lane_off, (unsigned)(NB_CP + 512 * k) * SB);
+        }
+        float acc = sb_power_first(q[0].x, q[0].y);
+        acc = sb_power_next(acc, q[0].z, q[0].w);
+#pragma unroll
+        for (int k = 1; k < 4; k++) { acc = sb_power_next(acc, q[k].x, q[k].y); acc = sb_power_next(acc, q[k].z, q[k].w); }
+        acc = wave_tree_sum(acc, lane);
+        if (lane == 0) sb_sums[wave] = acc;
+    }
 
     // PLL constants: this thread always touches sample pairs (n, n+1) with n & 3 == 2*(t&1)
     const int k0 = 2 * (t & 1);
@@ -286,6 +315,12 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
     __syncthreads();
     const f4* const w1p = reinterpret_cast<const f4*>(tw1l + 6 * t);      // (w1a[k], w1b[k]) = w1p[k - 1]
     const f2* const w3p = tw3l + (lane & 7);      // w3[k] = w3p[8 (k - 1)]
+    float soft_k = 0.0f;
+    if constexpr (CSI) {
+        const float P = sb_power_join(sb_sums[0], sb_sums[1], sb_sums[2], sb_sums[3]);
+        soft_k = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sb_scale(soft.level, P))));      // uniform: a scalar register
+        if (chunk == 0 && t == 0 && soft.scale != nullptr) soft.scale[frame] = soft_k;
+    }
 
     // LDS addresses (float2 element indices); every per-k term below is an instruction immediate
     f2* patch = patch0 + wave * WAVE_PATCH;
@@ -442,16 +477,35 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
         const bool emit = (i > out0) && (i < NB_FRAME_SYMBOLS);
         if (emit) {
             // ---- DQPSK (X_{i-1} * conj(X_i)) + soft bits, scattered to their de-interleaved positions ----
-            f2 dq[6];
-            float An[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-                const f2 d = conj_mul(pv[k], cur[k]);
+            // natural order: every byte goes to LDS as soon as it exists; class order keeps the twelve until the (uniform) choice of
+            // the position set, so that the choice is one branch and not twelve selects
+            int bx[CLASSED ? 6 : 1], by[CLASSED ? 6 : 1];
+            auto put = [&](const int k, const int vx, const int vy) __attribute__((always_inline)) {
+                if constexpr (CLASSED) { bx[k] = vx; by[k] = vy; }
+                else { obuf[pos[k]] = (int8_t)vx; obuf[pos[k] + 1536] = (int8_t)vy; }
+            };
+            auto view = [&](const int k, const f2 d) __attribute__((always_inline)) {
                 if (dqpsk_out != nullptr) {                              // GetFrameDataVec() view, natural carrier order
                     const int cbase[6] = {767, 1023, 1279, 0, 256, 512};
                     const int c = (k == 0 && Kb == 0) ? 1535 : (cbase[k] + Kb);
                     dqpsk_out[((size_t)frame * (NB_FRAME_SYMBOLS - 1) + (i - 1)) * 1536 + c] = d;
                 }
+            };
+            if constexpr (CSI) {
+                // weighted: the amplitude of d stays, one multiplication per component by the frame's scale (softbit_csi_core.h)
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    const f2 d = conj_mul(pv[k], cur[k]);
+                    view(k, d);
+                    put(k, sb_soft_bit(d.x, soft_k), sb_soft_bit(-d.y, soft_k));
+                }
+            } else {
+            f2 dq[6];
+            float An[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                const f2 d = conj_mul(pv[k], cur[k]);
+                view(k, d);
                 const float ar = __builtin_fabsf(d.x), ai = __builtin_fabsf(d.y);
                 dq[k] = d;
                 An[k] = (ar < ai) ? ai : ar;                             // std::max, ofdm_demodulator.cpp:882
@@ -462,13 +516,6 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
             // depends on A only and is shared by both quotients; outside the range (or NaN) the plain expressions run.
             const float amin = __builtin_fminf(__builtin_fminf(__builtin_fminf(An[0], An[1]), An[2]), __builtin_fminf(__builtin_fminf(An[3], An[4]), An[5]));
             const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(An[0], An[1]), An[2]), __builtin_fmaxf(__builtin_fmaxf(An[3], An[4]), An[5]));
-            // natural order: every byte goes to LDS as soon as it exists; class order keeps the twelve until the (uniform) choice of
-            // the position set, so that the choice is one branch and not twelve selects
-            int bx[CLASSED ? 6 : 1], by[CLASSED ? 6 : 1];
-            auto put = [&](const int k, const int vx, const int vy) __attribute__((always_inline)) {
-                if constexpr (CLASSED) { bx[k] = vx; by[k] = vy; }
-                else { obuf[pos[k]] = (int8_t)vx; obuf[pos[k] + 1536] = (int8_t)vy; }
-            };
             if (amin >= 0x1p-60f && amax <= 0x1p60f) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
@@ -485,6 +532,7 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
             } else {
 #pragma unroll
                 for (int k = 0; k < 6; k++) put(k, to_vbit(dq[k].x / An[k]), to_vbit(-(dq[k].y / An[k])));
+            }
             }
             if constexpr (CLASSED) {
                 if (i - 1 >= NB_FIC_SYMBOLS) {                                    // (uniform) MSC symbol in class order
@@ -547,14 +595,18 @@ void ofdm_phase_kernel(const f2* __restrict__ cp_corr, int n_frames, float beta,
 // ---- launchers ----
 namespace {
 using namespace dabgpu;
-// variant -> kernel, the planner's numbering (dabgpu_host_logic.h): ((loader * 2 + bank) * 3 + layout), layout 1 = display views, 2 = class order
+// variant -> kernel, the planner's numbering (dabgpu_host_logic.h): ((loader * 2 + bank) * 3 + layout), layout 1 = display views, 2 = class order;
+// behind those, the weighted soft bits: 24 + loader * 3 + layout (no stream-bank loader)
 using demod_kernel_t = decltype(&ofdm_demod_kernel<SRC_C32, false>);
+constexpr int NORM_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS;
 template <int... V>
 constexpr std::array<demod_kernel_t, sizeof...(V)> mode1_kernels(std::integer_sequence<int, V...>) {
-    return {{ofdm_demod_kernel<V / 6, (V / 3) % 2 == 1, V % 3 == 1, V % 3 == 2>...}};
+    return {{ofdm_demod_kernel<(V < NORM_VARIANTS ? V / 6 : (V - NORM_VARIANTS) / 3), (V < NORM_VARIANTS && (V / 3) % 2 == 1), V % 3 == 1, V % 3 == 2,
+                               (V >= NORM_VARIANTS)>...}};
 }
 constexpr auto MODE1_KERNELS = mode1_kernels(std::make_integer_sequence<int, DABGPU_DEMOD_MODE1_VARIANTS>{});
-static_assert(DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3, "the planner's variants are (loader, bank, layout): the formula above instantiates nothing else");
+static_assert(DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS == 4 * 2 * 3 && DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3 + 4 * 3 && NORM_VARIANTS % 3 == 0,
+              "the planner's variants are (loader, bank, layout), then (loader, layout) weighted: the formula above instantiates nothing else");
 static_assert(SRC_C32 == 0 && SRC_U8 == 1 && SRC_S8 == 2 && SRC_S16 == 3, "the planner's loader numbers");
 
 hipError_t enqueue_demod_mode1(const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t, hipStream_t stream) {
@@ -565,7 +617,7 @@ hipError_t enqueue_demod_mode1(const dabgpu_demod_plan& p, const dabgpu_demod_ca
     hipLaunchKernelGGL(MODE1_KERNELS[p.variant], dim3(p.grid), dim3(p.threads), DEMOD_LDS_BYTES, stream, a.d_iq, a.d_freq, a.d_bits,
                        reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<f2*>(a.d_fft), reinterpret_cast<f2*>(a.d_dqpsk), reinterpret_cast<const f2*>(d_tw),
                        t.inv_map16, a.n_frames, p.symbols_per_block, p.chunks, a.bits_frame_stride ? a.bits_frame_stride : (size_t)NB_FRAME_BITS, a.d_desc,
-                       a.d_block, a.block_stride, pt, a.d_prev_block, fs);
+                       a.d_block, a.block_stride, pt, a.d_prev_block, fs, demod_soft{a.soft_level, a.d_soft_scale});
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && p.tail == DABGPU_DEMOD_TAIL_LAUNCH) {
         hipLaunchKernelGGL(ofdm_phase_kernel, dim3((unsigned)a.n_frames), dim3(64), 0, stream, reinterpret_cast<const f2*>(a.d_cp_corr), a.n_frames, a.beta,
@@ -582,6 +634,7 @@ int dabgpu_launch_demod(dabgpu_ctx* c, int mode, const dabgpu_demod_call& a, hip
     f.src = a.src; f.desc = a.d_desc != nullptr; f.fft = a.d_fft != nullptr; f.dqpsk = a.d_dqpsk != nullptr; f.sync = a.d_sync != nullptr;
     f.frame_stride = a.frame_stride_samples != 0; f.total_phase = a.d_total_phase != nullptr; f.fine_freq = a.d_fine_freq != nullptr;
     f.classed = a.classed != 0; f.symbols_per_block = a.symbols_per_block; f.n_frames = a.n_frames; f.generic_mode1 = a.generic_mode1;
+    f.soft_policy = a.soft_policy; f.soft_level = a.soft_level;
     // development switches of modes II-IV (the tests cross-check the kernels of a mode with them)
     f.switch_generic = mode != 1 && getenv("DABGPU_MODE_GENERIC");
     f.switch_mode3_single = mode == 3 && getenv("DABGPU_MODE3_SINGLE");

@@ -59,6 +59,7 @@ struct dabgpu_receiver {
     unsigned char* h_rec = nullptr;          // laid out like d_rec
     hipEvent_t sync_done = nullptr; bool sync_pending = false; bool sync_coarse = false;
     std::atomic<int> decode_fic{0};          // (written by set_subchannels, read where the decode is submitted: possibly another thread)
+    std::atomic<uint64_t> soft{0x42800000u}; // dabgpu_receiver_set_soft: policy << 32 | bits of the level (64.0f), read where a frame is submitted
     // a BANKED receiver (receiver_bank.hip): the staging buffers above are its own, everything else is the bank's; submit_* post jobs
     dabgpu_rx_member* member = nullptr;
     int device = 0;
@@ -183,6 +184,22 @@ extern "C" int dabgpu_receiver_set_subchannels(dabgpu_receiver* rx, const dabgpu
     return DABGPU_OK;
 }
 
+extern "C" int dabgpu_receiver_set_soft(dabgpu_receiver* rx, const dabgpu_soft_cfg* cfg) {
+    if (!rx) { dabgpu_set_error("receiver_set_soft: null receiver"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_check_soft_cfg("receiver_set_soft", cfg);
+    if (st) return st;
+    if (cfg->policy == DABGPU_SOFT_NORMALISED) {
+        if (!rx->member) rx->soft.store(0x42800000u);
+        return DABGPU_OK;
+    }
+    if (rx->member) { dabgpu_set_error("receiver_set_soft: a banked receiver demodulates with the bank's kernel, which has the normalised soft bits only"); return DABGPU_ERR_UNSUPPORTED; }
+    if (rx->mode != 1) { dabgpu_set_error("receiver_set_soft: the weighted soft bits exist for transmission mode I only"); return DABGPU_ERR_UNSUPPORTED; }
+    uint32_t lb;
+    memcpy(&lb, &cfg->level, sizeof(float));
+    rx->soft.store(((uint64_t)(uint32_t)cfg->policy << 32) | lb);
+    return DABGPU_OK;
+}
+
 extern "C" int dabgpu_receiver_stage(dabgpu_receiver* rx, float** h_stage, size_t* capacity_samples) {
     if (!rx || !h_stage) { dabgpu_set_error("receiver_stage: null argument"); return DABGPU_ERR_INVALID_ARG; }
     *h_stage = rx->h_stage[rx->cur];
@@ -290,7 +307,14 @@ static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float
     rx_net_freq_kernel<<<1, 64, 0, a>>>(rx->d_state, rx->d_small);
     DABGPU_CK(hipGetLastError());
     float* d_fine = &rx->d_state->freq_fine;
-    st = (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a)
+    const uint64_t soft_word = rx->soft.load();
+    dabgpu_soft_cfg soft;
+    soft.policy = (int)(soft_word >> 32);
+    { const uint32_t lb = (uint32_t)soft_word; memcpy(&soft.level, &lb, sizeof(float)); }
+    st = (rx->mode == 1 && soft.policy != DABGPU_SOFT_NORMALISED)
+             ? dabgpu_ofdm_demod_frames_soft(c, rx->d_iq, DABGPU_IQ_RAW_F32L, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr,
+                                             want_dq ? rx->d_dq : nullptr, 0, 0, DABGPU_BITS_NATURAL, &soft, nullptr, a)
+         : (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a)
                          : dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, 0, a);
     if (st || (st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
     // the decode may start; what the host reads of this frame -- soft bits, h_aux (the head of the device record: the frequency state after this frame's update, the sum of

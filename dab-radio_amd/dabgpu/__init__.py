@@ -92,7 +92,10 @@ ABI_SYMBOLS = [
     "dabgpu_tii_bank_create", "dabgpu_tii_bank_destroy", "dabgpu_tii_bank_reset", "dabgpu_tii_bank_process", "dabgpu_tii_bank_process_host_sync",
     "dabgpu_tii_bank_read",
     "dabgpu_ber_plan", "dabgpu_ber_frames_layout", "dabgpu_ber_ring_layout", "dabgpu_ber_fib_group_host_sync", "dabgpu_ber_codeword_host_sync",
+    "dabgpu_soft_cfg_default", "dabgpu_soft_scale_host", "dabgpu_ofdm_demod_frames_soft", "dabgpu_ofdm_sync_demod_frames_soft",
+    "dabgpu_receiver_set_soft",
 ]
+SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 
 # channel model (include/dabgpu.h)
 CHANNEL_MAX_TAPS = 8
@@ -250,6 +253,14 @@ class SyncCfg(C.Structure):
                 ("impulse_peak_threshold_db", C.c_float), ("impulse_peak_distance_probability", C.c_float)]
 
 
+class SoftCfg(C.Structure):
+    """dabgpu_soft_cfg: the soft-decision policy of the mode I demodulator (SOFT_NORMALISED / SOFT_CSI) and the level of SOFT_CSI"""
+    _fields_ = [("policy", C.c_int), ("level", C.c_float)]
+
+    def __init__(self, policy=SOFT_NORMALISED, level=64.0):
+        super().__init__(int(policy), float(level))
+
+
 class SyncState(C.Structure):
     """dabgpu_sync_state"""
     _fields_ = [("freq_coarse", C.c_float), ("freq_fine", C.c_float), ("is_found_coarse", C.c_int),
@@ -348,6 +359,16 @@ def lib():
         L.dabgpu_ofdm_tuned_symbols_per_block.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int]
         L.dabgpu_ofdm_sync_demod_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        L.dabgpu_soft_cfg_default.argtypes = [C.c_void_p]
+        L.dabgpu_soft_cfg_default.restype = None
+        L.dabgpu_soft_scale_host.argtypes = [C.c_void_p, C.c_float]
+        L.dabgpu_soft_scale_host.restype = C.c_float
+        L.dabgpu_ofdm_demod_frames_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_ofdm_sync_demod_frames_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]
+        L.dabgpu_receiver_set_soft.argtypes = [C.c_void_p, C.c_void_p]
         L.dabgpu_viterbi_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         L.dabgpu_fic_decode_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]
@@ -724,6 +745,24 @@ class Context:
         check(lib().dabgpu_ofdm_sync_demod_frames(self._h, _ptr(iq), n_streams, stream_stride_samples, prs_offset_samples, C.byref(cfg),
                                                   _ptr(states), _ptr(bits), _ptr(cp_corr), symbols_per_block, bits_frame_stride,
                                                   int(bits_layout), _ptr(total_phase), self._stream(stream)), "dabgpu_ofdm_sync_demod_frames")
+
+    def ofdm_demod_frames_soft(self, raw, fmt, n_frames, bits, soft, freq_offset=None, cp_corr=None, fft=None, dqpsk=None, symbols_per_block=0,
+                               bits_frame_stride=0, bits_layout=BITS_NATURAL, soft_scale=None, stream=None):
+        """ofdm_demod_frames_raw / _history with a soft-decision policy (`soft` = a SoftCfg); soft_scale [n_frames] float32 on the
+        device receives the scale of every frame under SOFT_CSI"""
+        check(lib().dabgpu_ofdm_demod_frames_soft(self._h, _ptr(raw), int(fmt), n_frames, _ptr(freq_offset), _ptr(bits), _ptr(cp_corr), _ptr(fft),
+                                                  _ptr(dqpsk), symbols_per_block, bits_frame_stride, int(bits_layout), C.byref(soft),
+                                                  _ptr(soft_scale), self._stream(stream)), "dabgpu_ofdm_demod_frames_soft")
+
+    def ofdm_sync_demod_frames_soft(self, iq, n_streams, stream_stride_samples, prs_offset_samples, states, bits, soft, cfg=None, cp_corr=None,
+                                    symbols_per_block=0, bits_frame_stride=0, bits_layout=BITS_NATURAL, total_phase=None, soft_scale=None,
+                                    stream=None):
+        """ofdm_sync_demod_frames with a soft-decision policy (`soft` = a SoftCfg)"""
+        cfg = cfg or sync_cfg_default()
+        check(lib().dabgpu_ofdm_sync_demod_frames_soft(self._h, _ptr(iq), n_streams, stream_stride_samples, prs_offset_samples, C.byref(cfg),
+                                                       _ptr(states), _ptr(bits), _ptr(cp_corr), symbols_per_block, bits_frame_stride,
+                                                       int(bits_layout), _ptr(total_phase), C.byref(soft), _ptr(soft_scale),
+                                                       self._stream(stream)), "dabgpu_ofdm_sync_demod_frames_soft")
 
     def ofdm_tune(self, raw, fmt, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, with_phase_tail=False, stream=None):
         """explicit (blocking) calibration of symbols_per_block = 0 for this call shape; returns the run length recorded"""
@@ -1746,6 +1785,21 @@ def sync_cfg_default():
     c = SyncCfg()
     lib().dabgpu_sync_cfg_default(C.byref(c))
     return c
+
+
+def soft_cfg_default():
+    c = SoftCfg()
+    lib().dabgpu_soft_cfg_default(C.byref(c))
+    return c
+
+
+def soft_scale(prs_useful, level=64.0):
+    """the scale k of SOFT_CSI from the 2048 useful samples of a frame's phase reference symbol (dabgpu_soft_scale_host)"""
+    import numpy as np
+    x = np.ascontiguousarray(prs_useful, dtype=np.complex64).reshape(-1)
+    if x.size != NB_FFT:
+        raise ValueError("soft_scale: 2048 complex samples")
+    return float(lib().dabgpu_soft_scale_host(_ptr(x), float(level)))
 
 
 def subchannel_plan(sc):

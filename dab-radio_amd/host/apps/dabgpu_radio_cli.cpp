@@ -25,6 +25,10 @@
 // de-interleaver fills).  The decoder classes stay as they are: the stage decodes each FIB group once more for its 96 bytes with the received
 // CRCs, keeps the last 16 CIFs of every sub-channel on the host, de-interleaves by index and hands both to DAB_Channel_BER.
 //
+// --soft-bits normalised|csi [--soft-level L] (not in the reference; include/dabgpu.h "Soft-decision policy"): csi hands the decoders
+// channel-state weighted soft bits (OFDM_Demod::SetSoftDecision), level L in [1, 127], default 64; normalised, the default, is the
+// reference's.  Transmission mode I and the OFDM stage only.
+//
 // --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
@@ -80,6 +84,9 @@ struct Args {
     bool channelise = false;
     double channel_offset_hz = 0.0;
     bool ber = false;
+    int soft_policy = DABGPU_SOFT_NORMALISED;
+    float soft_level = 64.0f;
+    bool soft_level_given = false;
 };
 
 static void usage(const char* argv0) {
@@ -90,6 +97,7 @@ static void usage(const char* argv0) {
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
+        "  [--soft-bits normalised|csi] [--soft-level 1..127]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -153,12 +161,22 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--tii") args.tii = true;
         else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
         else if (a == "--ber") args.ber = true;
+        else if (a == "--soft-bits") {
+            const std::string p = value();
+            if (p == "normalised") args.soft_policy = DABGPU_SOFT_NORMALISED;
+            else if (p == "csi") args.soft_policy = DABGPU_SOFT_CSI;
+            else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised or csi)");
+        }
+        else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
         else if (a == "--input-rate") args.input_rate = std::stod(value());
         else if (a == "--channel-offset-hz") { args.channel_offset_hz = std::stod(value()); args.channelise = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
     if (args.ber && !args.is_dab_used) throw std::runtime_error("--ber needs the channel decode stage");
+    if (args.soft_policy != DABGPU_SOFT_NORMALISED && !args.is_ofdm_used) throw std::runtime_error("--soft-bits needs the OFDM stage");
+    if (args.soft_level_given && args.soft_policy != DABGPU_SOFT_CSI) throw std::runtime_error("--soft-level needs --soft-bits csi");
+    if (!(args.soft_level >= 1.0f && args.soft_level <= 127.0f)) throw std::runtime_error("--soft-level: a level from 1 to 127");
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
@@ -313,6 +331,7 @@ static int run(const Args& args) {
         }
         auto demod = Create_OFDM_Demodulator(args.transmission_mode);
         demod->GetConfig().sync.is_coarse_freq_correction = !args.ofdm_disable_coarse_freq;
+        if (args.soft_policy != DABGPU_SOFT_NORMALISED) demod->SetSoftDecision(args.soft_policy, args.soft_level);
         std::vector<uint8_t> hard;
         std::unique_ptr<TII_Decoder> tii;
         if (args.tii) tii = std::make_unique<TII_Decoder>(args.transmission_mode);

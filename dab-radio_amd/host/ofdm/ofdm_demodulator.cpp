@@ -17,7 +17,16 @@
 #include "dab/dabgpu_frame_batcher.h"
 #include "dab/dabgpu_shared_context.h"
 
+// The ABI grows without a new version number: the entry point of the soft-decision policy is bound weakly, so that these classes still load
+// against a library of the same ABI version that predates it; asking for the policy there is an error.
+extern "C" int dabgpu_receiver_set_soft(dabgpu_receiver* rx, const dabgpu_soft_cfg* cfg) __attribute__((weak));
+
 namespace {
+int set_soft(dabgpu_receiver* rx, int policy, float level) {
+    if (!dabgpu_receiver_set_soft) throw std::runtime_error("OFDM_Demod: this libdabgpu.so has no soft-decision policies (dabgpu_receiver_set_soft)");
+    const dabgpu_soft_cfg cfg = {policy, level};
+    return dabgpu_receiver_set_soft(rx, &cfg);
+}
 double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 [[noreturn]] void fail(const char* what, int st) {
     throw std::runtime_error(std::string("OFDM_Demod: ") + what + ": " + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
@@ -124,6 +133,37 @@ OFDM_Demod::~OFDM_Demod() {
                              "delivery { wait for the frame %.1f, batcher %.1f, observers %.1f }\n", m_total_frames_read.load(), m_t_sync_wait / n,
                      m_t_slot_wait / n, m_t_submit / n, m_t_frame_wait / n, m_t_batcher / n, m_t_observers / n);
     }
+}
+
+void OFDM_Demod::SetSoftDecision(int policy, float level) {
+    if (m_banked && policy != DABGPU_SOFT_NORMALISED) {
+        // The bank's kernel has the normalised soft bits only: with the policy on, the receiver keeps a pipeline of its own.  A member that has
+        // not seen a sample yet leaves the bank for one (a member is always on the library's own tables); later the change has no clean place.
+        const bool untouched = m_total_frames_read.load() == 0 && m_stage_length == 0 && m_ring_length == 0 && m_corr_length == 0 && !m_sync_pending &&
+                               m_state == FINDING_NULL_POWER_DIP;
+        if (!untouched)
+            throw std::runtime_error("OFDM_Demod::SetSoftDecision: this receiver is a member of the receiver bank, whose kernel has the normalised soft bits "
+                                     "only; choose the policy before the first Process() call and the receiver leaves the bank");
+        const char* dev = std::getenv("DABGPU_DEVICE");
+        dabgpu_receiver* own = nullptr;
+        int st = dabgpu_receiver_create(&own, dev ? std::atoi(dev) : 0, 1, nullptr, nullptr);
+        if (st != DABGPU_OK) fail("dabgpu_receiver_create", st);
+        float* stage = nullptr;
+        size_t capacity = 0;
+        try {
+            if ((st = set_soft(own, policy, level)) != DABGPU_OK) fail("dabgpu_receiver_set_soft", st);
+            if ((st = dabgpu_receiver_stage(own, &stage, &capacity)) != DABGPU_OK) fail("dabgpu_receiver_stage", st);
+        } catch (...) { dabgpu_receiver_destroy(own); throw; }
+        dabgpu_receiver_destroy(m_rx);
+        m_rx = own;
+        m_banked = false;
+        m_stage = reinterpret_cast<std::complex<float>*>(stage);
+        m_stage_capacity = capacity;
+        m_subs_version = ~0ull;              // (the new receiver has not been given the batcher's subscription)
+        return;
+    }
+    const int st = set_soft(m_rx, policy, level);
+    if (st != DABGPU_OK) fail("dabgpu_receiver_set_soft", st);
 }
 
 void OFDM_Demod::RethrowDeliveryError() {

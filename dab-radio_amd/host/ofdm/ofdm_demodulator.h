@@ -110,6 +110,13 @@ public:
     tcb::span<const std::complex<float>> GetCorrelationTimeBuffer() const { return m_corr; }
     auto& On_OFDM_Frame() { return m_on_frame; }
     void EnableDebugBuffers(bool enable) { m_fetch_debug.store(enable, std::memory_order_relaxed); }
+    // The soft-decision policy of the frames submitted from now on (not in the reference; OFDM_Demod_Config stays the reference's):
+    // DABGPU_SOFT_NORMALISED, the reference's soft bits and the default, or DABGPU_SOFT_CSI, channel-state weighted with `level` in [1, 127]
+    // (include/dabgpu.h).  Transmission mode I, and a receiver with a pipeline of its own: the receiver bank's kernel has the normalised soft
+    // bits only, so a member of the bank that is given DABGPU_SOFT_CSI before its first Process() call leaves the bank for a pipeline of its own
+    // and stays private; after the first Process() call the call throws on a member.  Call it from the thread that calls Process().
+    void SetSoftDecision(int policy, float level = 64.0f);
+    bool IsBankMember() const { return m_banked; }
 
 private:
     size_t FindNullPowerDip(tcb::span<const std::complex<float>> buf);

@@ -267,6 +267,44 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx *ctx, const float *d_iq, size_t n_s
                                   float *d_total_phase, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Soft-decision policy of the mode I demodulator.
+ *   DABGPU_SOFT_NORMALISED  the reference's (CalculateViterbiBits, ofdm_demodulator.cpp:867-889): every DQPSK product d is divided by
+ *                           max(|re d|, |im d|), so every carrier reaches the decoder with the same weight.  The default; the entry
+ *                           points without a dabgpu_soft_cfg compute exactly this.
+ *   DABGPU_SOFT_CSI         channel-state weighted: the amplitude of d = X_i conj(X_i+1) -- small for a carrier in a fade -- stays in
+ *                           the soft bit.  One factor per frame, k = level * 1536 / (2048 P), P = sum of re^2 + im^2 over the 2048
+ *                           useful samples of the frame's phase reference symbol (samples 504 .. 2551 of the frame as the loader
+ *                           delivers them, before the PLL), puts a component of mean size at +-level; soft bit = -(c k), c = re d
+ *                           and -im d, NaN -> 0, clamped to [-127, 127], truncated towards zero.  P zero or not finite, or k not
+ *                           finite: k = 0, every soft bit of the frame is 0 (an erasure).  Frequency de-interleave and both layouts
+ *                           as ever.  Arithmetic: csrc/softbit_csi_core.h, the device equals dabgpu_soft_scale_host bit for bit.
+ * level: [1, 127], default 64; anything else is DABGPU_ERR_INVALID_ARG.  Mode I only, no stream bank, no banked receiver.
+ */
+#define DABGPU_SOFT_NORMALISED 0
+#define DABGPU_SOFT_CSI 1
+typedef struct { int policy; float level; } dabgpu_soft_cfg;
+void dabgpu_soft_cfg_default(dabgpu_soft_cfg *cfg);
+/* k of a frame from the 2048 useful samples (complex float) of its phase reference symbol; 0 for a level outside [1, 127] */
+float dabgpu_soft_scale_host(const float *h_prs_useful, float level);
+/*
+ * dabgpu_ofdm_demod_frames_raw (display views, natural layout) / dabgpu_ofdm_demod_frames_history (either layout, no views) with a
+ * soft-decision policy; formats with a fused loader only.  cfg->policy = DABGPU_SOFT_NORMALISED: those calls, byte for byte, and
+ * d_soft_scale is not written.  d_soft_scale [n_frames] (may be NULL): k as used.  symbols_per_block = 0 resolves as for the
+ * normalised call of the same loader and layout; the result does not depend on it.
+ */
+int dabgpu_ofdm_demod_frames_soft(dabgpu_ctx *ctx, const void *d_raw, int format, size_t n_frames, const float *d_freq_offset,
+                                  int8_t *d_bits, float *d_cp_corr, float *d_fft, float *d_dqpsk, int symbols_per_block,
+                                  size_t bits_frame_stride, int bits_layout, const dabgpu_soft_cfg *cfg, float *d_soft_scale,
+                                  void *stream);
+/* dabgpu_ofdm_sync_demod_frames with a soft-decision policy: the frame position comes from the sync record, and with it the window of
+ * P.  A receiver with sync_valid = 0 leaves its d_soft_scale word untouched too. */
+int dabgpu_ofdm_sync_demod_frames_soft(dabgpu_ctx *ctx, const float *d_iq, size_t n_streams, size_t stream_stride_samples,
+                                       size_t prs_offset_samples, const dabgpu_sync_cfg *cfg, dabgpu_sync_state *d_states,
+                                       int8_t *d_bits, float *d_cp_corr, int symbols_per_block, size_t bits_frame_stride,
+                                       int bits_layout, float *d_total_phase, const dabgpu_soft_cfg *soft, float *d_soft_scale,
+                                       void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Channel decoding: punctured K=7 rate-1/4 Viterbi (+ time de-interleave, energy dispersal, FIB CRC16),
  * one wavefront per codeword, batched.
  * Replaces DAB_Viterbi_Decoder::update/chainback (src/dab/algorithms/dab_viterbi_decoder.cpp:114-181) and the
@@ -563,6 +601,9 @@ void dabgpu_receiver_destroy(dabgpu_receiver *rx);
 dabgpu_frame_session *dabgpu_receiver_session(dabgpu_receiver *rx);      /* owned by the receiver */
 /* what is decoded for the frames submitted from now on (mode I; n <= 64) */
 int dabgpu_receiver_set_subchannels(dabgpu_receiver *rx, const dabgpu_subchannel *h_subchannels, int n, int decode_fic);
+/* the soft-decision policy of the frames submitted from now on (dabgpu_soft_cfg; the default is DABGPU_SOFT_NORMALISED).  DABGPU_SOFT_CSI:
+ * a private mode I receiver only -- a banked receiver and modes II-IV answer DABGPU_ERR_UNSUPPORTED and keep the normalised soft bits */
+int dabgpu_receiver_set_soft(dabgpu_receiver *rx, const dabgpu_soft_cfg *cfg);
 int dabgpu_receiver_stage(dabgpu_receiver *rx, float **h_stage, size_t *capacity_samples);
 int dabgpu_receiver_reset(dabgpu_receiver *rx);
 /* PRS slot = nb_fft samples from sample prs_sample of the current staging buffer (m_correlation_time_buffer[nb_null_period ...]); asynchronous */

@@ -19,6 +19,9 @@ With --ber every table gains two columns: the channel BER the receiver MEASURES 
 FIB groups of every frame and the sub-channel code words from CIF 15 on) and the TRUE channel BER of the same soft bits against the transmitted
 bits (a second TxBank keeps the frame bits).  The two agree while the decoders deliver; below the waterfall the measured figure falls short of
 the true one, because a wrongly decoded code word is re-encoded into a neighbour of what was received.  Without the flag the output is unchanged.
+With --soft-bits csi [--soft-level L] every receiver runs twice on the same received samples, with the reference's soft bits and with the
+channel-state weighted ones (dabgpu_ofdm_sync_demod_frames_soft), and every cell reads `normalised -> csi`; the output goes to
+profiles/tx/waterfall_csi.md (waterfall.md is not rewritten), a run with --doppler-hz being APPENDED to it.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
                               [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber]"""
 import argparse
@@ -48,7 +51,14 @@ def main():
     ap.add_argument("--adjacent-db", default=None)
     ap.add_argument("--adjacent-sides", type=int, default=2, choices=(1, 2))
     ap.add_argument("--ber", action="store_true")
+    ap.add_argument("--soft-bits", default="normalised", choices=("normalised", "csi"))
+    ap.add_argument("--soft-level", type=float, default=64.0)
     a = ap.parse_args()
+    csi = a.soft_bits == "csi"
+    if csi and (a.clock_ppm is not None or a.adjacent_db is not None):
+        ap.error("--soft-bits csi is not available with --clock-ppm or --adjacent-db")
+    if csi and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_csi.md")           # (waterfall.md is never rewritten by such a run)
     if a.adjacent_db is not None and (a.doppler_hz is not None or a.clock_ppm is not None):
         ap.error("--adjacent-db is not available with --doppler-hz or --clock-ppm")
     adjacent_db = [float(v) for v in a.adjacent_db.split(",")] if a.adjacent_db is not None else []
@@ -60,6 +70,7 @@ def main():
     import numpy as np
     import torch
     import dabgpu
+    policies = [dabgpu.SOFT_NORMALISED, dabgpu.SOFT_CSI] if csi else [dabgpu.SOFT_NORMALISED]
     lo, hi, step = (float(v) for v in a.snr.split(":"))
     snrs = [lo + i * step for i in range(int(round((hi - lo) / step)) + 1)]
     E, F, H = a.streams, a.frames, 8
@@ -119,8 +130,16 @@ def main():
             f"FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on "
             f"(per point: {', '.join(f'{name} {E * (4 * F - 15) * sum(spans[i][1] for i in range(len(subs)) if owner[i] == li)}' for li, (name, _) in enumerate(LEVELS))} bytes).  "
             "No carrier or timing offset.  `python tools/waterfall.py`.", ""]
+    if csi:
+        fading_args = "" if a.doppler_hz is None else f" --profile {a.profile or 'tu6'} --doppler-hz {a.doppler_hz:g}"
+        text = [f"# Receiver sensitivity of the two soft-decision policies{' (fading channel, appended)' if a.doppler_hz is not None else ''}", "",
+                f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall.md` with the receiver call switched: every cell is "
+                f"`normalised -> csi` (dabgpu_ofdm_sync_demod_frames -> dabgpu_ofdm_sync_demod_frames_soft, DABGPU_SOFT_CSI, level {a.soft_level:g}) on the SAME received samples.  "
+                f"{E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
+                f"`python tools/waterfall.py --soft-bits csi{fading_args}`; "
+                "the verdict line is the csi policy's.", ""]
     verdicts = []
-    profiles, fading = [(n, t, None, None) for n, t in PROFILES], None
+    profiles, fading =[(n, t, None, None) for n, t in PROFILES], None
     if adjacent_db:
         text = [f"# Adjacent blocks (appended by `python tools/waterfall.py --adjacent-db {a.adjacent_db} --adjacent-sides {a.adjacent_sides}`)", "",
                 f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The white-noise channel of the first table followed by the combiner and the "
@@ -149,7 +168,7 @@ def main():
             comb, spl = dabgpu.Channeliser(ctx, both, E, ADJ_D), dabgpu.Channeliser(ctx, wanted, E, ADJ_D)
         rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
-        rows, chan = [], []
+        rows, rows_ref, chan = [], [], []
         ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
@@ -166,51 +185,66 @@ def main():
                 rs.seek(0)
                 rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
                 d_use = d_rs
-            d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
-            hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
-            d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
-            msc = torch.zeros((E, 4, nb), dtype=torch.uint8, device="cuda"); mres = torch.zeros((E * 4 * len(subs), 16), dtype=torch.uint8, device="cuda")
-            crc_ok, crc_n = 0, 0
-            if a.ber:
-                fic_ber = torch.zeros((E, 4, 16), dtype=torch.uint8, device="cuda"); msc_ber = torch.zeros((E, 4, len(subs), 16), dtype=torch.uint8, device="cuda")
-                m_err = m_bits = t_err = t_bits = 0
-            err = [0] * len(LEVELS); tot = [0] * len(LEVELS)
-            for j in range(F):
-                a0 = NULL + j * S - P_LEAD
-                sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
-                seg = d_use[:, a0:a0 + STRIDE]
-                sl[:, :seg.shape[1]] = seg
-                ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
-                ctx.decode_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
+            for pol in policies:
+                d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
+                hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
+                d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
+                msc = torch.zeros((E, 4, nb), dtype=torch.uint8, device="cuda"); mres = torch.zeros((E * 4 * len(subs), 16), dtype=torch.uint8, device="cuda")
+                crc_ok, crc_n = 0, 0
                 if a.ber:
-                    ctx.ber_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, msc, 4 * nb, fic_ber, msc_ber)
+                    fic_ber = torch.zeros((E, 4, 16), dtype=torch.uint8, device="cuda"); msc_ber = torch.zeros((E, 4, len(subs), 16), dtype=torch.uint8, device="cuda")
+                    m_err = m_bits = t_err = t_bits = 0
+                err = [0] * len(LEVELS); tot = [0] * len(LEVELS)
+                for j in range(F):
+                    a0 = NULL + j * S - P_LEAD
+                    sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
+                    seg = d_use[:, a0:a0 + STRIDE]
+                    sl[:, :seg.shape[1]] = seg
+                    if pol == dabgpu.SOFT_NORMALISED:
+                        ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                    else:
+                        ctx.ofdm_sync_demod_frames_soft(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], dabgpu.SoftCfg(pol, a.soft_level),
+                                                        bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                    ctx.decode_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
+                    if a.ber:
+                        ctx.ber_frames(hist, E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, msc, 4 * nb, fic_ber, msc_ber)
+                        torch.cuda.synchronize()
+                        recs = [fic_ber.cpu().numpy().view(bdt).reshape(E, 4)] + [msc_ber.cpu().numpy().view(bdt).reshape(E, 4, len(subs))[:, c]
+                                                                                  for c in range(4) if 4 * j + c >= 15]
+                        m_err += sum(int(r["n_errors"].sum()) for r in recs); m_bits += sum(int(r["n_bits"].sum()) for r in recs)
+                        fr, pos = consumed[j]
+                        soft = hist[:, fr % H, pos]
+                        t_err += int(((soft != 0) & ((soft >= 0) != sent[fr, pos][None, :])).sum()); t_bits += int((soft != 0).sum())
                     torch.cuda.synchronize()
-                    recs = [fic_ber.cpu().numpy().view(bdt).reshape(E, 4)] + [msc_ber.cpu().numpy().view(bdt).reshape(E, 4, len(subs))[:, c]
-                                                                              for c in range(4) if 4 * j + c >= 15]
-                    m_err += sum(int(r["n_errors"].sum()) for r in recs); m_bits += sum(int(r["n_bits"].sum()) for r in recs)
-                    fr, pos = consumed[j]
-                    soft = hist[:, fr % H, pos]
-                    t_err += int(((soft != 0) & ((soft >= 0) != sent[fr, pos][None, :])).sum()); t_bits += int((soft != 0).sum())
-                torch.cuda.synchronize()
-                masks = fres.cpu().numpy().view(rdt)["crc_ok_mask"].reshape(-1)
-                crc_ok += int(sum(bin(int(m) & 7).count("1") for m in masks)); crc_n += 3 * masks.size
-                for c in range(4):
-                    if 4 * j + c < 15:
-                        continue
-                    bad = (msc[:, c] != cifs[4 * j + c - 15][None, :])
-                    for i, (off, n) in enumerate(spans):
-                        err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
-            rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
-            if a.ber:
-                assert m_bits == t_bits
-                chan.append((m_err / m_bits, t_err / t_bits))
+                    masks = fres.cpu().numpy().view(rdt)["crc_ok_mask"].reshape(-1)
+                    crc_ok += int(sum(bin(int(m) & 7).count("1") for m in masks)); crc_n += 3 * masks.size
+                    for c in range(4):
+                        if 4 * j + c < 15:
+                            continue
+                        bad = (msc[:, c] != cifs[4 * j + c - 15][None, :])
+                        for i, (off, n) in enumerate(spans):
+                            err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
+                if pol == policies[-1]:
+                    rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
+                    if a.ber:
+                        assert m_bits == t_bits
+                        chan.append((m_err / m_bits, t_err / t_bits))
+                else:
+                    rows_ref.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
         ch.close()
         if rs is not None:
             rs.close()
         if comb is not None:
             comb.close(); spl.close()
-        text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
-        text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
+        if csi:
+            # both policies side by side: normalised -> csi in every cell
+            text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
+            fmt = lambda r: f"{r:.2e}" if r else "0"
+            text += [f"| {snr:g} | {ok0:.4f} -> {ok:.4f} | " + " | ".join(f"{fmt(r0)} -> {fmt(r)}" for r0, r in zip(ber0, ber)) + " |"
+                     for (snr, ok0, ber0, _), (_, ok, ber, _) in zip(rows_ref, rows)]
+        else:
+            text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
+            text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
         if a.ber:
             n0 = len(text) - len(rows) - 2
             text[n0] += " channel BER measured | channel BER true |"; text[n0 + 1] += "---|---|"
@@ -233,7 +267,8 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    open(a.out, "a" if clock_ppm or adjacent_db else "w").write(("\n" if clock_ppm or adjacent_db else "") + text)
+    append = bool(clock_ppm or adjacent_db or (csi and a.doppler_hz is not None))       # (the csi record: white noise and two paths first, the fading run behind them)
+    open(a.out, "a" if append else "w").write(("\n" if append else "") + text)
     return 0 if all(verdicts) else 1
 
 
