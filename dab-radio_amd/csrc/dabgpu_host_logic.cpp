@@ -197,12 +197,18 @@ dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f) 
         p.family = DABGPU_DEMOD_MODE1;
         p.variant = (f.src * 2 + (f.desc ? 1 : 0)) * 3 + (f.classed ? 2 : views ? 1 : 0);
     }
+    // bank_soft is the stream bank's explicit statement that its round runs the weighted policy: it means nothing without descriptors or
+    // under the normalised policy, and a caller that hands descriptors without it is refused as before
+    if (f.bank_soft && !f.desc) { dabgpu_set_error("ofdm_demod: bank_soft is a bank round's fact: it needs frame descriptors"); return p; }
+    if (f.bank_soft && f.soft_policy == DABGPU_SOFT_NORMALISED) { dabgpu_set_error("ofdm_demod: bank_soft asks for DABGPU_SOFT_CSI, the policy is the normalised one"); return p; }
     if (f.soft_policy != DABGPU_SOFT_NORMALISED) {
         if (f.soft_policy != DABGPU_SOFT_CSI) { dabgpu_set_error("ofdm_demod: no soft-decision policy %d", f.soft_policy); return p; }
         if (!mode1) { dabgpu_set_error("ofdm_demod: the weighted soft bits exist for the transmission mode I kernel only (mode %d)", mode); return p; }
-        if (f.desc) { dabgpu_set_error("ofdm_demod: the weighted soft bits have no stream-bank loader (frame descriptors)"); return p; }
+        if (f.desc && !f.bank_soft) { dabgpu_set_error("ofdm_demod: the weighted soft bits have no stream-bank loader (frame descriptors)"); return p; }
+        if (f.bank_soft && views) { dabgpu_set_error("ofdm_demod: a bank round has no display views under the weighted policy"); return p; }
         if (!dabgpu::sb_level_ok(f.soft_level)) { dabgpu_set_error("ofdm_demod: soft level %g outside [1, 127]", (double)f.soft_level); return p; }
-        p.variant = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + f.src * 3 + (f.classed ? 2 : views ? 1 : 0);
+        p.variant = f.bank_soft ? DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST + f.src * 2 + (f.classed ? 1 : 0)
+                                : DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + f.src * 3 + (f.classed ? 2 : views ? 1 : 0);
     }
     if (!mode1) {
         // modes II-IV run register-resident unless the FFT view, which only the size-generic kernel writes, is wanted

@@ -180,6 +180,7 @@ struct dabgpu_demod_call {
     int soft_policy = DABGPU_SOFT_NORMALISED;
     float soft_level = 64.0f;
     float* d_soft_scale = nullptr;
+    bool bank_soft = false;                     // a bank round under DABGPU_SOFT_CSI: d_soft_scale is indexed by the descriptors' bits slot (bank_process_impl only)
 };
 // plans the call (dabgpu_host_plan_demod) and launches the demodulation kernel of the mode's family, then the phase kernel if the plan asks for it;
 // what = how a HIP failure of the mode I launch is reported (the entry points' own wording)

@@ -155,7 +155,9 @@ constexpr size_t DEMOD_LDS_BYTES = (4 * WAVE_PATCH) * sizeof(f2) + NB_SYM_BITS +
 // one factor per frame, k = level * 1536 / (2048 P), P = the power of the 2048 useful samples of the frame's symbol 0 as the loader
 // delivers them.  Every workgroup forms P once, before its first symbol, by the header's tree: a run that starts at symbol 0 has the
 // samples in registers already, any other reads them in addition; the four wavefront sums meet in LDS at the barrier the set-up has
-// anyway.  The demapper is then one multiplication per component: no quotient, no range test.
+// anyway.  The demapper is then one multiplication per component: no quotient, no range test.  A stream bank's frame (BANK) has its
+// symbol 0 in the frame buffer, in a block, or split between the two: the extra read goes through the loader's own source selection,
+// frame-buffer samples as stored, block samples through the reader arithmetic of SRC, and the scale is reported at the frame's bits slot.
 template <int SRC, bool BANK, bool VIEWS = true, bool CLASSED = false, bool CSI = false>
 __global__ __launch_bounds__(256, (VIEWS || (BANK && CLASSED)) ? 3 : 4)      // (the display views, and the stream-bank loader with the
                                                                             // second position set, need a few more registers: 3 workgroups per CU instead of spills)
@@ -166,7 +168,7 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
                        const dabgpu_frame_desc* __restrict__ desc, const void* __restrict__ tail, size_t tail_stride, demod_phase_tail pt,
                        const void* __restrict__ prev_tail, demod_frame_src fs, demod_soft soft)
 {
-    static_assert(!(CSI && BANK), "the weighted soft bits have no stream-bank loader");
+    static_assert(!(CSI && BANK && VIEWS), "a bank round has no display views under the weighted policy");
     f2* const fft_out = VIEWS ? fft_out_ : nullptr;
     f2* const dqpsk_out = VIEWS ? dqpsk_out_ : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -231,9 +233,8 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
     const __amdgpu_buffer_rsrc_t iq_rs = frame_rsrc(fbase, NB_FRAME_SAMPLES * SB);
     // coalesced loads of one symbol: 16 B per lane, 4 for the FFT body + 1 for the cyclic-prefix head (threads 0..3 have no head
     // sample: they load a valid address and never use it, so that the load stays unconditional inside the wave)
-    auto load_symbol = [&](int i, f4 (&v)[4], f4& h) __attribute__((always_inline)) {
-        const size_t sym = (size_t)i * NB_SYMBOL_PERIOD;
-        const bool dc = (i < NB_FRAME_SYMBOLS) && (i < out1 || i == NB_FRAME_SYMBOLS - 1);
+    // (dc = the cyclic-prefix head is wanted too; the weighted policy's extra read of symbol 0 passes a constant false: the body only)
+    auto load_symbol_at = [&](const size_t sym, const bool dc, f4 (&v)[4], f4& h) __attribute__((always_inline)) {
         if constexpr (BANK) {
             // A symbol lies in ONE of the frame's sources -- frame buffer, previous block, current block -- except the one or two that
             // hold a boundary: the choice is uniform, so the symbol is loaded through a buffer descriptor of that source like an aligned
@@ -253,15 +254,28 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
                 for (int k = 0; k < 4; k++) v[k] = load_pair_buf<SRC>(rs, lane_s, (unsigned)(sym + NB_CP + 512 * k) * SS);
                 if (dc) h = load_pair_buf<SRC>(rs, head_s, (unsigned)sym * SS);
             } else {
+                // (weighted bank kernels: the lane's sample numbers of this rare path are formed here every time -- hoisted out of the symbol
+                // loop as 64-bit byte offsets they cost the two VGPRs that the normalised twins of the quantised loaders spill)
+                if constexpr (CSI) {
+                    int tl = t;
+                    asm volatile("" : "+v"(tl));
 #pragma unroll
-                for (int k = 0; k < 4; k++) v[k] = load_pair_bank<SRC>(fbase, tbase, split, sym + NB_CP + 2 * t + 512 * k, pbase, cd, ce);
-                if (dc) h = load_pair_bank<SRC>(fbase, tbase, split, sym + 2 * ((t >= 4) ? t - 4 : 0), pbase, cd, ce);   // uniform per workgroup
+                    for (int k = 0; k < 4; k++) v[k] = load_pair_bank<SRC>(fbase, tbase, split, sym + NB_CP + 2 * tl + 512 * k, pbase, cd, ce);
+                    if (dc) h = load_pair_bank<SRC>(fbase, tbase, split, sym + 2 * ((tl >= 4) ? tl - 4 : 0), pbase, cd, ce);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) v[k] = load_pair_bank<SRC>(fbase, tbase, split, sym + NB_CP + 2 * t + 512 * k, pbase, cd, ce);
+                    if (dc) h = load_pair_bank<SRC>(fbase, tbase, split, sym + 2 * ((t >= 4) ? t - 4 : 0), pbase, cd, ce);   // uniform per workgroup
+                }
             }
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) v[k] = load_pair_buf<SRC>(iq_rs, lane_off, (unsigned)(sym + NB_CP + 512 * k) * SB);
             if (dc) h = load_pair_buf<SRC>(iq_rs, head_off, (unsigned)sym * SB);
         }
+    };
+    auto load_symbol = [&](int i, f4 (&v)[4], f4& h) __attribute__((always_inline)) {
+        load_symbol_at((size_t)i * NB_SYMBOL_PERIOD, (i < NB_FRAME_SYMBOLS) && (i < out1 || i == NB_FRAME_SYMBOLS - 1), v, h);
     };
     // the first symbol's samples are requested before anything else: the table reads and the barrier of the set-up below run while
     // they are on their way (they were issued behind them: two memory latencies in series at the start of every workgroup)
@@ -274,6 +288,11 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
         if (out0 == 0) {                                                 // (uniform)
 #pragma unroll
             for (int k = 0; k < 4; k++) q[k] = v[k];
+        } else if constexpr (BANK) {
+            // symbol 0 of a bank frame through the source selection of every other symbol: the frame buffer when the frame was found
+            // at or before its expected position, a boundary inside the useful part (per-lane selection) when it was found later
+            f4 no_head;
+            load_symbol_at(0, false, q, no_head);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) q[k] = load_pair_buf<SRC>(iq_rs, lane_off, (unsigned)(NB_CP + 512 * k) * SB);
@@ -319,7 +338,7 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
     if constexpr (CSI) {
         const float P = sb_power_join(sb_sums[0], sb_sums[1], sb_sums[2], sb_sums[3]);
         soft_k = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sb_scale(soft.level, P))));      // uniform: a scalar register
-        if (chunk == 0 && t == 0 && soft.scale != nullptr) soft.scale[frame] = soft_k;
+        if (chunk == 0 && t == 0 && soft.scale != nullptr) soft.scale[out_frame] = soft_k;      // (bank: the slot the bits go to)
     }
 
     // LDS addresses (float2 element indices); every per-k term below is an instruction immediate
@@ -596,17 +615,23 @@ void ofdm_phase_kernel(const f2* __restrict__ cp_corr, int n_frames, float beta,
 namespace {
 using namespace dabgpu;
 // variant -> kernel, the planner's numbering (dabgpu_host_logic.h): ((loader * 2 + bank) * 3 + layout), layout 1 = display views, 2 = class order;
-// behind those, the weighted soft bits: 24 + loader * 3 + layout (no stream-bank loader)
+// behind those, the weighted soft bits: 24 + loader * 3 + layout for aligned frames, then 36 + loader * 2 + (class order) for a bank round
+// (the bank launches soft bits and class order, never the display views)
 using demod_kernel_t = decltype(&ofdm_demod_kernel<SRC_C32, false>);
-constexpr int NORM_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS;
-template <int... V>
-constexpr std::array<demod_kernel_t, sizeof...(V)> mode1_kernels(std::integer_sequence<int, V...>) {
-    return {{ofdm_demod_kernel<(V < NORM_VARIANTS ? V / 6 : (V - NORM_VARIANTS) / 3), (V < NORM_VARIANTS && (V / 3) % 2 == 1), V % 3 == 1, V % 3 == 2,
-                               (V >= NORM_VARIANTS)>...}};
+constexpr int NORM_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS, BANK_SOFT_FIRST = DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST;
+template <int V>
+constexpr demod_kernel_t mode1_kernel() {
+    if constexpr (V < NORM_VARIANTS) return ofdm_demod_kernel<V / 6, (V / 3) % 2 == 1, V % 3 == 1, V % 3 == 2, false>;
+    else if constexpr (V < BANK_SOFT_FIRST) return ofdm_demod_kernel<(V - NORM_VARIANTS) / 3, false, V % 3 == 1, V % 3 == 2, true>;
+    else return ofdm_demod_kernel<(V - BANK_SOFT_FIRST) / 2, true, false, (V - BANK_SOFT_FIRST) % 2 == 1, true>;
 }
+template <int... V>
+constexpr std::array<demod_kernel_t, sizeof...(V)> mode1_kernels(std::integer_sequence<int, V...>) { return {{mode1_kernel<V>()...}}; }
 constexpr auto MODE1_KERNELS = mode1_kernels(std::make_integer_sequence<int, DABGPU_DEMOD_MODE1_VARIANTS>{});
-static_assert(DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS == 4 * 2 * 3 && DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3 + 4 * 3 && NORM_VARIANTS % 3 == 0,
-              "the planner's variants are (loader, bank, layout), then (loader, layout) weighted: the formula above instantiates nothing else");
+static_assert(DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS == 4 * 2 * 3 && DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST == 4 * 2 * 3 + 4 * 3 &&
+              DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3 + 4 * 3 + 4 * 2 && NORM_VARIANTS % 3 == 0 && BANK_SOFT_FIRST % 3 == 0,
+              "the planner's variants are (loader, bank, layout), then (loader, layout) weighted, then (loader, class order) weighted in a bank round: "
+              "the formulas above instantiate nothing else");
 static_assert(SRC_C32 == 0 && SRC_U8 == 1 && SRC_S8 == 2 && SRC_S16 == 3, "the planner's loader numbers");
 
 hipError_t enqueue_demod_mode1(const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t, hipStream_t stream) {
@@ -634,7 +659,7 @@ int dabgpu_launch_demod(dabgpu_ctx* c, int mode, const dabgpu_demod_call& a, hip
     f.src = a.src; f.desc = a.d_desc != nullptr; f.fft = a.d_fft != nullptr; f.dqpsk = a.d_dqpsk != nullptr; f.sync = a.d_sync != nullptr;
     f.frame_stride = a.frame_stride_samples != 0; f.total_phase = a.d_total_phase != nullptr; f.fine_freq = a.d_fine_freq != nullptr;
     f.classed = a.classed != 0; f.symbols_per_block = a.symbols_per_block; f.n_frames = a.n_frames; f.generic_mode1 = a.generic_mode1;
-    f.soft_policy = a.soft_policy; f.soft_level = a.soft_level;
+    f.soft_policy = a.soft_policy; f.soft_level = a.soft_level; f.bank_soft = a.bank_soft;
     // development switches of modes II-IV (the tests cross-check the kernels of a mode with them)
     f.switch_generic = mode != 1 && getenv("DABGPU_MODE_GENERIC");
     f.switch_mode3_single = mode == 3 && getenv("DABGPU_MODE3_SINGLE");

@@ -423,7 +423,19 @@ struct dabgpu_stream_bank {
     bool carry_pending = false;
     int carry_src = 0;                 // loader kind (SRC) and stream stride of that block
     size_t carry_stride = 0;
+    // soft-decision policy of the frames demodulated from the next process call on (dabgpu_stream_bank_set_soft); survives a reset
+    dabgpu_soft_cfg soft = {DABGPU_SOFT_NORMALISED, 64.0f};
+    float* d_soft_scale = nullptr;     // the caller's: scale of the frame in bits slot k at [k], soft_scale_cap floats
+    size_t soft_scale_cap = 0;
 };
+
+// DABGPU_SOFT_CSI with a scale buffer: every bits slot of the call has its word (checked before a call launches anything)
+static int bank_soft_scale_fits(const dabgpu_stream_bank* b, size_t slots_per_stream) {
+    if (b->soft.policy != DABGPU_SOFT_CSI || b->d_soft_scale == nullptr || slots_per_stream <= b->soft_scale_cap / b->n) return DABGPU_OK;
+    dabgpu_set_error("stream_bank_process: %zu streams x %zu bits slots need more scale words than the %zu dabgpu_stream_bank_set_soft was given", b->n,
+                     slots_per_stream, b->soft_scale_cap);
+    return DABGPU_ERR_INVALID_ARG;
+}
 
 extern "C" {
 
@@ -531,6 +543,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
         return DABGPU_ERR_INVALID_ARG;
     }
     if (((uintptr_t)d_iq & (src_sample_bytes<SRC>::value - 1)) || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("stream_bank_process: misaligned buffer"); return DABGPU_ERR_INVALID_ARG; }
+    if (int fits = bank_soft_scale_fits(b, max_frames_per_stream)) return fits;
     dabgpu_ctx* c = b->ctx;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
@@ -611,6 +624,9 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
             call.n_frames = cnt; call.symbols_per_block = bank_spb;
             call.d_desc = b->view.desc + s0; call.d_block = iq_l; call.block_stride = stream_stride_samples;
             call.d_prev_block = prev_iq ? prev_iq + (size_t)s0 * stream_stride_samples * sb : nullptr;
+            if (b->soft.policy == DABGPU_SOFT_CSI) {         // (mode I banks only: set_soft refuses the others)
+                call.bank_soft = true; call.soft_policy = DABGPU_SOFT_CSI; call.soft_level = b->soft.level; call.d_soft_scale = b->d_soft_scale;
+            }
             CKS(dabgpu_launch_demod(c, G.mode, call, ls));
             CKL(dabgpu_launch_ofdm_phase(corr_l, cnt, b->cfg.sync.fine_freq_update_beta, nullptr, &b->view.sync[s0].freq_fine,
                                         (int)(sizeof(dabgpu_sync_state) / sizeof(float)), b->view.desc + s0, G.n_sym, G.n_fft, ls));
@@ -715,9 +731,10 @@ int dabgpu_stream_bank_process_raw(dabgpu_stream_bank* b, const void* d_raw, int
     if (((stream_stride_samples * sb) & 15) != 0 && b->n > 1) {
         dabgpu_set_error("stream_bank_process_raw: the byte stride between streams must be a multiple of 16"); return DABGPU_ERR_INVALID_ARG;
     }
+    if (int fits = bank_soft_scale_fits(b, max_frames_per_stream)) return fits;          // (before the conversion is launched)
     DABGPU_BIND(b->ctx);
     hipStream_t s = (hipStream_t)stream;
-    const size_t padded = (n_samples + 1) & ~(size_t)1;                    // keeps every stream's converted block 16-byte aligned
+    const size_t padded = (n_samples + 1) & ~(size_t)1;                   // keeps every stream's converted block 16-byte aligned
     const size_t need = b->n * padded * 2 * sizeof(float);
     if (need > b->raw_scratch_bytes) {
         int st = dabgpu_check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
@@ -771,6 +788,27 @@ int dabgpu_stream_bank_process_ring(dabgpu_stream_bank* b, const void* d_raw, in
                                     int8_t* d_hist, int hist_frames, int32_t* d_newest_slot, void* stream) {
     return dabgpu_stream_bank_process_ring_layout(b, d_raw, format, stream_stride_samples, n_samples, d_hist, hist_frames, d_newest_slot,
                                                   DABGPU_BITS_NATURAL, stream);
+}
+
+int dabgpu_stream_bank_set_soft(dabgpu_stream_bank* b, const dabgpu_soft_cfg* cfg, float* d_soft_scale, size_t scale_capacity) {
+    if (!b) { dabgpu_set_error("stream_bank_set_soft: null bank"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_check_soft_cfg("stream_bank_set_soft", cfg);
+    if (st) return st;
+    if (cfg->policy != DABGPU_SOFT_NORMALISED && b->view.g.mode != 1) {
+        dabgpu_set_error("stream_bank_set_soft: the weighted soft bits exist for transmission mode I banks only (mode %d)", b->view.g.mode);
+        return DABGPU_ERR_UNSUPPORTED;
+    }
+    if ((uintptr_t)d_soft_scale & 3) { dabgpu_set_error("stream_bank_set_soft: misaligned scale buffer"); return DABGPU_ERR_INVALID_ARG; }
+    b->soft = *cfg;
+    b->d_soft_scale = d_soft_scale;
+    b->soft_scale_cap = d_soft_scale ? scale_capacity : 0;
+    return DABGPU_OK;
+}
+
+int dabgpu_stream_bank_get_soft(const dabgpu_stream_bank* b, dabgpu_soft_cfg* cfg) {
+    if (!b || !cfg) { dabgpu_set_error("stream_bank_get_soft: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    *cfg = b->soft;
+    return DABGPU_OK;
 }
 
 int dabgpu_stream_bank_status(dabgpu_stream_bank* b, dabgpu_stream_status* h_status, void* stream) {

@@ -93,7 +93,7 @@ ABI_SYMBOLS = [
     "dabgpu_tii_bank_read",
     "dabgpu_ber_plan", "dabgpu_ber_frames_layout", "dabgpu_ber_ring_layout", "dabgpu_ber_fib_group_host_sync", "dabgpu_ber_codeword_host_sync",
     "dabgpu_soft_cfg_default", "dabgpu_soft_scale_host", "dabgpu_ofdm_demod_frames_soft", "dabgpu_ofdm_sync_demod_frames_soft",
-    "dabgpu_receiver_set_soft",
+    "dabgpu_receiver_set_soft", "dabgpu_stream_bank_set_soft", "dabgpu_stream_bank_get_soft",
 ]
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 
@@ -412,6 +412,8 @@ def lib():
         L.dabgpu_dabplus_bank_process_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                                          C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.dabgpu_stream_bank_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_stream_bank_set_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabgpu_stream_bank_get_soft.argtypes = [C.c_void_p, C.c_void_p]
         L.dabgpu_dabplus_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.dabgpu_dabplus_bank_destroy.argtypes = [C.c_void_p]
         L.dabgpu_dabplus_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
@@ -1020,6 +1022,20 @@ class StreamBank(_Handle):
         check(lib().dabgpu_stream_bank_process_ring_retained(self._h, _ptr(raw), int(fmt), stream_stride_samples, n_samples, _ptr(prev_raw), _ptr(hist),
                                                              hist_frames, _ptr(newest_slot), int(bits_layout), Context._stream(stream)),
               "dabgpu_stream_bank_process_ring_retained")
+
+    def set_soft(self, soft, soft_scale=None):
+        """the soft-decision policy (`soft` = a SoftCfg) of every frame demodulated from the next process call on; soft_scale = a float32
+        tensor on the device that receives the scale of the frame in bits slot j of stream s at [s * max_frames + j] (ring forms:
+        [s * hist_frames + ring slot]).  The bank keeps the address: keep the tensor alive while the policy is set
+        (dabgpu_stream_bank_set_soft)"""
+        check(lib().dabgpu_stream_bank_set_soft(self._h, C.byref(soft), _ptr(soft_scale), 0 if soft_scale is None else int(soft_scale.numel())),
+              "dabgpu_stream_bank_set_soft")
+        self._soft_scale = soft_scale
+
+    def get_soft(self):
+        soft = SoftCfg()
+        check(lib().dabgpu_stream_bank_get_soft(self._h, C.byref(soft)), "dabgpu_stream_bank_get_soft")
+        return soft
 
     def status(self, stream=None):
         import numpy as np

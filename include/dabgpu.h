@@ -278,7 +278,9 @@ int dabgpu_ofdm_sync_demod_frames(dabgpu_ctx *ctx, const float *d_iq, size_t n_s
  *                           and -im d, NaN -> 0, clamped to [-127, 127], truncated towards zero.  P zero or not finite, or k not
  *                           finite: k = 0, every soft bit of the frame is 0 (an erasure).  Frequency de-interleave and both layouts
  *                           as ever.  Arithmetic: csrc/softbit_csi_core.h, the device equals dabgpu_soft_scale_host bit for bit.
- * level: [1, 127], default 64; anything else is DABGPU_ERR_INVALID_ARG.  Mode I only, no stream bank, no banked receiver.
+ * level: [1, 127], default 64; anything else is DABGPU_ERR_INVALID_ARG.  Mode I only, no banked receiver.  The stream bank takes the
+ * policy through dabgpu_stream_bank_set_soft: its frames lie in the stream's frame buffer and in the caller's blocks, P is the power of
+ * symbol 0 as the bank's loader delivers it (frame-buffer samples as stored, block samples through the reader arithmetic of the format).
  */
 #define DABGPU_SOFT_NORMALISED 0
 #define DABGPU_SOFT_CSI 1
@@ -746,6 +748,18 @@ int dabgpu_stream_bank_process_ring_layout(dabgpu_stream_bank *bank, const void 
 int dabgpu_stream_bank_process_ring_retained(dabgpu_stream_bank *bank, const void *d_raw, int format, size_t stream_stride_samples,
                                              size_t n_samples, const void *d_prev_raw, int8_t *d_hist, int hist_frames,
                                              int32_t *d_newest_slot, int bits_layout, void *stream);
+/* the soft-decision policy of every frame the bank demodulates from the next process call on (any of the six forms); default
+ * DABGPU_SOFT_NORMALISED.  d_soft_scale (may be NULL): scale_capacity floats on the device; the scale k of the frame written to
+ * bits slot j of stream s goes to d_soft_scale[s * max_frames_per_stream + j] (ring forms: s * hist_frames + ring slot) -- the
+ * numbering of that call's d_bits / d_hist; a call with n_streams * max_frames_per_stream (hist_frames) > scale_capacity is refused
+ * before anything is launched.  Kept across dabgpu_stream_bank_reset, like the bank's configuration.  Mode I banks; a bank of
+ * modes II-IV answers DABGPU_ERR_UNSUPPORTED with a reason and keeps the normalised policy.  Synchronises with nothing.
+ * Under DABGPU_SOFT_NORMALISED every process call is what it is without this call, and d_soft_scale is never written.  The policy may
+ * change between two retained calls: it belongs to the frame that completes, not to the block in which the frame began.  The bank's
+ * state machine (level, NULL search, synchroniser, fine-frequency loop) never reads a soft bit: the policy changes no frame count, no
+ * frame position and no status field, only the bits. */
+int dabgpu_stream_bank_set_soft(dabgpu_stream_bank *bank, const dabgpu_soft_cfg *cfg, float *d_soft_scale, size_t scale_capacity);
+int dabgpu_stream_bank_get_soft(const dabgpu_stream_bank *bank, dabgpu_soft_cfg *cfg);
 /* snapshot of every stream's getters (GetState, GetSignalAverage, Get*FrequencyOffset, ...) into host memory; synchronous */
 int dabgpu_stream_bank_status(dabgpu_stream_bank *bank, dabgpu_stream_status *h_status, void *stream);
 

@@ -12,7 +12,7 @@ frames completed per second over the timed steps (read from the bank's counters 
 `overlap`: the bank runs on one HIP stream, the decoders + DAB+ on another (own context), so block j + 1's front end runs beside block
 j's trellis kernel; `sequential`: everything on one stream.
 
-    python tools/bench_chain.py [--ensembles 4096] [--steps 12] [--distinct 64]
+    python tools/bench_chain.py [--ensembles 4096] [--steps 12] [--distinct 64] [--soft-bits normalised|csi [--soft-level 64]]
 (bench.py calls run_chain() for its `extra.chain` block.)"""
 import argparse
 import json
@@ -30,7 +30,7 @@ REALTIME_FRAMES_PER_S = 2.048e6 / 196608
 
 
 def run_chain(ctx, dabgpu, torch, device, E, n_distinct, steps=12, warm_steps=8, seed=31, layout=1, rs_errors=1, with_dabplus=True, noise=0.05,
-              sequential_steps=4, retained=True):
+              sequential_steps=4, retained=True, soft_bits="normalised", soft_level=64.0):
     import numpy as np
     import dabsynth
     prs, mapper, _ = dabgpu.host_tables()
@@ -47,6 +47,8 @@ def run_chain(ctx, dabgpu, torch, device, E, n_distinct, steps=12, warm_steps=8,
     stride = raw.shape[1]                                        # samples per receiver buffer (rep + BLOCK)
     fmt_u8 = dabgpu.IQ_FORMATS.index("raw_u8")
     bank = dabgpu.StreamBank(ctx, E)
+    if soft_bits != "normalised":                                # the weighted soft bits in the front end (dabgpu_stream_bank_set_soft)
+        bank.set_soft(dabgpu.SoftCfg(dabgpu.SOFT_CSI, soft_level))
     ctx2 = dabgpu.Context(device.index)
     dp = dabgpu.DabPlusBank(ctx2, E * nsub) if with_dabplus else None
     subs = mux.subchannels(dabgpu)
@@ -194,6 +196,8 @@ def run_chain(ctx, dabgpu, torch, device, E, n_distinct, steps=12, warm_steps=8,
            "history_layout": "time-interleaver class order" if layout else "natural",
            "blocks": "retained (dabgpu_stream_bank_process_ring_retained: no carry-over copy)" if retained else "copied (dabgpu_stream_bank_process_ring_layout)",
            "input_bytes_per_frame": 2 * dabsynth.NB_FRAME_SAMPLES, "generation_s_untimed": t_gen, "check": chk}
+    if soft_bits != "normalised":
+        out["soft_bits"] = {"policy": soft_bits, "level": soft_level}
     bank.close()
     if dp is not None:
         dp.close()
@@ -212,6 +216,8 @@ def main():
     ap.add_argument("--rs-errors", type=int, default=1)
     ap.add_argument("--no-dabplus", action="store_true")
     ap.add_argument("--copying", action="store_true", help="the ring form that copies the unfinished frame at a block's end (blocks need not outlive the call)")
+    ap.add_argument("--soft-bits", choices=("normalised", "csi"), default="normalised", help="soft-decision policy of the stream bank")
+    ap.add_argument("--soft-level", type=float, default=64.0, help="level of --soft-bits csi")
     a = ap.parse_args()
     import torch
     import dabgpu
@@ -219,7 +225,7 @@ def main():
     torch.cuda.set_device(0)
     ctx = dabgpu.Context(0)
     out = run_chain(ctx, dabgpu, torch, device, a.ensembles, a.distinct, steps=a.steps, layout=int(a.hist_layout == "classed"),
-                    rs_errors=a.rs_errors, with_dabplus=not a.no_dabplus, retained=not a.copying)
+                    rs_errors=a.rs_errors, with_dabplus=not a.no_dabplus, retained=not a.copying, soft_bits=a.soft_bits, soft_level=a.soft_level)
     print(json.dumps(out))
 
 
