@@ -9,7 +9,8 @@
 // live in HBM between calls.  Syndromes: every lane adds the terms of a share of one codeword's symbols for all ten roots
 // (XOR shuffles fold the shares); a codeword with a non-zero syndrome gets its error locator from ONE lane (Berlekamp-Massey,
 // all codewords of the super frame in parallel), the Chien search and Forney's corrections are dealt over all 64 lanes; the
-// access-unit CRCs are shared by 8-32 lanes each.  LDS table look-ups throughout (GF(2^8) log / exp, CRC-16).
+// access-unit CRCs are shared by 8-32 lanes each.  LDS table look-ups throughout (GF(2^8) log / exp, CRC-16).  The Reed-Solomon arithmetic
+// is rs_core.h's (host check: tests/test_rs_core_host.py), tables and the shared-lane CRC rs_device.h's: both shared with packet_fec.hip.
 // Integer / byte work, bit-exact by construction; checked against the oracle and the reference-generated vectors.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,61 +43,21 @@ struct DpState {                     // per stream, persistent
     int wait_frame_start, curr_dab_frame, prev_n, synced, desync_count;
 };
 
-__device__ __forceinline__ uint8_t gmul(const DpLds& L, uint8_t a, uint8_t b) { return (a && b) ? L.exp[L.log[a] + L.log[b]] : (uint8_t)0; }
-__device__ __forceinline__ uint8_t gdiv(const DpLds& L, uint8_t a, uint8_t b) { return a ? L.exp[L.log[a] + 255 - L.log[b]] : (uint8_t)0; }
-__device__ __forceinline__ uint8_t gpow(const DpLds& L, int e) { e %= 255; if (e < 0) e += 255; return L.exp[e]; }
-
-// RS(120,110) decoding of a super frame's codewords (restates dab_rs120_decode of the oracle), in two phases:
-// rs_locator: ONE lane per codeword with a non-zero syndrome runs Berlekamp-Massey and leaves the error locator (C_1..C_10, degree) in the
-// codeword's record and the evaluator omega = S C mod x^deg in place of the syndromes;
+// RS(120,110) decoding of a super frame's codewords (the arithmetic: rs_core.h), in two phases:
+// rs_locator: ONE lane per codeword with a non-zero syndrome runs Berlekamp-Massey, its polynomials in registers, and leaves the error
+// locator (C_1..C_10, degree) in the codeword's record and the evaluator omega in place of the syndromes;
 // rs_search_and_correct: the Chien search over alpha^1..alpha^255 and Forney's formula are shared by ALL lanes -- the wavefront's lanes are
 // dealt to the codewords (64 / n_rs each), every lane scans its share of the 255 candidates and corrects the symbol of each root it
 // finds, counting it in the record.  A locator of degree d has at most d roots, so scanning all candidates finds what the reference's scan
 // (which stops after d) finds; corrections made for a codeword that then turns out uncorrectable (roots != degree) are undone by the
 // caller from the received bytes.
 __device__ void rs_locator(DpLds& L, int i) {
+    uint8_t* const omega = &L.syn[i * RS_ROOTS];             // (the syndromes are done with once S holds them)
     uint8_t S[RS_ROOTS];
 #pragma unroll
-    for (int r = 0; r < RS_ROOTS; r++) S[r] = L.syn[i * RS_ROOTS + r];
+    for (int r = 0; r < RS_ROOTS; r++) S[r] = omega[r];
     uint8_t C[RS_ROOTS + 1], B[RS_ROOTS + 1], T[RS_ROOTS + 1];
-#pragma unroll
-    for (int k = 0; k <= RS_ROOTS; k++) { C[k] = (k == 0); B[k] = (k == 0); }
-    int len = 0;
-    for (int r = 1; r <= RS_ROOTS; r++) {
-        uint8_t d = 0;
-#pragma unroll
-        for (int k = 0; k < RS_ROOTS; k++) if (k < r) d ^= gmul(L, C[k], S[(r - 1 - k) < 0 ? 0 : (r - 1 - k)]);
-        if (d == 0) {
-#pragma unroll
-            for (int k = RS_ROOTS; k > 0; k--) B[k] = B[k - 1];
-            B[0] = 0;
-        } else {
-            T[0] = C[0];
-#pragma unroll
-            for (int k = 0; k < RS_ROOTS; k++) T[k + 1] = (uint8_t)(C[k + 1] ^ gmul(L, d, B[k]));
-            if (2 * len <= r - 1) {
-                len = r - len;
-#pragma unroll
-                for (int k = 0; k <= RS_ROOTS; k++) B[k] = gdiv(L, C[k], d);
-            } else {
-#pragma unroll
-                for (int k = RS_ROOTS; k > 0; k--) B[k] = B[k - 1];
-                B[0] = 0;
-            }
-#pragma unroll
-            for (int k = 0; k <= RS_ROOTS; k++) C[k] = T[k];
-        }
-    }
-    int deg = 0;
-#pragma unroll
-    for (int k = 0; k <= RS_ROOTS; k++) if (C[k]) deg = k;
-#pragma unroll
-    for (int a = 0; a < RS_ROOTS; a++) {
-        uint8_t t = 0;
-#pragma unroll
-        for (int b = 0; b < RS_ROOTS; b++) if (b <= a) t ^= gmul(L, S[a - b < 0 ? 0 : a - b], C[b]);
-        L.syn[i * RS_ROOTS + a] = t;                                    // omega_a (the syndromes are done with)
-    }
+    const int deg = rs::locator<RS_ROOTS>(L, S, C, B, T, omega);
 #pragma unroll
     for (int k = 1; k <= RS_ROOTS; k++) L.rs_rec[i * 16 + k - 1] = C[k];
     *reinterpret_cast<int*>(&L.rs_rec[i * 16 + 12]) = deg;
@@ -107,37 +68,19 @@ __device__ void rs_search_and_correct(DpLds& L, int i, int q, int per, int n_rs)
     const int deg = *rec & 0xFF;
     if (deg == 0) return;
     const int span = (255 + per - 1) / per, x0 = 1 + q * span, x1 = (x0 + span - 1 < 255) ? (x0 + span - 1) : 255;
+    const uint8_t* const omega = &L.syn[i * RS_ROOTS];
     uint8_t C[RS_ROOTS + 1];
-    int reg[RS_ROOTS + 1];                                   // log C_k + x k (mod 255), advanced incrementally
+    int reg[RS_ROOTS + 1];
     C[0] = 1;
 #pragma unroll
-    for (int k = 1; k <= RS_ROOTS; k++) {
-        C[k] = L.rs_rec[i * 16 + k - 1];
-        reg[k] = (L.log[C[k]] + k * (x0 - 1)) % 255;
-    }
+    for (int k = 1; k <= RS_ROOTS; k++) C[k] = L.rs_rec[i * 16 + k - 1];
+    rs::chien_start<RS_ROOTS>(L, C, x0, reg);
     for (int x = x0; x <= x1; x++) {
-        uint8_t v = 1;
-#pragma unroll
-        for (int k = 1; k <= RS_ROOTS; k++) {
-            if (k <= deg && C[k]) {
-                reg[k] += k;
-                if (reg[k] >= 255) reg[k] -= 255;
-                v ^= L.exp[reg[k]];
-            }
-        }
-        if (v) continue;
+        if (rs::chien_next<RS_ROOTS>(L, C, deg, reg)) continue;
         atomicAdd(rec, 0x100);
-        // Forney: e = omega(X^-1) X / C'(X^-1), first root alpha^0
-        const int rk = x;
-        uint8_t num1 = 0, den = 0;
-#pragma unroll
-        for (int a = RS_ROOTS - 1; a >= 0; a--) if (a < deg) num1 ^= gmul(L, L.syn[i * RS_ROOTS + a], gpow(L, a * rk));
-        const uint8_t num2 = gpow(L, -rk);
-        const int top = ((deg < RS_ROOTS - 1) ? deg : (RS_ROOTS - 1)) & ~1;
-#pragma unroll
-        for (int a = 8; a >= 0; a -= 2) if (a <= top) den ^= gmul(L, C[a + 1], gpow(L, a * rk));
-        const int loc = rk - 1;
-        if (num1 != 0 && loc >= RS_PAD) L.sf[i + (loc - RS_PAD) * n_rs] ^= gdiv(L, gmul(L, num1, num2), den);
+        const uint8_t val = rs::forney<RS_ROOTS>(L, C, omega, deg, x);
+        const int loc = x - 1;
+        if (val && loc >= RS_PAD) L.sf[i + (loc - RS_PAD) * n_rs] ^= val;
     }
 }
 
@@ -157,14 +100,7 @@ void dabplus_kernel(DpState* __restrict__ states, const uint8_t* __restrict__ fr
         if (lane == 0) { counts[4 * s] = 0; counts[4 * s + 1] = 0; counts[4 * s + 2] = 0; counts[4 * s + 3] = states[s].curr_dab_frame; }
         return;
     }
-    for (int k = lane; k < 512; k += 64) L.exp[k] = GF_TABLES.exp[k];
-    for (int k = lane; k < 256; k += 64) {
-        L.log[k] = GF_TABLES.log[k];
-        uint16_t c = (uint16_t)(k << 8);
-#pragma unroll
-        for (int j = 0; j < 8; j++) c = (c & 0x8000u) ? (uint16_t)((c << 1) ^ 0x1021u) : (uint16_t)(c << 1);
-        L.crc_tab[k] = c;
-    }
+    load_gf_crc_tables(L, lane);
     DpState st = states[s];
     const int n = (int)frame_bytes[s];
     // what this kernel cannot hold is reported, not skipped in silence: logical frames above 1536 bytes (the reference accepts any
@@ -212,24 +148,15 @@ void dabplus_kernel(DpState* __restrict__ states, const uint8_t* __restrict__ fr
         // (GF(2^8) addition: exact, order-free).  Other sizes keep the (codeword, root) Horner form.
         if (n_rs > 0 && (64 % n_rs) == 0) {              // (frames below 24 bytes hold no codeword at all: n_rs = 0, nothing to correct)
             const int per = 64 / n_rs, i = lane % n_rs, q = lane / n_rs;
-            uint32_t w0 = 0, w1 = 0, w2 = 0;                               // roots 0-3, 4-7, 8-9: one byte each
-            for (int j = q; j < RS_N; j += per) {
-                const uint8_t cj = L.sf[i + j * n_rs];
-                if (cj) {
-                    const int lc = L.log[cj], e = RS_N - 1 - j;
-                    int t = 0;                                             // (r e) mod 255
+            uint32_t w[3] = {0, 0, 0};                                     // roots 0-3, 4-7, 8-9: one byte each
+            for (int j = q; j < RS_N; j += per) rs::syndrome_add<RS_N, RS_ROOTS>(L, L.sf[i + j * n_rs], j, w);
+            for (int sft = 32; sft >= n_rs; sft >>= 1) {
 #pragma unroll
-                    for (int r = 0; r < RS_ROOTS; r++) {
-                        const uint32_t term = L.exp[lc + t];
-                        if (r < 4) w0 ^= term << (8 * r); else if (r < 8) w1 ^= term << (8 * (r - 4)); else w2 ^= term << (8 * (r - 8));
-                        t += e; if (t >= 255) t -= 255;
-                    }
-                }
+                for (int k = 0; k < 3; k++) w[k] ^= (uint32_t)__shfl_xor((int)w[k], sft);
             }
-            for (int sft = 32; sft >= n_rs; sft >>= 1) { w0 ^= (uint32_t)__shfl_xor((int)w0, sft); w1 ^= (uint32_t)__shfl_xor((int)w1, sft); w2 ^= (uint32_t)__shfl_xor((int)w2, sft); }
             if (q == 0) {
 #pragma unroll
-                for (int r = 0; r < RS_ROOTS; r++) L.syn[i * RS_ROOTS + r] = (uint8_t)(((r < 4) ? (w0 >> (8 * r)) : (r < 8) ? (w1 >> (8 * (r - 4))) : (w2 >> (8 * (r - 8)))) & 0xFFu);
+                for (int r = 0; r < RS_ROOTS; r++) L.syn[i * RS_ROOTS + r] = rs::packed_byte<RS_ROOTS>(w, r);
             }
         } else {
             for (int w = lane; w < n_rs * RS_ROOTS; w += 64) {             // work item = (codeword i, root r)
@@ -265,12 +192,7 @@ void dabplus_kernel(DpState* __restrict__ states, const uint8_t* __restrict__ fr
                 my_cnt = (found == deg) ? deg : -1;
             }
             __syncthreads();
-            for (int k = lane; k < 256; k += 64) {          // the CRC table back in its place
-                uint16_t c = (uint16_t)(k << 8);
-#pragma unroll
-                for (int j = 0; j < 8; j++) c = (c & 0x8000u) ? (uint16_t)((c << 1) ^ 0x1021u) : (uint16_t)(c << 1);
-                L.crc_tab[k] = c;
-            }
+            load_crc_table(L, lane);                        // back in its place
         }
         __syncthreads();
         if (lane == 0) L.flags[3] = 0x7FFFFFFF;
@@ -337,10 +259,7 @@ void dabplus_kernel(DpState* __restrict__ states, const uint8_t* __restrict__ fr
             }
             res.au_walk_stopped_at = stop;
             const int walked = (stop < 0) ? num_aus : stop;
-            // access-unit CRCs (x^16+x^12+x^5+1, start value 0xFFFF, inverted).  An access unit is shared by `per` lanes: with the
-            // start value folded into its first two bytes the register is linear in the message, so the unit is padded at the FRONT
-            // with zero bytes to per x c, lane q runs chunk q from a zero register (and x^(8c) beside it, on the same table), and the
-            // chunks are joined pairwise -- left x^(8 c 2^k) + right -- in log2(per) rounds of shuffles.
+            // access-unit CRCs (x^16+x^12+x^5+1, start value 0xFFFF, inverted), each unit shared by 32 / 16 / 8 lanes
             if (lane == 0) L.flags[0] = 0;
             if (lane == 0) {
 #pragma unroll
@@ -352,26 +271,8 @@ void dabplus_kernel(DpState* __restrict__ states, const uint8_t* __restrict__ fr
                 const int a = lane >> lg, q = lane & (per - 1);
                 const bool mine = a < walked;
                 const int a0 = mine ? L.au[a] : 0, nb_data = mine ? (L.au[a + 1] - a0 - 2) : 0;
-                uint32_t state = 0, m = 1;
-                if (nb_data >= 2) {
-                    const int c = (nb_data + per - 1) >> lg, z = per * c - nb_data;
-                    for (int t = 0, k = q * c - z; t < c; t++, k++) {
-                        uint32_t byte = (k >= 0) ? L.sf[a0 + k] : 0u;
-                        if (k == 0 || k == 1) byte ^= 0xFFu;
-                        state = ((state << 8) ^ L.crc_tab[((state >> 8) ^ byte) & 0xFFu]) & 0xFFFFu;
-                        m = ((m << 8) ^ L.crc_tab[(m >> 8) & 0xFFu]) & 0xFFFFu;
-                    }
-                } else if (nb_data == 1 && q == per - 1) {
-                    state = 0xFFFFu;
-                    state = ((state << 8) ^ L.crc_tab[((state >> 8) ^ L.sf[a0]) & 0xFFu]) & 0xFFFFu;
-                } else if (q == per - 1) state = 0xFFFFu;
-                for (int d = 1; d < per; d <<= 1) {
-                    const uint32_t left = (uint32_t)__shfl_xor((int)state, d);
-                    if (q & d) state ^= crc_mulmod(left, m);
-                    m = crc_mulmod(m, m);
-                }
+                const uint16_t crc = au_crc_lanes([&](int k) { return (uint32_t)L.sf[a0 + k]; }, nb_data, L.crc_tab, lg, q);
                 if (mine && q == per - 1) {
-                    const uint16_t crc = (uint16_t)(state ^ 0xFFFFu);
                     const uint16_t rx = (uint16_t)((L.sf[a0 + nb_data] << 8) | L.sf[a0 + nb_data + 1]);
                     if (rx == crc) atomicOr(&L.flags[0], 1 << a);
                     L.syn[2 * a] = (uint8_t)(crc >> 8); L.syn[2 * a + 1] = (uint8_t)(crc & 0xFF);       // syndromes are done with

@@ -1,9 +1,11 @@
-// dabplus_common.h -- what the DAB+ outer decoder (dabplus.hip) and the super-frame encoder (dabplus_tx.hip) share: the GF(2^8) tables of
-// RS(120,110), the fire code's and the access-unit CRC's linear maps (ETSI TS 102 563 clauses 5.2, 5.3.2, 6).  Tables are built at compile
-// time; every translation unit that includes this header holds its own copy in constant memory.
+// dabplus_common.h -- what only the DAB+ outer decoder (dabplus.hip) and the super-frame encoder (dabplus_tx.hip) share: the constants of
+// RS(120,110) and of the super frame, the fire code's linear map and the access-unit CRC's short units (ETSI TS 102 563 clauses 5.2, 5.3.2,
+// 6).  The fire-code table is built at compile time; every translation unit that includes this header holds its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "rs_device.h"
 
 namespace dabgpu {
 
@@ -11,21 +13,6 @@ constexpr int RS_N = 120, RS_ROOTS = 10, RS_PAD = 135;
 constexpr int RS_DATA = RS_N - RS_ROOTS;
 constexpr int DP_MAX_FRAME_BYTES = 1536;                 // 5 n / 120 <= 64 codewords = one per lane
 constexpr int DP_MAX_SF = 5 * DP_MAX_FRAME_BYTES;
-
-struct GfTables { uint8_t exp[512]; uint8_t log[256]; };
-constexpr GfTables make_gf() {
-    GfTables t{};
-    unsigned x = 1;
-    for (int i = 0; i < 255; i++) {
-        t.exp[i] = (uint8_t)x; t.exp[i + 255] = (uint8_t)x; t.log[x] = (uint8_t)i;
-        x <<= 1;
-        if (x & 0x100u) x ^= 0x11Du;
-    }
-    t.exp[510] = t.exp[0]; t.exp[511] = t.exp[1];
-    t.log[0] = 0;
-    return t;
-}
-static __constant__ GfTables GF_TABLES = make_gf();
 
 // fire code x^16+x^14+x^13+x^12+x^11+x^5+x^3+x^2+x+1 over the 72 bits after the check word, zero start value: message bit b (0 = MSB of
 // the first byte) contributes x^(16 + 71 - b) mod p(x); the check word is the XOR of the contributions of the set bits
@@ -50,15 +37,15 @@ __device__ __forceinline__ uint16_t firecode_wave(const uint8_t* x, int lane) {
     return (uint16_t)v;
 }
 
-// a(x) b(x) mod x^16+x^12+x^5+1 (16-bit residues)
-__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        r ^= (0u - ((b >> i) & 1u)) & a;
-        a = (a << 1) ^ ((0u - ((a >> 15) & 1u)) & 0x11021u);
+// CRC of an access unit shared by 1 << lg lanes (crc_lanes).  A unit of one byte or none has no two bytes to fold the start value into: the
+// group's last lane starts from the register after it, and no lane has a chunk to run.
+template <class F> __device__ __forceinline__ uint16_t au_crc_lanes(F byte_at, int nb_data, const uint16_t* crc_tab, int lg, int q) {
+    uint32_t state = 0;
+    if (q == (1 << lg) - 1) {
+        if (nb_data == 1) state = ((0xFFFFu << 8) ^ crc_tab[(0xFFu ^ byte_at(0)) & 0xFFu]) & 0xFFFFu;
+        else if (nb_data < 1) state = 0xFFFFu;
     }
-    return r;
+    return crc_lanes(byte_at, (nb_data < 2) ? 0 : nb_data, crc_tab, lg, q, state);
 }
 
 }  // namespace dabgpu

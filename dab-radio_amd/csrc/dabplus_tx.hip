@@ -5,15 +5,15 @@
 // One wavefront (a 64-thread workgroup) per super frame, the super frame in LDS:
 //   1. layout: every lane evaluates dabgpu_dabplus_layout (dabgpu_host_logic.h, the host entry point's body) on wave-uniform inputs;
 //   2. fill: header bytes 2.., then the access units copied from global memory, 64 consecutive bytes per load;
-//   3. access-unit CRCs: 32 / 16 / 8 lanes per unit for 2 / 3-4 / 6 units, each lane a chunk, the chunks joined by crc_mulmod -- the method of
-//      dabplus.hip's check, here writing the two bytes instead of comparing them;
+//   3. access-unit CRCs: 32 / 16 / 8 lanes per unit for 2 / 3-4 / 6 units, each lane a chunk, the chunks joined by crc_mulmod
+//      (au_crc_lanes, which dabplus.hip's check calls too), here writing the two bytes instead of comparing them;
 //   4. fire code of bytes 2..10 (firecode_wave);
 //   5. RS parity.  The ten parity bytes are linear in the data bytes: data byte j of a code word contributes d_j x^(119 - j) mod g(x), ten
-//      bytes whose logarithms are a row of a constant table.  A code word is dealt to `per` lanes, lane (i, q) adds the contributions of
-//      symbols q, q + per, ... of code word i (1 + 1 + 10 LDS look-ups per symbol: the byte, its logarithm and the table row in one 16-byte
-//      read, ten antilogarithms), and the shares are folded by XOR into three LDS words per code word.  n_rs x per work items are walked
-//      64 at a time: per = 64 / n_rs up to 32 code words (one pass, at least 33 lanes busy), 128 / n_rs from 33 on (two passes of at most 55
-//      symbols instead of one of 110 with half the wavefront idle);
+//      bytes whose logarithms are a row of a constant table (rs_core.h makes it, for packet_fec.hip's code too).  A code word is dealt to
+//      `per` lanes, lane (i, q) adds the contributions of symbols q, q + per, ... of code word i (1 + 1 + 10 LDS look-ups per symbol: the
+//      byte, its logarithm and the table row in one 16-byte read, ten antilogarithms), and the shares are folded by XOR into three LDS
+//      words per code word.  n_rs x per work items are walked 64 at a time: per = 64 / n_rs up to 32 code words (one pass, at least 33
+//      lanes busy), 128 / n_rs from 33 on (two passes of at most 55 symbols instead of one of 110 with half the wavefront idle);
 //   6. the 120 n_rs bytes leave LDS as dwords, frame by frame (frame sizes, offsets and the stride are multiples of 4).
 // A super frame the layout refuses writes zeros and its code.  Integer / byte work, bit-exact by construction.
 #include <hip/hip_runtime.h>
@@ -28,35 +28,10 @@
 
 namespace dabgpu {
 
-// row j = log of the ten coefficients of x^(119 - j) mod g(x), highest power first (= parity byte order), g(x) = prod (x + alpha^r), r = 0..9;
-// 16 bytes per row for one aligned read.  No coefficient is zero (checked below), so no row needs a "no contribution" mark.
-struct RsParityTab { alignas(16) uint8_t log_coef[RS_DATA][16]; bool all_nonzero; };
-constexpr RsParityTab make_rs_parity_tab() {
-    const GfTables gf = make_gf();
-    auto mul = [&](unsigned a, unsigned b) -> unsigned { return (a && b) ? gf.exp[gf.log[a] + gf.log[b]] : 0u; };
-    unsigned g[RS_ROOTS + 1] = {1};                          // ascending powers
-    for (int r = 0; r < RS_ROOTS; r++) {
-        for (int k = r + 1; k > 0; k--) g[k] = g[k - 1] ^ mul(g[k], gf.exp[r]);
-        g[0] = mul(g[0], gf.exp[r]);
-    }
-    RsParityTab t{};
-    t.all_nonzero = true;
-    unsigned rem[RS_ROOTS] = {};                             // x^e mod g(x), ascending powers; e = 10 first
-    for (int k = 0; k < RS_ROOTS; k++) rem[k] = g[k];        // x^10 = g(x) - x^10 = the lower coefficients (characteristic 2)
-    for (int j = RS_DATA - 1; j >= 0; j--) {                 // e = 119 - j
-        for (int r = 0; r < RS_ROOTS; r++) {
-            t.log_coef[j][r] = gf.log[rem[RS_ROOTS - 1 - r]];
-            if (rem[RS_ROOTS - 1 - r] == 0) t.all_nonzero = false;
-        }
-        const unsigned top = rem[RS_ROOTS - 1];              // times x
-        for (int k = RS_ROOTS - 1; k > 0; k--) rem[k] = rem[k - 1] ^ mul(top, g[k]);
-        rem[0] = mul(top, g[0]);
-    }
-    return t;
-}
-constexpr RsParityTab RS_PARITY_TAB_HOST = make_rs_parity_tab();
-static_assert(RS_PARITY_TAB_HOST.all_nonzero, "a zero coefficient would need a mark in the logarithm table");
-static __constant__ RsParityTab RS_PARITY_TAB = make_rs_parity_tab();
+// the parity map of RS(120,110) (rs_core.h).  No coefficient is zero, so no row needs its "no contribution" mark
+constexpr rs::ParityTab<RS_DATA, RS_ROOTS> RS_PARITY_TAB_HOST = rs::make_parity_tab<RS_DATA, RS_ROOTS>();
+static_assert(RS_PARITY_TAB_HOST.all_nonzero, "a zero coefficient would need its mark read");
+static __constant__ rs::ParityTab<RS_DATA, RS_ROOTS> RS_PARITY_TAB = rs::make_parity_tab<RS_DATA, RS_ROOTS>();
 
 struct TxLds {
     alignas(16) uint8_t par_log[RS_DATA][16];
@@ -67,33 +42,6 @@ struct TxLds {
     uint32_t par[64][3];             // parity of code word i: bytes 0-3 | 4-7 | 8-9, byte r in bits 8 (r % 4) ..
     int au[8];                       // access-unit starts
 };
-
-// CRC of an access unit (start value 0xFFFF, inverted) shared by per = 1 << lg lanes, this one lane q of them; lane per - 1 returns it.
-// With the start value folded into its first two bytes the register is linear in the message, so the unit is padded at the FRONT with zero
-// bytes to per x c, lane q runs chunk q from a zero register (and x^(8c) beside it, on the same table), and the chunks are joined pairwise
-// -- left x^(8 c 2^k) + right -- in lg rounds of shuffles (dabplus.hip checks the units the same way).
-__device__ __forceinline__ uint16_t au_crc_lanes(const uint8_t* bytes, int nb_data, const uint16_t* crc_tab, int lg, int q) {
-    const int per = 1 << lg;
-    uint32_t state = 0, m = 1;
-    if (nb_data >= 2) {
-        const int c = (nb_data + per - 1) >> lg, z = per * c - nb_data;
-        for (int t = 0, k = q * c - z; t < c; t++, k++) {
-            uint32_t byte = (k >= 0) ? bytes[k] : 0u;
-            if (k == 0 || k == 1) byte ^= 0xFFu;
-            state = ((state << 8) ^ crc_tab[((state >> 8) ^ byte) & 0xFFu]) & 0xFFFFu;
-            m = ((m << 8) ^ crc_tab[(m >> 8) & 0xFFu]) & 0xFFFFu;
-        }
-    } else if (nb_data == 1 && q == per - 1) {
-        state = 0xFFFFu;
-        state = ((state << 8) ^ crc_tab[((state >> 8) ^ bytes[0]) & 0xFFu]) & 0xFFFFu;
-    } else if (q == per - 1) state = 0xFFFFu;
-    for (int d = 1; d < per; d <<= 1) {
-        const uint32_t left = (uint32_t)__shfl_xor((int)state, d);
-        if (q & d) state ^= crc_mulmod(left, m);
-        m = crc_mulmod(m, m);
-    }
-    return (uint16_t)(state ^ 0xFFFFu);
-}
 
 __global__ __launch_bounds__(64)
 void dabplus_tx_kernel(const uint8_t* __restrict__ au_bytes, const unsigned long long* __restrict__ au_offsets, const uint16_t* __restrict__ au_len,
@@ -121,16 +69,9 @@ void dabplus_tx_kernel(const uint8_t* __restrict__ au_bytes, const unsigned long
         return;
     }
     // tables
-    for (int i = lane; i < 512; i += 64) L.exp[i] = GF_TABLES.exp[i];
-    for (int i = lane; i < 256; i += 64) L.log[i] = GF_TABLES.log[i];
+    load_gf_crc_tables(L, lane);
     for (int i = lane; i < RS_DATA; i += 64)
         *reinterpret_cast<uint4*>(L.par_log[i]) = *reinterpret_cast<const uint4*>(RS_PARITY_TAB.log_coef[i]);
-    for (int i = lane; i < 256; i += 64) {
-        uint16_t c = (uint16_t)(i << 8);
-#pragma unroll
-        for (int j = 0; j < 8; j++) c = (c & 0x8000u) ? (uint16_t)((c << 1) ^ 0x1021u) : (uint16_t)(c << 1);
-        L.crc_tab[i] = c;
-    }
     for (int i = lane; i < 64 * 3; i += 64) (&L.par[0][0])[i] = 0;
     if (lane < 7) {
         int v = 0;
@@ -161,7 +102,7 @@ void dabplus_tx_kernel(const uint8_t* __restrict__ au_bytes, const unsigned long
         const int a = lane >> lg, q = lane & (per - 1);
         const bool mine = a < num_aus;
         const int a0 = mine ? L.au[a] : 0, nb_data = mine ? (L.au[a + 1] - a0 - 2) : 0;
-        const uint16_t crc = au_crc_lanes(L.sf + a0, nb_data, L.crc_tab, lg, q);
+        const uint16_t crc = au_crc_lanes([&](int k) { return (uint32_t)L.sf[a0 + k]; }, nb_data, L.crc_tab, lg, q);
         if (mine && q == per - 1) { L.sf[a0 + nb_data] = (uint8_t)(crc >> 8); L.sf[a0 + nb_data + 1] = (uint8_t)(crc & 0xFFu); }
     }
     __syncthreads();
@@ -177,21 +118,18 @@ void dabplus_tx_kernel(const uint8_t* __restrict__ au_bytes, const unsigned long
         const uint32_t items = n_rs * per;
         for (uint32_t w = lane; w < items; w += 64) {
             const uint32_t q = w / n_rs, i = w - q * n_rs;
-            uint32_t w0 = 0, w1 = 0, w2 = 0;
+            uint32_t pw[3] = {0, 0, 0};
             for (uint32_t j = q; j < (uint32_t)RS_DATA; j += per) {
                 const uint32_t d = L.sf[i + j * n_rs];
                 if (d) {
                     const uint32_t ld = L.log[d];
                     const uint4 row = *reinterpret_cast<const uint4*>(L.par_log[j]);
-#pragma unroll
-                    for (int r = 0; r < 4; r++) w0 ^= (uint32_t)L.exp[ld + ((row.x >> (8 * r)) & 0xFFu)] << (8 * r);
-#pragma unroll
-                    for (int r = 0; r < 4; r++) w1 ^= (uint32_t)L.exp[ld + ((row.y >> (8 * r)) & 0xFFu)] << (8 * r);
-#pragma unroll
-                    for (int r = 0; r < 2; r++) w2 ^= (uint32_t)L.exp[ld + ((row.z >> (8 * r)) & 0xFFu)] << (8 * r);
+                    const uint32_t rw[4] = {row.x, row.y, row.z, row.w};
+                    rs::parity_add<RS_ROOTS>(L, ld, rw, 0u, pw);
                 }
             }
-            atomicXor(&L.par[i][0], w0); atomicXor(&L.par[i][1], w1); atomicXor(&L.par[i][2], w2);
+#pragma unroll
+            for (int k = 0; k < 3; k++) atomicXor(&L.par[i][k], pw[k]);
         }
     }
     __syncthreads();

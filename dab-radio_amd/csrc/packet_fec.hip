@@ -1,5 +1,5 @@
 // packet_fec.hip -- MSC packet mode and its FEC scheme on the device, both directions (include/dabgpu.h, "MSC packet mode"; EN 300 401
-// clauses 5.3.2 and 5.3.5).  The arithmetic both kernels share with the host is in packet_fec_core.h.
+// clauses 5.3.2 and 5.3.5).  The packet and ring arithmetic both kernels share with the host is in packet_fec_core.h.
 //
 // Receive (packet_kernel): what MSC_Reed_Solomon_Data_Packet_Processor does (src/dab/msc/msc_reed_solomon_data_packet_processor.cpp), one
 // wavefront per stream.  The stream's ring lives in HBM between calls and in LDS during one; logical frames are staged through an LDS
@@ -13,7 +13,7 @@
 //               applied once their number is known to equal the locator's degree (reed_solomon_decoder.cpp:412-419), to positions
 //               0..187 alone (msc_reed_solomon_data_packet_processor.cpp:232-247)
 // Packets handed out are copied from the ring by all lanes; their CRCs are computed eight packets at a time, eight lanes per packet, each
-// lane a chunk joined by crc_mulmod (the method of dabplus.hip's access-unit check).
+// lane a chunk joined by crc_mulmod (crc_lanes, as for DAB+'s access units).  Field, syndromes and parity map: rs_core.h, as for DAB+.
 //
 // Transmit (packet_tx_kernel): one wavefront per (stream, FEC frame): the frame's packets are built in LDS from the planner's table
 // (headers, data, zero padding, CRC), the 12 x 16 parity bytes are linear maps of the 188 row symbols through a constant 188 x 16 table of
@@ -28,8 +28,8 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
-#include "dabplus_common.h"          // GF(2^8) tables of p(x) = x^8+x^4+x^3+x^2+1 (the same field), crc_mulmod
 #include "packet_fec_core.h"
+#include "rs_device.h"
 
 namespace dabgpu {
 using namespace pkt;
@@ -58,64 +58,25 @@ struct PkLds {
     int8_t rs_count[RS_ROWS];
 };
 
-template <class T> __device__ __forceinline__ uint8_t gmul(const T& L, uint8_t a, uint8_t b) { return (a && b) ? L.exp[L.log[a] + L.log[b]] : (uint8_t)0; }
-template <class T> __device__ __forceinline__ uint8_t gdiv(const T& L, uint8_t a, uint8_t b) { return a ? L.exp[L.log[a] + 255 - L.log[b]] : (uint8_t)0; }
-template <class T> __device__ __forceinline__ uint8_t gpow(const T& L, int e) { e %= 255; if (e < 0) e += 255; return L.exp[e]; }
-
-template <class T> __device__ __forceinline__ void load_tables(T& L, int lane) {
-    for (int k = lane; k < 512; k += 64) L.exp[k] = GF_TABLES.exp[k];
-    for (int k = lane; k < 256; k += 64) {
-        L.log[k] = GF_TABLES.log[k];
-        uint16_t c = (uint16_t)(k << 8);
-#pragma unroll
-        for (int j = 0; j < 8; j++) c = (c & 0x8000u) ? (uint16_t)((c << 1) ^ 0x1021u) : (uint16_t)(c << 1);
-        L.crc_tab[k] = c;
-    }
-}
-
-// CRC (start 0xFFFF, inverted) of nb bytes shared by 8 lanes, this one lane q of them; lane 7 returns it.  With the start value folded into
-// the first two bytes the register is linear in the message: the message is padded at the FRONT with zero bytes to 8 c, lane q runs chunk q
-// from a zero register (and x^(8c) beside it), the chunks are joined pairwise in three rounds of shuffles.  nb <= 0: no work, shuffles only.
-template <class F> __device__ __forceinline__ uint16_t crc_8lanes(F byte_at, int nb, const uint16_t* crc_tab, int q) {
-    uint32_t state = 0, m = 1;
-    if (nb > 0) {
-        const int c = (nb + 7) >> 3, z = 8 * c - nb;
-        for (int t = 0, k = q * c - z; t < c; t++, k++) {
-            uint32_t byte = (k >= 0) ? byte_at(k) : 0u;
-            if (k == 0 || k == 1) byte ^= 0xFFu;
-            state = ((state << 8) ^ crc_tab[((state >> 8) ^ byte) & 0xFFu]) & 0xFFFFu;
-            m = ((m << 8) ^ crc_tab[(m >> 8) & 0xFFu]) & 0xFFFFu;
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 8; d <<= 1) {
-        const uint32_t left = (uint32_t)__shfl_xor((int)state, d);
-        if (q & d) state ^= crc_mulmod(left, m);
-        m = crc_mulmod(m, m);
-    }
-    return (uint16_t)(state ^ 0xFFFFu);
-}
-
-// Berlekamp-Massey for row i (reed_solomon_decoder.cpp:323-382 in polynomial form), then omega = S C mod x^16 (:425-434)
+// Berlekamp-Massey for row i, then omega = S C mod x^16: rs::locator's algorithm with run-time trip counts over polynomials in LDS (the
+// shared body, unrolled for register arrays, costs this kernel its occupancy).  Checked by the GPU tests alone.
 __device__ void pk_locator(PkLds& L, int i) {
     const uint8_t* S = &L.syn[i * PK_ROOTS];
-    uint8_t* C = L.lam[i];
-    uint8_t* B = L.bm_b[i];
-    uint8_t* T = L.bm_t[i];
+    uint8_t *C = L.lam[i], *B = L.bm_b[i], *T = L.bm_t[i];
     for (int k = 0; k <= PK_ROOTS; k++) { C[k] = (k == 0); B[k] = (k == 0); }
     int len = 0;
     for (int r = 1; r <= PK_ROOTS; r++) {
         uint8_t d = 0;
-        for (int k = 0; k < r; k++) d ^= gmul(L, C[k], S[r - 1 - k]);
+        for (int k = 0; k < r; k++) d ^= rs::mul(L, C[k], S[r - 1 - k]);
         if (d == 0) {
             for (int k = PK_ROOTS; k > 0; k--) B[k] = B[k - 1];
             B[0] = 0;
         } else {
             T[0] = C[0];
-            for (int k = 0; k < PK_ROOTS; k++) T[k + 1] = (uint8_t)(C[k + 1] ^ gmul(L, d, B[k]));
+            for (int k = 0; k < PK_ROOTS; k++) T[k + 1] = (uint8_t)(C[k + 1] ^ rs::mul(L, d, B[k]));
             if (2 * len <= r - 1) {
                 len = r - len;
-                for (int k = 0; k <= PK_ROOTS; k++) B[k] = gdiv(L, C[k], d);
+                for (int k = 0; k <= PK_ROOTS; k++) B[k] = rs::div(L, C[k], d);
             } else {
                 for (int k = PK_ROOTS; k > 0; k--) B[k] = B[k - 1];
                 B[0] = 0;
@@ -127,29 +88,30 @@ __device__ void pk_locator(PkLds& L, int i) {
     for (int k = 0; k <= PK_ROOTS; k++) if (C[k]) deg = k;
     for (int a = 0; a < PK_ROOTS; a++) {
         uint8_t t = 0;
-        for (int b = 0; b <= a; b++) t ^= gmul(L, S[a - b], C[b]);
+        for (int b = 0; b <= a; b++) t ^= rs::mul(L, S[a - b], C[b]);
         L.omega[i][a] = t;
     }
     L.rec[i] = deg;
 }
 
-// Chien search over candidates x0..x1 of row i and Forney's value of every root found (:387-410, :440-467)
+// Chien search over candidates x0..x1 of row i and Forney's value of every root found, with run-time trip counts likewise
 __device__ void pk_search(PkLds& L, int i, int x0, int x1) {
     const int deg = L.rec[i] & 0xFF;
     if (deg == 0) return;
     const uint8_t* C = L.lam[i];
+    const uint8_t* omega = L.omega[i];
     for (int x = x0; x <= x1; x++) {
         uint8_t v = 1;
         for (int k = 1; k <= deg; k++) if (C[k]) v ^= L.exp[(L.log[C[k]] + k * x) % 255];
         if (v) continue;
         const int slot = (atomicAdd(&L.rec[i], 0x100) >> 8) & (PK_ROOTS - 1);     // a locator of degree <= 16 has at most 16 roots
-        uint8_t num1 = 0, den = 0;
-        for (int a = 0; a < deg; a++) num1 ^= gmul(L, L.omega[i][a], gpow(L, a * x));
-        const uint8_t num2 = gpow(L, -x);                                           // first root alpha^0
-        const int top = ((deg < PK_ROOTS - 1) ? deg : (PK_ROOTS - 1)) & ~1;
-        for (int a = 0; a <= top; a += 2) den ^= gmul(L, C[a + 1], gpow(L, a * x));
         const int loc = x - 1;
-        const uint8_t val = (num1 != 0 && loc >= RS_PADDING) ? gdiv(L, gmul(L, num1, num2), den) : (uint8_t)0;
+        uint8_t num1 = 0, den = 0;
+        for (int a = 0; a < deg; a++) num1 ^= rs::mul(L, omega[a], rs::pow(L, a * x));
+        const uint8_t num2 = rs::pow(L, -x);                                        // first root alpha^0
+        const int top = ((deg < PK_ROOTS - 1) ? deg : (PK_ROOTS - 1)) & ~1;
+        for (int a = 0; a <= top; a += 2) den ^= rs::mul(L, C[a + 1], rs::pow(L, a * x));
+        const uint8_t val = (num1 != 0 && loc >= RS_PADDING) ? rs::div(L, rs::mul(L, num1, num2), den) : (uint8_t)0;
         L.fix[i][slot] = (uint16_t)(loc | (val << 8));
     }
 }
@@ -160,18 +122,8 @@ __device__ void pk_correct_rows(PkLds& L, int rd, int lane) {
         const int row = lane & 15, share = lane >> 4;
         uint32_t w[4] = {0, 0, 0, 0};
         if (row < RS_ROWS) {
-            for (int j = share * 51; j < share * 51 + 51; j++) {
-                const uint8_t cj = L.ring[ring_at(rd, row_symbol_offset(row, j))];
-                if (cj) {
-                    const int lc = L.log[cj], e = RS_MESSAGE_BYTES - 1 - j;
-                    int t = 0;                                                      // (r e) mod 255
-#pragma unroll
-                    for (int r = 0; r < PK_ROOTS; r++) {
-                        w[r >> 2] ^= (uint32_t)L.exp[lc + t] << (8 * (r & 3));
-                        t += e; if (t >= 255) t -= 255;
-                    }
-                }
-            }
+            for (int j = share * 51; j < share * 51 + 51; j++)
+                rs::syndrome_add<RS_MESSAGE_BYTES, PK_ROOTS>(L, L.ring[ring_at(rd, row_symbol_offset(row, j))], j, w);
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -180,7 +132,7 @@ __device__ void pk_correct_rows(PkLds& L, int rd, int lane) {
         }
         if (share == 0 && row < RS_ROWS) {
 #pragma unroll
-            for (int r = 0; r < PK_ROOTS; r++) L.syn[row * PK_ROOTS + r] = (uint8_t)(w[r >> 2] >> (8 * (r & 3)));
+            for (int r = 0; r < PK_ROOTS; r++) L.syn[row * PK_ROOTS + r] = rs::packed_byte<PK_ROOTS>(w, r);
         }
     }
     __syncthreads();
@@ -241,7 +193,7 @@ __device__ void pk_hand_out(PkLds& L, PkState& st, int limit, int corrected, PkO
         const int p = base + (lane >> 3), q = lane & 7;
         const bool mine = p < np;
         const int off = mine ? L.pk_off[p] : 0, len = mine ? (L.pk_off[p + 1] - off) : 0;
-        const uint16_t crc = crc_8lanes([&](int k) { return (uint32_t)L.ring[ring_at(rd, off + k)]; }, len - 2, L.crc_tab, q);
+        const uint16_t crc = crc_lanes([&](int k) { return (uint32_t)L.ring[ring_at(rd, off + k)]; }, len - 2, L.crc_tab, 3, q);
         if (mine && q == 7 && o.n_packets + p < o.max_records) {
             const uint8_t b0 = L.ring[ring_at(rd, off)], b1 = L.ring[ring_at(rd, off + 1)], b2 = L.ring[ring_at(rd, off + 2)];
             const uint16_t rx = (uint16_t)((L.ring[ring_at(rd, off + len - 2)] << 8) | L.ring[ring_at(rd, off + len - 1)]);
@@ -287,7 +239,7 @@ void packet_kernel(PkState* __restrict__ states, uint32_t* __restrict__ rings, c
         if (lane < 4) counts[4 * s + lane] = (lane == 1) ? -2 : 0;
         return;
     }
-    load_tables(L, lane);
+    load_gf_crc_tables(L, lane);
     PkState st = states[s];
     uint32_t* ring_hbm = rings + (size_t)s * (RING_BYTES / 4);
     for (int k = lane; k < RING_BYTES / 4; k += 64) reinterpret_cast<uint32_t*>(L.ring)[k] = ring_hbm[k];
@@ -363,33 +315,8 @@ void packet_kernel(PkState* __restrict__ states, uint32_t* __restrict__ rings, c
 }
 
 // ---- transmit ----
-// row j = logarithms of the sixteen coefficients of x^(203 - j) mod g(x), highest power first (= parity byte order), g(x) = prod (x + alpha^r),
-// r = 0..15; a zero coefficient is marked in `zero` (bit r)
-struct PkParityTab { alignas(16) uint8_t log_coef[RS_DATA_BYTES][PK_ROOTS]; uint16_t zero[RS_DATA_BYTES]; };
-constexpr PkParityTab make_pk_parity_tab() {
-    const GfTables gf = make_gf();
-    auto mul = [&](unsigned a, unsigned b) -> unsigned { return (a && b) ? gf.exp[gf.log[a] + gf.log[b]] : 0u; };
-    unsigned g[PK_ROOTS + 1] = {1};                          // ascending powers
-    for (int r = 0; r < PK_ROOTS; r++) {
-        for (int k = r + 1; k > 0; k--) g[k] = g[k - 1] ^ mul(g[k], gf.exp[r]);
-        g[0] = mul(g[0], gf.exp[r]);
-    }
-    PkParityTab t{};
-    unsigned rem[PK_ROOTS] = {};                             // x^e mod g(x), ascending powers; e = 16 first
-    for (int k = 0; k < PK_ROOTS; k++) rem[k] = g[k];
-    for (int j = RS_DATA_BYTES - 1; j >= 0; j--) {           // e = 203 - j
-        t.zero[j] = 0;
-        for (int r = 0; r < PK_ROOTS; r++) {
-            t.log_coef[j][r] = gf.log[rem[PK_ROOTS - 1 - r]];
-            if (rem[PK_ROOTS - 1 - r] == 0) t.zero[j] |= (uint16_t)(1u << r);
-        }
-        const unsigned top = rem[PK_ROOTS - 1];              // times x
-        for (int k = PK_ROOTS - 1; k > 0; k--) rem[k] = rem[k - 1] ^ mul(top, g[k]);
-        rem[0] = mul(top, g[0]);
-    }
-    return t;
-}
-static __constant__ PkParityTab PK_PARITY_TAB = make_pk_parity_tab();
+// the parity map of RS(204,188) (rs_core.h); some of its coefficients are zero, so the rows' marks are read
+static __constant__ rs::ParityTab<RS_DATA_BYTES, PK_ROOTS> PK_PARITY_TAB = rs::make_parity_tab<RS_DATA_BYTES, PK_ROOTS>();
 
 struct PkTxLds {
     alignas(16) uint8_t par_log[RS_DATA_BYTES][PK_ROOTS];
@@ -426,7 +353,7 @@ void packet_tx_kernel(const uint8_t* __restrict__ data, const unsigned long long
     else if (start % 24u) st = DABGPU_PACKET_TX_BAD_START;
     else if (end <= first || end - first > (uint32_t)MAX_FRAME_PACKETS || (size_t)end > table_stride) st = DABGPU_PACKET_TX_BAD_TABLE;
     if (fb == 0u) { if (lane == 0) status[item] = st; return; }
-    load_tables(L, lane);
+    load_gf_crc_tables(L, lane);
     for (int i = lane; i < RS_DATA_BYTES; i += 64) {
         *reinterpret_cast<uint4*>(L.par_log[i]) = *reinterpret_cast<const uint4*>(PK_PARITY_TAB.log_coef[i]);
         L.par_zero[i] = PK_PARITY_TAB.zero[i];
@@ -485,7 +412,7 @@ void packet_tx_kernel(const uint8_t* __restrict__ data, const unsigned long long
         const int p = base + (lane >> 3), q = lane & 7;
         const bool mine = p < cnt;
         const int off = mine ? (int)(L.ent[p].position - pos0) : 0, len = mine ? (int)L.ent[p].length : 0;
-        const uint16_t crc = crc_8lanes([&](int k) { return (uint32_t)L.frame[off + k]; }, len - 2, L.crc_tab, q);
+        const uint16_t crc = crc_lanes([&](int k) { return (uint32_t)L.frame[off + k]; }, len - 2, L.crc_tab, 3, q);
         if (mine && q == 7) { L.frame[off + len - 2] = (uint8_t)(crc >> 8); L.frame[off + len - 1] = (uint8_t)(crc & 0xFFu); }
     }
     __syncthreads();
@@ -499,9 +426,7 @@ void packet_tx_kernel(const uint8_t* __restrict__ data, const unsigned long long
                 const uint32_t ld = L.log[d], zero = L.par_zero[j];
                 const uint4 row = *reinterpret_cast<const uint4*>(L.par_log[j]);
                 const uint32_t rw[4] = {row.x, row.y, row.z, row.w};
-#pragma unroll
-                for (int r = 0; r < PK_ROOTS; r++)
-                    if (!((zero >> r) & 1u)) w[r >> 2] ^= (uint32_t)L.exp[ld + ((rw[r >> 2] >> (8 * (r & 3))) & 0xFFu)] << (8 * (r & 3));
+                rs::parity_add<PK_ROOTS>(L, ld, rw, zero, w);
             }
         }
 #pragma unroll

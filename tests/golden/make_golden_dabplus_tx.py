@@ -16,7 +16,7 @@ Which case fails first when ONE step of the encoder is wrong (every accepted cas
                    contributes nothing" branch
   interleaving     rand_48_13 (n_rs = 2, the smallest with a stride) and rand_72_6f (n_rs = 3, no power of two)
   unit CRC         ones_72 (start value and inversion), empty_24 and empty_72 -- the ONLY cases with zero-length units, whose CRC 0x0000 is a
-                   branch of its own in au_crc_lanes -- and onebyte_24, the ONLY case with one-byte units, the other special branch
+                   branch of its own in crc_lanes -- and onebyte_24, the ONLY case with one-byte units, the other special branch
   fire code        rand_24_51 and empty_24: six units put unit bytes and, in empty_24, CRC bytes inside bytes 2..10 that the fire code covers
   header packing   rand_24_3a (1 field, 4 pad bits), rand_24_6f (2 fields, none), rand_24_13 (3 fields, 4 pad bits), rand_24_51 (5 fields, 4 pad
                    bits); edge_4095 sets every bit of a field"""
