@@ -409,7 +409,8 @@ int dabgpu_ofdm_tuned_symbols_per_block(dabgpu_ctx* c, int format, size_t n_fram
 // first read by the second and third on the device.
 static int sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
                              const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
-                             size_t bits_frame_stride, int bits_layout, float* d_total_phase, const dabgpu_soft_cfg* soft, float* d_soft_scale, void* stream) {
+                             size_t bits_frame_stride, int bits_layout, float* d_total_phase, const dabgpu_soft_cfg* soft, float* d_soft_scale, void* stream,
+                             float* d_dqpsk = nullptr) {
     if (!c || !d_iq || !cfg || !d_states || !d_bits) { dabgpu_set_error("ofdm_sync_demod_frames: null argument"); return DABGPU_ERR_INVALID_ARG; }
     int st = dabgpu_check_bits_layout("ofdm_sync_demod_frames", bits_layout);
     if (st) return st;
@@ -432,7 +433,10 @@ static int sync_demod_frames(dabgpu_ctx* c, const float* d_iq, size_t n_streams,
     call.d_iq = d_iq; call.frame_stride_samples = stream_stride_samples;
     call.d_bits = d_bits; call.bits_frame_stride = bits_frame_stride; call.classed = bits_layout == DABGPU_BITS_MSC_CLASSED;
     call.d_cp_corr = corr; call.n_frames = (int)n_streams;
-    call.symbols_per_block = symbols_per_block > 0 ? symbols_per_block : demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
+    call.symbols_per_block = symbols_per_block > 0 ? symbols_per_block
+                             : d_dqpsk             ? dabgpu_host_small_batch_spb(n_streams)      /* display views: not tuned, as in ofdm_demod_any */
+                                                   : demod_cached_spb(c, n_streams, dabgpu_host_spb_variant(0, bits_layout, true));
+    call.d_dqpsk = d_dqpsk;
     call.d_sync = d_states; call.prs_offset = (int)prs_offset_samples;
     call.d_total_phase = d_total_phase; call.beta = cfg->fine_freq_update_beta;
     if (soft && soft->policy != DABGPU_SOFT_NORMALISED) { call.soft_policy = soft->policy; call.soft_level = soft->level; call.d_soft_scale = d_soft_scale; }
@@ -453,6 +457,20 @@ int dabgpu_ofdm_sync_demod_frames_soft(dabgpu_ctx* c, const float* d_iq, size_t 
     if (!soft) { dabgpu_set_error("ofdm_sync_demod_frames_soft: null soft-decision configuration"); return DABGPU_ERR_INVALID_ARG; }
     return sync_demod_frames(c, d_iq, n_streams, stream_stride_samples, prs_offset_samples, cfg, d_states, d_bits, d_cp_corr, symbols_per_block,
                              bits_frame_stride, bits_layout, d_total_phase, soft, d_soft_scale, stream);
+}
+
+// a synchronised diversity branch: the same call with the DQPSK view.  The planner pairs sync records with the display views already: the
+// views instantiation of the kernel runs, and the phase tail goes out as its own launch (views never fuse it).
+int dabgpu_ofdm_sync_demod_frames_branch(dabgpu_ctx* c, const float* d_iq, size_t n_streams, size_t stream_stride_samples, size_t prs_offset_samples,
+                                         const dabgpu_sync_cfg* cfg, dabgpu_sync_state* d_states, int8_t* d_bits, float* d_cp_corr, int symbols_per_block,
+                                         size_t bits_frame_stride, float* d_total_phase, const dabgpu_soft_cfg* soft, float* d_soft_scale, float* d_dqpsk,
+                                         void* stream) {
+    if (!soft) { dabgpu_set_error("ofdm_sync_demod_frames_branch: null soft-decision configuration"); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_dqpsk || ((uintptr_t)d_dqpsk & 15)) {
+        dabgpu_set_error("ofdm_sync_demod_frames_branch: d_dqpsk must be non-null and 16-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    return sync_demod_frames(c, d_iq, n_streams, stream_stride_samples, prs_offset_samples, cfg, d_states, d_bits, d_cp_corr, symbols_per_block,
+                             bits_frame_stride, DABGPU_BITS_NATURAL, d_total_phase, soft, d_soft_scale, stream, d_dqpsk);
 }
 
 // ---- one body per operation for every transmission mode: the mode I entry points are the mode forms with mode = 1 ----

@@ -2,6 +2,7 @@
 #include "dabgpu_host_logic.h"
 #include "packet_fec_core.h"
 #include "softbit_csi_core.h"
+#include "diversity_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -124,6 +125,31 @@ float dabgpu_soft_scale_host(const float* h_prs_useful, float level) {
     return dabgpu::sb_scale(level, dabgpu::sb_frame_power(h_prs_useful));
 }
 
+float dabgpu_diversity_scale_host(const float* k, const float* w, const int* valid, int n_branches, uint32_t* live_mask) {
+    if (live_mask) *live_mask = 0;
+    if (!k || n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) return 0.0f;
+    return dabgpu::dv_scale(k, w, valid, n_branches, live_mask);
+}
+
+int dabgpu_diversity_plan(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits, size_t bits_frame_stride,
+                          int bits_layout, int symbols_per_block, dabgpu_diversity_geometry* out) {
+    if (out) *out = dabgpu_diversity_geometry{};              // a refusal leaves no geometry behind
+    if (!h_branches || !out) { dabgpu_set_error("diversity_plan: null branch table or result"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_plan_diversity(n_branches, n_frames, bits_layout, symbols_per_block, bits_frame_stride, out);
+    if (st) return st;
+    *out = dabgpu_diversity_geometry{};
+    if (!d_bits || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("diversity_plan: d_bits must be non-null and 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    for (int b = 0; b < n_branches; b++) {
+        const dabgpu_diversity_branch& B = h_branches[b];
+        if (!B.d_dqpsk || !B.d_scale) { dabgpu_set_error("diversity_plan: branch %d has no products or no scales", b); return DABGPU_ERR_INVALID_ARG; }
+        if ((uintptr_t)B.d_dqpsk & 15) { dabgpu_set_error("diversity_plan: branch %d: d_dqpsk must be 16-byte aligned", b); return DABGPU_ERR_INVALID_ARG; }
+        if (((uintptr_t)B.d_scale | (uintptr_t)B.d_weight | (uintptr_t)B.d_sync) & 3) {
+            dabgpu_set_error("diversity_plan: branch %d: scales, weights and sync records must be 4-byte aligned", b); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    return dabgpu_host_plan_diversity(n_branches, n_frames, bits_layout, symbols_per_block, bits_frame_stride, out);
+}
+
 void dabgpu_stream_cfg_default(dabgpu_stream_cfg* c) {
     if (!c) return;
     c->signal_l1_update_beta = 0.95f; c->signal_l1_nb_samples = 100; c->signal_l1_nb_decimate = 5;      // ofdm_demodulator.h:25-29
@@ -180,6 +206,31 @@ int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg) {
         dabgpu_set_error("%s: no soft-decision policy %d", who, cfg->policy); return DABGPU_ERR_INVALID_ARG;
     }
     if (!dabgpu::sb_level_ok(cfg->level)) { dabgpu_set_error("%s: soft level %g outside [1, 127]", who, (double)cfg->level); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout, int symbols_per_block, size_t bits_frame_stride,
+                               dabgpu_diversity_geometry* out) {
+    *out = dabgpu_diversity_geometry{};
+    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
+        dabgpu_set_error("diversity_plan: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_frames > (size_t)(1 << 24)) { dabgpu_set_error("diversity_plan: n_frames too large"); return DABGPU_ERR_INVALID_ARG; }
+    if (bits_layout != DABGPU_BITS_NATURAL && bits_layout != DABGPU_BITS_MSC_CLASSED) {
+        dabgpu_set_error("diversity_plan: unknown bits_layout %d", bits_layout); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (symbols_per_block < 0 || symbols_per_block > 75) {
+        dabgpu_set_error("diversity_plan: symbols_per_block %d outside 0 .. 75", symbols_per_block); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (bits_frame_stride != 0 && (bits_frame_stride < DABGPU_NB_FRAME_BITS || (bits_frame_stride & 15))) {
+        dabgpu_set_error("diversity_plan: bits_frame_stride must be 0 or a multiple of 16 >= 230400"); return DABGPU_ERR_INVALID_ARG;
+    }
+    const uint32_t spb = symbols_per_block ? (uint32_t)symbols_per_block : (uint32_t)dabgpu_host_small_batch_spb(n_frames ? n_frames : 1);
+    out->symbols_per_block = spb;
+    out->runs_per_frame = (75u + spb - 1u) / spb;
+    out->grid = (uint32_t)n_frames * out->runs_per_frame;            // at most 2^24 x 75
+    out->threads = DABGPU_DIVERSITY_THREADS;
+    out->lds_bytes = DABGPU_DIVERSITY_LDS_BYTES;
     return DABGPU_OK;
 }
 

@@ -227,6 +227,15 @@ dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f);
 // a dabgpu_soft_cfg as an entry point receives it (`who` names it in the message): a policy that exists, a level in [1, 127]
 int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg);
 
+// ---- receive diversity planner (diversity.hip launches from it; include/dabgpu.h, dabgpu_diversity_plan) ----
+// the facts of a call that are not addresses: DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason.  symbols_per_block = 0
+// resolves as the demodulator's small-batch rule does (dabgpu_host_small_batch_spb): the combiner has no halo symbol, a shorter run costs
+// it one more set-up (scale, six de-interleave positions) and nothing else.
+#define DABGPU_DIVERSITY_THREADS 256u
+#define DABGPU_DIVERSITY_LDS_BYTES (2u * 3072u)        // two symbol rows of soft bits: scatter into one while the other is stored
+int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout, int symbols_per_block, size_t bits_frame_stride,
+                               dabgpu_diversity_geometry* out);
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

@@ -293,6 +293,7 @@ struct dabgpu_frame_session {
         // receiver pipeline only (pinned, allocated at first use): the frame's soft bits, a few scalars of the producer, display views
         int8_t* h_bits = nullptr; float* h_aux = nullptr; float* h_fft = nullptr; float* h_dq = nullptr;
         size_t h_fft_cap = 0, h_dq_cap = 0;
+        bool soft_csi = false;                                                   // receiver pipeline: the frame was demodulated under DABGPU_SOFT_CSI (its scale is in h_aux)
     } slots[R];
     std::mutex mu;
 };

@@ -1,0 +1,196 @@
+// diversity.hip -- receive diversity (include/dabgpu.h, "Receive diversity"): the DQPSK products of up to 8 branches of one ensemble, as
+// the demodulator's display view holds them ([75][1536] complex float per frame, carrier order), summed carrier by carrier, scaled by
+// the combined factor of the frame and quantised into the decoder's soft bits.  Arithmetic: diversity_core.h (every step; this file adds
+// none).  A stage of its own behind the demodulator: the demodulation kernel is untouched.
+//
+// One workgroup of 256 lanes per (frame, run of symbols).  The branch table travels by value as a kernel argument -- no host-to-device
+// copy, so a call is one launch and can be captured.  The workgroup forms the live mask and k once (wave-uniform: the table entries are
+// scalar loads, the arithmetic is the same in every lane).  Per symbol a lane reads, for every live branch, three 16-byte pieces of the
+// branch's row = two carriers each, lane after lane (coalesced, 12288 bytes per branch and symbol), accumulates the six carriers in
+// registers, scales and quantises, and scatters the twelve soft bits to their de-interleaved positions in an LDS row (inv_map16; in
+// class order the second position set, bit p of the symbol at (p mod 16) * 192 + p / 16).  192 lanes then store the 3072-byte row with
+// 16-byte stores.  Two LDS rows alternate, so a symbol costs one barrier.  HBM-bound: K * 921,600 bytes in, 230,400 out per frame.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "dabgpu_internal.h"
+#include "diversity_core.h"
+
+namespace dabgpu {
+
+typedef float dv_f4 __attribute__((ext_vector_type(4)));
+struct dv_table { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; };
+
+constexpr int DV_DATA_SYMBOLS = 75, DV_CARRIERS = 1536, DV_SYM_BITS = 3072, DV_FIC_SYMBOLS = 3, DV_CIF_SYMBOLS = 18, DV_CIF_BITS = 55296;
+constexpr int DV_ROW_PIECES = DV_CARRIERS / 2;              // 16-byte pieces of a branch's symbol row: 768 = 3 per lane
+static_assert(DV_ROW_PIECES == 3 * (int)DABGPU_DIVERSITY_THREADS && DV_SYM_BITS / 16 <= (int)DABGPU_DIVERSITY_THREADS, "three pieces per lane, 192 storing lanes");
+
+__global__ __launch_bounds__(DABGPU_DIVERSITY_THREADS)
+void diversity_combine_kernel(const dv_table tab, const int n_branches, const int n_frames, const int sym_per_run, const int runs_per_frame,
+                              int8_t* __restrict__ bits, const size_t bits_frame_stride, const int classed, const uint16_t* __restrict__ inv_map,
+                              float* __restrict__ soft_scale, uint32_t* __restrict__ live_mask)
+{
+    __shared__ __attribute__((aligned(16))) int8_t obuf[2][DV_SYM_BITS];
+    const int t = threadIdx.x;
+    const int frame = blockIdx.x / runs_per_frame, run = blockIdx.x % runs_per_frame;
+    if (frame >= n_frames) return;
+    const int row0 = run * sym_per_run, row1 = min(row0 + sym_per_run, DV_DATA_SYMBOLS);
+
+    // ---- the frame's live branches and its scale (uniform) ----
+    float w[DV_MAX_BRANCHES];
+    dv_scale_state st = dv_scale_begin();
+#pragma unroll
+    for (int b = 0; b < DV_MAX_BRANCHES; b++) {
+        w[b] = 1.0f;
+        if (b < n_branches) {
+            const dabgpu_diversity_branch B = tab.b[b];
+            const bool sync_ok = B.d_sync == nullptr || B.d_sync[frame].sync_valid != 0;
+            if (B.d_weight != nullptr) w[b] = B.d_weight[frame];
+            dv_scale_add(st, b, sync_ok, B.d_scale[frame], w[b]);
+        }
+    }
+    const float k = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(dv_scale_end(st))));
+    const uint32_t mask = __builtin_amdgcn_readfirstlane(st.mask);
+    if (run == 0 && t == 0) {
+        if (soft_scale != nullptr) soft_scale[frame] = k;
+        if (live_mask != nullptr) live_mask[frame] = mask;
+    }
+    // an erased frame is all zeros whatever its products hold (c * 0 is 0 or NaN, and NaN quantises to 0): nothing is read
+    const uint32_t read_mask = (k == 0.0f) ? 0u : mask;
+
+    // ---- de-interleave positions of this lane's six carriers: pieces t, t + 256, t + 512 = carriers 2 (t + 256 j), + 1 ----
+    int pos[6], posc[6];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        pos[2 * j] = inv_map[2 * (t + 256 * j)];
+        pos[2 * j + 1] = inv_map[2 * (t + 256 * j) + 1];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) posc[i] = (pos[i] & 15) * 192 + (pos[i] >> 4);        // class order; the second bit sits 96 further
+
+    int8_t* const out_frame = bits + (size_t)frame * bits_frame_stride;
+    for (int row = row0; row < row1; row++) {
+        dv_f4 acc[3] = {dv_f4{0.0f, 0.0f, 0.0f, 0.0f}, dv_f4{0.0f, 0.0f, 0.0f, 0.0f}, dv_f4{0.0f, 0.0f, 0.0f, 0.0f}};
+        bool first = true;
+#pragma unroll
+        for (int b = 0; b < DV_MAX_BRANCHES; b++) {
+            if ((read_mask >> b) & 1u) {                                              // (uniform)
+                const dv_f4* const p = reinterpret_cast<const dv_f4*>(tab.b[b].d_dqpsk) + ((size_t)frame * DV_DATA_SYMBOLS + (size_t)row) * DV_ROW_PIECES + t;
+                const dv_f4 v0 = p[0], v1 = p[256], v2 = p[512];
+                const dv_f4 v[3] = {v0, v1, v2};
+                const float wb = w[b];
+                if (first) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++)
+                        acc[j] = dv_f4{dv_sum_first(wb, v[j].x), dv_sum_first(wb, v[j].y), dv_sum_first(wb, v[j].z), dv_sum_first(wb, v[j].w)};
+                    first = false;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 3; j++)
+                        acc[j] = dv_f4{dv_sum_next(acc[j].x, wb, v[j].x), dv_sum_next(acc[j].y, wb, v[j].y), dv_sum_next(acc[j].z, wb, v[j].z),
+                                       dv_sum_next(acc[j].w, wb, v[j].w)};
+                }
+            }
+        }
+        // soft bits of the six carriers into this symbol's LDS row
+        int8_t* const ob = obuf[(row - row0) & 1];
+        const bool class_row = classed && row >= DV_FIC_SYMBOLS;                      // (uniform)
+        const int second = class_row ? 96 : DV_CARRIERS;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int p0 = class_row ? posc[2 * j] : pos[2 * j], p1 = class_row ? posc[2 * j + 1] : pos[2 * j + 1];
+            ob[p0] = (int8_t)sb_soft_bit(acc[j].x, k);
+            ob[p0 + second] = (int8_t)sb_soft_bit(-acc[j].y, k);
+            ob[p1] = (int8_t)sb_soft_bit(acc[j].z, k);
+            ob[p1 + second] = (int8_t)sb_soft_bit(-acc[j].w, k);
+        }
+        // the row is complete behind this barrier; the other LDS row takes the next symbol, and the barrier of that symbol orders this
+        // row's reads below before the scatter of the symbol after it
+        __syncthreads();
+        if (t < DV_SYM_BITS / 16) {
+            const uint4 o = reinterpret_cast<const uint4*>(ob)[t];
+            size_t off;
+            if (class_row) {                                                          // class t / 12, bytes 16 (t mod 12) .. + 15 of this symbol's 192
+                const int q = (row - DV_FIC_SYMBOLS) / DV_CIF_SYMBOLS, sy = (row - DV_FIC_SYMBOLS) % DV_CIF_SYMBOLS;
+                off = (size_t)(DV_FIC_SYMBOLS * DV_SYM_BITS + q * DV_CIF_BITS + (t / 12) * (DV_CIF_BITS / 16) + sy * (DV_SYM_BITS / 16) + 16 * (t % 12));
+            } else {
+                off = (size_t)(row * DV_SYM_BITS + 16 * t);
+            }
+            *reinterpret_cast<uint4*>(out_frame + off) = o;
+        }
+    }
+}
+
+}  // namespace dabgpu
+
+using namespace dabgpu;
+
+int dabgpu_diversity_combine_frames(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                                    size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale, uint32_t* d_live_mask,
+                                    void* stream) {
+    if (!c) { dabgpu_set_error("diversity_combine_frames: null context"); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu_diversity_geometry g;
+    int st = dabgpu_diversity_plan(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, &g);
+    if (st) return st;
+    if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
+        dabgpu_set_error("diversity_combine_frames: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_frames == 0) return DABGPU_OK;
+    DABGPU_BIND(c);
+    const dabgpu_mode_tables* t;
+    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames"))) return st;
+    dv_table tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int b = 0; b < n_branches; b++) tab.b[b] = h_branches[b];
+    hipLaunchKernelGGL(diversity_combine_kernel, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
+                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
+    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel launch");
+}
+
+int dabgpu_diversity_combine_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight, const int* h_valid,
+                                       int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale, uint32_t* h_live_mask) {
+    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
+        dabgpu_set_error("diversity_combine_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES); return DABGPU_ERR_INVALID_ARG;
+    }
+    int st = dabgpu_check_bits_layout("diversity_combine_host_sync", bits_layout);
+    if (st) return st;
+    // what the kernel will find live decides which products are uploaded: a branch the synchroniser refused travels as scale 0
+    float small[2 * DABGPU_DIVERSITY_MAX_BRANCHES];
+    for (int b = 0; b < n_branches; b++) {
+        const float w = h_weight ? h_weight[b] : 1.0f;
+        const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
+        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
+        small[b] = live ? h_scale[b] : 0.0f;
+        small[DABGPU_DIVERSITY_MAX_BRANCHES + b] = w;
+    }
+    DABGPU_BIND(c);
+    DABGPU_HOST_LOCK(c);
+    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
+    float *d_dq, *d_small; int8_t* d_bits;
+    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * DABGPU_DIVERSITY_MAX_BRANCHES + 2) * sizeof(float), (void**)&d_small))) return st;
+    hipStream_t s = c->stream;
+    dabgpu_diversity_branch br[DABGPU_DIVERSITY_MAX_BRANCHES];
+    for (int b = 0; b < n_branches; b++) {
+        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
+        br[b].d_scale = d_small + b;
+        br[b].d_weight = d_small + DABGPU_DIVERSITY_MAX_BRANCHES + b;
+        br[b].d_sync = nullptr;
+        if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
+    float* const d_k = d_small + 2 * DABGPU_DIVERSITY_MAX_BRANCHES;
+    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
+    if ((st = dabgpu_diversity_combine_frames(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, s))) return st;
+    uint32_t back[2];
+    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
+    if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
+    if (h_live_mask) *h_live_mask = back[1];
+    return DABGPU_OK;
+}

@@ -51,7 +51,7 @@ struct dabgpu_receiver {
     // the state and the scalars after a frame in ONE copy (the head), the head and the responses after a synchronisation
     void* d_rec = nullptr;
     dabgpu_sync_state* d_state = nullptr;    // (into d_rec)
-    float* d_small = nullptr;                // (into d_rec) [0] net offset of the frame, [2] sum of the cyclic-prefix angles
+    float* d_small = nullptr;                // (into d_rec) [0] net offset of the frame, [2] sum of the cyclic-prefix angles, [3] the frame's scale under DABGPU_SOFT_CSI
     float* d_corr = nullptr;
     float* d_imp = nullptr;                  // (into d_rec) impulse response | coarse frequency response, nb_fft floats each
     float* d_fft = nullptr; float* d_dq = nullptr;
@@ -311,9 +311,10 @@ static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float
     dabgpu_soft_cfg soft;
     soft.policy = (int)(soft_word >> 32);
     { const uint32_t lb = (uint32_t)soft_word; memcpy(&soft.level, &lb, sizeof(float)); }
-    st = (rx->mode == 1 && soft.policy != DABGPU_SOFT_NORMALISED)
+    sl->soft_csi = rx->mode == 1 && soft.policy != DABGPU_SOFT_NORMALISED;      // (dabgpu_receiver_frame_soft_scale)
+    st = sl->soft_csi
              ? dabgpu_ofdm_demod_frames_soft(c, rx->d_iq, DABGPU_IQ_RAW_F32L, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr,
-                                             want_dq ? rx->d_dq : nullptr, 0, 0, DABGPU_BITS_NATURAL, &soft, nullptr, a)
+                                             want_dq ? rx->d_dq : nullptr, 0, 0, DABGPU_BITS_NATURAL, &soft, rx->d_small + 3, a)
          : (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a)
                          : dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, 0, a);
     if (st || (st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
@@ -420,5 +421,19 @@ extern "C" int dabgpu_receiver_wait_frame(dabgpu_receiver* rx, uint64_t generati
     out->total_phase = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux) + REC_SMALL)[2];
     out->fft = sl->h_fft;
     out->dqpsk = sl->h_dq;
+    return DABGPU_OK;
+}
+
+// the scale k of a frame dabgpu_receiver_wait_frame has delivered (and whose slot has not been reused since): what the weighted policy scaled
+// its soft bits with; 0 for a frame demodulated under the normalised policy and for a banked receiver (whose kernel has that policy only)
+extern "C" int dabgpu_receiver_frame_soft_scale(dabgpu_receiver* rx, uint64_t generation, float* scale) {
+    if (!rx || !scale) { dabgpu_set_error("receiver_frame_soft_scale: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    *scale = 0.0f;
+    if (rx->member) return DABGPU_OK;
+    dabgpu_frame_session* s = rx->ses;
+    dabgpu_frame_session::slot* sl = &s->slots[generation % dabgpu_frame_session::R];
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (sl->gen != generation || !sl->h_aux) { dabgpu_set_error("receiver_frame_soft_scale: generation %llu is gone or was never submitted", (unsigned long long)generation); return DABGPU_ERR_NOT_READY; }
+    if (sl->soft_csi) *scale = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux) + REC_SMALL)[3];
     return DABGPU_OK;
 }

@@ -94,8 +94,11 @@ ABI_SYMBOLS = [
     "dabgpu_ber_plan", "dabgpu_ber_frames_layout", "dabgpu_ber_ring_layout", "dabgpu_ber_fib_group_host_sync", "dabgpu_ber_codeword_host_sync",
     "dabgpu_soft_cfg_default", "dabgpu_soft_scale_host", "dabgpu_ofdm_demod_frames_soft", "dabgpu_ofdm_sync_demod_frames_soft",
     "dabgpu_receiver_set_soft", "dabgpu_stream_bank_set_soft", "dabgpu_stream_bank_get_soft",
+    "dabgpu_diversity_plan", "dabgpu_diversity_combine_frames", "dabgpu_diversity_combine_host_sync", "dabgpu_diversity_scale_host",
+    "dabgpu_ofdm_sync_demod_frames_branch", "dabgpu_receiver_frame_soft_scale",
 ]
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
+DIVERSITY_MAX_BRANCHES = 8                # receive diversity (include/dabgpu.h)
 
 # channel model (include/dabgpu.h)
 CHANNEL_MAX_TAPS = 8
@@ -178,6 +181,17 @@ class BerGeometry(C.Structure):
     _fields_ = [("n_sub", C.c_uint32), ("codewords_per_ensemble", C.c_uint32), ("cif_bytes", C.c_uint32), ("n_sched", C.c_uint32),
                 ("sched_offset", C.c_uint32 * 65), ("max_kept_bits", C.c_uint32), ("lds_bytes", C.c_uint32), ("waves_per_block", C.c_uint32),
                 ("block_threads", C.c_uint32), ("grid", C.c_uint32)]
+
+
+class DiversityBranch(C.Structure):
+    """dabgpu_diversity_branch: device addresses of one branch's products, scales, weights (0: weight 1) and sync records (0: none)"""
+    _fields_ = [("d_dqpsk", C.c_void_p), ("d_scale", C.c_void_p), ("d_weight", C.c_void_p), ("d_sync", C.c_void_p)]
+
+
+class DiversityGeometry(C.Structure):
+    """dabgpu_diversity_geometry"""
+    _fields_ = [("symbols_per_block", C.c_uint32), ("runs_per_frame", C.c_uint32), ("grid", C.c_uint32), ("threads", C.c_uint32),
+                ("lds_bytes", C.c_uint32)]
 
 
 class ChannelStream(C.Structure):
@@ -369,6 +383,17 @@ def lib():
                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p]
         L.dabgpu_receiver_set_soft.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_receiver_frame_soft_scale.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_diversity_plan.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        L.dabgpu_diversity_combine_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_combine_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_scale_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_diversity_scale_host.restype = C.c_float
+        L.dabgpu_ofdm_sync_demod_frames_branch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p]
         L.dabgpu_viterbi_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
         L.dabgpu_fic_decode_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p]
@@ -765,6 +790,42 @@ class Context:
                                                        _ptr(states), _ptr(bits), _ptr(cp_corr), symbols_per_block, bits_frame_stride,
                                                        int(bits_layout), _ptr(total_phase), C.byref(soft), _ptr(soft_scale),
                                                        self._stream(stream)), "dabgpu_ofdm_sync_demod_frames_soft")
+
+    def ofdm_sync_demod_frames_branch(self, iq, n_streams, stream_stride_samples, prs_offset_samples, states, bits, soft, dqpsk, cfg=None,
+                                      cp_corr=None, symbols_per_block=0, bits_frame_stride=0, total_phase=None, soft_scale=None, stream=None):
+        """a synchronised diversity branch: ofdm_sync_demod_frames_soft (natural layout) that also writes the receivers' DQPSK products,
+        dqpsk [n_streams][75][1536] complex float on the device"""
+        cfg = cfg or sync_cfg_default()
+        check(lib().dabgpu_ofdm_sync_demod_frames_branch(self._h, _ptr(iq), n_streams, stream_stride_samples, prs_offset_samples, C.byref(cfg),
+                                                         _ptr(states), _ptr(bits), _ptr(cp_corr), symbols_per_block, bits_frame_stride,
+                                                         _ptr(total_phase), C.byref(soft), _ptr(soft_scale), _ptr(dqpsk),
+                                                         self._stream(stream)), "dabgpu_ofdm_sync_demod_frames_branch")
+
+    def diversity_combine(self, branches, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0, soft_scale=None,
+                          live_mask=None, stream=None):
+        """receive diversity: `branches` = up to 8 of (dqpsk, scale[, weight[, sync]]) device buffers (or DiversityBranch records) of the same
+        n_frames frames -> their combined soft bits in `bits`; soft_scale [n_frames] float32 and live_mask [n_frames] uint32 on the device
+        receive the scale used and the live branches.  One kernel launch, no copy: capturable"""
+        table = diversity_table(branches)
+        check(lib().dabgpu_diversity_combine_frames(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                                    int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), self._stream(stream)),
+              "dabgpu_diversity_combine_frames")
+
+    def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL):
+        """numpy convenience over dabgpu_diversity_combine_host_sync: one frame; dqpsk = a list of [75][1536] complex64 arrays (None where the
+        branch is not live); returns (bits [230400] int8, scale, live mask)"""
+        import numpy as np
+        n = len(dqpsk)
+        keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
+        ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
+        k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+        bits = np.empty(NB_FRAME_BITS, np.int8)
+        out_k, out_m = C.c_float(0.0), C.c_uint32(0)
+        check(lib().dabgpu_diversity_combine_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits), C.byref(out_k),
+                                                       C.byref(out_m)), "dabgpu_diversity_combine_host_sync")
+        return bits, out_k.value, out_m.value
 
     def ofdm_tune(self, raw, fmt, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, with_phase_tail=False, stream=None):
         """explicit (blocking) calibration of symbols_per_block = 0 for this call shape; returns the run length recorded"""
@@ -1816,6 +1877,39 @@ def soft_scale(prs_useful, level=64.0):
     if x.size != NB_FFT:
         raise ValueError("soft_scale: 2048 complex samples")
     return float(lib().dabgpu_soft_scale_host(_ptr(x), float(level)))
+
+
+def diversity_table(branches):
+    """a ctypes array of DiversityBranch from DiversityBranch records or (dqpsk, scale[, weight[, sync]]) tuples of buffers / addresses"""
+    rows = []
+    for b in branches:
+        if isinstance(b, DiversityBranch):
+            rows.append(b)
+            continue
+        f = list(b) + [None] * (4 - len(b))
+        rows.append(DiversityBranch(*[getattr(_ptr(x), "value", None) for x in f[:4]]))
+    return (DiversityBranch * len(rows))(*rows)
+
+
+def diversity_plan(branches, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0):
+    """dabgpu_diversity_plan (host only, nothing is dereferenced): the DiversityGeometry of a diversity_combine call with these arguments;
+    DabGpuError with the reason when refused"""
+    table = diversity_table(branches)
+    g = DiversityGeometry()
+    check(lib().dabgpu_diversity_plan(table if len(table) else None, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                      int(symbols_per_block), C.byref(g)), "dabgpu_diversity_plan")
+    return g
+
+
+def diversity_scale(scales, weights=None, valid=None):
+    """(k, live mask) of one frame from its branches' scales, weights (None: 1) and sync flags (None: valid): dabgpu_diversity_scale_host"""
+    import numpy as np
+    k = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(k.size)
+    v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(k.size)
+    mask = C.c_uint32(0)
+    out = lib().dabgpu_diversity_scale_host(_ptr(k), _ptr(w), _ptr(v), int(k.size), C.byref(mask))
+    return float(out), mask.value
 
 
 def subchannel_plan(sc):

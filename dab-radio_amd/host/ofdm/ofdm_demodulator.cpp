@@ -20,6 +20,7 @@
 // The ABI grows without a new version number: the entry point of the soft-decision policy is bound weakly, so that these classes still load
 // against a library of the same ABI version that predates it; asking for the policy there is an error.
 extern "C" int dabgpu_receiver_set_soft(dabgpu_receiver* rx, const dabgpu_soft_cfg* cfg) __attribute__((weak));
+extern "C" int dabgpu_receiver_frame_soft_scale(dabgpu_receiver* rx, uint64_t generation, float* scale) __attribute__((weak));
 
 namespace {
 int set_soft(dabgpu_receiver* rx, int policy, float level) {
@@ -522,6 +523,11 @@ void OFDM_Demod::DeliveryThread() {
                 if (rc != DABGPU_OK) fail("dabgpu_receiver_wait_frame", rc);
                 const double t1 = m_profile ? now_us() : 0.0;
                 m_freq_fine = fr.freq_fine;
+                {
+                    float k = 0.0f;                                              // (a library without the entry point has the normalised policy only)
+                    if (dabgpu_receiver_frame_soft_scale && dabgpu_receiver_frame_soft_scale(m_rx, it.gen, &k) != DABGPU_OK) k = 0.0f;
+                    m_soft_scale = k;
+                }
                 m_total_frames_read.fetch_add(1, std::memory_order_relaxed);
                 m_bits_ptr.store(fr.bits, std::memory_order_release);          // (fr.n_bits == m_bits_len: the frame length of the mode)
                 if (it.views) {

@@ -116,6 +116,9 @@ public:
     // bits only, so a member of the bank that is given DABGPU_SOFT_CSI before its first Process() call leaves the bank for a pipeline of its own
     // and stays private; after the first Process() call the call throws on a member.  Call it from the thread that calls Process().
     void SetSoftDecision(int policy, float level = 64.0f);
+    // the scale k of the newest delivered frame under DABGPU_SOFT_CSI (inside an On_OFDM_Frame observer: that frame's), 0 under the normalised
+    // policy: with GetFrameDataVec() what a receive-diversity branch hands to DAB_Diversity_Combiner (ofdm/dab_diversity_combiner.h)
+    float GetSoftScale() const { return m_soft_scale.load(std::memory_order_relaxed); }
     bool IsBankMember() const { return m_banked; }
 
 private:
@@ -168,6 +171,7 @@ private:
     std::atomic<int> m_total_frames_desync{0};
     std::atomic<float> m_freq_coarse{0.0f};
     std::atomic<float> m_freq_fine{0.0f};
+    std::atomic<float> m_soft_scale{0.0f};
     std::atomic<int> m_fine_time_offset{0};
     std::atomic<const viterbi_bit_t*> m_bits_ptr{nullptr};
     size_t m_bits_len = 0;                                   // (set once in the constructor: the frame length of the mode)

@@ -626,6 +626,9 @@ int dabgpu_receiver_submit_frame(dabgpu_receiver *rx, size_t frame_sample, float
 int dabgpu_receiver_submit_demod(dabgpu_receiver *rx, size_t frame_sample, float fine_freq_update_beta, int want_views, uint64_t *generation);
 int dabgpu_receiver_submit_decode(dabgpu_receiver *rx, uint64_t generation, int tie_rule);
 int dabgpu_receiver_wait_frame(dabgpu_receiver *rx, uint64_t generation, dabgpu_receiver_frame *out);
+/* the scale k (DABGPU_SOFT_CSI, dabgpu_soft_scale_host) of a frame dabgpu_receiver_wait_frame has delivered, while its result slot lasts;
+ * 0 for a frame demodulated under DABGPU_SOFT_NORMALISED and for a banked receiver.  Feeds receive diversity (see "Receive diversity"). */
+int dabgpu_receiver_frame_soft_scale(dabgpu_receiver *rx, uint64_t generation, float *scale);
 
 /* ==================================================================================================
  * Transmission modes II, III and IV (geometries of src/ofdm/dab_ofdm_params_ref.cpp:11-60).
@@ -1689,6 +1692,63 @@ int dabgpu_ber_ring_layout(dabgpu_ctx *ctx, const int8_t *d_hist, size_t n_ensem
 int dabgpu_ber_fib_group_host_sync(dabgpu_ctx *ctx, const int8_t *h_bits /*[2304]*/, const uint8_t *h_bytes /*[96]*/, dabgpu_ber_result *result);
 int dabgpu_ber_codeword_host_sync(dabgpu_ctx *ctx, const dabgpu_subchannel *sc, const int8_t *h_deinterleaved_bits, const uint8_t *h_bytes,
                                   dabgpu_ber_result *result);
+
+/* ------------------------------------------------------------------------------------------------
+ * Receive diversity: the DQPSK products of several receivers of one ensemble (antennas, tuners, sites) combined into one frame of soft
+ * bits.  A differential product carries no channel phase, so the products of K branches add coherently carrier by carrier, each
+ * weighted by the channel amplitude it keeps (the amplitude DABGPU_SOFT_CSI keeps: every branch is demodulated under that policy with
+ * one level L, its products are the demodulator's d_dqpsk view, its scale k_b the demodulator's d_soft_scale word).
+ *   live branch   its sync record, if given, has sync_valid != 0; its scale k_b is finite and > 0; its weight w_b (1 without a weight
+ *                 pointer) is finite and > 0.  The products of a branch that is not live are never read.
+ *   sum           over the live branches in branch order: the first contributes w_b * c, the next ones fmaf(w_b, c_b, sum), c = re d
+ *                 and im d.  w_b = 1 / (noise power of branch b) is the maximal-ratio weight; receivers of equal noise take 1.
+ *   scale         k = 1 / sum_live (w_b / k_b) = L 1536 / (2048 sum w_b P_b); 0 -- every soft bit of the frame 0 -- without a live
+ *                 branch, or where that sum is not a normal number.  One live branch of weight exactly 1: k = k_b, so that K = 1
+ *                 reproduces the demodulator's weighted soft bits bit for bit.
+ *   soft bits     -(c k) of the sum, c = re and -im, NaN -> 0, clamped to [-127, 127], truncated; frequency de-interleave and both
+ *                 layouts (DABGPU_BITS_NATURAL / DABGPU_BITS_MSC_CLASSED) exactly as the demodulator's.
+ * Arithmetic: csrc/diversity_core.h; the device equals dabgpu_diversity_scale_host and the tests' host model bit for bit.
+ */
+#define DABGPU_DIVERSITY_MAX_BRANCHES 8
+typedef struct {
+    const float *d_dqpsk;                 /* [n_frames][75][1536] complex float, 16-byte aligned */
+    const float *d_scale;                 /* [n_frames] k_b */
+    const float *d_weight;                /* [n_frames] w_b, may be NULL: weight 1 */
+    const dabgpu_sync_state *d_sync;      /* [n_frames], may be NULL: every frame of the branch was demodulated */
+} dabgpu_diversity_branch;
+typedef struct { uint32_t symbols_per_block, runs_per_frame, grid, threads, lds_bytes; } dabgpu_diversity_geometry;
+/* What a dabgpu_diversity_combine_frames call with these arguments launches; needs no device (no address is dereferenced, h_branches is
+ * a table in host memory).  DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null table or result; n_branches
+ * outside 1 .. DABGPU_DIVERSITY_MAX_BRANCHES; n_frames above 2^24; an unknown bits_layout; symbols_per_block outside 0 .. 75;
+ * bits_frame_stride neither 0 nor a multiple of 16 >= 230400; d_bits null or not 16-byte aligned; a branch without products or scales,
+ * products that are not 16-byte aligned, scales / weights / records that are not 4-byte aligned.  symbols_per_block = 0: the planner
+ * chooses (short runs for small batches, so that the launch still spreads over the chip); the result never depends on it. */
+int dabgpu_diversity_plan(const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames, const int8_t *d_bits,
+                          size_t bits_frame_stride, int bits_layout, int symbols_per_block, dabgpu_diversity_geometry *out);
+/* n_frames frames of n_branches branches -> d_bits + frame * bits_frame_stride (0 = 230400, packed; a larger stride writes into a
+ * history ring and leaves the bytes between the slots alone).  d_soft_scale [n_frames] (may be NULL): k as used; d_live_mask [n_frames]
+ * (may be NULL): bit b = branch b was live.  The table travels as a kernel argument: the call is ONE kernel launch, no copy, and may be
+ * captured in a HIP graph. */
+int dabgpu_diversity_combine_frames(dabgpu_ctx *ctx, const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames,
+                                    int8_t *d_bits, size_t bits_frame_stride, int bits_layout, int symbols_per_block,
+                                    float *d_soft_scale, uint32_t *d_live_mask, void *stream);
+/* One frame from and to host memory, synchronous, on the context's stream (the mirror layer's form): h_dqpsk[b] -> [75][1536] complex
+ * float of branch b (not read where the branch is not live; may then be NULL), h_scale [n_branches], h_weight [n_branches] or NULL,
+ * h_valid [n_branches] or NULL (0 = the branch's synchroniser refused the frame); h_bits [230400]; *h_soft_scale, *h_live_mask may be NULL */
+int dabgpu_diversity_combine_host_sync(dabgpu_ctx *ctx, const float *const *h_dqpsk, const float *h_scale, const float *h_weight,
+                                       const int *h_valid, int n_branches, int bits_layout, int8_t *h_bits, float *h_soft_scale,
+                                       uint32_t *h_live_mask);
+/* k of one frame on the host (w, valid may be NULL; *live_mask may be NULL); 0 for n_branches outside 1 .. 8 or a null k */
+float dabgpu_diversity_scale_host(const float *k, const float *w, const int *valid, int n_branches, uint32_t *live_mask);
+/* A synchronised diversity branch: dabgpu_ofdm_sync_demod_frames_soft in the natural layout that also writes the receivers' DQPSK
+ * products, d_dqpsk [n_streams][75][1536] complex float (required, 16-byte aligned).  Bits, records, scales, total phases and
+ * correlations are those of dabgpu_ofdm_sync_demod_frames_soft, bit for bit; the products those of dabgpu_ofdm_demod_frames_soft on the
+ * shifted frames.  A receiver with sync_valid = 0 leaves its products untouched as well: its branch is dead through d_sync. */
+int dabgpu_ofdm_sync_demod_frames_branch(dabgpu_ctx *ctx, const float *d_iq, size_t n_streams, size_t stream_stride_samples,
+                                         size_t prs_offset_samples, const dabgpu_sync_cfg *cfg, dabgpu_sync_state *d_states,
+                                         int8_t *d_bits, float *d_cp_corr, int symbols_per_block, size_t bits_frame_stride,
+                                         float *d_total_phase, const dabgpu_soft_cfg *soft, float *d_soft_scale, float *d_dqpsk,
+                                         void *stream);
 
 #ifdef __cplusplus
 }

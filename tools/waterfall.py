@@ -22,8 +22,13 @@ the true one, because a wrongly decoded code word is re-encoded into a neighbour
 With --soft-bits csi [--soft-level L] every receiver runs twice on the same received samples, with the reference's soft bits and with the
 channel-state weighted ones (dabgpu_ofdm_sync_demod_frames_soft), and every cell reads `normalised -> csi`; the output goes to
 profiles/tx/waterfall_csi.md (waterfall.md is not rewritten), a run with --doppler-hz being APPENDED to it.
+With --branches K (receive diversity; K = 2 .. 8) every receiver hears K realisations of the channel -- branch b of receiver e is channel stream
+b x streams + e, with a noise seed and (under --doppler-hz) a fading seed of its own -- through dabgpu_ofdm_sync_demod_frames_branch (weighted soft
+bits at --soft-level, DQPSK products, scale, sync record), and dabgpu_diversity_combine_frames puts the K branches' products into one frame of soft
+bits in the decoder's ring.  Every cell reads `single -> combined`: branch 0 decoded alone, and the combination.  The output goes to
+profiles/tx/waterfall_diversity.md.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
-                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber]"""
+                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]"""
 import argparse
 import math
 import os
@@ -53,7 +58,16 @@ def main():
     ap.add_argument("--ber", action="store_true")
     ap.add_argument("--soft-bits", default="normalised", choices=("normalised", "csi"))
     ap.add_argument("--soft-level", type=float, default=64.0)
+    ap.add_argument("--branches", type=int, default=1)
     a = ap.parse_args()
+    K = a.branches
+    if K != 1:
+        if K < 2 or K > 8:
+            ap.error("--branches takes 2 .. 8")
+        if a.clock_ppm is not None or a.adjacent_db is not None or a.ber or a.soft_bits == "csi":
+            ap.error("--branches is not available with --clock-ppm, --adjacent-db, --ber or --soft-bits (its branches are weighted already)")
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_diversity.md")
     csi = a.soft_bits == "csi"
     if csi and (a.clock_ppm is not None or a.adjacent_db is not None):
         ap.error("--soft-bits csi is not available with --clock-ppm or --adjacent-db")
@@ -74,6 +88,7 @@ def main():
     lo, hi, step = (float(v) for v in a.snr.split(":"))
     snrs = [lo + i * step for i in range(int(round((hi - lo) / step)) + 1)]
     E, F, H = a.streams, a.frames, 8
+    EC = E * K                                                                  # channel streams: K realisations per receiver
     ctx = dabgpu.Context(0)
     subs, owner = [], []
     for li, (_, lst) in enumerate(LEVELS):
@@ -116,7 +131,7 @@ def main():
     n_rows = 1 + (a.adjacent_sides if adjacent_db else 0)
     n_wide = n_out * ADJ_D + 72 * ADJ_D
     # with neighbours a receiver has n_rows block rows: the channel writes row 0, the others hold the clean transmission rolled
-    d_rows = torch.zeros((E, n_rows, n_rx, 2), dtype=torch.float32, device="cuda")
+    d_rows = torch.zeros((EC, n_rows, n_rx, 2), dtype=torch.float32, device="cuda")
     d_rx = d_rows[:, 0]
     for k, roll in enumerate(ADJ_ROLLS[2 - a.adjacent_sides:] if adjacent_db else ()):
         d_rows[:, 1 + k, :F * S] = torch.roll(d_iq, roll, 0)
@@ -138,6 +153,15 @@ def main():
                 f"{E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
                 f"`python tools/waterfall.py --soft-bits csi{fading_args}`; "
                 "the verdict line is the csi policy's.", ""]
+    if K > 1:
+        fading_args = "" if a.doppler_hz is None else f" --profile {a.profile or 'tu6'} --doppler-hz {a.doppler_hz:g}"
+        text = [f"# Receiver sensitivity with receive diversity: {K} branches per receiver", "",
+                f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  Every receiver hears {K} realisations of the channel (a noise seed"
+                f"{'' if a.doppler_hz is None else ' and a fading seed'} per branch): dabgpu_ofdm_sync_demod_frames_branch per branch (DABGPU_SOFT_CSI, level {a.soft_level:g}), "
+                f"dabgpu_diversity_combine_frames over the branches' products, scales and sync records into the decoder's ring.  Every cell is `single -> combined`: branch 0 "
+                f"decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), "
+                f"sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  SNR is per branch.  "
+                f"`python tools/waterfall.py --branches {K} --streams {E} --frames {F} --snr {a.snr}{fading_args}`; the verdict line is the combination's.", ""]
     verdicts = []
     profiles, fading =[(n, t, None, None) for n, t in PROFILES], None
     if adjacent_db:
@@ -156,9 +180,9 @@ def main():
     if a.doppler_hz is not None:
         prof = dabgpu.channel_profile(a.profile or "tu6")
         profiles = [(f"{a.profile or 'tu6'} (as recalled from COST 207), Doppler {a.doppler_hz:g} Hz, a fading seed per receiver, + noise", prof["taps"], None, None)]
-        fading = dabgpu.channel_fading_plan([dabgpu.channel_stream(taps=prof["taps"]) for _ in range(E)],
+        fading = dabgpu.channel_fading_plan([dabgpu.channel_stream(taps=prof["taps"]) for _ in range(EC)],
                                             [dabgpu.channel_fading_spec(a.doppler_hz / 2.048e6, 5000 + e, prof["kinds"], prof["rice_k"], prof["los_cos"])
-                                             for e in range(E)])
+                                             for e in range(EC)])
     for pname, taps, ppm, adb in profiles:
         comb = spl = None
         if adb is not None:
@@ -169,10 +193,10 @@ def main():
         rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
         rows, rows_ref, chan = [], [], []
-        ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(E)], fading=fading)
+        ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(EC)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
-            ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(E)])
+            ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(EC)])
             ch.seek(0)
             ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rows * n_rx * 8)
             d_use = d_rx
@@ -185,7 +209,43 @@ def main():
                 rs.seek(0)
                 rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
                 d_use = d_rs
-            for pol in policies:
+            if K > 1:
+                # receive diversity: ring 0 takes branch 0's own soft bits, ring 1 the combination of the K branches
+                soft = dabgpu.SoftCfg(dabgpu.SOFT_CSI, a.soft_level)
+                d_st = [torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda") for _ in range(K)]
+                dq = [torch.zeros((E, 75, 1536, 2), dtype=torch.float32, device="cuda") for _ in range(K)]
+                kb = [torch.zeros((E,), dtype=torch.float32, device="cuda") for _ in range(K)]
+                rings = [torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda") for _ in range(2)]
+                own = torch.zeros((E, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
+                d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
+                msc = torch.zeros((E, 4, nb), dtype=torch.uint8, device="cuda"); mres = torch.zeros((E * 4 * len(subs), 16), dtype=torch.uint8, device="cuda")
+                crc_ok, crc_n = [0, 0], [0, 0]
+                err = [[0] * len(LEVELS) for _ in range(2)]; tot = [[0] * len(LEVELS) for _ in range(2)]
+                for j in range(F):
+                    a0 = NULL + j * S - P_LEAD
+                    for b in range(K):
+                        sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
+                        seg = d_use[b * E:(b + 1) * E, a0:a0 + STRIDE]
+                        sl[:, :seg.shape[1]] = seg
+                        if b == 0:
+                            rings[0][:, j % H].zero_()                  # (a frame the synchroniser refuses stays an erasure, not a stale frame)
+                        ctx.ofdm_sync_demod_frames_branch(sl, E, STRIDE, P_LEAD, d_st[b], rings[0][:, j % H] if b == 0 else own, soft, dq[b],
+                                                          bits_frame_stride=H * dabgpu.NB_FRAME_BITS if b == 0 else 0, soft_scale=kb[b])
+                    ctx.diversity_combine([(dq[b], kb[b], None, d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                    for r in range(2):
+                        ctx.decode_frames(rings[r], E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
+                        torch.cuda.synchronize()
+                        masks = fres.cpu().numpy().view(rdt)["crc_ok_mask"].reshape(-1)
+                        crc_ok[r] += int(sum(bin(int(m) & 7).count("1") for m in masks)); crc_n[r] += 3 * masks.size
+                        for c in range(4):
+                            if 4 * j + c < 15:
+                                continue
+                            bad = (msc[:, c] != cifs[4 * j + c - 15][None, :])
+                            for i, (off, n) in enumerate(spans):
+                                err[r][owner[i]] += int(bad[:, off:off + n].sum()); tot[r][owner[i]] += E * n
+                rows_ref.append((snr, crc_ok[0] / crc_n[0], [e / t for e, t in zip(err[0], tot[0])], tot[0]))
+                rows.append((snr, crc_ok[1] / crc_n[1], [e / t for e, t in zip(err[1], tot[1])], tot[1]))
+            for pol in (policies if K == 1 else []):
                 d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
                 hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
                 d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
@@ -236,8 +296,8 @@ def main():
             rs.close()
         if comb is not None:
             comb.close(); spl.close()
-        if csi:
-            # both policies side by side: normalised -> csi in every cell
+        if csi or K > 1:
+            # both policies side by side: normalised -> csi in every cell (receive diversity: single -> combined)
             text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
             fmt = lambda r: f"{r:.2e}" if r else "0"
             text += [f"| {snr:g} | {ok0:.4f} -> {ok:.4f} | " + " | ".join(f"{fmt(r0)} -> {fmt(r)}" for r0, r in zip(ber0, ber)) + " |"
@@ -267,7 +327,7 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    append = bool(clock_ppm or adjacent_db or (csi and a.doppler_hz is not None))       # (the csi record: white noise and two paths first, the fading run behind them)
+    append = bool(clock_ppm or adjacent_db or ((csi or K > 1) and a.doppler_hz is not None))       # (the csi record: white noise and two paths first, the fading run behind them)
     open(a.out, "a" if append else "w").write(("\n" if append else "") + text)
     return 0 if all(verdicts) else 1
 
