@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <new>
 #include <vector>
 
 #include "dabgpu.h"
@@ -126,7 +127,7 @@ struct dabgpu_channel_bank : SignalBank {         // d_mem: position (16 bytes) 
     size_t n = 0;
     dabgpu_channel_geometry geom = {};
     dabgpu_channel_stream* d_params = nullptr;
-    dabgpu_channel_fading_stream* d_fading = nullptr;   // a fading bank's tables (its own allocation); null: a plain bank
+    DeviceBuffer<dabgpu_channel_fading_stream> d_fading;   // a fading bank's tables (its own allocation); empty: a plain bank
     std::vector<dabgpu_channel_stream> h_params;        // a fading bank keeps its parameters and tables on the host: _set_fading and
     std::vector<dabgpu_channel_fading_stream> h_tables; // _set_params check the one against the other (n_taps may grow past checked kinds)
 };
@@ -142,7 +143,7 @@ static int ch_launch(dabgpu_channel_bank* b, const float* d_in, size_t in_stride
     hipLaunchKernelGGL((channel_kernel<OUT, STAGE>), dim3(grid), dim3(256), lds, s, b->d_params, b->d_pos, in, in_stride, (int64_t)n_in, wrap, \
                        (uint32_t)n_out, tiles, static_cast<uint8_t*>(d_out), out_stride_bytes, u8_scale)
     if (b->d_fading)
-        ch_launch_fading(b->d_params, b->d_fading, b->d_pos, b->geom, tiles, grid, d_in, in_stride, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, s);
+        ch_launch_fading(b->d_params, b->d_fading.get(), b->d_pos, b->geom, tiles, grid, d_in, in_stride, n_in, wrap, n_out, d_out, out_format, out_stride_bytes, u8_scale, s);
     else if (out_format == DABGPU_IQ_RAW_F32L) { if (stage) CH_GO(DABGPU_IQ_RAW_F32L, true); else CH_GO(DABGPU_IQ_RAW_F32L, false); }
     else { if (stage) CH_GO(DABGPU_IQ_RAW_U8, true); else CH_GO(DABGPU_IQ_RAW_U8, false); }
 #undef CH_GO
@@ -158,7 +159,8 @@ static int ch_create(const char* who, dabgpu_ctx* c, size_t n_streams, const dab
     int st = dabgpu_host_channel_plan(h_params, n_streams, &g);
     if (st) return st;
     if (fading && (st = dabgpu_host_channel_fading_check(who, h_params, h_tables, n_streams))) return st;
-    dabgpu_channel_bank* b = new dabgpu_channel_bank;
+    dabgpu_channel_bank* b = new (std::nothrow) dabgpu_channel_bank;
+    if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n = n_streams; b->geom = fading ? dabgpu_host_channel_fading_geometry(g) : g;
     auto fail = [&](int status) { dabgpu_channel_bank_destroy(b); return status; };
     if ((st = dabgpu_bind_device(c))) return fail(st);
@@ -166,8 +168,8 @@ static int ch_create(const char* who, dabgpu_ctx* c, size_t n_streams, const dab
         b->h_params.assign(h_params, h_params + n_streams);
         b->h_tables.assign(h_tables, h_tables + n_streams);
         const size_t table_bytes = n_streams * sizeof(dabgpu_channel_fading_stream);
-        if ((st = dabgpu_check_hip(hipMalloc((void**)&b->d_fading, table_bytes), "hipMalloc(channel fading tables)"))) return fail(st);
-        if ((st = dabgpu_stage_h2d(c, b->d_fading, h_tables, table_bytes, c->stream))) return fail(st);
+        if ((st = b->d_fading.alloc(n_streams, "hipMalloc(channel fading tables)"))) return fail(st);
+        if ((st = dabgpu_stage_h2d(c, b->d_fading.get(), h_tables, table_bytes, c->stream))) return fail(st);
     }
     uint8_t* payload;
     if ((st = sb_alloc(b, n_streams * sizeof(dabgpu_channel_stream), "channel", &payload))) return fail(st);
@@ -196,12 +198,11 @@ int dabgpu_channel_bank_set_fading(dabgpu_channel_bank* b, const dabgpu_channel_
     if (st) return st;
     b->h_tables.assign(h_tables, h_tables + b->n);
     DABGPU_BIND(b->ctx);
-    return dabgpu_stage_h2d(b->ctx, b->d_fading, h_tables, b->n * sizeof(dabgpu_channel_fading_stream), (hipStream_t)stream);
+    return dabgpu_stage_h2d(b->ctx, b->d_fading.get(), h_tables, b->n * sizeof(dabgpu_channel_fading_stream), (hipStream_t)stream);
 }
 
 void dabgpu_channel_bank_destroy(dabgpu_channel_bank* b) {
-    if (!b) return;
-    if (sb_release(b) && b->d_fading) (void)hipFree(b->d_fading);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 

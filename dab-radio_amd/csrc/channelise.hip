@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <new>
 #include <vector>
 
 #include "dabgpu.h"
@@ -285,7 +286,8 @@ int dabgpu_channeliser_bank_create(dabgpu_ctx* c, const dabgpu_channeliser_chann
     dabgpu_channeliser_geometry g;
     int st = dabgpu_host_channeliser_plan("channeliser_bank_create", h_channels, n_channels, n_streams, start, design->decim, &g, nullptr);
     if (st) return st;
-    dabgpu_channeliser_bank* b = new dabgpu_channeliser_bank;
+    dabgpu_channeliser_bank* b = new (std::nothrow) dabgpu_channeliser_bank;
+    if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n_streams = n_streams; b->capacity = n_channels; b->decim = design->decim; b->geom = g;
     b->first_bytes = ((n_streams + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
     auto fail = [&](int status) { dabgpu_channeliser_bank_destroy(b); return status; };
@@ -317,8 +319,7 @@ int dabgpu_channeliser_bank_create(dabgpu_ctx* c, const dabgpu_channeliser_chann
 }
 
 void dabgpu_channeliser_bank_destroy(dabgpu_channeliser_bank* b) {
-    if (!b) return;
-    sb_release(b);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 

@@ -17,6 +17,7 @@
 // replays onto the following frames.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <new>
 
 #include "dab_encode_core.h"
 #include "dabgpu_internal.h"
@@ -117,35 +118,31 @@ struct dabgpu_tx_bank {
     size_t n_ens = 0;
     int n_sub = 0;
     dabgpu_tx_plan plan;
-    void* d_tables = nullptr;                   // one allocation: sub plans | schedules | gaps | energy-dispersal words
-    dabgpu_tx_sub_plan* d_subs = nullptr;
+    DeviceBuffer<> d_tables;                    // one allocation: sub plans | schedules | gaps | energy-dispersal words
+    dabgpu_tx_sub_plan* d_subs = nullptr;       // (these four into d_tables)
     dabgpu_tx_sched_entry* d_sched = nullptr;
     uint32_t* d_gaps = nullptr;
     uint32_t* d_prbs = nullptr;
-    uint32_t* d_ring = nullptr;                 // [n_ens][16][ring_slot_dwords] | frame counter
+    DeviceBuffer<uint32_t> d_ring;              // [n_ens][16][ring_slot_dwords] | frame counter
     size_t ring_bytes = 0;
-    uint32_t* d_count = nullptr;
+    uint32_t* d_count = nullptr;                // (into d_ring)
     size_t lds_bytes = 0;
     // grow-only buffers: [0] transmit_frames' frame bits; host forms: [1] FIB bodies, [2] payload, [3] frame bits / IQ out
-    void* buf[4] = {};
-    size_t buf_bytes[4] = {};
+    DeviceBuffer<> buf[4];
 };
 
-static int tx_buffer(dabgpu_tx_bank* b, int which, size_t bytes, void** out, hipStream_t user, const char* who) {
+// room for `bytes` in a grow-only buffer: never while `user` captures a graph (it would hold the old address), else behind a hipDeviceSynchronize
+static int tx_grow(DeviceBuffer<>& buf, size_t bytes, hipStream_t user, const char* who) {
     int st = DABGPU_OK;
-    if (b->buf_bytes[which] < bytes) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(user, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+    if (buf.needs(bytes)) {
+        if (dabgpu_stream_capturing(user)) {
             dabgpu_set_error("%s: this call needs more frame-bit scratch than the bank holds (%zu -> %zu bytes): run it once with this frame count before capturing",
-                             who, b->buf_bytes[which], bytes);
+                             who, buf.capacity(), bytes);
             return DABGPU_ERR_INVALID_ARG;
         }
-        (void)hipGetLastError();
-        if (b->buf[which]) { DABGPU_CK(hipDeviceSynchronize()); DABGPU_CK(hipFree(b->buf[which])); b->buf[which] = nullptr; b->buf_bytes[which] = 0; }
-        DABGPU_CK(hipMalloc(&b->buf[which], bytes));
-        b->buf_bytes[which] = bytes;
+        if (buf) DABGPU_CK(hipDeviceSynchronize());
+        st = buf.regrow(bytes, "hipMalloc(&b->buf[which], bytes)");
     }
-    *out = b->buf[which];
     return st;
 }
 
@@ -160,7 +157,7 @@ static int tx_bank_check(const dabgpu_tx_bank* b, const void* fib, const void* p
 static int tx_launch_encode(dabgpu_tx_bank* b, const uint8_t* d_fib, const uint8_t* d_payload, size_t F, uint8_t* d_bits, size_t stride, hipStream_t s) {
     const unsigned grid = (unsigned)(b->n_ens * (size_t)(b->n_sub + 1));
     hipLaunchKernelGGL(tx_encode_kernel, dim3(grid), dim3(256), b->lds_bytes, s, b->d_subs, b->d_sched, b->d_gaps, (int)(b->plan.gaps.size() / 2),
-                       b->d_prbs, b->n_sub, (uint32_t)F, b->plan.cif_in_bytes, b->plan.ring_slot_dwords, d_fib, d_payload, b->d_ring, b->d_count, d_bits,
+                       b->d_prbs, b->n_sub, (uint32_t)F, b->plan.cif_in_bytes, b->plan.ring_slot_dwords, d_fib, d_payload, b->d_ring.get(), b->d_count, d_bits,
                        stride);
     hipLaunchKernelGGL(tx_advance_kernel, dim3(1), dim3(1), 0, s, b->d_count, (uint32_t)F);
     return dabgpu_check_hip(hipGetLastError(), "tx_encode_kernel launch");
@@ -172,7 +169,8 @@ int dabgpu_tx_bank_create(dabgpu_ctx* c, size_t n_ens, const dabgpu_subchannel* 
     if (!c || !out) { dabgpu_set_error("tx_bank_create: null context / result"); return DABGPU_ERR_INVALID_ARG; }
     *out = nullptr;
     if (n_ens == 0 || n_ens > (size_t)(1 << 20)) { dabgpu_set_error("tx_bank_create: %zu ensembles (1..1048576 are accepted)", n_ens); return DABGPU_ERR_INVALID_ARG; }
-    dabgpu_tx_bank* b = new dabgpu_tx_bank;
+    dabgpu_tx_bank* b = new (std::nothrow) dabgpu_tx_bank;
+    if (!b) return DABGPU_ERR_HIP;
     int st = dabgpu_host_tx_plan(subs, n_sub, &b->plan);
     if (st) { delete b; return st; }
     b->ctx = c; b->n_ens = n_ens; b->n_sub = n_sub;
@@ -193,18 +191,17 @@ int dabgpu_tx_bank_create(dabgpu_ctx* c, size_t n_ens, const dabgpu_subchannel* 
     memcpy(img.data() + subs_bytes, P.sched.data(), sched_bytes);
     if (!P.gaps.empty()) memcpy(img.data() + subs_bytes + sched_bytes, P.gaps.data(), P.gaps.size() * 4);
     memcpy(img.data() + subs_bytes + sched_bytes + gaps_bytes, prbs.data(), prbs_bytes);
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_tables, img.size()), "hipMalloc(tx tables)"))) return fail(st);
-    unsigned char* t = static_cast<unsigned char*>(b->d_tables);
+    if ((st = b->d_tables.alloc(img.size(), "hipMalloc(tx tables)"))) return fail(st);
+    unsigned char* t = static_cast<unsigned char*>(b->d_tables.get());
     b->d_subs = reinterpret_cast<dabgpu_tx_sub_plan*>(t);
     b->d_sched = reinterpret_cast<dabgpu_tx_sched_entry*>(t + subs_bytes);
     b->d_gaps = reinterpret_cast<uint32_t*>(t + subs_bytes + sched_bytes);
     b->d_prbs = reinterpret_cast<uint32_t*>(t + subs_bytes + sched_bytes + gaps_bytes);
     b->ring_bytes = n_ens * 16 * (size_t)P.ring_slot_dwords * 4;
-    if ((st = dabgpu_check_hip(hipMalloc(reinterpret_cast<void**>(&b->d_ring), b->ring_bytes + 16), "hipMalloc(tx ring)"))) return fail(st);
-    b->d_count = b->d_ring + b->ring_bytes / 4;
-    void* bits;
-    if ((st = tx_buffer(b, 0, n_ens * TX_FRAME_BYTES, &bits, c->stream, "tx_bank_create"))) return fail(st);
-    if ((st = dabgpu_check_hip(hipMemcpyAsync(b->d_tables, img.data(), img.size(), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(tx tables)"))) return fail(st);
+    if ((st = b->d_ring.alloc(b->ring_bytes / 4 + 4, "hipMalloc(tx ring)"))) return fail(st);
+    b->d_count = b->d_ring.get() + b->ring_bytes / 4;
+    if ((st = tx_grow(b->buf[0], n_ens * TX_FRAME_BYTES, c->stream, "tx_bank_create"))) return fail(st);
+    if ((st = dabgpu_check_hip(hipMemcpyAsync(t, img.data(), img.size(), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(tx tables)"))) return fail(st);
     if ((st = dabgpu_tx_bank_reset(b, c->stream))) return fail(st);
     if ((st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(tx_bank_create)"))) return fail(st);
     *out = b;
@@ -212,20 +209,14 @@ int dabgpu_tx_bank_create(dabgpu_ctx* c, size_t n_ens, const dabgpu_subchannel* 
 }
 
 void dabgpu_tx_bank_destroy(dabgpu_tx_bank* b) {
-    if (!b) return;
-    if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
-        (void)hipDeviceSynchronize();
-        for (void* p : b->buf) if (p) (void)hipFree(p);
-        if (b->d_ring) (void)hipFree(b->d_ring);
-        if (b->d_tables) (void)hipFree(b->d_tables);
-    }
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 
 int dabgpu_tx_bank_reset(dabgpu_tx_bank* b, void* stream) {
     if (!b) { dabgpu_set_error("tx_bank_reset: null bank"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(b->ctx);
-    return dabgpu_check_hip(hipMemsetAsync(b->d_ring, 0, b->ring_bytes + 16, (hipStream_t)stream), "hipMemsetAsync(tx ring)");
+    return dabgpu_check_hip(hipMemsetAsync(b->d_ring.get(), 0, b->ring_bytes + 16, (hipStream_t)stream), "hipMemsetAsync(tx ring)");
 }
 
 int dabgpu_tx_bank_encode_frames(dabgpu_tx_bank* b, const uint8_t* d_fib, const uint8_t* d_payload, size_t F, uint8_t* d_bits, size_t frame_stride,
@@ -259,10 +250,10 @@ int dabgpu_tx_bank_transmit_frames(dabgpu_tx_bank* b, const uint8_t* d_fib, cons
     }
     DABGPU_BIND(b->ctx);
     hipStream_t s = (hipStream_t)stream;
-    void* bits;
-    if ((st = tx_buffer(b, 0, b->n_ens * F * TX_FRAME_BYTES, &bits, s, "tx_bank_transmit_frames"))) return st;
-    if ((st = tx_launch_encode(b, d_fib, d_payload, F, static_cast<uint8_t*>(bits), TX_FRAME_BYTES, s))) return st;
-    return dabgpu_launch_ofdm_mod(b->ctx, 1, static_cast<const uint8_t*>(bits), DABGPU_TX_PAYLOAD_FRAME_BITS, b->n_ens * F, nullptr, freq_norm, d_out,
+    if ((st = tx_grow(b->buf[0], b->n_ens * F * TX_FRAME_BYTES, s, "tx_bank_transmit_frames"))) return st;
+    uint8_t* bits = static_cast<uint8_t*>(b->buf[0].get());
+    if ((st = tx_launch_encode(b, d_fib, d_payload, F, bits, TX_FRAME_BYTES, s))) return st;
+    return dabgpu_launch_ofdm_mod(b->ctx, 1, bits, DABGPU_TX_PAYLOAD_FRAME_BITS, b->n_ens * F, nullptr, freq_norm, d_out,
                                   out_format, s);
 }
 
@@ -281,10 +272,10 @@ static int tx_host(dabgpu_tx_bank* b, const uint8_t* h_fib, const uint8_t* h_pay
     const size_t n = b->n_ens * F;
     const size_t fib_bytes = n * 360, pay_bytes = n * 4 * (size_t)b->plan.cif_in_bytes;
     const size_t out_bytes = iq ? n * DABGPU_NB_FRAME_SAMPLES * (out_format == DABGPU_IQ_RAW_F32L ? 8 : 2) : n * TX_FRAME_BYTES;
-    void *d_fib, *d_pay = nullptr, *d_out;
-    if ((st = tx_buffer(b, 1, fib_bytes, &d_fib, s, who))) return st;
-    if (pay_bytes && (st = tx_buffer(b, 2, pay_bytes, &d_pay, s, who))) return st;
-    if ((st = tx_buffer(b, 3, out_bytes, &d_out, s, who))) return st;
+    if ((st = tx_grow(b->buf[1], fib_bytes, s, who))) return st;
+    if (pay_bytes && (st = tx_grow(b->buf[2], pay_bytes, s, who))) return st;
+    if ((st = tx_grow(b->buf[3], out_bytes, s, who))) return st;
+    void *d_fib = b->buf[1].get(), *d_pay = pay_bytes ? b->buf[2].get() : nullptr, *d_out = b->buf[3].get();
     DABGPU_CK(hipMemcpyAsync(d_fib, h_fib, fib_bytes, hipMemcpyHostToDevice, s));
     if (pay_bytes) DABGPU_CK(hipMemcpyAsync(d_pay, h_payload, pay_bytes, hipMemcpyHostToDevice, s));
     st = iq ? dabgpu_tx_bank_transmit_frames(b, static_cast<uint8_t*>(d_fib), static_cast<uint8_t*>(d_pay), F, freq_norm, d_out, out_format, s)

@@ -38,6 +38,22 @@ int dabgpu_bind_device(const dabgpu_ctx* c) {
     return dabgpu_check_hip(hipSetDevice(c->device), "hipSetDevice");
 }
 
+bool dabgpu_destroy_begin(const void* obj, const dabgpu_ctx* c, bool device_wait) {
+    if (!obj || dabgpu_bind_device(c) != DABGPU_OK) return false;
+    if (device_wait) (void)hipDeviceSynchronize();
+    return true;
+}
+
+bool dabgpu_stream_capturing(hipStream_t s) {
+    if (!tl_capture.valid || tl_capture.stream != s) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        const bool is = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        if (!is) (void)hipGetLastError();
+        tl_capture = {s, true, is};
+    }
+    return tl_capture.capturing;
+}
+
 extern "C" {
 
 int dabgpu_device_count(void) {
@@ -646,16 +662,8 @@ int dabgpu_mode_tables_of(dabgpu_ctx* c, int mode, const dabgpu_mode_tables** ou
 //   * once a call of this context has run under capture, a slot that grows later (a larger eager call) PARKS its old buffer until
 //     dabgpu_destroy instead of freeing it: a replay of the earlier graph then still reads and writes memory the context owns.
 static int scratch_any(dabgpu_ctx* c, dabgpu_scratch_slot slot, size_t bytes, void** out, hipStream_t user, bool user_given) {
-    bool capturing = false;
-    if (user_given) {
-        if (!tl_capture.valid || tl_capture.stream != user) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            const bool is = hipStreamIsCapturing(user, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-            if (!is) (void)hipGetLastError();
-            tl_capture = {user, true, is};
-        }
-        if (tl_capture.capturing) { capturing = true; c->captured_once = true; }
-    }
+    const bool capturing = user_given && dabgpu_stream_capturing(user);
+    if (capturing) c->captured_once = true;
     if (c->scratch_bytes[slot] < bytes) {
         if (capturing) {
             dabgpu_set_error("this call needs more device scratch than the context holds (slot %d: %zu -> %zu bytes): run it once with these shapes before capturing", (int)slot,

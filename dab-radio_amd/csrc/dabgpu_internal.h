@@ -1,4 +1,5 @@
 // dabgpu_internal.h -- shared between the translation units of libdabgpu.so (not installed)
+// Who owns what the runtime hands out (device and pinned memory, events, streams), and who only points at it: device_mem.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -8,6 +9,7 @@
 
 #include "dabgpu.h"
 #include "dabgpu_host_logic.h"
+#include "device_mem.h"
 
 // device tables of one transmission mode, one allocation (starting at prs)
 struct dabgpu_mode_tables {
@@ -95,6 +97,12 @@ int dabgpu_check_hip(hipError_t e, const char* what);
 // thread of a one-process multi-GPU host starts on device 0) -- checked: a failed hipSetDevice is the call's status.
 int dabgpu_bind_device(const dabgpu_ctx* c);
 #define DABGPU_BIND(ctx) do { const int dabgpu_bind_st_ = dabgpu_bind_device(ctx); if (dabgpu_bind_st_) return dabgpu_bind_st_; } while (0)
+// The head of every destroy function, `delete obj` its end.  False: no object, or its device cannot be bound -- nothing is freed on a device that is
+// not current, the object is left alone whole (leaked, the error set).  True: the device is bound and idle (hipDeviceSynchronize); a destroy that
+// waits for less (its own streams, an event) passes device_wait = false and waits itself.
+bool dabgpu_destroy_begin(const void* obj, const dabgpu_ctx* c, bool device_wait = true);
+// is `s` capturing a graph?  Asked of the runtime once per entry point, thread and stream (dabgpu_bind_device drops the memo)
+bool dabgpu_stream_capturing(hipStream_t s);
 // flags of the events host threads wait on (receiver pipeline, frame session, receiver bank): DABGPU_EVENT_WAIT=block makes hipEventSynchronize SLEEP
 // instead of spinning -- threads that wait for the device then cost no CPU (a container's CPU quota is shared by every waiting thread of a many-receiver
 // process), at ~20-50 us more wake-up latency; =spin is the runtime's default.  Unset: `bank_default` for the receiver bank's events, spin elsewhere.
@@ -270,11 +278,11 @@ struct dabgpu_frame_session {
     static constexpr int H = 8, R = 8;
     dabgpu_ctx* ctx = nullptr;
     bool owns_ctx = true;                           // false: a result store of a receiver-bank member (receiver_bank.hip): no history, no stream of its own
-    int8_t* d_hist = nullptr;                       // [H][230400]
+    dabgpu::DeviceBuffer<int8_t> d_hist;            // [H][230400]
     // one device block per session, one pinned block per result slot: [4][96] FIB bytes | [4] FIC results | [4][n_sub] MSC results |
     // [4][cif_out] sub-channel bytes -- a frame's results reach the host in ONE copy (they were four; each is an operation on the stream
     // between two trellis launches)
-    uint8_t* d_block = nullptr; size_t block_bytes = 0;
+    dabgpu::DeviceBuffer<uint8_t> d_block;
     uint8_t* d_fib = nullptr; dabgpu_codeword_result* d_fres = nullptr;       // (into d_block)
     uint8_t* d_msc = nullptr; dabgpu_codeword_result* d_mres = nullptr;
     std::vector<dabgpu_subchannel> subs;
@@ -285,14 +293,13 @@ struct dabgpu_frame_session {
     struct slot {
         uint64_t gen = ~0ull; bool fic = false, pending = false;
         std::vector<dabgpu_subchannel> subs; std::vector<uint32_t> sub_off, sub_n; uint32_t cif_out = 0;
-        uint8_t* h_block = nullptr; size_t h_block_cap = 0;                      // pinned, laid out like the session's d_block
+        dabgpu::PinnedBuffer<uint8_t> h_block;                                   // laid out like the session's d_block
         uint8_t* h_fib = nullptr; dabgpu_codeword_result* h_fres = nullptr;      // (into h_block) [4][96], [4]
         uint8_t* h_msc = nullptr; dabgpu_codeword_result* h_mres = nullptr;      // (into h_block) [4][cif_out], [4][n_sub]
-        hipEvent_t done = nullptr;
-        hipEvent_t ev_ready = nullptr, ev_copied = nullptr;                    // receiver pipeline: frame demodulated / its host copies made (producer stream)
+        dabgpu::Event done;
+        dabgpu::Event ev_ready, ev_copied;                                     // receiver pipeline: frame demodulated / its host copies made (producer stream)
         // receiver pipeline only (pinned, allocated at first use): the frame's soft bits, a few scalars of the producer, display views
-        int8_t* h_bits = nullptr; float* h_aux = nullptr; float* h_fft = nullptr; float* h_dq = nullptr;
-        size_t h_fft_cap = 0, h_dq_cap = 0;
+        dabgpu::PinnedBuffer<int8_t> h_bits; dabgpu::PinnedBuffer<float> h_aux, h_fft, h_dq;
         bool soft_csi = false;                                                   // receiver pipeline: the frame was demodulated under DABGPU_SOFT_CSI (its scale is in h_aux)
     } slots[R];
     std::mutex mu;

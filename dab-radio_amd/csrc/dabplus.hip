@@ -308,21 +308,17 @@ using namespace dabgpu;
 struct dabgpu_dabplus_bank {
     dabgpu_ctx* ctx = nullptr;
     size_t n = 0;
-    DpState* d_states = nullptr;
-    uint8_t* d_acc = nullptr;
+    DeviceBuffer<DpState> d_states;
+    DeviceBuffer<uint8_t> d_acc;
     // single-stream host-buffer path
-    uint8_t* d_frame = nullptr; unsigned long long* d_off = nullptr; uint32_t* d_n = nullptr;
-    uint8_t* d_sf = nullptr; dabgpu_superframe_result* d_res = nullptr; int32_t* d_counts = nullptr;   // d_counts [4]
-    std::vector<void*> allocs;
+    DeviceBuffer<uint8_t> d_frame; DeviceBuffer<unsigned long long> d_off; DeviceBuffer<uint32_t> d_n;
+    DeviceBuffer<uint8_t> d_sf; DeviceBuffer<dabgpu_superframe_result> d_res; DeviceBuffer<int32_t> d_counts;   // d_counts [4]
 };
 
 extern "C" {
 
 void dabgpu_dabplus_bank_destroy(dabgpu_dabplus_bank* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : b->allocs) (void)hipFree(p);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 
@@ -331,32 +327,28 @@ int dabgpu_dabplus_bank_reset(dabgpu_dabplus_bank* b, void* stream) {
     DABGPU_BIND(b->ctx);
     // AAC_Frame_Processor's constructor state (:121-125): WAIT_FRAME_START, nothing collected, unsynchronised
     std::vector<DpState> init(b->n, DpState{1, 0, 0, 0, 0});
-    int st = dabgpu_check_hip(hipMemcpyAsync(b->d_states, init.data(), b->n * sizeof(DpState), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync");
+    int st = dabgpu_check_hip(hipMemcpyAsync(b->d_states.get(), init.data(), b->n * sizeof(DpState), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync");
     if (st) return st;
     return dabgpu_check_hip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
 }
 
 int dabgpu_dabplus_bank_create(dabgpu_ctx* c, size_t n_streams, dabgpu_dabplus_bank** out) {
     if (!c || !out || n_streams == 0 || n_streams > (size_t)(1 << 22)) { dabgpu_set_error("dabplus_bank_create: invalid argument"); return DABGPU_ERR_INVALID_ARG; }
+    *out = nullptr;
     DABGPU_BIND(c);
     dabgpu_dabplus_bank* b = new (std::nothrow) dabgpu_dabplus_bank();
     if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n = n_streams;
-    int st = DABGPU_OK;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (st) return;
-        st = dabgpu_check_hip(hipMalloc(p, bytes), "hipMalloc(dabplus bank)");
-        if (!st) b->allocs.push_back(*p);
-    };
-    alloc((void**)&b->d_states, n_streams * sizeof(DpState));
-    alloc((void**)&b->d_acc, n_streams * (size_t)DP_MAX_SF);
-    alloc((void**)&b->d_frame, DP_MAX_FRAME_BYTES);
-    alloc((void**)&b->d_off, sizeof(unsigned long long));
-    alloc((void**)&b->d_n, sizeof(uint32_t));
-    alloc((void**)&b->d_sf, DP_MAX_SF);
-    alloc((void**)&b->d_res, sizeof(dabgpu_superframe_result));
-    alloc((void**)&b->d_counts, 4 * sizeof(int32_t));
-    if (!st) st = dabgpu_check_hip(hipMemsetAsync(b->d_off, 0, sizeof(unsigned long long), c->stream), "hipMemsetAsync");
+    const char* what = "hipMalloc(dabplus bank)";
+    int st = b->d_states.alloc(n_streams, what);
+    if (!st) st = b->d_acc.alloc(n_streams * (size_t)DP_MAX_SF, what);
+    if (!st) st = b->d_frame.alloc(DP_MAX_FRAME_BYTES, what);
+    if (!st) st = b->d_off.alloc(1, what);
+    if (!st) st = b->d_n.alloc(1, what);
+    if (!st) st = b->d_sf.alloc(DP_MAX_SF, what);
+    if (!st) st = b->d_res.alloc(1, what);
+    if (!st) st = b->d_counts.alloc(4, what);
+    if (!st) st = dabgpu_check_hip(hipMemsetAsync(b->d_off.get(), 0, sizeof(unsigned long long), c->stream), "hipMemsetAsync");
     if (!st) st = dabgpu_dabplus_bank_reset(b, c->stream);
     if (st) { dabgpu_dabplus_bank_destroy(b); return st; }
     *out = b;
@@ -383,8 +375,8 @@ int dabgpu_dabplus_bank_process_masked(dabgpu_dabplus_bank* b, const uint8_t* d_
         dabgpu_set_error("dabplus_bank_process: max_superframes must be at least ceil(n_frames / 5)"); return DABGPU_ERR_INVALID_ARG;
     }
     DABGPU_BIND(b->ctx);
-    hipLaunchKernelGGL(dabplus_kernel, dim3((unsigned)b->n), dim3(64), 0, (hipStream_t)stream, b->d_states, d_frames,
-                       reinterpret_cast<const unsigned long long*>(d_stream_offsets), frame_stride_bytes, d_frame_bytes, n_frames, b->d_acc,
+    hipLaunchKernelGGL(dabplus_kernel, dim3((unsigned)b->n), dim3(64), 0, (hipStream_t)stream, b->d_states.get(), d_frames,
+                       reinterpret_cast<const unsigned long long*>(d_stream_offsets), frame_stride_bytes, d_frame_bytes, n_frames, b->d_acc.get(),
                        d_superframes, superframe_stride_bytes, d_results, max_superframes, d_counts, (int)b->n, d_active, streams_per_flag);
     return dabgpu_check_hip(hipGetLastError(), "dabplus_kernel launch");
 }
@@ -406,19 +398,19 @@ int dabgpu_dabplus_process_frame_host_sync(dabgpu_dabplus_bank* b, const uint8_t
     DABGPU_HOST_LOCK(b->ctx);
     hipStream_t s = c->stream;
     int st;
-    DABGPU_CK(hipMemcpyAsync(b->d_frame, h_frame, n_bytes, hipMemcpyHostToDevice, s));
-    DABGPU_CK(hipMemcpyAsync(b->d_n, &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_dabplus_bank_process(b, b->d_frame, reinterpret_cast<const uint64_t*>(b->d_off), 0, b->d_n, 1, b->d_sf, DP_MAX_SF, b->d_res, 1,
-                                          b->d_counts, s))) return st;
+    DABGPU_CK(hipMemcpyAsync(b->d_frame.get(), h_frame, n_bytes, hipMemcpyHostToDevice, s));
+    DABGPU_CK(hipMemcpyAsync(b->d_n.get(), &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if ((st = dabgpu_dabplus_bank_process(b, b->d_frame.get(), reinterpret_cast<const uint64_t*>(b->d_off.get()), 0, b->d_n.get(), 1, b->d_sf.get(), DP_MAX_SF, b->d_res.get(), 1,
+                                          b->d_counts.get(), s))) return st;
     int32_t counts[4];
-    DABGPU_CK(hipMemcpyAsync(counts, b->d_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(counts, b->d_counts.get(), sizeof(counts), hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipStreamSynchronize(s));
     *superframe_done = counts[0];
     *firecode_wait_failed = counts[1];
     if (firecode_wait_rx_calc) *firecode_wait_rx_calc = (uint32_t)counts[2];
     if (counts[0]) {
-        DABGPU_CK(hipMemcpyAsync(h_result, b->d_res, sizeof(dabgpu_superframe_result), hipMemcpyDeviceToHost, s));
-        DABGPU_CK(hipMemcpyAsync(h_superframe, b->d_sf, 5 * (size_t)n_bytes, hipMemcpyDeviceToHost, s));
+        DABGPU_CK(hipMemcpyAsync(h_result, b->d_res.get(), sizeof(dabgpu_superframe_result), hipMemcpyDeviceToHost, s));
+        DABGPU_CK(hipMemcpyAsync(h_superframe, b->d_sf.get(), 5 * (size_t)n_bytes, hipMemcpyDeviceToHost, s));
         DABGPU_CK(hipStreamSynchronize(s));
     }
     return DABGPU_OK;

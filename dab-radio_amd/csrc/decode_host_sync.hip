@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
+#include <new>
 #include <vector>
 
 #include "dabgpu.h"
@@ -106,8 +107,8 @@ struct dabgpu_msc_stream {
     dabgpu_ctx* ctx;
     dabgpu_subchannel sc;
     dabgpu_cw_desc proto;       // plan with ring geometry, d_src = ring base
-    int8_t* d_ring;
-    int8_t* d_logical;
+    dabgpu::DeviceBuffer<int8_t> d_ring;
+    dabgpu::DeviceBuffer<int8_t> d_logical;
     int n_bits;
     int n_out_bytes;
     int next_slot;
@@ -115,7 +116,7 @@ struct dabgpu_msc_stream {
     // Consume (push_cif) only files the CIF in this page-locked twin of the ring; a slot crosses to the device when a call that reads the
     // device ring comes (deinterleave_sync / decode_sync).  A decoder whose results come from its demodulator's frame session
     // (dab-radio_amd/host/dab/dabgpu_frame_batcher.h) never reads its own ring: its DecodeCIF then costs a 3 KB host copy, not a DMA.
-    int8_t* h_ring;
+    dabgpu::PinnedBuffer<int8_t> h_ring;
     uint32_t dirty;             // bit k: slot k of h_ring is newer than the device's
 };
 
@@ -124,7 +125,7 @@ struct dabgpu_msc_stream {
 static int msc_stream_flush(dabgpu_msc_stream* s) {
     for (int k = 0; k < 16 && s->dirty; k++) {
         if (!(s->dirty >> k & 1u)) continue;
-        const int st = dabgpu_check_hip(hipMemcpyAsync(s->d_ring + (size_t)k * s->n_bits, s->h_ring + (size_t)k * s->n_bits, (size_t)s->n_bits,
+        const int st = dabgpu_check_hip(hipMemcpyAsync(s->d_ring.get() + (size_t)k * s->n_bits, s->h_ring.get() + (size_t)k * s->n_bits, (size_t)s->n_bits,
                                                        hipMemcpyHostToDevice, s->ctx->stream), "hipMemcpyAsync(msc stream ring)");
         if (st) return st;
         s->dirty &= ~(1u << k);
@@ -143,15 +144,16 @@ extern "C" int dabgpu_msc_stream_create(dabgpu_ctx* c, const dabgpu_subchannel* 
     }
     if (dabgpu_subchannel_plan(sc, pi, lx, &nb) < 0) { dabgpu_set_error("msc_stream_create: invalid protection profile"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(c);
-    dabgpu_msc_stream* s = new dabgpu_msc_stream();
+    dabgpu_msc_stream* s = new (std::nothrow) dabgpu_msc_stream();
+    if (!s) return DABGPU_ERR_HIP;
     s->ctx = c; s->sc = *sc; s->n_bits = sc->length * 64; s->n_out_bytes = nb; s->next_slot = 0; s->stored = 0;
-    s->d_ring = nullptr; s->d_logical = nullptr; s->h_ring = nullptr; s->dirty = 0;
-    int st = dabgpu_check_hip(hipMalloc((void**)&s->d_ring, (size_t)16 * s->n_bits), "hipMalloc(ring)");
-    if (!st) st = dabgpu_check_hip(hipHostMalloc((void**)&s->h_ring, (size_t)16 * s->n_bits, hipHostMallocDefault), "hipHostMalloc(ring)");
-    if (!st) st = dabgpu_check_hip(hipMalloc((void**)&s->d_logical, (size_t)s->n_bits), "hipMalloc(logical)");
+    s->dirty = 0;
+    int st = s->d_ring.alloc((size_t)16 * s->n_bits, "hipMalloc(ring)");
+    if (!st) st = s->h_ring.alloc((size_t)16 * s->n_bits, "hipHostMalloc(ring)");
+    if (!st) st = s->d_logical.alloc((size_t)s->n_bits, "hipMalloc(logical)");
     // on the context's own stream and waited for: hipMemset runs on the NULL stream, with which a hipStreamNonBlocking stream does not synchronise -- a
     // ring uploaded right after creation (MSC_Decoder creates its stream on its first call-by-call decode) was overwritten by the late zeros
-    if (!st) st = dabgpu_check_hip(hipMemsetAsync(s->d_ring, 0, (size_t)16 * s->n_bits, c->stream), "hipMemsetAsync(ring)");
+    if (!st) st = dabgpu_check_hip(hipMemsetAsync(s->d_ring.get(), 0, (size_t)16 * s->n_bits, c->stream), "hipMemsetAsync(ring)");
     if (!st) st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(ring)");
     if (st) { dabgpu_msc_stream_destroy(s); return st; }
     dabgpu_cw_desc& D = s->proto;
@@ -159,18 +161,15 @@ extern "C" int dabgpu_msc_stream_create(dabgpu_ctx* c, const dabgpu_subchannel* 
     const uint32_t seg_pi[4] = {(uint32_t)pi[0], (uint32_t)pi[1], (uint32_t)pi[2], (uint32_t)pi[3]};
     const uint32_t seg_steps[4] = {32u * (uint32_t)lx[0], 32u * (uint32_t)lx[1], 32u * (uint32_t)lx[2], 32u * (uint32_t)lx[3]};
     dabgpu_cw_set_segments(&D, seg_pi, seg_steps);
-    D.d_src = (uint64_t)(uintptr_t)s->d_ring;
+    D.d_src = (uint64_t)(uintptr_t)s->d_ring.get();
     D.n_slots = 16; D.cifs_per_frame = 1; D.frame_stride = (uint32_t)s->n_bits; D.cif_stride = 0;
     *out = s;
     return DABGPU_OK;
 }
 
 extern "C" void dabgpu_msc_stream_destroy(dabgpu_msc_stream* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->ctx->device);
-    if (s->d_ring) (void)hipFree(s->d_ring);
-    if (s->d_logical) (void)hipFree(s->d_logical);
-    if (s->h_ring) { (void)hipStreamSynchronize(s->ctx->stream); (void)hipHostFree(s->h_ring); }
+    if (!dabgpu_destroy_begin(s, s ? s->ctx : nullptr, false)) return;
+    if (s->h_ring) (void)hipStreamSynchronize(s->ctx->stream);         // (an upload of the ring's twin may be in flight)
     delete s;
 }
 
@@ -178,7 +177,7 @@ extern "C" int dabgpu_msc_stream_push_cif(dabgpu_msc_stream* s, const int8_t* h_
     if (!s || !h_bits) return DABGPU_ERR_INVALID_ARG;
     DABGPU_HOST_LOCK(s->ctx);
     // copied here and now: the caller's span is only valid during DecodeCIF (SURVEY 8b ownership)
-    memcpy(s->h_ring + (size_t)s->next_slot * s->n_bits, h_bits, (size_t)s->n_bits);
+    memcpy(s->h_ring.get() + (size_t)s->next_slot * s->n_bits, h_bits, (size_t)s->n_bits);
     s->dirty |= 1u << s->next_slot;
     s->next_slot = (s->next_slot + 1) % 16;                    // cif_deinterleaver.cpp:28-33
     if (s->stored < 16) s->stored++;
@@ -192,9 +191,9 @@ extern "C" int dabgpu_msc_stream_deinterleave_sync(dabgpu_msc_stream* s, int8_t*
     DABGPU_BIND(s->ctx);
     hipStream_t q = s->ctx->stream;
     int st = msc_stream_flush(s);
-    if (!st) st = dabgpu_check_hip(dabgpu_launch_cif_deinterleave(s->d_ring, s->n_bits, 16, (s->next_slot + 15) % 16, s->d_logical, q),
+    if (!st) st = dabgpu_check_hip(dabgpu_launch_cif_deinterleave(s->d_ring.get(), s->n_bits, 16, (s->next_slot + 15) % 16, s->d_logical.get(), q),
                               "cif_deinterleave launch");
-    if (!st) st = dabgpu_check_hip(hipMemcpyAsync(h_out, s->d_logical, (size_t)s->n_bits, hipMemcpyDeviceToHost, q), "hipMemcpyAsync");
+    if (!st) st = dabgpu_check_hip(hipMemcpyAsync(h_out, s->d_logical.get(), (size_t)s->n_bits, hipMemcpyDeviceToHost, q), "hipMemcpyAsync");
     if (!st) st = dabgpu_check_hip(hipStreamSynchronize(q), "hipStreamSynchronize");
     return st;
 }

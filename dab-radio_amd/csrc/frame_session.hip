@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "dabgpu.h"
@@ -32,44 +33,35 @@ static void block_pointers(uint8_t* base, size_t n_sub, uint8_t** fib, dabgpu_co
 // (re)allocates the session's device block for n_sub sub-channels of cif_out bytes per CIF; the session's stream must be idle
 static int session_layout(dabgpu_frame_session* s, size_t n_sub, size_t cif_out) {
     const size_t need = session_block_bytes(n_sub, cif_out);
-    if (need > s->block_bytes || !s->d_block) {
-        if (s->d_block) (void)hipFree(s->d_block);
-        s->d_block = nullptr; s->block_bytes = 0;
-        int st = dabgpu_check_hip(hipMalloc((void**)&s->d_block, need), "hipMalloc(session results)");
-        if (st) return st;
-        s->block_bytes = need;
-    }
-    block_pointers(s->d_block, n_sub, &s->d_fib, &s->d_fres, &s->d_mres, &s->d_msc);
+    if (const int st = s->d_block.regrow(need, "hipMalloc(session results)")) return st;       // (no wait here: the caller's, see above)
+    block_pointers(s->d_block.get(), n_sub, &s->d_fib, &s->d_fres, &s->d_mres, &s->d_msc);
     return DABGPU_OK;
 }
 // the slot's pinned block for the session's current layout
 static int slot_block(dabgpu_frame_session* s, dabgpu_frame_session::slot& sl) {
     const size_t need = session_block_bytes(s->subs.size(), s->cif_out);
-    if (sl.h_block_cap < need) {
-        if (sl.h_block) (void)hipHostFree(sl.h_block);
-        sl.h_block = nullptr; sl.h_block_cap = 0;
-        int st = dabgpu_check_hip(hipHostMalloc((void**)&sl.h_block, need, hipHostMallocDefault), "hipHostMalloc(session results)");
-        if (st) return st;
-        sl.h_block_cap = need;
-    }
-    block_pointers(sl.h_block, s->subs.size(), &sl.h_fib, &sl.h_fres, &sl.h_mres, &sl.h_msc);
+    // (no wait: the slot's previous frame has been waited for, nothing writes the old block)
+    if (const int st = sl.h_block.regrow(need, "hipHostMalloc(session results)")) return st;
+    block_pointers(sl.h_block.get(), s->subs.size(), &sl.h_fib, &sl.h_fres, &sl.h_mres, &sl.h_msc);
     return DABGPU_OK;
 }
 
 extern "C" int dabgpu_frame_session_create(dabgpu_frame_session** out, int device) {
     if (!out) return DABGPU_ERR_INVALID_ARG;
     *out = nullptr;
-    dabgpu_frame_session* s = new dabgpu_frame_session();
+    dabgpu_frame_session* s = new (std::nothrow) dabgpu_frame_session();
+    if (!s) return DABGPU_ERR_HIP;
     int st = dabgpu_create(&s->ctx, device, nullptr, nullptr);
-    if (!st) st = dabgpu_check_hip(hipMalloc((void**)&s->d_hist, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS), "hipMalloc(session history)");
-    if (!st) st = dabgpu_check_hip(hipMemsetAsync(s->d_hist, 0, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, s->ctx->stream), "hipMemsetAsync(session history)");
+    if (st) { delete s; return st; }              // (no context, nothing else yet)
+    st = s->d_hist.alloc((size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, "hipMalloc(session history)");
+    if (!st) st = dabgpu_check_hip(hipMemsetAsync(s->d_hist.get(), 0, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, s->ctx->stream), "hipMemsetAsync(session history)");
     if (!st) st = dabgpu_check_hip(hipStreamSynchronize(s->ctx->stream), "hipStreamSynchronize(session history)");      // (not the NULL stream: see dabgpu_msc_stream_create)
     if (!st) st = session_layout(s, 0, 0);
     for (auto& sl : s->slots) {
         if (!st) st = slot_block(s, sl);
-        if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&sl.done, dabgpu_wait_event_flags(false)), "hipEventCreate(session)");
-        if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&sl.ev_ready, dabgpu_wait_event_flags(false)), "hipEventCreate(session)");
-        if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&sl.ev_copied, dabgpu_wait_event_flags(false)), "hipEventCreate(session)");
+        if (!st) st = sl.done.create(dabgpu_wait_event_flags(false), "hipEventCreate(session)");
+        if (!st) st = sl.ev_ready.create(dabgpu_wait_event_flags(false), "hipEventCreate(session)");
+        if (!st) st = sl.ev_copied.create(dabgpu_wait_event_flags(false), "hipEventCreate(session)");
     }
     if (st) { dabgpu_frame_session_destroy(s); return st; }
     *out = s;
@@ -77,7 +69,9 @@ extern "C" int dabgpu_frame_session_create(dabgpu_frame_session** out, int devic
 }
 
 int dabgpu_frame_session_create_store(dabgpu_frame_session** out, dabgpu_ctx* ctx) {
-    dabgpu_frame_session* s = new dabgpu_frame_session();
+    *out = nullptr;
+    dabgpu_frame_session* s = new (std::nothrow) dabgpu_frame_session();
+    if (!s) return DABGPU_ERR_HIP;
     s->ctx = ctx;
     s->owns_ctx = false;
     *out = s;
@@ -85,25 +79,11 @@ int dabgpu_frame_session_create_store(dabgpu_frame_session** out, dabgpu_ctx* ct
 }
 
 extern "C" void dabgpu_frame_session_destroy(dabgpu_frame_session* s) {
-    if (!s) return;
-    if (s->ctx) {
-        (void)hipSetDevice(s->ctx->device);
-        if (s->owns_ctx) (void)hipStreamSynchronize(s->ctx->stream);
-    }
-    for (auto& sl : s->slots) {
-        if (sl.h_block) (void)hipHostFree(sl.h_block);
-        if (sl.h_bits) (void)hipHostFree(sl.h_bits);
-        if (sl.h_aux) (void)hipHostFree(sl.h_aux);
-        if (sl.h_fft) (void)hipHostFree(sl.h_fft);
-        if (sl.h_dq) (void)hipHostFree(sl.h_dq);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.ev_ready) (void)hipEventDestroy(sl.ev_ready);
-        if (sl.ev_copied) (void)hipEventDestroy(sl.ev_copied);
-    }
-    if (s->d_hist) (void)hipFree(s->d_hist);
-    if (s->d_block) (void)hipFree(s->d_block);
-    if (s->ctx && s->owns_ctx) dabgpu_destroy(s->ctx);
+    if (!dabgpu_destroy_begin(s, s ? s->ctx : nullptr, false)) return;
+    dabgpu_ctx* own = s->owns_ctx ? s->ctx : nullptr;
+    if (own) (void)hipStreamSynchronize(own->stream);                   // (a store's results were waited for by the bank)
     delete s;
+    if (own) dabgpu_destroy(own);
 }
 
 extern "C" int dabgpu_frame_session_set_subchannels(dabgpu_frame_session* s, const dabgpu_subchannel* subs, int n) {
@@ -133,7 +113,7 @@ static int session_decode(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_se
     dabgpu_ctx* c = s->ctx;
     hipStream_t q = c->stream;
     const int hs = (int)(gen % dabgpu_frame_session::H);
-    int8_t* d_frame = s->d_hist + (size_t)hs * DABGPU_NB_FRAME_BITS;
+    int8_t* d_frame = s->d_hist.get() + (size_t)hs * DABGPU_NB_FRAME_BITS;
     const int n_sub = (int)s->subs.size();
     int st;
     sl.fic = decode_fic != 0;
@@ -145,15 +125,15 @@ static int session_decode(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_se
     if (n_sub) {
         const size_t need = (size_t)4 * s->cif_out;
         // the frame's FIC and sub-channels in one call (one launch in the wave mapping: msc_decode_any)
-        if (decode_fic) st = dabgpu_decode_frames_layout(c, s->d_hist, 1, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, dabgpu_frame_session::H, hs,
+        if (decode_fic) st = dabgpu_decode_frames_layout(c, s->d_hist.get(), 1, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, dabgpu_frame_session::H, hs,
                                                          s->subs.data(), n_sub, s->d_fib, s->d_fres, s->d_msc, need, s->d_mres, tie_rule, DABGPU_BITS_NATURAL, q);
-        else st = dabgpu_msc_decode_frames(c, s->d_hist, 1, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, dabgpu_frame_session::H, hs,
+        else st = dabgpu_msc_decode_frames(c, s->d_hist.get(), 1, (size_t)dabgpu_frame_session::H * DABGPU_NB_FRAME_BITS, dabgpu_frame_session::H, hs,
                                            s->subs.data(), n_sub, s->d_msc, need, s->d_mres, tie_rule, q);
         if (st) return st;
     }
     // one copy: the whole block with sub-channels, its FIC head without
     if (n_sub || decode_fic)
-        DABGPU_CK(hipMemcpyAsync(sl.h_block, s->d_block, n_sub ? session_block_bytes((size_t)n_sub, s->cif_out) : session_block_bytes(0, 0), hipMemcpyDeviceToHost, q));
+        DABGPU_CK(hipMemcpyAsync(sl.h_block.get(), s->d_block.get(), n_sub ? session_block_bytes((size_t)n_sub, s->cif_out) : session_block_bytes(0, 0), hipMemcpyDeviceToHost, q));
     return DABGPU_OK;
 }
 
@@ -169,14 +149,14 @@ extern "C" int dabgpu_frame_session_push_frame(dabgpu_frame_session* s, const in
     dabgpu_frame_session::slot& sl = s->slots[gen % dabgpu_frame_session::R];
     int st;
     if (sl.pending) {                                                   // the slot's previous frame (R frames ago)
-        if ((st = dabgpu_check_hip(hipEventSynchronize(sl.done), "hipEventSynchronize(session)"))) return st;
+        if ((st = dabgpu_check_hip(hipEventSynchronize(sl.done.get()), "hipEventSynchronize(session)"))) return st;
         sl.pending = false;
     }
-    int8_t* d_frame = s->d_hist + (size_t)hs * DABGPU_NB_FRAME_BITS;
+    int8_t* d_frame = s->d_hist.get() + (size_t)hs * DABGPU_NB_FRAME_BITS;
     if ((st = dabgpu_stage_h2d(c, d_frame, h_bits, DABGPU_NB_FRAME_BITS, q))) return st;
     sl.gen = ~0ull;
     if ((st = session_decode(s, gen, sl, decode_fic, tie_rule))) return st;
-    if ((st = dabgpu_check_hip(hipEventRecord(sl.done, q), "hipEventRecord(session)"))) return st;
+    if ((st = dabgpu_check_hip(hipEventRecord(sl.done.get(), q), "hipEventRecord(session)"))) return st;
     sl.pending = true;
     sl.gen = gen;
     s->next_gen = gen + 1;
@@ -197,13 +177,13 @@ int dabgpu_session_reserve(dabgpu_frame_session* s, hipStream_t producer, uint64
             std::lock_guard<std::mutex> lock(s->mu);
             gen0 = s->next_reserve;
             dabgpu_frame_session::slot& sl0 = s->slots[gen0 % dabgpu_frame_session::R];
-            if (sl0.pending) done = sl0.done;
+            if (sl0.pending) done = sl0.done.get();
         }
         if (done) {
             if ((st = dabgpu_check_hip(hipEventSynchronize(done), "hipEventSynchronize(session)"))) return st;
             std::lock_guard<std::mutex> lock(s->mu);
             dabgpu_frame_session::slot& sl0 = s->slots[gen0 % dabgpu_frame_session::R];
-            if (s->next_reserve == gen0 && sl0.done == done) sl0.pending = false;
+            if (s->next_reserve == gen0 && sl0.done.get() == done) sl0.pending = false;
         }
     }
     std::lock_guard<std::mutex> lock(s->mu);
@@ -216,7 +196,7 @@ int dabgpu_session_reserve(dabgpu_frame_session* s, hipStream_t producer, uint64
     }
     dabgpu_frame_session::slot& sl = s->slots[gen % dabgpu_frame_session::R];
     if (sl.pending) {                                                  // (only if the wait above raced with a commit of that slot: cannot happen with one reserving thread)
-        if ((st = dabgpu_check_hip(hipEventSynchronize(sl.done), "hipEventSynchronize(session)"))) return st;
+        if ((st = dabgpu_check_hip(hipEventSynchronize(sl.done.get()), "hipEventSynchronize(session)"))) return st;
         sl.pending = false;
     }
     // history slot gen % H holds frame gen - H, which the decodes of the frames gen - H .. gen - 4 read (5 frames = 16 CIFs + the frame's own
@@ -229,12 +209,12 @@ int dabgpu_session_reserve(dabgpu_frame_session* s, hipStream_t producer, uint64
         }
         dabgpu_frame_session::slot& old = s->slots[(gen - 4) % dabgpu_frame_session::R];
         if (old.pending && old.gen == gen - 4 &&
-            (st = dabgpu_check_hip(hipStreamWaitEvent(producer, old.done, 0), "hipStreamWaitEvent(session history)"))) return st;
+            (st = dabgpu_check_hip(hipStreamWaitEvent(producer, old.done.get(), 0), "hipStreamWaitEvent(session history)"))) return st;
     }
     sl.gen = ~0ull;
     s->next_reserve = gen + 1;
     *gen_out = gen;
-    *d_frame_bits = s->d_hist + (size_t)(gen % dabgpu_frame_session::H) * DABGPU_NB_FRAME_BITS;
+    *d_frame_bits = s->d_hist.get() + (size_t)(gen % dabgpu_frame_session::H) * DABGPU_NB_FRAME_BITS;
     *slot_out = &sl;
     return DABGPU_OK;
 }
@@ -254,14 +234,14 @@ int dabgpu_session_commit(dabgpu_frame_session* s, uint64_t gen, hipEvent_t read
     int st;
     if (ready && (st = dabgpu_check_hip(hipStreamWaitEvent(q, ready, 0), "hipStreamWaitEvent(session producer)"))) return st;
     if (bits_bytes) {
-        if (!sl.h_bits && (st = dabgpu_check_hip(hipHostMalloc((void**)&sl.h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault), "hipHostMalloc(session bits)"))) return st;
-        if ((st = dabgpu_check_hip(hipMemcpyAsync(sl.h_bits, s->d_hist + (size_t)(gen % dabgpu_frame_session::H) * DABGPU_NB_FRAME_BITS, bits_bytes,
+        if (!sl.h_bits && (st = sl.h_bits.alloc(DABGPU_NB_FRAME_BITS, "hipHostMalloc(session bits)"))) return st;
+        if ((st = dabgpu_check_hip(hipMemcpyAsync(sl.h_bits.get(), s->d_hist.get() + (size_t)(gen % dabgpu_frame_session::H) * DABGPU_NB_FRAME_BITS, bits_bytes,
                                                   hipMemcpyDeviceToHost, q), "hipMemcpyAsync(session bits)"))) return st;
     }
     sl.fic = false; sl.subs.clear(); sl.sub_off.clear(); sl.sub_n.clear(); sl.cif_out = 0;
     if (decode && (st = session_decode(s, gen, sl, decode_fic, tie_rule))) return st;
     if (producer_done && (st = dabgpu_check_hip(hipStreamWaitEvent(q, producer_done, 0), "hipStreamWaitEvent(session producer copies)"))) return st;
-    if ((st = dabgpu_check_hip(hipEventRecord(sl.done, q), "hipEventRecord(session)"))) return st;
+    if ((st = dabgpu_check_hip(hipEventRecord(sl.done.get(), q), "hipEventRecord(session)"))) return st;
     sl.pending = true;
     sl.gen = gen;
     s->next_gen = gen + 1;
@@ -280,7 +260,7 @@ int dabgpu_session_slot(dabgpu_frame_session* s, uint64_t gen, dabgpu_frame_sess
     if (sl.gen != gen) return DABGPU_ERR_NOT_READY;                     // never pushed, or overwritten by a later frame
     if (sl.pending) {
         DABGPU_BIND(s->ctx);
-        int st = dabgpu_check_hip(hipEventSynchronize(sl.done), "hipEventSynchronize(session)");
+        int st = dabgpu_check_hip(hipEventSynchronize(sl.done.get()), "hipEventSynchronize(session)");
         if (st) return st;
         sl.pending = false;
     }

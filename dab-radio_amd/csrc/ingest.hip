@@ -9,6 +9,7 @@
 // k + 1 runs while batch k is demodulated; nothing in the steady state blocks the host except a full ring.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <new>
 #include <vector>
 
 #include "dabgpu_internal.h"
@@ -18,8 +19,8 @@ struct dabgpu_ingest {
     size_t bytes = 0;
     int depth = 0;
     int cur = -1;                                 // slot handed out by the last acquire
-    hipStream_t copy_stream = nullptr;
-    struct slot { void* h = nullptr; void* d = nullptr; hipEvent_t h2d = nullptr, consumed = nullptr; bool h2d_pending = false, consumed_pending = false; };
+    dabgpu::Stream copy_stream;
+    struct slot { dabgpu::PinnedBuffer<> h; dabgpu::DeviceBuffer<> d; dabgpu::Event h2d, consumed; bool h2d_pending = false, consumed_pending = false; };
     std::vector<slot> slots;
 };
 
@@ -27,17 +28,19 @@ extern "C" {
 
 int dabgpu_ingest_create(dabgpu_ctx* c, size_t buffer_bytes, int depth, dabgpu_ingest** out) {
     if (!c || !out || buffer_bytes == 0 || depth < 1 || depth > 16) { dabgpu_set_error("ingest_create: invalid argument"); return DABGPU_ERR_INVALID_ARG; }
+    *out = nullptr;
     DABGPU_BIND(c);
-    dabgpu_ingest* g = new dabgpu_ingest();
+    dabgpu_ingest* g = new (std::nothrow) dabgpu_ingest();
+    if (!g) return DABGPU_ERR_HIP;
     g->ctx = c; g->bytes = buffer_bytes; g->depth = depth;
-    g->slots.resize((size_t)depth);
-    int st = dabgpu_check_hip(hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking), "hipStreamCreate(ingest copy stream)");
+    g->slots = std::vector<dabgpu_ingest::slot>((size_t)depth);
+    int st = g->copy_stream.create(hipStreamNonBlocking, "hipStreamCreate(ingest copy stream)");
     for (int k = 0; k < depth && !st; k++) {
         auto& s = g->slots[(size_t)k];
-        if ((st = dabgpu_check_hip(hipHostMalloc(&s.h, buffer_bytes, hipHostMallocDefault), "hipHostMalloc(ingest)"))) break;
-        if ((st = dabgpu_check_hip(hipMalloc(&s.d, buffer_bytes), "hipMalloc(ingest)"))) break;
-        if ((st = dabgpu_check_hip(hipEventCreateWithFlags(&s.h2d, hipEventDisableTiming), "hipEventCreate(ingest)"))) break;
-        if ((st = dabgpu_check_hip(hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming), "hipEventCreate(ingest)"))) break;
+        if ((st = s.h.alloc(buffer_bytes, "hipHostMalloc(ingest)"))) break;
+        if ((st = s.d.alloc(buffer_bytes, "hipMalloc(ingest)"))) break;
+        if ((st = s.h2d.create(hipEventDisableTiming, "hipEventCreate(ingest)"))) break;
+        if ((st = s.consumed.create(hipEventDisableTiming, "hipEventCreate(ingest)"))) break;
     }
     if (st) { dabgpu_ingest_destroy(g); return st; }
     *out = g;
@@ -45,17 +48,10 @@ int dabgpu_ingest_create(dabgpu_ctx* c, size_t buffer_bytes, int depth, dabgpu_i
 }
 
 void dabgpu_ingest_destroy(dabgpu_ingest* g) {
-    if (!g) return;
-    (void)hipSetDevice(g->ctx->device);
-    if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
-    for (auto& s : g->slots) {
-        if (s.consumed_pending) (void)hipEventSynchronize(s.consumed);
-        if (s.h2d) (void)hipEventDestroy(s.h2d);
-        if (s.consumed) (void)hipEventDestroy(s.consumed);
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-    }
-    if (g->copy_stream) (void)hipStreamDestroy(g->copy_stream);
+    if (!dabgpu_destroy_begin(g, g ? g->ctx : nullptr, false)) return;
+    // the copies in flight, and the kernels that still read a twin
+    if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream.get());
+    for (auto& s : g->slots) if (s.consumed_pending) (void)hipEventSynchronize(s.consumed.get());
     delete g;
 }
 
@@ -66,16 +62,16 @@ int dabgpu_ingest_acquire(dabgpu_ingest* g, void** h_buffer) {
     g->cur = (g->cur + 1) % g->depth;
     auto& s = g->slots[(size_t)g->cur];
     if (s.h2d_pending) {
-        int st = dabgpu_check_hip(hipEventSynchronize(s.h2d), "hipEventSynchronize(ingest h2d)");
+        int st = dabgpu_check_hip(hipEventSynchronize(s.h2d.get()), "hipEventSynchronize(ingest h2d)");
         if (st) return st;
         s.h2d_pending = false;
     }
-    *h_buffer = s.h;
+    *h_buffer = s.h.get();
     return DABGPU_OK;
 }
 
 static dabgpu_ingest::slot* slot_of(dabgpu_ingest* g, const void* d_buffer) {
-    for (auto& s : g->slots) if (s.d == d_buffer) return &s;
+    for (auto& s : g->slots) if (s.d.get() == d_buffer) return &s;
     return nullptr;
 }
 
@@ -87,13 +83,13 @@ int dabgpu_ingest_submit(dabgpu_ingest* g, size_t bytes, void** d_buffer) {
     auto& s = g->slots[(size_t)g->cur];
     int st;
     if (s.consumed_pending) {
-        if ((st = dabgpu_check_hip(hipStreamWaitEvent(g->copy_stream, s.consumed, 0), "hipStreamWaitEvent(ingest consumed)"))) return st;
+        if ((st = dabgpu_check_hip(hipStreamWaitEvent(g->copy_stream.get(), s.consumed.get(), 0), "hipStreamWaitEvent(ingest consumed)"))) return st;
         s.consumed_pending = false;
     }
-    if (bytes && (st = dabgpu_check_hip(hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, g->copy_stream), "hipMemcpyAsync(ingest)"))) return st;
-    if ((st = dabgpu_check_hip(hipEventRecord(s.h2d, g->copy_stream), "hipEventRecord(ingest h2d)"))) return st;
+    if (bytes && (st = dabgpu_check_hip(hipMemcpyAsync(s.d.get(), s.h.get(), bytes, hipMemcpyHostToDevice, g->copy_stream.get()), "hipMemcpyAsync(ingest)"))) return st;
+    if ((st = dabgpu_check_hip(hipEventRecord(s.h2d.get(), g->copy_stream.get()), "hipEventRecord(ingest h2d)"))) return st;
     s.h2d_pending = true;
-    *d_buffer = s.d;
+    *d_buffer = s.d.get();
     return DABGPU_OK;
 }
 
@@ -103,7 +99,7 @@ int dabgpu_ingest_wait(dabgpu_ingest* g, const void* d_buffer, void* compute_str
     dabgpu_ingest::slot* s = g ? slot_of(g, d_buffer) : nullptr;
     if (!s) { dabgpu_set_error("ingest_wait: not a buffer of this pipe"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(g->ctx);
-    return dabgpu_check_hip(hipStreamWaitEvent((hipStream_t)compute_stream, s->h2d, 0), "hipStreamWaitEvent(ingest h2d)");
+    return dabgpu_check_hip(hipStreamWaitEvent((hipStream_t)compute_stream, s->h2d.get(), 0), "hipStreamWaitEvent(ingest h2d)");
 }
 
 // call after the kernels reading the twin d_buffer have been enqueued on `compute_stream`: it may be overwritten once they ran
@@ -111,7 +107,7 @@ int dabgpu_ingest_consumed(dabgpu_ingest* g, const void* d_buffer, void* compute
     dabgpu_ingest::slot* s = g ? slot_of(g, d_buffer) : nullptr;
     if (!s) { dabgpu_set_error("ingest_consumed: not a buffer of this pipe"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(g->ctx);
-    int st = dabgpu_check_hip(hipEventRecord(s->consumed, (hipStream_t)compute_stream), "hipEventRecord(ingest consumed)");
+    int st = dabgpu_check_hip(hipEventRecord(s->consumed.get(), (hipStream_t)compute_stream), "hipEventRecord(ingest consumed)");
     if (st) return st;
     s->consumed_pending = true;
     return DABGPU_OK;

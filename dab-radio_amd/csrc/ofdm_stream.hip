@@ -21,9 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <algorithm>
 #include <new>
-#include <vector>
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -410,14 +408,14 @@ struct dabgpu_stream_bank {
     dabgpu_ctx* ctx = nullptr;
     size_t n = 0;
     dabgpu_stream_cfg cfg{};
-    BankView view{};
+    BankView view{};                   // its pointers, d_corr_out and d_status point at the allocations of `mem` and `win`
     float* d_corr_out = nullptr;       // [n][n_sym][2] cyclic-prefix correlations of the last demodulated frames
     dabgpu_stream_status* d_status = nullptr;
-    float* d_raw_scratch = nullptr;    // converted block of dabgpu_stream_bank_process_raw (grow-only)
-    size_t raw_scratch_bytes = 0;
-    std::vector<void*> allocs;
-    hipStream_t side = nullptr;        // second lane of a call (mode I banks of >= 1024 streams): half of the streams run their rounds here
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DeviceBuffer<> mem[14];            // in the order dabgpu_stream_bank_create_mode makes them
+    DeviceBuffer<float> win;           // view.win: L1 windows (grow-only)
+    DeviceBuffer<float> raw_scratch;   // converted block of dabgpu_stream_bank_process_raw (grow-only)
+    Stream side;                       // second lane of a call (mode I banks of >= 1024 streams): half of the streams run their rounds here
+    Event ev_fork, ev_join;
     // retained blocks: the last call left the unfinished frames' samples in ITS block (no carry-over copy); the next call must be handed
     // that block again (dabgpu_stream_bank_process_retained), or dabgpu_stream_bank_release must copy them out of it first
     bool carry_pending = false;
@@ -437,16 +435,17 @@ static int bank_soft_scale_fits(const dabgpu_stream_bank* b, size_t slots_per_st
     return DABGPU_ERR_INVALID_ARG;
 }
 
+// n elements for *p, owned by `owner`
+template <class T> static int bank_alloc(DeviceBuffer<>& owner, T** p, size_t n) {
+    const int st = owner.alloc(n * sizeof(T), "hipMalloc(stream bank)");
+    *p = static_cast<T*>(owner.get());
+    return st;
+}
+
 extern "C" {
 
 void dabgpu_stream_bank_destroy(dabgpu_stream_bank* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : b->allocs) (void)hipFree(p);
-    if (b->side) (void)hipStreamDestroy(b->side);
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_join) (void)hipEventDestroy(b->ev_join);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 
@@ -473,6 +472,7 @@ int dabgpu_stream_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_stre
 
 int dabgpu_stream_bank_create_mode(dabgpu_ctx* c, int mode, size_t n_streams, const dabgpu_stream_cfg* cfg, dabgpu_stream_bank** out) {
     if (!c || !out || n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("stream_bank_create: invalid argument"); return DABGPU_ERR_INVALID_ARG; }
+    *out = nullptr;
     ModeGeom mg;
     if (!mode_geometry(mode, mg)) { dabgpu_set_error("stream_bank_create: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
     dabgpu_stream_cfg k;
@@ -486,28 +486,24 @@ int dabgpu_stream_bank_create_mode(dabgpu_ctx* c, int mode, size_t n_streams, co
     G.mode = mode; G.null_period = mg.null_period; G.period = mg.period; G.n_sym = mg.n_sym; G.n_fft = mg.n_fft;
     G.frame_samples = mg.frame_samples; G.n_corr = mg.null_period + mg.period; G.frame_bits = mg.frame_bits;
     int st = DABGPU_OK;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (st) return;
-        st = dabgpu_check_hip(hipMalloc(p, bytes), "hipMalloc(stream bank)");
-        if (!st) b->allocs.push_back(*p);
-    };
-    alloc((void**)&b->view.st, n_streams * sizeof(StreamState));
-    alloc((void**)&b->view.sync, n_streams * sizeof(dabgpu_sync_state));
-    alloc((void**)&b->view.ring, n_streams * (size_t)G.null_period * sizeof(f2));
-    alloc((void**)&b->view.corr, n_streams * (size_t)G.n_corr * sizeof(f2));
-    alloc((void**)&b->view.frame, n_streams * (size_t)G.frame_samples * sizeof(f2));
-    alloc((void**)&b->view.freq, n_streams * sizeof(float));
-    alloc((void**)&b->view.sync_active, n_streams * sizeof(int));
-    alloc((void**)&b->view.desc, n_streams * sizeof(dabgpu_frame_desc));
-    alloc((void**)&b->view.copy_src, n_streams * sizeof(long long));
-    alloc((void**)&b->view.copy_dst, n_streams * sizeof(int));
-    alloc((void**)&b->view.copy_cnt, n_streams * sizeof(int));
-    alloc((void**)&b->view.not_done, 16 * sizeof(int));
-    alloc((void**)&b->d_corr_out, n_streams * (size_t)G.n_sym * 2 * sizeof(float));
-    alloc((void**)&b->d_status, n_streams * sizeof(dabgpu_stream_status));
-    if (!st) st = dabgpu_check_hip(hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking), "hipStreamCreate(stream bank)");
-    if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming), "hipEventCreate");
-    if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming), "hipEventCreate");
+    DeviceBuffer<>* m = b->mem;
+    if (!st) st = bank_alloc(*m++, &b->view.st, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.sync, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.ring, n_streams * (size_t)G.null_period);
+    if (!st) st = bank_alloc(*m++, &b->view.corr, n_streams * (size_t)G.n_corr);
+    if (!st) st = bank_alloc(*m++, &b->view.frame, n_streams * (size_t)G.frame_samples);
+    if (!st) st = bank_alloc(*m++, &b->view.freq, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.sync_active, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.desc, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.copy_src, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.copy_dst, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.copy_cnt, n_streams);
+    if (!st) st = bank_alloc(*m++, &b->view.not_done, 16);
+    if (!st) st = bank_alloc(*m++, &b->d_corr_out, n_streams * (size_t)G.n_sym * 2);
+    if (!st) st = bank_alloc(*m++, &b->d_status, n_streams);
+    if (!st) st = b->side.create(hipStreamNonBlocking, "hipStreamCreate(stream bank)");
+    if (!st) st = b->ev_fork.create(hipEventDisableTiming, "hipEventCreate");
+    if (!st) st = b->ev_join.create(hipEventDisableTiming, "hipEventCreate");
     if (!st) st = dabgpu_stream_bank_reset(b, c->stream);
     if (!st) st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
     if (st) { dabgpu_stream_bank_destroy(b); return st; }
@@ -568,13 +564,11 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     if (n_samples >= (size_t)k) {
         const long long stride = (long long)k * b->cfg.signal_l1_nb_decimate;
         const long long n_win = ((long long)n_samples - k + stride - 1) / stride;
-        if (n_win > b->view.win_cap) {
+        if (b->win.needs((size_t)n * (size_t)n_win)) {
             DABGPU_CK(hipStreamSynchronize(s));
-            if (b->view.win) { (void)hipFree(b->view.win); b->allocs.erase(std::find(b->allocs.begin(), b->allocs.end(), (void*)b->view.win)); }
             b->view.win = nullptr; b->view.win_cap = 0;
-            DABGPU_CK(hipMalloc((void**)&b->view.win, (size_t)n * (size_t)n_win * sizeof(float)));
-            b->allocs.push_back(b->view.win);
-            b->view.win_cap = n_win;
+            if ((st = b->win.regrow((size_t)n * (size_t)n_win, "hipMalloc((void**)&b->view.win, (size_t)n * (size_t)n_win * sizeof(float))"))) return st;
+            b->view.win = b->win.get(); b->view.win_cap = n_win;
         }
         if (n_win > 0) {
             hipLaunchKernelGGL(stream_l1_kernel<SRC>, dim3((unsigned)((n_win + L1_WINDOWS - 1) / L1_WINDOWS), (unsigned)n), dim3(256), 0, s,
@@ -591,15 +585,15 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     // of >= 1024 streams runs the two halves of its streams on two HIP streams, so that one half's small kernels run beside the other
     // half's demodulation.  Same kernels, same per-stream order, same results.
     const int n_lanes = (G.mode == 1 && n >= 1024) ? 2 : 1;      // (each half must still fill the chip: 256 streams lost 10-30 % in two lanes)
-    hipStream_t lane_stream[2] = {s, b->side};
+    hipStream_t lane_stream[2] = {s, b->side.get()};
     const int lane_lo[3] = {0, (n_lanes == 2) ? n / 2 : n, n};
     if (n_lanes == 2) {
-        DABGPU_CK(hipEventRecord(b->ev_fork, s));
-        DABGPU_CK(hipStreamWaitEvent(b->side, b->ev_fork, 0));
+        DABGPU_CK(hipEventRecord(b->ev_fork.get(), s));
+        DABGPU_CK(hipStreamWaitEvent(b->side.get(), b->ev_fork.get(), 0));
     }
     // (an error inside the rounds must not leave work on the side stream unordered with the caller's stream: the caller may free the
     // block and the output buffers as soon as the call has returned)
-#define CKS(status) do { st = (status); if (st) { if (n_lanes == 2) (void)hipStreamSynchronize(b->side); return st; } } while (0)
+#define CKS(status) do { st = (status); if (st) { if (n_lanes == 2) (void)hipStreamSynchronize(b->side.get()); return st; } } while (0)
 #define CKL(call) CKS(dabgpu_check_hip((call), #call))
     const size_t sb = src_sample_bytes<SRC>::value;
     // run length of the bank's demodulation: four workgroups per frame (19 + 19 + 19 + 18 symbols).  Shorter-lived workgroups hand
@@ -638,7 +632,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
             for (int l = 0; l < n_lanes; l++) CKL(hipMemcpyAsync(&h_not_done[l], b->view.not_done + 8 * l + (round & 7), sizeof(int), hipMemcpyDeviceToHost, lane_stream[l]));
             for (int l = 0; l < n_lanes; l++) CKL(hipStreamSynchronize(lane_stream[l]));
         }
-        if (round > (1 << 22)) { dabgpu_set_error("stream_bank_process: no progress"); if (n_lanes == 2) (void)hipStreamSynchronize(b->side); return DABGPU_ERR_HIP; }
+        if (round > (1 << 22)) { dabgpu_set_error("stream_bank_process: no progress"); if (n_lanes == 2) (void)hipStreamSynchronize(b->side.get()); return DABGPU_ERR_HIP; }
     }
     for (int l = 0; l < n_lanes && !use_retain; l++) {                    // the carry-over copies of the call, every lane its own streams
         hipLaunchKernelGGL(stream_copy_kernel<SRC>, dim3(COPY_WGS, (unsigned)(lane_lo[l + 1] - lane_lo[l])), dim3(256), 0, lane_stream[l], b->view,
@@ -648,8 +642,8 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
 #undef CKL
 #undef CKS
     if (n_lanes == 2) {
-        DABGPU_CK(hipEventRecord(b->ev_join, b->side));
-        DABGPU_CK(hipStreamWaitEvent(s, b->ev_join, 0));
+        DABGPU_CK(hipEventRecord(b->ev_join.get(), b->side.get()));
+        DABGPU_CK(hipStreamWaitEvent(s, b->ev_join.get(), 0));
     }
     if (d_n_frames) {
         hipLaunchKernelGGL(stream_report_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, b->view, n, d_n_frames,
@@ -735,22 +729,17 @@ int dabgpu_stream_bank_process_raw(dabgpu_stream_bank* b, const void* d_raw, int
     DABGPU_BIND(b->ctx);
     hipStream_t s = (hipStream_t)stream;
     const size_t padded = (n_samples + 1) & ~(size_t)1;                   // keeps every stream's converted block 16-byte aligned
-    const size_t need = b->n * padded * 2 * sizeof(float);
-    if (need > b->raw_scratch_bytes) {
+    const size_t need = b->n * padded * 2;                                // floats
+    if (b->raw_scratch.needs(need)) {
         int st = dabgpu_check_hip(hipStreamSynchronize(s), "hipStreamSynchronize");
-        if (st) return st;
-        if (b->d_raw_scratch) { (void)hipFree(b->d_raw_scratch); b->allocs.erase(std::find(b->allocs.begin(), b->allocs.end(), (void*)b->d_raw_scratch)); }
-        b->d_raw_scratch = nullptr; b->raw_scratch_bytes = 0;
-        if ((st = dabgpu_check_hip(hipMalloc((void**)&b->d_raw_scratch, need), "hipMalloc(stream bank raw scratch)"))) return st;
-        b->allocs.push_back(b->d_raw_scratch);
-        b->raw_scratch_bytes = need;
+        if (st || (st = b->raw_scratch.regrow(need, "hipMalloc(stream bank raw scratch)"))) return st;
     }
     for (size_t k = 0; k < b->n; k++) {
         const int st = dabgpu_iq_convert(b->ctx, static_cast<const uint8_t*>(d_raw) + k * stream_stride_samples * sb, format, n_samples,
-                                         b->d_raw_scratch + k * padded * 2, stream);
+                                         b->raw_scratch.get() + k * padded * 2, stream);
         if (st) return st;
     }
-    return dabgpu_stream_bank_process(b, b->d_raw_scratch, padded, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
+    return dabgpu_stream_bank_process(b, b->raw_scratch.get(), padded, n_samples, d_bits, max_frames_per_stream, d_n_frames, stream);
 }
 
 // frames go straight into per-stream frame-history rings (the layout dabgpu_fic_decode_ring / dabgpu_msc_decode_ring read)

@@ -468,19 +468,15 @@ using namespace dabgpu;
 struct dabgpu_packet_bank {
     dabgpu_ctx* ctx = nullptr;
     size_t n = 0;
-    PkState* d_states = nullptr;
-    uint32_t* d_rings = nullptr;
-    unsigned long long* d_off = nullptr; uint32_t* d_n = nullptr; int32_t* d_counts = nullptr;    // single-stream host-buffer path
-    std::vector<void*> allocs;
+    DeviceBuffer<PkState> d_states;
+    DeviceBuffer<uint32_t> d_rings;
+    DeviceBuffer<unsigned long long> d_off; DeviceBuffer<uint32_t> d_n; DeviceBuffer<int32_t> d_counts;    // single-stream host-buffer path
 };
 
 extern "C" {
 
 void dabgpu_packet_bank_destroy(dabgpu_packet_bank* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->ctx->device);
-    (void)hipDeviceSynchronize();
-    for (void* p : b->allocs) (void)hipFree(p);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 
@@ -489,32 +485,28 @@ int dabgpu_packet_bank_reset(dabgpu_packet_bank* b, void* stream) {
     DABGPU_BIND(b->ctx);
     // the constructor's state: empty ring, no FEC counter remembered
     std::vector<PkState> init(b->n, PkState{0, 0, 0, -1, 0, 0, {0, 0}});
-    int st = dabgpu_check_hip(hipMemcpyAsync(b->d_states, init.data(), b->n * sizeof(PkState), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync");
+    int st = dabgpu_check_hip(hipMemcpyAsync(b->d_states.get(), init.data(), b->n * sizeof(PkState), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync");
     if (st) return st;
-    st = dabgpu_check_hip(hipMemsetAsync(b->d_rings, 0, b->n * (size_t)RING_BYTES, (hipStream_t)stream), "hipMemsetAsync");
+    st = dabgpu_check_hip(hipMemsetAsync(b->d_rings.get(), 0, b->n * (size_t)RING_BYTES, (hipStream_t)stream), "hipMemsetAsync");
     if (st) return st;
     return dabgpu_check_hip(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
 }
 
 int dabgpu_packet_bank_create(dabgpu_ctx* c, size_t n_streams, dabgpu_packet_bank** out) {
     if (!c || !out || n_streams > (size_t)(1 << 22)) { dabgpu_set_error("packet_bank_create: invalid argument"); return DABGPU_ERR_INVALID_ARG; }
+    *out = nullptr;
     DABGPU_BIND(c);
     dabgpu_packet_bank* b = new (std::nothrow) dabgpu_packet_bank();
     if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n = n_streams;
-    int st = DABGPU_OK;
-    auto alloc = [&](void** p, size_t bytes) {
-        if (st) return;
-        st = dabgpu_check_hip(hipMalloc(p, bytes), "hipMalloc(packet bank)");
-        if (!st) b->allocs.push_back(*p);
-    };
+    const char* what = "hipMalloc(packet bank)";
     const size_t n1 = std::max<size_t>(n_streams, 1);       // (a bank of no streams is legal and does nothing)
-    alloc((void**)&b->d_states, n1 * sizeof(PkState));
-    alloc((void**)&b->d_rings, n1 * (size_t)RING_BYTES);
-    alloc((void**)&b->d_off, sizeof(unsigned long long));
-    alloc((void**)&b->d_n, sizeof(uint32_t));
-    alloc((void**)&b->d_counts, 4 * sizeof(int32_t));
-    if (!st) st = dabgpu_check_hip(hipMemsetAsync(b->d_off, 0, sizeof(unsigned long long), c->stream), "hipMemsetAsync");
+    int st = b->d_states.alloc(n1, what);
+    if (!st) st = b->d_rings.alloc(n1 * (size_t)RING_BYTES / sizeof(uint32_t), what);
+    if (!st) st = b->d_off.alloc(1, what);
+    if (!st) st = b->d_n.alloc(1, what);
+    if (!st) st = b->d_counts.alloc(4, what);
+    if (!st) st = dabgpu_check_hip(hipMemsetAsync(b->d_off.get(), 0, sizeof(unsigned long long), c->stream), "hipMemsetAsync");
     if (!st) st = dabgpu_packet_bank_reset(b, c->stream);
     if (st) { dabgpu_packet_bank_destroy(b); return st; }
     *out = b;
@@ -544,7 +536,7 @@ int dabgpu_packet_bank_process_masked(dabgpu_packet_bank* b, const uint8_t* d_fr
         dabgpu_set_error("packet_bank_process: null argument"); return DABGPU_ERR_INVALID_ARG;
     }
     DABGPU_BIND(b->ctx);
-    hipLaunchKernelGGL(packet_kernel, dim3((unsigned)b->n), dim3(64), 0, (hipStream_t)stream, b->d_states, b->d_rings, d_frames,
+    hipLaunchKernelGGL(packet_kernel, dim3((unsigned)b->n), dim3(64), 0, (hipStream_t)stream, b->d_states.get(), b->d_rings.get(), d_frames,
                        reinterpret_cast<const unsigned long long*>(d_stream_offsets), frame_stride_bytes, d_frame_bytes, n_frames, d_packets,
                        packet_stride_bytes, d_records, max_records, d_fec_frames, max_fec_frames, d_counts, (int)b->n, d_active, streams_per_flag);
     return dabgpu_check_hip(hipGetLastError(), "packet_kernel launch");
@@ -575,11 +567,11 @@ int dabgpu_packet_fec_read_host_sync(dabgpu_packet_bank* b, const uint8_t* h_buf
     if ((st = dabgpu_scratch(c, SCR_CONVERT_OUT, out_bytes, &d_out))) return st;
     uint8_t* dout = static_cast<uint8_t*>(d_out);
     DABGPU_CK(hipMemcpyAsync(d_in, h_buf, n_bytes, hipMemcpyHostToDevice, s));
-    DABGPU_CK(hipMemcpyAsync(b->d_n, &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if ((st = dabgpu_packet_bank_process(b, static_cast<const uint8_t*>(d_in), reinterpret_cast<const uint64_t*>(b->d_off), 0, b->d_n, 1, dout, cap,
+    DABGPU_CK(hipMemcpyAsync(b->d_n.get(), &n_bytes, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if ((st = dabgpu_packet_bank_process(b, static_cast<const uint8_t*>(d_in), reinterpret_cast<const uint64_t*>(b->d_off.get()), 0, b->d_n.get(), 1, dout, cap,
                                          reinterpret_cast<dabgpu_packet_record*>(dout + off_rec), max_records,
-                                         reinterpret_cast<dabgpu_packet_fec_frame*>(dout + off_fec), max_fec_frames, b->d_counts, s))) return st;
-    DABGPU_CK(hipMemcpyAsync(h_counts, b->d_counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                                         reinterpret_cast<dabgpu_packet_fec_frame*>(dout + off_fec), max_fec_frames, b->d_counts.get(), s))) return st;
+    DABGPU_CK(hipMemcpyAsync(h_counts, b->d_counts.get(), 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipStreamSynchronize(s));
     const size_t np = (size_t)std::min(std::max(h_counts[0], 0), max_records), nf = (size_t)std::min(std::max(h_counts[2], 0), max_fec_frames);
     if (h_counts[1] > 0) DABGPU_CK(hipMemcpyAsync(h_packets, dout, (size_t)h_counts[1], hipMemcpyDeviceToHost, s));

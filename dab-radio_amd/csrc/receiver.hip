@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <atomic>
+#include <new>
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
@@ -35,29 +36,30 @@ static constexpr size_t REC_SMALL = (sizeof(dabgpu_sync_state) + 15) & ~(size_t)
 
 struct dabgpu_receiver {
     dabgpu_ctx* ctx = nullptr;               // tables of the mode
-    hipStream_t a = nullptr;                 // stream A, at the device's highest stream priority: its launches are tens of microseconds long and the
+    dabgpu::Stream a;                        // stream A, at the device's highest stream priority: its launches are tens of microseconds long and the
                                              // host's frame position hangs on them; they must not queue behind another receiver's 0.2 ms trellis launch
     dabgpu_frame_session* ses = nullptr;     // history ring, decode, result slots + stream B
     int mode = 1;
     dabgpu::ModeGeom g{};
     size_t stage_cap = 0;                    // samples
-    float* h_stage[STAGES] = {nullptr, nullptr, nullptr};
-    hipEvent_t stage_free[STAGES] = {nullptr, nullptr, nullptr};
+    dabgpu::PinnedBuffer<float> stage[STAGES];
+    float* h_stage[STAGES] = {nullptr, nullptr, nullptr};      // (stage[k].get(): the array a bank is handed)
+    dabgpu::Event stage_free[STAGES];
     bool stage_pending[STAGES] = {false, false, false};
     int cur = 0;
-    float* d_prs = nullptr;                  // nb_fft samples of the PRS slot
-    float* d_iq = nullptr;                   // one frame, aligned
+    dabgpu::DeviceBuffer<float> d_prs;       // nb_fft samples of the PRS slot
+    dabgpu::DeviceBuffer<float> d_iq;        // one frame, aligned
     // one device record: [frequency state + last synchroniser record | 4 scalars | impulse response | coarse frequency response] -- the host reads
     // the state and the scalars after a frame in ONE copy (the head), the head and the responses after a synchronisation
-    void* d_rec = nullptr;
+    dabgpu::DeviceBuffer<> d_rec;
     dabgpu_sync_state* d_state = nullptr;    // (into d_rec)
     float* d_small = nullptr;                // (into d_rec) [0] net offset of the frame, [2] sum of the cyclic-prefix angles, [3] the frame's scale under DABGPU_SOFT_CSI
-    float* d_corr = nullptr;
+    dabgpu::DeviceBuffer<float> d_corr;
     float* d_imp = nullptr;                  // (into d_rec) impulse response | coarse frequency response, nb_fft floats each
-    float* d_fft = nullptr; float* d_dq = nullptr;
+    dabgpu::DeviceBuffer<float> d_fft, d_dq; // display views, allocated at first use
     // pinned: the synchroniser's record and responses
-    unsigned char* h_rec = nullptr;          // laid out like d_rec
-    hipEvent_t sync_done = nullptr; bool sync_pending = false; bool sync_coarse = false;
+    dabgpu::PinnedBuffer<unsigned char> h_rec;   // laid out like d_rec
+    dabgpu::Event sync_done; bool sync_pending = false; bool sync_coarse = false;
     std::atomic<int> decode_fic{0};          // (written by set_subchannels, read where the decode is submitted: possibly another thread)
     std::atomic<uint64_t> soft{0x42800000u}; // dabgpu_receiver_set_soft: policy << 32 | bits of the level (64.0f), read where a frame is submitted
     // a BANKED receiver (receiver_bank.hip): the staging buffers above are its own, everything else is the bank's; submit_* post jobs
@@ -68,32 +70,17 @@ struct dabgpu_receiver {
 extern "C" void dabgpu_receiver_destroy(dabgpu_receiver* rx) {
     if (!rx) return;
     if (rx->member) {
+        const dabgpu_ctx* bank_ctx = dabgpu_rx_bank_session(rx->member)->ctx;      // (the bank's: it stays for the life of the process)
         dabgpu_rx_bank_leave(rx->member);                            // (waits for the member's jobs: nothing reads the staging buffers afterwards)
-        (void)hipSetDevice(rx->device);
-        for (int k = 0; k < STAGES; k++) if (rx->h_stage[k]) (void)hipHostFree(rx->h_stage[k]);
-        delete rx;
+        if (dabgpu_destroy_begin(rx, bank_ctx, false)) delete rx;
         return;
     }
-    if (rx->ctx) {
-        (void)hipSetDevice(rx->ctx->device);
-        if (rx->a) (void)hipStreamSynchronize(rx->a);
-    }
+    if (!dabgpu_destroy_begin(rx, rx->ctx, false)) return;
+    if (rx->a) (void)hipStreamSynchronize(rx->a.get());
     if (rx->ses) dabgpu_frame_session_destroy(rx->ses);          // (synchronises stream B)
-    for (int k = 0; k < STAGES; k++) {
-        if (rx->h_stage[k]) (void)hipHostFree(rx->h_stage[k]);
-        if (rx->stage_free[k]) (void)hipEventDestroy(rx->stage_free[k]);
-    }
-    if (rx->d_prs) (void)hipFree(rx->d_prs);
-    if (rx->d_iq) (void)hipFree(rx->d_iq);
-    if (rx->d_rec) (void)hipFree(rx->d_rec);
-    if (rx->d_corr) (void)hipFree(rx->d_corr);
-    if (rx->d_fft) (void)hipFree(rx->d_fft);
-    if (rx->d_dq) (void)hipFree(rx->d_dq);
-    if (rx->h_rec) (void)hipHostFree(rx->h_rec);
-    if (rx->sync_done) (void)hipEventDestroy(rx->sync_done);
-    if (rx->a) (void)hipStreamDestroy(rx->a);
-    if (rx->ctx) dabgpu_destroy(rx->ctx);
+    dabgpu_ctx* c = rx->ctx;
     delete rx;
+    dabgpu_destroy(c);
 }
 
 extern "C" int dabgpu_receiver_create(dabgpu_receiver** out, int device, int mode, const float* h_prs, const int* h_mapper) {
@@ -102,42 +89,45 @@ extern "C" int dabgpu_receiver_create(dabgpu_receiver** out, int device, int mod
     dabgpu::ModeGeom g;
     if (!dabgpu::mode_geometry(mode, g)) { dabgpu_set_error("receiver_create: invalid transmission mode %d", mode); return DABGPU_ERR_INVALID_ARG; }
     if (mode != 1 && (h_prs || h_mapper)) { dabgpu_set_error("receiver_create: custom PRS / carrier tables are only supported in transmission mode I"); return DABGPU_ERR_INVALID_ARG; }
-    dabgpu_receiver* rx = new dabgpu_receiver();
+    dabgpu_receiver* rx = new (std::nothrow) dabgpu_receiver();
+    if (!rx) return DABGPU_ERR_HIP;
     rx->mode = mode;
     rx->g = g;
     int st = dabgpu_create(&rx->ctx, device, h_prs, h_mapper);
-    if (!st) st = dabgpu_frame_session_create(&rx->ses, device);
+    if (st) { delete rx; return st; }                                  // (no context, nothing else yet)
+    st = dabgpu_frame_session_create(&rx->ses, device);
     if (!st) {
         int least = 0, greatest = 0;                                   // (numerically lower = higher priority; both 0 where priorities do not exist)
         st = dabgpu_check_hip(hipDeviceGetStreamPriorityRange(&least, &greatest), "hipDeviceGetStreamPriorityRange");
-        if (!st) st = dabgpu_check_hip(hipStreamCreateWithPriority(&rx->a, hipStreamNonBlocking, greatest), "hipStreamCreateWithPriority(receiver)");
+        if (!st) st = rx->a.create(hipStreamNonBlocking, greatest, "hipStreamCreateWithPriority(receiver)");
     }
     const size_t n_fft = (size_t)g.n_fft, n_sym = (size_t)g.n_sym, frame_samples = (size_t)g.frame_samples;
     // NULL symbol | frame, the frame between nb_cyclic_prefix samples before and nb_fft - nb_cyclic_prefix - 1 after the expected position
     rx->stage_cap = (size_t)g.null_period + (n_fft - (size_t)g.n_cp) + frame_samples;
     for (int k = 0; k < STAGES && !st; k++) {
-        st = dabgpu_check_hip(hipHostMalloc((void**)&rx->h_stage[k], rx->stage_cap * 2 * sizeof(float), hipHostMallocDefault), "hipHostMalloc(receiver stage)");
-        if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&rx->stage_free[k], dabgpu_wait_event_flags(false)), "hipEventCreate(receiver)");
+        st = rx->stage[k].alloc(rx->stage_cap * 2, "hipHostMalloc(receiver stage)");
+        rx->h_stage[k] = rx->stage[k].get();
+        if (!st) st = rx->stage_free[k].create(dabgpu_wait_event_flags(false), "hipEventCreate(receiver)");
     }
-    if (!st) st = dabgpu_check_hip(hipMalloc((void**)&rx->d_prs, n_fft * 2 * sizeof(float)), "hipMalloc(receiver)");
-    if (!st) st = dabgpu_check_hip(hipMalloc((void**)&rx->d_iq, frame_samples * 2 * sizeof(float)), "hipMalloc(receiver)");
+    if (!st) st = rx->d_prs.alloc(n_fft * 2, "hipMalloc(receiver)");
+    if (!st) st = rx->d_iq.alloc(frame_samples * 2, "hipMalloc(receiver)");
     const size_t rec_bytes = REC_HEAD + 2 * n_fft * sizeof(float);
-    if (!st) st = dabgpu_check_hip(hipMalloc(&rx->d_rec, rec_bytes), "hipMalloc(receiver)");
-    if (!st) st = dabgpu_check_hip(hipMemsetAsync(rx->d_rec, 0, rec_bytes, rx->a), "hipMemsetAsync(receiver)");      // (on stream A: ordered before its first synchroniser)
+    if (!st) st = rx->d_rec.alloc(rec_bytes, "hipMalloc(receiver)");
+    if (!st) st = dabgpu_check_hip(hipMemsetAsync(rx->d_rec.get(), 0, rec_bytes, rx->a.get()), "hipMemsetAsync(receiver)");      // (on stream A: ordered before its first synchroniser)
     if (!st) {
-        rx->d_state = static_cast<dabgpu_sync_state*>(rx->d_rec);
-        rx->d_small = reinterpret_cast<float*>(static_cast<unsigned char*>(rx->d_rec) + REC_SMALL);
-        rx->d_imp = reinterpret_cast<float*>(static_cast<unsigned char*>(rx->d_rec) + REC_HEAD);
+        rx->d_state = static_cast<dabgpu_sync_state*>(rx->d_rec.get());
+        rx->d_small = reinterpret_cast<float*>(static_cast<unsigned char*>(rx->d_rec.get()) + REC_SMALL);
+        rx->d_imp = reinterpret_cast<float*>(static_cast<unsigned char*>(rx->d_rec.get()) + REC_HEAD);
     }
-    if (!st) st = dabgpu_check_hip(hipMalloc((void**)&rx->d_corr, n_sym * 2 * sizeof(float)), "hipMalloc(receiver)");
-    if (!st) st = dabgpu_check_hip(hipHostMalloc((void**)&rx->h_rec, rec_bytes, hipHostMallocDefault), "hipHostMalloc(receiver)");
-    if (!st) st = dabgpu_check_hip(hipEventCreateWithFlags(&rx->sync_done, dabgpu_wait_event_flags(false)), "hipEventCreate(receiver)");
+    if (!st) st = rx->d_corr.alloc(n_sym * 2, "hipMalloc(receiver)");
+    if (!st) st = rx->h_rec.alloc(rec_bytes, "hipHostMalloc(receiver)");
+    if (!st) st = rx->sync_done.create(dabgpu_wait_event_flags(false), "hipEventCreate(receiver)");
     // the result slots' page-locked soft-bit and scalar buffers now, not at the first frame that uses each slot (eight allocations of ~1 ms in the first eight frames
     // of a stream otherwise; the session frees them)
     for (int k = 0; k < dabgpu_frame_session::R && !st; k++) {
         dabgpu_frame_session::slot& sl = rx->ses->slots[k];
-        st = dabgpu_check_hip(hipHostMalloc((void**)&sl.h_aux, REC_HEAD, hipHostMallocDefault), "hipHostMalloc(receiver slot)");
-        if (!st) st = dabgpu_check_hip(hipHostMalloc((void**)&sl.h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault), "hipHostMalloc(receiver slot)");
+        st = sl.h_aux.alloc(REC_HEAD / sizeof(float), "hipHostMalloc(receiver slot)");
+        if (!st) st = sl.h_bits.alloc(DABGPU_NB_FRAME_BITS, "hipHostMalloc(receiver slot)");
     }
     if (st) { dabgpu_receiver_destroy(rx); return st; }
     *out = rx;
@@ -154,20 +144,19 @@ extern "C" int dabgpu_receiver_create_banked(dabgpu_receiver** out, int device) 
     if (device < 0 || device >= n) { dabgpu_set_error("device %d out of range (%d devices)", device, n); return DABGPU_ERR_INVALID_ARG; }
     int st = dabgpu_check_hip(hipSetDevice(device), "hipSetDevice");
     if (st) return st;
-    dabgpu_receiver* rx = new dabgpu_receiver();
+    dabgpu_receiver* rx = new (std::nothrow) dabgpu_receiver();
+    if (!rx) return DABGPU_ERR_HIP;
     rx->mode = 1;
     rx->device = device;
     rx->g = g;
     const size_t n_fft = (size_t)g.n_fft, frame_samples = (size_t)g.frame_samples;
     rx->stage_cap = (size_t)g.null_period + (n_fft - (size_t)g.n_cp) + frame_samples;
-    for (int k = 0; k < STAGES && !st; k++)
-        st = dabgpu_check_hip(hipHostMalloc((void**)&rx->h_stage[k], rx->stage_cap * 2 * sizeof(float), hipHostMallocDefault), "hipHostMalloc(receiver stage)");
-    if (!st) st = dabgpu_rx_bank_join(device, rx->h_stage, &rx->member);
-    if (st) {
-        for (int k = 0; k < STAGES; k++) if (rx->h_stage[k]) (void)hipHostFree(rx->h_stage[k]);
-        delete rx;
-        return st;
+    for (int k = 0; k < STAGES && !st; k++) {
+        st = rx->stage[k].alloc(rx->stage_cap * 2, "hipHostMalloc(receiver stage)");
+        rx->h_stage[k] = rx->stage[k].get();
     }
+    if (!st) st = dabgpu_rx_bank_join(device, rx->h_stage, &rx->member);
+    if (st) { delete rx; return st; }
     *out = rx;
     return DABGPU_OK;
 }
@@ -212,7 +201,7 @@ extern "C" int dabgpu_receiver_reset(dabgpu_receiver* rx) {
     if (rx->member) return dabgpu_rx_bank_reset(rx->member);
     DABGPU_BIND(rx->ctx);
     // :277-289 coarse = fine = 0, no coarse offset found -- behind everything already enqueued (a frame in flight keeps its offsets)
-    return dabgpu_check_hip(hipMemsetAsync(rx->d_state, 0, sizeof(dabgpu_sync_state), rx->a), "hipMemsetAsync(receiver state)");
+    return dabgpu_check_hip(hipMemsetAsync(rx->d_state, 0, sizeof(dabgpu_sync_state), rx->a.get()), "hipMemsetAsync(receiver state)");
 }
 
 extern "C" int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_sync_cfg* cfg, size_t prs_sample) {
@@ -223,16 +212,16 @@ extern "C" int dabgpu_receiver_submit_sync(dabgpu_receiver* rx, const dabgpu_syn
     if (rx->sync_pending) { dabgpu_set_error("receiver_submit_sync: the previous record has not been collected (dabgpu_receiver_wait_sync)"); return DABGPU_ERR_INVALID_ARG; }
     dabgpu_ctx* c = rx->ctx;
     DABGPU_BIND(c);
-    hipStream_t a = rx->a;
+    hipStream_t a = rx->a.get();
     int st;
-    DABGPU_CK(hipMemcpyAsync(rx->d_prs, rx->h_stage[rx->cur] + 2 * prs_sample, n_fft * 2 * sizeof(float), hipMemcpyHostToDevice, a));
+    DABGPU_CK(hipMemcpyAsync(rx->d_prs.get(), rx->h_stage[rx->cur] + 2 * prs_sample, n_fft * 2 * sizeof(float), hipMemcpyHostToDevice, a));
     rx->sync_coarse = cfg->is_coarse_freq_correction != 0;
-    if ((st = dabgpu_ofdm_sync_mode(c, rx->mode, rx->d_prs, 1, n_fft, cfg, rx->d_state, rx->d_imp, rx->sync_coarse ? rx->d_imp + n_fft : nullptr, a))) return st;
+    if ((st = dabgpu_ofdm_sync_mode(c, rx->mode, rx->d_prs.get(), 1, n_fft, cfg, rx->d_state, rx->d_imp, rx->sync_coarse ? rx->d_imp + n_fft : nullptr, a))) return st;
     // (two copies on purpose: head + responses in one is 48 bytes over 16 KiB, and a device-to-host copy above 16 KiB takes a slower path in the
     //  runtime -- +18 us until the record is on the host, tools/exp/ab_mirror.sh)
-    DABGPU_CK(hipMemcpyAsync(rx->h_rec, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
-    DABGPU_CK(hipMemcpyAsync(rx->h_rec + REC_HEAD, rx->d_imp, (rx->sync_coarse ? 2 : 1) * n_fft * sizeof(float), hipMemcpyDeviceToHost, a));
-    DABGPU_CK(hipEventRecord(rx->sync_done, a));
+    DABGPU_CK(hipMemcpyAsync(rx->h_rec.get(), rx->d_rec.get(), REC_HEAD, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipMemcpyAsync(rx->h_rec.get() + REC_HEAD, rx->d_imp, (rx->sync_coarse ? 2 : 1) * n_fft * sizeof(float), hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipEventRecord(rx->sync_done.get(), a));
     rx->sync_pending = true;
     return DABGPU_OK;
 }
@@ -243,10 +232,10 @@ extern "C" int dabgpu_receiver_wait_sync(dabgpu_receiver* rx, dabgpu_sync_state*
     if (!rx->sync_pending) { dabgpu_set_error("receiver_wait_sync: no synchronisation was submitted"); return DABGPU_ERR_NOT_READY; }
     DABGPU_BIND(rx->ctx);
     int st;
-    DABGPU_CK(hipEventSynchronize(rx->sync_done));
+    DABGPU_CK(hipEventSynchronize(rx->sync_done.get()));
     rx->sync_pending = false;
-    *out = *reinterpret_cast<const dabgpu_sync_state*>(rx->h_rec);
-    const float* h_imp = reinterpret_cast<const float*>(rx->h_rec + REC_HEAD);
+    *out = *reinterpret_cast<const dabgpu_sync_state*>(rx->h_rec.get());
+    const float* h_imp = reinterpret_cast<const float*>(rx->h_rec.get() + REC_HEAD);
     const size_t n_fft = (size_t)rx->g.n_fft;
     if (h_impulse) memcpy(h_impulse, h_imp, n_fft * sizeof(float));
     if (h_freq_response && rx->sync_coarse) memcpy(h_freq_response, h_imp + n_fft, n_fft * sizeof(float));
@@ -265,7 +254,7 @@ static int submit_demod(dabgpu_receiver* rx, size_t frame_sample, float beta, in
     uint64_t gen = 0;
     int8_t* d_bits = nullptr;
     dabgpu_frame_session::slot* sl = nullptr;
-    int st = dabgpu_session_reserve(rx->ses, rx->a, &gen, &d_bits, &sl);
+    int st = dabgpu_session_reserve(rx->ses, rx->a.get(), &gen, &d_bits, &sl);
     if (st) return st;
     // a failure behind the reservation gives the generation back: the session would otherwise refuse every later commit ("not the one reserved")
     // and the receiver were wedged for good
@@ -279,30 +268,21 @@ static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float
     const size_t frame_samples = (size_t)rx->g.frame_samples, n_fft = (size_t)rx->g.n_fft, n_sym = (size_t)rx->g.n_sym, frame_bits = (size_t)rx->g.frame_bits;
     dabgpu_ctx* c = rx->ctx;
     DABGPU_BIND(c);
-    hipStream_t a = rx->a;
+    hipStream_t a = rx->a.get();
     int st;
     const size_t fft_bytes = (n_sym + 1) * n_fft * 2 * sizeof(float), dq_bytes = (n_sym - 1) * (size_t)rx->g.n_carriers * 2 * sizeof(float);
     const bool want_dq = want_views && rx->mode == 1;
     if (want_views) {
-        if (!rx->d_fft) DABGPU_CK(hipMalloc((void**)&rx->d_fft, fft_bytes));
-        if (want_dq && !rx->d_dq) DABGPU_CK(hipMalloc((void**)&rx->d_dq, dq_bytes));
-        if (sl->h_fft_cap < fft_bytes) {
-            if (sl->h_fft) (void)hipHostFree(sl->h_fft);
-            sl->h_fft = nullptr; sl->h_fft_cap = 0;
-            DABGPU_CK(hipHostMalloc((void**)&sl->h_fft, fft_bytes, hipHostMallocDefault));
-            sl->h_fft_cap = fft_bytes;
-        }
-        if (want_dq && sl->h_dq_cap < dq_bytes) {
-            if (sl->h_dq) (void)hipHostFree(sl->h_dq);
-            sl->h_dq = nullptr; sl->h_dq_cap = 0;
-            DABGPU_CK(hipHostMalloc((void**)&sl->h_dq, dq_bytes, hipHostMallocDefault));
-            sl->h_dq_cap = dq_bytes;
-        }
+        // (no wait: the views are the receiver's for good, and the slot's previous frame was waited for when the slot was reserved)
+        if (!rx->d_fft && (st = rx->d_fft.alloc(fft_bytes / sizeof(float), "hipMalloc((void**)&rx->d_fft, fft_bytes)"))) return st;
+        if (want_dq && !rx->d_dq && (st = rx->d_dq.alloc(dq_bytes / sizeof(float), "hipMalloc((void**)&rx->d_dq, dq_bytes)"))) return st;
+        if ((st = sl->h_fft.regrow(fft_bytes / sizeof(float), "hipHostMalloc((void**)&sl->h_fft, fft_bytes, hipHostMallocDefault)"))) return st;
+        if (want_dq && (st = sl->h_dq.regrow(dq_bytes / sizeof(float), "hipHostMalloc((void**)&sl->h_dq, dq_bytes, hipHostMallocDefault)"))) return st;
     }
-    if (!sl->h_aux) DABGPU_CK(hipHostMalloc((void**)&sl->h_aux, REC_HEAD, hipHostMallocDefault));
-    if (!sl->h_bits) DABGPU_CK(hipHostMalloc((void**)&sl->h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault));
-    DABGPU_CK(hipMemcpyAsync(rx->d_iq, rx->h_stage[rx->cur] + 2 * frame_sample, frame_samples * 2 * sizeof(float), hipMemcpyHostToDevice, a));
-    DABGPU_CK(hipEventRecord(rx->stage_free[rx->cur], a));
+    if (!sl->h_aux && (st = sl->h_aux.alloc(REC_HEAD / sizeof(float), "hipHostMalloc((void**)&sl->h_aux, REC_HEAD, hipHostMallocDefault)"))) return st;
+    if (!sl->h_bits && (st = sl->h_bits.alloc(DABGPU_NB_FRAME_BITS, "hipHostMalloc((void**)&sl->h_bits, DABGPU_NB_FRAME_BITS, hipHostMallocDefault)"))) return st;
+    DABGPU_CK(hipMemcpyAsync(rx->d_iq.get(), rx->h_stage[rx->cur] + 2 * frame_sample, frame_samples * 2 * sizeof(float), hipMemcpyHostToDevice, a));
+    DABGPU_CK(hipEventRecord(rx->stage_free[rx->cur].get(), a));
     rx->stage_pending[rx->cur] = true;
     rx_net_freq_kernel<<<1, 64, 0, a>>>(rx->d_state, rx->d_small);
     DABGPU_CK(hipGetLastError());
@@ -313,24 +293,24 @@ static int submit_demod_reserved(dabgpu_receiver* rx, size_t frame_sample, float
     { const uint32_t lb = (uint32_t)soft_word; memcpy(&soft.level, &lb, sizeof(float)); }
     sl->soft_csi = rx->mode == 1 && soft.policy != DABGPU_SOFT_NORMALISED;      // (dabgpu_receiver_frame_soft_scale)
     st = sl->soft_csi
-             ? dabgpu_ofdm_demod_frames_soft(c, rx->d_iq, DABGPU_IQ_RAW_F32L, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr,
-                                             want_dq ? rx->d_dq : nullptr, 0, 0, DABGPU_BITS_NATURAL, &soft, rx->d_small + 3, a)
-         : (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, want_dq ? rx->d_dq : nullptr, 0, 0, a)
-                         : dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq, 1, rx->d_small, d_bits, rx->d_corr, want_views ? rx->d_fft : nullptr, 0, a);
-    if (st || (st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr, 1, beta, rx->d_small + 2, d_fine, a))) return st;
+             ? dabgpu_ofdm_demod_frames_soft(c, rx->d_iq.get(), DABGPU_IQ_RAW_F32L, 1, rx->d_small, d_bits, rx->d_corr.get(), want_views ? rx->d_fft.get() : nullptr,
+                                             want_dq ? rx->d_dq.get() : nullptr, 0, 0, DABGPU_BITS_NATURAL, &soft, rx->d_small + 3, a)
+         : (rx->mode == 1) ? dabgpu_ofdm_demod_frames(c, rx->d_iq.get(), 1, rx->d_small, d_bits, rx->d_corr.get(), want_views ? rx->d_fft.get() : nullptr, want_dq ? rx->d_dq.get() : nullptr, 0, 0, a)
+                         : dabgpu_ofdm_demod_frames_mode(c, rx->mode, rx->d_iq.get(), 1, rx->d_small, d_bits, rx->d_corr.get(), want_views ? rx->d_fft.get() : nullptr, 0, a);
+    if (st || (st = dabgpu_ofdm_phase_update_mode(c, rx->mode, rx->d_corr.get(), 1, beta, rx->d_small + 2, d_fine, a))) return st;
     // the decode may start; what the host reads of this frame -- soft bits, h_aux (the head of the device record: the frequency state after this frame's update, the sum of
     // the cyclic-prefix angles), the display views -- is copied on THIS stream beside it (the 230 KB of soft bits used to sit on the session's
     // stream in front of every trellis launch); the slot's done event waits for both
-    DABGPU_CK(hipEventRecord(sl->ev_ready, a));
-    DABGPU_CK(hipMemcpyAsync(sl->h_bits, d_bits, frame_bits, hipMemcpyDeviceToHost, a));
-    DABGPU_CK(hipMemcpyAsync(sl->h_aux, rx->d_rec, REC_HEAD, hipMemcpyDeviceToHost, a));
-    if (want_views) DABGPU_CK(hipMemcpyAsync(sl->h_fft, rx->d_fft, fft_bytes, hipMemcpyDeviceToHost, a));
-    if (want_dq) DABGPU_CK(hipMemcpyAsync(sl->h_dq, rx->d_dq, dq_bytes, hipMemcpyDeviceToHost, a));
-    DABGPU_CK(hipEventRecord(sl->ev_copied, a));
+    DABGPU_CK(hipEventRecord(sl->ev_ready.get(), a));
+    DABGPU_CK(hipMemcpyAsync(sl->h_bits.get(), d_bits, frame_bits, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipMemcpyAsync(sl->h_aux.get(), rx->d_rec.get(), REC_HEAD, hipMemcpyDeviceToHost, a));
+    if (want_views) DABGPU_CK(hipMemcpyAsync(sl->h_fft.get(), rx->d_fft.get(), fft_bytes, hipMemcpyDeviceToHost, a));
+    if (want_dq) DABGPU_CK(hipMemcpyAsync(sl->h_dq.get(), rx->d_dq.get(), dq_bytes, hipMemcpyDeviceToHost, a));
+    DABGPU_CK(hipEventRecord(sl->ev_copied.get(), a));
     // the next frame is assembled in the next staging buffer; its last upload (STAGES frames ago) has long finished
     rx->cur = (rx->cur + 1) % STAGES;
     if (rx->stage_pending[rx->cur]) {
-        DABGPU_CK(hipEventSynchronize(rx->stage_free[rx->cur]));
+        DABGPU_CK(hipEventSynchronize(rx->stage_free[rx->cur].get()));
         rx->stage_pending[rx->cur] = false;
     }
     return DABGPU_OK;
@@ -360,7 +340,7 @@ extern "C" int dabgpu_receiver_submit_frame(dabgpu_receiver* rx, size_t frame_sa
     const int fic = rx->decode_fic.load();
     bool decode;
     { std::lock_guard<std::mutex> lock(rx->ses->mu); decode = rx->mode == 1 && (fic || !rx->ses->subs.empty()); }
-    if ((st = dabgpu_session_commit(rx->ses, gen, sl->ev_ready, 0, decode ? 1 : 0, fic, tie_rule, sl->ev_copied))) return st;
+    if ((st = dabgpu_session_commit(rx->ses, gen, sl->ev_ready.get(), 0, decode ? 1 : 0, fic, tie_rule, sl->ev_copied.get()))) return st;
     if (generation) *generation = gen;
     return DABGPU_OK;
 }
@@ -383,7 +363,7 @@ extern "C" int dabgpu_receiver_submit_decode(dabgpu_receiver* rx, uint64_t gener
     dabgpu_frame_session* s = rx->ses;
     DABGPU_BIND(s->ctx);
     dabgpu_frame_session::slot* sl = &s->slots[generation % dabgpu_frame_session::R];
-    int st = dabgpu_check_hip(hipEventSynchronize(sl->ev_ready), "hipEventSynchronize(receiver frame demodulated)");
+    int st = dabgpu_check_hip(hipEventSynchronize(sl->ev_ready.get()), "hipEventSynchronize(receiver frame demodulated)");
     if (st) return st;
     const int fic = rx->decode_fic.load();
     bool decode;
@@ -402,7 +382,7 @@ extern "C" int dabgpu_receiver_wait_frame(dabgpu_receiver* rx, uint64_t generati
     {
         std::lock_guard<std::mutex> lock(s->mu);
         if (sl->gen != generation) { dabgpu_set_error("receiver_wait_frame: generation %llu is gone or was never submitted", (unsigned long long)generation); return DABGPU_ERR_NOT_READY; }
-        if (sl->pending) done = sl->done;
+        if (sl->pending) done = sl->done.get();
     }
     // waited for outside the session's lock: the producer thread submits the next frame meanwhile (the slot is not reused before
     // R more frames were submitted -- the caller bounds the frames in flight)
@@ -413,14 +393,14 @@ extern "C" int dabgpu_receiver_wait_frame(dabgpu_receiver* rx, uint64_t generati
         if (sl->gen == generation) sl->pending = false;
     }
     // (the host copies of the producer stream: already behind `done` after dabgpu_receiver_submit_frame, on their own after _submit_decode)
-    { int st = dabgpu_check_hip(hipEventSynchronize(sl->ev_copied), "hipEventSynchronize(receiver copies)"); if (st) return st; }
+    { int st = dabgpu_check_hip(hipEventSynchronize(sl->ev_copied.get()), "hipEventSynchronize(receiver copies)"); if (st) return st; }
     out->generation = generation;
-    out->bits = sl->h_bits;
+    out->bits = sl->h_bits.get();
     out->n_bits = (size_t)rx->g.frame_bits;
-    out->freq_fine = reinterpret_cast<const dabgpu_sync_state*>(sl->h_aux)->freq_fine;
-    out->total_phase = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux) + REC_SMALL)[2];
-    out->fft = sl->h_fft;
-    out->dqpsk = sl->h_dq;
+    out->freq_fine = reinterpret_cast<const dabgpu_sync_state*>(sl->h_aux.get())->freq_fine;
+    out->total_phase = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux.get()) + REC_SMALL)[2];
+    out->fft = sl->h_fft.get();
+    out->dqpsk = sl->h_dq.get();
     return DABGPU_OK;
 }
 
@@ -434,6 +414,6 @@ extern "C" int dabgpu_receiver_frame_soft_scale(dabgpu_receiver* rx, uint64_t ge
     dabgpu_frame_session::slot* sl = &s->slots[generation % dabgpu_frame_session::R];
     std::lock_guard<std::mutex> lock(s->mu);
     if (sl->gen != generation || !sl->h_aux) { dabgpu_set_error("receiver_frame_soft_scale: generation %llu is gone or was never submitted", (unsigned long long)generation); return DABGPU_ERR_NOT_READY; }
-    if (sl->soft_csi) *scale = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux) + REC_SMALL)[3];
+    if (sl->soft_csi) *scale = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sl->h_aux.get()) + REC_SMALL)[3];
     return DABGPU_OK;
 }

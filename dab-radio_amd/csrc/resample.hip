@@ -13,6 +13,7 @@
 // the same for the whole workgroup (scalar loads).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <new>
 #include <vector>
 
 #include "dabgpu.h"
@@ -146,7 +147,8 @@ int dabgpu_resample_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_re
     const uint64_t max_step_q62 = dabgpu_host_resample_max_step_q62(design->max_step);
     int st = dabgpu_host_resample_plan("resample_bank_create", h_params, n_streams, max_step_q62, &g);
     if (st) return st;
-    dabgpu_resample_bank* b = new dabgpu_resample_bank;
+    dabgpu_resample_bank* b = new (std::nothrow) dabgpu_resample_bank;
+    if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n = n_streams; b->geom = g; b->max_step_q62 = max_step_q62;
     auto fail = [&](int status) { dabgpu_resample_bank_destroy(b); return status; };
     if ((st = dabgpu_bind_device(c))) return fail(st);
@@ -172,8 +174,7 @@ int dabgpu_resample_bank_create(dabgpu_ctx* c, size_t n_streams, const dabgpu_re
 }
 
 void dabgpu_resample_bank_destroy(dabgpu_resample_bank* b) {
-    if (!b) return;
-    sb_release(b);
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 

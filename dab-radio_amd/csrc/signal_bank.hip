@@ -14,12 +14,12 @@ void sb_enqueue_advance(uint64_t* d_pos, size_t n_out, hipStream_t s) {
 int sb_alloc(SignalBank* b, size_t payload_bytes, const char* label, uint8_t** payload) {
     char what[64];
     snprintf(what, sizeof(what), "hipMalloc(%s bank)", label);
-    int st = dabgpu_check_hip(hipMalloc(&b->d_mem, 16 + payload_bytes), what);
+    int st = b->d_mem.alloc(16 + payload_bytes, what);
     if (st) return st;
-    b->d_pos = static_cast<uint64_t*>(b->d_mem);
-    *payload = static_cast<uint8_t*>(b->d_mem) + 16;
+    b->d_pos = static_cast<uint64_t*>(b->d_mem.get());
+    *payload = static_cast<uint8_t*>(b->d_mem.get()) + 16;
     snprintf(what, sizeof(what), "hipMemsetAsync(%s position)", label);
-    return dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, 16, b->ctx->stream), what);
+    return dabgpu_check_hip(hipMemsetAsync(b->d_pos, 0, 16, b->ctx->stream), what);
 }
 
 int sb_seek(SignalBank* b, const char* who, uint64_t position, uint64_t cap, const char* cap_text, void* stream) {
@@ -27,25 +27,6 @@ int sb_seek(SignalBank* b, const char* who, uint64_t position, uint64_t cap, con
     if (position > cap) { dabgpu_set_error("%s: position above %s", who, cap_text); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(b->ctx);
     return dabgpu_stage_h2d(b->ctx, b->d_pos, &position, sizeof(position), (hipStream_t)stream);
-}
-
-bool sb_release(SignalBank* b) {
-    if (!b->ctx || dabgpu_bind_device(b->ctx) != DABGPU_OK) return false;
-    (void)hipDeviceSynchronize();
-    for (void* p : b->buf) if (p) (void)hipFree(p);
-    if (b->d_mem) (void)hipFree(b->d_mem);
-    return true;
-}
-
-int sb_buffer(SignalBank* b, int which, size_t bytes, void** out) {
-    int st = DABGPU_OK;
-    if (b->buf_bytes[which] < bytes) {
-        if (b->buf[which]) { DABGPU_CK(hipDeviceSynchronize()); DABGPU_CK(hipFree(b->buf[which])); b->buf[which] = nullptr; b->buf_bytes[which] = 0; }
-        DABGPU_CK(hipMalloc(&b->buf[which], bytes));
-        b->buf_bytes[which] = bytes;
-    }
-    *out = b->buf[which];
-    return st;
 }
 
 }  // namespace dabgpu

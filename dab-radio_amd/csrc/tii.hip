@@ -94,12 +94,11 @@ struct dabgpu_tii_bank {
     dabgpu_ctx* ctx = nullptr;
     size_t n = 0;
     float threshold = DABGPU_TII_DEFAULT_THRESHOLD;
-    void* d_mem = nullptr;                      // one allocation: accumulators [n][192] | frame counts [n]
-    float* d_acc = nullptr;
+    DeviceBuffer<> d_mem;                       // one allocation: accumulators [n][192] | frame counts [n]
+    float* d_acc = nullptr;                     // (into d_mem)
     uint32_t* d_frames = nullptr;
     // host form (one receiver): the window's samples, records and count
-    void* d_host_iq = nullptr;
-    void* d_host_res = nullptr;
+    DeviceBuffer<> d_host_iq, d_host_res;
 };
 
 static int tii_launch(dabgpu_tii_bank* b, const float* d_iq, size_t stride, long long null_offset, const dabgpu_sync_state* d_states, const float* d_freq,
@@ -121,38 +120,33 @@ int dabgpu_tii_bank_create(dabgpu_ctx* c, size_t n, const dabgpu_tii_cfg* cfg, d
     if (!(cfg->threshold >= 1.0f) || !(cfg->threshold <= 1.0e6f)) {
         dabgpu_set_error("tii_bank_create: threshold %g outside 1 .. 1e6", (double)cfg->threshold); return DABGPU_ERR_INVALID_ARG;
     }
-    dabgpu_tii_bank* b = new dabgpu_tii_bank;
+    dabgpu_tii_bank* b = new (std::nothrow) dabgpu_tii_bank;
+    if (!b) return DABGPU_ERR_HIP;
     b->ctx = c; b->n = n; b->threshold = cfg->threshold;
     auto fail = [&](int status) { dabgpu_tii_bank_destroy(b); return status; };
     int st;
     if ((st = dabgpu_bind_device(c))) return fail(st);
     const size_t acc_bytes = n * TII_ACC * sizeof(float), bytes = acc_bytes + n * sizeof(uint32_t);
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_mem, bytes), "hipMalloc(tii bank)"))) return fail(st);
-    b->d_acc = static_cast<float*>(b->d_mem);
-    b->d_frames = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b->d_mem) + acc_bytes);
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_host_res, TII_COMBS * sizeof(dabgpu_tii_record) + 16), "hipMalloc(tii results)"))) return fail(st);
-    if ((st = dabgpu_check_hip(hipMalloc(&b->d_host_iq, (size_t)TII_FFT * 8), "hipMalloc(tii window)"))) return fail(st);
-    if ((st = dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, bytes, c->stream), "hipMemsetAsync(tii bank)"))) return fail(st);
+    if ((st = b->d_mem.alloc(bytes, "hipMalloc(tii bank)"))) return fail(st);
+    b->d_acc = static_cast<float*>(b->d_mem.get());
+    b->d_frames = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(b->d_mem.get()) + acc_bytes);
+    if ((st = b->d_host_res.alloc(TII_COMBS * sizeof(dabgpu_tii_record) + 16, "hipMalloc(tii results)"))) return fail(st);
+    if ((st = b->d_host_iq.alloc((size_t)TII_FFT * 8, "hipMalloc(tii window)"))) return fail(st);
+    if ((st = dabgpu_check_hip(hipMemsetAsync(b->d_acc, 0, bytes, c->stream), "hipMemsetAsync(tii bank)"))) return fail(st);
     if ((st = dabgpu_check_hip(hipStreamSynchronize(c->stream), "hipStreamSynchronize(tii_bank_create)"))) return fail(st);
     *out = b;
     return DABGPU_OK;
 }
 
 void dabgpu_tii_bank_destroy(dabgpu_tii_bank* b) {
-    if (!b) return;
-    if (b->ctx && dabgpu_bind_device(b->ctx) == DABGPU_OK) {
-        (void)hipDeviceSynchronize();
-        if (b->d_host_iq) (void)hipFree(b->d_host_iq);
-        if (b->d_host_res) (void)hipFree(b->d_host_res);
-        if (b->d_mem) (void)hipFree(b->d_mem);
-    }
+    if (!dabgpu_destroy_begin(b, b ? b->ctx : nullptr)) return;
     delete b;
 }
 
 int dabgpu_tii_bank_reset(dabgpu_tii_bank* b, void* stream) {
     if (!b) { dabgpu_set_error("tii_bank_reset: null bank"); return DABGPU_ERR_INVALID_ARG; }
     DABGPU_BIND(b->ctx);
-    return dabgpu_check_hip(hipMemsetAsync(b->d_mem, 0, b->n * (TII_ACC * sizeof(float) + sizeof(uint32_t)), (hipStream_t)stream),
+    return dabgpu_check_hip(hipMemsetAsync(b->d_acc, 0, b->n * (TII_ACC * sizeof(float) + sizeof(uint32_t)), (hipStream_t)stream),
                             "hipMemsetAsync(tii_bank_reset)");
 }
 
@@ -195,10 +189,10 @@ int dabgpu_tii_bank_process_host_sync(dabgpu_tii_bank* b, const float* h_iq, siz
     hipStream_t s = c->stream;
     // only the window travels
     const size_t bytes = (size_t)TII_FFT * 8;
-    dabgpu_tii_record* d_res = static_cast<dabgpu_tii_record*>(b->d_host_res);
+    dabgpu_tii_record* d_res = static_cast<dabgpu_tii_record*>(b->d_host_res.get());
     uint32_t* d_cnt = reinterpret_cast<uint32_t*>(d_res + TII_COMBS);
-    DABGPU_CK(hipMemcpyAsync(b->d_host_iq, h_iq + 2 * (size_t)first, bytes, hipMemcpyHostToDevice, s));
-    if ((st = tii_launch(b, static_cast<const float*>(b->d_host_iq), TII_FFT, -(long long)TII_PREFIX, nullptr, nullptr, freq_offset, 0, decide, d_res,
+    DABGPU_CK(hipMemcpyAsync(b->d_host_iq.get(), h_iq + 2 * (size_t)first, bytes, hipMemcpyHostToDevice, s));
+    if ((st = tii_launch(b, static_cast<const float*>(b->d_host_iq.get()), TII_FFT, -(long long)TII_PREFIX, nullptr, nullptr, freq_offset, 0, decide, d_res,
                          d_cnt, s)))
         return st;
     if (decide) {
