@@ -3,6 +3,7 @@
 #include "packet_fec_core.h"
 #include "softbit_csi_core.h"
 #include "diversity_core.h"
+#include "noise_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -148,6 +149,42 @@ int dabgpu_diversity_plan(const dabgpu_diversity_branch* h_branches, int n_branc
         }
     }
     return dabgpu_host_plan_diversity(n_branches, n_frames, bits_layout, symbols_per_block, bits_frame_stride, out);
+}
+
+float dabgpu_noise_unbias(void) { return dabgpu::NOISE_UNBIAS; }
+
+int dabgpu_noise_floor_host(const float group_energy[192], float signal_power, dabgpu_noise_record* out) {
+    if (out) *out = dabgpu_noise_record{};
+    if (!group_energy || !out) return 0;
+    return dabgpu::noise_finish(dabgpu::noise_floor(group_energy), signal_power, out) ? 1 : 0;
+}
+
+int dabgpu_noise_plan(int transmission_mode, const float* d_iq, size_t n_frames, size_t stream_stride_samples, size_t null_offset_samples,
+                      const dabgpu_sync_state* d_states, const float* d_freq_offset, const float* d_noise_power, const float* d_signal_power,
+                      const float* d_weight, const float* d_snr, const float* d_group_energy, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
+    if (!out) { dabgpu_set_error("noise_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("noise_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("noise_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_iq) { dabgpu_set_error("noise_plan: null samples"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("noise_plan: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_states | (uintptr_t)d_freq_offset | (uintptr_t)d_noise_power | (uintptr_t)d_signal_power | (uintptr_t)d_weight | (uintptr_t)d_snr |
+         (uintptr_t)d_group_energy | (uintptr_t)d_valid) & 3) {
+        dabgpu_set_error("noise_plan: records, offsets and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    const size_t reach = (size_t)dabgpu::NOISE_REACH + (d_states ? 1543u : 0u);
+    if (null_offset_samples > ((size_t)1 << 40) || stream_stride_samples > ((size_t)1 << 40) || stream_stride_samples < null_offset_samples + reach) {
+        dabgpu_set_error("noise_plan: stream_stride_samples %zu does not hold null_offset_samples %zu + %zu", stream_stride_samples, null_offset_samples,
+                         reach);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!d_noise_power && !d_signal_power && !d_weight && !d_snr && !d_group_energy && !d_valid) {
+        dabgpu_set_error("noise_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
+    }
+    out->grid = (uint32_t)n_frames;
+    out->threads = DABGPU_NOISE_THREADS;
+    out->lds_bytes = DABGPU_NOISE_LDS_BYTES;
+    return DABGPU_OK;
 }
 
 void dabgpu_stream_cfg_default(dabgpu_stream_cfg* c) {

@@ -236,6 +236,12 @@ int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg);
 int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout, int symbols_per_block, size_t bits_frame_stride,
                                dabgpu_diversity_geometry* out);
 
+// ---- noise estimator (noise.hip launches from dabgpu_noise_plan; include/dabgpu.h, "Noise estimate") ----
+// one 256-thread workgroup per frame; static LDS: the transform's patches, 2048 bin powers, 192 group energies, 24 floor shares, the four
+// wave sums of the frame power and the decision word
+#define DABGPU_NOISE_THREADS 256u
+#define DABGPU_NOISE_LDS_BYTES (18432u + 8192u + 768u + 96u + 16u + 4u)
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

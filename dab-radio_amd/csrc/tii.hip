@@ -2,9 +2,8 @@
 // 24 x 8 group energies per receiver, accumulated over frames and decided against a noise floor.  The arithmetic behind the transform is
 // tii_core.h's (shared with the tests' host model); the transform is ofdm_fft_lds.h's, the PLL ofdm_device.h's.
 //
-// One 256-thread workgroup per receiver.  Thread t reads the window samples 2 t + 512 j, 2 t + 1 + 512 j (j < 4: the eight inputs of its
-// first butterflies) as four 16-byte loads (8-byte loads when the window starts on an odd sample), rotates them in registers and puts
-// them into LDS with 16-byte stores; fft2048_lds in place; 2048 powers into LDS; threads 0 .. 191 own one (comb, group) each for the fold
+// One 256-thread workgroup per receiver.  Window, rotation, transform and the 2048 powers in LDS are null_window.h's (shared with the
+// noise estimator, noise.hip); threads 0 .. 191 own one (comb, group) each for the fold
 // and the accumulate; wave 0 decides: lane c < 24 sorts comb c in registers, the 24 floor shares meet in LDS and every lane sums them in
 // the same order, the active lanes compact their records in comb order through a ballot.  LDS: 18432 + 8192 + 768 + 96 bytes.
 #include <hip/hip_runtime.h>
@@ -12,9 +11,7 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
-#include "ofdm_device.h"
-#include "ofdm_fft_lds.h"
-#include "tii_core.h"
+#include "null_window.h"
 
 namespace dabgpu {
 
@@ -41,24 +38,8 @@ void tii_kernel(const f2* __restrict__ iq, size_t stride, long long null_offset,
     }
     if (freq) { const float fc = freq[rx]; if (fc == fc) f = fc; }                   // a caller's offset (NaN: none for this receiver)
     const f2* win = iq + rx * stride + (null_offset + fto + TII_PREFIX);
-    const bool wide = ((uintptr_t)win & 15) == 0;
     const Fft2048Tw w = fft2048_twiddles(tw);
-
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int n = 2 * t + 512 * j;
-        f2 a, b;
-        if (wide) { const f4 v = *reinterpret_cast<const f4*>(win + n); a = mk2(v.x, v.y); b = mk2(v.z, v.w); }
-        else { a = win[n]; b = win[n + 1]; }
-        a = pll_any(a, n, TII_FFT, f, 0.0f);
-        b = pll_any(b, n + 1, TII_FFT, f, 0.0f);
-        *reinterpret_cast<f4*>(A + n) = f4{a.x, a.y, b.x, b.y};
-    }
-    __syncthreads();
-    fft2048_lds(A, w, false);
-#pragma unroll
-    for (int r = 0; r < 8; r++) { const f2 x = A[t + 256 * r]; Pw[t + 256 * r] = tii_power(x.x, x.y); }
-    __syncthreads();
+    null_window_powers(win, f, w, A, Pw, t);
     if (t < TII_ACC) {
         const float e = tii_fold([&](int bin) { return Pw[bin]; }, t >> 3, t & 7);
         const float a = acc[rx * TII_ACC + t] + e;

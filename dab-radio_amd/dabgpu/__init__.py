@@ -96,9 +96,11 @@ ABI_SYMBOLS = [
     "dabgpu_receiver_set_soft", "dabgpu_stream_bank_set_soft", "dabgpu_stream_bank_get_soft",
     "dabgpu_diversity_plan", "dabgpu_diversity_combine_frames", "dabgpu_diversity_combine_host_sync", "dabgpu_diversity_scale_host",
     "dabgpu_ofdm_sync_demod_frames_branch", "dabgpu_receiver_frame_soft_scale",
+    "dabgpu_noise_plan", "dabgpu_noise_estimate_frames", "dabgpu_noise_estimate_host_sync", "dabgpu_noise_unbias", "dabgpu_noise_floor_host",
 ]
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 DIVERSITY_MAX_BRANCHES = 8                # receive diversity (include/dabgpu.h)
+NOISE_RECORD_DTYPE = [("noise_power", "<f4"), ("signal_power", "<f4"), ("weight", "<f4"), ("snr", "<f4"), ("valid", "<u4")]   # dabgpu_noise_record
 
 # channel model (include/dabgpu.h)
 CHANNEL_MAX_TAPS = 8
@@ -192,6 +194,11 @@ class DiversityGeometry(C.Structure):
     """dabgpu_diversity_geometry"""
     _fields_ = [("symbols_per_block", C.c_uint32), ("runs_per_frame", C.c_uint32), ("grid", C.c_uint32), ("threads", C.c_uint32),
                 ("lds_bytes", C.c_uint32)]
+
+
+class NoiseGeometry(C.Structure):
+    """dabgpu_noise_geometry"""
+    _fields_ = [("grid", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
 class ChannelStream(C.Structure):
@@ -391,6 +398,12 @@ def lib():
                                                          C.c_void_p, C.c_void_p]
         L.dabgpu_diversity_scale_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.dabgpu_diversity_scale_host.restype = C.c_float
+        L.dabgpu_noise_plan.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 9
+        L.dabgpu_noise_estimate_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 9
+        L.dabgpu_noise_estimate_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_void_p]
+        L.dabgpu_noise_unbias.argtypes = []
+        L.dabgpu_noise_unbias.restype = C.c_float
+        L.dabgpu_noise_floor_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
         L.dabgpu_ofdm_sync_demod_frames_branch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p]
@@ -826,6 +839,25 @@ class Context:
         check(lib().dabgpu_diversity_combine_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits), C.byref(out_k),
                                                        C.byref(out_m)), "dabgpu_diversity_combine_host_sync")
         return bits, out_k.value, out_m.value
+
+    def noise_estimate(self, iq, n_frames, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, noise_power=None,
+                       signal_power=None, weight=None, snr=None, group_energy=None, valid=None, stream=None):
+        """the noise estimate of n_frames frames (include/dabgpu.h, "Noise estimate"): every output an optional device buffer, [n_frames]
+        float32 each (group_energy [n_frames][192], valid uint32); `weight` can be a diversity branch's weight array as it is.  One kernel
+        launch, no copy: capturable"""
+        check(lib().dabgpu_noise_estimate_frames(self._h, _ptr(iq), n_frames, stream_stride_samples, null_offset_samples, _ptr(states),
+                                                 _ptr(freq_offset), _ptr(noise_power), _ptr(signal_power), _ptr(weight), _ptr(snr),
+                                                 _ptr(group_energy), _ptr(valid), self._stream(stream)), "dabgpu_noise_estimate_frames")
+
+    def noise_estimate_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0):
+        """numpy convenience over dabgpu_noise_estimate_host_sync: one frame's NULL and phase reference symbol out of complex64 samples ->
+        a NOISE_RECORD_DTYPE record"""
+        import numpy as np
+        x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+        rec = np.zeros(1, np.dtype(NOISE_RECORD_DTYPE))
+        check(lib().dabgpu_noise_estimate_host_sync(self._h, _ptr(x), x.size, null_offset_samples, float(freq_offset), int(fine_time_offset),
+                                                    _ptr(rec)), "dabgpu_noise_estimate_host_sync")
+        return rec[0]
 
     def ofdm_tune(self, raw, fmt, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, with_phase_tail=False, stream=None):
         """explicit (blocking) calibration of symbols_per_block = 0 for this call shape; returns the run length recorded"""
@@ -1899,6 +1931,31 @@ def diversity_plan(branches, n_frames, bits, bits_frame_stride=0, bits_layout=BI
     check(lib().dabgpu_diversity_plan(table if len(table) else None, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
                                       int(symbols_per_block), C.byref(g)), "dabgpu_diversity_plan")
     return g
+
+
+def noise_plan(iq, n_frames, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, noise_power=None, signal_power=None,
+               weight=None, snr=None, group_energy=None, valid=None, mode=1):
+    """dabgpu_noise_plan (host only, nothing is dereferenced): the NoiseGeometry of a noise_estimate call with these arguments; raises
+    DabGpuError with the reason where that call would be refused"""
+    g = NoiseGeometry()
+    check(lib().dabgpu_noise_plan(int(mode), _ptr(iq), n_frames, stream_stride_samples, null_offset_samples, _ptr(states), _ptr(freq_offset),
+                                  _ptr(noise_power), _ptr(signal_power), _ptr(weight), _ptr(snr), _ptr(group_energy), _ptr(valid), C.byref(g)),
+          "dabgpu_noise_plan")
+    return g
+
+
+def noise_unbias():
+    """the calibration constant of the noise estimate: noise_power = floor * noise_unbias()"""
+    return float(lib().dabgpu_noise_unbias())
+
+
+def noise_floor_host(group_energy, signal_power):
+    """steps 2 .. 5 of the noise estimate on the host: 192 group energies and the frame power -> a NOISE_RECORD_DTYPE record"""
+    import numpy as np
+    E = np.ascontiguousarray(group_energy, dtype=np.float32).reshape(TII_COMBS * TII_GROUPS)
+    rec = np.zeros(1, np.dtype(NOISE_RECORD_DTYPE))
+    lib().dabgpu_noise_floor_host(_ptr(E), float(signal_power), _ptr(rec))
+    return rec[0]
 
 
 def diversity_scale(scales, weights=None, valid=None):

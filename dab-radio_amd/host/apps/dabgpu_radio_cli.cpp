@@ -19,6 +19,18 @@
 // The reader must not overwrite the buffer's head while the observer reads it, so with --tii every Process() call is followed by
 // Synchronize() and --ofdm-block-size may not exceed one frame less a NULL period.
 //
+// --snr (not in the reference; include/dabgpu.h "Noise estimate"): a DAB_Noise_Estimator is fed from the same buffer as --tii, under the same
+// restrictions.  The frame observer keeps a copy of the buffer's head, the NULL period that follows the delivered frame; the phase reference
+// symbol that belongs to it is the one BEHIND it, which the reader has not seen yet.  So the estimate is made on the reading thread, after the
+// Synchronize() that follows the NEXT Process() call: by then the 2552 samples behind that NULL are in the buffer (a block holds at least
+// that many), and they stay there until the next frame ends (two blocks are shorter than a frame), which the unchanged head confirms.  The
+// window is cut with the delivered frame's timing, so the fine time offset given is 0; the rotation is GetNetFrequencyOffset().  One line
+// per frame on stdout:
+//   snr frame=N noise=NOISE signal=SIGNAL snr_db=DB
+// N = frames read when the NULL was kept, NOISE = noise_power (per sample), SIGNAL = signal_power / 2048 - noise_power (the symbol's mean
+// power per sample less the noise in it), DB = 10 log10(SIGNAL / NOISE).  The NULL behind the first frame after an acquisition is skipped,
+// as for --tii; so is a frame without a finite estimate.  --ofdm-block-size from 2552 to 98304.
+//
 // --ber (not in the reference; include/dabgpu.h "Channel BER"): the channel decode stage prints one line per frame to stdout,
 //   ber frame=N fic=ERRORS/BITS sub0=ERRORS/BITS ...
 // the channel bit errors of the frame's four FIB groups and of each sub-channel's CIFs that were decoded (0/0 while the time
@@ -45,6 +57,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+#include <cmath>
 #include <complex>
 #include <memory>
 #include <stdexcept>
@@ -62,6 +76,7 @@
 #include "dab/tx/dab_resampler.h"
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
+#include "ofdm/dab_noise_estimator.h"
 
 struct Args {
     std::string input_file;
@@ -80,6 +95,7 @@ struct Args {
     std::vector<Subchannel> subchannels;
     bool tii = false;
     int tii_frames = 8;
+    bool snr = false;
     double input_rate = 2.048e6;
     bool channelise = false;
     double channel_offset_hz = 0.0;
@@ -96,7 +112,7 @@ static void usage(const char* argv0) {
         "  [--ofdm-enable-output] [--ofdm-output FILE] [--ofdm-output-hard-bytes]\n"
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
-        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
+        "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
         "  [--soft-bits normalised|csi] [--soft-level 1..127]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
@@ -159,6 +175,7 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--radio-msc-output") args.radio_msc_output = value();
         else if (a == "--radio-subchannel") { const auto v = value(); args.subchannels.push_back(parse_subchannel(v, args.subchannels.size())); }
         else if (a == "--tii") args.tii = true;
+        else if (a == "--snr") args.snr = true;
         else if (a == "--tii-frames") { args.tii_frames = std::stoi(value()); args.tii = true; }
         else if (a == "--ber") args.ber = true;
         else if (a == "--soft-bits") {
@@ -177,6 +194,8 @@ static bool parse_args(int argc, char** argv, Args& args) {
     if (args.soft_policy != DABGPU_SOFT_NORMALISED && !args.is_ofdm_used) throw std::runtime_error("--soft-bits needs the OFDM stage");
     if (args.soft_level_given && args.soft_policy != DABGPU_SOFT_CSI) throw std::runtime_error("--soft-level needs --soft-bits csi");
     if (!(args.soft_level >= 1.0f && args.soft_level <= 127.0f)) throw std::runtime_error("--soft-level: a level from 1 to 127");
+    if (args.snr && !args.is_ofdm_used) throw std::runtime_error("--snr needs the OFDM stage");
+    if (args.snr && (args.ofdm_block_size < 2552 || args.ofdm_block_size > 98304)) throw std::runtime_error("--snr: --ofdm-block-size from 2552 to 98304");
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
@@ -185,12 +204,14 @@ static bool parse_args(int argc, char** argv, Args& args) {
         if (!(std::fabs(args.channel_offset_hz) <= 0.5 * args.input_rate)) throw std::runtime_error("--channel-offset-hz: within half of --input-rate either way");
         if (!args.is_ofdm_used) throw std::runtime_error("--channel-offset-hz needs the OFDM stage");
         if (args.tii) throw std::runtime_error("--channel-offset-hz is not available with --tii");
+        if (args.snr) throw std::runtime_error("--channel-offset-hz is not available with --snr");
         if (args.channel_offset_hz == 0.0 && args.input_rate < 4.096e6) args.channelise = false;       // the resampler alone
     }
     if (!args.channelise && !(args.input_rate >= 1.024e6 && args.input_rate <= 4.096e6))
         throw std::runtime_error("--input-rate: 1024000 .. 4096000 samples per second");
     if (args.input_rate != 2.048e6 && !args.is_ofdm_used) throw std::runtime_error("--input-rate needs the OFDM stage");
     if (args.input_rate != 2.048e6 && args.tii) throw std::runtime_error("--input-rate is not available with --tii (resampled blocks may exceed --ofdm-block-size)");
+    if (args.input_rate != 2.048e6 && args.snr) throw std::runtime_error("--input-rate is not available with --snr (resampled blocks may exceed --ofdm-block-size)");
     if (args.transmission_mode != 1) throw std::runtime_error("only transmission mode I is implemented");
     if (args.ofdm_block_size == 0) throw std::runtime_error("--ofdm-block-size must be positive");
     return true;
@@ -336,7 +357,32 @@ static int run(const Args& args) {
         std::unique_ptr<TII_Decoder> tii;
         if (args.tii) tii = std::make_unique<TII_Decoder>(args.transmission_mode);
         int tii_desync = 0;
+        // --snr: the NULL kept by the observer, the frame it follows, frames since the acquisition, Process() calls since it was kept
+        std::unique_ptr<DAB_Noise_Estimator> snr;
+        if (args.snr) snr = std::make_unique<DAB_Noise_Estimator>();
+        std::vector<std::complex<float>> snr_null;
+        int snr_frame = 0, snr_desync = 0, snr_since_acquisition = 0, snr_calls = 0;
+        auto snr_poll = [&]() {                                                      // on the reading thread, behind Synchronize()
+            if (snr_null.empty() || snr_calls++ == 0) return;                        // (the call that delivered the frame may end inside its window)
+            const auto corr = demod->GetCorrelationTimeBuffer();
+            dabgpu_noise_record rec;
+            if (demod->GetTotalFramesDesync() == snr_desync && std::equal(snr_null.begin(), snr_null.end(), corr.begin()) &&
+                snr->Estimate(corr, demod->GetNetFrequencyOffset(), 0, rec) && rec.valid) {
+                const double noise = rec.noise_power, signal = (double)rec.signal_power / 2048.0 - noise;
+                printf("snr frame=%d noise=%.6g signal=%.6g snr_db=%.2f\n", snr_frame, noise, signal, 10.0 * std::log10(signal / noise));
+            }
+            snr_null.clear();
+        };
         demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> bits) {
+            if (snr) {
+                if (demod->GetTotalFramesDesync() != snr_desync) { snr_desync = demod->GetTotalFramesDesync(); snr_since_acquisition = 0; }
+                snr_null.clear();
+                if (snr_since_acquisition++ > 0) {
+                    const auto null_region = demod->GetCorrelationTimeBuffer().first(2656);
+                    snr_null.assign(null_region.begin(), null_region.end());
+                    snr_frame = demod->GetTotalFramesRead(); snr_calls = 0;
+                }
+            }
             if (tii) {
                 if (demod->GetTotalFramesDesync() != tii_desync) { tii_desync = demod->GetTotalFramesDesync(); tii->Reset(); }
                 const auto null_region = demod->GetCorrelationTimeBuffer().first(2656);
@@ -399,7 +445,8 @@ static int run(const Args& args) {
                 if (!resampled.empty()) demod->Process(resampled);
             } else
             demod->Process(tcb::span<const std::complex<float>>(block.data(), length));
-            if (tii) demod->Synchronize();                                          // the observer reads the head of the correlation buffer
+            if (tii || snr) demod->Synchronize();                                   // the observer reads the head of the correlation buffer
+            if (snr) snr_poll();
             if (length != block.size()) break;
         }
         demod->Synchronize();

@@ -1750,6 +1750,71 @@ int dabgpu_ofdm_sync_demod_frames_branch(dabgpu_ctx *ctx, const float *d_iq, siz
                                          float *d_total_phase, const dabgpu_soft_cfg *soft, float *d_soft_scale, float *d_dqpsk,
                                          void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Noise estimate: one frame's NULL symbol turned into a calibrated noise power, the frame's signal power and the maximal-ratio weight
+ * w_b = 1 / (noise power) that "Receive diversity" takes, as arrays on the device (mode I; stateless, batched, one kernel launch per
+ * call, no host state: a call may be captured in a HIP graph).  The reference has no such code; this section is the definition.
+ * Per frame:
+ *   1 energies    steps 1 to 5 of the TII detector, statement for statement: the 2048 samples that begin 608 samples after the NULL's
+ *                 first sample (the NULL begins at null_offset_samples + fine_time_offset of the frame's dabgpu_sync_state, 0 without
+ *                 records), apply_pll with the record's freq_coarse + freq_fine (d_freq_offset[k] instead unless it is NaN; neither:
+ *                 0), the demodulator's 2048-point transform, P[k] = fma(re, re, im * im), the fold into E[24][8].  The 192 values
+ *                 equal, bit for bit, the accumulator of a freshly reset dabgpu_tii_bank after one _process of the same samples.
+ *   2 floor       F = the mean over the 24 combs, in order of c, of the mean of each comb's four smallest groups: the detector's own
+ *                 statistic at one frame.  Any transmitter leaves four of its comb's eight groups empty.
+ *   3 calibration noise_power N = F * dabgpu_noise_unbias().  Under white noise of power s2 per complex sample a group is 2048 s2 times
+ *                 a Gamma(8, 1) draw; with mu = E[mean of the four smallest of eight independent such draws] = 5.982762381925 the
+ *                 constant is 8 / (mu * 8 * 2048) = 8.161468e-05 as one float, and E[N] = s2.  One frame's N has a relative standard
+ *                 deviation of 0.0319 (0.14 dB).  Derivation and variance: tests/noise_model.py.
+ *   4 signal      signal_power P = the sum of |x|^2 over the useful part of the phase reference symbol, samples 504 .. 2551 behind the
+ *                 NULL's 2656, not rotated, in the demodulator's summation tree: the weighted soft bits' scale of (level, P) is the
+ *                 demodulator's d_soft_scale word of that frame bit for bit.  P is a sum over 2048 samples of signal plus noise, N a
+ *                 power per sample: the mean signal-to-noise ratio per sample is (P / 2048 - N) / N.
+ *   5 outputs     weight = 1 / max(N, P * 2^-40): the cap holds P * weight at 2^40 (120 dB), so a branch without noise (a synthetic
+ *                 one) is live with a finite weight, not dead.  The reciprocal is Newton's in fmaf on the mantissa, the exponent
+ *                 mirrored exactly: at most 1 ulp from the correctly rounded quotient.  snr = max(P - N, 0) * weight, a plain ratio
+ *                 of the two outputs (decibels, and the 2048 of step 4, are the caller's).
+ *   skipped       a record with sync_valid = 0, a fine_time_offset outside [-504, 1543] or one that puts the NULL's first sample in
+ *                 front of the frame's slice (null_offset_samples + fine_time_offset < 0): none of the frame's samples is read.  P or
+ *                 N not finite, P not above 0, or max(N, P * 2^-40) below the normal range (no finite weight).  A skipped frame
+ *                 writes 0 to EVERY output, group energies included, and clears d_valid[k] -- a stale weight can never be applied,
+ *                 and weight 0 is a dead branch for the combiner.
+ * Limits: T strong TII transmitters on distinct combs raise E[N] by (24 + T (8 / mu - 1)) / 24 -- such a comb's four smallest groups
+ * are its four empty ones, plain draws of mean 8 -- which is 1.0140 at T = 1 and 1.0562 (0.24 dB) at T = 4.  Two main ids on ONE comb
+ * may leave that comb no empty group; its share is then signal, and the bias is not bounded (stated, not fixed).  A carrier offset of
+ * up to half a spacing moves power into the combs c - 1 and c + 1 at the same group index, so every comb keeps four empty groups.
+ * Echoes of the previous frame up to 608 samples long stay in front of the window.  As for TII, the record of the first frame after
+ * an acquisition may be half a spacing off; that only matters with TII on the air.  No smoothing across frames: average noise_power.
+ * Arithmetic: csrc/noise_core.h; the device equals dabgpu_noise_floor_host and the tests' host model bit for bit.
+ */
+typedef struct { float noise_power, signal_power, weight, snr; uint32_t valid; } dabgpu_noise_record;
+typedef struct { uint32_t grid, threads, lds_bytes; } dabgpu_noise_geometry;
+/* What a dabgpu_noise_estimate_frames call with these arguments launches; needs no device (no address is dereferenced).
+ * DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null result; a transmission_mode other than 1; n_frames of 0 or
+ * above 2^24; d_iq null or not 8-byte aligned; records, offsets or outputs that are not 4-byte aligned; stream_stride_samples below
+ * null_offset_samples + 2656 + 2552, + 1543 more when d_states is given (either above 2^40); no output at all (d_valid counts as one). */
+int dabgpu_noise_plan(int transmission_mode, const float *d_iq, size_t n_frames, size_t stream_stride_samples, size_t null_offset_samples,
+                      const dabgpu_sync_state *d_states, const float *d_freq_offset, const float *d_noise_power,
+                      const float *d_signal_power, const float *d_weight, const float *d_snr, const float *d_group_energy,
+                      const uint32_t *d_valid, dabgpu_noise_geometry *out);
+/* d_iq, stream_stride_samples and null_offset_samples = prs_offset_samples - 2656 are those of dabgpu_ofdm_sync_demod_frames_branch and
+ * d_states the records it left, so the call sits behind a branch's demodulation with no copy (16-byte aligned windows are read with
+ * 16-byte loads, others with 8-byte loads).  Every output is optional: d_noise_power, d_signal_power, d_weight, d_snr [n_frames]
+ * float (d_weight can be a dabgpu_diversity_branch's d_weight as it is), d_group_energy [n_frames][192], d_valid [n_frames] (1 or 0). */
+int dabgpu_noise_estimate_frames(dabgpu_ctx *ctx, const float *d_iq, size_t n_frames, size_t stream_stride_samples,
+                                 size_t null_offset_samples, const dabgpu_sync_state *d_states, const float *d_freq_offset,
+                                 float *d_noise_power, float *d_signal_power, float *d_weight, float *d_snr, float *d_group_energy,
+                                 uint32_t *d_valid, void *stream);
+/* One frame from host memory, synchronous, on the context's stream: h_iq holds n_samples samples, the NULL begins at
+ * null_offset_samples + fine_time_offset, and NULL and phase reference symbol (2656 + 2552 samples) must lie inside them.  A
+ * fine_time_offset outside [-504, 1543], which the batched form skips, is refused here (DABGPU_ERR_INVALID_ARG), as is a frame that
+ * leaves the samples; *out is then all zero */
+int dabgpu_noise_estimate_host_sync(dabgpu_ctx *ctx, const float *h_iq, size_t n_samples, size_t null_offset_samples, float freq_offset,
+                                    int fine_time_offset, dabgpu_noise_record *out);
+float dabgpu_noise_unbias(void);
+/* steps 2 .. 5 on the host (no device): 1 and the record, or 0 and a record of zeros for a skipped frame (or a null argument) */
+int dabgpu_noise_floor_host(const float group_energy[192], float signal_power, dabgpu_noise_record *out);
+
 #ifdef __cplusplus
 }
 #endif

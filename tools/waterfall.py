@@ -27,8 +27,15 @@ b x streams + e, with a noise seed and (under --doppler-hz) a fading seed of its
 bits at --soft-level, DQPSK products, scale, sync record), and dabgpu_diversity_combine_frames puts the K branches' products into one frame of soft
 bits in the decoder's ring.  Every cell reads `single -> combined`: branch 0 decoded alone, and the combination.  The output goes to
 profiles/tx/waterfall_diversity.md.
+With --branches K --branch-noise-db a,b,... (the extra noise of each branch in dB, K values) and / or --weights unit|estimated|true the branches are
+combined with maximal-ratio weights: `estimated` takes them from dabgpu_noise_estimate_frames on every branch's slice and sync records (the slices
+then hold the whole NULL in front of each frame), `true` is 1 / (2 noise_sigma^2) of the branch's own channel stream, `unit` no weight.  SNR is
+that of a branch without extra noise.  The output goes to profiles/tx/waterfall_mrc.md, which such a run writes anew unless --append is given: the
+committed file is a unit run followed by an estimated and a true run with --append, and any of them can be repeated alone into an --out of its own.
+Without these two options the output is what it was.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
-                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]"""
+                              [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]
+                              [--branch-noise-db A,B,...] [--weights unit|estimated|true] [--append]"""
 import argparse
 import math
 import os
@@ -59,15 +66,28 @@ def main():
     ap.add_argument("--soft-bits", default="normalised", choices=("normalised", "csi"))
     ap.add_argument("--soft-level", type=float, default=64.0)
     ap.add_argument("--branches", type=int, default=1)
+    ap.add_argument("--branch-noise-db", default=None)
+    ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true"))
+    ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     K = a.branches
+    mrc = a.branch_noise_db is not None or a.weights != "unit"
+    if mrc and K == 1:
+        ap.error("--branch-noise-db and --weights want --branches K")
+    if a.append and not mrc:
+        ap.error("--append wants --branch-noise-db or --weights (the other records decide by their options whether they append)")
+    branch_db = [float(v) for v in a.branch_noise_db.split(",")] if a.branch_noise_db is not None else [0.0] * K
+    if len(branch_db) != K:
+        ap.error("--branch-noise-db takes one value per branch")
+    p_lead = NULL + P_LEAD if mrc else P_LEAD                                   # (with weights: the whole NULL in front of every frame)
+    stride = p_lead + 1544 + S
     if K != 1:
         if K < 2 or K > 8:
             ap.error("--branches takes 2 .. 8")
         if a.clock_ppm is not None or a.adjacent_db is not None or a.ber or a.soft_bits == "csi":
             ap.error("--branches is not available with --clock-ppm, --adjacent-db, --ber or --soft-bits (its branches are weighted already)")
         if a.out == ap.get_default("out"):
-            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_diversity.md")
+            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_mrc.md" if mrc else "waterfall_diversity.md")
     csi = a.soft_bits == "csi"
     if csi and (a.clock_ppm is not None or a.adjacent_db is not None):
         ap.error("--soft-bits csi is not available with --clock-ppm or --adjacent-db")
@@ -162,6 +182,16 @@ def main():
                 f"decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), "
                 f"sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  SNR is per branch.  "
                 f"`python tools/waterfall.py --branches {K} --streams {E} --frames {F} --snr {a.snr}{fading_args}`; the verdict line is the combination's.", ""]
+        if mrc:
+            how = {"unit": "no weights (every branch 1)", "estimated": "the weight arrays dabgpu_noise_estimate_frames wrote from every branch's slice and sync records",
+                   "true": "the true weights 1 / (2 noise_sigma^2) of every branch's channel stream"}[a.weights]
+            text = [f"# Receive diversity with branches of unequal noise: weights {a.weights}", "",
+                    f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall_diversity.md` with the branches' noise raised by "
+                    f"{', '.join(f'{d:g}' for d in branch_db)} dB (SNR is that of a branch without extra noise) and the combination made with {how}.  Every cell is "
+                    f"`single -> combined`: branch 0 decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of "
+                    f"every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
+                    f"`python tools/waterfall.py --branches {K} --branch-noise-db {','.join(f'{d:g}' for d in branch_db)} --weights {a.weights} --streams {E} --frames {F} "
+                    f"--snr {a.snr}{fading_args}{' --append' if a.append else ''}`; the verdict line is the combination's.", ""]
     verdicts = []
     profiles, fading =[(n, t, None, None) for n, t in PROFILES], None
     if adjacent_db:
@@ -196,7 +226,7 @@ def main():
         ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(EC)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
-            ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma) for e in range(EC)])
+            ch.set_params([dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=sigma * 10.0 ** (branch_db[e // E] / 20.0)) for e in range(EC)])
             ch.seek(0)
             ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rows * n_rx * 8)
             d_use = d_rx
@@ -215,6 +245,11 @@ def main():
                 d_st = [torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda") for _ in range(K)]
                 dq = [torch.zeros((E, 75, 1536, 2), dtype=torch.float32, device="cuda") for _ in range(K)]
                 kb = [torch.zeros((E,), dtype=torch.float32, device="cuda") for _ in range(K)]
+                wb = [None] * K
+                if a.weights == "estimated":
+                    wb = [torch.zeros((E,), dtype=torch.float32, device="cuda") for _ in range(K)]
+                elif a.weights == "true":
+                    wb = [torch.full((E,), 1.0 / (2.0 * (sigma * 10.0 ** (branch_db[b] / 20.0)) ** 2), dtype=torch.float32, device="cuda") for b in range(K)]
                 rings = [torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda") for _ in range(2)]
                 own = torch.zeros((E, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
                 d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
@@ -222,16 +257,19 @@ def main():
                 crc_ok, crc_n = [0, 0], [0, 0]
                 err = [[0] * len(LEVELS) for _ in range(2)]; tot = [[0] * len(LEVELS) for _ in range(2)]
                 for j in range(F):
-                    a0 = NULL + j * S - P_LEAD
+                    a0 = NULL + j * S - p_lead
+                    lo = max(a0, 0)                                     # (frame 0's slice begins in front of the stream when it holds the NULL)
                     for b in range(K):
-                        sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
-                        seg = d_use[b * E:(b + 1) * E, a0:a0 + STRIDE]
-                        sl[:, :seg.shape[1]] = seg
+                        sl = torch.zeros((E, stride, 2), dtype=torch.float32, device="cuda")
+                        seg = d_use[b * E:(b + 1) * E, lo:a0 + stride]
+                        sl[:, lo - a0:lo - a0 + seg.shape[1]] = seg
                         if b == 0:
                             rings[0][:, j % H].zero_()                  # (a frame the synchroniser refuses stays an erasure, not a stale frame)
-                        ctx.ofdm_sync_demod_frames_branch(sl, E, STRIDE, P_LEAD, d_st[b], rings[0][:, j % H] if b == 0 else own, soft, dq[b],
+                        ctx.ofdm_sync_demod_frames_branch(sl, E, stride, p_lead, d_st[b], rings[0][:, j % H] if b == 0 else own, soft, dq[b],
                                                           bits_frame_stride=H * dabgpu.NB_FRAME_BITS if b == 0 else 0, soft_scale=kb[b])
-                    ctx.diversity_combine([(dq[b], kb[b], None, d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                        if a.weights == "estimated":
+                            ctx.noise_estimate(sl, E, stride, p_lead - NULL, states=d_st[b], weight=wb[b])
+                    ctx.diversity_combine([(dq[b], kb[b], wb[b], d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
                     for r in range(2):
                         ctx.decode_frames(rings[r], E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
                         torch.cuda.synchronize()
@@ -327,7 +365,7 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    append = bool(clock_ppm or adjacent_db or ((csi or K > 1) and a.doppler_hz is not None))       # (the csi record: white noise and two paths first, the fading run behind them)
+    append = bool(clock_ppm or adjacent_db or ((csi or K > 1) and a.doppler_hz is not None) or a.append)       # (the csi record: white noise and two paths first, the fading run behind them)
     open(a.out, "a" if append else "w").write(("\n" if append else "") + text)
     return 0 if all(verdicts) else 1
 
