@@ -4,6 +4,7 @@
 #include "softbit_csi_core.h"
 #include "diversity_core.h"
 #include "noise_core.h"
+#include "noise_profile_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -184,6 +185,90 @@ int dabgpu_noise_plan(int transmission_mode, const float* d_iq, size_t n_frames,
     out->grid = (uint32_t)n_frames;
     out->threads = DABGPU_NOISE_THREADS;
     out->lds_bytes = DABGPU_NOISE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_noise_profile_plan(int transmission_mode, const float* d_iq, size_t n_frames, size_t stream_stride_samples, size_t null_offset_samples,
+                              const dabgpu_sync_state* d_states, const float* d_freq_offset, const uint32_t* d_exclude, const float* d_profile_in,
+                              float alpha, const float* d_profile_out, const float* d_band_weight, const float* d_mean_noise,
+                              const float* d_carrier_power, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
+    if (!out) { dabgpu_set_error("noise_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("noise_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("noise_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_iq) { dabgpu_set_error("noise_profile_plan: null samples"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("noise_profile_plan: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_states | (uintptr_t)d_freq_offset | (uintptr_t)d_exclude | (uintptr_t)d_profile_in | (uintptr_t)d_profile_out |
+         (uintptr_t)d_band_weight | (uintptr_t)d_mean_noise | (uintptr_t)d_carrier_power | (uintptr_t)d_valid) & 3) {
+        dabgpu_set_error("noise_profile_plan: records, offsets, tables and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    const size_t reach = (size_t)dabgpu::NP_NULL + (d_states ? 1543u : 0u);
+    if (null_offset_samples > ((size_t)1 << 40) || stream_stride_samples > ((size_t)1 << 40) || stream_stride_samples < null_offset_samples + reach) {
+        dabgpu_set_error("noise_profile_plan: stream_stride_samples %zu does not hold null_offset_samples %zu + %zu", stream_stride_samples,
+                         null_offset_samples, reach);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!dabgpu::np_alpha_ok(alpha)) { dabgpu_set_error("noise_profile_plan: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
+    if (d_profile_in && d_profile_out && d_profile_in != d_profile_out) {
+        const uintptr_t a = (uintptr_t)d_profile_in, b = (uintptr_t)d_profile_out, bytes = (uintptr_t)n_frames * dabgpu::NP_BANDS * sizeof(float);
+        if (a < b + bytes && b < a + bytes) {
+            dabgpu_set_error("noise_profile_plan: d_profile_in and d_profile_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!d_profile_out && !d_band_weight && !d_mean_noise && !d_carrier_power && !d_valid) {
+        dabgpu_set_error("noise_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
+    }
+    out->grid = (uint32_t)n_frames;
+    out->threads = DABGPU_NOISE_PROFILE_THREADS;
+    out->lds_bytes = DABGPU_NOISE_PROFILE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_noise_profile_bands_host(const float carrier_power[1536], const uint32_t* exclude, const float* profile_in, float alpha,
+                                    float* profile_out, float* band_weight, float* mean_noise) {
+    if (!carrier_power || !dabgpu::np_alpha_ok(alpha)) return -1;
+    return dabgpu::np_frame_bands(carrier_power, exclude, profile_in, alpha, profile_out, band_weight, mean_noise) ? 1 : 0;
+}
+
+int dabgpu_noise_profile_exclude_tii(const uint8_t* main_ids, const uint8_t* sub_ids, int n, uint32_t out[48]) {
+    if (!out || n < 0 || (n > 0 && (!main_ids || !sub_ids))) { dabgpu_set_error("noise_profile_exclude_tii: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    for (int i = 0; i < dabgpu::NP_EXCLUDE_WORDS; i++) out[i] = 0u;
+    for (int i = 0; i < n; i++) {
+        if (main_ids[i] >= DABGPU_TII_NB_MAIN || sub_ids[i] >= DABGPU_TII_COMBS) {
+            dabgpu_set_error("noise_profile_exclude_tii: transmitter %d: main_id %d, sub_id %d out of range", i, main_ids[i], sub_ids[i]);
+            for (int j = 0; j < dabgpu::NP_EXCLUDE_WORDS; j++) out[j] = 0u;
+            return DABGPU_ERR_INVALID_ARG;
+        }
+        for (int q = 0; q < 32; q++) {
+            int k0;
+            const int c = dabgpu::np_carrier_index(dabgpu::tii_carrier(main_ids[i], sub_ids[i], q, &k0));
+            out[c >> 5] |= 1u << (c & 31);
+        }
+    }
+    return DABGPU_OK;
+}
+
+float dabgpu_diversity_band_mean_host(const float band_weight[128]) { return band_weight ? dabgpu::np_branch_weight(band_weight) : 0.0f; }
+
+int dabgpu_diversity_plan_banded(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
+                                 size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
+                                 dabgpu_diversity_geometry* out) {
+    const int st = dabgpu_diversity_plan(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, out);
+    if (st || !h_band_weight) return st;
+    bool any = false;
+    for (int b = 0; b < n_branches; b++) {
+        if (!h_band_weight[b]) continue;
+        any = true;
+        if ((uintptr_t)h_band_weight[b] & 3) {
+            *out = dabgpu_diversity_geometry{};
+            dabgpu_set_error("diversity_plan_banded: branch %d: band weights must be 4-byte aligned", b); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (h_branches[b].d_weight) {
+            *out = dabgpu_diversity_geometry{};
+            dabgpu_set_error("diversity_plan_banded: branch %d has both a band table and d_weight", b); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (any) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;
     return DABGPU_OK;
 }
 

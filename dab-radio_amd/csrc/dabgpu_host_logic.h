@@ -242,6 +242,13 @@ int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout,
 #define DABGPU_NOISE_THREADS 256u
 #define DABGPU_NOISE_LDS_BYTES (18432u + 8192u + 768u + 96u + 16u + 4u)
 
+// ---- noise profile (noise_profile.hip launches from dabgpu_noise_profile_plan; include/dabgpu.h, "Noise profile") ----
+// one 256-thread workgroup per frame; static LDS: the transform's patches, 2048 bin powers, the two wave sums of the mean
+#define DABGPU_NOISE_PROFILE_THREADS 256u
+#define DABGPU_NOISE_PROFILE_LDS_BYTES (18432u + 8192u + 8u)
+// the banded combiner's instantiation adds the two wave sums of every branch's mean weight to the combiner's LDS
+#define DABGPU_DIVERSITY_BANDED_LDS_BYTES (DABGPU_DIVERSITY_LDS_BYTES + 8u * 2u * 4u)
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

@@ -16,18 +16,29 @@
 
 #include "dabgpu_internal.h"
 #include "diversity_core.h"
+#include "noise_profile_core.h"
+#include "ofdm_device.h"
 
 namespace dabgpu {
 
 typedef float dv_f4 __attribute__((ext_vector_type(4)));
 struct dv_table { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; };
+// the banded call's argument: the branch table and, per branch, its band weights [n_frames][128] (null: the branch has a scalar weight)
+struct dv_table_banded { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; const float* band[DV_MAX_BRANCHES]; };
+template <bool BANDED> struct dv_table_of { typedef dv_table type; };
+template <> struct dv_table_of<true> { typedef dv_table_banded type; };
 
 constexpr int DV_DATA_SYMBOLS = 75, DV_CARRIERS = 1536, DV_SYM_BITS = 3072, DV_FIC_SYMBOLS = 3, DV_CIF_SYMBOLS = 18, DV_CIF_BITS = 55296;
 constexpr int DV_ROW_PIECES = DV_CARRIERS / 2;              // 16-byte pieces of a branch's symbol row: 768 = 3 per lane
 static_assert(DV_ROW_PIECES == 3 * (int)DABGPU_DIVERSITY_THREADS && DV_SYM_BITS / 16 <= (int)DABGPU_DIVERSITY_THREADS, "three pieces per lane, 192 storing lanes");
 
+// BANDED (include/dabgpu.h, "Banded receive diversity"): a branch with a band table takes the tree mean of the frame's 128 band weights
+// for its weight -- lanes 0 .. 127 hold one band each, the two wave sums meet in LDS -- and every lane keeps the band weights of its three
+// pieces (carriers 2 (t + 256 j), + 1: band (t + 256 j) / 6) in registers for all symbols of the run.  The first instantiation is the
+// kernel as it was.
+template <bool BANDED>
 __global__ __launch_bounds__(DABGPU_DIVERSITY_THREADS)
-void diversity_combine_kernel(const dv_table tab, const int n_branches, const int n_frames, const int sym_per_run, const int runs_per_frame,
+void diversity_combine_kernel(const typename dv_table_of<BANDED>::type tab, const int n_branches, const int n_frames, const int sym_per_run, const int runs_per_frame,
                               int8_t* __restrict__ bits, const size_t bits_frame_stride, const int classed, const uint16_t* __restrict__ inv_map,
                               float* __restrict__ soft_scale, uint32_t* __restrict__ live_mask)
 {
@@ -39,6 +50,25 @@ void diversity_combine_kernel(const dv_table tab, const int n_branches, const in
 
     // ---- the frame's live branches and its scale (uniform) ----
     float w[DV_MAX_BRANCHES];
+    float wl[BANDED ? DV_MAX_BRANCHES : 1][3], wmean[BANDED ? DV_MAX_BRANCHES : 1];
+    if constexpr (BANDED) {
+        __shared__ float meanS[DV_MAX_BRANCHES][2];
+#pragma unroll
+        for (int b = 0; b < DV_MAX_BRANCHES; b++) {
+            if (b < n_branches && tab.band[b] != nullptr) {                           // (uniform)
+                const float* const bw = tab.band[b] + (size_t)frame * NP_BANDS;
+                if (t < NP_BANDS) {
+                    const float s = wave_tree_sum(np_clean_weight(bw[t]), t & 63);
+                    if ((t & 63) == 0) meanS[b][t >> 6] = s;
+                }
+#pragma unroll
+                for (int j = 0; j < 3; j++) wl[b][j] = np_clean_weight(bw[(t + 256 * j) / 6]);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < DV_MAX_BRANCHES; b++) wmean[b] = (b < n_branches && tab.band[b] != nullptr) ? np_mean_join(meanS[b][0], meanS[b][1]) : 1.0f;
+    }
     dv_scale_state st = dv_scale_begin();
 #pragma unroll
     for (int b = 0; b < DV_MAX_BRANCHES; b++) {
@@ -47,6 +77,10 @@ void diversity_combine_kernel(const dv_table tab, const int n_branches, const in
             const dabgpu_diversity_branch B = tab.b[b];
             const bool sync_ok = B.d_sync == nullptr || B.d_sync[frame].sync_valid != 0;
             if (B.d_weight != nullptr) w[b] = B.d_weight[frame];
+            if constexpr (BANDED) {
+                if (tab.band[b] != nullptr) w[b] = wmean[b];
+                else { wl[b][0] = w[b]; wl[b][1] = w[b]; wl[b][2] = w[b]; }
+            }
             dv_scale_add(st, b, sync_ok, B.d_scale[frame], w[b]);
         }
     }
@@ -79,17 +113,18 @@ void diversity_combine_kernel(const dv_table tab, const int n_branches, const in
                 const dv_f4* const p = reinterpret_cast<const dv_f4*>(tab.b[b].d_dqpsk) + ((size_t)frame * DV_DATA_SYMBOLS + (size_t)row) * DV_ROW_PIECES + t;
                 const dv_f4 v0 = p[0], v1 = p[256], v2 = p[512];
                 const dv_f4 v[3] = {v0, v1, v2};
-                const float wb = w[b];
+                // the weight of piece j: the branch's, or (BANDED) the one of the piece's band
+                auto wj = [&](int j) __attribute__((always_inline)) { if constexpr (BANDED) return wl[b][j]; else return w[b]; };
                 if (first) {
 #pragma unroll
                     for (int j = 0; j < 3; j++)
-                        acc[j] = dv_f4{dv_sum_first(wb, v[j].x), dv_sum_first(wb, v[j].y), dv_sum_first(wb, v[j].z), dv_sum_first(wb, v[j].w)};
+                        acc[j] = dv_f4{dv_sum_first(wj(j), v[j].x), dv_sum_first(wj(j), v[j].y), dv_sum_first(wj(j), v[j].z), dv_sum_first(wj(j), v[j].w)};
                     first = false;
                 } else {
 #pragma unroll
                     for (int j = 0; j < 3; j++)
-                        acc[j] = dv_f4{dv_sum_next(acc[j].x, wb, v[j].x), dv_sum_next(acc[j].y, wb, v[j].y), dv_sum_next(acc[j].z, wb, v[j].z),
-                                       dv_sum_next(acc[j].w, wb, v[j].w)};
+                        acc[j] = dv_f4{dv_sum_next(acc[j].x, wj(j), v[j].x), dv_sum_next(acc[j].y, wj(j), v[j].y), dv_sum_next(acc[j].z, wj(j), v[j].z),
+                                       dv_sum_next(acc[j].w, wj(j), v[j].w)};
                 }
             }
         }
@@ -143,10 +178,37 @@ int dabgpu_diversity_combine_frames(dabgpu_ctx* c, const dabgpu_diversity_branch
     dv_table tab;
     memset(&tab, 0, sizeof(tab));
     for (int b = 0; b < n_branches; b++) tab.b[b] = h_branches[b];
-    hipLaunchKernelGGL(diversity_combine_kernel, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+    hipLaunchKernelGGL(diversity_combine_kernel<false>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
                        (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
                        bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
     return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel launch");
+}
+
+int dabgpu_diversity_combine_frames_banded(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                                           size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale,
+                                           uint32_t* d_live_mask, const float* const* h_band_weight, void* stream) {
+    if (!c) { dabgpu_set_error("diversity_combine_frames_banded: null context"); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu_diversity_geometry g;
+    int st = dabgpu_diversity_plan_banded(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight, &g);
+    if (st) return st;
+    // no table at all: the scalar call, exactly
+    if (g.lds_bytes != DABGPU_DIVERSITY_BANDED_LDS_BYTES)
+        return dabgpu_diversity_combine_frames(c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
+                                               d_soft_scale, d_live_mask, stream);
+    if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
+        dabgpu_set_error("diversity_combine_frames_banded: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_frames == 0) return DABGPU_OK;
+    DABGPU_BIND(c);
+    const dabgpu_mode_tables* t;
+    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames_banded"))) return st;
+    dv_table_banded tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int b = 0; b < n_branches; b++) { tab.b[b] = h_branches[b]; tab.band[b] = h_band_weight[b]; }
+    hipLaunchKernelGGL(diversity_combine_kernel<true>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
+                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
+    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel (banded) launch");
 }
 
 int dabgpu_diversity_combine_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight, const int* h_valid,
@@ -186,6 +248,61 @@ int dabgpu_diversity_combine_host_sync(dabgpu_ctx* c, const float* const* h_dqps
     float* const d_k = d_small + 2 * DABGPU_DIVERSITY_MAX_BRANCHES;
     uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
     if ((st = dabgpu_diversity_combine_frames(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, s))) return st;
+    uint32_t back[2];
+    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
+    if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
+    if (h_live_mask) *h_live_mask = back[1];
+    return DABGPU_OK;
+}
+
+int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight,
+                                              const int* h_valid, int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale,
+                                              uint32_t* h_live_mask, const float* const* h_band_weight) {
+    if (!h_band_weight)
+        return dabgpu_diversity_combine_host_sync(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale, h_live_mask);
+    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_banded_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
+        dabgpu_set_error("diversity_combine_banded_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    int st = dabgpu_check_bits_layout("diversity_combine_banded_host_sync", bits_layout);
+    if (st) return st;
+    // as the scalar form: what the kernel will find live decides which products are uploaded
+    constexpr int K = DABGPU_DIVERSITY_MAX_BRANCHES;
+    float small[2 * K];
+    for (int b = 0; b < n_branches; b++) {
+        const float w = h_band_weight[b] ? np_branch_weight(h_band_weight[b]) : (h_weight ? h_weight[b] : 1.0f);
+        const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
+        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_banded_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
+        small[b] = live ? h_scale[b] : 0.0f;
+        small[K + b] = w;
+    }
+    DABGPU_BIND(c);
+    DABGPU_HOST_LOCK(c);
+    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
+    float *d_dq, *d_small; int8_t* d_bits;
+    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * K + 2 + K * NP_BANDS) * sizeof(float), (void**)&d_small))) return st;
+    hipStream_t s = c->stream;
+    dabgpu_diversity_branch br[K];
+    const float* band[K];
+    float* const d_band = d_small + 2 * K + 2;
+    for (int b = 0; b < n_branches; b++) {
+        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
+        br[b].d_scale = d_small + b;
+        br[b].d_weight = h_band_weight[b] ? nullptr : d_small + K + b;
+        br[b].d_sync = nullptr;
+        band[b] = h_band_weight[b] ? d_band + (size_t)b * NP_BANDS : nullptr;
+        if (h_band_weight[b]) DABGPU_CK(hipMemcpyAsync(d_band + (size_t)b * NP_BANDS, h_band_weight[b], NP_BANDS * sizeof(float), hipMemcpyHostToDevice, s));
+        if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
+    float* const d_k = d_small + 2 * K;
+    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
+    if ((st = dabgpu_diversity_combine_frames_banded(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, s))) return st;
     uint32_t back[2];
     DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));

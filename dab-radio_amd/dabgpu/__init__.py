@@ -97,7 +97,11 @@ ABI_SYMBOLS = [
     "dabgpu_diversity_plan", "dabgpu_diversity_combine_frames", "dabgpu_diversity_combine_host_sync", "dabgpu_diversity_scale_host",
     "dabgpu_ofdm_sync_demod_frames_branch", "dabgpu_receiver_frame_soft_scale",
     "dabgpu_noise_plan", "dabgpu_noise_estimate_frames", "dabgpu_noise_estimate_host_sync", "dabgpu_noise_unbias", "dabgpu_noise_floor_host",
+    "dabgpu_noise_profile_plan", "dabgpu_noise_profile_frames", "dabgpu_noise_profile_host_sync", "dabgpu_noise_profile_bands_host",
+    "dabgpu_noise_profile_exclude_tii", "dabgpu_diversity_plan_banded", "dabgpu_diversity_combine_frames_banded",
+    "dabgpu_diversity_combine_banded_host_sync", "dabgpu_diversity_band_mean_host",
 ]
+NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 DIVERSITY_MAX_BRANCHES = 8                # receive diversity (include/dabgpu.h)
 NOISE_RECORD_DTYPE = [("noise_power", "<f4"), ("signal_power", "<f4"), ("weight", "<f4"), ("snr", "<f4"), ("valid", "<u4")]   # dabgpu_noise_record
@@ -404,6 +408,20 @@ def lib():
         L.dabgpu_noise_unbias.argtypes = []
         L.dabgpu_noise_unbias.restype = C.c_float
         L.dabgpu_noise_floor_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        L.dabgpu_noise_profile_plan.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 6
+        L.dabgpu_noise_profile_frames.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 4 + [C.c_float] +
+                                                  [C.c_void_p] * 6)
+        L.dabgpu_noise_profile_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_noise_profile_bands_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_noise_profile_exclude_tii.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_diversity_plan_banded.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_combine_frames_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_combine_banded_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_band_mean_host.argtypes = [C.c_void_p]
+        L.dabgpu_diversity_band_mean_host.restype = C.c_float
         L.dabgpu_ofdm_sync_demod_frames_branch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p]
@@ -815,20 +833,43 @@ class Context:
                                                          self._stream(stream)), "dabgpu_ofdm_sync_demod_frames_branch")
 
     def diversity_combine(self, branches, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0, soft_scale=None,
-                          live_mask=None, stream=None):
+                          live_mask=None, stream=None, band_weights=None):
         """receive diversity: `branches` = up to 8 of (dqpsk, scale[, weight[, sync]]) device buffers (or DiversityBranch records) of the same
         n_frames frames -> their combined soft bits in `bits`; soft_scale [n_frames] float32 and live_mask [n_frames] uint32 on the device
-        receive the scale used and the live branches.  One kernel launch, no copy: capturable"""
+        receive the scale used and the live branches.  One kernel launch, no copy: capturable.  band_weights = one entry per branch, a
+        device buffer [n_frames][128] of band weights (Context.noise_profile's) or None: dabgpu_diversity_combine_frames_banded"""
         table = diversity_table(branches)
+        if band_weights is not None:
+            bands = band_weight_table(band_weights, len(table))
+            check(lib().dabgpu_diversity_combine_frames_banded(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                                               int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), bands,
+                                                               self._stream(stream)), "dabgpu_diversity_combine_frames_banded")
+            return
         check(lib().dabgpu_diversity_combine_frames(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
                                                     int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), self._stream(stream)),
               "dabgpu_diversity_combine_frames")
 
-    def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL):
+    def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL, band_weights=None):
         """numpy convenience over dabgpu_diversity_combine_host_sync: one frame; dqpsk = a list of [75][1536] complex64 arrays (None where the
-        branch is not live); returns (bits [230400] int8, scale, live mask)"""
+        branch is not live); returns (bits [230400] int8, scale, live mask).  band_weights = one [128] float32 array or None per branch:
+        dabgpu_diversity_combine_banded_host_sync"""
         import numpy as np
         n = len(dqpsk)
+        if band_weights is not None:
+            if len(band_weights) != n:
+                raise ValueError("diversity_combine_host: one band_weights entry per branch")
+            keep_w = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(NOISE_PROFILE_BANDS) for x in band_weights]
+            bands = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_w])
+            keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
+            ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
+            k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
+            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
+            v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+            bits = np.empty(NB_FRAME_BITS, np.int8)
+            out_k, out_m = C.c_float(0.0), C.c_uint32(0)
+            check(lib().dabgpu_diversity_combine_banded_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits),
+                                                                  C.byref(out_k), C.byref(out_m), bands), "dabgpu_diversity_combine_banded_host_sync")
+            return bits, out_k.value, out_m.value
         keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
         ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
         k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
@@ -848,6 +889,33 @@ class Context:
         check(lib().dabgpu_noise_estimate_frames(self._h, _ptr(iq), n_frames, stream_stride_samples, null_offset_samples, _ptr(states),
                                                  _ptr(freq_offset), _ptr(noise_power), _ptr(signal_power), _ptr(weight), _ptr(snr),
                                                  _ptr(group_energy), _ptr(valid), self._stream(stream)), "dabgpu_noise_estimate_frames")
+
+    def noise_profile(self, iq, n_frames, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, exclude=None,
+                      profile_in=None, alpha=1.0, profile_out=None, band_weight=None, mean_noise=None, carrier_power=None, valid=None, stream=None):
+        """the noise profile of n_frames frames (include/dabgpu.h, "Noise profile"): exclude = 48 uint32 words on the device
+        (noise_profile_exclude), profile_in / profile_out [n_frames][128] float32 the smoothing state (may be one buffer), band_weight
+        [n_frames][128] (an entry of diversity_combine's band_weights as it is), mean_noise [n_frames], carrier_power [n_frames][1536],
+        valid [n_frames] uint32; every output optional.  One kernel launch, no copy: capturable"""
+        check(lib().dabgpu_noise_profile_frames(self._h, _ptr(iq), n_frames, stream_stride_samples, null_offset_samples, _ptr(states),
+                                                _ptr(freq_offset), _ptr(exclude), _ptr(profile_in), float(alpha), _ptr(profile_out),
+                                                _ptr(band_weight), _ptr(mean_noise), _ptr(carrier_power), _ptr(valid), self._stream(stream)),
+              "dabgpu_noise_profile_frames")
+
+    def noise_profile_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0, exclude=None, profile=None, alpha=1.0,
+                           carrier_power=False):
+        """numpy convenience over dabgpu_noise_profile_host_sync: one frame's NULL out of complex64 samples -> (band weights [128], mean
+        noise, valid[, carrier powers [1536]]); profile = a [128] float32 array, the state, updated in place"""
+        import numpy as np
+        x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint32).reshape(NOISE_PROFILE_EXCLUDE_WORDS)
+        if profile is not None and (profile.dtype != np.float32 or profile.size != NOISE_PROFILE_BANDS or not profile.flags.c_contiguous):
+            raise ValueError("noise_profile_host: profile must be a contiguous float32 array of 128")
+        bw, cp = np.zeros(NOISE_PROFILE_BANDS, np.float32), (np.zeros(NB_CARRIERS, np.float32) if carrier_power else None)
+        mean, ok = C.c_float(0.0), C.c_uint32(0)
+        check(lib().dabgpu_noise_profile_host_sync(self._h, _ptr(x), x.size, null_offset_samples, float(freq_offset), int(fine_time_offset), _ptr(ex),
+                                                   _ptr(profile), float(alpha), _ptr(bw), C.byref(mean), _ptr(cp), C.byref(ok)),
+              "dabgpu_noise_profile_host_sync")
+        return (bw, mean.value, ok.value) + ((cp,) if carrier_power else ())
 
     def noise_estimate_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0):
         """numpy convenience over dabgpu_noise_estimate_host_sync: one frame's NULL and phase reference symbol out of complex64 samples ->
@@ -1942,6 +2010,69 @@ def noise_plan(iq, n_frames, stream_stride_samples, null_offset_samples, states=
                                   _ptr(noise_power), _ptr(signal_power), _ptr(weight), _ptr(snr), _ptr(group_energy), _ptr(valid), C.byref(g)),
           "dabgpu_noise_plan")
     return g
+
+
+def band_weight_table(band_weights, n_branches):
+    """a ctypes array of n_branches device addresses from buffers / addresses / None (a branch without a band table)"""
+    if len(band_weights) != n_branches:
+        raise ValueError("band_weights: one entry (a buffer or None) per branch")
+    return (C.c_void_p * n_branches)(*[getattr(_ptr(x), "value", None) for x in band_weights])
+
+
+def diversity_plan_banded(branches, n_frames, bits, band_weights, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0):
+    """dabgpu_diversity_plan_banded (host only, nothing is dereferenced): the DiversityGeometry of a diversity_combine call with
+    band_weights (None: no table at all); DabGpuError with the reason when refused"""
+    table = diversity_table(branches)
+    g = DiversityGeometry()
+    bands = None if band_weights is None else band_weight_table(band_weights, len(table))
+    check(lib().dabgpu_diversity_plan_banded(table if len(table) else None, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                             int(symbols_per_block), bands, C.byref(g)), "dabgpu_diversity_plan_banded")
+    return g
+
+
+def noise_profile_plan(iq, n_frames, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, exclude=None, profile_in=None,
+                       alpha=1.0, profile_out=None, band_weight=None, mean_noise=None, carrier_power=None, valid=None, mode=1):
+    """dabgpu_noise_profile_plan (host only, nothing is dereferenced): the NoiseGeometry of a noise_profile call with these arguments; raises
+    DabGpuError with the reason where that call would be refused"""
+    g = NoiseGeometry()
+    check(lib().dabgpu_noise_profile_plan(int(mode), _ptr(iq), n_frames, stream_stride_samples, null_offset_samples, _ptr(states), _ptr(freq_offset),
+                                          _ptr(exclude), _ptr(profile_in), float(alpha), _ptr(profile_out), _ptr(band_weight), _ptr(mean_noise),
+                                          _ptr(carrier_power), _ptr(valid), C.byref(g)), "dabgpu_noise_profile_plan")
+    return g
+
+
+def noise_profile_exclude(transmitters):
+    """the 48 exclusion words of the noise profile from TII ids: `transmitters` = (main_id, sub_id[, ...]) tuples
+    (dabgpu_noise_profile_exclude_tii); every carrier of those transmitters is left out of its band"""
+    import numpy as np
+    main = np.array([int(t[0]) for t in transmitters], np.uint8)
+    sub = np.array([int(t[1]) for t in transmitters], np.uint8)
+    if any(not 0 <= int(t[0]) < 256 or not 0 <= int(t[1]) < 256 for t in transmitters):
+        raise ValueError("noise_profile_exclude: ids must fit a byte")
+    out = np.zeros(NOISE_PROFILE_EXCLUDE_WORDS, np.uint32)
+    check(lib().dabgpu_noise_profile_exclude_tii(_ptr(main) if main.size else None, _ptr(sub) if sub.size else None, int(main.size), _ptr(out)),
+          "dabgpu_noise_profile_exclude_tii")
+    return out
+
+
+def noise_profile_bands_host(carrier_power, exclude=None, profile_in=None, alpha=1.0):
+    """steps 2 to 5 of the noise profile on the host: 1536 carrier powers -> (profile [128], band weights [128], mean noise, valid)"""
+    import numpy as np
+    cp = np.ascontiguousarray(carrier_power, dtype=np.float32).reshape(NB_CARRIERS)
+    ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint32).reshape(NOISE_PROFILE_EXCLUDE_WORDS)
+    pin = None if profile_in is None else np.ascontiguousarray(profile_in, dtype=np.float32).reshape(NOISE_PROFILE_BANDS)
+    prof, bw, mean = np.zeros(NOISE_PROFILE_BANDS, np.float32), np.zeros(NOISE_PROFILE_BANDS, np.float32), C.c_float(0.0)
+    st = lib().dabgpu_noise_profile_bands_host(_ptr(cp), _ptr(ex), _ptr(pin), float(alpha), _ptr(prof), _ptr(bw), C.byref(mean))
+    if st < 0:
+        raise DabGpuError("dabgpu_noise_profile_bands_host: alpha outside (0, 1]")
+    return prof, bw, mean.value, st
+
+
+def diversity_band_mean(band_weight):
+    """the branch weight of a band table: dabgpu_diversity_band_mean_host"""
+    import numpy as np
+    bw = np.ascontiguousarray(band_weight, dtype=np.float32).reshape(NOISE_PROFILE_BANDS)
+    return float(lib().dabgpu_diversity_band_mean_host(_ptr(bw)))
 
 
 def noise_unbias():

@@ -23,6 +23,11 @@ public:
     // DABGPU_BITS_NATURAL unless SetBitsLayout says otherwise.  false for wrong sizes.
     bool Combine(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales, tcb::span<const float> weights,
                  tcb::span<viterbi_bit_t> out_bits);
+    // the same with band weights (include/dabgpu.h, "Banded receive diversity"): band_weights[b] = the 128 band weights of branch b's frame
+    // (DAB_Noise_Profile::Update's) or an empty span for a branch without a table, which then takes weights[b] (1 without weights); for a
+    // branch with a table weights[b] is not looked at.  false for wrong sizes.
+    bool Combine(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales, tcb::span<const float> weights,
+                 tcb::span<const tcb::span<const float>> band_weights, tcb::span<viterbi_bit_t> out_bits);
     void SetBitsLayout(int bits_layout) { m_layout = bits_layout; }
     float GetScale() const { return m_scale; }              // k of the last frame combined (0: erased)
     uint32_t GetLiveMask() const { return m_live_mask; }    // bit b: branch b took part in it

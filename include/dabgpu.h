@@ -1815,6 +1815,108 @@ float dabgpu_noise_unbias(void);
 /* steps 2 .. 5 on the host (no device): 1 and the record, or 0 and a record of zeros for a skipped frame (or a null argument) */
 int dabgpu_noise_floor_host(const float group_energy[192], float signal_power, dabgpu_noise_record *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Noise profile: one frame's NULL symbol turned into a noise power per frequency band and the maximal-ratio weights of the bands, for
+ * a combiner that applies them carrier by carrier (mode I; batched, one kernel launch per call, no host state: a call may be captured
+ * in a HIP graph; the smoothing state is the caller's array).  "Noise estimate" holds the noise of a branch to be white and gives it
+ * one weight per frame; a narrowband interferer (a spur cluster, a co-channel carrier, a neighbour's shoulder) makes the carriers
+ * under it the largest products of the frame, and under DABGPU_SOFT_CSI the most confident soft bits.  The reference has no such code;
+ * this section is the definition.  Per frame:
+ *   1 powers      steps 1 to 4 of the TII detector, statement for statement (window, rotation, transform, P[k] = fma(re, re, im * im):
+ *                 the window, the records and d_freq_offset as "Noise estimate" step 1 reads them).  In the carrier order of d_dqpsk,
+ *                 C[c] = P[1280 + c] for c < 768 (carriers -768 .. -1) and P[c - 767] for c >= 768 (carriers 1 .. 768); DC is left out.
+ *                 d_carrier_power [n_frames][1536] (optional).
+ *   2 bands       128 bands of 12 adjacent carriers, band b = carriers 12 b .. 12 b + 11: 64 bands on either side of DC, none
+ *                 straddles it, and a pair of carriers 2 i, 2 i + 1 never straddles a band.  sum = the included carriers of the band
+ *                 added one after the other in carrier order (the first included one starts the chain), count = how many were
+ *                 included.  m_b = (sum * R[count]) * 2^-11, R[n] the float nearest 1 / n.  The transform is not normalised, so under
+ *                 white noise of power s2 per complex sample E[C[c]] = 2048 s2 and E[m_b] = s2: no calibration constant.  One
+ *                 frame's m_b is a mean of 12 unit exponentials: relative standard deviation 1 / sqrt(12).
+ *   3 exclusion   d_exclude (optional): 48 words, bit c mod 32 of word c / 32 set = carrier c is left out of its band (the TII carriers
+ *                 that are on the air: dabgpu_tii_carriers; carrier k of -768 .. 768 is c = k + 768 below DC and k + 767 above).  One
+ *                 table serves all frames of the call.  A band whose 12 carriers are ALL excluded ignores the mask: it is measured from
+ *                 all 12, since a band without a measurement would have no weight.
+ *   4 smoothing   d_profile_in [n_frames][128] (optional: the previous n_b of each frame's receiver) and alpha in (0, 1]:
+ *                 n_b = fmaf(alpha, m_b - p_b, p_b) where p_b is finite and > 0, n_b = m_b otherwise, so a zeroed buffer starts
+ *                 cleanly.  Without d_profile_in n_b = m_b.  With independent frames the relative deviation settles at
+ *                 sqrt(alpha / (2 - alpha)) / sqrt(12).  d_profile_out [n_frames][128] (optional) takes n_b; it may be d_profile_in
+ *                 itself (in place); any other overlap is the caller's error.
+ *   5 weights     M = the mean of the 128 n_b in a fixed tree: 64 + 64 values, each half folded pairwise with partner distance 32, 16,
+ *                 8, 4, 2, 1 (the demodulator's wavefront tree), the two results added, times 2^-7.  w_b = 1 / max(n_b, M * 2^-20)
+ *                 by the combiner's reciprocal (csrc/diversity_core.h, dv_reciprocal): a band is never weighted more than 60 dB
+ *                 above the mean, and a band without noise (a synthetic signal) has a finite weight.  Where M * 2^-20 is below the
+ *                 normal range and n_b below it as well, w_b is +infinity, which the combiner counts as 0.
+ *                 d_band_weight [n_frames][128], d_mean_noise [n_frames] (= M), d_valid [n_frames] (1 or 0).
+ *   skipped       a frame "Noise estimate" skips by its record (none of its samples is read), or whose M is not a normal positive
+ *                 finite number (NaN, infinity, all zero).  It writes 0 to every band weight, to d_mean_noise and to d_carrier_power
+ *                 and clears d_valid; d_profile_out takes d_profile_in unchanged, or 0 without one: a stale weight is never
+ *                 applied, and the state survives.
+ * Arithmetic: csrc/noise_profile_core.h; the device equals dabgpu_noise_profile_bands_host and the tests' host model bit for bit. */
+#define DABGPU_NOISE_PROFILE_BANDS 128
+#define DABGPU_NOISE_PROFILE_BAND_CARRIERS 12
+#define DABGPU_NOISE_PROFILE_EXCLUDE_WORDS 48
+/* What a dabgpu_noise_profile_frames call with these arguments launches; needs no device (no address is dereferenced).
+ * DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null result; a transmission_mode other than 1; n_frames of 0 or
+ * above 2^24; d_iq null or not 8-byte aligned; records, offsets, tables or outputs that are not 4-byte aligned; stream_stride_samples
+ * below null_offset_samples + 2656, + 1543 more when d_states is given (either above 2^40); alpha outside (0, 1] (NaN included);
+ * d_profile_in and d_profile_out that overlap without being equal; no output at all (d_valid and d_profile_out count as outputs). */
+int dabgpu_noise_profile_plan(int transmission_mode, const float *d_iq, size_t n_frames, size_t stream_stride_samples,
+                              size_t null_offset_samples, const dabgpu_sync_state *d_states, const float *d_freq_offset,
+                              const uint32_t *d_exclude, const float *d_profile_in, float alpha, const float *d_profile_out,
+                              const float *d_band_weight, const float *d_mean_noise, const float *d_carrier_power,
+                              const uint32_t *d_valid, dabgpu_noise_geometry *out);
+/* d_iq, stream_stride_samples, null_offset_samples, d_states and d_freq_offset are those of dabgpu_noise_estimate_frames: the call sits
+ * behind a branch's demodulation with no copy.  Every output is optional; d_band_weight can be an entry of
+ * dabgpu_diversity_combine_frames_banded's h_band_weight as it is. */
+int dabgpu_noise_profile_frames(dabgpu_ctx *ctx, const float *d_iq, size_t n_frames, size_t stream_stride_samples,
+                                size_t null_offset_samples, const dabgpu_sync_state *d_states, const float *d_freq_offset,
+                                const uint32_t *d_exclude, const float *d_profile_in, float alpha, float *d_profile_out,
+                                float *d_band_weight, float *d_mean_noise, float *d_carrier_power, uint32_t *d_valid, void *stream);
+/* One frame from host memory, synchronous, on the context's stream: h_iq holds n_samples samples, the NULL (2656 samples) begins at
+ * null_offset_samples + fine_time_offset and must lie inside them; a fine_time_offset outside [-504, 1543] is refused.  h_exclude [48]
+ * or NULL; h_profile [128] or NULL: the state, read and written in place; h_band_weight [128], h_mean_noise, h_carrier_power [1536]
+ * may be NULL.  Returns DABGPU_OK with *h_valid (may be NULL) 1 or 0. */
+int dabgpu_noise_profile_host_sync(dabgpu_ctx *ctx, const float *h_iq, size_t n_samples, size_t null_offset_samples, float freq_offset,
+                                   int fine_time_offset, const uint32_t *h_exclude, float *h_profile, float alpha, float *h_band_weight,
+                                   float *h_mean_noise, float *h_carrier_power, uint32_t *h_valid);
+/* steps 2 to 5 on the host (no device) from the 1536 carrier powers of step 1: exclude [48] or NULL, profile_in [128] or NULL,
+ * profile_out / band_weight [128] and mean_noise may be NULL (profile_out may be profile_in).  1 for a valid frame, 0 for a skipped
+ * one (whose outputs are those of "skipped" above), -1 for a null carrier_power or an alpha outside (0, 1]. */
+int dabgpu_noise_profile_bands_host(const float carrier_power[1536], const uint32_t *exclude, const float *profile_in, float alpha,
+                                    float *profile_out, float *band_weight, float *mean_noise);
+/* The exclusion words of step 3 from n transmitters' (main_id, sub_id): every carrier of dabgpu_tii_carriers set in out[48] (cleared
+ * first).  DABGPU_ERR_INVALID_ARG for an id out of range or a null argument (n = 0: all clear). */
+int dabgpu_noise_profile_exclude_tii(const uint8_t *main_ids, const uint8_t *sub_ids, int n, uint32_t out[48]);
+
+/* Banded receive diversity: dabgpu_diversity_combine_frames with a noise profile per branch.  h_band_weight [n_branches] (host memory,
+ * travels by value in the kernel argument like the branch table): entry b = a device pointer to [n_frames][128] band weights of
+ * branch b, or NULL for a branch without one.  h_band_weight NULL, or every entry NULL: exactly dabgpu_diversity_combine_frames.  For
+ * a branch with a table:
+ *   d_weight      must be NULL (the planner refuses both)
+ *   branch weight the mean of the frame's 128 band weights in the tree of "Noise profile" step 5, a band weight that is not positive
+ *                 and finite counting as 0.  It takes the place of w_b in the live rule and in the scale, the exception for one live
+ *                 branch of weight exactly 1 included.  The table of a frame is read whatever the branch's record says.
+ *   sum           carrier c of the branch enters with the weight of band c / 12 (0 where that is not positive and finite) in place of w_b
+ * A table that holds one normal value w in all 128 bands has the mean w exactly (for w < 2^121: above, the tree's sum overflows and the
+ * branch is dead), and the call then equals the scalar call with d_weight = w bit for bit; a table of ones on a single branch
+ * reproduces the demodulator's weighted soft bits.  With one branch the call gives interference-aware soft bits, with several
+ * maximal-ratio combining per band: a branch that is jammed in one part of the block still contributes everywhere else.
+ * Limit: the frame scale still rests on the power of the phase reference symbol, which includes the interferer: under an interferer
+ * of power I beside the signal power S every soft bit shrinks by (S + I) / S.
+ * _plan_banded: what dabgpu_diversity_plan refuses, then a table entry that is not 4-byte aligned and a branch with both a table and
+ * d_weight.  The host form takes h_band_weight[b] -> [128] floats in host memory (or NULL; NULL array: the scalar form). */
+int dabgpu_diversity_plan_banded(const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames, const int8_t *d_bits,
+                                 size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float *const *h_band_weight,
+                                 dabgpu_diversity_geometry *out);
+int dabgpu_diversity_combine_frames_banded(dabgpu_ctx *ctx, const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames,
+                                           int8_t *d_bits, size_t bits_frame_stride, int bits_layout, int symbols_per_block,
+                                           float *d_soft_scale, uint32_t *d_live_mask, const float *const *h_band_weight, void *stream);
+int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx *ctx, const float *const *h_dqpsk, const float *h_scale, const float *h_weight,
+                                              const int *h_valid, int n_branches, int bits_layout, int8_t *h_bits, float *h_soft_scale,
+                                              uint32_t *h_live_mask, const float *const *h_band_weight);
+/* the branch weight of a band table on the host: the tree mean above of 128 band weights */
+float dabgpu_diversity_band_mean_host(const float band_weight[128]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,9 +33,18 @@ then hold the whole NULL in front of each frame), `true` is 1 / (2 noise_sigma^2
 that of a branch without extra noise.  The output goes to profiles/tx/waterfall_mrc.md, which such a run writes anew unless --append is given: the
 committed file is a unit run followed by an estimated and a true run with --append, and any of them can be repeated alone into an --out of its own.
 Without these two options the output is what it was.
+With --interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB a narrowband interferer is added to every channel stream behind the channel: Gaussian noise confined to
+WIDTH_KHZ around OFFSET_KHZ from the block's centre (white noise made with torch on the device, every bin of its transform outside the band cleared;
+a seed per stream), its total power IS_DB relative to the signal power the SNR refers to.  The option is the tool's own: the channel model has no
+interferer.  It wants the branch path (--branches K, or --weights banded, which also takes K = 1).  With --weights banded [--alpha A] every branch's
+slice and sync records go through dabgpu_noise_profile_frames (the state carried from frame to frame in place, smoothing A, default 0.25) and the
+band weights into dabgpu_diversity_combine_frames_banded: with one branch interference-aware soft bits, with several maximal-ratio combining per
+band.  Every cell still reads `single -> combined`, branch 0's own weighted soft bits against the banded combination.  The output goes to
+profiles/tx/waterfall_banded.md.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
                               [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]
-                              [--branch-noise-db A,B,...] [--weights unit|estimated|true] [--append]"""
+                              [--branch-noise-db A,B,...] [--weights unit|estimated|true|banded] [--alpha A] [--interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB]
+                              [--append]"""
 import argparse
 import math
 import os
@@ -67,13 +76,26 @@ def main():
     ap.add_argument("--soft-level", type=float, default=64.0)
     ap.add_argument("--branches", type=int, default=1)
     ap.add_argument("--branch-noise-db", default=None)
-    ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true"))
+    ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true", "banded"))
+    ap.add_argument("--alpha", type=float, default=0.25)
+    ap.add_argument("--interferer", default=None)
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     K = a.branches
     mrc = a.branch_noise_db is not None or a.weights != "unit"
-    if mrc and K == 1:
+    banded = a.weights == "banded"
+    branch_path = K > 1 or banded
+    if mrc and K == 1 and not banded:
         ap.error("--branch-noise-db and --weights want --branches K")
+    if not 0.0 < a.alpha <= 1.0:
+        ap.error("--alpha takes a value in (0, 1]")
+    jam = None
+    if a.interferer is not None:
+        if not branch_path:
+            ap.error("--interferer wants --branches K or --weights banded")
+        jam = [float(v) for v in a.interferer.split(":")]
+        if len(jam) != 3 or not 0.0 < jam[1] <= 2048.0 or abs(jam[0]) + jam[1] / 2.0 > 1024.0:
+            ap.error("--interferer takes OFFSET_KHZ:WIDTH_KHZ:IS_DB inside the sampled band")
     if a.append and not mrc:
         ap.error("--append wants --branch-noise-db or --weights (the other records decide by their options whether they append)")
     branch_db = [float(v) for v in a.branch_noise_db.split(",")] if a.branch_noise_db is not None else [0.0] * K
@@ -81,13 +103,13 @@ def main():
         ap.error("--branch-noise-db takes one value per branch")
     p_lead = NULL + P_LEAD if mrc else P_LEAD                                   # (with weights: the whole NULL in front of every frame)
     stride = p_lead + 1544 + S
-    if K != 1:
-        if K < 2 or K > 8:
+    if branch_path:
+        if (K < 2 and not banded) or K < 1 or K > 8:
             ap.error("--branches takes 2 .. 8")
         if a.clock_ppm is not None or a.adjacent_db is not None or a.ber or a.soft_bits == "csi":
             ap.error("--branches is not available with --clock-ppm, --adjacent-db, --ber or --soft-bits (its branches are weighted already)")
         if a.out == ap.get_default("out"):
-            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_mrc.md" if mrc else "waterfall_diversity.md")
+            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_banded.md" if banded else "waterfall_mrc.md" if mrc else "waterfall_diversity.md")
     csi = a.soft_bits == "csi"
     if csi and (a.clock_ppm is not None or a.adjacent_db is not None):
         ap.error("--soft-bits csi is not available with --clock-ppm or --adjacent-db")
@@ -173,7 +195,7 @@ def main():
                 f"{E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
                 f"`python tools/waterfall.py --soft-bits csi{fading_args}`; "
                 "the verdict line is the csi policy's.", ""]
-    if K > 1:
+    if branch_path:
         fading_args = "" if a.doppler_hz is None else f" --profile {a.profile or 'tu6'} --doppler-hz {a.doppler_hz:g}"
         text = [f"# Receiver sensitivity with receive diversity: {K} branches per receiver", "",
                 f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  Every receiver hears {K} realisations of the channel (a noise seed"
@@ -184,14 +206,19 @@ def main():
                 f"`python tools/waterfall.py --branches {K} --streams {E} --frames {F} --snr {a.snr}{fading_args}`; the verdict line is the combination's.", ""]
         if mrc:
             how = {"unit": "no weights (every branch 1)", "estimated": "the weight arrays dabgpu_noise_estimate_frames wrote from every branch's slice and sync records",
+                   "banded": f"the band weights dabgpu_noise_profile_frames wrote from every branch's slice and sync records (alpha {a.alpha:g}, the state carried from "
+                             "frame to frame), applied by dabgpu_diversity_combine_frames_banded",
                    "true": "the true weights 1 / (2 noise_sigma^2) of every branch's channel stream"}[a.weights]
-            text = [f"# Receive diversity with branches of unequal noise: weights {a.weights}", "",
+            text = [f"# Receive diversity with {'band weights' if banded else 'branches of unequal noise'}: weights {a.weights}", "",
                     f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall_diversity.md` with the branches' noise raised by "
                     f"{', '.join(f'{d:g}' for d in branch_db)} dB (SNR is that of a branch without extra noise) and the combination made with {how}.  Every cell is "
                     f"`single -> combined`: branch 0 decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of "
                     f"every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
                     f"`python tools/waterfall.py --branches {K} --branch-noise-db {','.join(f'{d:g}' for d in branch_db)} --weights {a.weights} --streams {E} --frames {F} "
-                    f"--snr {a.snr}{fading_args}{' --append' if a.append else ''}`; the verdict line is the combination's.", ""]
+                    f"--snr {a.snr}{fading_args}{' --alpha %g' % a.alpha if banded else ''}{' --interferer ' + a.interferer if jam else ''}"
+                    f"{' --append' if a.append else ''}`; the verdict line is the combination's."
+                    + (f"  Interferer: Gaussian noise {jam[1]:g} kHz wide {jam[0]:+g} kHz from the centre, {jam[2]:+g} dB relative to the signal, a seed per stream; the "
+                       "frame scale rests on the power of the phase reference symbol, interferer included." if jam else ""), ""]
     verdicts = []
     profiles, fading =[(n, t, None, None) for n, t in PROFILES], None
     if adjacent_db:
@@ -230,6 +257,18 @@ def main():
             ch.seek(0)
             ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rows * n_rx * 8)
             d_use = d_rx
+            if jam is not None:
+                # Gaussian noise confined to the band, total power IS_DB over the signal's 1536 h2, a seed per stream
+                gen = torch.Generator(device="cuda")
+                f_khz = torch.fft.fftfreq(n_rx, device="cuda") * 2048.0
+                keep = (f_khz - jam[0] + 1024.0) % 2048.0 - 1024.0
+                keep = keep.abs() <= jam[1] / 2.0
+                for e in range(EC):
+                    gen.manual_seed(7000 + e)
+                    X = torch.fft.fft(torch.view_as_complex(torch.randn((n_rx, 2), dtype=torch.float32, device="cuda", generator=gen)))
+                    x = torch.fft.ifft(torch.where(keep, X, torch.zeros_like(X)))
+                    x = x * math.sqrt(1536.0 * h2 * 10.0 ** (jam[2] / 10.0)) / x.abs().square().mean().sqrt()
+                    d_rx[e] += torch.view_as_real(x)
             if comb is not None:
                 comb.seek(0); spl.seek(0)
                 comb.combine(d_rows, n_rx, n_wide, d_wide, in_stride_samples=n_rx, out_stride_bytes=n_wide * 8)
@@ -239,7 +278,7 @@ def main():
                 rs.seek(0)
                 rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
                 d_use = d_rs
-            if K > 1:
+            if branch_path:
                 # receive diversity: ring 0 takes branch 0's own soft bits, ring 1 the combination of the K branches
                 soft = dabgpu.SoftCfg(dabgpu.SOFT_CSI, a.soft_level)
                 d_st = [torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda") for _ in range(K)]
@@ -248,6 +287,9 @@ def main():
                 wb = [None] * K
                 if a.weights == "estimated":
                     wb = [torch.zeros((E,), dtype=torch.float32, device="cuda") for _ in range(K)]
+                elif banded:
+                    state = [torch.zeros((E, 128), dtype=torch.float32, device="cuda") for _ in range(K)]
+                    bands = [torch.zeros((E, 128), dtype=torch.float32, device="cuda") for _ in range(K)]
                 elif a.weights == "true":
                     wb = [torch.full((E,), 1.0 / (2.0 * (sigma * 10.0 ** (branch_db[b] / 20.0)) ** 2), dtype=torch.float32, device="cuda") for b in range(K)]
                 rings = [torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda") for _ in range(2)]
@@ -269,7 +311,11 @@ def main():
                                                           bits_frame_stride=H * dabgpu.NB_FRAME_BITS if b == 0 else 0, soft_scale=kb[b])
                         if a.weights == "estimated":
                             ctx.noise_estimate(sl, E, stride, p_lead - NULL, states=d_st[b], weight=wb[b])
-                    ctx.diversity_combine([(dq[b], kb[b], wb[b], d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
+                        if banded:
+                            ctx.noise_profile(sl, E, stride, p_lead - NULL, states=d_st[b], profile_in=state[b], alpha=a.alpha, profile_out=state[b],
+                                              band_weight=bands[b])
+                    ctx.diversity_combine([(dq[b], kb[b], wb[b], d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS,
+                                          band_weights=bands if banded else None)
                     for r in range(2):
                         ctx.decode_frames(rings[r], E, H * dabgpu.NB_FRAME_BITS, H, j % H, subs, d_fib, fres, msc, 4 * nb, mres)
                         torch.cuda.synchronize()
@@ -283,7 +329,7 @@ def main():
                                 err[r][owner[i]] += int(bad[:, off:off + n].sum()); tot[r][owner[i]] += E * n
                 rows_ref.append((snr, crc_ok[0] / crc_n[0], [e / t for e, t in zip(err[0], tot[0])], tot[0]))
                 rows.append((snr, crc_ok[1] / crc_n[1], [e / t for e, t in zip(err[1], tot[1])], tot[1]))
-            for pol in (policies if K == 1 else []):
+            for pol in (policies if not branch_path else []):
                 d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
                 hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
                 d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
@@ -334,7 +380,7 @@ def main():
             rs.close()
         if comb is not None:
             comb.close(); spl.close()
-        if csi or K > 1:
+        if csi or branch_path:
             # both policies side by side: normalised -> csi in every cell (receive diversity: single -> combined)
             text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
             fmt = lambda r: f"{r:.2e}" if r else "0"
@@ -365,7 +411,7 @@ def main():
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    append = bool(clock_ppm or adjacent_db or ((csi or K > 1) and a.doppler_hz is not None) or a.append)       # (the csi record: white noise and two paths first, the fading run behind them)
+    append = bool(clock_ppm or adjacent_db or ((csi or branch_path) and a.doppler_hz is not None) or a.append)       # (the csi record: white noise and two paths first, the fading run behind them)
     open(a.out, "a" if append else "w").write(("\n" if append else "") + text)
     return 0 if all(verdicts) else 1
 
