@@ -1615,6 +1615,170 @@ extern "C" int dabgpu_channeliser_decim_for(double rate_hz) {
     return 0;                                                                // (NaN included)
 }
 
+// ---- interferer (include/dabgpu.h, "Interferer"; the arithmetic is interferer_core.h's, shared with the kernel) ----
+#include "interferer_core.h"
+
+namespace {
+constexpr double ITF_BETA = 6.2;            // Kaiser: 16 taps per phase and a transition of 0.25 low-rate cycles give about -65 dB
+constexpr int ITF_GRID = 8192;              // the figures' frequencies: 0.5 i / ITF_GRID, i = 0 .. ITF_GRID (a 16384-point spectrum's)
+}
+
+extern "C" int dabgpu_interferer_design(double width_cycles, dabgpu_interferer_shape* out) {
+    if (!out) { dabgpu_set_error("interferer_design: null result"); return DABGPU_ERR_INVALID_ARG; }
+    if (!std::isfinite(width_cycles)) { dabgpu_set_error("interferer_design: width_cycles is not finite"); return DABGPU_ERR_INVALID_ARG; }
+    if (width_cycles > 1.0 || width_cycles < DABGPU_INTERFERER_MIN_WIDTH) {
+        dabgpu_set_error("interferer_design: width_cycles %g (%g..1 are accepted)", width_cycles, DABGPU_INTERFERER_MIN_WIDTH); return DABGPU_ERR_INVALID_ARG;
+    }
+    int L = DABGPU_INTERFERER_MAX_INTERP;
+    while (L > 1 && !(width_cycles * (double)L + DABGPU_INTERFERER_TRANSITION <= 1.0)) L >>= 1;
+    const int K = DABGPU_INTERFERER_TAPS * L;
+    const double fc = 0.5 * width_cycles;
+    const double centre = 0.5 * (double)(K - 1), i0_beta = rs_bessel_i0(ITF_BETA);
+    static thread_local double h[DABGPU_INTERFERER_TAPS * DABGPU_INTERFERER_MAX_INTERP];
+    double energy = 0.0;
+    for (int j = 0; j < K; j++) {
+        const double t = (double)j - centre, u = 2.0 * t / (double)K;
+        const double win = rs_bessel_i0(ITF_BETA * std::sqrt(1.0 - u * u)) / i0_beta;
+        const double a = RS_PI * 2.0 * fc * t;
+        h[j] = 2.0 * fc * ((a == 0.0) ? 1.0 : std::sin(a) / a) * win;
+        energy += h[j] * h[j];
+    }
+    const double scale = std::sqrt(0.5 * (double)L / energy);
+    for (float& v : out->taps) v = 0.0f;
+    for (int j = 0; j < K; j++) out->taps[j] = (float)(h[j] * scale);
+    out->interp = L; out->reserved = 0;
+    out->width_cycles = width_cycles; out->cutoff_cycles = fc; out->beta = ITF_BETA;
+    // the figures, from the float table
+    double lo = INFINITY, hi = 0.0;
+    for (int r = 0; r < L; r++) {
+        double p = 0.0;
+        for (int t = 0; t < DABGPU_INTERFERER_TAPS; t++) p += (double)out->taps[r + L * t] * (double)out->taps[r + L * t];
+        lo = std::min(lo, p); hi = std::max(hi, p);
+    }
+    out->phase_ripple = hi / lo;
+    const double stop = 0.5 * width_cycles + 0.5 * DABGPU_INTERFERER_TRANSITION / (double)L;
+    double total = 0.0, inband = 0.0, worst_stop = 0.0, p0 = 0.0, p_prev = 0.0, half_width = 0.5;
+    bool crossed = false;
+    for (int i = 0; i <= ITF_GRID; i++) {
+        const double f = 0.5 * (double)i / (double)ITF_GRID;
+        const double step_re = std::cos(2.0 * RS_PI * f), step_im = -std::sin(2.0 * RS_PI * f);
+        double er = 1.0, ei = 0.0, sr = 0.0, si = 0.0;
+        for (int j = 0; j < K; j++) {
+            sr += (double)out->taps[j] * er; si += (double)out->taps[j] * ei;
+            const double nr = er * step_re - ei * step_im;
+            ei = er * step_im + ei * step_re; er = nr;
+        }
+        const double p = sr * sr + si * si, w = (i == 0 || i == ITF_GRID) ? 0.5 : 1.0;
+        if (i == 0) p0 = p;
+        total += w * p;
+        if (f <= 0.5 * width_cycles) inband += w * p;
+        if (f >= stop) worst_stop = std::max(worst_stop, p);
+        if (!crossed && i > 0 && p < 0.5 * p0) {                            // the first crossing of half the power at 0, interpolated
+            crossed = true;
+            half_width = (0.5 / (double)ITF_GRID) * ((double)(i - 1) + (p_prev - 0.5 * p0) / (p_prev - p));
+        }
+        p_prev = p;
+    }
+    out->width_3db_cycles = 2.0 * half_width;
+    out->inband_share = inband / total;
+    out->stopband_level = std::sqrt(worst_stop / p0);
+    return DABGPU_OK;
+}
+
+int dabgpu_host_interferer_plan(const char* who, const dabgpu_interferer_stream* params, size_t n_streams, const dabgpu_interferer_shape* shapes,
+                                int n_shapes, dabgpu_interferer_geometry* out) {
+    if (out) *out = dabgpu_interferer_geometry{DABGPU_INTERFERER_BLOCK, 0, 0, 0};
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("%s: %zu streams (1..1048576 are accepted)", who, n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (n_shapes < 0 || n_shapes > DABGPU_INTERFERER_MAX_SHAPES) {
+        dabgpu_set_error("%s: %d shapes (0..%d are accepted)", who, n_shapes, DABGPU_INTERFERER_MAX_SHAPES); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!params || (n_shapes > 0 && !shapes)) { dabgpu_set_error("%s: null parameters / shapes", who); return DABGPU_ERR_INVALID_ARG; }
+    uint32_t slot_bytes = 0, band_slots = 0;
+    for (int i = 0; i < n_shapes; i++) {
+        const int L = shapes[i].interp;
+        if (L < 1 || L > DABGPU_INTERFERER_MAX_INTERP || (L & (L - 1))) {
+            dabgpu_set_error("%s: shape %d: interp %d (a power of two in 1..%d)", who, i, L, DABGPU_INTERFERER_MAX_INTERP); return DABGPU_ERR_INVALID_ARG;
+        }
+        for (int j = 0; j < DABGPU_INTERFERER_TAPS * L; j++)
+            if (!std::isfinite(shapes[i].taps[j])) { dabgpu_set_error("%s: shape %d: tap %d is not finite", who, i, j); return DABGPU_ERR_INVALID_ARG; }
+        slot_bytes = std::max(slot_bytes, dabgpu::itf_slot_bytes(L));
+    }
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_interferer_stream& P = params[s];
+        if (P.n_sources < 0 || P.n_sources > DABGPU_INTERFERER_MAX) {
+            dabgpu_set_error("%s: stream %zu: %d sources (0..%d are accepted)", who, s, P.n_sources, DABGPU_INTERFERER_MAX); return DABGPU_ERR_INVALID_ARG;
+        }
+        uint32_t shaped = 0;
+        for (int k = 0; k < P.n_sources; k++) {
+            const dabgpu_interferer_source& S = P.source[k];
+            if (S.kind == DABGPU_INTERFERER_OFF) continue;
+            if (S.kind != DABGPU_INTERFERER_TONE && S.kind != DABGPU_INTERFERER_BAND) {
+                dabgpu_set_error("%s: stream %zu: source %d: kind %d (OFF, TONE or BAND)", who, s, k, S.kind); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (!std::isfinite(S.amp)) { dabgpu_set_error("%s: stream %zu: source %d: amp is not finite", who, s, k); return DABGPU_ERR_INVALID_ARG; }
+            if (S.amp < 0.0f) { dabgpu_set_error("%s: stream %zu: source %d: amp is negative", who, s, k); return DABGPU_ERR_INVALID_ARG; }
+            if (S.gate_on > S.gate_period) {
+                dabgpu_set_error("%s: stream %zu: source %d: gate_on %llu above gate_period %llu", who, s, k, (unsigned long long)S.gate_on,
+                                 (unsigned long long)S.gate_period);
+                return DABGPU_ERR_INVALID_ARG;
+            }
+            if (S.gate_offset >= DABGPU_INTERFERER_MAX_POSITION || S.gate_offset <= -DABGPU_INTERFERER_MAX_POSITION) {
+                dabgpu_set_error("%s: stream %zu: source %d: gate_offset at or beyond +-2^62", who, s, k); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (S.kind == DABGPU_INTERFERER_BAND && (S.shape < -1 || S.shape >= n_shapes)) {
+                dabgpu_set_error("%s: stream %zu: source %d: shape %d of %d (-1 = white)", who, s, k, S.shape, n_shapes); return DABGPU_ERR_INVALID_ARG;
+            }
+            if (dabgpu::itf_shaped(S)) shaped++;
+        }
+        band_slots = std::max(band_slots, shaped);
+    }
+    if (out) { out->band_slots = band_slots; out->slot_bytes = band_slots ? slot_bytes : 0u; out->lds_bytes = band_slots * slot_bytes; }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_interferer_fits(const dabgpu_interferer_geometry& created, const dabgpu_interferer_geometry& wanted) {
+    if (wanted.band_slots > created.band_slots) {
+        dabgpu_set_error("interferer_bank_set_params: %u shaped BAND sources on one stream, the bank was created for %u (create the bank with its "
+                         "widest parameters)", wanted.band_slots, created.band_slots);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_interferer_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_out, const void* out,
+                                       int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers) {
+    const bool has_in = in != nullptr;                                      // (NULL: the interferer alone, the stride is not read)
+    if (out_format != DABGPU_IQ_RAW_F32L && out_format != DABGPU_IQ_RAW_U8) {
+        dabgpu_set_error("%s: output format %d (DABGPU_IQ_RAW_F32L or DABGPU_IQ_RAW_U8 only)", who, out_format); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_out > ((size_t)1 << 31)) { dabgpu_set_error("%s: n_out = %zu (up to 2^31 per call)", who, n_out); return DABGPU_ERR_INVALID_ARG; }
+    if (n_out > 0 && !out) { dabgpu_set_error("%s: null output", who); return DABGPU_ERR_INVALID_ARG; }
+    if (has_in && in_stride_samples != 0 && (in_stride_samples < n_out || ((in_stride_samples & 1) && device_pointers))) {
+        dabgpu_set_error("%s: in_stride_samples must be 0 (one shared input) or an even count >= n_out", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    const size_t exact = n_out * (out_format == DABGPU_IQ_RAW_F32L ? 8u : 2u);
+    const size_t row = device_pointers ? (exact + 15u) & ~(size_t)15 : exact;
+    if (*out_stride_bytes == 0) *out_stride_bytes = row;
+    if ((device_pointers && (*out_stride_bytes & 15)) || *out_stride_bytes < row) {
+        dabgpu_set_error("%s: out_stride_bytes must be 0 or a multiple of 16 that holds n_out samples", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (device_pointers && ((has_in && ((uintptr_t)in & 15)) || ((uintptr_t)out & 15))) {
+        dabgpu_set_error("%s: input and output must be 16-byte aligned", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (has_in && in == out && (out_format != DABGPU_IQ_RAW_F32L || (n_streams > 1 && in_stride_samples * 8u != *out_stride_bytes))) {
+        dabgpu_set_error("%s: in place needs complex float output and rows equally far apart", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (out_format == DABGPU_IQ_RAW_U8 && !std::isfinite(u8_scale)) { dabgpu_set_error("%s: u8_scale is not finite", who); return DABGPU_ERR_INVALID_ARG; }
+    const size_t tiles = (n_out + 3 + DABGPU_INTERFERER_BLOCK - 1) / DABGPU_INTERFERER_BLOCK;
+    if (tiles * n_streams > 0x7FFFFFFFull) { dabgpu_set_error("%s: n_streams x n_out too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_interferer_plan(const dabgpu_interferer_stream* params, size_t n_streams, const dabgpu_interferer_shape* shapes, int n_shapes,
+                                      dabgpu_interferer_geometry* out) {
+    return dabgpu_host_interferer_plan("interferer_plan", params, n_streams, shapes, n_shapes, out);
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

@@ -291,6 +291,16 @@ int dabgpu_host_channel_fading_check(const char* who, const dabgpu_channel_strea
 // the geometry of a fading bank from the plain one: always staged, the tile's grid gains behind the staged input
 dabgpu_channel_geometry dabgpu_host_channel_fading_geometry(dabgpu_channel_geometry plain);
 
+// ---- interferer planner (interferer.hip launches from it; include/dabgpu.h, dabgpu_interferer_plan) ----
+// DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream, source, field); `who` names the entry point
+int dabgpu_host_interferer_plan(const char* who, const dabgpu_interferer_stream* params, size_t n_streams, const dabgpu_interferer_shape* shapes,
+                                int n_shapes, dabgpu_interferer_geometry* out);
+// dabgpu_interferer_bank_set_params: new parameters must fit the LDS slots of the bank's creation (a captured call has them baked in)
+int dabgpu_host_interferer_fits(const dabgpu_interferer_geometry& created, const dabgpu_interferer_geometry& wanted);
+// the arguments of a dabgpu_interferer_bank_apply call, as dabgpu_host_channel_check_apply; in may be NULL, in == out is in place
+int dabgpu_host_interferer_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_out, const void* out,
+                                       int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers = true);
+
 // ---- resampler planner (resample.hip launches from it; include/dabgpu.h, dabgpu_resample_plan) ----
 // DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream index, field); `who` names the entry point.
 // max_step_q62: the largest step the bank's design serves (dabgpu_host_resample_max_step_q62 of its max_step)

@@ -100,6 +100,8 @@ ABI_SYMBOLS = [
     "dabgpu_noise_profile_plan", "dabgpu_noise_profile_frames", "dabgpu_noise_profile_host_sync", "dabgpu_noise_profile_bands_host",
     "dabgpu_noise_profile_exclude_tii", "dabgpu_diversity_plan_banded", "dabgpu_diversity_combine_frames_banded",
     "dabgpu_diversity_combine_banded_host_sync", "dabgpu_diversity_band_mean_host",
+    "dabgpu_interferer_design", "dabgpu_interferer_plan", "dabgpu_interferer_bank_create", "dabgpu_interferer_bank_destroy",
+    "dabgpu_interferer_bank_set_params", "dabgpu_interferer_bank_seek", "dabgpu_interferer_bank_apply", "dabgpu_interferer_bank_apply_host_sync",
 ]
 NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
@@ -234,6 +236,35 @@ FADING_OSC, FADING_GRID, FADING_MAX_DOPPLER_CYCLES = 17, 64, 2.0 ** -11
 class ChannelGeometry(C.Structure):
     """dabgpu_channel_geometry"""
     _fields_ = [("halo", C.c_uint32), ("block_samples", C.c_uint32), ("lds_bytes", C.c_uint32), ("staged", C.c_uint32)]
+
+
+# interferer (include/dabgpu.h)
+INTERFERER_MAX, INTERFERER_MAX_SHAPES, INTERFERER_TAPS, INTERFERER_MAX_INTERP, INTERFERER_BLOCK = 4, 4, 16, 64, 1024
+INTERFERER_TRANSITION, INTERFERER_MIN_WIDTH, INTERFERER_MAX_POSITION = 0.25, 2.0 ** -8, 1 << 62
+INTERFERER_OFF, INTERFERER_TONE, INTERFERER_BAND = 0, 1, 2
+
+
+class InterfererSource(C.Structure):
+    """dabgpu_interferer_source"""
+    _fields_ = [("kind", C.c_int32), ("shape", C.c_int32), ("amp", C.c_float), ("reserved", C.c_int32), ("freq_q64", C.c_uint64),
+                ("phase0_q64", C.c_uint64), ("gate_period", C.c_uint64), ("gate_on", C.c_uint64), ("gate_offset", C.c_int64)]
+
+
+class InterfererStream(C.Structure):
+    """dabgpu_interferer_stream"""
+    _fields_ = [("seed", C.c_uint64), ("n_sources", C.c_int32), ("reserved", C.c_int32), ("source", InterfererSource * INTERFERER_MAX)]
+
+
+class InterfererShape(C.Structure):
+    """dabgpu_interferer_shape: the design record (its own figures) and the table of 16 x interp taps"""
+    _fields_ = [("interp", C.c_int32), ("reserved", C.c_int32), ("width_cycles", C.c_double), ("cutoff_cycles", C.c_double), ("beta", C.c_double),
+                ("width_3db_cycles", C.c_double), ("inband_share", C.c_double), ("stopband_level", C.c_double), ("phase_ripple", C.c_double),
+                ("taps", C.c_float * (INTERFERER_TAPS * INTERFERER_MAX_INTERP))]
+
+
+class InterfererGeometry(C.Structure):
+    """dabgpu_interferer_geometry"""
+    _fields_ = [("block_samples", C.c_uint32), ("band_slots", C.c_uint32), ("slot_bytes", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
 class ResampleStream(C.Structure):
@@ -603,6 +634,15 @@ def lib():
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.dabgpu_ber_fib_group_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_ber_codeword_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_interferer_design.argtypes = [C.c_double, C.c_void_p]
+        L.dabgpu_interferer_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_interferer_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.dabgpu_interferer_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_interferer_bank_destroy.restype = None
+        L.dabgpu_interferer_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_interferer_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_interferer_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p]
+        L.dabgpu_interferer_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float]
         _lib = L
     return _lib
 
@@ -1365,6 +1405,91 @@ class Channel(_Handle):
         return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_channel_bank_apply_host_sync(
             self._h, _ptr(x), in_stride_samples, n_in, int(bool(wrap)), n_out, _ptr(out), fmt, stride, float(u8_scale)),
             "dabgpu_channel_bank_apply_host_sync"), h_in, self.n, n_out, fmt)
+
+
+def interferer_source(kind=INTERFERER_OFF, amp=0.0, cycles_per_sample=0.0, phase0_cycles=0.0, shape=-1, gate_period=0, gate_on=0, gate_offset=0,
+                      freq_q64=None, phase0_q64=None):
+    """an InterfererSource: a tone at, or a band centred on, cycles_per_sample (Hz / 2.048e6 for DAB); shape = index of a bank's shape, -1 = white;
+    the gate in samples (gate_period = 0: always on)"""
+    S = InterfererSource()
+    S.kind, S.shape, S.amp = int(kind), int(shape), float(amp)
+    S.freq_q64 = lib().dabgpu_channel_freq_q64(float(cycles_per_sample)) if freq_q64 is None else int(freq_q64)
+    S.phase0_q64 = lib().dabgpu_channel_freq_q64(float(phase0_cycles)) if phase0_q64 is None else int(phase0_q64)
+    S.gate_period, S.gate_on, S.gate_offset = int(gate_period), int(gate_on), int(gate_offset)
+    return S
+
+
+def interferer_stream(sources=(), seed=0):
+    """an InterfererStream from up to INTERFERER_MAX InterfererSource, in list order"""
+    P = InterfererStream()
+    P.seed, P.n_sources = int(seed), len(sources)
+    for k, S in enumerate(sources[:INTERFERER_MAX]):
+        P.source[k] = S
+    return P
+
+
+def interferer_design(width_cycles):
+    """dabgpu_interferer_design (host only): the InterfererShape of a flat band width_cycles wide (two-sided, a fraction of the sample rate:
+    Hz / 2.048e6 for DAB) with its own figures; raises DabGpuError"""
+    H = InterfererShape()
+    check(lib().dabgpu_interferer_design(float(width_cycles), C.byref(H)), "dabgpu_interferer_design")
+    return H
+
+
+def interferer_plan(streams, shapes=()):
+    """dabgpu_interferer_plan (host only): {"block_samples", "band_slots", "slot_bytes", "lds_bytes"} of a list of InterfererStream against a
+    list of InterfererShape; raises DabGpuError"""
+    n, ns = len(streams), len(shapes)
+    arr = (InterfererStream * n)(*streams) if n else None
+    sh = (InterfererShape * ns)(*shapes) if ns else None
+    g = InterfererGeometry()
+    check(lib().dabgpu_interferer_plan(arr, n, sh, ns, C.byref(g)), "dabgpu_interferer_plan")
+    return {"block_samples": g.block_samples, "band_slots": g.band_slots, "slot_bytes": g.slot_bytes, "lds_bytes": g.lds_bytes}
+
+
+class Interferer(_Handle):
+    """dabgpu_interferer_bank: tones, band-limited noise and gated bursts added to n streams; the stream position lives on the device"""
+    _destroy = "dabgpu_interferer_bank_destroy"
+
+    def __init__(self, ctx, streams, shapes=()):
+        self._ctx = ctx
+        self.n = len(streams)
+        self.plan = interferer_plan(streams, shapes)
+        arr = (InterfererStream * self.n)(*streams)
+        sh = (InterfererShape * len(shapes))(*shapes) if len(shapes) else None
+        self._h = C.c_void_p()
+        check(lib().dabgpu_interferer_bank_create(ctx._h, self.n, arr, sh, len(shapes), C.byref(self._h)), "dabgpu_interferer_bank_create")
+
+    def set_params(self, streams, stream=None):
+        assert len(streams) == self.n
+        arr = (InterfererStream * self.n)(*streams)
+        check(lib().dabgpu_interferer_bank_set_params(self._h, arr, Context._stream(stream)), "dabgpu_interferer_bank_set_params")
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_interferer_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_interferer_bank_seek")
+
+    def apply(self, d_in, n_out, d_out, in_stride_samples=0, out_format=None, out_stride_bytes=0, u8_scale=1.0, stream=None):
+        """d_in complex float (device, or None: the interferer alone) -> d_out rows of n_out samples, complex float (default) or u8 pairs;
+        d_out may be d_in; asynchronous"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_interferer_bank_apply(self._h, _ptr(d_in), in_stride_samples, n_out, _ptr(d_out), fmt, out_stride_bytes, float(u8_scale),
+                                                 Context._stream(stream)), "dabgpu_interferer_bank_apply")
+
+    def apply_host(self, h_in, n_out, in_stride_samples=0, out_format=None, u8_scale=1.0):
+        """h_in [n][>= n_out] complex64 (or [>= n_out] shared with in_stride_samples = 0, or None) -> [n][n_out] complex64 / [n][n_out][2] uint8"""
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        if h_in is None:
+            sb = 8 if fmt == IQ_FORMATS.index("raw_f32l") else 2
+            stride = (n_out * sb + 15) & ~15
+            out = np.zeros((self.n, stride), np.uint8)
+            check(lib().dabgpu_interferer_bank_apply_host_sync(self._h, None, 0, n_out, _ptr(out), fmt, stride, float(u8_scale)),
+                  "dabgpu_interferer_bank_apply_host_sync")
+            out = out[:, :n_out * sb]
+            return out.copy().view(np.complex64) if sb == 8 else out.reshape(self.n, n_out, 2).copy()
+        return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_interferer_bank_apply_host_sync(
+            self._h, _ptr(x), in_stride_samples, n_out, _ptr(out), fmt, stride, float(u8_scale)),
+            "dabgpu_interferer_bank_apply_host_sync"), h_in, self.n, n_out, fmt)
 
 
 def resample_step(in_rate_hz=2048000.0, out_rate_hz=2048000.0, ppm=0.0):

@@ -41,6 +41,14 @@
 // channel-state weighted soft bits (OFDM_Demod::SetSoftDecision), level L in [1, 127], default 64; normalised, the default, is the
 // reference's.  Transmission mode I and the OFDM stage only.
 //
+// --soft-bits banded [--alpha A] [--soft-level L] (include/dabgpu.h "Noise profile", "Banded receive diversity"): the demodulator runs under
+// the csi policy; inside the frame observer the head of GetCorrelationTimeBuffer() -- the NULL behind the delivered frame, as --tii reads it:
+// fine time offset 0, rotation GetNetFrequencyOffset() -- goes to DAB_Noise_Profile::Update (smoothing A in (0, 1], default 0.25), and the 128
+// band weights with GetFrameDataVec() and GetSoftScale() to DAB_Diversity_Combiner::Combine with one branch; the combined soft bits take the
+// place of the demodulator's for the decoders and the output file.  A frame whose profile is not valid keeps the demodulator's own csi
+// bits.  The restrictions are --tii's: Synchronize() after every Process(), --ofdm-block-size up to 193952, not with --input-rate or
+// --channel-offset-hz.
+//
 // --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
@@ -77,6 +85,8 @@
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
+#include "ofdm/dab_noise_profile.h"
+#include "ofdm/dab_diversity_combiner.h"
 
 struct Args {
     std::string input_file;
@@ -103,6 +113,9 @@ struct Args {
     int soft_policy = DABGPU_SOFT_NORMALISED;
     float soft_level = 64.0f;
     bool soft_level_given = false;
+    bool soft_banded = false;
+    float alpha = 0.25f;
+    bool alpha_given = false;
 };
 
 static void usage(const char* argv0) {
@@ -113,7 +126,7 @@ static void usage(const char* argv0) {
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
-        "  [--soft-bits normalised|csi] [--soft-level 1..127]\n"
+        "  [--soft-bits normalised|csi|banded] [--soft-level 1..127] [--alpha A]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -182,8 +195,10 @@ static bool parse_args(int argc, char** argv, Args& args) {
             const std::string p = value();
             if (p == "normalised") args.soft_policy = DABGPU_SOFT_NORMALISED;
             else if (p == "csi") args.soft_policy = DABGPU_SOFT_CSI;
-            else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised or csi)");
+            else if (p == "banded") { args.soft_policy = DABGPU_SOFT_CSI; args.soft_banded = true; }
+            else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised, csi or banded)");
         }
+        else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
         else if (a == "--input-rate") args.input_rate = std::stod(value());
         else if (a == "--channel-offset-hz") { args.channel_offset_hz = std::stod(value()); args.channelise = true; }
@@ -194,6 +209,11 @@ static bool parse_args(int argc, char** argv, Args& args) {
     if (args.soft_policy != DABGPU_SOFT_NORMALISED && !args.is_ofdm_used) throw std::runtime_error("--soft-bits needs the OFDM stage");
     if (args.soft_level_given && args.soft_policy != DABGPU_SOFT_CSI) throw std::runtime_error("--soft-level needs --soft-bits csi");
     if (!(args.soft_level >= 1.0f && args.soft_level <= 127.0f)) throw std::runtime_error("--soft-level: a level from 1 to 127");
+    if (args.alpha_given && !args.soft_banded) throw std::runtime_error("--alpha needs --soft-bits banded");
+    if (!(args.alpha > 0.0f && args.alpha <= 1.0f)) throw std::runtime_error("--alpha: above 0, up to 1");
+    if (args.soft_banded && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--soft-bits banded: --ofdm-block-size may not exceed 193952");
+    if (args.soft_banded && args.channelise) throw std::runtime_error("--channel-offset-hz is not available with --soft-bits banded");
+    if (args.soft_banded && args.input_rate != 2.048e6) throw std::runtime_error("--input-rate is not available with --soft-bits banded (resampled blocks may exceed --ofdm-block-size)");
     if (args.snr && !args.is_ofdm_used) throw std::runtime_error("--snr needs the OFDM stage");
     if (args.snr && (args.ofdm_block_size < 2552 || args.ofdm_block_size > 98304)) throw std::runtime_error("--snr: --ofdm-block-size from 2552 to 98304");
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
@@ -354,6 +374,19 @@ static int run(const Args& args) {
         demod->GetConfig().sync.is_coarse_freq_correction = !args.ofdm_disable_coarse_freq;
         if (args.soft_policy != DABGPU_SOFT_NORMALISED) demod->SetSoftDecision(args.soft_policy, args.soft_level);
         std::vector<uint8_t> hard;
+        // --soft-bits banded: the profile of the NULL symbols, the one-branch combiner and the frame's combined soft bits
+        std::unique_ptr<DAB_Noise_Profile> profile;
+        std::unique_ptr<DAB_Diversity_Combiner> combiner;
+        std::vector<viterbi_bit_t> banded_bits;
+        int banded_desync = 0;
+        size_t banded_frames = 0, banded_kept = 0;
+        if (args.soft_banded) {
+            profile = std::make_unique<DAB_Noise_Profile>();
+            profile->SetAlpha(args.alpha);
+            combiner = std::make_unique<DAB_Diversity_Combiner>(1);
+            banded_bits.resize(DABGPU_NB_FRAME_BITS);
+            demod->EnableDebugBuffers(true);                                         // the products of every frame, from the first
+        }
         std::unique_ptr<TII_Decoder> tii;
         if (args.tii) tii = std::make_unique<TII_Decoder>(args.transmission_mode);
         int tii_desync = 0;
@@ -373,7 +406,22 @@ static int run(const Args& args) {
             }
             snr_null.clear();
         };
-        demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> bits) {
+        demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> demod_bits) {
+            tcb::span<const viterbi_bit_t> bits = demod_bits;
+            if (profile) {
+                if (demod->GetTotalFramesDesync() != banded_desync) { banded_desync = demod->GetTotalFramesDesync(); profile->Reset(); }
+                float w[DABGPU_NOISE_PROFILE_BANDS];
+                const auto null_region = demod->GetCorrelationTimeBuffer().first(2656);
+                bool combined = false;
+                if (profile->Update(null_region, 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid()) {
+                    // (the buffer has the reference's size, 75 x 2048; the products are its first 75 x 1536)
+                    const tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
+                    const tcb::span<const float> band_weights[1] = {{w, (size_t)DABGPU_NOISE_PROFILE_BANDS}};
+                    const float scale[1] = {demod->GetSoftScale()};
+                    combined = combiner->Combine(products, scale, tcb::span<const float>(), band_weights, banded_bits);
+                }
+                if (combined) { bits = banded_bits; banded_frames++; } else banded_kept++;
+            }
             if (snr) {
                 if (demod->GetTotalFramesDesync() != snr_desync) { snr_desync = demod->GetTotalFramesDesync(); snr_since_acquisition = 0; }
                 snr_null.clear();
@@ -445,13 +493,14 @@ static int run(const Args& args) {
                 if (!resampled.empty()) demod->Process(resampled);
             } else
             demod->Process(tcb::span<const std::complex<float>>(block.data(), length));
-            if (tii || snr) demod->Synchronize();                                   // the observer reads the head of the correlation buffer
+            if (tii || snr || profile) demod->Synchronize();                                   // the observer reads the head of the correlation buffer
             if (snr) snr_poll();
             if (length != block.size()) break;
         }
         demod->Synchronize();
         fprintf(stderr, "ofdm: frames_read=%d frames_desync=%d coarse=%.6g fine=%.6g\n", demod->GetTotalFramesRead(),
                 demod->GetTotalFramesDesync(), demod->GetCoarseFrequencyOffset(), demod->GetFineFrequencyOffset());
+        if (profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
     } else {
         std::vector<viterbi_bit_t> bits(radio->frame_bits());                         // Basic_Radio_Block::run, app_radio_blocks.h:31-38
         std::vector<uint8_t> packed(bits.size() / 8);

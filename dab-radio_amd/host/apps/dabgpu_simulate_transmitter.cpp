@@ -46,6 +46,14 @@
 //   --tap-kind K:static|rayleigh|rice:KDB   kind of tap K (list order, from 0); rice:KDB = Rice factor in dB, line of sight at cos 0.7
 // Without --doppler-hz, or with --doppler-hz 0 and every tap static, no fading bank is made: the code path and the bytes are those of the
 // channel options above.
+// Interferer (include/dabgpu.h "Interferer", DAB_Interferer): behind the channel and in front of the resampler and the combiner, so that it is
+// resampled and channelised like the noise.  IS_DB is the source's power, while its gate is on, relative to the signal power P that --snr-db
+// refers to.
+//   --interferer tone:OFFSET_HZ:IS_DB            repeatable, up to 4 in all: a carrier OFFSET_HZ from the block's centre
+//   --interferer band:OFFSET_HZ:WIDTH_HZ:IS_DB   band-limited Gaussian noise WIDTH_HZ wide (8000 .. 2048000) around OFFSET_HZ
+//   --interferer white:IS_DB                     white Gaussian noise over the whole sampled band (with a gate: bursts)
+//   --interferer-gate PERIOD:ON[:OFFSET]         for the --interferer before it: on for ON of every PERIOD samples, from sample OFFSET on
+//   --interferer-seed N                          default 1
 // TII (not in the reference, mode I; include/dabgpu.h "TII"):
 //   --tii P:C[:AMP]                repeatable, up to 4: a transmitter with main id P (0..69), sub id C (0..23) and amplitude AMP (default 1 =
 //                                  the power of a data carrier) fills the NULL period of every other frame, the first one included; the
@@ -65,6 +73,7 @@
 #include "dab/dabgpu_shared_context.h"
 #include "dab/tx/dab_channel_model.h"
 #include "dab/tx/dab_channeliser.h"
+#include "dab/tx/dab_interferer.h"
 #include "dab/tx/dab_resampler.h"
 #include "dabgpu.h"
 #include "ofdm/dab_ofdm_params_ref.h"
@@ -111,6 +120,10 @@ struct Args {
     struct TapKind { int tap; int kind; float rice_k; };
     std::vector<TapKind> tap_kinds;
     std::vector<dabgpu_tii_tx> tii;
+    // interferer: behind the channel, in front of the resampler
+    struct Interferer { int kind; bool white; double offset_hz, width_hz, is_db; unsigned long long gate_period, gate_on; long long gate_offset; };
+    std::vector<Interferer> interferers;
+    unsigned long long interferer_seed = 1;
     // resampler: behind the channel
     bool resample = false;
     double clock_ppm = 0.0, frac_delay = 0.0, output_rate = 2.048e6;
@@ -214,6 +227,54 @@ static dabgpu_channel_stream channel_params(const Args& args, int nb_carriers) {
     }
     P.noise_sigma = args.have_snr ? DAB_Channel_Model::NoiseSigma((double)nb_carriers * h2, args.snr_db) : 0.0f;
     return P;
+}
+
+// the interferer of the options for a signal of the channel's parameters (nullptr: none): every band source brings its own shape
+static std::unique_ptr<DAB_Interferer> make_interferer(const Args& args, const dabgpu_channel_stream& cp, int nb_carriers) {
+    if (args.interferers.empty()) return nullptr;
+    double h2 = 0.0;
+    for (int k = 0; k < cp.n_taps; k++) h2 += (double)cp.tap_re[k] * cp.tap_re[k] + (double)cp.tap_im[k] * cp.tap_im[k];
+    dabgpu_interferer_stream P = {};
+    std::vector<dabgpu_interferer_shape> shapes;
+    P.seed = args.interferer_seed;
+    P.n_sources = (int)args.interferers.size();
+    for (size_t k = 0; k < args.interferers.size(); k++) {
+        const Args::Interferer& I = args.interferers[k];
+        dabgpu_interferer_source& S = P.source[k];
+        S.kind = I.kind;
+        S.shape = -1;
+        if (I.kind == DABGPU_INTERFERER_BAND && !I.white) { S.shape = (int)shapes.size(); shapes.push_back(DAB_Interferer::Shape(I.width_hz)); }
+        S.amp = DAB_Interferer::Amplitude((double)nb_carriers * h2, I.is_db);
+        S.freq_q64 = DAB_Interferer::FrequencyWord(I.offset_hz);
+        S.gate_period = I.gate_period; S.gate_on = I.gate_on; S.gate_offset = I.gate_offset;
+    }
+    return std::make_unique<DAB_Interferer>(P, shapes);
+}
+
+// tone:OFFSET_HZ:IS_DB | band:OFFSET_HZ:WIDTH_HZ:IS_DB | white:IS_DB
+static Args::Interferer parse_interferer(const std::string& v) {
+    std::vector<std::string> f;
+    for (size_t at = 0;;) {
+        const size_t c = v.find(':', at);
+        f.push_back(v.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    if (f[0] == "tone" && f.size() == 3) return {DABGPU_INTERFERER_TONE, false, std::stod(f[1]), 0.0, std::stod(f[2]), 0, 0, 0};
+    if (f[0] == "band" && f.size() == 4) return {DABGPU_INTERFERER_BAND, false, std::stod(f[1]), std::stod(f[2]), std::stod(f[3]), 0, 0, 0};
+    if (f[0] == "white" && f.size() == 2) return {DABGPU_INTERFERER_BAND, true, 0.0, 0.0, std::stod(f[1]), 0, 0, 0};
+    throw std::runtime_error("--interferer wants tone:OFFSET_HZ:IS_DB, band:OFFSET_HZ:WIDTH_HZ:IS_DB or white:IS_DB, got " + v);
+}
+
+// PERIOD:ON[:OFFSET] onto the interferer before it
+static void parse_interferer_gate(const std::string& v, Args& args) {
+    if (args.interferers.empty()) throw std::runtime_error("--interferer-gate applies to the --interferer before it");
+    const size_t a = v.find(':'), b = v.find(':', a == std::string::npos ? a : a + 1);
+    if (a == std::string::npos) throw std::runtime_error("--interferer-gate wants PERIOD:ON[:OFFSET], got " + v);
+    Args::Interferer& I = args.interferers.back();
+    I.gate_period = std::stoull(v.substr(0, a));
+    I.gate_on = std::stoull(v.substr(a + 1, b == std::string::npos ? b : b - a - 1));
+    I.gate_offset = b == std::string::npos ? 0 : std::stoll(v.substr(b + 1));
 }
 
 // the fading spec of the options; false: no tap fades (no fading bank is made)
@@ -331,10 +392,11 @@ static int run_coded(const Args& args, FILE* fp_out) {
         if (fading_spec(args, cp, spec)) channel->SetFading(spec);
         window.assign(2 * S, std::complex<float>(0.0f, 0.0f));
     }
+    auto interferer = make_interferer(args, cp, 1536);
     auto resampler = make_resampler(args);
     const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
     auto wide = make_wideband(args, u8_scale, 1536);
-    std::vector<std::complex<float>> impaired((resampler || wide) ? S : 0), resampled;
+    std::vector<std::complex<float>> impaired((resampler || wide || interferer) ? S : 0), resampled;
     int rc = 0;
     for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
         fibs.read(fib.data(), 360);
@@ -346,8 +408,10 @@ static int run_coded(const Args& args, FILE* fp_out) {
                 dabgpu_channel_stream now = cp;
                 now.start = cp.start + (k - 1) * (long long)S;             // window sample 0 = stream sample (k - 1) S
                 channel->SetParams(now);
-                if (resampler || wide) channel->Apply(impaired, window, false);
+                if (resampler || wide || interferer) channel->Apply(impaired, window, false);
                 else channel->ApplyU8(quantised, window, false, u8_scale);
+                if (interferer && (resampler || wide)) interferer->Apply(impaired, impaired);
+                else if (interferer) interferer->ApplyU8(quantised, impaired, u8_scale);
             }
         } else
         st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
@@ -372,7 +436,8 @@ static void usage(const char* argv0) {
                     "          [--subchannel START:LENGTH:eepL-A|eepL-B|uepROW]... [--fib-file FILE] [--payload-file FILE] [--seed N]\n"
                     "          [--snr-db DB] [--cfo-hz HZ] [--timing-offset N] [--tap DELAY:RE:IM]... [--noise-seed N] [--tii P:C[:AMP]]...\n"
                     "          [--doppler-hz F] [--fading-seed S] [--profile tu6|ra6|sfn2] [--tap-kind K:static|rayleigh|rice:KDB]...\n"
-                    "          [--clock-ppm X] [--frac-delay D] [--output-rate HZ]\n"
+                    "          [--interferer tone:OFFSET_HZ:IS_DB|band:OFFSET_HZ:WIDTH_HZ:IS_DB|white:IS_DB]... [--interferer-gate PERIOD:ON[:OFFSET]]\n"
+                    "          [--interferer-seed N] [--clock-ppm X] [--frac-delay D] [--output-rate HZ]\n"
                     "          [--wideband D] [--centre-offset-hz F] [--neighbour OFFSET_HZ:LEVEL_DB]...\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
@@ -382,6 +447,8 @@ static void usage(const char* argv0) {
                     "(the mean power of the modulator's symbols after the taps; the NULL period is not counted);\n"
                     "with --doppler-hz F (0..1000) the taps fade (Rayleigh; --tap-kind sets single taps static or Rice with a factor in dB,\n"
                     "--profile takes taps and kinds from a preset as recalled from COST 207), unit mean power each, seeded by --fading-seed;\n"
+                    "with --interferer (up to 4) a carrier, a band of Gaussian noise or white noise is added behind the channel, IS_DB relative to the\n"
+                    "signal power P of --snr-db while its --interferer-gate (on for ON of every PERIOD samples) is on, seeded by --interferer-seed;\n"
                     "with --clock-ppm X / --frac-delay D / --output-rate HZ the signal is resampled behind the channel (the noise too, as at a\n"
                     "receiver's ADC): HZ samples per second (default 2048000), every sample period X ppm longer, D of a sample late;\n"
                     "with --wideband D (1..8) the block goes onto a capture at D times the rate, --centre-offset-hz F above its centre, with up to 7\n"
@@ -415,6 +482,9 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--profile") { args.profile = value(); args.channel = true; }
         else if (a == "--tap-kind") { args.tap_kinds.push_back(parse_tap_kind(value())); args.channel = true; }
         else if (a == "--tii") args.tii.push_back(parse_tii(value()));
+        else if (a == "--interferer") { args.interferers.push_back(parse_interferer(value())); args.channel = true; }
+        else if (a == "--interferer-gate") parse_interferer_gate(value(), args);
+        else if (a == "--interferer-seed") args.interferer_seed = std::stoull(value());
         else if (a == "--clock-ppm") { args.clock_ppm = std::stod(value()); args.resample = true; }
         else if (a == "--frac-delay") { args.frac_delay = std::stod(value()); args.resample = true; }
         else if (a == "--output-rate") { args.output_rate = std::stod(value()); args.resample = true; }
@@ -454,6 +524,7 @@ static bool parse_args(int argc, char** argv, Args& args) {
         if (!(std::fabs(args.clock_ppm) <= 1000.0)) throw std::runtime_error("--clock-ppm: -1000 .. 1000");
     }
     if (!args.profile.empty() && !args.taps.empty()) throw std::runtime_error("--profile is not available with --tap");
+    if (args.interferers.size() > DABGPU_INTERFERER_MAX) throw std::runtime_error("--interferer: at most 4 sources");
     if (args.tii.size() > DABGPU_TII_MAX_TX) throw std::runtime_error("--tii: at most 4 transmitters");
     if (!args.tii.empty() && args.coded) throw std::runtime_error("--tii is not available with channel-coded frames");
     if (args.transmission_mode < 1 || args.transmission_mode > 4) throw std::runtime_error("--transmission-mode must be one of 1,2,3,4");
@@ -530,20 +601,27 @@ int main(int argc, char** argv) {
             dabgpu_channel_fading_spec spec;
             if (fading_spec(args, cp, spec)) channel.SetFading(spec);
             const float u8_scale = (1.0f / (float)params.nb_data_carriers * 4.0f) * 127.5f;
+            auto interferer = make_interferer(args, cp, (int)params.nb_data_carriers);
             auto resampler = make_resampler(args);
             auto wide = make_wideband(args, u8_scale, (int)params.nb_data_carriers);
-            std::vector<std::complex<float>> impaired((resampler || wide) ? frame_size : 0), resampled;
+            std::vector<std::complex<float>> impaired((resampler || wide || interferer) ? frame_size : 0), resampled;
             for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
                 if (wide) {
                     channel.Apply(impaired, frame, true);
+                    if (interferer) interferer->Apply(impaired, impaired);
                     if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out)) break;
                     continue;
                 }
                 if (resampler) {
                     channel.Apply(impaired, frame, true);
+                    if (interferer) interferer->Apply(impaired, impaired);
                     if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
                     continue;
                 }
+                if (interferer) {
+                    channel.Apply(impaired, frame, true);
+                    interferer->ApplyU8(quantised, impaired, u8_scale);
+                } else
                 channel.ApplyU8(quantised, frame, true, u8_scale);
                 const size_t nb_write = fwrite(quantised.data(), 2, frame_size, fp_out);
                 if (nb_write != frame_size) {

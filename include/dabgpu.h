@@ -1315,6 +1315,113 @@ int dabgpu_channel_bank_create_fading(dabgpu_ctx *ctx, size_t n_streams, const d
 int dabgpu_channel_bank_set_fading(dabgpu_channel_bank *bank, const dabgpu_channel_fading_stream *h_tables, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Interferer: narrowband spurs, a band-limited jammer and impulsive bursts added to n_streams independent streams of complex float
+ * samples -- what the noise profile and the banded combiner defend against.  The reference has no interferer; the definition is this
+ * library's own, written once in dab-radio_amd/csrc/interferer_core.h for the kernel (interferer.hip) and for the host model the
+ * tests build from the same header (tests/cpp/interferer_host_model.cpp), pinned to an independent numpy model (tests/interferer_model.py,
+ * tests/test_interferer_model.py) and on the device bit for bit to the host model (tests/test_gpu_interferer.py).  Philox, Box-Muller, the
+ * 64-bit oscillator and sine / cosine are the channel model's (channel_core.h), unchanged.  Bounds and measurements: DESIGN.md 4.28.
+ *
+ * For stream s, absolute sample m (the bank's 64-bit position + the sample's index i in the call), n_sources <= DABGPU_INTERFERER_MAX
+ * sources k in list order:
+ *   TONE   v = amp * e^(j 2 pi phase), phase = phase0_q64 + m * freq_q64 in unsigned 64-bit arithmetic, its top 24 bits the angle
+ *   BAND   band-limited Gaussian noise from shape `shape` of the bank (interp L = 2^l, 16 taps per phase): q = m >> l, r = m & (L - 1),
+ *            b = sum over t = 0 .. 15 of taps[r + L t] * g[q - t]
+ *          in that order, the first term a plain product, the others fmaf, re and im separately; g[n] = the Box-Muller pair of
+ *          Philox4x32-10 with key = seed and counter = (low word of n >> 1, high word of n >> 1, s, 16 + k), words 2 (n & 1) and
+ *          2 (n & 1) + 1; n is an unsigned 64-bit number, so q - t wraps below 0.  (Counter word 3 is 0 for the channel's noise and 1 for
+ *          the fading tables: one seed serves all three independently.)  Then v = (amp * b) * e^(j 2 pi phase), the rotation to the band's
+ *          centre (skipped when freq_q64 = phase0_q64 = 0).
+ *          shape = -1: white over the whole sampled band, no filter: b = g[m] * 0.70710678f (the division by sqrt 2 written as a
+ *          product with the nearest float, because `/` is not the same operation under every compiler: channel_core.h)
+ *   gate   gate_period = 0: always on.  Otherwise on iff ((m - gate_offset) mod gate_period) < gate_on, in exact integer arithmetic with
+ *          a non-negative remainder; the edges are abrupt (a burst interferer).  amp is the amplitude while the gate is on.
+ *   y[i]   = x[i] + v_0 + v_1 + ... added in list order (plain float additions per component); d_in = NULL: x = 0.  A source of kind OFF
+ *          or with amp = 0 runs no generator and adds nothing; a stream with no live source returns its input bit for bit.
+ * The value of a sample depends on (parameters, shapes, seed, s, k, m) alone: a call of a + b samples equals a call of a and then one of b
+ * on the following input, at any split, and replays of a captured call continue the stream.  E|v|^2 = amp^2 while the gate is on.
+ *
+ * dabgpu_interferer_design (host only, no device): a flat band of width_cycles (a fraction of the sample rate, two-sided) as a
+ * Kaiser-windowed sinc of 16 L taps computed in double and rounded to float.  L is the largest power of two <= 64 for which the passband
+ * and the transition stay inside the low rate's Nyquist band.  The cutoff (the -6 dB point of the window method) is the nominal edge
+ * width_cycles / 2 and the transition, DABGPU_INTERFERER_TRANSITION / L cycles wide, lies around it; the rule is
+ * width_cycles / 2 + transition / (2 L) <= 1 / (2 L), so the images of the interpolation fall into the stopband and the output power is
+ * the same at every one of the L phases.  The table is scaled so that the mean over the phases of sum_t taps[r + L t]^2 is 1/2 (g has
+ * variance 1 per component, hence E|b|^2 = 1).  The record carries its own figures, from the table's spectrum at the 8193 frequencies
+ * 0 .. 1/2 of a 2^14-point transform: width_3db_cycles (two-sided), inband_share (power inside +-width / 2 over the whole),
+ * stopband_level (largest |H| from width / 2 + transition / (2 L) on, relative to |H(0)|), phase_ripple (max / min over the phases of
+ * sum_t taps[r + L t]^2).  Refused with DABGPU_ERR_INVALID_ARG: NULL out, width_cycles not finite, above 1, or below
+ * DABGPU_INTERFERER_MIN_WIDTH (narrower than the transition of L = 64 no flat part is left: that is a tone).
+ *
+ * dabgpu_interferer_plan (host only): checks a parameter list against n_shapes shapes and returns the launch geometry.  Refused, naming
+ * stream, source and field: n_streams outside 1..1048576, n_shapes outside 0..4, NULL params (or shapes with n_shapes > 0), a shape whose
+ * interp is no power of two in 1..64 or that has a tap that is not finite, n_sources outside 0..4, a kind that is none of OFF, TONE,
+ * BAND, of the sources below n_sources that are not OFF: amp not finite or negative, gate_on > gate_period, |gate_offset| >= 2^62, and of
+ * BAND sources a shape index outside -1 .. n_shapes - 1.
+ *   block_samples  output samples one workgroup produces (DABGPU_INTERFERER_BLOCK)
+ *   band_slots     the largest count of shaped BAND sources (shape >= 0, amp != 0) on one stream
+ *   slot_bytes     LDS of one such source: the largest, over the shapes, of 16 L floats + (1024 / L + 18) complex floats
+ *   lds_bytes      band_slots x slot_bytes; 0 for a bank of tones and white sources (that kernel variant allocates none) */
+#define DABGPU_INTERFERER_MAX 4
+#define DABGPU_INTERFERER_MAX_SHAPES 4
+#define DABGPU_INTERFERER_TAPS 16
+#define DABGPU_INTERFERER_MAX_INTERP 64
+#define DABGPU_INTERFERER_BLOCK 1024
+#define DABGPU_INTERFERER_TRANSITION 0.25                   /* transition width of a shape, in cycles of its low rate */
+#define DABGPU_INTERFERER_MIN_WIDTH 0.00390625              /* 2^-8 = the transition of L = 64; L = 64 serves widths up to 0.75 / 64 */
+#define DABGPU_INTERFERER_MAX_POSITION ((int64_t)1 << 62)   /* |gate_offset| and the stream position stay below */
+enum { DABGPU_INTERFERER_OFF = 0, DABGPU_INTERFERER_TONE = 1, DABGPU_INTERFERER_BAND = 2 };
+typedef struct {
+    int32_t kind;                   /* DABGPU_INTERFERER_OFF / _TONE / _BAND */
+    int32_t shape;                  /* BAND: index of a shape of the bank, or -1 = white */
+    float amp;
+    int32_t reserved;
+    uint64_t freq_q64, phase0_q64;  /* the tone, or the band's centre (dabgpu_channel_freq_q64) */
+    uint64_t gate_period, gate_on;  /* samples; gate_period = 0: always on */
+    int64_t gate_offset;
+} dabgpu_interferer_source;
+typedef struct {
+    uint64_t seed;
+    int32_t n_sources, reserved;
+    dabgpu_interferer_source source[DABGPU_INTERFERER_MAX];
+} dabgpu_interferer_stream;
+typedef struct {
+    int32_t interp, reserved;       /* L */
+    double width_cycles, cutoff_cycles, beta;
+    double width_3db_cycles, inband_share, stopband_level, phase_ripple;
+    float taps[DABGPU_INTERFERER_TAPS * DABGPU_INTERFERER_MAX_INTERP];      /* the first 16 L are used: tap j = r + L t */
+} dabgpu_interferer_shape;
+typedef struct { uint32_t block_samples, band_slots, slot_bytes, lds_bytes; } dabgpu_interferer_geometry;
+int dabgpu_interferer_design(double width_cycles, dabgpu_interferer_shape *out);
+int dabgpu_interferer_plan(const dabgpu_interferer_stream *params, size_t n_streams, const dabgpu_interferer_shape *shapes, int n_shapes,
+                           dabgpu_interferer_geometry *out);
+
+/* Interferer bank: the parameters of n_streams streams, up to 4 shapes shared by all of them and the common position on the device,
+ * built like the channel bank above.
+ *   d_in    NULL (the bank generates the interferer alone), or stream s reads n_out complex float from d_in + s * in_stride_samples;
+ *           in_stride_samples = 0: every stream reads the same row, otherwise >= n_out and even.  16-byte aligned.
+ *   d_out   as dabgpu_channel_bank_apply: complex float or the modulator's u8 pairs with u8_scale, rows out_stride_bytes apart (a multiple
+ *           of 16 that holds n_out samples; 0 = the default), 16-byte aligned.  d_out == d_in (complex float, rows equally far apart) is
+ *           allowed: the operation is sample-wise in x.
+ * A call is the interferer kernel and the one-thread kernel that adds n_out to the position, on `stream`; no host state changes, so a
+ * call may be captured and its replays continue the stream.  _seek sets the position (< 2^62), _set_params replaces all parameters within
+ * the geometry fixed at creation: more shaped BAND sources on one stream than band_slots of the creation are refused, and so is any in a
+ * bank created without (the shapes stay those of the creation).  Arguments are checked in plain C++ (dabgpu_host_logic.cpp) before any
+ * device call, and a refusal leaves the output untouched (tests/test_interferer_plan.py, tests/test_gpu_interferer.py). */
+typedef struct dabgpu_interferer_bank dabgpu_interferer_bank;
+int dabgpu_interferer_bank_create(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_interferer_stream *h_params,
+                                  const dabgpu_interferer_shape *h_shapes, int n_shapes, dabgpu_interferer_bank **out);
+void dabgpu_interferer_bank_destroy(dabgpu_interferer_bank *bank);
+int dabgpu_interferer_bank_set_params(dabgpu_interferer_bank *bank, const dabgpu_interferer_stream *h_params, void *stream);
+int dabgpu_interferer_bank_seek(dabgpu_interferer_bank *bank, uint64_t position, void *stream);
+int dabgpu_interferer_bank_apply(dabgpu_interferer_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_out, void *d_out,
+                                 int out_format, size_t out_stride_bytes, float u8_scale, void *stream);
+/* the same from and to host memory on the context's stream (h_in may be NULL; rows of any length >= n_out, no alignment rule), as
+ * dabgpu_channel_bank_apply_host_sync */
+int dabgpu_interferer_bank_apply_host_sync(dabgpu_interferer_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_out,
+                                           void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Resampler: arbitrary-ratio, fractional-delay resampling of n_streams independent streams of complex float samples -- a receiver's
  * sampling-clock error and fractional delay behind the channel model, and captures at 2.4, 2.56, 3.072 or 4.096 MS/s brought to the 2.048 MHz
  * grid in front of the demodulator.  The reference has nothing comparable; the definition is this library's own, written once in

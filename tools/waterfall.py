@@ -33,10 +33,12 @@ then hold the whole NULL in front of each frame), `true` is 1 / (2 noise_sigma^2
 that of a branch without extra noise.  The output goes to profiles/tx/waterfall_mrc.md, which such a run writes anew unless --append is given: the
 committed file is a unit run followed by an estimated and a true run with --append, and any of them can be repeated alone into an --out of its own.
 Without these two options the output is what it was.
+(--interferer-source device: the interferer comes from dabgpu.Interferer, the library's own bank, in place of the torch one below; the default,
+torch, is what the committed outputs were made with.)
 With --interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB a narrowband interferer is added to every channel stream behind the channel: Gaussian noise confined to
 WIDTH_KHZ around OFFSET_KHZ from the block's centre (white noise made with torch on the device, every bin of its transform outside the band cleared;
-a seed per stream), its total power IS_DB relative to the signal power the SNR refers to.  The option is the tool's own: the channel model has no
-interferer.  It wants the branch path (--branches K, or --weights banded, which also takes K = 1).  With --weights banded [--alpha A] every branch's
+a seed per stream), its total power IS_DB relative to the signal power the SNR refers to.  The torch source is the tool's own, kept so that the
+committed outputs can be made again; the library's is dabgpu.Interferer.  It wants the branch path (--branches K, or --weights banded, which also takes K = 1).  With --weights banded [--alpha A] every branch's
 slice and sync records go through dabgpu_noise_profile_frames (the state carried from frame to frame in place, smoothing A, default 0.25) and the
 band weights into dabgpu_diversity_combine_frames_banded: with one branch interference-aware soft bits, with several maximal-ratio combining per
 band.  Every cell still reads `single -> combined`, branch 0's own weighted soft bits against the banded combination.  The output goes to
@@ -79,6 +81,7 @@ def main():
     ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true", "banded"))
     ap.add_argument("--alpha", type=float, default=0.25)
     ap.add_argument("--interferer", default=None)
+    ap.add_argument("--interferer-source", default="torch", choices=("torch", "device"))
     ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
     K = a.branches
@@ -215,7 +218,7 @@ def main():
                     f"`single -> combined`: branch 0 decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of "
                     f"every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
                     f"`python tools/waterfall.py --branches {K} --branch-noise-db {','.join(f'{d:g}' for d in branch_db)} --weights {a.weights} --streams {E} --frames {F} "
-                    f"--snr {a.snr}{fading_args}{' --alpha %g' % a.alpha if banded else ''}{' --interferer ' + a.interferer if jam else ''}"
+                    f"--snr {a.snr}{fading_args}{' --alpha %g' % a.alpha if banded else ''}{' --interferer ' + a.interferer if jam else ''}{' --interferer-source device' if jam and a.interferer_source == 'device' else ''}"
                     f"{' --append' if a.append else ''}`; the verdict line is the combination's."
                     + (f"  Interferer: Gaussian noise {jam[1]:g} kHz wide {jam[0]:+g} kHz from the centre, {jam[2]:+g} dB relative to the signal, a seed per stream; the "
                        "frame scale rests on the power of the phase reference symbol, interferer included." if jam else ""), ""]
@@ -257,7 +260,17 @@ def main():
             ch.seek(0)
             ch.apply(d_iq, F * S, n_rx, d_rx, in_stride_samples=0, out_stride_bytes=n_rows * n_rx * 8)
             d_use = d_rx
-            if jam is not None:
+            if jam is not None and a.interferer_source == "device":
+                # the library's own source (include/dabgpu.h "Interferer"): a BAND source of that width and power, a seed per stream, in place
+                shape = dabgpu.interferer_design(jam[1] / 2048.0)
+                amp = math.sqrt(1536.0 * h2 * 10.0 ** (jam[2] / 10.0))
+                itf = dabgpu.Interferer(ctx, [dabgpu.interferer_stream([dabgpu.interferer_source(dabgpu.INTERFERER_BAND, amp=amp, shape=0,
+                                                                                                  cycles_per_sample=jam[0] / 2048.0)], seed=7000 + e)
+                                              for e in range(EC)], [shape])
+                itf.apply(d_rx, n_rx, d_rx, in_stride_samples=n_rows * n_rx, out_stride_bytes=n_rows * n_rx * 8)
+                torch.cuda.synchronize()
+                itf.close()
+            elif jam is not None:
                 # Gaussian noise confined to the band, total power IS_DB over the signal's 1536 h2, a seed per stream
                 gen = torch.Generator(device="cuda")
                 f_khz = torch.fft.fftfreq(n_rx, device="cuda") * 2048.0
