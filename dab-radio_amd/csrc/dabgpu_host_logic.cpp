@@ -1779,6 +1779,96 @@ extern "C" int dabgpu_interferer_plan(const dabgpu_interferer_stream* params, si
     return dabgpu_host_interferer_plan("interferer_plan", params, n_streams, shapes, n_shapes, out);
 }
 
+// ---- impulse blanker (include/dabgpu.h, "Impulse blanker"; the arithmetic is blanker_core.h's, shared with the kernel) ----
+extern "C" dabgpu_blanker_stream dabgpu_blanker_defaults(void) { return dabgpu_blanker_stream{0, 3.0f, 8, 16, 1, 1, 0}; }
+
+extern "C" size_t dabgpu_blanker_mask_words(size_t n_out) { return n_out / DABGPU_BLANKER_BLOCK + 2; }
+
+int dabgpu_host_blanker_plan(const char* who, const dabgpu_blanker_stream* params, size_t n_streams, dabgpu_blanker_geometry* out) {
+    if (out) *out = dabgpu_blanker_geometry{0, DABGPU_BLANKER_BLOCK, 0, 0};
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("%s: %zu streams (1..1048576 are accepted)", who, n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (!params) { dabgpu_set_error("%s: null parameters", who); return DABGPU_ERR_INVALID_ARG; }
+    uint32_t reach = 0;
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_blanker_stream& P = params[s];
+        if (!std::isfinite(P.threshold)) { dabgpu_set_error("%s: stream %zu: threshold is not finite", who, s); return DABGPU_ERR_INVALID_ARG; }
+        if (!(P.threshold > 1.0f && P.threshold <= DABGPU_BLANKER_MAX_THRESHOLD)) {
+            dabgpu_set_error("%s: stream %zu: threshold %g (above 1, up to 1024)", who, s, (double)P.threshold); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (P.window < 1 || P.window > DABGPU_BLANKER_MAX_WINDOW) {
+            dabgpu_set_error("%s: stream %zu: window %d (1..%d are accepted)", who, s, P.window, DABGPU_BLANKER_MAX_WINDOW); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (P.gap < 0 || P.gap > DABGPU_BLANKER_MAX_GAP) {
+            dabgpu_set_error("%s: stream %zu: gap %d (0..%d are accepted)", who, s, P.gap, DABGPU_BLANKER_MAX_GAP); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (P.guard < 0 || P.guard > DABGPU_BLANKER_MAX_GUARD) {
+            dabgpu_set_error("%s: stream %zu: guard %d (0..%d are accepted)", who, s, P.guard, DABGPU_BLANKER_MAX_GUARD); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (P.start > DABGPU_BLANKER_MAX_POSITION || P.start < -DABGPU_BLANKER_MAX_POSITION) {
+            dabgpu_set_error("%s: stream %zu: start outside +-2^62", who, s); return DABGPU_ERR_INVALID_ARG;
+        }
+        reach = std::max(reach, (uint32_t)(P.gap + P.window + P.guard));
+    }
+    if (out) {
+        out->reach_blocks = reach;
+        out->lds_bytes = (DABGPU_BLANKER_BLOCK / DABGPU_BLANKER_POWER_BLOCK + 2u * reach) * 4u
+                         + (DABGPU_BLANKER_BLOCK / DABGPU_BLANKER_POWER_BLOCK + 2u * DABGPU_BLANKER_MAX_GUARD) * 4u;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_blanker_fits(const dabgpu_blanker_geometry& created, const dabgpu_blanker_geometry& wanted) {
+    if (wanted.reach_blocks > created.reach_blocks) {
+        dabgpu_set_error("blanker_bank_set_params: gap + window + guard reaches %u blocks, the bank was created for %u (create the bank with its "
+                         "widest parameters)", wanted.reach_blocks, created.reach_blocks);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_blanker_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_in, size_t n_out,
+                                    const void* out, size_t* out_stride_bytes, const void* mask, size_t* mask_stride_words, bool device_pointers) {
+    const int st = dabgpu_host_channel_check_apply(who, n_streams, in, in_stride_samples, n_in, n_out, out, DABGPU_IQ_RAW_F32L, out_stride_bytes, 1.0f,
+                                                   device_pointers);
+    if (st) return st;
+    if (in == out) { dabgpu_set_error("%s: in place is not defined (a tile reads its neighbours' input): d_out must not be d_in", who); return DABGPU_ERR_INVALID_ARG; }
+    const size_t words = dabgpu_blanker_mask_words(n_out);
+    if (*mask_stride_words == 0) *mask_stride_words = words;
+    if (*mask_stride_words < words) {
+        dabgpu_set_error("%s: mask_stride_words must be 0 or at least n_out / 1024 + 2 = %zu", who, words); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (mask && ((uintptr_t)mask & 3)) { dabgpu_set_error("%s: the mask must be 4-byte aligned", who); return DABGPU_ERR_INVALID_ARG; }
+    if (words * n_streams > 0x7FFFFFFFull) { dabgpu_set_error("%s: n_streams x n_out too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_blanker_plan(const dabgpu_blanker_stream* params, size_t n_streams, dabgpu_blanker_geometry* out) {
+    return dabgpu_host_blanker_plan("blanker_plan", params, n_streams, out);
+}
+
+extern "C" int dabgpu_blanker_input_needed(const dabgpu_blanker_stream* params, uint64_t position, size_t n_out, int64_t* first, uint64_t* count) {
+    if (first) *first = 0;
+    if (count) *count = 0;
+    if (!first || !count) { dabgpu_set_error("blanker_input_needed: null result"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_blanker_plan("blanker_input_needed", params, 1, nullptr);
+    if (st) return st;
+    if (position > (uint64_t)DABGPU_BLANKER_MAX_POSITION) { dabgpu_set_error("blanker_input_needed: position above 2^62"); return DABGPU_ERR_INVALID_ARG; }
+    if (n_out > ((size_t)1 << 31)) { dabgpu_set_error("blanker_input_needed: n_out = %zu (up to 2^31 per call)", n_out); return DABGPU_ERR_INVALID_ARG; }
+    // position - start reaches 2^63 only where both stand at their caps: the index saturates there (no input is that long)
+    auto index = [&](int64_t m) {
+        const __int128 i = (__int128)m - (__int128)params->start;
+        return i > (__int128)INT64_MAX ? INT64_MAX : (int64_t)i;
+    };
+    *first = index((int64_t)position);
+    if (n_out == 0) return DABGPU_OK;
+    if (!params->enabled) { *count = n_out; return DABGPU_OK; }
+    const int64_t reach = params->gap + params->window + params->guard;
+    const int64_t b0 = (int64_t)(position >> 5) - reach, b1 = (int64_t)((position + n_out - 1) >> 5) + reach;
+    *first = index(b0 * DABGPU_BLANKER_POWER_BLOCK);
+    *count = (uint64_t)(b1 - b0 + 1) * DABGPU_BLANKER_POWER_BLOCK;
+    return DABGPU_OK;
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

@@ -301,6 +301,16 @@ int dabgpu_host_interferer_fits(const dabgpu_interferer_geometry& created, const
 int dabgpu_host_interferer_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_out, const void* out,
                                        int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers = true);
 
+// ---- impulse blanker planner (blanker.hip launches from it; include/dabgpu.h, dabgpu_blanker_plan) ----
+// DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream, field); `who` names the entry point
+int dabgpu_host_blanker_plan(const char* who, const dabgpu_blanker_stream* params, size_t n_streams, dabgpu_blanker_geometry* out);
+// dabgpu_blanker_bank_set_params: new parameters must fit the reach of the bank's creation (a captured call has its LDS size baked in)
+int dabgpu_host_blanker_fits(const dabgpu_blanker_geometry& created, const dabgpu_blanker_geometry& wanted);
+// the arguments of a dabgpu_blanker_bank_apply call (no device address is dereferenced); *out_stride_bytes and *mask_stride_words: 0 is
+// replaced by the default
+int dabgpu_host_blanker_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_in, size_t n_out,
+                                    const void* out, size_t* out_stride_bytes, const void* mask, size_t* mask_stride_words, bool device_pointers = true);
+
 // ---- resampler planner (resample.hip launches from it; include/dabgpu.h, dabgpu_resample_plan) ----
 // DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream index, field); `who` names the entry point.
 // max_step_q62: the largest step the bank's design serves (dabgpu_host_resample_max_step_q62 of its max_step)

@@ -102,6 +102,9 @@ ABI_SYMBOLS = [
     "dabgpu_diversity_combine_banded_host_sync", "dabgpu_diversity_band_mean_host",
     "dabgpu_interferer_design", "dabgpu_interferer_plan", "dabgpu_interferer_bank_create", "dabgpu_interferer_bank_destroy",
     "dabgpu_interferer_bank_set_params", "dabgpu_interferer_bank_seek", "dabgpu_interferer_bank_apply", "dabgpu_interferer_bank_apply_host_sync",
+    "dabgpu_blanker_defaults", "dabgpu_blanker_mask_words", "dabgpu_blanker_plan", "dabgpu_blanker_input_needed", "dabgpu_blanker_bank_create",
+    "dabgpu_blanker_bank_destroy", "dabgpu_blanker_bank_set_params", "dabgpu_blanker_bank_seek", "dabgpu_blanker_bank_apply",
+    "dabgpu_blanker_bank_apply_host_sync",
 ]
 NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
@@ -265,6 +268,21 @@ class InterfererShape(C.Structure):
 class InterfererGeometry(C.Structure):
     """dabgpu_interferer_geometry"""
     _fields_ = [("block_samples", C.c_uint32), ("band_slots", C.c_uint32), ("slot_bytes", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
+# impulse blanker (include/dabgpu.h)
+BLANKER_POWER_BLOCK, BLANKER_BLOCK, BLANKER_MAX_WINDOW, BLANKER_MAX_GAP, BLANKER_MAX_GUARD, BLANKER_MAX_POSITION = 32, 1024, 32, 32, 4, 1 << 62
+
+
+class BlankerStream(C.Structure):
+    """dabgpu_blanker_stream"""
+    _fields_ = [("start", C.c_int64), ("threshold", C.c_float), ("gap", C.c_int32), ("window", C.c_int32), ("guard", C.c_int32),
+                ("enabled", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BlankerGeometry(C.Structure):
+    """dabgpu_blanker_geometry"""
+    _fields_ = [("reach_blocks", C.c_uint32), ("block_samples", C.c_uint32), ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ResampleStream(C.Structure):
@@ -643,6 +661,19 @@ def lib():
         L.dabgpu_interferer_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.dabgpu_interferer_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p]
         L.dabgpu_interferer_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float]
+        L.dabgpu_blanker_defaults.argtypes, L.dabgpu_blanker_defaults.restype = [], BlankerStream
+        L.dabgpu_blanker_mask_words.argtypes, L.dabgpu_blanker_mask_words.restype = [C.c_size_t], C.c_size_t
+        L.dabgpu_blanker_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dabgpu_blanker_input_needed.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.dabgpu_blanker_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.dabgpu_blanker_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_blanker_bank_destroy.restype = None
+        L.dabgpu_blanker_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_blanker_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_blanker_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]
+        L.dabgpu_blanker_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                          C.c_size_t]
         _lib = L
     return _lib
 
@@ -1490,6 +1521,82 @@ class Interferer(_Handle):
         return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_interferer_bank_apply_host_sync(
             self._h, _ptr(x), in_stride_samples, n_out, _ptr(out), fmt, stride, float(u8_scale)),
             "dabgpu_interferer_bank_apply_host_sync"), h_in, self.n, n_out, fmt)
+
+
+def blanker_stream(threshold=None, gap=None, window=None, guard=None, start=0, enabled=True):
+    """a BlankerStream: dabgpu_blanker_defaults (threshold 3, gap 8, window 16, guard 1) with the given fields replaced; gap, window and guard
+    in blocks of 32 samples"""
+    P = lib().dabgpu_blanker_defaults()
+    if threshold is not None:
+        P.threshold = float(threshold)
+    if gap is not None:
+        P.gap = int(gap)
+    if window is not None:
+        P.window = int(window)
+    if guard is not None:
+        P.guard = int(guard)
+    P.start, P.enabled = int(start), int(bool(enabled))
+    return P
+
+
+def blanker_mask_words(n_out):
+    """dabgpu_blanker_mask_words: the mask words per stream that a call of n_out samples writes"""
+    return int(lib().dabgpu_blanker_mask_words(int(n_out)))
+
+
+def blanker_plan(streams):
+    """dabgpu_blanker_plan (host only): {"reach_blocks", "block_samples", "lds_bytes"} of a list of BlankerStream; raises DabGpuError"""
+    n = len(streams)
+    arr = (BlankerStream * n)(*streams) if n else None
+    g = BlankerGeometry()
+    check(lib().dabgpu_blanker_plan(arr, n, C.byref(g)), "dabgpu_blanker_plan")
+    return {"reach_blocks": g.reach_blocks, "block_samples": g.block_samples, "lds_bytes": g.lds_bytes}
+
+
+def blanker_input_needed(stream_params, position, n_out):
+    """dabgpu_blanker_input_needed (host only): (first, count), the input indices a call of n_out samples at `position` reads"""
+    first, count = C.c_int64(), C.c_uint64()
+    check(lib().dabgpu_blanker_input_needed(C.byref(stream_params) if stream_params is not None else None, int(position), int(n_out), C.byref(first),
+                                            C.byref(count)), "dabgpu_blanker_input_needed")
+    return first.value, count.value
+
+
+class Blanker(_Handle):
+    """dabgpu_blanker_bank: zeroes bursts in n streams ahead of the demodulator; the stream position lives on the device"""
+    _destroy = "dabgpu_blanker_bank_destroy"
+
+    def __init__(self, ctx, streams):
+        self._ctx = ctx
+        self.n = len(streams)
+        self.plan = blanker_plan(streams)
+        arr = (BlankerStream * self.n)(*streams)
+        self._h = C.c_void_p()
+        check(lib().dabgpu_blanker_bank_create(ctx._h, self.n, arr, C.byref(self._h)), "dabgpu_blanker_bank_create")
+
+    def set_params(self, streams, stream=None):
+        assert len(streams) == self.n
+        arr = (BlankerStream * self.n)(*streams)
+        check(lib().dabgpu_blanker_bank_set_params(self._h, arr, Context._stream(stream)), "dabgpu_blanker_bank_set_params")
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_blanker_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_blanker_bank_seek")
+
+    def apply(self, d_in, n_in, n_out, d_out, in_stride_samples=0, out_stride_bytes=0, d_mask=None, mask_stride_words=0, stream=None):
+        """d_in complex float (device) -> d_out rows of n_out complex float; d_mask (optional): rows of blanker_mask_words(n_out) uint32;
+        d_out must not be d_in; asynchronous"""
+        check(lib().dabgpu_blanker_bank_apply(self._h, _ptr(d_in), in_stride_samples, n_in, n_out, _ptr(d_out), out_stride_bytes, _ptr(d_mask),
+                                              mask_stride_words, Context._stream(stream)), "dabgpu_blanker_bank_apply")
+
+    def apply_host(self, h_in, n_out, in_stride_samples=0, mask=False):
+        """h_in [n][n_in] complex64 (or [n_in] shared with in_stride_samples = 0) -> [n][n_out] complex64; mask = True: (that, the mask words
+        [n][blanker_mask_words(n_out)] uint32)"""
+        import numpy as np
+        words = blanker_mask_words(n_out)
+        m = np.zeros((self.n, words), np.uint32) if mask else None
+        y = _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_blanker_bank_apply_host_sync(
+            self._h, _ptr(x), in_stride_samples, n_in, n_out, _ptr(out), stride, _ptr(m), words), "dabgpu_blanker_bank_apply_host_sync"),
+            h_in, self.n, n_out, IQ_FORMATS.index("raw_f32l"))
+        return (y, m) if mask else y
 
 
 def resample_step(in_rate_hz=2048000.0, out_rate_hz=2048000.0, ppm=0.0):

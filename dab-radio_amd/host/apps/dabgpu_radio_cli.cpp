@@ -49,6 +49,14 @@
 // bits.  The restrictions are --tii's: Synchronize() after every Process(), --ofdm-block-size up to 193952, not with --input-rate or
 // --channel-offset-hz.
 //
+// --blank [THRESHOLD] (not in the reference; include/dabgpu.h "Impulse blanker"): every block of samples at 2.048 MHz -- behind --input-rate
+// and --channel-offset-hz -- goes through a DAB_Stream_Blanker with dabgpu_blanker_defaults() (threshold 3 unless given) in front of
+// OFDM_Demod, which so runs 800 samples behind the input; the rest is flushed at the end of the input.  One "blank blocks=N of M" line
+// follows the ofdm line.  Transmission mode I and the OFDM stage only.  The blanker emits whole blocks of 32 samples, so a call to the
+// demodulator may be up to 31 samples longer than the block just read: with --tii or --soft-bits banded --ofdm-block-size may not exceed
+// 193920, with --snr 98272.  THRESHOLD is taken only where the next argument is a number ("--blank -i FILE" and "--blank abc" leave it at 3;
+// "abc" is then an unknown argument).  Absent: no blanker is made and the tool does what it did.
+//
 // --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
@@ -82,6 +90,7 @@
 #include "dab/quality/dab_channel_ber.h"
 #include "dab/tx/dab_channeliser.h"
 #include "dab/tx/dab_resampler.h"
+#include "ofdm/dab_blanker.h"
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
@@ -116,6 +125,8 @@ struct Args {
     bool soft_banded = false;
     float alpha = 0.25f;
     bool alpha_given = false;
+    bool blank = false;
+    float blank_threshold = 3.0f;
 };
 
 static void usage(const char* argv0) {
@@ -126,7 +137,7 @@ static void usage(const char* argv0) {
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
-        "  [--soft-bits normalised|csi|banded] [--soft-level 1..127] [--alpha A]\n"
+        "  [--soft-bits normalised|csi|banded] [--soft-level 1..127] [--alpha A] [--blank [THRESHOLD]]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -200,12 +211,23 @@ static bool parse_args(int argc, char** argv, Args& args) {
         }
         else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
+        else if (a == "--blank") {
+            args.blank = true;
+            char* end = nullptr;                                                  // the value is optional: taken only where the next argument is a number
+            if (i + 1 < argc) {
+                const float t = std::strtof(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == '\0') { args.blank_threshold = t; i++; }
+            }
+        }
         else if (a == "--input-rate") args.input_rate = std::stod(value());
         else if (a == "--channel-offset-hz") { args.channel_offset_hz = std::stod(value()); args.channelise = true; }
         else if (a == "-h" || a == "--help") return false;
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
     if (args.ber && !args.is_dab_used) throw std::runtime_error("--ber needs the channel decode stage");
+    if (args.blank && !args.is_ofdm_used) throw std::runtime_error("--blank needs the OFDM stage");
+    if (args.blank && args.transmission_mode != 1) throw std::runtime_error("--blank is available in transmission mode 1 only");
+    if (args.blank && !(args.blank_threshold > 1.0f && args.blank_threshold <= 1024.0f)) throw std::runtime_error("--blank: a threshold above 1, up to 1024");
     if (args.soft_policy != DABGPU_SOFT_NORMALISED && !args.is_ofdm_used) throw std::runtime_error("--soft-bits needs the OFDM stage");
     if (args.soft_level_given && args.soft_policy != DABGPU_SOFT_CSI) throw std::runtime_error("--soft-level needs --soft-bits csi");
     if (!(args.soft_level >= 1.0f && args.soft_level <= 127.0f)) throw std::runtime_error("--soft-level: a level from 1 to 127");
@@ -219,6 +241,10 @@ static bool parse_args(int argc, char** argv, Args& args) {
     if (args.tii && !args.is_ofdm_used) throw std::runtime_error("--tii needs the OFDM stage");
     if (args.tii && args.tii_frames < 1) throw std::runtime_error("--tii-frames must be positive");
     if (args.tii && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--tii: --ofdm-block-size may not exceed 193952");
+    // the blanker hands OFDM_Demod whole blocks of 32 samples: up to 31 samples more than the block just read
+    if (args.blank && (args.soft_banded || args.tii) && args.ofdm_block_size > 196608 - 2656 - 32)
+        throw std::runtime_error("--blank with --tii or --soft-bits banded: --ofdm-block-size may not exceed 193920");
+    if (args.blank && args.snr && args.ofdm_block_size > 98304 - 32) throw std::runtime_error("--blank with --snr: --ofdm-block-size may not exceed 98272");
     if (args.channelise) {
         if (!(args.input_rate >= 2.048e6 && args.input_rate <= 8 * 4.096e6)) throw std::runtime_error("--channel-offset-hz: --input-rate 2048000 .. 32768000 samples per second");
         if (!(std::fabs(args.channel_offset_hz) <= 0.5 * args.input_rate)) throw std::runtime_error("--channel-offset-hz: within half of --input-rate either way");
@@ -474,6 +500,16 @@ static int run(const Args& args) {
                                 "block's edge and its neighbour's is narrower at this rate)\n");
         }
         if (block_rate != 2.048e6) resampler = std::make_unique<DAB_Stream_Resampler>(DAB_Resampler::StepWord(block_rate, 2.048e6));
+        // --blank: the impulse blanker between the 2.048 MHz samples and the demodulator, `reach` samples behind its input
+        std::unique_ptr<DAB_Stream_Blanker> blanker;
+        std::vector<std::complex<float>> blanked;
+        if (args.blank) blanker = std::make_unique<DAB_Stream_Blanker>(DAB_Blanker::Defaults(args.blank_threshold));
+        auto feed = [&](tcb::span<const std::complex<float>> x) {
+            if (!blanker) { demod->Process(x); return; }
+            blanked.clear();
+            blanker->Process(x, blanked);
+            if (!blanked.empty()) demod->Process(blanked);
+        };
         for (;;) {
             const size_t length = reader->read(block);
             if (length == 0) break;
@@ -484,23 +520,29 @@ static int run(const Args& args) {
                     if (resampler) {
                         resampled.clear();
                         resampler->Process(split[0], resampled);
-                        if (!resampled.empty()) demod->Process(resampled);
-                    } else demod->Process(split[0]);
+                        if (!resampled.empty()) feed(resampled);
+                    } else feed(split[0]);
                 }
             } else if (resampler) {
                 resampled.clear();
                 resampler->Process(tcb::span<const std::complex<float>>(block.data(), length), resampled);
-                if (!resampled.empty()) demod->Process(resampled);
+                if (!resampled.empty()) feed(resampled);
             } else
-            demod->Process(tcb::span<const std::complex<float>>(block.data(), length));
+            feed(tcb::span<const std::complex<float>>(block.data(), length));
             if (tii || snr || profile) demod->Synchronize();                                   // the observer reads the head of the correlation buffer
             if (snr) snr_poll();
             if (length != block.size()) break;
+        }
+        if (blanker) {                                                                       // the end of the input: what the blanker still holds
+            blanked.clear();
+            blanker->Flush(blanked);
+            if (!blanked.empty()) demod->Process(blanked);
         }
         demod->Synchronize();
         fprintf(stderr, "ofdm: frames_read=%d frames_desync=%d coarse=%.6g fine=%.6g\n", demod->GetTotalFramesRead(),
                 demod->GetTotalFramesDesync(), demod->GetCoarseFrequencyOffset(), demod->GetFineFrequencyOffset());
         if (profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
+        if (blanker) fprintf(stderr, "blank blocks=%llu of %llu\n", (unsigned long long)blanker->BlankedBlocks(), (unsigned long long)blanker->TotalBlocks());
     } else {
         std::vector<viterbi_bit_t> bits(radio->frame_bits());                         // Basic_Radio_Block::run, app_radio_blocks.h:31-38
         std::vector<uint8_t> packed(bits.size() / 8);

@@ -1422,6 +1422,87 @@ int dabgpu_interferer_bank_apply_host_sync(dabgpu_interferer_bank *bank, const f
                                            void *h_out, int out_format, size_t out_stride_bytes, float u8_scale);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Impulse blanker: zeroes bursts (ignition-like impulsive interference, the interferer's gated white source) in n_streams independent
+ * streams of complex float samples ahead of the demodulator.  The reference has no blanker; the definition is this library's own,
+ * written once in dab-radio_amd/csrc/blanker_core.h for the kernel (blanker.hip) and for the host model the tests build from the same
+ * header (tests/cpp/blanker_host_model.cpp), pinned to an independent numpy model (tests/blanker_model.py, tests/test_blanker_model.py)
+ * and on the device bit for bit to the host model (tests/test_gpu_blanker.py).  Derivation and measurements: DESIGN.md 4.29.
+ *
+ * A greatest-of cell-averaging detector on block powers.  It takes no level from outside and keeps no state: output sample m of stream s
+ * depends on (parameters, the input around m) alone, so a call of a + b samples equals a call of a and then one of b on the same d_in and
+ * n_in at any split (inside a block too), and replays of a captured call continue the stream.
+ *   input   x[i], i = m - start, of the caller's d_in; m is absolute (the bank's 64-bit position + the sample's index in the call) and
+ *           signed where blocks before sample 0 are read; samples outside [0, n_in) are 0.  A caller that holds a window from absolute
+ *           sample W on passes it as d_in and adds W to `start`.
+ *   p[b]    block b = absolute samples [32 b, 32 b + 32): the mean of |x|^2 in float32.  |x|^2 = fmaf(im, im, re * re); the 32 values
+ *           are summed as a pairwise tree (neighbours first, 5 levels); the mean is a product with 2^-5.  No division anywhere.
+ *   ref[b]  q[b] = p[b] where finite, else 0.  before = sum_{k = 1..window} q[b - gap - k], after = sum_{k = 1..window} q[b + gap + k],
+ *           each from 0 in increasing k in float32; ref = the greater of the two (the smaller cannot be trusted at a NULL -> PRS edge,
+ *           where "before" holds noise only and would blank the start of every frame).
+ *   flag[b] = p[b] not finite, or (ref[b] > 0 and (float)window * p[b] > threshold * ref[b])
+ *   blank[b] = the OR of flag[b - guard .. b + guard]
+ *   y[m]    = +0 + j(+0) where blank[m >> 5], else x[m - start] bit for bit.  A stream with enabled = 0 copies its input.
+ *   mask    (optional) one uint32 per stream and absolute tile of 1024 samples: bit k of tile t's word is blank[32 t + k].  Word j of a
+ *           call at position p is tile (p >> 10) + j; a call sets only the bits of blocks whose FIRST sample lies in [p, p + n_out) and
+ *           writes all dabgpu_blanker_mask_words(n_out) = n_out / 1024 + 2 words of every stream (the others 0), so the words of split
+ *           calls OR together to the words of one call.  A disabled stream's words are 0.
+ * dabgpu_blanker_defaults: threshold 3, gap 8, window 16, guard 1, enabled, start 0.  Against one 16-block side a threshold of 3 has a
+ * per-block false-alarm probability of 3.9e-13 for complex Gaussian samples (tests/blanker_model.py recomputes it).
+ *
+ * dabgpu_blanker_plan (host only, no device): refused with DABGPU_ERR_INVALID_ARG, naming stream and field: n_streams outside
+ * 1..1048576, NULL params, a threshold that is not finite or outside (1, 1024], window outside 1..32, gap outside 0..32, guard outside
+ * 0..4, |start| above 2^62.  (enabled = 0 streams are checked all the same.)
+ *   reach_blocks   the largest gap + window + guard of the list: blocks either side of a block that its output depends on
+ *   block_samples  output samples one workgroup produces (DABGPU_BLANKER_BLOCK)
+ *   lds_bytes      a workgroup's block powers and flags: (block_samples / 32 + 2 reach_blocks) floats + (block_samples / 32 + 8) words
+ * dabgpu_blanker_input_needed (host only): the input indices [first, first + count) (first may be negative, count may run past n_in)
+ * that a call of n_out samples at `position` reads of a stream with these parameters: whole blocks, gap + window + guard blocks either
+ * side; count = 0 for n_out = 0; a disabled stream reads its n_out samples only.  With the defaults the look-ahead is 25 blocks = 800
+ * samples, about 0.39 ms at 2.048 MS/s. */
+#define DABGPU_BLANKER_POWER_BLOCK 32                       /* samples of one block power */
+#define DABGPU_BLANKER_BLOCK 1024                           /* samples of one workgroup's tile = one mask word */
+#define DABGPU_BLANKER_MAX_WINDOW 32
+#define DABGPU_BLANKER_MAX_GAP 32
+#define DABGPU_BLANKER_MAX_GUARD 4
+#define DABGPU_BLANKER_MAX_THRESHOLD 1024.0f
+#define DABGPU_BLANKER_MAX_POSITION ((int64_t)1 << 62)      /* |start| and the stream position stay below */
+typedef struct {
+    int64_t start;
+    float threshold;
+    int32_t gap, window, guard;     /* blocks */
+    int32_t enabled, reserved;
+} dabgpu_blanker_stream;
+typedef struct { uint32_t reach_blocks, block_samples, lds_bytes, reserved; } dabgpu_blanker_geometry;
+dabgpu_blanker_stream dabgpu_blanker_defaults(void);
+size_t dabgpu_blanker_mask_words(size_t n_out);
+int dabgpu_blanker_plan(const dabgpu_blanker_stream *params, size_t n_streams, dabgpu_blanker_geometry *out);
+int dabgpu_blanker_input_needed(const dabgpu_blanker_stream *params, uint64_t position, size_t n_out, int64_t *first, uint64_t *count);
+
+/* Impulse blanker bank: the parameters of n_streams streams and their common position on the device, built like the channel bank.
+ *   d_in    stream s reads d_in + s * in_stride_samples complex float; in_stride_samples = 0: one shared row, otherwise >= n_in and even.
+ *           16-byte aligned.  n_in >= 1.
+ *   d_out   stream s writes n_out complex float from d_out + s * out_stride_bytes on (a multiple of 16 that holds n_out samples; 0 = the
+ *           default), 16-byte aligned.  d_out == d_in is refused: a workgroup reads its neighbours' tiles, so in place is not defined.
+ *   d_mask  NULL, or stream s writes dabgpu_blanker_mask_words(n_out) words from d_mask + s * mask_stride_words on (0 = that count;
+ *           otherwise at least that count), 4-byte aligned.
+ * A call is two launches on `stream`: the blanker kernel and the one-thread kernel that adds n_out to the position; no host state
+ * changes, so a call may be captured and its replays continue the stream.  _seek sets the position (<= 2^62), _set_params replaces all
+ * parameters within the geometry fixed at creation: a larger reach_blocks is refused (create the bank with its widest parameters).
+ * Arguments are checked in plain C++ (dabgpu_host_logic.cpp) before any device call, and a refusal leaves the output untouched
+ * (tests/test_blanker_plan.py, tests/test_gpu_blanker.py). */
+typedef struct dabgpu_blanker_bank dabgpu_blanker_bank;
+int dabgpu_blanker_bank_create(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_blanker_stream *h_params, dabgpu_blanker_bank **out);
+void dabgpu_blanker_bank_destroy(dabgpu_blanker_bank *bank);
+int dabgpu_blanker_bank_set_params(dabgpu_blanker_bank *bank, const dabgpu_blanker_stream *h_params, void *stream);
+int dabgpu_blanker_bank_seek(dabgpu_blanker_bank *bank, uint64_t position, void *stream);
+int dabgpu_blanker_bank_apply(dabgpu_blanker_bank *bank, const float *d_in, size_t in_stride_samples, size_t n_in, size_t n_out, void *d_out,
+                              size_t out_stride_bytes, uint32_t *d_mask, size_t mask_stride_words, void *stream);
+/* the same from and to host memory on the context's stream (rows of any length >= n_in, no alignment rule; h_mask may be NULL), as
+ * dabgpu_channel_bank_apply_host_sync */
+int dabgpu_blanker_bank_apply_host_sync(dabgpu_blanker_bank *bank, const float *h_in, size_t in_stride_samples, size_t n_in, size_t n_out,
+                                        void *h_out, size_t out_stride_bytes, uint32_t *h_mask, size_t mask_stride_words);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Resampler: arbitrary-ratio, fractional-delay resampling of n_streams independent streams of complex float samples -- a receiver's
  * sampling-clock error and fractional delay behind the channel model, and captures at 2.4, 2.56, 3.072 or 4.096 MS/s brought to the 2.048 MHz
  * grid in front of the demodulator.  The reference has nothing comparable; the definition is this library's own, written once in

@@ -43,10 +43,17 @@ slice and sync records go through dabgpu_noise_profile_frames (the state carried
 band weights into dabgpu_diversity_combine_frames_banded: with one branch interference-aware soft bits, with several maximal-ratio combining per
 band.  Every cell still reads `single -> combined`, branch 0's own weighted soft bits against the banded combination.  The output goes to
 profiles/tx/waterfall_banded.md.
+With --interferer-gate PERIOD:ON:IS_DB a burst interferer is added to every channel stream behind the channel: white noise from the library's own
+bank (dabgpu.Interferer, a seed per stream) behind its integer gate, on for ON of every PERIOD samples (20480:205 = 100 us every 10 ms), IS_DB
+relative to the signal power while it is on.  With --blank [THRESHOLD] every receiver runs twice, on the received samples as they are and on the
+same samples through the impulse blanker (dabgpu.Blanker, dabgpu_blanker_defaults with that threshold, default 3), and every cell reads
+`unblanked -> blanked`; under every table the share of the blocks the blanker zeroed.  The output goes to profiles/tx/waterfall_blank.md.  Both
+options belong to the plain receiver path (not with --branches, --weights, --soft-bits csi, --clock-ppm, --adjacent-db, --doppler-hz or --ber).
+Without them the run and its outputs are what they were.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
                               [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]
                               [--branch-noise-db A,B,...] [--weights unit|estimated|true|banded] [--alpha A] [--interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB]
-                              [--append]"""
+                              [--append] [--interferer-gate PERIOD:ON:IS_DB] [--blank [THRESHOLD]]"""
 import argparse
 import math
 import os
@@ -83,6 +90,8 @@ def main():
     ap.add_argument("--interferer", default=None)
     ap.add_argument("--interferer-source", default="torch", choices=("torch", "device"))
     ap.add_argument("--append", action="store_true")
+    ap.add_argument("--interferer-gate", default=None)
+    ap.add_argument("--blank", nargs="?", type=float, const=3.0, default=None)
     a = ap.parse_args()
     K = a.branches
     mrc = a.branch_noise_db is not None or a.weights != "unit"
@@ -126,6 +135,23 @@ def main():
     clock_ppm = [float(v) for v in a.clock_ppm.split(",")] if a.clock_ppm is not None else []
     if a.profile is not None and a.doppler_hz is None:
         ap.error("--profile wants --doppler-hz")
+    gate = None
+    if a.interferer_gate is not None:
+        gate = a.interferer_gate.split(":")
+        if len(gate) != 3:
+            ap.error("--interferer-gate takes PERIOD:ON:IS_DB")
+        gate = (int(gate[0]), int(gate[1]), float(gate[2]))
+        if not 0 < gate[1] <= gate[0]:
+            ap.error("--interferer-gate: 0 < ON <= PERIOD samples")
+    blank = a.blank is not None
+    if blank or gate is not None:
+        if branch_path or mrc or csi or a.clock_ppm is not None or a.adjacent_db is not None or a.doppler_hz is not None or a.ber:
+            ap.error("--interferer-gate and --blank belong to the plain receiver path")
+    if blank:
+        if not 1.0 < a.blank <= 1024.0:
+            ap.error("--blank takes a threshold above 1, up to 1024")
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_blank.md")          # (waterfall.md is never rewritten by such a run)
     import numpy as np
     import torch
     import dabgpu
@@ -222,6 +248,18 @@ def main():
                     f"{' --append' if a.append else ''}`; the verdict line is the combination's."
                     + (f"  Interferer: Gaussian noise {jam[1]:g} kHz wide {jam[0]:+g} kHz from the centre, {jam[2]:+g} dB relative to the signal, a seed per stream; the "
                        "frame scale rests on the power of the phase reference symbol, interferer included." if jam else ""), ""]
+    if blank:
+        text = ["# Receiver sensitivity with and without the impulse blanker", "",
+                f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall.md` with every receiver run twice on the SAME received "
+                f"samples: as they are, and through dabgpu.Blanker (threshold {a.blank:g}, gap 8, window 16, guard 1 blocks of 32 samples); every cell is `unblanked -> blanked`.  "
+                + (f"Interferer: white noise from dabgpu.Interferer behind a gate, on for {gate[1]} of every {gate[0]} samples, {gate[2]:+g} dB relative to the signal while on, "
+                   "a seed per stream.  " if gate else "No interferer.  ") +
+                f"{E} receivers x {F} mode I frames per point, FIBs of every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
+                f"`python tools/waterfall.py --blank {a.blank:g}{' --interferer-gate ' + a.interferer_gate if gate else ''} --streams {E} --frames {F} --snr {a.snr}`; "
+                "the verdict line is the blanked receiver's.", ""]
+        blanker = dabgpu.Blanker(ctx, [dabgpu.blanker_stream(threshold=a.blank) for _ in range(E)])
+        d_blank = torch.zeros((E, n_rx, 2), dtype=torch.float32, device="cuda")
+        d_mask = torch.zeros((E, dabgpu.blanker_mask_words(n_rx)), dtype=torch.int32, device="cuda")
     verdicts = []
     profiles, fading =[(n, t, None, None) for n, t in PROFILES], None
     if adjacent_db:
@@ -252,7 +290,7 @@ def main():
             comb, spl = dabgpu.Channeliser(ctx, both, E, ADJ_D), dabgpu.Channeliser(ctx, wanted, E, ADJ_D)
         rs = dabgpu.Resampler(ctx, [dabgpu.resample_stream(dabgpu.resample_step(ppm=ppm)) for _ in range(E)]) if ppm is not None else None
         h2 = sum(re * re + im * im for _, re, im in taps)
-        rows, rows_ref, chan = [], [], []
+        rows, rows_ref, chan, shares = [], [], [], []
         ch = dabgpu.Channel(ctx, [dabgpu.channel_stream(taps=taps, seed=1000 + e, noise_sigma=1.0) for e in range(EC)], fading=fading)
         for snr in snrs:
             sigma = math.sqrt(1536.0 * h2 / (2.0 * 10.0 ** (snr / 10.0)))
@@ -282,6 +320,22 @@ def main():
                     x = torch.fft.ifft(torch.where(keep, X, torch.zeros_like(X)))
                     x = x * math.sqrt(1536.0 * h2 * 10.0 ** (jam[2] / 10.0)) / x.abs().square().mean().sqrt()
                     d_rx[e] += torch.view_as_real(x)
+            if gate is not None:
+                # the library's burst source (include/dabgpu.h "Interferer"): white noise behind an integer gate, a seed per stream, in place
+                amp = math.sqrt(1536.0 * h2 * 10.0 ** (gate[2] / 10.0))
+                itf = dabgpu.Interferer(ctx, [dabgpu.interferer_stream([dabgpu.interferer_source(dabgpu.INTERFERER_BAND, amp=amp, shape=-1, gate_period=gate[0],
+                                                                                                  gate_on=gate[1], gate_offset=-1000)], seed=7000 + e)
+                                              for e in range(EC)])
+                itf.apply(d_rx, n_rx, d_rx, in_stride_samples=n_rows * n_rx, out_stride_bytes=n_rows * n_rx * 8)
+                torch.cuda.synchronize()
+                itf.close()
+            if blank:
+                blanker.seek(0)
+                blanker.apply(d_rx, n_rx, n_rx, d_blank, in_stride_samples=n_rx, d_mask=d_mask)
+                torch.cuda.synchronize()
+                bits = int(np.unpackbits(d_mask.cpu().numpy().view(np.uint8)).sum())
+                shares.append(bits / (E * ((n_rx + 31) // 32)))
+                passes = [(dabgpu.SOFT_NORMALISED, d_rx), (dabgpu.SOFT_NORMALISED, d_blank)]
             if comb is not None:
                 comb.seek(0); spl.seek(0)
                 comb.combine(d_rows, n_rx, n_wide, d_wide, in_stride_samples=n_rx, out_stride_bytes=n_wide * 8)
@@ -291,6 +345,8 @@ def main():
                 rs.seek(0)
                 rs.apply(d_rx, n_rx, n_out, d_rs, in_stride_samples=n_rx, out_stride_bytes=n_out * 8)
                 d_use = d_rs
+            if not blank:
+                passes = [(pol, d_use) for pol in policies]                 # (receiver call, its samples)
             if branch_path:
                 # receive diversity: ring 0 takes branch 0's own soft bits, ring 1 the combination of the K branches
                 soft = dabgpu.SoftCfg(dabgpu.SOFT_CSI, a.soft_level)
@@ -342,7 +398,7 @@ def main():
                                 err[r][owner[i]] += int(bad[:, off:off + n].sum()); tot[r][owner[i]] += E * n
                 rows_ref.append((snr, crc_ok[0] / crc_n[0], [e / t for e, t in zip(err[0], tot[0])], tot[0]))
                 rows.append((snr, crc_ok[1] / crc_n[1], [e / t for e, t in zip(err[1], tot[1])], tot[1]))
-            for pol in (policies if not branch_path else []):
+            for pi, (pol, d_src) in enumerate(passes if not branch_path else []):
                 d_st = torch.zeros(E * sdt.itemsize, dtype=torch.uint8, device="cuda")
                 hist = torch.zeros((E, H, dabgpu.NB_FRAME_BITS), dtype=torch.int8, device="cuda")
                 d_fib = torch.zeros((E, 4, 96), dtype=torch.uint8, device="cuda"); fres = torch.zeros((E * 4, 16), dtype=torch.uint8, device="cuda")
@@ -355,7 +411,7 @@ def main():
                 for j in range(F):
                     a0 = NULL + j * S - P_LEAD
                     sl = torch.zeros((E, STRIDE, 2), dtype=torch.float32, device="cuda")
-                    seg = d_use[:, a0:a0 + STRIDE]
+                    seg = d_src[:, a0:a0 + STRIDE]
                     sl[:, :seg.shape[1]] = seg
                     if pol == dabgpu.SOFT_NORMALISED:
                         ctx.ofdm_sync_demod_frames(sl, E, STRIDE, P_LEAD, d_st, hist[:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS)
@@ -381,7 +437,7 @@ def main():
                         bad = (msc[:, c] != cifs[4 * j + c - 15][None, :])
                         for i, (off, n) in enumerate(spans):
                             err[owner[i]] += int(bad[:, off:off + n].sum()); tot[owner[i]] += E * n
-                if pol == policies[-1]:
+                if pi == len(passes) - 1:
                     rows.append((snr, crc_ok / crc_n, [e / t for e, t in zip(err, tot)], tot))
                     if a.ber:
                         assert m_bits == t_bits
@@ -393,7 +449,7 @@ def main():
             rs.close()
         if comb is not None:
             comb.close(); spl.close()
-        if csi or branch_path:
+        if csi or branch_path or blank:
             # both policies side by side: normalised -> csi in every cell (receive diversity: single -> combined)
             text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
             fmt = lambda r: f"{r:.2e}" if r else "0"
@@ -402,6 +458,8 @@ def main():
         else:
             text += [f"## {pname}", "", "| SNR dB | FIB CRC pass | " + " | ".join(name + " byte errors" for name, _ in LEVELS) + " |", "|---|---|" + "---|" * len(LEVELS)]
             text += [f"| {snr:g} | {ok:.4f} | " + " | ".join(f"{r:.2e}" if r else "0" for r in ber) + " |" for snr, ok, ber, _ in rows]
+        if blank:
+            text += ["", "Blocks the blanker zeroed, of all: " + ", ".join(f"{snr:g} dB {100.0 * sh:.2f} %" for (snr, _, _, _), sh in zip(rows, shares)) + "."]
         if a.ber:
             n0 = len(text) - len(rows) - 2
             text[n0] += " channel BER measured | channel BER true |"; text[n0 + 1] += "---|---|"
@@ -421,6 +479,8 @@ def main():
                  f"First SNR from which no byte error remains: " + ", ".join(f"{name} {n:g} dB" for (name, _), n in zip(LEVELS, need)) +
                  f" -- ordered 1-A <= 2-A <= 3-A <= 4-A: {'yes' if order else 'NO'}.", ""]
         verdicts.append(free and mono and order)
+    if blank:
+        blanker.close()
     text = "\n".join(text) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
