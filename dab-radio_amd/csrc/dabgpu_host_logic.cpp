@@ -5,6 +5,7 @@
 #include "diversity_core.h"
 #include "noise_core.h"
 #include "noise_profile_core.h"
+#include "dd_profile_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -246,6 +247,44 @@ int dabgpu_noise_profile_exclude_tii(const uint8_t* main_ids, const uint8_t* sub
         }
     }
     return DABGPU_OK;
+}
+
+int dabgpu_dd_profile_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const uint32_t* d_exclude,
+                           const float* d_profile_in, float alpha, const float* d_profile_out, const float* d_band_weight, const float* d_mean_noise,
+                           const float* d_carrier_noise, const float* d_carrier_amplitude, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
+    if (!out) { dabgpu_set_error("dd_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("dd_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("dd_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_dqpsk) { dabgpu_set_error("dd_profile_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("dd_profile_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_sync | (uintptr_t)d_exclude | (uintptr_t)d_profile_in | (uintptr_t)d_profile_out | (uintptr_t)d_band_weight |
+         (uintptr_t)d_mean_noise | (uintptr_t)d_valid) & 3) {
+        dabgpu_set_error("dd_profile_plan: records, tables and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_carrier_noise | (uintptr_t)d_carrier_amplitude) & 7) {
+        dabgpu_set_error("dd_profile_plan: d_carrier_noise and d_carrier_amplitude must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!dabgpu::np_alpha_ok(alpha)) { dabgpu_set_error("dd_profile_plan: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
+    if (d_profile_in && d_profile_out && d_profile_in != d_profile_out) {
+        const uintptr_t a = (uintptr_t)d_profile_in, b = (uintptr_t)d_profile_out, bytes = (uintptr_t)n_frames * dabgpu::NP_BANDS * sizeof(float);
+        if (a < b + bytes && b < a + bytes) {
+            dabgpu_set_error("dd_profile_plan: d_profile_in and d_profile_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!d_profile_out && !d_band_weight && !d_mean_noise && !d_carrier_noise && !d_carrier_amplitude && !d_valid) {
+        dabgpu_set_error("dd_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
+    }
+    out->grid = (uint32_t)n_frames;
+    out->threads = DABGPU_DD_PROFILE_THREADS;
+    out->lds_bytes = DABGPU_DD_PROFILE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_dd_profile_carriers_host(const float* dqpsk, float* carrier_noise, float* carrier_amplitude) {
+    if (!dqpsk) return -1;
+    dabgpu::ddp_frame_carriers(dqpsk, carrier_noise, carrier_amplitude);
+    return 0;
 }
 
 float dabgpu_diversity_band_mean_host(const float band_weight[128]) { return band_weight ? dabgpu::np_branch_weight(band_weight) : 0.0f; }

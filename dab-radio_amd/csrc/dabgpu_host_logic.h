@@ -249,6 +249,11 @@ int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout,
 // the banded combiner's instantiation adds the two wave sums of every branch's mean weight to the combiner's LDS
 #define DABGPU_DIVERSITY_BANDED_LDS_BYTES (DABGPU_DIVERSITY_LDS_BYTES + 8u * 2u * 4u)
 
+// ---- decision-directed noise profile (dd_profile.hip launches from dabgpu_dd_profile_plan; include/dabgpu.h) ----
+// one 256-thread workgroup per frame; static LDS: 1536 carrier values, the two wave sums of the mean
+#define DABGPU_DD_PROFILE_THREADS 256u
+#define DABGPU_DD_PROFILE_LDS_BYTES (6144u + 8u)
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

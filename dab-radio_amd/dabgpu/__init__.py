@@ -100,6 +100,7 @@ ABI_SYMBOLS = [
     "dabgpu_noise_profile_plan", "dabgpu_noise_profile_frames", "dabgpu_noise_profile_host_sync", "dabgpu_noise_profile_bands_host",
     "dabgpu_noise_profile_exclude_tii", "dabgpu_diversity_plan_banded", "dabgpu_diversity_combine_frames_banded",
     "dabgpu_diversity_combine_banded_host_sync", "dabgpu_diversity_band_mean_host",
+    "dabgpu_dd_profile_plan", "dabgpu_dd_profile_frames", "dabgpu_dd_profile_host_sync", "dabgpu_dd_profile_carriers_host",
     "dabgpu_interferer_design", "dabgpu_interferer_plan", "dabgpu_interferer_bank_create", "dabgpu_interferer_bank_destroy",
     "dabgpu_interferer_bank_set_params", "dabgpu_interferer_bank_seek", "dabgpu_interferer_bank_apply", "dabgpu_interferer_bank_apply_host_sync",
     "dabgpu_blanker_defaults", "dabgpu_blanker_mask_words", "dabgpu_blanker_plan", "dabgpu_blanker_input_needed", "dabgpu_blanker_bank_create",
@@ -464,6 +465,10 @@ def lib():
                                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_noise_profile_bands_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_noise_profile_exclude_tii.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_dd_profile_plan.argtypes = [C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 7
+        L.dabgpu_dd_profile_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 7
+        L.dabgpu_dd_profile_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
+        L.dabgpu_dd_profile_carriers_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_diversity_plan_banded.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.dabgpu_diversity_combine_frames_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -987,6 +992,32 @@ class Context:
                                                    _ptr(profile), float(alpha), _ptr(bw), C.byref(mean), _ptr(cp), C.byref(ok)),
               "dabgpu_noise_profile_host_sync")
         return (bw, mean.value, ok.value) + ((cp,) if carrier_power else ())
+
+    def dd_profile(self, dqpsk, n_frames, sync=None, exclude=None, profile_in=None, alpha=1.0, profile_out=None, band_weight=None,
+                   mean_noise=None, carrier_noise=None, carrier_amplitude=None, valid=None, stream=None):
+        """the decision-directed noise profile of n_frames frames (include/dabgpu.h, "Decision-directed noise profile"): dqpsk
+        [n_frames][75][1536] complex64 and sync the records of ofdm_sync_demod_frames_branch, exclude = 48 uint32 words on the device,
+        profile_in / profile_out [n_frames][128] float32 the smoothing state (may be one buffer), band_weight [n_frames][128] (an entry
+        of diversity_combine's band_weights as it is), mean_noise [n_frames], carrier_noise / carrier_amplitude [n_frames][1536], valid
+        [n_frames] uint32; every output optional.  One kernel launch, no copy: capturable"""
+        check(lib().dabgpu_dd_profile_frames(self._h, _ptr(dqpsk), n_frames, _ptr(sync), _ptr(exclude), _ptr(profile_in), float(alpha),
+                                             _ptr(profile_out), _ptr(band_weight), _ptr(mean_noise), _ptr(carrier_noise), _ptr(carrier_amplitude),
+                                             _ptr(valid), self._stream(stream)), "dabgpu_dd_profile_frames")
+
+    def dd_profile_host(self, dqpsk, exclude=None, profile=None, alpha=1.0, carriers=False):
+        """numpy convenience over dabgpu_dd_profile_host_sync: one frame's products [75][1536] complex64 -> (band weights [128], mean
+        noise, valid[, carrier noise [1536], carrier amplitude [1536]]); profile = a [128] float32 array, the state, updated in place"""
+        import numpy as np
+        x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(75 * NB_CARRIERS)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint32).reshape(NOISE_PROFILE_EXCLUDE_WORDS)
+        if profile is not None and (profile.dtype != np.float32 or profile.size != NOISE_PROFILE_BANDS or not profile.flags.c_contiguous):
+            raise ValueError("dd_profile_host: profile must be a contiguous float32 array of 128")
+        bw = np.zeros(NOISE_PROFILE_BANDS, np.float32)
+        q, a = (np.zeros(NB_CARRIERS, np.float32), np.zeros(NB_CARRIERS, np.float32)) if carriers else (None, None)
+        mean, ok = C.c_float(0.0), C.c_uint32(0)
+        check(lib().dabgpu_dd_profile_host_sync(self._h, _ptr(x), _ptr(ex), _ptr(profile), float(alpha), _ptr(bw), C.byref(mean), _ptr(q), _ptr(a),
+                                                C.byref(ok)), "dabgpu_dd_profile_host_sync")
+        return (bw, mean.value, ok.value) + ((q, a) if carriers else ())
 
     def noise_estimate_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0):
         """numpy convenience over dabgpu_noise_estimate_host_sync: one frame's NULL and phase reference symbol out of complex64 samples ->
@@ -2298,6 +2329,28 @@ def noise_profile_bands_host(carrier_power, exclude=None, profile_in=None, alpha
     if st < 0:
         raise DabGpuError("dabgpu_noise_profile_bands_host: alpha outside (0, 1]")
     return prof, bw, mean.value, st
+
+
+def dd_profile_plan(dqpsk, n_frames, sync=None, exclude=None, profile_in=None, alpha=1.0, profile_out=None, band_weight=None, mean_noise=None,
+                    carrier_noise=None, carrier_amplitude=None, valid=None, mode=1):
+    """dabgpu_dd_profile_plan (host only, nothing is dereferenced): the NoiseGeometry of a dd_profile call with these arguments; raises
+    DabGpuError with the reason where that call would be refused"""
+    g = NoiseGeometry()
+    check(lib().dabgpu_dd_profile_plan(int(mode), _ptr(dqpsk), n_frames, _ptr(sync), _ptr(exclude), _ptr(profile_in), float(alpha), _ptr(profile_out),
+                                       _ptr(band_weight), _ptr(mean_noise), _ptr(carrier_noise), _ptr(carrier_amplitude), _ptr(valid), C.byref(g)),
+          "dabgpu_dd_profile_plan")
+    return g
+
+
+def dd_profile_carriers_host(dqpsk):
+    """steps 1 and 2 of the decision-directed noise profile on the host: one frame's products [75][1536] complex64 -> (carrier noise
+    [1536], carrier amplitude [1536]); noise_profile_bands_host takes the first from there"""
+    import numpy as np
+    x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(75 * NB_CARRIERS)
+    q, a = np.zeros(NB_CARRIERS, np.float32), np.zeros(NB_CARRIERS, np.float32)
+    if lib().dabgpu_dd_profile_carriers_host(_ptr(x), _ptr(q), _ptr(a)) != 0:
+        raise DabGpuError("dabgpu_dd_profile_carriers_host: null products")
+    return q, a
 
 
 def diversity_band_mean(band_weight):

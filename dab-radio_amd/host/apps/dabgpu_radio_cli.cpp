@@ -49,6 +49,10 @@
 // bits.  The restrictions are --tii's: Synchronize() after every Process(), --ofdm-block-size up to 193952, not with --input-rate or
 // --channel-offset-hz.
 //
+// --soft-bits banded-dd [--alpha A] [--soft-level L] (include/dabgpu.h "Decision-directed noise profile"): the banded path with DAB_DD_Profile in
+// the profile's place: the band weights come from the delivered frame's own products (GetFrameDataVec()), not from the NULL behind it, so an
+// interferer that is silent during the NULL symbol (gated, TDMA) is still weighted down.  Options and restrictions are banded's.
+//
 // --blank [THRESHOLD] (not in the reference; include/dabgpu.h "Impulse blanker"): every block of samples at 2.048 MHz -- behind --input-rate
 // and --channel-offset-hz -- goes through a DAB_Stream_Blanker with dabgpu_blanker_defaults() (threshold 3 unless given) in front of
 // OFDM_Demod, which so runs 800 samples behind the input; the rest is flushed at the end of the input.  One "blank blocks=N of M" line
@@ -94,6 +98,7 @@
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
+#include "ofdm/dab_dd_profile.h"
 #include "ofdm/dab_noise_profile.h"
 #include "ofdm/dab_diversity_combiner.h"
 
@@ -123,6 +128,7 @@ struct Args {
     float soft_level = 64.0f;
     bool soft_level_given = false;
     bool soft_banded = false;
+    bool soft_banded_dd = false;                     // (with soft_banded: the decision-directed profile in the NULL-based one's place)
     float alpha = 0.25f;
     bool alpha_given = false;
     bool blank = false;
@@ -137,7 +143,7 @@ static void usage(const char* argv0) {
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
-        "  [--soft-bits normalised|csi|banded] [--soft-level 1..127] [--alpha A] [--blank [THRESHOLD]]\n"
+        "  [--soft-bits normalised|csi|banded|banded-dd] [--soft-level 1..127] [--alpha A] [--blank [THRESHOLD]]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -207,7 +213,8 @@ static bool parse_args(int argc, char** argv, Args& args) {
             if (p == "normalised") args.soft_policy = DABGPU_SOFT_NORMALISED;
             else if (p == "csi") args.soft_policy = DABGPU_SOFT_CSI;
             else if (p == "banded") { args.soft_policy = DABGPU_SOFT_CSI; args.soft_banded = true; }
-            else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised, csi or banded)");
+            else if (p == "banded-dd") { args.soft_policy = DABGPU_SOFT_CSI; args.soft_banded = true; args.soft_banded_dd = true; }
+            else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised, csi, banded or banded-dd)");
         }
         else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
@@ -402,13 +409,14 @@ static int run(const Args& args) {
         std::vector<uint8_t> hard;
         // --soft-bits banded: the profile of the NULL symbols, the one-branch combiner and the frame's combined soft bits
         std::unique_ptr<DAB_Noise_Profile> profile;
+        std::unique_ptr<DAB_DD_Profile> dd_profile;                                  // --soft-bits banded-dd: in its place
         std::unique_ptr<DAB_Diversity_Combiner> combiner;
         std::vector<viterbi_bit_t> banded_bits;
         int banded_desync = 0;
         size_t banded_frames = 0, banded_kept = 0;
         if (args.soft_banded) {
-            profile = std::make_unique<DAB_Noise_Profile>();
-            profile->SetAlpha(args.alpha);
+            if (args.soft_banded_dd) { dd_profile = std::make_unique<DAB_DD_Profile>(); dd_profile->SetAlpha(args.alpha); }
+            else { profile = std::make_unique<DAB_Noise_Profile>(); profile->SetAlpha(args.alpha); }
             combiner = std::make_unique<DAB_Diversity_Combiner>(1);
             banded_bits.resize(DABGPU_NB_FRAME_BITS);
             demod->EnableDebugBuffers(true);                                         // the products of every frame, from the first
@@ -434,14 +442,17 @@ static int run(const Args& args) {
         };
         demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> demod_bits) {
             tcb::span<const viterbi_bit_t> bits = demod_bits;
-            if (profile) {
-                if (demod->GetTotalFramesDesync() != banded_desync) { banded_desync = demod->GetTotalFramesDesync(); profile->Reset(); }
+            if (profile || dd_profile) {
+                if (demod->GetTotalFramesDesync() != banded_desync) {
+                    banded_desync = demod->GetTotalFramesDesync();
+                    if (profile) profile->Reset(); else dd_profile->Reset();
+                }
                 float w[DABGPU_NOISE_PROFILE_BANDS];
-                const auto null_region = demod->GetCorrelationTimeBuffer().first(2656);
+                // (the buffer has the reference's size, 75 x 2048; the products are its first 75 x 1536)
+                const tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
                 bool combined = false;
-                if (profile->Update(null_region, 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid()) {
-                    // (the buffer has the reference's size, 75 x 2048; the products are its first 75 x 1536)
-                    const tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
+                if (profile ? (profile->Update(demod->GetCorrelationTimeBuffer().first(2656), 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid())
+                            : (dd_profile->Update(products[0], w) && dd_profile->IsValid())) {
                     const tcb::span<const float> band_weights[1] = {{w, (size_t)DABGPU_NOISE_PROFILE_BANDS}};
                     const float scale[1] = {demod->GetSoftScale()};
                     combined = combiner->Combine(products, scale, tcb::span<const float>(), band_weights, banded_bits);
@@ -541,7 +552,7 @@ static int run(const Args& args) {
         demod->Synchronize();
         fprintf(stderr, "ofdm: frames_read=%d frames_desync=%d coarse=%.6g fine=%.6g\n", demod->GetTotalFramesRead(),
                 demod->GetTotalFramesDesync(), demod->GetCoarseFrequencyOffset(), demod->GetFineFrequencyOffset());
-        if (profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
+        if (profile || dd_profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
         if (blanker) fprintf(stderr, "blank blocks=%llu of %llu\n", (unsigned long long)blanker->BlankedBlocks(), (unsigned long long)blanker->TotalBlocks());
     } else {
         std::vector<viterbi_bit_t> bits(radio->frame_bits());                         // Basic_Radio_Block::run, app_radio_blocks.h:31-38

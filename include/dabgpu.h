@@ -2105,6 +2105,59 @@ int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx *ctx, const float *cons
 /* the branch weight of a band table on the host: the tree mean above of 128 band weights */
 float dabgpu_diversity_band_mean_host(const float band_weight[128]);
 
+/* ------------------------------------------------------------------------------------------------
+ * Decision-directed noise profile: "Noise profile" with the frame's own DQPSK products in the NULL symbol's place (mode I; batched, one
+ * kernel launch per call, no host state: a call may be captured in a HIP graph; the smoothing state is the caller's array).  The NULL
+ * symbol shows what is on the air for 1.3 ms of a frame's 96 ms; an interferer that is silent then (a TDMA neighbour, a gated source)
+ * leaves a flat profile and unweighted bands.  The products behind dabgpu_ofdm_sync_demod_frames_branch carry the noise of the 75 data
+ * symbols themselves: for a carrier with channel power a = |H|^2 and noise power q per bin of the unnormalised transform,
+ * E|d|^2 = (a + q)^2, and while decisions are right the mean of (|re d| + |im d|) / sqrt(2) is a.  The reference has no such code;
+ * this section is the definition.  Per frame, from d_dqpsk [n_frames][75][1536] complex float in carrier order c:
+ *   1 sums        S2[c] = the sum over the 75 products of fma(re, re, im * im), S1[c] = the sum of |re| + |im|: each a sequential chain
+ *                 in symbol order begun at +0, whatever the launch geometry.
+ *   2 carriers    A[c] = S1[c] * k1, k1 the float nearest 1 / (75 sqrt(2)); Q[c] = max(sqrt(S2[c] * k75) - A[c], 0), k75 the float
+ *                 nearest 1 / 75, the root correctly rounded; a NaN gives Q[c] = 0.  Q is in the units of "Noise profile" step 1
+ *                 (white noise of power s2 per sample: E[Q] = 2048 s2).  d_carrier_noise [n_frames][1536] takes Q,
+ *                 d_carrier_amplitude [n_frames][1536] takes A (both optional).
+ *   3 bands       steps 2 to 5 of "Noise profile" with Q in the place of C: d_exclude, d_profile_in, alpha, d_profile_out (may be
+ *                 d_profile_in itself), M, w_b = 1 / max(n_b, M * 2^-20); d_band_weight [n_frames][128], d_mean_noise, d_valid.
+ *   skipped       a frame whose record in d_sync (optional) has sync_valid = 0: its products are stale and none is read; or a frame
+ *                 whose M is not a normal positive finite number.  Outputs are those of "Noise profile: skipped": 0 to every band
+ *                 weight, to d_mean_noise, d_carrier_noise and d_carrier_amplitude, d_valid cleared, d_profile_out = d_profile_in (0
+ *                 without one).
+ * One frame's band value is far steadier than the NULL's (12 carriers x 75 products: relative deviation about 0.04 against 0.29),
+ * and TII carriers do not bias it; the exclusion table remains for carriers known to be bad.  Limits: the estimate under-reads where
+ * decisions fail (q^ / q about 0.98 from 12 dB carrier SNR up, 0.8 at 6 dB, 0.5 at 0 dB, 0.3 at -10 dB) but stays monotone, so a jammed
+ * band still reads far above its neighbours; amplitude that changes within the frame (fast fading) reads as noise; the frame scale
+ * still rests on the power of the phase reference symbol, and under a jammed band A is inflated, so A is no cure for that.
+ * Arithmetic: csrc/dd_profile_core.h; the device equals dabgpu_dd_profile_carriers_host followed by dabgpu_noise_profile_bands_host
+ * and the tests' host model bit for bit. */
+/* What a dabgpu_dd_profile_frames call with these arguments launches; needs no device (no address is dereferenced).
+ * DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null result; a transmission_mode other than 1; n_frames of 0 or
+ * above 2^24; d_dqpsk null or not 16-byte aligned; records, tables or outputs that are not 4-byte aligned, d_carrier_noise or
+ * d_carrier_amplitude not 8-byte aligned; alpha outside (0, 1] (NaN included); d_profile_in and d_profile_out that overlap without
+ * being equal; no output at all (d_valid and d_profile_out count as outputs). */
+int dabgpu_dd_profile_plan(int transmission_mode, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                           const uint32_t *d_exclude, const float *d_profile_in, float alpha, const float *d_profile_out,
+                           const float *d_band_weight, const float *d_mean_noise, const float *d_carrier_noise,
+                           const float *d_carrier_amplitude, const uint32_t *d_valid, dabgpu_noise_geometry *out);
+/* d_dqpsk and d_sync are dabgpu_ofdm_sync_demod_frames_branch's d_dqpsk and records: the call sits behind a branch's demodulation with
+ * no copy.  Every output is optional; d_band_weight can be an entry of dabgpu_diversity_combine_frames_banded's h_band_weight as it is. */
+int dabgpu_dd_profile_frames(dabgpu_ctx *ctx, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                             const uint32_t *d_exclude, const float *d_profile_in, float alpha, float *d_profile_out,
+                             float *d_band_weight, float *d_mean_noise, float *d_carrier_noise, float *d_carrier_amplitude,
+                             uint32_t *d_valid, void *stream);
+/* One frame from host memory, synchronous, on the context's stream: h_dqpsk [75][1536] complex float.  h_exclude [48] or NULL;
+ * h_profile [128] or NULL: the state, read and written in place; h_band_weight [128], h_mean_noise, h_carrier_noise [1536],
+ * h_carrier_amplitude [1536] may be NULL.  Returns DABGPU_OK with *h_valid (may be NULL) 1 or 0. */
+int dabgpu_dd_profile_host_sync(dabgpu_ctx *ctx, const float *h_dqpsk, const uint32_t *h_exclude, float *h_profile, float alpha,
+                                float *h_band_weight, float *h_mean_noise, float *h_carrier_noise, float *h_carrier_amplitude,
+                                uint32_t *h_valid);
+/* steps 1 and 2 on the host (no device): one frame's products [75][1536] complex float -> carrier_noise [1536] and
+ * carrier_amplitude [1536] (either may be NULL).  Followed by dabgpu_noise_profile_bands_host it is the whole definition.
+ * 0, or -1 for null products. */
+int dabgpu_dd_profile_carriers_host(const float *dqpsk, float *carrier_noise, float *carrier_amplitude);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,10 +49,14 @@ relative to the signal power while it is on.  With --blank [THRESHOLD] every rec
 same samples through the impulse blanker (dabgpu.Blanker, dabgpu_blanker_defaults with that threshold, default 3), and every cell reads
 `unblanked -> blanked`; under every table the share of the blocks the blanker zeroed.  The output goes to profiles/tx/waterfall_blank.md.  Both
 options belong to the plain receiver path (not with --branches, --weights, --soft-bits csi, --clock-ppm, --adjacent-db, --doppler-hz or --ber).
+With --weights banded-dd the band weights come from dabgpu_dd_profile_frames on every branch's own DQPSK products in the place of
+the NULL-based profile; the output goes to profiles/tx/waterfall_banded_dd.md.  With --weights banded|banded-dd, --interferer takes the bank's gate:
+--interferer-gate PERIOD:ON:OFFSET then gates the band interferer itself (the library's source: on iff ((m - OFFSET) mod PERIOD) < ON), e.g.
+196608:191952:3656 silences it from 1000 samples in front of every NULL symbol to 1000 behind it.
 Without them the run and its outputs are what they were.
     python tools/waterfall.py [--streams 64] [--frames 6] [--snr 2:15:1] [--out profiles/tx/waterfall.md] [--doppler-hz F] [--profile NAME]
                               [--clock-ppm X[,Y...]] [--adjacent-db A[,B...]] [--adjacent-sides 1|2] [--ber] [--soft-bits csi] [--branches K]
-                              [--branch-noise-db A,B,...] [--weights unit|estimated|true|banded] [--alpha A] [--interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB]
+                              [--branch-noise-db A,B,...] [--weights unit|estimated|true|banded|banded-dd] [--alpha A] [--interferer OFFSET_KHZ:WIDTH_KHZ:IS_DB]
                               [--append] [--interferer-gate PERIOD:ON:IS_DB] [--blank [THRESHOLD]]"""
 import argparse
 import math
@@ -85,7 +89,7 @@ def main():
     ap.add_argument("--soft-level", type=float, default=64.0)
     ap.add_argument("--branches", type=int, default=1)
     ap.add_argument("--branch-noise-db", default=None)
-    ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true", "banded"))
+    ap.add_argument("--weights", default="unit", choices=("unit", "estimated", "true", "banded", "banded-dd"))
     ap.add_argument("--alpha", type=float, default=0.25)
     ap.add_argument("--interferer", default=None)
     ap.add_argument("--interferer-source", default="torch", choices=("torch", "device"))
@@ -95,7 +99,8 @@ def main():
     a = ap.parse_args()
     K = a.branches
     mrc = a.branch_noise_db is not None or a.weights != "unit"
-    banded = a.weights == "banded"
+    banded = a.weights in ("banded", "banded-dd")
+    dd = a.weights == "banded-dd"
     branch_path = K > 1 or banded
     if mrc and K == 1 and not banded:
         ap.error("--branch-noise-db and --weights want --branches K")
@@ -121,7 +126,7 @@ def main():
         if a.clock_ppm is not None or a.adjacent_db is not None or a.ber or a.soft_bits == "csi":
             ap.error("--branches is not available with --clock-ppm, --adjacent-db, --ber or --soft-bits (its branches are weighted already)")
         if a.out == ap.get_default("out"):
-            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_banded.md" if banded else "waterfall_mrc.md" if mrc else "waterfall_diversity.md")
+            a.out = os.path.join(ROOT, "profiles", "tx", "waterfall_banded_dd.md" if dd else "waterfall_banded.md" if banded else "waterfall_mrc.md" if mrc else "waterfall_diversity.md")
     csi = a.soft_bits == "csi"
     if csi and (a.clock_ppm is not None or a.adjacent_db is not None):
         ap.error("--soft-bits csi is not available with --clock-ppm or --adjacent-db")
@@ -143,6 +148,13 @@ def main():
         gate = (int(gate[0]), int(gate[1]), float(gate[2]))
         if not 0 < gate[1] <= gate[0]:
             ap.error("--interferer-gate: 0 < ON <= PERIOD samples")
+    jam_gate = None
+    if gate is not None and jam is not None:
+        # the band interferer behind the bank's own gate: the third field is the gate's offset in samples, the source the library's
+        if not banded or gate[2] != int(gate[2]):
+            ap.error("--interferer with --interferer-gate PERIOD:ON:OFFSET wants --weights banded or banded-dd")
+        jam_gate, gate = dict(gate_period=gate[0], gate_on=gate[1], gate_offset=int(gate[2])), None
+        a.interferer_source = "device"
     blank = a.blank is not None
     if blank or gate is not None:
         if branch_path or mrc or csi or a.clock_ppm is not None or a.adjacent_db is not None or a.doppler_hz is not None or a.ber:
@@ -237,6 +249,8 @@ def main():
             how = {"unit": "no weights (every branch 1)", "estimated": "the weight arrays dabgpu_noise_estimate_frames wrote from every branch's slice and sync records",
                    "banded": f"the band weights dabgpu_noise_profile_frames wrote from every branch's slice and sync records (alpha {a.alpha:g}, the state carried from "
                              "frame to frame), applied by dabgpu_diversity_combine_frames_banded",
+                   "banded-dd": f"the band weights dabgpu_dd_profile_frames wrote from every branch's own DQPSK products and sync records (alpha {a.alpha:g}, the state "
+                                "carried from frame to frame), applied by dabgpu_diversity_combine_frames_banded",
                    "true": "the true weights 1 / (2 noise_sigma^2) of every branch's channel stream"}[a.weights]
             text = [f"# Receive diversity with {'band weights' if banded else 'branches of unequal noise'}: weights {a.weights}", "",
                     f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall_diversity.md` with the branches' noise raised by "
@@ -244,10 +258,11 @@ def main():
                     f"`single -> combined`: branch 0 decoded alone, and the combination, on the SAME received samples.  {E} receivers x {F} mode I frames per point, FIBs of "
                     f"every frame ({E * F * 12} per point), sub-channel bytes of the {4 * F - 15} CIFs from CIF 15 on.  "
                     f"`python tools/waterfall.py --branches {K} --branch-noise-db {','.join(f'{d:g}' for d in branch_db)} --weights {a.weights} --streams {E} --frames {F} "
-                    f"--snr {a.snr}{fading_args}{' --alpha %g' % a.alpha if banded else ''}{' --interferer ' + a.interferer if jam else ''}{' --interferer-source device' if jam and a.interferer_source == 'device' else ''}"
+                    f"--snr {a.snr}{fading_args}{' --alpha %g' % a.alpha if banded else ''}{' --interferer ' + a.interferer if jam else ''}{' --interferer-source device' if jam and a.interferer_source == 'device' and not jam_gate else ''}{' --interferer-gate ' + a.interferer_gate if jam_gate else ''}"
                     f"{' --append' if a.append else ''}`; the verdict line is the combination's."
                     + (f"  Interferer: Gaussian noise {jam[1]:g} kHz wide {jam[0]:+g} kHz from the centre, {jam[2]:+g} dB relative to the signal, a seed per stream; the "
-                       "frame scale rests on the power of the phase reference symbol, interferer included." if jam else ""), ""]
+                       "frame scale rests on the power of the phase reference symbol, interferer included." if jam else "")
+                    + (f"  The interferer is gated: on for {jam_gate['gate_on']} of every {jam_gate['gate_period']} samples from sample {jam_gate['gate_offset']} on." if jam_gate else ""), ""]
     if blank:
         text = ["# Receiver sensitivity with and without the impulse blanker", "",
                 f"Device: AMD Instinct MI355X ({torch.cuda.get_device_properties(0).gcnArchName}).  The run of `waterfall.md` with every receiver run twice on the SAME received "
@@ -303,7 +318,8 @@ def main():
                 shape = dabgpu.interferer_design(jam[1] / 2048.0)
                 amp = math.sqrt(1536.0 * h2 * 10.0 ** (jam[2] / 10.0))
                 itf = dabgpu.Interferer(ctx, [dabgpu.interferer_stream([dabgpu.interferer_source(dabgpu.INTERFERER_BAND, amp=amp, shape=0,
-                                                                                                  cycles_per_sample=jam[0] / 2048.0)], seed=7000 + e)
+                                                                                                  cycles_per_sample=jam[0] / 2048.0, **(jam_gate or {}))],
+                                                                          seed=7000 + e)
                                               for e in range(EC)], [shape])
                 itf.apply(d_rx, n_rx, d_rx, in_stride_samples=n_rows * n_rx, out_stride_bytes=n_rows * n_rx * 8)
                 torch.cuda.synchronize()
@@ -380,7 +396,9 @@ def main():
                                                           bits_frame_stride=H * dabgpu.NB_FRAME_BITS if b == 0 else 0, soft_scale=kb[b])
                         if a.weights == "estimated":
                             ctx.noise_estimate(sl, E, stride, p_lead - NULL, states=d_st[b], weight=wb[b])
-                        if banded:
+                        if dd:
+                            ctx.dd_profile(dq[b], E, sync=d_st[b], profile_in=state[b], alpha=a.alpha, profile_out=state[b], band_weight=bands[b])
+                        elif banded:
                             ctx.noise_profile(sl, E, stride, p_lead - NULL, states=d_st[b], profile_in=state[b], alpha=a.alpha, profile_out=state[b],
                                               band_weight=bands[b])
                     ctx.diversity_combine([(dq[b], kb[b], wb[b], d_st[b]) for b in range(K)], E, rings[1][:, j % H], bits_frame_stride=H * dabgpu.NB_FRAME_BITS,
