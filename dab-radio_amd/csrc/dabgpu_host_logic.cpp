@@ -6,6 +6,7 @@
 #include "noise_core.h"
 #include "noise_profile_core.h"
 #include "dd_profile_core.h"
+#include "sym_profile_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -287,6 +288,31 @@ int dabgpu_dd_profile_carriers_host(const float* dqpsk, float* carrier_noise, fl
     return 0;
 }
 
+int dabgpu_sym_profile_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const float* d_symbol_weight,
+                            const float* d_symbol_noise, const float* d_ref_noise, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
+    if (!out) { dabgpu_set_error("sym_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("sym_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("sym_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_dqpsk) { dabgpu_set_error("sym_profile_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("sym_profile_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_sync | (uintptr_t)d_symbol_weight | (uintptr_t)d_symbol_noise | (uintptr_t)d_ref_noise | (uintptr_t)d_valid) & 3) {
+        dabgpu_set_error("sym_profile_plan: records and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!d_symbol_weight && !d_symbol_noise && !d_ref_noise && !d_valid) {
+        dabgpu_set_error("sym_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
+    }
+    out->grid = (uint32_t)n_frames;
+    out->threads = DABGPU_SYM_PROFILE_THREADS;
+    out->lds_bytes = DABGPU_SYM_PROFILE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_sym_profile_rows_host(const float* dqpsk, float* symbol_weight, float* symbol_noise, float* ref_noise) {
+    if (!dqpsk) return -1;
+    return dabgpu::syp_frame(dqpsk, true, symbol_weight, symbol_noise, ref_noise) ? 1 : 0;
+}
+
 float dabgpu_diversity_band_mean_host(const float band_weight[128]) { return band_weight ? dabgpu::np_branch_weight(band_weight) : 0.0f; }
 
 int dabgpu_diversity_plan_banded(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
@@ -308,6 +334,25 @@ int dabgpu_diversity_plan_banded(const dabgpu_diversity_branch* h_branches, int 
         }
     }
     if (any) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_diversity_plan_symbols(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
+                                  size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
+                                  const float* const* h_symbol_weight, dabgpu_diversity_geometry* out) {
+    const int st = dabgpu_diversity_plan_banded(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
+                                                h_band_weight, out);
+    if (st || !h_symbol_weight) return st;
+    bool any = false;
+    for (int b = 0; b < n_branches; b++) {
+        if (!h_symbol_weight[b]) continue;
+        any = true;
+        if ((uintptr_t)h_symbol_weight[b] & 3) {
+            *out = dabgpu_diversity_geometry{};
+            dabgpu_set_error("diversity_plan_symbols: branch %d: symbol weights must be 4-byte aligned", b); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (any) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;      // the third instantiation keeps the banded one's LDS
     return DABGPU_OK;
 }
 

@@ -254,6 +254,11 @@ int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout,
 #define DABGPU_DD_PROFILE_THREADS 256u
 #define DABGPU_DD_PROFILE_LDS_BYTES (6144u + 8u)
 
+// ---- symbol noise profile (sym_profile.hip launches from dabgpu_sym_profile_plan; include/dabgpu.h) ----
+// one 256-thread workgroup per frame; static LDS: 75 x 4 x 3 wave sums, three rows of 75 figures, three medians
+#define DABGPU_SYM_PROFILE_THREADS 256u
+#define DABGPU_SYM_PROFILE_LDS_BYTES (3600u + 900u + 12u)
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

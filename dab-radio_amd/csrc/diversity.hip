@@ -25,8 +25,12 @@ typedef float dv_f4 __attribute__((ext_vector_type(4)));
 struct dv_table { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; };
 // the banded call's argument: the branch table and, per branch, its band weights [n_frames][128] (null: the branch has a scalar weight)
 struct dv_table_banded { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; const float* band[DV_MAX_BRANCHES]; };
-template <bool BANDED> struct dv_table_of { typedef dv_table type; };
-template <> struct dv_table_of<true> { typedef dv_table_banded type; };
+// the symbol-weighted call's: per branch also its symbol weights [n_frames][75] (null: none)
+struct dv_table_symbols { dabgpu_diversity_branch b[DV_MAX_BRANCHES]; const float* band[DV_MAX_BRANCHES]; const float* sym[DV_MAX_BRANCHES]; };
+enum dv_mode { DV_SCALAR = 0, DV_BANDED = 1, DV_SYMBOLS = 2 };
+template <int MODE> struct dv_table_of { typedef dv_table type; };
+template <> struct dv_table_of<DV_BANDED> { typedef dv_table_banded type; };
+template <> struct dv_table_of<DV_SYMBOLS> { typedef dv_table_symbols type; };
 
 constexpr int DV_DATA_SYMBOLS = 75, DV_CARRIERS = 1536, DV_SYM_BITS = 3072, DV_FIC_SYMBOLS = 3, DV_CIF_SYMBOLS = 18, DV_CIF_BITS = 55296;
 constexpr int DV_ROW_PIECES = DV_CARRIERS / 2;              // 16-byte pieces of a branch's symbol row: 768 = 3 per lane
@@ -35,10 +39,12 @@ static_assert(DV_ROW_PIECES == 3 * (int)DABGPU_DIVERSITY_THREADS && DV_SYM_BITS 
 // BANDED (include/dabgpu.h, "Banded receive diversity"): a branch with a band table takes the tree mean of the frame's 128 band weights
 // for its weight -- lanes 0 .. 127 hold one band each, the two wave sums meet in LDS -- and every lane keeps the band weights of its three
 // pieces (carriers 2 (t + 256 j), + 1: band (t + 256 j) / 6) in registers for all symbols of the run.  The first instantiation is the
-// kernel as it was.
-template <bool BANDED>
+// kernel as it was.  DV_SYMBOLS (include/dabgpu.h, "Symbol-weighted receive diversity") is the banded instantiation with one more factor:
+// a branch with a symbol table multiplies the piece's weight by the clean weight of the row, one uniform load per branch and row, the
+// product rounded once.  Symbol weights enter neither the live rule nor the scale.
+template <int MODE>
 __global__ __launch_bounds__(DABGPU_DIVERSITY_THREADS)
-void diversity_combine_kernel(const typename dv_table_of<BANDED>::type tab, const int n_branches, const int n_frames, const int sym_per_run, const int runs_per_frame,
+void diversity_combine_kernel(const typename dv_table_of<MODE>::type tab, const int n_branches, const int n_frames, const int sym_per_run, const int runs_per_frame,
                               int8_t* __restrict__ bits, const size_t bits_frame_stride, const int classed, const uint16_t* __restrict__ inv_map,
                               float* __restrict__ soft_scale, uint32_t* __restrict__ live_mask)
 {
@@ -46,6 +52,7 @@ void diversity_combine_kernel(const typename dv_table_of<BANDED>::type tab, cons
     const int t = threadIdx.x;
     const int frame = blockIdx.x / runs_per_frame, run = blockIdx.x % runs_per_frame;
     if (frame >= n_frames) return;
+    constexpr bool BANDED = MODE != DV_SCALAR;
     const int row0 = run * sym_per_run, row1 = min(row0 + sym_per_run, DV_DATA_SYMBOLS);
 
     // ---- the frame's live branches and its scale (uniform) ----
@@ -114,7 +121,15 @@ void diversity_combine_kernel(const typename dv_table_of<BANDED>::type tab, cons
                 const dv_f4 v0 = p[0], v1 = p[256], v2 = p[512];
                 const dv_f4 v[3] = {v0, v1, v2};
                 // the weight of piece j: the branch's, or (BANDED) the one of the piece's band
-                auto wj = [&](int j) __attribute__((always_inline)) { if constexpr (BANDED) return wl[b][j]; else return w[b]; };
+                float ws = 1.0f;
+                if constexpr (MODE == DV_SYMBOLS) {
+                    if (tab.sym[b] != nullptr) ws = np_clean_weight(tab.sym[b][(size_t)frame * DV_DATA_SYMBOLS + (size_t)row]);   // (uniform)
+                }
+                auto wj = [&](int j) __attribute__((always_inline)) {
+                    if constexpr (MODE == DV_SYMBOLS) return wl[b][j] * ws;
+                    else if constexpr (BANDED) return wl[b][j];
+                    else return w[b];
+                };
                 if (first) {
 #pragma unroll
                     for (int j = 0; j < 3; j++)
@@ -178,7 +193,7 @@ int dabgpu_diversity_combine_frames(dabgpu_ctx* c, const dabgpu_diversity_branch
     dv_table tab;
     memset(&tab, 0, sizeof(tab));
     for (int b = 0; b < n_branches; b++) tab.b[b] = h_branches[b];
-    hipLaunchKernelGGL(diversity_combine_kernel<false>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+    hipLaunchKernelGGL(diversity_combine_kernel<DV_SCALAR>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
                        (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
                        bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
     return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel launch");
@@ -205,7 +220,7 @@ int dabgpu_diversity_combine_frames_banded(dabgpu_ctx* c, const dabgpu_diversity
     dv_table_banded tab;
     memset(&tab, 0, sizeof(tab));
     for (int b = 0; b < n_branches; b++) { tab.b[b] = h_branches[b]; tab.band[b] = h_band_weight[b]; }
-    hipLaunchKernelGGL(diversity_combine_kernel<true>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+    hipLaunchKernelGGL(diversity_combine_kernel<DV_BANDED>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
                        (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
                        bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
     return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel (banded) launch");
@@ -303,6 +318,103 @@ int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx* c, const float* const*
     float* const d_k = d_small + 2 * K;
     uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
     if ((st = dabgpu_diversity_combine_frames_banded(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, s))) return st;
+    uint32_t back[2];
+    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
+    DABGPU_CK(hipStreamSynchronize(s));
+    if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
+    if (h_live_mask) *h_live_mask = back[1];
+    return DABGPU_OK;
+}
+
+int dabgpu_diversity_combine_frames_symbols(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                                            size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale,
+                                            uint32_t* d_live_mask, const float* const* h_band_weight, const float* const* h_symbol_weight,
+                                            void* stream) {
+    if (!c) { dabgpu_set_error("diversity_combine_frames_symbols: null context"); return DABGPU_ERR_INVALID_ARG; }
+    dabgpu_diversity_geometry g;
+    int st = dabgpu_diversity_plan_symbols(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight,
+                                           h_symbol_weight, &g);
+    if (st) return st;
+    // no symbol table at all: the banded call, exactly
+    bool any = false;
+    for (int b = 0; h_symbol_weight && b < n_branches; b++) any = any || h_symbol_weight[b] != nullptr;
+    if (!any)
+        return dabgpu_diversity_combine_frames_banded(c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
+                                                      d_soft_scale, d_live_mask, h_band_weight, stream);
+    if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
+        dabgpu_set_error("diversity_combine_frames_symbols: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (n_frames == 0) return DABGPU_OK;
+    DABGPU_BIND(c);
+    const dabgpu_mode_tables* t;
+    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames_symbols"))) return st;
+    dv_table_symbols tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int b = 0; b < n_branches; b++) {
+        tab.b[b] = h_branches[b];
+        tab.band[b] = h_band_weight ? h_band_weight[b] : nullptr;
+        tab.sym[b] = h_symbol_weight[b];
+    }
+    hipLaunchKernelGGL(diversity_combine_kernel<DV_SYMBOLS>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
+                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
+    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel (symbols) launch");
+}
+
+int dabgpu_diversity_combine_symbols_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight,
+                                               const int* h_valid, int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale,
+                                               uint32_t* h_live_mask, const float* const* h_band_weight, const float* const* h_symbol_weight) {
+    if (!h_symbol_weight)
+        return dabgpu_diversity_combine_banded_host_sync(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale,
+                                                         h_live_mask, h_band_weight);
+    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_symbols_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
+        dabgpu_set_error("diversity_combine_symbols_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    int st = dabgpu_check_bits_layout("diversity_combine_symbols_host_sync", bits_layout);
+    if (st) return st;
+    // as the banded form: what the kernel will find live decides which products are uploaded (symbol weights have no say in that)
+    constexpr int K = DABGPU_DIVERSITY_MAX_BRANCHES;
+    float small[2 * K];
+    for (int b = 0; b < n_branches; b++) {
+        const bool banded = h_band_weight && h_band_weight[b];
+        const float w = banded ? np_branch_weight(h_band_weight[b]) : (h_weight ? h_weight[b] : 1.0f);
+        const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
+        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_symbols_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
+        small[b] = live ? h_scale[b] : 0.0f;
+        small[K + b] = w;
+    }
+    DABGPU_BIND(c);
+    DABGPU_HOST_LOCK(c);
+    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
+    float *d_dq, *d_small; int8_t* d_bits;
+    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * K + 2 + K * NP_BANDS + K * DV_DATA_SYMBOLS) * sizeof(float), (void**)&d_small))) return st;
+    hipStream_t s = c->stream;
+    dabgpu_diversity_branch br[K];
+    const float *band[K], *sym[K];
+    float* const d_band = d_small + 2 * K + 2;
+    float* const d_sym = d_band + (size_t)K * NP_BANDS;
+    for (int b = 0; b < n_branches; b++) {
+        const bool banded = h_band_weight && h_band_weight[b];
+        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
+        br[b].d_scale = d_small + b;
+        br[b].d_weight = banded ? nullptr : d_small + K + b;
+        br[b].d_sync = nullptr;
+        band[b] = banded ? d_band + (size_t)b * NP_BANDS : nullptr;
+        sym[b] = h_symbol_weight[b] ? d_sym + (size_t)b * DV_DATA_SYMBOLS : nullptr;
+        if (banded) DABGPU_CK(hipMemcpyAsync(d_band + (size_t)b * NP_BANDS, h_band_weight[b], NP_BANDS * sizeof(float), hipMemcpyHostToDevice, s));
+        if (h_symbol_weight[b])
+            DABGPU_CK(hipMemcpyAsync(d_sym + (size_t)b * DV_DATA_SYMBOLS, h_symbol_weight[b], DV_DATA_SYMBOLS * sizeof(float), hipMemcpyHostToDevice, s));
+        if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
+    float* const d_k = d_small + 2 * K;
+    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
+    if ((st = dabgpu_diversity_combine_frames_symbols(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, sym, s))) return st;
     uint32_t back[2];
     DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));

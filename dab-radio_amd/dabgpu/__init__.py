@@ -101,6 +101,8 @@ ABI_SYMBOLS = [
     "dabgpu_noise_profile_exclude_tii", "dabgpu_diversity_plan_banded", "dabgpu_diversity_combine_frames_banded",
     "dabgpu_diversity_combine_banded_host_sync", "dabgpu_diversity_band_mean_host",
     "dabgpu_dd_profile_plan", "dabgpu_dd_profile_frames", "dabgpu_dd_profile_host_sync", "dabgpu_dd_profile_carriers_host",
+    "dabgpu_sym_profile_plan", "dabgpu_sym_profile_frames", "dabgpu_sym_profile_host_sync", "dabgpu_sym_profile_rows_host",
+    "dabgpu_diversity_plan_symbols", "dabgpu_diversity_combine_frames_symbols", "dabgpu_diversity_combine_symbols_host_sync",
     "dabgpu_interferer_design", "dabgpu_interferer_plan", "dabgpu_interferer_bank_create", "dabgpu_interferer_bank_destroy",
     "dabgpu_interferer_bank_set_params", "dabgpu_interferer_bank_seek", "dabgpu_interferer_bank_apply", "dabgpu_interferer_bank_apply_host_sync",
     "dabgpu_blanker_defaults", "dabgpu_blanker_mask_words", "dabgpu_blanker_plan", "dabgpu_blanker_input_needed", "dabgpu_blanker_bank_create",
@@ -108,6 +110,7 @@ ABI_SYMBOLS = [
     "dabgpu_blanker_bank_apply_host_sync",
 ]
 NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
+SYM_PROFILE_SYMBOLS = 75                  # symbol noise profile: product rows of a mode I frame
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 DIVERSITY_MAX_BRANCHES = 8                # receive diversity (include/dabgpu.h)
 NOISE_RECORD_DTYPE = [("noise_power", "<f4"), ("signal_power", "<f4"), ("weight", "<f4"), ("snr", "<f4"), ("valid", "<u4")]   # dabgpu_noise_record
@@ -476,6 +479,16 @@ def lib():
                                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_diversity_band_mean_host.argtypes = [C.c_void_p]
         L.dabgpu_diversity_band_mean_host.restype = C.c_float
+        L.dabgpu_sym_profile_plan.argtypes = [C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
+        L.dabgpu_sym_profile_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
+        L.dabgpu_sym_profile_host_sync.argtypes = [C.c_void_p] * 6
+        L.dabgpu_sym_profile_rows_host.argtypes = [C.c_void_p] * 4
+        L.dabgpu_diversity_plan_symbols.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
+        L.dabgpu_diversity_combine_frames_symbols.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_diversity_combine_symbols_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_ofdm_sync_demod_frames_branch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p]
@@ -909,12 +922,21 @@ class Context:
                                                          self._stream(stream)), "dabgpu_ofdm_sync_demod_frames_branch")
 
     def diversity_combine(self, branches, n_frames, bits, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0, soft_scale=None,
-                          live_mask=None, stream=None, band_weights=None):
+                          live_mask=None, stream=None, band_weights=None, symbol_weights=None):
         """receive diversity: `branches` = up to 8 of (dqpsk, scale[, weight[, sync]]) device buffers (or DiversityBranch records) of the same
         n_frames frames -> their combined soft bits in `bits`; soft_scale [n_frames] float32 and live_mask [n_frames] uint32 on the device
         receive the scale used and the live branches.  One kernel launch, no copy: capturable.  band_weights = one entry per branch, a
-        device buffer [n_frames][128] of band weights (Context.noise_profile's) or None: dabgpu_diversity_combine_frames_banded"""
+        device buffer [n_frames][128] of band weights (Context.noise_profile's) or None: dabgpu_diversity_combine_frames_banded.
+        symbol_weights = one entry per branch, a device buffer [n_frames][75] of symbol weights (Context.sym_profile's) or None:
+        dabgpu_diversity_combine_frames_symbols"""
         table = diversity_table(branches)
+        if symbol_weights is not None:
+            bands = None if band_weights is None else band_weight_table(band_weights, len(table))
+            syms = band_weight_table(symbol_weights, len(table), "symbol_weights")
+            check(lib().dabgpu_diversity_combine_frames_symbols(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                                                int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), bands, syms,
+                                                                self._stream(stream)), "dabgpu_diversity_combine_frames_symbols")
+            return
         if band_weights is not None:
             bands = band_weight_table(band_weights, len(table))
             check(lib().dabgpu_diversity_combine_frames_banded(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
@@ -925,12 +947,31 @@ class Context:
                                                     int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), self._stream(stream)),
               "dabgpu_diversity_combine_frames")
 
-    def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL, band_weights=None):
+    def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL, band_weights=None, symbol_weights=None):
         """numpy convenience over dabgpu_diversity_combine_host_sync: one frame; dqpsk = a list of [75][1536] complex64 arrays (None where the
         branch is not live); returns (bits [230400] int8, scale, live mask).  band_weights = one [128] float32 array or None per branch:
-        dabgpu_diversity_combine_banded_host_sync"""
+        dabgpu_diversity_combine_banded_host_sync; symbol_weights = one [75] float32 array or None per branch:
+        dabgpu_diversity_combine_symbols_host_sync"""
         import numpy as np
         n = len(dqpsk)
+        if symbol_weights is not None:
+            if len(symbol_weights) != n or (band_weights is not None and len(band_weights) != n):
+                raise ValueError("diversity_combine_host: one band_weights and one symbol_weights entry per branch")
+            keep_w = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(NOISE_PROFILE_BANDS) for x in (band_weights or [None] * n)]
+            keep_s = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(SYM_PROFILE_SYMBOLS) for x in symbol_weights]
+            bands = None if band_weights is None else (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_w])
+            syms = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_s])
+            keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
+            ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
+            k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
+            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
+            v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+            bits = np.empty(NB_FRAME_BITS, np.int8)
+            out_k, out_m = C.c_float(0.0), C.c_uint32(0)
+            check(lib().dabgpu_diversity_combine_symbols_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits),
+                                                                   C.byref(out_k), C.byref(out_m), bands, syms),
+                  "dabgpu_diversity_combine_symbols_host_sync")
+            return bits, out_k.value, out_m.value
         if band_weights is not None:
             if len(band_weights) != n:
                 raise ValueError("diversity_combine_host: one band_weights entry per branch")
@@ -1018,6 +1059,24 @@ class Context:
         check(lib().dabgpu_dd_profile_host_sync(self._h, _ptr(x), _ptr(ex), _ptr(profile), float(alpha), _ptr(bw), C.byref(mean), _ptr(q), _ptr(a),
                                                 C.byref(ok)), "dabgpu_dd_profile_host_sync")
         return (bw, mean.value, ok.value) + ((q, a) if carriers else ())
+
+    def sym_profile(self, dqpsk, n_frames, sync=None, symbol_weight=None, symbol_noise=None, ref_noise=None, valid=None, stream=None):
+        """the symbol noise profile of n_frames frames (include/dabgpu.h, "Symbol noise profile"): dqpsk [n_frames][75][1536] complex64 and
+        sync the records of ofdm_sync_demod_frames_branch; symbol_weight [n_frames][75] float32 (an entry of diversity_combine's
+        symbol_weights as it is), symbol_noise [n_frames][75], ref_noise [n_frames], valid [n_frames] uint32; every output optional.  One
+        kernel launch, no copy: capturable"""
+        check(lib().dabgpu_sym_profile_frames(self._h, _ptr(dqpsk), n_frames, _ptr(sync), _ptr(symbol_weight), _ptr(symbol_noise), _ptr(ref_noise),
+                                              _ptr(valid), self._stream(stream)), "dabgpu_sym_profile_frames")
+
+    def sym_profile_host(self, dqpsk):
+        """numpy convenience over dabgpu_sym_profile_host_sync: one frame's products [75][1536] complex64 -> (symbol weights [75], symbol
+        noise [75], reference noise, valid)"""
+        import numpy as np
+        x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(SYM_PROFILE_SYMBOLS * NB_CARRIERS)
+        v, q = np.zeros(SYM_PROFILE_SYMBOLS, np.float32), np.zeros(SYM_PROFILE_SYMBOLS, np.float32)
+        ref, ok = C.c_float(0.0), C.c_uint32(0)
+        check(lib().dabgpu_sym_profile_host_sync(self._h, _ptr(x), _ptr(v), _ptr(q), C.byref(ref), C.byref(ok)), "dabgpu_sym_profile_host_sync")
+        return v, q, ref.value, ok.value
 
     def noise_estimate_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0):
         """numpy convenience over dabgpu_noise_estimate_host_sync: one frame's NULL and phase reference symbol out of complex64 samples ->
@@ -2275,11 +2334,45 @@ def noise_plan(iq, n_frames, stream_stride_samples, null_offset_samples, states=
     return g
 
 
-def band_weight_table(band_weights, n_branches):
+def band_weight_table(band_weights, n_branches, what="band_weights"):
     """a ctypes array of n_branches device addresses from buffers / addresses / None (a branch without a band table)"""
     if len(band_weights) != n_branches:
-        raise ValueError("band_weights: one entry (a buffer or None) per branch")
+        raise ValueError(f"{what}: one entry (a buffer or None) per branch")
     return (C.c_void_p * n_branches)(*[getattr(_ptr(x), "value", None) for x in band_weights])
+
+
+def diversity_plan_symbols(branches, n_frames, bits, band_weights, symbol_weights, bits_frame_stride=0, bits_layout=BITS_NATURAL,
+                           symbols_per_block=0):
+    """dabgpu_diversity_plan_symbols (host only, nothing is dereferenced): the DiversityGeometry of a diversity_combine call with
+    band_weights and symbol_weights (either None: no such table at all); DabGpuError with the reason when refused"""
+    table = diversity_table(branches)
+    g = DiversityGeometry()
+    bands = None if band_weights is None else band_weight_table(band_weights, len(table))
+    syms = None if symbol_weights is None else band_weight_table(symbol_weights, len(table), "symbol_weights")
+    check(lib().dabgpu_diversity_plan_symbols(table if len(table) else None, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
+                                              int(symbols_per_block), bands, syms, C.byref(g)), "dabgpu_diversity_plan_symbols")
+    return g
+
+
+def sym_profile_plan(dqpsk, n_frames, sync=None, symbol_weight=None, symbol_noise=None, ref_noise=None, valid=None, mode=1):
+    """dabgpu_sym_profile_plan (host only, nothing is dereferenced): the NoiseGeometry of a sym_profile call with these arguments; raises
+    DabGpuError with the reason where that call would be refused"""
+    g = NoiseGeometry()
+    check(lib().dabgpu_sym_profile_plan(int(mode), _ptr(dqpsk), n_frames, _ptr(sync), _ptr(symbol_weight), _ptr(symbol_noise), _ptr(ref_noise),
+                                        _ptr(valid), C.byref(g)), "dabgpu_sym_profile_plan")
+    return g
+
+
+def sym_profile_rows_host(dqpsk):
+    """the symbol noise profile on the host (no device): one frame's products [75][1536] complex64 -> (symbol weights [75], symbol noise
+    [75], reference noise, valid)"""
+    import numpy as np
+    x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(SYM_PROFILE_SYMBOLS * NB_CARRIERS)
+    v, q, ref = np.zeros(SYM_PROFILE_SYMBOLS, np.float32), np.zeros(SYM_PROFILE_SYMBOLS, np.float32), C.c_float(0.0)
+    st = lib().dabgpu_sym_profile_rows_host(_ptr(x), _ptr(v), _ptr(q), C.byref(ref))
+    if st < 0:
+        raise DabGpuError("dabgpu_sym_profile_rows_host: null products")
+    return v, q, ref.value, st
 
 
 def diversity_plan_banded(branches, n_frames, bits, band_weights, bits_frame_stride=0, bits_layout=BITS_NATURAL, symbols_per_block=0):

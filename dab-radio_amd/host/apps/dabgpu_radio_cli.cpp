@@ -53,6 +53,14 @@
 // the profile's place: the band weights come from the delivered frame's own products (GetFrameDataVec()), not from the NULL behind it, so an
 // interferer that is silent during the NULL symbol (gated, TDMA) is still weighted down.  Options and restrictions are banded's.
 //
+// --symbol-weights (include/dabgpu.h "Symbol noise profile", "Symbol-weighted receive diversity"; with --soft-bits csi, banded or banded-dd):
+// the delivered frame's own products (GetFrameDataVec()) go to DAB_Symbol_Profile::Update, and its 75 symbol weights to
+// DAB_Diversity_Combiner::Combine on top of what the policy gives: under csi the frame goes through the one-branch combiner with no band
+// table, under banded and banded-dd the weights join the band weights (a frame whose band profile is not valid still takes the symbol
+// weights alone).  A frame whose symbol profile is not valid is treated as without the flag.  This answers wideband bursts of a symbol or
+// longer; FIC symbols under a burst stay lost.  Refused with --soft-bits normalised: that policy divides every product by its own
+// amplitude, which is what the weights act on.
+//
 // --blank [THRESHOLD] (not in the reference; include/dabgpu.h "Impulse blanker"): every block of samples at 2.048 MHz -- behind --input-rate
 // and --channel-offset-hz -- goes through a DAB_Stream_Blanker with dabgpu_blanker_defaults() (threshold 3 unless given) in front of
 // OFDM_Demod, which so runs 800 samples behind the input; the rest is flushed at the end of the input.  One "blank blocks=N of M" line
@@ -99,6 +107,7 @@
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
 #include "ofdm/dab_dd_profile.h"
+#include "ofdm/dab_symbol_profile.h"
 #include "ofdm/dab_noise_profile.h"
 #include "ofdm/dab_diversity_combiner.h"
 
@@ -128,6 +137,7 @@ struct Args {
     float soft_level = 64.0f;
     bool soft_level_given = false;
     bool soft_banded = false;
+    bool symbol_weights = false;                     // --symbol-weights: DAB_Symbol_Profile's weights into the one-branch combiner
     bool soft_banded_dd = false;                     // (with soft_banded: the decision-directed profile in the NULL-based one's place)
     float alpha = 0.25f;
     bool alpha_given = false;
@@ -143,7 +153,7 @@ static void usage(const char* argv0) {
         "  [--radio-input-hard-bytes] [--radio-fib-output FILE]\n"
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
-        "  [--soft-bits normalised|csi|banded|banded-dd] [--soft-level 1..127] [--alpha A] [--blank [THRESHOLD]]\n"
+        "  [--soft-bits normalised|csi|banded|banded-dd] [--soft-level 1..127] [--alpha A] [--symbol-weights] [--blank [THRESHOLD]]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -216,6 +226,7 @@ static bool parse_args(int argc, char** argv, Args& args) {
             else if (p == "banded-dd") { args.soft_policy = DABGPU_SOFT_CSI; args.soft_banded = true; args.soft_banded_dd = true; }
             else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised, csi, banded or banded-dd)");
         }
+        else if (a == "--symbol-weights") args.symbol_weights = true;
         else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
         else if (a == "--blank") {
@@ -238,6 +249,9 @@ static bool parse_args(int argc, char** argv, Args& args) {
     if (args.soft_policy != DABGPU_SOFT_NORMALISED && !args.is_ofdm_used) throw std::runtime_error("--soft-bits needs the OFDM stage");
     if (args.soft_level_given && args.soft_policy != DABGPU_SOFT_CSI) throw std::runtime_error("--soft-level needs --soft-bits csi");
     if (!(args.soft_level >= 1.0f && args.soft_level <= 127.0f)) throw std::runtime_error("--soft-level: a level from 1 to 127");
+    if (args.symbol_weights && args.soft_policy != DABGPU_SOFT_CSI)
+        throw std::runtime_error("--symbol-weights needs --soft-bits csi, banded or banded-dd: the normalised policy divides every product by its own amplitude, "
+                                 "which is what the weights act on");
     if (args.alpha_given && !args.soft_banded) throw std::runtime_error("--alpha needs --soft-bits banded");
     if (!(args.alpha > 0.0f && args.alpha <= 1.0f)) throw std::runtime_error("--alpha: above 0, up to 1");
     if (args.soft_banded && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--soft-bits banded: --ofdm-block-size may not exceed 193952");
@@ -417,6 +431,12 @@ static int run(const Args& args) {
         if (args.soft_banded) {
             if (args.soft_banded_dd) { dd_profile = std::make_unique<DAB_DD_Profile>(); dd_profile->SetAlpha(args.alpha); }
             else { profile = std::make_unique<DAB_Noise_Profile>(); profile->SetAlpha(args.alpha); }
+        }
+        // --symbol-weights: the profile of the frame's product rows; its weights join the band weights, or go alone
+        std::unique_ptr<DAB_Symbol_Profile> sym_profile;
+        size_t sym_frames = 0, sym_kept = 0;
+        if (args.symbol_weights) sym_profile = std::make_unique<DAB_Symbol_Profile>();
+        if (args.soft_banded || args.symbol_weights) {
             combiner = std::make_unique<DAB_Diversity_Combiner>(1);
             banded_bits.resize(DABGPU_NB_FRAME_BITS);
             demod->EnableDebugBuffers(true);                                         // the products of every frame, from the first
@@ -442,22 +462,31 @@ static int run(const Args& args) {
         };
         demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> demod_bits) {
             tcb::span<const viterbi_bit_t> bits = demod_bits;
-            if (profile || dd_profile) {
-                if (demod->GetTotalFramesDesync() != banded_desync) {
+            if (profile || dd_profile || sym_profile) {
+                if ((profile || dd_profile) && demod->GetTotalFramesDesync() != banded_desync) {
                     banded_desync = demod->GetTotalFramesDesync();
                     if (profile) profile->Reset(); else dd_profile->Reset();
                 }
-                float w[DABGPU_NOISE_PROFILE_BANDS];
+                float w[DABGPU_NOISE_PROFILE_BANDS], v[DABGPU_SYM_PROFILE_SYMBOLS];
                 // (the buffer has the reference's size, 75 x 2048; the products are its first 75 x 1536)
                 const tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
+                const bool banded = (profile || dd_profile) &&
+                                    (profile ? (profile->Update(demod->GetCorrelationTimeBuffer().first(2656), 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid())
+                                             : (dd_profile->Update(products[0], w) && dd_profile->IsValid()));
+                const bool weighted = sym_profile && sym_profile->Update(products[0], v) && sym_profile->IsValid();
+                const tcb::span<const float> band_weights[1] = {{w, (size_t)DABGPU_NOISE_PROFILE_BANDS}};
+                const tcb::span<const float> symbol_weights[1] = {{v, (size_t)DABGPU_SYM_PROFILE_SYMBOLS}};
+                const float scale[1] = {demod->GetSoftScale()};
                 bool combined = false;
-                if (profile ? (profile->Update(demod->GetCorrelationTimeBuffer().first(2656), 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid())
-                            : (dd_profile->Update(products[0], w) && dd_profile->IsValid())) {
-                    const tcb::span<const float> band_weights[1] = {{w, (size_t)DABGPU_NOISE_PROFILE_BANDS}};
-                    const float scale[1] = {demod->GetSoftScale()};
+                if (weighted)
+                    combined = combiner->Combine(products, scale, tcb::span<const float>(),
+                                                 banded ? tcb::span<const tcb::span<const float>>(band_weights) : tcb::span<const tcb::span<const float>>(),
+                                                 symbol_weights, banded_bits);
+                else if (banded)
                     combined = combiner->Combine(products, scale, tcb::span<const float>(), band_weights, banded_bits);
-                }
-                if (combined) { bits = banded_bits; banded_frames++; } else banded_kept++;
+                if (combined) bits = banded_bits;
+                if (profile || dd_profile) { if (combined && banded) banded_frames++; else banded_kept++; }
+                if (sym_profile) { if (combined && weighted) sym_frames++; else sym_kept++; }
             }
             if (snr) {
                 if (demod->GetTotalFramesDesync() != snr_desync) { snr_desync = demod->GetTotalFramesDesync(); snr_since_acquisition = 0; }
@@ -553,6 +582,7 @@ static int run(const Args& args) {
         fprintf(stderr, "ofdm: frames_read=%d frames_desync=%d coarse=%.6g fine=%.6g\n", demod->GetTotalFramesRead(),
                 demod->GetTotalFramesDesync(), demod->GetCoarseFrequencyOffset(), demod->GetFineFrequencyOffset());
         if (profile || dd_profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
+        if (sym_profile) fprintf(stderr, "symbols: frames_weighted=%zu frames_kept=%zu\n", sym_frames, sym_kept);
         if (blanker) fprintf(stderr, "blank blocks=%llu of %llu\n", (unsigned long long)blanker->BlankedBlocks(), (unsigned long long)blanker->TotalBlocks());
     } else {
         std::vector<viterbi_bit_t> bits(radio->frame_bits());                         // Basic_Radio_Block::run, app_radio_blocks.h:31-38

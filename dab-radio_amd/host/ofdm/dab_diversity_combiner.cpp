@@ -48,3 +48,27 @@ bool DAB_Diversity_Combiner::Combine(tcb::span<const tcb::span<const std::comple
     if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Diversity_Combiner: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
     return true;
 }
+
+bool DAB_Diversity_Combiner::Combine(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales,
+                                     tcb::span<const float> weights, tcb::span<const tcb::span<const float>> band_weights,
+                                     tcb::span<const tcb::span<const float>> symbol_weights, tcb::span<viterbi_bit_t> out_bits) {
+    const size_t n = (size_t)m_nb_branches, frame = (size_t)(DABGPU_NB_FRAME_SYMBOLS - 1) * DABGPU_NB_DATA_CARRIERS;
+    if (products.size() != n || scales.size() != n || (!weights.empty() && weights.size() != n) || (!band_weights.empty() && band_weights.size() != n) ||
+        symbol_weights.size() != n || out_bits.size() != DABGPU_NB_FRAME_BITS)
+        return false;
+    const float *ptr[DABGPU_DIVERSITY_MAX_BRANCHES], *band[DABGPU_DIVERSITY_MAX_BRANCHES], *sym[DABGPU_DIVERSITY_MAX_BRANCHES];
+    int valid[DABGPU_DIVERSITY_MAX_BRANCHES];
+    for (size_t b = 0; b < n; b++) {
+        if (!products[b].empty() && products[b].size() != frame) return false;
+        if (!band_weights.empty() && !band_weights[b].empty() && band_weights[b].size() != DABGPU_NOISE_PROFILE_BANDS) return false;
+        if (!symbol_weights[b].empty() && symbol_weights[b].size() != DABGPU_SYM_PROFILE_SYMBOLS) return false;
+        valid[b] = products[b].empty() ? 0 : 1;
+        ptr[b] = products[b].empty() ? nullptr : reinterpret_cast<const float*>(products[b].data());
+        band[b] = (band_weights.empty() || band_weights[b].empty()) ? nullptr : band_weights[b].data();
+        sym[b] = symbol_weights[b].empty() ? nullptr : symbol_weights[b].data();
+    }
+    const int st = dabgpu_diversity_combine_symbols_host_sync(m_ctx, ptr, scales.data(), weights.empty() ? nullptr : weights.data(), valid, m_nb_branches,
+                                                              m_layout, out_bits.data(), &m_scale, &m_live_mask, band_weights.empty() ? nullptr : band, sym);
+    if (st != DABGPU_OK) throw std::runtime_error(std::string("DAB_Diversity_Combiner: ") + dabgpu_strerror(st) + " -- " + dabgpu_last_error());
+    return true;
+}

@@ -28,6 +28,12 @@ public:
     // branch with a table weights[b] is not looked at.  false for wrong sizes.
     bool Combine(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales, tcb::span<const float> weights,
                  tcb::span<const tcb::span<const float>> band_weights, tcb::span<viterbi_bit_t> out_bits);
+    // the same with symbol weights on top (include/dabgpu.h, "Symbol-weighted receive diversity"): symbol_weights[b] = the 75 symbol
+    // weights of branch b's frame (DAB_Symbol_Profile::Update's) or an empty span for a branch without them; band_weights as above, or an
+    // empty span of spans for no band table at all.  false for wrong sizes.
+    bool Combine(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales, tcb::span<const float> weights,
+                 tcb::span<const tcb::span<const float>> band_weights, tcb::span<const tcb::span<const float>> symbol_weights,
+                 tcb::span<viterbi_bit_t> out_bits);
     void SetBitsLayout(int bits_layout) { m_layout = bits_layout; }
     float GetScale() const { return m_scale; }              // k of the last frame combined (0: erased)
     uint32_t GetLiveMask() const { return m_live_mask; }    // bit b: branch b took part in it

@@ -2158,6 +2158,79 @@ int dabgpu_dd_profile_host_sync(dabgpu_ctx *ctx, const float *h_dqpsk, const uin
  * 0, or -1 for null products. */
 int dabgpu_dd_profile_carriers_host(const float *dqpsk, float *carrier_noise, float *carrier_amplitude);
 
+/* ------------------------------------------------------------------------------------------------
+ * Symbol noise profile: one noise figure and one relative weight per DQPSK product row of a frame (mode I; batched, one kernel launch
+ * per call, no host state and no smoothing: a call may be captured in a HIP graph).  A wideband burst that lasts an OFDM symbol or
+ * longer escapes the other defences: the blanker's neighbourhood rises with it, the NULL profile hears it only on the NULL, and the
+ * decision-directed profile averages every carrier over the frame, so all bands rise alike.  Here the sums run over the 1536 carriers
+ * of one row.  The reference has no such code; this section is the definition.  Per frame, from d_dqpsk [n_frames][75][1536] complex
+ * float in carrier order, per row s = 0 .. 74:
+ *   1 sums        S1 = sum of |re| + |im|, SD = sum of (|re| - |im|)^2, S2 = sum of fma(re, re, im * im) over the row's carriers.
+ *                 Order: owner t = 0 .. 255 chains the carriers 2 p, 2 p + 1 of p = t, t + 256, t + 512 from +0; owners
+ *                 64 w .. 64 w + 63 meet in the wavefront tree of "Noise profile" step 5; the four sums join as (p0 + p1) + (p2 + p3).
+ *   2 quadrature  folded into the first quadrant, the component of a product across the decision diagonal has variance a q + q^2 / 2
+ *                 (a channel power, q noise power per bin).  P = S1 * r2 (r2 the float nearest 1 / sqrt 2) stands for the sum of a:
+ *                 768 q^2 + P q - SD / 2 = 0, qa = max((sqrt(fma(1536, SD, P * P)) - P) * k1536, 0), k1536 the float nearest
+ *                 1 / 1536, the root correctly rounded.  Units of "Noise profile" step 1: white noise of power s2 per sample reads
+ *                 as 2048 s2.
+ *   3 power       qa saturates where decisions fail; R = sqrt(S2 * k1536) = a + q does not.
+ *                 q_s = max(qa_s, med(qa) + (R_s - med(R))), med the 38th smallest of the 75 values (rank counting, ties by row index).
+ *   4 weights     q_ref = med(q); v_s = 1 where q_s <= q_ref, else min(1, q_ref * (1 / max(q_s, q_ref * 2^-20))), the reciprocal that
+ *                 of "Receive diversity".  Relative weights: exactly 1 for at least 38 rows of a valid frame.
+ *   bad rows      a row whose S2 * k1536 or discriminant is not finite (a NaN or an infinity among its products, an overflow) has
+ *                 qa = R = q = +infinity: it ranks last in every median, v_s = 0, and d_symbol_noise shows the infinity.
+ *   skipped       a frame whose record in d_sync (optional) has sync_valid = 0: its products are stale and none is read; or a frame
+ *                 whose q_ref is not a normal positive finite number (all zeros; 38 bad rows).  0 to all of d_symbol_weight,
+ *                 d_symbol_noise and d_ref_noise, d_valid cleared.
+ * Limits: product s mixes symbols s and s + 1, so a burst's edge weighs on one neighbour row; a frame of which more than half is burst
+ * has a jammed q_ref and weights near 1; qa / q is about 0.98 from 12 dB carrier SNR up, 0.8 at 6 dB, 0.45 at 0 dB.
+ * Arithmetic: csrc/sym_profile_core.h; the device equals dabgpu_sym_profile_rows_host and the tests' host model bit for bit. */
+#define DABGPU_SYM_PROFILE_SYMBOLS 75
+/* What a dabgpu_sym_profile_frames call with these arguments launches; needs no device (no address is dereferenced).
+ * DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null result; a transmission_mode other than 1; n_frames of 0 or
+ * above 2^24; d_dqpsk null or not 16-byte aligned; records or outputs that are not 4-byte aligned; no output at all (d_valid counts
+ * as one). */
+int dabgpu_sym_profile_plan(int transmission_mode, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                            const float *d_symbol_weight, const float *d_symbol_noise, const float *d_ref_noise,
+                            const uint32_t *d_valid, dabgpu_noise_geometry *out);
+/* d_dqpsk and d_sync are dabgpu_ofdm_sync_demod_frames_branch's d_dqpsk and records: the call sits behind a branch's demodulation with
+ * no copy.  d_symbol_weight, d_symbol_noise [n_frames][75], d_ref_noise, d_valid [n_frames]: every output is optional;
+ * d_symbol_weight can be an entry of dabgpu_diversity_combine_frames_symbols' h_symbol_weight as it is. */
+int dabgpu_sym_profile_frames(dabgpu_ctx *ctx, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                              float *d_symbol_weight, float *d_symbol_noise, float *d_ref_noise, uint32_t *d_valid, void *stream);
+/* One frame from host memory, synchronous, on the context's stream: h_dqpsk [75][1536] complex float; h_symbol_weight [75],
+ * h_symbol_noise [75], h_ref_noise may be NULL.  Returns DABGPU_OK with *h_valid (may be NULL) 1 or 0. */
+int dabgpu_sym_profile_host_sync(dabgpu_ctx *ctx, const float *h_dqpsk, float *h_symbol_weight, float *h_symbol_noise,
+                                 float *h_ref_noise, uint32_t *h_valid);
+/* the whole definition on the host (no device): one frame's products [75][1536] complex float -> symbol_weight [75],
+ * symbol_noise [75], ref_noise (each may be NULL).  1 for a valid frame, 0 for a skipped one, -1 for null products. */
+int dabgpu_sym_profile_rows_host(const float *dqpsk, float *symbol_weight, float *symbol_noise, float *ref_noise);
+
+/* Symbol-weighted receive diversity: dabgpu_diversity_combine_frames_banded with a symbol noise profile per branch.  h_symbol_weight
+ * [n_branches] (host memory, travels by value in the kernel argument): entry b = a device pointer to [n_frames][75] symbol weights of
+ * branch b, or NULL.  h_symbol_weight NULL, or every entry NULL: exactly dabgpu_diversity_combine_frames_banded (which itself falls
+ * through to the scalar call without band tables).  For a branch with a symbol table, carrier c of product row s enters the sum with
+ *     wband * clean(v[s])
+ * where wband is what the banded call uses (the band weight of c / 12, or the branch's scalar weight without a band table) and
+ * clean(v) is v where v is positive and finite, else 0; the product is rounded once and takes the place of the weight in the sum.
+ * Symbol weights enter neither the live rule nor the frame scale: they are relative weights with median 1, and time interleaving
+ * spreads a down-weighted row over 16 CIFs.  A table of ones reproduces the banded call bit for bit.
+ * Limits: the FIC is not time-interleaved, so FIC symbols under a burst are lost whatever their weight; the frame scale still rests on
+ * the power of the phase reference symbol.
+ * _plan_symbols: what dabgpu_diversity_plan_banded refuses, then a symbol table entry that is not 4-byte aligned.  The host form takes
+ * h_symbol_weight[b] -> [75] floats in host memory (or NULL; NULL array: the banded host form). */
+int dabgpu_diversity_plan_symbols(const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames, const int8_t *d_bits,
+                                  size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float *const *h_band_weight,
+                                  const float *const *h_symbol_weight, dabgpu_diversity_geometry *out);
+int dabgpu_diversity_combine_frames_symbols(dabgpu_ctx *ctx, const dabgpu_diversity_branch *h_branches, int n_branches, size_t n_frames,
+                                            int8_t *d_bits, size_t bits_frame_stride, int bits_layout, int symbols_per_block,
+                                            float *d_soft_scale, uint32_t *d_live_mask, const float *const *h_band_weight,
+                                            const float *const *h_symbol_weight, void *stream);
+int dabgpu_diversity_combine_symbols_host_sync(dabgpu_ctx *ctx, const float *const *h_dqpsk, const float *h_scale, const float *h_weight,
+                                               const int *h_valid, int n_branches, int bits_layout, int8_t *h_bits, float *h_soft_scale,
+                                               uint32_t *h_live_mask, const float *const *h_band_weight,
+                                               const float *const *h_symbol_weight);
+
 #ifdef __cplusplus
 }
 #endif
