@@ -70,9 +70,10 @@ struct dabgpu_receiver {
 extern "C" void dabgpu_receiver_destroy(dabgpu_receiver* rx) {
     if (!rx) return;
     if (rx->member) {
-        const dabgpu_ctx* bank_ctx = dabgpu_rx_bank_session(rx->member)->ctx;      // (the bank's: it stays for the life of the process)
+        // (the bank's context, looked at BEFORE the leave: the last member of a bank that was shut down frees it, context included)
+        const bool bound = dabgpu_destroy_begin(rx, dabgpu_rx_bank_session(rx->member)->ctx, false);
         dabgpu_rx_bank_leave(rx->member);                            // (waits for the member's jobs: nothing reads the staging buffers afterwards)
-        if (dabgpu_destroy_begin(rx, bank_ctx, false)) delete rx;
+        if (bound) delete rx;
         return;
     }
     if (!dabgpu_destroy_begin(rx, rx->ctx, false)) return;

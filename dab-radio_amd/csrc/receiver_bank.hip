@@ -71,7 +71,7 @@ __global__ void bank_scatter_kernel(const int8_t* __restrict__ bits, int8_t* __r
 }  // namespace
 
 struct rx_member_device {
-    dabgpu::DeviceBuffer<float> d_iq;           // [2][frame]: the member uploads frame g to half g % 2 when it posts it (see upload)
+    dabgpu::DeviceBuffer<float> d_iq;           // [RX_BANK_IQ_FRAMES][frame]: the member uploads frame g to buffer g % RX_BANK_IQ_FRAMES when it posts it (see upload)
     dabgpu::Event stage_ev[3];                  // recorded behind the upload of the frame posted from that staging buffer
     // views (display buffers), allocated at first use
     dabgpu::DeviceBuffer<float> d_fft, d_dq;
@@ -361,11 +361,13 @@ int hip_bank::deliver_frame(const rx_bank_round& r, size_t j, int st) {
     return st;
 }
 
-// Half gen % 2 of the member's device buffer: frame g - 2, which used it, was read by the gather of its round, and that round lies on stream A in front
-// of the synchroniser whose record this frame was cut with (a member's jobs run in posting order; the synchroniser of frame g is posted after frame g - 1).
+// Buffer gen % RX_BANK_IQ_FRAMES of the member's device buffer, on an upload stream that waits for nothing: frame gen - RX_BANK_IQ_FRAMES, which used it, has
+// been handed out -- post_frame lets gen in only while gen < done_gen + R - 1 -- so the completer's host wait for its round, gather included, came before this
+// copy was enqueued.  (Two buffers, on the argument that a synchroniser is posted between two frames, were overwritten by the third of the up to R - 1 frames
+// that may be posted with none in between: the round of frame g records its event on the upload stream behind the uploads of g + 1 and g + 2.)
 int hip_bank::upload(dabgpu_rx_member* m, int stage, size_t frame_sample, uint64_t gen, int up_k, const float** d_out_iq) {
     (void)hipSetDevice(device);
-    float* d = m->dev->d_iq.get() + (size_t)(gen % 2) * FRAME_SAMPLES * 2;
+    float* d = m->dev->d_iq.get() + (size_t)(gen % RX_BANK_IQ_FRAMES) * FRAME_SAMPLES * 2;
     hipStream_t u = up[up_k].get();
     int st = dabgpu_check_hip(hipMemcpyAsync(d, m->h_stage[stage] + 2 * frame_sample, FRAME_SAMPLES * 2 * sizeof(float), hipMemcpyHostToDevice, u), "hipMemcpyAsync(bank frame)");
     if (!st) st = dabgpu_check_hip(hipEventRecord(m->dev->stage_ev[stage].get(), u), "hipEventRecord(bank stage)");
@@ -392,7 +394,7 @@ int hip_bank::member_open(dabgpu_rx_member* m) {
     if (!d) return DABGPU_ERR_HIP;
     int st = dabgpu_frame_session_create_store(&m->ses, ctx.get());
     for (int k = 0; k < 3 && !st; k++) st = d->stage_ev[k].create(dabgpu_wait_event_flags(true), "hipEventCreate(bank member)");
-    if (!st) st = d->d_iq.alloc((size_t)2 * FRAME_SAMPLES * 2, "hipMalloc(bank member samples)");
+    if (!st) st = d->d_iq.alloc((size_t)RX_BANK_IQ_FRAMES * FRAME_SAMPLES * 2, "hipMalloc(bank member samples)");
     // the rounds copy a frame's soft bits straight into the result slot's page-locked buffer (the session owns them)
     for (int k = 0; k < dabgpu_frame_session::R && !st; k++) st = m->ses->slots[k].h_bits.alloc(FRAME_BITS, "hipHostMalloc(bank member soft bits)");
     if (!st) st = dabgpu_check_hip(hipMemsetAsync(d_states.get() + m->slot, 0, sizeof(dabgpu_sync_state), a.get()), "hipMemsetAsync(bank member state)");

@@ -38,9 +38,14 @@ struct dabgpu_rx_bank {
     std::mutex mu;
     std::condition_variable cv_jobs, cv_done, cv_ticks;
     std::deque<rx_bank_job> jobs;
-    bool stop = false;
+    bool stop = false;                           // shutdown: nothing more is posted; the worker forms rounds until the queue is empty, the completers hand all of them out
+    bool worker_done = false;                    // the worker has returned: n_ticks is final
     std::thread worker, completer, sync_completer;
     int refs = 0;
+    // shutdown with members left (receivers destroyed after it, e.g. by destructors that run behind the atexit handler): the bank is stopped and taken
+    // out of g_banks but stays, with its device half, for the members' results and their leave; the last leave frees it.  Both under g_banks_mu.
+    int attached = 0;                            // members between join and the end of their leave
+    bool detached = false;
     // DABGPU_BANK_PROFILE=1: what the rounds looked like, printed at shutdown
     bool profile = false;
     int gather_us = 1000;                        // DABGPU_BANK_GATHER_US
@@ -71,7 +76,12 @@ void worker_main(dabgpu_rx_bank* b) {
         const double ti0 = b->profile ? bank_now_us() : 0.0;
         b->cv_jobs.wait(lock, [b] { return b->stop || !b->jobs.empty(); });
         if (b->profile && b->n_ticks) b->p_worker_idle_us += bank_now_us() - ti0;       // (not the wait for the very first job: the members are still being constructed)
-        if (b->stop && b->jobs.empty()) return;
+        if (b->stop && b->jobs.empty()) {                                  // (nothing is posted to a stopped bank: the queue stays empty)
+            b->worker_done = true;
+            lock.unlock();
+            b->cv_done.notify_all();
+            return;
+        }
         if (b->gather_us > 0) {
             // (1) A frame was posted a moment ago and the synchroniser of the NEXT frame is not in the queue yet: the reader posts it as soon as it has read the
             // NULL symbol and the PRS that follow (tens of us, when the samples are there) -- a round formed in between carries the frame alone and the
@@ -157,7 +167,8 @@ void sync_completer_main(dabgpu_rx_bank* b) {
     b->dev->bind_thread();
     for (;;) {
         std::unique_lock<std::mutex> lock(b->mu);
-        b->cv_done.wait(lock, [b] { return (b->stop && b->n_sync_handed == b->n_ticks) || (b->n_sync_handed < b->n_ticks && b->ticks[b->n_sync_handed % TICKS].status != -1); });
+        // (leaves when the worker has returned and its last round is handed out: `stop` alone is too early, the worker still forms rounds out of what is queued)
+        b->cv_done.wait(lock, [b] { return (b->worker_done && b->n_sync_handed == b->n_ticks) || (b->n_sync_handed < b->n_ticks && b->ticks[b->n_sync_handed % TICKS].status != -1); });
         if (b->n_sync_handed == b->n_ticks) return;
         rx_bank_round& t = b->ticks[b->n_sync_handed % TICKS];
         lock.unlock();
@@ -188,7 +199,7 @@ void completer_main(dabgpu_rx_bank* b) {
     b->dev->bind_thread();
     for (;;) {
         std::unique_lock<std::mutex> lock(b->mu);
-        b->cv_done.wait(lock, [b] { return (b->stop && b->n_handed == b->n_ticks) || (b->n_handed < b->n_ticks && b->ticks[b->n_handed % TICKS].status != -1); });
+        b->cv_done.wait(lock, [b] { return (b->worker_done && b->n_handed == b->n_ticks) || (b->n_handed < b->n_ticks && b->ticks[b->n_handed % TICKS].status != -1); });
         if (b->n_handed == b->n_ticks) return;
         rx_bank_round& t = b->ticks[b->n_handed % TICKS];
         lock.unlock();
@@ -200,7 +211,7 @@ void completer_main(dabgpu_rx_bank* b) {
             for (size_t j = 0; j < t.frame_jobs.size(); j++) st = b->dev->deliver_frame(t, j, st);
             lock.lock();
             for (const auto& f : t.frame_jobs) {
-                f.m->frame_status = st ? st : f.m->frame_status;
+                f.m->frame_status[f.gen % R] = st;                         // this generation's: the slot's next frame writes its own
                 f.m->done_gen = f.gen + 1;
                 f.m->jobs_in_flight--;
                 f.m->cv.notify_all();
@@ -262,14 +273,20 @@ int dabgpu_rx_bank_join(int device, float* const* h_stage, dabgpu_rx_member** ou
         delete m;
         return st;
     }
+    b->attached++;
     *out = m;
     return DABGPU_OK;
+}
+
+namespace {
+void bank_free(dabgpu_rx_bank* b) { delete b->dev; delete b; }               // (its threads were joined)
 }
 
 void dabgpu_rx_bank_leave(dabgpu_rx_member* m) {
     if (!m) return;
     dabgpu_rx_bank* b = m->bank;
     {
+        // (a stopped bank: its threads handed out every job before they returned, and none was accepted since)
         std::unique_lock<std::mutex> lock(b->mu);
         m->cv.wait(lock, [m] { return m->jobs_in_flight == 0; });
         b->members[m->slot] = nullptr;
@@ -277,7 +294,11 @@ void dabgpu_rx_bank_leave(dabgpu_rx_member* m) {
     }
     b->dev->member_close(m);
     delete m;
-    // the bank itself stays for the life of the process (its threads are joined by dabgpu_rx_bank_shutdown, which the library's unload calls)
+    // the bank itself stays for the life of the process (its threads are joined by dabgpu_rx_bank_shutdown, which the library's unload calls) -- unless it
+    // was shut down over this member's head: then the last member to leave frees it
+    bool last;
+    { std::lock_guard<std::mutex> g(g_banks_mu); last = --b->attached == 0 && b->detached; }
+    if (last) bank_free(b);
 }
 
 dabgpu_frame_session* dabgpu_rx_bank_session(dabgpu_rx_member* m) { return m->ses; }
@@ -303,9 +324,22 @@ int dabgpu_rx_bank_set_subchannels(dabgpu_rx_member* m, const dabgpu_subchannel*
     return DABGPU_OK;
 }
 
+namespace {
+// under the bank's mutex, before a job is queued: a bank that was shut down takes none (its worker returns on an empty queue and nothing may follow)
+int refuse_if_stopped(const dabgpu_rx_bank* b, const char* what) {
+    if (!b->stop) return DABGPU_OK;
+    dabgpu_set_error("%s: the receiver bank was shut down", what);
+    return DABGPU_ERR_UNSUPPORTED;
+}
+}  // namespace
+
 int dabgpu_rx_bank_reset(dabgpu_rx_member* m) {
     dabgpu_rx_bank* b = m->bank;
-    { std::lock_guard<std::mutex> lock(b->mu); rx_bank_job j{}; j.kind = rx_bank_job::RESET; j.m = m; b->jobs.push_back(j); m->jobs_in_flight++; }
+    {
+        std::lock_guard<std::mutex> lock(b->mu);
+        if (const int st = refuse_if_stopped(b, "receiver_reset")) return st;
+        rx_bank_job j{}; j.kind = rx_bank_job::RESET; j.m = m; b->jobs.push_back(j); m->jobs_in_flight++;
+    }
     b->cv_jobs.notify_one();
     return DABGPU_OK;
 }
@@ -315,11 +349,13 @@ int dabgpu_rx_bank_post_sync(dabgpu_rx_member* m, const dabgpu_sync_cfg* cfg, in
     {
         std::lock_guard<std::mutex> lock(b->mu);
         if (m->sync_state != 0) { dabgpu_set_error("receiver_submit_sync: the previous record has not been collected (dabgpu_receiver_wait_sync)"); return DABGPU_ERR_INVALID_ARG; }
+        if (const int st = refuse_if_stopped(b, "receiver_submit_sync")) return st;
     }
     // the member's row of the bank's PRS array is its own until the record has come back (one synchroniser at a time per member)
     memcpy(b->dev->prs_row(m->slot), m->h_stage[stage] + 2 * prs_sample, NFFT * 2 * sizeof(float));
     {
         std::lock_guard<std::mutex> lock(b->mu);
+        if (const int st = refuse_if_stopped(b, "receiver_submit_sync")) return st;
         rx_bank_job j{}; j.kind = rx_bank_job::SYNC; j.m = m; j.stage = stage; j.sample = prs_sample; j.cfg = *cfg;
         b->jobs.push_back(j);
         m->sync_state = 1;
@@ -351,6 +387,7 @@ int dabgpu_rx_bank_post_frame(dabgpu_rx_member* m, int stage, size_t frame_sampl
     int n_up;
     {
         std::lock_guard<std::mutex> lock(b->mu);
+        if (const int st = refuse_if_stopped(b, "receiver_submit_frame")) return st;
         if (m->next_gen >= m->done_gen + (uint64_t)(R - 1)) {
             dabgpu_set_error("receiver_submit_frame: %d frames submitted and not yet collected (at most %d)", (int)(m->next_gen - m->done_gen), R - 1);
             return DABGPU_ERR_NOT_READY;
@@ -366,6 +403,7 @@ int dabgpu_rx_bank_post_frame(dabgpu_rx_member* m, int stage, size_t frame_sampl
     if (st) return st;
     {
         std::lock_guard<std::mutex> lock(b->mu);
+        if (const int st2 = refuse_if_stopped(b, "receiver_submit_frame")) return st2;     // (stopped during the upload: the copy is made, no round reads it)
         rx_bank_job j{}; j.kind = rx_bank_job::FRAME; j.m = m; j.stage = stage; j.sample = frame_sample; j.beta = beta; j.want_views = want_views; j.tie = tie;
         j.gen = gen; j.d_iq = d; j.up = up_k;
         m->next_gen = gen + 1;
@@ -398,7 +436,9 @@ int dabgpu_rx_bank_wait_frame(dabgpu_rx_member* m, uint64_t generation, dabgpu_r
         std::unique_lock<std::mutex> lock(b->mu);
         if (generation >= m->next_gen) { dabgpu_set_error("receiver_wait_frame: generation %llu was never submitted", (unsigned long long)generation); return DABGPU_ERR_NOT_READY; }
         m->cv.wait(lock, [&] { return m->done_gen > generation; });
-        if (m->frame_status) { dabgpu_set_error("receiver bank: the tick that carried the frame failed"); return m->frame_status; }
+        // (the status of THIS generation: its place is written again when generation + R is handed out, and then the frame is gone anyway -- fetch_frame says so)
+        const int st = m->done_gen <= generation + (uint64_t)R ? m->frame_status[generation % R] : DABGPU_OK;
+        if (st) { dabgpu_set_error("receiver bank: the tick that carried the frame failed"); return st; }
     }
     return b->dev->fetch_frame(m, generation, out);
 }
@@ -422,13 +462,16 @@ void dabgpu_rx_bank_shutdown(void) {
         if (b->worker.joinable()) b->worker.join();
         if (b->completer.joinable()) b->completer.join();
         if (b->sync_completer.joinable()) b->sync_completer.join();
+        // (every job that was queued has been handed out: the worker returns on an empty queue only, the completers after its last round)
         if (b->profile && b->n_ticks)
             fprintf(stderr, "receiver bank (device %d): %llu rounds, %llu with frames; %.2f frames and %.2f synchronisers per round; per round us: enqueue %.1f, completer { wait sync %.1f, "
                             "wait frames %.1f, whole hand-out %.1f }; worker idle %.1f\n", b->device, (unsigned long long)b->n_ticks, (unsigned long long)b->p_ticks_with_frames,
                     (double)b->p_frame_jobs / (double)b->n_ticks, (double)b->p_sync_jobs / (double)b->n_ticks, b->p_enqueue_us / (double)b->n_ticks, b->p_wait_sync_us / (double)b->n_ticks,
                     b->p_wait_frames_us / (double)b->n_ticks, b->p_handout_us / (double)b->n_ticks, b->p_worker_idle_us / (double)b->n_ticks);
-        delete b->dev;
-        delete b;
+        // members left (a receiver destroyed behind this call): they keep the stopped bank -- their results stay fetchable, what they post is refused -- and
+        // the last of them to leave frees it
+        if (b->attached > 0) b->detached = true;
+        else bank_free(b);
         b = nullptr;
     }
 }

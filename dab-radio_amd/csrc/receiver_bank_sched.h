@@ -10,6 +10,11 @@
 constexpr int RX_BANK_TICKS = 8;                // rounds that may be under way (their buffers)
 constexpr int RX_BANK_SLOTS = 8;                // result slots of a member's frame session (dabgpu_frame_session::R, dabgpu_internal.h)
 constexpr int RX_BANK_UPLOADS = 3;              // upload streams (member slot % n): frames cross PCIe on several DMA engines at once
+// Frames of samples a member's device half keeps: upload puts frame gen into buffer gen % RX_BANK_IQ_FRAMES, on a stream that waits for nothing.  As many
+// as result slots: post_frame accepts gen only while gen < done_gen + RX_BANK_SLOTS - 1, so frame gen - RX_BANK_SLOTS has been handed out -- the completer
+// waited for the device work of its round, the gather of its samples included, before this upload could be enqueued.  (Two buffers were not enough: up to
+// RX_BANK_SLOTS - 1 frames may be posted with no synchroniser in between, and the third overwrote the first before its round had read it.)
+constexpr int RX_BANK_IQ_FRAMES = RX_BANK_SLOTS;
 
 struct rx_member_device;                        // the device half of a member: whatever the rx_bank_device in use keeps per member
 
@@ -41,7 +46,7 @@ struct dabgpu_rx_member {
     int stage_state[3] = {0, 0, 0};             // 0 free, 2 a frame was posted from it: its upload is enqueued
     uint64_t next_gen = 0;                      // next generation to post
     uint64_t done_gen = 0;                      // generations < done_gen have their results in the session's slots
-    int frame_status = DABGPU_OK;
+    int frame_status[RX_BANK_SLOTS] = {0};      // of generation gen at gen % RX_BANK_SLOTS, written when its round is handed out: a failed round fails its own frames only
     int jobs_in_flight = 0;
     std::condition_variable cv;                 // the member's own threads wait here (on the bank's mutex): a hand-out wakes the members it concerns, not all of them
     double last_post_us = -1e18;                // when the member posted last (the worker's gathering rule)

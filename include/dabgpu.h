@@ -614,7 +614,10 @@ int dabgpu_receiver_submit_sync(dabgpu_receiver *rx, const dabgpu_sync_cfg *cfg,
  * fine_time_offset, sync_valid (0: the caller resets, :529-532); h_impulse / h_freq_response [nb_fft] dB, may be NULL */
 int dabgpu_receiver_wait_sync(dabgpu_receiver *rx, dabgpu_sync_state *out, float *h_impulse, float *h_freq_response);
 /* the frame = samples-per-frame samples from sample frame_sample of the current staging buffer (nb_null_period + fine_time_offset); asynchronous:
- * upload, demodulation, fine-frequency update with `beta`, decode, results to host memory.  *generation counts the frames submitted. */
+ * upload, demodulation, fine-frequency update with `beta`, decode, results to host memory.  *generation counts the frames submitted.
+ * No synchroniser is required between two frames: up to R - 1 = 7 frames may be submitted one behind the other (each from the staging buffer that is
+ * current then; every frame is demodulated with the fine-frequency word the frame before it left), on private and banked receivers alike.  A banked
+ * receiver answers DABGPU_ERR_NOT_READY to a frame beyond 7 not yet delivered, and DABGPU_ERR_UNSUPPORTED once its bank was shut down. */
 int dabgpu_receiver_submit_frame(dabgpu_receiver *rx, size_t frame_sample, float fine_freq_update_beta, int want_views, int tie_rule,
                                  uint64_t *generation);
 /* The same in two calls, for two threads (what the OFDM_Demod mirror does): submit_demod enqueues the upload, the demodulation, the fine-frequency

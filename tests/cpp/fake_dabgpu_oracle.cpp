@@ -258,7 +258,8 @@ static int demod_into(dabgpu_ctx* ctx, const float* iq, dabgpu_sync_state& state
 // ---- the device half of a receiver bank on the oracle: enqueue computes, the waits return at once, delivery fills the members' result slots ----
 struct rx_member_device {
     dabgpu_sync_state state = {0, 0, 0, 0, 0, 0};        // (the worker thread's: rounds are enqueued one at a time)
-    std::vector<float> iq[RX_BANK_SLOTS];                // "uploaded" frames by generation: every frame post_frame accepts keeps its samples until its round
+    std::vector<float> iq[RX_BANK_IQ_FRAMES];            // "uploaded" frames, generation g in buffer g % RX_BANK_IQ_FRAMES as in the product's device half: a frame
+                                                         // posted before an earlier one's round has read that buffer overwrites it (the vectors keep their storage)
     std::mutex mu;                                       // result slots: written by the frames' completer, read by the member's delivery thread
     dabgpu_receiver::Slot slots[RX_BANK_SLOTS];
 };
@@ -266,6 +267,14 @@ static std::mutex g_hold_mu;                             // fake_dabgpu_bank_hol
 static std::condition_variable g_hold_cv;
 static bool g_hold = false;
 extern "C" void fake_dabgpu_bank_hold(int on) { { std::lock_guard<std::mutex> g(g_hold_mu); g_hold = on != 0; } g_hold_cv.notify_all(); }
+// Failures to order (under g_hold_mu).  fake_dabgpu_bank_fail_rounds(n, status): the next n rounds that ENTER enqueue -- not one that is in it already, held --
+// return `status`; the round is computed all the same (a device whose work ran and whose runtime then reported an error), so the members' frequency words and
+// history go on as a private receiver's.  fake_dabgpu_bank_fail_waits(n, status): the next n wait_frames return `status`.  fake_dabgpu_bank_enqueues(): rounds
+// that have entered enqueue so far (a driver waits for it to know that the worker sits in a held round).
+static int g_fail_rounds = 0, g_fail_rounds_status = 0, g_fail_waits = 0, g_fail_waits_status = 0, g_enqueues = 0;
+extern "C" void fake_dabgpu_bank_fail_rounds(int n, int status) { std::lock_guard<std::mutex> g(g_hold_mu); g_fail_rounds = n; g_fail_rounds_status = status; }
+extern "C" void fake_dabgpu_bank_fail_waits(int n, int status) { std::lock_guard<std::mutex> g(g_hold_mu); g_fail_waits = n; g_fail_waits_status = status; }
+extern "C" int fake_dabgpu_bank_enqueues(void) { std::lock_guard<std::mutex> g(g_hold_mu); return g_enqueues; }
 struct oracle_bank final : rx_bank_device {
     dabgpu_ctx* ctx = nullptr;
     std::vector<float> prs = std::vector<float>((size_t)DABGPU_RX_BANK_MAX * DABGPU_NB_FFT * 2);
@@ -278,7 +287,13 @@ struct oracle_bank final : rx_bank_device {
     float* prs_row(int slot) override { return prs.data() + (size_t)slot * DABGPU_NB_FFT * 2; }
     int enqueue(const rx_bank_round& r) override {                            // the product's order: resets, frames, synchronisers behind them
         Tick& t = ticks[r.no % RX_BANK_TICKS];
-        { std::unique_lock<std::mutex> g(g_hold_mu); g_hold_cv.wait(g, [] { return !g_hold; }); }
+        int ordered = DABGPU_OK;
+        {
+            std::unique_lock<std::mutex> g(g_hold_mu);
+            g_enqueues++;
+            if (g_fail_rounds > 0) { g_fail_rounds--; ordered = g_fail_rounds_status; }
+            g_hold_cv.wait(g, [] { return !g_hold; });
+        }
         for (const auto& j : r.resets) j.m->dev->state = {0, 0, 0, 0, 0, 0};
         t.frames.assign(r.frame_jobs.size(), dabgpu_receiver::Slot());
         for (size_t j = 0; j < r.frame_jobs.size(); j++) {
@@ -298,7 +313,7 @@ struct oracle_bank final : rx_bank_device {
             if (st) return st;
             t.rec[k] = j.m->dev->state;
         }
-        return DABGPU_OK;
+        return ordered;
     }
     int wait_sync(const rx_bank_round&) override { return DABGPU_OK; }
     void hand_sync(const rx_bank_round& r, size_t k) override {
@@ -307,7 +322,12 @@ struct oracle_bank final : rx_bank_device {
         m->sync_rec = t.rec[k]; m->sync_coarse = r.sync_jobs[k].cfg.is_coarse_freq_correction != 0;
         m->sync_imp = t.imp[k]; if (m->sync_coarse) m->sync_frq = t.frq[k];
     }
-    int wait_frames(const rx_bank_round&) override { return DABGPU_OK; }
+    int wait_frames(const rx_bank_round&) override {
+        std::lock_guard<std::mutex> g(g_hold_mu);
+        if (g_fail_waits <= 0) return DABGPU_OK;
+        g_fail_waits--;
+        return g_fail_waits_status;
+    }
     int deliver_frame(const rx_bank_round& r, size_t j, int st) override {
         const rx_bank_job& f = r.frame_jobs[j];
         std::lock_guard<std::mutex> g(f.m->dev->mu);
@@ -315,7 +335,7 @@ struct oracle_bank final : rx_bank_device {
         return st;
     }
     int upload(dabgpu_rx_member* m, int stage, size_t frame_sample, uint64_t gen, int, const float** d_iq) override {
-        std::vector<float>& v = m->dev->iq[gen % RX_BANK_SLOTS];
+        std::vector<float>& v = m->dev->iq[gen % RX_BANK_IQ_FRAMES];
         v.assign(m->h_stage[stage] + 2 * frame_sample, m->h_stage[stage] + 2 * (frame_sample + DABGPU_NB_FRAME_SAMPLES));
         *d_iq = v.data();
         return DABGPU_OK;

@@ -43,6 +43,88 @@ def _api(dabgpu):
     return L
 
 
+class OracleReceiver:
+    """The oracle's per-frame composition for one receiver (ofdm_demodulator.cpp:360-548 -> :650-766 -> :606-618; fic_decoder.cpp:53-117;
+    msc_decoder.cpp:46-154) on the record it carries from frame to frame: sync() is a synchroniser on the staging buffer's PRS slot, frame() the
+    demodulation of a frame with the record's frequency words, the fine-frequency update, the four FIB groups and every sub-channel's CIFs through
+    its time de-interleaver.  tests/test_gpu_receiver_bank.py runs the same composition."""
+
+    def __init__(self, O, subs_o):
+        self.O, self.subs = O, subs_o
+        self.st = O.SyncState(0.0, 0.0, 0, 0, 0, 0)
+        self.conj_ref, self.time_ref = O.sync_refs()
+        self.deint = [O.Deinterleaver(s.length * 8) for s in subs_o]
+
+    def net_freq(self):
+        return np.float32(np.float32(self.st.freq_coarse) + np.float32(self.st.freq_fine))
+
+    def sync(self, stage):
+        """-> (impulse peak found, fine time offset, impulse response); the record's frequency words are updated"""
+        O = self.O
+        prs_sym = stage[O.NB_NULL_PERIOD:O.NB_NULL_PERIOD + 2048].copy()
+        O.coarse_freq_sync(prs_sym, self.st, None, self.time_ref)
+        return O.fine_time_sync(prs_sym, self.net_freq(), None, self.conj_ref)
+
+    def frame(self, stage, off, want_fft=False):
+        """the frame cut `off` samples behind the NULL symbol of the staging buffer -> what the receiver must deliver for it"""
+        O = self.O
+        r = O.demod_frame(stage[O.NB_NULL_PERIOD + off:O.NB_NULL_PERIOD + off + O.NB_FRAME_SAMPLES].copy(), self.net_freq(), want_fft=want_fft)
+        self.st.freq_fine = float(O.update_fine_freq(self.st.freq_fine, r["total_phase"]))
+        exp = dict(bits=r["bits"], fine=np.float32(self.st.freq_fine), total=np.float32(r["total_phase"]), fft=r["fft"])
+        exp["fib"] = [O.fic_decode_group(r["bits"][g * 2304:(g + 1) * 2304], 0) for g in range(4)]
+        exp["msc"] = []
+        for c in range(4):
+            row = []
+            for si, s in enumerate(self.subs):
+                cif = r["bits"][9216 + c * 55296:9216 + (c + 1) * 55296]
+                self.deint[si].consume(cif[s.start_address * 64:(s.start_address + s.length) * 64])
+                lf = self.deint[si].deinterleave()
+                row.append(None if lf is None else O.msc_decode_logical(s, lf, 0))
+            exp["msc"].append(row)
+        return exp
+
+
+def fetch_frame(L, ck, rx, ses, g, dsubs):
+    """everything a receiver delivers for generation g, as host arrays: dabgpu_receiver_wait_frame, the four FIB groups, every sub-channel's four CIFs
+    (a CIF's entry is (bytes, path error), or None where the session has none: the time de-interleaver is still filling)"""
+    fr = Frame()
+    ck(L.dabgpu_receiver_wait_frame(rx, g, C.byref(fr)), "dabgpu_receiver_wait_frame")
+    got = dict(generation=fr.generation, n_bits=fr.n_bits, bits=np.ctypeslib.as_array(C.cast(fr.bits, C.POINTER(C.c_int8)), shape=(fr.n_bits,)).copy(),
+               fine=np.float32(fr.freq_fine), total=np.float32(fr.total_phase), fft_ptr=fr.fft, fib=[], msc=[])
+    for grp in range(4):
+        out, mask, err = np.zeros(96, np.uint8), C.c_uint32(), C.c_uint64()
+        ck(L.dabgpu_frame_session_fetch_fib_group(ses, g, grp, out.ctypes.data, C.byref(mask), C.byref(err)), "fetch_fib_group")
+        got["fib"].append((out, mask.value, err.value))
+    for c in range(4):
+        row = []
+        for si in range(len(dsubs)):
+            out, nb, err = np.zeros(4096, np.uint8), C.c_size_t(), C.c_uint64()
+            st = L.dabgpu_frame_session_fetch_cif(ses, g, C.byref(dsubs[si]), c, out.ctypes.data, out.size, C.byref(nb), C.byref(err))
+            row.append((out[:nb.value].copy(), err.value) if st == 0 else None)
+        got["msc"].append(row)
+    return got
+
+
+def assert_frame(got, e, g):
+    """what fetch_frame collected for generation g against OracleReceiver.frame's expectation: soft bits byte for byte, the frequency words as float32
+    bit patterns, FIB bytes with CRC mask and path error, every CIF the oracle's de-interleaver has produced with its path error"""
+    assert got["generation"] == g and got["n_bits"] == e["bits"].size and np.array_equal(got["bits"], e["bits"]), f"frame {g}: soft bits"
+    assert got["fine"].view(np.uint32) == e["fine"].view(np.uint32), f"frame {g}: fine frequency word"
+    assert got["total"].view(np.uint32) == e["total"].view(np.uint32), f"frame {g}: total phase"
+    for grp in range(4):
+        out, mask, err = got["fib"][grp]
+        eb, em, ee = e["fib"][grp]
+        assert np.array_equal(out, eb) and mask == em and err == ee, (g, grp)
+    for c in range(4):
+        for si in range(len(e["msc"][c])):
+            if e["msc"][c][si] is None:
+                continue                                     # the time de-interleaver is still filling: the session's output is garbage by contract
+            dec, perr = e["msc"][c][si]
+            assert got["msc"][c][si] is not None, (g, c, si, "fetch_cif")
+            out, err = got["msc"][c][si]
+            assert out.size == dec.size and np.array_equal(out, dec) and err == perr, (g, c, si)
+
+
 @pytest.mark.parametrize("form", ["private", "banked"])
 @pytest.mark.parametrize("calls", ["submit_frame", "submit_demod_then_decode"])
 def test_receiver_pipeline_equals_the_oracle_composition(oracle, calls, form):
@@ -80,9 +162,8 @@ def test_receiver_pipeline_equals_the_oracle_composition(oracle, calls, form):
         ck(L.dabgpu_receiver_set_subchannels(rx, dsubs, 2, 1), "dabgpu_receiver_set_subchannels")
         ses = L.dabgpu_receiver_session(rx)
         cfg = dabgpu.sync_cfg_default()
-        st_o = O.SyncState(0.0, 0.0, 0, 0, 0, 0)
-        conj_ref, time_ref = O.sync_refs()
-        deint = [O.Deinterleaver(s.length * 8) for s in subs_o]
+        orx = OracleReceiver(O, subs_o)
+        st_o, time_ref = orx.st, orx.time_ref
         pending, expected, undecoded = [], {}, []
         for j in range(n_frames + 1):
             if j < n_frames:
@@ -98,16 +179,12 @@ def test_receiver_pipeline_equals_the_oracle_composition(oracle, calls, form):
                 imp = np.zeros(2048, np.float32)
                 ck(L.dabgpu_receiver_wait_sync(rx, C.byref(rec), imp.ctypes.data, None), "dabgpu_receiver_wait_sync")
                 # oracle: the same frame on the record it carries from frame to frame
-                prs_sym = stage[NULL:NULL + 2048].copy()
-                O.coarse_freq_sync(prs_sym, st_o, None, time_ref)
-                f = np.float32(np.float32(st_o.freq_coarse) + np.float32(st_o.freq_fine))
-                ok, off, imp_o = O.fine_time_sync(prs_sym, f, None, conj_ref)
+                ok, off, imp_o = orx.sync(stage)
                 assert rec.sync_valid == 1 and ok and rec.fine_time_offset == off == toff, (j, rec.fine_time_offset, off)
                 assert np.float32(rec.freq_coarse).view(np.uint32) == np.float32(st_o.freq_coarse).view(np.uint32)
                 assert np.float32(rec.freq_fine).view(np.uint32) == np.float32(st_o.freq_fine).view(np.uint32)
                 assert np.array_equal(imp.view(np.uint32), np.asarray(imp_o, np.float32).view(np.uint32)), "GetImpulseResponse()"
-                r = O.demod_frame(stage[NULL + off:NULL + off + FRAME].copy(), f)
-                st_o.freq_fine = float(O.update_fine_freq(st_o.freq_fine, r["total_phase"]))
+                exp = orx.frame(stage, off)
                 gen = C.c_uint64()
                 if calls == "submit_frame":
                     ck(L.dabgpu_receiver_submit_frame(rx, NULL + off, cfg.fine_freq_update_beta, 0, 0, C.byref(gen)), "dabgpu_receiver_submit_frame")
@@ -117,17 +194,6 @@ def test_receiver_pipeline_equals_the_oracle_composition(oracle, calls, form):
                     while len(undecoded) > 2:
                         ck(L.dabgpu_receiver_submit_decode(rx, undecoded.pop(0), 0), "dabgpu_receiver_submit_decode")
                 assert gen.value == j
-                exp = dict(bits=r["bits"], fine=np.float32(st_o.freq_fine), total=np.float32(r["total_phase"]))
-                exp["fib"] = [O.fic_decode_group(r["bits"][g * 2304:(g + 1) * 2304], 0) for g in range(4)]
-                exp["msc"] = []
-                for c in range(4):
-                    row = []
-                    for si, s in enumerate(subs_o):
-                        cif = r["bits"][9216 + c * 55296:9216 + (c + 1) * 55296]
-                        deint[si].consume(cif[s.start_address * 64:(s.start_address + s.length) * 64])
-                        lf = deint[si].deinterleave()
-                        row.append(None if lf is None else O.msc_decode_logical(s, lf, 0))
-                    exp["msc"].append(row)
                 expected[j] = exp
                 pending.append(j)
             # collect late: three frames in flight
@@ -135,26 +201,7 @@ def test_receiver_pipeline_equals_the_oracle_composition(oracle, calls, form):
                 g = pending.pop(0)
                 while undecoded and undecoded[0] <= g:
                     ck(L.dabgpu_receiver_submit_decode(rx, undecoded.pop(0), 0), "dabgpu_receiver_submit_decode")
-                fr = Frame()
-                ck(L.dabgpu_receiver_wait_frame(rx, g, C.byref(fr)), "dabgpu_receiver_wait_frame")
-                e = expected.pop(g)
-                bits = np.ctypeslib.as_array(C.cast(fr.bits, C.POINTER(C.c_int8)), shape=(fr.n_bits,))
-                assert fr.n_bits == O.NB_FRAME_BITS and np.array_equal(bits, e["bits"]), f"frame {g}: soft bits"
-                assert np.float32(fr.freq_fine).view(np.uint32) == e["fine"].view(np.uint32), f"frame {g}: fine frequency word"
-                assert np.float32(fr.total_phase).view(np.uint32) == e["total"].view(np.uint32)
-                for grp in range(4):
-                    out, mask, err = np.zeros(96, np.uint8), C.c_uint32(), C.c_uint64()
-                    ck(L.dabgpu_frame_session_fetch_fib_group(ses, g, grp, out.ctypes.data, C.byref(mask), C.byref(err)), "fetch_fib_group")
-                    eb, em, ee = e["fib"][grp]
-                    assert np.array_equal(out, eb) and mask.value == em and err.value == ee, (g, grp)
-                for c in range(4):
-                    for si in range(2):
-                        if e["msc"][c][si] is None:
-                            continue                                     # the time de-interleaver is still filling: the session's output is garbage by contract
-                        dec, perr = e["msc"][c][si]
-                        out, nb, err = np.zeros(4096, np.uint8), C.c_size_t(), C.c_uint64()
-                        ck(L.dabgpu_frame_session_fetch_cif(ses, g, C.byref(dsubs[si]), c, out.ctypes.data, out.size, C.byref(nb), C.byref(err)), "fetch_cif")
-                        assert nb.value == dec.size and np.array_equal(out[:nb.value], dec) and err.value == perr, (g, c, si)
+                assert_frame(fetch_frame(L, ck, rx, ses, g, dsubs), expected.pop(g), g)
         # the last frame's logical frames are what was transmitted 15 CIFs earlier
         # (checked through the oracle's bytes above; here: the oracle's own agree with the generator)
         # ---- a failed impulse-peak test: noise in the PRS slot -> sync_valid 0 -> reset in stream order -> re-acquisition from a zeroed record ----

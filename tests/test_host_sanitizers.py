@@ -13,7 +13,8 @@ AddressSanitizer preset, CMakePresets.json:47-53):
      (tests/cpp/fake_dabgpu_oracle.cpp -- under tests/, never part of the product);
  (d) the RECEIVER BANK'S SCHEDULER (dab-radio_amd/csrc/receiver_bank_sched.cpp: job queue, worker and completer threads, round formation, join / leave /
      shutdown), the product's file compiled into the same executables and run over the fake's oracle-backed device half: eight banked receivers behind
-     the classes, a backlog of posted frames and join / leave churn through the C entry points (tests/cpp/bank_sched_driver.cpp)."""
+     the classes, a backlog of posted frames, join / leave churn, failed rounds, receivers destroyed after the shutdown and a shutdown over queued jobs
+     through the C entry points (tests/cpp/bank_sched_driver.cpp)."""
 import json
 import os
 import subprocess
@@ -162,12 +163,13 @@ def test_eight_banked_receivers_equal_private_ones_under_sanitizers(tmp_path, tw
     assert [r["digest"] for r in outs["1"]["per_receiver"]] == [private[k % 2] for k in range(8)]
 
 
-def bank_driver(tmp_path, case, tag, flags, env):
+def bank_driver(tmp_path, case, tag, flags, env, timeout=1200):
+    """`timeout`: the wall-clock limit of the driver's run (a scheduler that leaves a member waiting for good ends there, as a failure)"""
     lib_of("libtsan.so" if tag == "tsan" else "libasan.so")
     import oracle as O
     O.build()
     exe = build_driver(tmp_path, tag, flags, driver="bank_sched_driver.cpp", mirror=False)
-    res = run([str(exe), case], env=dict(os.environ, **env), timeout=1200)
+    res = run([str(exe), case], env=dict(os.environ, **env), timeout=timeout)
     assert "ThreadSanitizer" not in res.stderr and "AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]
     return json.loads(res.stdout.strip().splitlines()[-1])
 
@@ -186,6 +188,44 @@ def test_bank_join_leave_churn_under_thread_sanitizer(tmp_path):
     afterwards the bank's slot table is empty and its reference count 0."""
     out = bank_driver(tmp_path, "churn", *SANITIZERS[0])
     assert out == {"threads": 8, "joins": 160, "wrong_results": 0, "members_left": 0, "refs": 0, "ok": True}, out
+
+
+# The three cases below run some twenty frames of the oracle's demodulator at most (about 0.1 s each under a sanitizer at -O1): seconds.  The limit is
+# what a run on a loaded machine may take, far below the suite's other limits: a member left waiting for good must not cost twenty minutes.
+BANK_CASE_LIMIT_S = 300
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
+def test_bank_failed_round_fails_its_own_frames_and_record_only(tmp_path, tag, flags, env):
+    """Two members.  A round that carries frame 2 of member 0 and frame 1 of member 1 returns a status from enqueue (tests/cpp/fake_dabgpu_oracle.cpp:
+    fake_dabgpu_bank_fail_rounds): wait_frame answers it for exactly those two generations -- frame 1 of member 0 and frame 2 of member 1, in the rounds before
+    and after, are delivered -- and frames 3, 4 and 6 of both, with no reset in between, are delivered with a private receiver's bits.  A failed round with a
+    synchroniser fails that wait_sync only; a failure reported by the wait for the device (fake_dabgpu_bank_fail_waits) frame 5 only.  3 = DABGPU_ERR_HIP."""
+    out = bank_driver(tmp_path, "failed_round", tag, flags, env, timeout=BANK_CASE_LIMIT_S)
+    assert out["injected"] == 3
+    assert out["status_member0"] == [0, 0, 3, 0, 0, 3, 0] and out["status_member1"] == [0, 3, 0, 0, 0, 3, 0], out
+    assert out["failed_sync"] == [3, 3] and out["delivered_equal_private"] and out["ok"], out
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
+def test_bank_receivers_destroyed_after_the_bank_was_shut_down(tmp_path, tag, flags, env):
+    """Two banked receivers run a frame each, dabgpu_rx_bank_shutdown() is called with both alive, then both are destroyed: the stopped bank stays for its
+    members (a delivered frame is still fetched; what they post is refused with a status), the last leave frees it (ASan: no use after free, no leak), the
+    device has no bank meanwhile (census -1, -1) and the next banked receiver gets a new one that works."""
+    out = bank_driver(tmp_path, "late_destroy", tag, flags, env, timeout=BANK_CASE_LIMIT_S)
+    assert out["frames_equal_private"] and out["bank_after_shutdown"] == [-1, -1] and out["delivered_frame_kept"] and out["new_bank_works"], out
+    assert all(st != 0 for st in out["posts_after_shutdown"]) and out["ok"], out
+
+
+@pytest.mark.parametrize("tag,flags,env", SANITIZERS)
+def test_bank_shutdown_with_jobs_still_queued_wakes_every_waiter(tmp_path, tag, flags, env):
+    """DABGPU_BANK_ROUNDS=1.  The round of frame 0 is held in enqueue, frame 1 and a synchroniser are queued behind it, another thread calls
+    dabgpu_rx_bank_shutdown(), the round is let go: wait_frame of both generations and wait_sync return -- with the result, equal to a private receiver's, or
+    with a status -- shutdown returns, the receiver is destroyed and the process ends inside the limit."""
+    out = bank_driver(tmp_path, "shutdown_with_queue", tag, flags, env, timeout=BANK_CASE_LIMIT_S)
+    assert out["shutdown_returned"] and out["results_equal_private"] and out["ok"], out
+    # the worker forms rounds until the queue is empty: what was accepted before the shutdown is delivered
+    assert out["wait_frame"] == [0, 0] and out["wait_sync"] == 0, out
 
 
 def test_decoders_created_and_dropped_on_the_delivery_thread_under_thread_sanitizer(tmp_path):
