@@ -1953,6 +1953,110 @@ extern "C" int dabgpu_blanker_input_needed(const dabgpu_blanker_stream* params, 
     return DABGPU_OK;
 }
 
+// ---- IQ balance (include/dabgpu.h, "IQ balance"; the arithmetic is iqbal_core.h's, shared with the kernels) ----
+#include "iqbal_core.h"
+
+extern "C" float dabgpu_iqbal_forget(double time_constant_samples) {
+    if (!(time_constant_samples >= (double)DABGPU_IQBAL_TILE)) return 0.0f;                  // (NaN too)
+    if (std::isinf(time_constant_samples)) return 1.0f;
+    return (float)std::exp(-(double)DABGPU_IQBAL_TILE / time_constant_samples);
+}
+
+// TRACK, identity, a memory of 16 mode-I frames, identity until 64 tiles are in (DESIGN.md 4.32 says why)
+extern "C" dabgpu_iqbal_stream dabgpu_iqbal_defaults(void) {
+    return dabgpu_iqbal_stream{DABGPU_IQBAL_TRACK, 0, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, dabgpu_iqbal_forget(16.0 * 196608.0), 65536.0f};
+}
+
+int dabgpu_host_iqbal_plan(const char* who, const dabgpu_iqbal_stream* params, size_t n_streams, size_t max_samples_per_call,
+                           dabgpu_iqbal_geometry* out) {
+    if (out) *out = dabgpu_iqbal_geometry{DABGPU_IQBAL_TILE, 0, 0};
+    if (n_streams == 0 || n_streams > (size_t)(1 << 20)) { dabgpu_set_error("%s: %zu streams (1..1048576 are accepted)", who, n_streams); return DABGPU_ERR_INVALID_ARG; }
+    if (!params) { dabgpu_set_error("%s: null parameters", who); return DABGPU_ERR_INVALID_ARG; }
+    if (max_samples_per_call < DABGPU_IQBAL_TILE || max_samples_per_call > ((size_t)1 << 31) || (max_samples_per_call & (DABGPU_IQBAL_TILE - 1))) {
+        dabgpu_set_error("%s: max_samples_per_call = %zu (a multiple of 1024 in 1024..2^31)", who, max_samples_per_call); return DABGPU_ERR_INVALID_ARG;
+    }
+    for (size_t s = 0; s < n_streams; s++) {
+        const dabgpu_iqbal_stream& P = params[s];
+        if (P.mode != DABGPU_IQBAL_OFF && P.mode != DABGPU_IQBAL_FIXED && P.mode != DABGPU_IQBAL_TRACK) {
+            dabgpu_set_error("%s: stream %zu: mode %d (OFF 0, FIXED 1, TRACK 2)", who, s, P.mode); return DABGPU_ERR_INVALID_ARG;
+        }
+        const float k[6] = {P.a_re, P.a_im, P.b_re, P.b_im, P.c_re, P.c_im};
+        static const char* const name[6] = {"a_re", "a_im", "b_re", "b_im", "c_re", "c_im"};
+        for (int i = 0; i < 6; i++)
+            if (!std::isfinite(k[i])) { dabgpu_set_error("%s: stream %zu: %s is not finite", who, s, name[i]); return DABGPU_ERR_INVALID_ARG; }
+        if (!(P.forget > 0.0f && P.forget <= 1.0f)) {
+            dabgpu_set_error("%s: stream %zu: forget %g (above 0, up to 1)", who, s, (double)P.forget); return DABGPU_ERR_INVALID_ARG;
+        }
+        if (!(std::isfinite(P.min_weight) && P.min_weight >= (float)DABGPU_IQBAL_TILE)) {
+            dabgpu_set_error("%s: stream %zu: min_weight %g (finite, at least 1024)", who, s, (double)P.min_weight); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    const uint64_t tiles = max_samples_per_call / DABGPU_IQBAL_TILE;
+    if (tiles * n_streams > 0x7FFFFFFFull) { dabgpu_set_error("%s: n_streams x max_samples_per_call too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    if (out) {
+        out->tiles_per_call = (uint32_t)tiles;
+        out->scratch_bytes = tiles * n_streams * 32u;
+    }
+    return DABGPU_OK;
+}
+
+int dabgpu_host_iqbal_check_apply(const char* who, size_t n_streams, const dabgpu_iqbal_geometry& geom, const void* in, size_t in_stride_samples,
+                                  size_t n, const void* out, int out_format, size_t* out_stride_bytes, float u8_scale, uint32_t flags,
+                                  bool device_pointers) {
+    if (flags == 0 || (flags & ~(DABGPU_IQBAL_MEASURE | DABGPU_IQBAL_APPLY))) {
+        dabgpu_set_error("%s: flags %u (DABGPU_IQBAL_MEASURE, DABGPU_IQBAL_APPLY or both)", who, flags); return DABGPU_ERR_INVALID_ARG;
+    }
+    const bool apply = (flags & DABGPU_IQBAL_APPLY) != 0;
+    if (n == 0) { dabgpu_set_error("%s: n = 0 (1..2^31 are accepted)", who); return DABGPU_ERR_INVALID_ARG; }
+    // without APPLY nothing is written: the output's rules are checked against the input, which satisfies them
+    size_t no_stride = 0;
+    const int st = dabgpu_host_channel_check_apply(who, n_streams, in, in_stride_samples, n, n, apply ? out : in, apply ? out_format : DABGPU_IQ_RAW_F32L,
+                                                   apply ? out_stride_bytes : &no_stride, apply ? u8_scale : 1.0f, device_pointers);
+    if (st) return st;
+    if (apply && in == out && (out_format != DABGPU_IQ_RAW_F32L || (in_stride_samples != 0 && in_stride_samples * 8 != *out_stride_bytes) ||
+                               (in_stride_samples == 0 && n_streams > 1))) {
+        dabgpu_set_error("%s: in place needs complex float output and rows of the input's stride", who); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (flags & DABGPU_IQBAL_MEASURE) {
+        if (n & (DABGPU_IQBAL_TILE - 1)) { dabgpu_set_error("%s: MEASURE needs n to be a multiple of 1024 (n = %zu)", who, n); return DABGPU_ERR_INVALID_ARG; }
+        if (n / DABGPU_IQBAL_TILE > geom.tiles_per_call) {
+            dabgpu_set_error("%s: MEASURE of %zu samples, the bank was created for %zu per call", who, n, (size_t)geom.tiles_per_call * DABGPU_IQBAL_TILE);
+            return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if ((n / DABGPU_IQBAL_TILE + 2) * n_streams > 0x7FFFFFFFull) { dabgpu_set_error("%s: n_streams x n too large for one call", who); return DABGPU_ERR_INVALID_ARG; }
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_iqbal_plan(const dabgpu_iqbal_stream* params, size_t n_streams, size_t max_samples_per_call, dabgpu_iqbal_geometry* out) {
+    return dabgpu_host_iqbal_plan("iqbal_plan", params, n_streams, max_samples_per_call, out);
+}
+
+extern "C" int dabgpu_iqbal_impairment(double gain_db, double phase_deg, double dc_re, double dc_im, dabgpu_iqbal_stream* out) {
+    if (!out) { dabgpu_set_error("iqbal_impairment: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_iqbal_defaults();
+    out->mode = DABGPU_IQBAL_FIXED;
+    if (!(std::fabs(gain_db) <= 20.0)) { dabgpu_set_error("iqbal_impairment: gain_db %g (-20..20 are accepted)", gain_db); return DABGPU_ERR_INVALID_ARG; }
+    if (!(std::fabs(phase_deg) <= 45.0)) { dabgpu_set_error("iqbal_impairment: phase_deg %g (-45..45 are accepted)", phase_deg); return DABGPU_ERR_INVALID_ARG; }
+    if (!std::isfinite(dc_re) || !std::isfinite(dc_im) || !std::isfinite((float)dc_re) || !std::isfinite((float)dc_im)) {
+        dabgpu_set_error("iqbal_impairment: the DC term is not finite"); return DABGPU_ERR_INVALID_ARG;
+    }
+    const double g = std::pow(10.0, gain_db / 20.0), phi = phase_deg * (3.14159265358979323846 / 180.0);
+    const double gc = g * std::cos(phi), gs = g * std::sin(phi);
+    out->a_re = (float)(0.5 * (1.0 + gc)); out->a_im = (float)(-0.5 * gs);       // K1 = (1 + g e^{-j phi}) / 2
+    out->b_re = (float)(0.5 * (1.0 - gc)); out->b_im = (float)(-0.5 * gs);       // K2 = (1 - g e^{+j phi}) / 2
+    out->c_re = (float)dc_re; out->c_im = (float)dc_im;
+    return DABGPU_OK;
+}
+
+extern "C" int dabgpu_iqbal_solve_host(const dabgpu_iqbal_stream* params, dabgpu_iqbal_record* record) {
+    if (!params || !record) { dabgpu_set_error("iqbal_solve_host: null parameters / record"); return DABGPU_ERR_INVALID_ARG; }
+    const int st = dabgpu_host_iqbal_plan("iqbal_solve_host", params, 1, DABGPU_IQBAL_TILE, nullptr);
+    if (st) return st;
+    dabgpu::iqb_fold_and_solve(*params, *record, 0, [](int) { return (const float*)nullptr; });
+    return DABGPU_OK;
+}
+
 // ---- TII (include/dabgpu.h, "TII"; the table and the carrier rule are tii_core.h's, shared with the kernels) ----
 #include "tii_core.h"
 

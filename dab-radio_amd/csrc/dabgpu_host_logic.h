@@ -311,6 +311,15 @@ int dabgpu_host_interferer_fits(const dabgpu_interferer_geometry& created, const
 int dabgpu_host_interferer_check_apply(const char* who, size_t n_streams, const void* in, size_t in_stride_samples, size_t n_out, const void* out,
                                        int out_format, size_t* out_stride_bytes, float u8_scale, bool device_pointers = true);
 
+// ---- IQ balance planner (iqbal.hip launches from it; include/dabgpu.h, dabgpu_iqbal_plan) ----
+// who = the entry point's name for the refusal text
+int dabgpu_host_iqbal_plan(const char* who, const dabgpu_iqbal_stream* params, size_t n_streams, size_t max_samples_per_call,
+                           dabgpu_iqbal_geometry* out);
+// the arguments of a dabgpu_iqbal_bank_apply call (no device address is dereferenced); *out_stride_bytes: 0 is replaced by the default
+int dabgpu_host_iqbal_check_apply(const char* who, size_t n_streams, const dabgpu_iqbal_geometry& geom, const void* in, size_t in_stride_samples,
+                                  size_t n, const void* out, int out_format, size_t* out_stride_bytes, float u8_scale, uint32_t flags,
+                                  bool device_pointers = true);
+
 // ---- impulse blanker planner (blanker.hip launches from it; include/dabgpu.h, dabgpu_blanker_plan) ----
 // DABGPU_OK and the geometry, or DABGPU_ERR_INVALID_ARG with the reason (stream, field); `who` names the entry point
 int dabgpu_host_blanker_plan(const char* who, const dabgpu_blanker_stream* params, size_t n_streams, dabgpu_blanker_geometry* out);

@@ -108,6 +108,10 @@ ABI_SYMBOLS = [
     "dabgpu_blanker_defaults", "dabgpu_blanker_mask_words", "dabgpu_blanker_plan", "dabgpu_blanker_input_needed", "dabgpu_blanker_bank_create",
     "dabgpu_blanker_bank_destroy", "dabgpu_blanker_bank_set_params", "dabgpu_blanker_bank_seek", "dabgpu_blanker_bank_apply",
     "dabgpu_blanker_bank_apply_host_sync",
+    "dabgpu_iqbal_defaults", "dabgpu_iqbal_plan", "dabgpu_iqbal_impairment", "dabgpu_iqbal_forget", "dabgpu_iqbal_solve_host",
+    "dabgpu_iqbal_bank_create", "dabgpu_iqbal_bank_destroy", "dabgpu_iqbal_bank_set_params", "dabgpu_iqbal_bank_seek", "dabgpu_iqbal_bank_reset",
+    "dabgpu_iqbal_bank_apply", "dabgpu_iqbal_bank_apply_host_sync", "dabgpu_iqbal_bank_read_state_host_sync",
+    "dabgpu_iqbal_bank_read_moments_host_sync",
 ]
 NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
 SYM_PROFILE_SYMBOLS = 75                  # symbol noise profile: product rows of a mode I frame
@@ -287,6 +291,28 @@ class BlankerStream(C.Structure):
 class BlankerGeometry(C.Structure):
     """dabgpu_blanker_geometry"""
     _fields_ = [("reach_blocks", C.c_uint32), ("block_samples", C.c_uint32), ("lds_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# IQ balance (include/dabgpu.h)
+IQBAL_TILE, IQBAL_OFF, IQBAL_FIXED, IQBAL_TRACK, IQBAL_MEASURE, IQBAL_APPLY, IQBAL_MAX_POSITION = 1024, 0, 1, 2, 1, 2, 1 << 62
+
+
+class IqBalanceStream(C.Structure):
+    """dabgpu_iqbal_stream"""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("a_re", C.c_float), ("a_im", C.c_float), ("b_re", C.c_float), ("b_im", C.c_float),
+                ("c_re", C.c_float), ("c_im", C.c_float), ("forget", C.c_float), ("min_weight", C.c_float)]
+
+
+class IqBalanceGeometry(C.Structure):
+    """dabgpu_iqbal_geometry"""
+    _fields_ = [("tile_samples", C.c_uint32), ("tiles_per_call", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+
+# dabgpu_iqbal_record
+IQBAL_RECORD_DTYPE = [("N", "<f4"), ("S", "<f4", (5,)), ("d_re", "<f4"), ("d_im", "<f4"), ("P", "<f4"), ("C_re", "<f4"), ("C_im", "<f4"),
+                      ("w_re", "<f4"), ("w_im", "<f4"), ("a_re", "<f4"), ("a_im", "<f4"), ("b_re", "<f4"), ("b_im", "<f4"), ("c_re", "<f4"),
+                      ("c_im", "<f4"), ("valid", "<u4"), ("tiles_used", "<u8"), ("tiles_skipped", "<u8"), ("calls_refused", "<u4"),
+                      ("reserved", "<u4")]
 
 
 class ResampleStream(C.Structure):
@@ -692,6 +718,23 @@ def lib():
                                                 C.c_void_p]
         L.dabgpu_blanker_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                                           C.c_size_t]
+        L.dabgpu_iqbal_defaults.argtypes, L.dabgpu_iqbal_defaults.restype = [], IqBalanceStream
+        L.dabgpu_iqbal_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.dabgpu_iqbal_impairment.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        L.dabgpu_iqbal_forget.argtypes, L.dabgpu_iqbal_forget.restype = [C.c_double], C.c_float
+        L.dabgpu_iqbal_solve_host.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_iqbal_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.dabgpu_iqbal_bank_destroy.argtypes = [C.c_void_p]
+        L.dabgpu_iqbal_bank_destroy.restype = None
+        L.dabgpu_iqbal_bank_set_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_iqbal_bank_seek.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.dabgpu_iqbal_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_iqbal_bank_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint32,
+                                              C.c_void_p]
+        L.dabgpu_iqbal_bank_apply_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_float,
+                                                        C.c_uint32]
+        L.dabgpu_iqbal_bank_read_state_host_sync.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_iqbal_bank_read_moments_host_sync.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1687,6 +1730,113 @@ class Blanker(_Handle):
             self._h, _ptr(x), in_stride_samples, n_in, n_out, _ptr(out), stride, _ptr(m), words), "dabgpu_blanker_bank_apply_host_sync"),
             h_in, self.n, n_out, IQ_FORMATS.index("raw_f32l"))
         return (y, m) if mask else y
+
+
+def iqbal_stream(mode=None, a=None, b=None, c=None, forget=None, min_weight=None):
+    """an IqBalanceStream: dabgpu_iqbal_defaults (TRACK, identity, a memory of 16 mode-I frames, min_weight 65536) with the given fields
+    replaced; a, b, c complex"""
+    P = lib().dabgpu_iqbal_defaults()
+    if mode is not None:
+        P.mode = int(mode)
+    for name, v in (("a", a), ("b", b), ("c", c)):
+        if v is not None:
+            setattr(P, name + "_re", complex(v).real)
+            setattr(P, name + "_im", complex(v).imag)
+    if forget is not None:
+        P.forget = float(forget)
+    if min_weight is not None:
+        P.min_weight = float(min_weight)
+    return P
+
+
+def iqbal_plan(streams, max_samples_per_call):
+    """dabgpu_iqbal_plan (host only): {"tile_samples", "tiles_per_call", "scratch_bytes"} of a list of IqBalanceStream; raises DabGpuError"""
+    n = len(streams)
+    arr = (IqBalanceStream * n)(*streams) if n else None
+    g = IqBalanceGeometry()
+    check(lib().dabgpu_iqbal_plan(arr, n, int(max_samples_per_call), C.byref(g)), "dabgpu_iqbal_plan")
+    return {"tile_samples": g.tile_samples, "tiles_per_call": g.tiles_per_call, "scratch_bytes": g.scratch_bytes}
+
+
+def iqbal_impairment(gain_db, phase_deg, dc=0j):
+    """dabgpu_iqbal_impairment: the FIXED IqBalanceStream of a front end with these errors (a = K1, b = K2, c = DC)"""
+    P = IqBalanceStream()
+    check(lib().dabgpu_iqbal_impairment(float(gain_db), float(phase_deg), complex(dc).real, complex(dc).imag, C.byref(P)), "dabgpu_iqbal_impairment")
+    return P
+
+
+def iqbal_forget(time_constant_samples):
+    """dabgpu_iqbal_forget: forget per tile of 1024 samples for a time constant in samples (0.0: not at least one tile)"""
+    return float(lib().dabgpu_iqbal_forget(float(time_constant_samples)))
+
+
+def iqbal_solve_host(stream_params, N, S):
+    """dabgpu_iqbal_solve_host: the record (a numpy scalar of IQBAL_RECORD_DTYPE) solved from the state N, S[5]"""
+    import numpy as np
+    rec = np.zeros(1, np.dtype(IQBAL_RECORD_DTYPE))
+    rec["N"], rec["S"] = N, np.asarray(S, np.float32)
+    check(lib().dabgpu_iqbal_solve_host(C.byref(stream_params) if stream_params is not None else None, _ptr(rec)), "dabgpu_iqbal_solve_host")
+    return rec[0]
+
+
+class IqBalance(_Handle):
+    """dabgpu_iqbal_bank: DC offset and mirror image made (FIXED) or removed blindly (TRACK) in n streams; position and records live on the
+    device"""
+    _destroy = "dabgpu_iqbal_bank_destroy"
+
+    def __init__(self, ctx, streams, max_samples_per_call):
+        self._ctx = ctx
+        self.n = len(streams)
+        self.plan = iqbal_plan(streams, max_samples_per_call)
+        arr = (IqBalanceStream * self.n)(*streams)
+        self._h = C.c_void_p()
+        check(lib().dabgpu_iqbal_bank_create(ctx._h, self.n, arr, int(max_samples_per_call), C.byref(self._h)), "dabgpu_iqbal_bank_create")
+
+    def set_params(self, streams, stream=None):
+        assert len(streams) == self.n
+        arr = (IqBalanceStream * self.n)(*streams)
+        check(lib().dabgpu_iqbal_bank_set_params(self._h, arr, Context._stream(stream)), "dabgpu_iqbal_bank_set_params")
+
+    def seek(self, position, stream=None):
+        check(lib().dabgpu_iqbal_bank_seek(self._h, int(position), Context._stream(stream)), "dabgpu_iqbal_bank_seek")
+
+    def reset(self, stream=None):
+        check(lib().dabgpu_iqbal_bank_reset(self._h, Context._stream(stream)), "dabgpu_iqbal_bank_reset")
+
+    def apply(self, d_in, n, d_out=None, flags=IQBAL_APPLY, in_stride_samples=0, out_format=None, out_stride_bytes=0, u8_scale=1.0, stream=None):
+        """d_in complex float (device) -> d_out rows of n samples, complex float (default) or u8 pairs (flags with IQBAL_APPLY; d_out may be
+        d_in), and / or the call's tiles folded into the records (IQBAL_MEASURE); asynchronous"""
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        check(lib().dabgpu_iqbal_bank_apply(self._h, _ptr(d_in), in_stride_samples, n, _ptr(d_out), fmt, out_stride_bytes, float(u8_scale), int(flags),
+                                            Context._stream(stream)), "dabgpu_iqbal_bank_apply")
+
+    def apply_host(self, h_in, n, flags=IQBAL_APPLY, in_stride_samples=0, out_format=None, u8_scale=1.0):
+        """h_in [n_streams][>= n] complex64 (or [>= n] shared with in_stride_samples = 0) -> [n_streams][n] complex64 / [n_streams][n][2] uint8;
+        None for a MEASURE-only call"""
+        import numpy as np
+        fmt = IQ_FORMATS.index("raw_f32l") if out_format is None else int(out_format)
+        if not flags & IQBAL_APPLY:
+            x = np.ascontiguousarray(h_in, dtype=np.complex64)
+            check(lib().dabgpu_iqbal_bank_apply_host_sync(self._h, _ptr(x), in_stride_samples, n, None, fmt, 0, 1.0, int(flags)),
+                  "dabgpu_iqbal_bank_apply_host_sync")
+            return None
+        return _host_form(lambda x, n_in, out, stride: check(lib().dabgpu_iqbal_bank_apply_host_sync(
+            self._h, _ptr(x), in_stride_samples, n, _ptr(out), fmt, stride, float(u8_scale), int(flags)), "dabgpu_iqbal_bank_apply_host_sync"),
+            h_in, self.n, n, fmt)
+
+    def read_state(self):
+        """the n records as a numpy array of IQBAL_RECORD_DTYPE (waits for the context's stream)"""
+        import numpy as np
+        rec = np.zeros(self.n, np.dtype(IQBAL_RECORD_DTYPE))
+        check(lib().dabgpu_iqbal_bank_read_state_host_sync(self._h, _ptr(rec)), "dabgpu_iqbal_bank_read_state_host_sync")
+        return rec
+
+    def read_moments(self, n_tiles):
+        """the five sums of the last MEASURE call's first n_tiles tiles, [n_streams][n_tiles][5] float32 (waits for the context's stream)"""
+        import numpy as np
+        m = np.zeros((self.n, n_tiles, 8), np.float32)
+        check(lib().dabgpu_iqbal_bank_read_moments_host_sync(self._h, int(n_tiles), _ptr(m)), "dabgpu_iqbal_bank_read_moments_host_sync")
+        return np.ascontiguousarray(m[:, :, :5])
 
 
 def resample_step(in_rate_hz=2048000.0, out_rate_hz=2048000.0, ppm=0.0):

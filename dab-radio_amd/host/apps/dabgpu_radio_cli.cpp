@@ -69,6 +69,15 @@
 // 193920, with --snr 98272.  THRESHOLD is taken only where the next argument is a number ("--blank -i FILE" and "--blank abc" leave it at 3;
 // "abc" is then an unknown argument).  Absent: no blanker is made and the tool does what it did.
 //
+// --iq-balance [TIME_CONSTANT_FRAMES] (not in the reference; include/dabgpu.h "IQ balance"): the readers' complex samples go first -- ahead of
+// --input-rate, --channel-offset-hz and --blank -- through a DAB_Stream_IQ_Balancer, which removes the DC term and the mirror image of a
+// zero-IF front end blindly: a frame's worth of samples at the capture's rate (rounded up to whole tiles of 1024) is measured, then mapped
+// with the coefficients that include it, so the first frame is corrected already; the rest is flushed at the end of the input.  The
+// estimator's memory is TIME_CONSTANT_FRAMES frames (16 unless given; taken only where the next argument is a number, as --blank's).  The
+// OFDM stage only.  --iq-report prints one "iq frame=N dc=RE,IM w=RE,IM irr_db=X" line per measured frame on stdout: the DC term, the image
+// coefficient w = K2 / conj(K1) and the front end's own rejection -20 log10 |w|, computed on the host.  Absent: no balancer is made and
+// the tool does what it did.
+//
 // --input-rate HZ (not in the reference; include/dabgpu.h "Resampler"): the capture's sample rate, e.g. 2400000, 2560000, 3072000 or 4096000.
 // Every block is resampled to 2.048 MHz on the device between the format conversion and OFDM_Demod (DAB_Stream_Resampler: the outputs do
 // not depend on the block size).  Absent or 2048000: no resampler is made and the tool does what it did.
@@ -103,6 +112,7 @@
 #include "dab/tx/dab_channeliser.h"
 #include "dab/tx/dab_resampler.h"
 #include "ofdm/dab_blanker.h"
+#include "ofdm/dab_iq_balancer.h"
 #include "ofdm/ofdm_helpers.h"
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
@@ -143,6 +153,8 @@ struct Args {
     bool alpha_given = false;
     bool blank = false;
     float blank_threshold = 3.0f;
+    bool iq_balance = false, iq_report = false;
+    double iq_frames = 16.0;
 };
 
 static void usage(const char* argv0) {
@@ -154,6 +166,7 @@ static void usage(const char* argv0) {
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
         "  [--soft-bits normalised|csi|banded|banded-dd] [--soft-level 1..127] [--alpha A] [--symbol-weights] [--blank [THRESHOLD]]\n"
+        "  [--iq-balance [TIME_CONSTANT_FRAMES]] [--iq-report]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
     fprintf(stderr, "\n");
@@ -229,6 +242,15 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--symbol-weights") args.symbol_weights = true;
         else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
+        else if (a == "--iq-report") args.iq_report = true;
+        else if (a == "--iq-balance") {
+            args.iq_balance = true;
+            char* end = nullptr;                                                  // the value is optional, as --blank's
+            if (i + 1 < argc) {
+                const double t = std::strtod(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == '\0') { args.iq_frames = t; i++; }
+            }
+        }
         else if (a == "--blank") {
             args.blank = true;
             char* end = nullptr;                                                  // the value is optional: taken only where the next argument is a number
@@ -243,6 +265,9 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else throw std::runtime_error("unknown argument '" + a + "'");
     }
     if (args.ber && !args.is_dab_used) throw std::runtime_error("--ber needs the channel decode stage");
+    if ((args.iq_balance || args.iq_report) && !args.is_ofdm_used) throw std::runtime_error("--iq-balance needs the OFDM stage");
+    if (args.iq_report && !args.iq_balance) throw std::runtime_error("--iq-report needs --iq-balance");
+    if (args.iq_balance && !(args.iq_frames >= 0.25 && args.iq_frames <= 1e6)) throw std::runtime_error("--iq-balance: a time constant of 0.25 .. 1e6 frames");
     if (args.blank && !args.is_ofdm_used) throw std::runtime_error("--blank needs the OFDM stage");
     if (args.blank && args.transmission_mode != 1) throw std::runtime_error("--blank is available in transmission mode 1 only");
     if (args.blank && !(args.blank_threshold > 1.0f && args.blank_threshold <= 1024.0f)) throw std::runtime_error("--blank: a threshold above 1, up to 1024");
@@ -550,12 +575,25 @@ static int run(const Args& args) {
             blanker->Process(x, blanked);
             if (!blanked.empty()) demod->Process(blanked);
         };
-        for (;;) {
-            const size_t length = reader->read(block);
-            if (length == 0) break;
+        // --iq-balance: first on the readers' samples, a frame's worth of the capture's rate at a time
+        std::unique_ptr<DAB_Stream_IQ_Balancer> balancer;
+        std::vector<std::complex<float>> balanced;
+        uint64_t iq_reported = 0;
+        if (args.iq_balance) {
+            const size_t frame = ((size_t)std::ceil(196608.0 * args.input_rate / 2.048e6) + DABGPU_IQBAL_TILE - 1) & ~(size_t)(DABGPU_IQBAL_TILE - 1);
+            balancer = std::make_unique<DAB_Stream_IQ_Balancer>(DAB_IQ_Balancer::Defaults(args.iq_frames * (double)frame), frame, true);
+        }
+        auto iq_report = [&]() {
+            if (!args.iq_report || balancer->Chunks() == iq_reported) return;
+            iq_reported = balancer->Chunks();
+            const dabgpu_iqbal_record R = balancer->State();
+            printf("iq frame=%llu dc=%.6g,%.6g w=%.6g,%.6g irr_db=%.2f\n", (unsigned long long)iq_reported, (double)R.d_re, (double)R.d_im, (double)R.w_re,
+                   (double)R.w_im, DAB_IQ_Balancer::FrontEndRejectionDb(R));
+        };
+        auto ingest = [&](tcb::span<const std::complex<float>> x) {
             if (channeliser) {
                 split.clear();
-                channeliser->Process(tcb::span<const std::complex<float>>(block.data(), length), split);
+                channeliser->Process(x, split);
                 if (!split.empty() && !split[0].empty()) {
                     if (resampler) {
                         resampled.clear();
@@ -565,13 +603,38 @@ static int run(const Args& args) {
                 }
             } else if (resampler) {
                 resampled.clear();
-                resampler->Process(tcb::span<const std::complex<float>>(block.data(), length), resampled);
+                resampler->Process(x, resampled);
                 if (!resampled.empty()) feed(resampled);
             } else
-            feed(tcb::span<const std::complex<float>>(block.data(), length));
+            feed(x);
+        };
+        // what the balancer emits (a frame's worth at a time) goes on in pieces of the block size, so that the observers below see the calls
+        // they see without it
+        auto ingest_balanced = [&]() {
+            for (size_t at = 0; at < balanced.size(); at += block.size()) {
+                ingest(tcb::span<const std::complex<float>>(balanced.data() + at, std::min(block.size(), balanced.size() - at)));
+                if (tii || snr || profile) demod->Synchronize();
+                if (snr) snr_poll();
+            }
+        };
+        for (;;) {
+            const size_t length = reader->read(block);
+            if (length == 0) break;
+            if (balancer) {
+                balanced.clear();
+                balancer->Process(tcb::span<const std::complex<float>>(block.data(), length), balanced);
+                iq_report();
+                ingest_balanced();
+            } else
+            ingest(tcb::span<const std::complex<float>>(block.data(), length));
             if (tii || snr || profile) demod->Synchronize();                                   // the observer reads the head of the correlation buffer
             if (snr) snr_poll();
             if (length != block.size()) break;
+        }
+        if (balancer) {                                                                      // the end of the input: what the balancer still holds
+            balanced.clear();
+            balancer->Flush(balanced);
+            ingest_balanced();
         }
         if (blanker) {                                                                       // the end of the input: what the blanker still holds
             blanked.clear();

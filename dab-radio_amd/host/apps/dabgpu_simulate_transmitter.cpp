@@ -54,6 +54,12 @@
 //   --interferer white:IS_DB                     white Gaussian noise over the whole sampled band (with a gate: bursts)
 //   --interferer-gate PERIOD:ON[:OFFSET]         for the --interferer before it: on for ON of every PERIOD samples, from sample OFFSET on
 //   --interferer-seed N                          default 1
+// Front end (not in the reference; include/dabgpu.h "IQ balance", DAB_IQ_Balancer): the gain and phase error between I and Q and the DC
+// term of a zero-IF tuner, applied last before the quantiser: behind the channel, the resampler and --wideband / --neighbour, so that a
+// neighbour's mirror image lands where the tuner would put it.
+//   --iq-imbalance GAIN_DB:PHASE_DEG   Q against I: -20..20 dB, -45..45 degrees; y = K1 x + K2 conj(x), K1 = (1 + g e^{-j phi}) / 2,
+//                                      K2 = (1 - g e^{j phi}) / 2; 0.42:3 rejects the mirror frequency by 29 dB
+//   --dc-offset RE:IM                  added behind it, in the units of the samples before the u8 scale (a data carrier has amplitude 1)
 // TII (not in the reference, mode I; include/dabgpu.h "TII"):
 //   --tii P:C[:AMP]                repeatable, up to 4: a transmitter with main id P (0..69), sub id C (0..23) and amplitude AMP (default 1 =
 //                                  the power of a data carrier) fills the NULL period of every other frame, the first one included; the
@@ -76,6 +82,7 @@
 #include "dab/tx/dab_interferer.h"
 #include "dab/tx/dab_resampler.h"
 #include "dabgpu.h"
+#include "ofdm/dab_iq_balancer.h"
 #include "ofdm/dab_ofdm_params_ref.h"
 #include "ofdm/dab_prs_ref.h"
 
@@ -132,7 +139,31 @@ struct Args {
     double centre_offset_hz = 0.0;
     struct Neighbour { double offset_hz, level_db; };
     std::vector<Neighbour> neighbours;
+    // front end: last before the quantiser
+    bool front_end = false;
+    double iq_gain_db = 0.0, iq_phase_deg = 0.0, dc_re = 0.0, dc_im = 0.0;
 };
+
+// --iq-imbalance / --dc-offset: the tuner's widely-linear map on the samples on their way to the quantiser
+struct FrontEnd {
+    DAB_IQ_Balancer bank;
+    std::vector<uint8_t> bytes;
+    explicit FrontEnd(const Args& args)
+        : bank(DAB_IQ_Balancer::Impairment(args.iq_gain_db, args.iq_phase_deg, {args.dc_re, args.dc_im}), DABGPU_IQBAL_TILE) {}
+    // the next samples of the output stream, quantised and written; false when a write fails
+    bool Write(tcb::span<const std::complex<float>> x, float u8_scale, FILE* fp_out) {
+        if (x.empty()) return true;
+        bytes.resize(2 * x.size());
+        bank.ApplyU8(bytes, x, u8_scale);
+        const size_t nb_write = fwrite(bytes.data(), 2, x.size(), fp_out);
+        if (nb_write != x.size()) { fprintf(stderr, "Failed to write out frame %zu/%zu\n", nb_write, x.size()); return false; }
+        return true;
+    }
+};
+static std::unique_ptr<FrontEnd> make_front_end(const Args& args) {
+    if (!args.front_end) return nullptr;
+    return std::make_unique<FrontEnd>(args);
+}
 
 // the wideband capture behind the channel and the resampler (include/dabgpu.h "Channeliser"): the block at --centre-offset-hz and its
 // --neighbour blocks, which carry the block's own stream a fixed count of samples late, combined at --wideband times the block rate
@@ -140,6 +171,7 @@ struct Wideband {
     std::unique_ptr<DAB_Stream_Combiner> combiner;
     std::vector<size_t> delay;                                 // per row, in block samples (row 0: the wanted block, 0)
     std::vector<std::complex<float>> history, rows;            // the last max(delay) samples of the stream; the rows of one call
+    std::vector<std::complex<float>> combined;                 // with a front end behind the combiner: its output as complex float
     std::vector<uint8_t> bytes;
     float u8_scale = 1.0f;
     Wideband(const Args& args, float block_u8_scale, int nb_carriers) {
@@ -161,12 +193,17 @@ struct Wideband {
         u8_scale = (float)std::min((double)block_u8_scale, 127.5 / (4.0 * std::sqrt(0.5 * (double)nb_carriers * power)));
     }
     // the next samples of the block stream through the combiner to the file; false when a write fails
-    bool Write(tcb::span<const std::complex<float>> block, FILE* fp_out) {
+    bool Write(tcb::span<const std::complex<float>> block, FILE* fp_out, FrontEnd* front = nullptr) {
         const size_t n = block.size(), H = history.size();
         history.insert(history.end(), block.begin(), block.end());          // stream samples (now - H) .. (now + n)
         rows.resize(delay.size() * n);
         for (size_t k = 0; k < delay.size(); k++) std::copy(history.begin() + (long)(H - delay[k]), history.begin() + (long)(H - delay[k] + n), rows.begin() + (long)(k * n));
         history.erase(history.begin(), history.begin() + (long)n);
+        if (front) {
+            combined.clear();
+            combiner->Process(rows, combined);
+            return front->Write(combined, u8_scale, fp_out);
+        }
         bytes.clear();
         combiner->ProcessU8(rows, bytes, u8_scale);
         const size_t nb_write = fwrite(bytes.data(), 2, bytes.size() / 2, fp_out);
@@ -179,11 +216,12 @@ static std::unique_ptr<Wideband> make_wideband(const Args& args, float block_u8_
     return std::make_unique<Wideband>(args, block_u8_scale, nb_carriers);
 }
 // one frame of the channel's output on its way out: through the resampler where there is one, then the combiner
-static bool write_wideband(Wideband& wide, DAB_Stream_Resampler* rs, tcb::span<const std::complex<float>> frame, std::vector<std::complex<float>>& resampled, FILE* fp_out) {
-    if (!rs) return wide.Write(frame, fp_out);
+static bool write_wideband(Wideband& wide, DAB_Stream_Resampler* rs, tcb::span<const std::complex<float>> frame, std::vector<std::complex<float>>& resampled, FILE* fp_out,
+                           FrontEnd* front = nullptr) {
+    if (!rs) return wide.Write(frame, fp_out, front);
     resampled.clear();
     rs->Process(frame, resampled);
-    return resampled.empty() ? true : wide.Write(resampled, fp_out);
+    return resampled.empty() ? true : wide.Write(resampled, fp_out, front);
 }
 
 // the receiver's ADC behind the channel (include/dabgpu.h "Resampler"): --output-rate HZ samples per second, its sample period --clock-ppm
@@ -195,7 +233,13 @@ static std::unique_ptr<DAB_Stream_Resampler> make_resampler(const Args& args) {
     return std::make_unique<DAB_Stream_Resampler>(step, args.frac_delay);
 }
 // one frame of the 2.048 MHz stream through the resampler to the file; false when a write fails
-static bool write_resampled(DAB_Stream_Resampler& rs, tcb::span<const std::complex<float>> frame, float u8_scale, std::vector<uint8_t>& bytes, FILE* fp_out) {
+static bool write_resampled(DAB_Stream_Resampler& rs, tcb::span<const std::complex<float>> frame, float u8_scale, std::vector<uint8_t>& bytes, FILE* fp_out,
+                            FrontEnd* front = nullptr, std::vector<std::complex<float>>* resampled = nullptr) {
+    if (front) {
+        resampled->clear();
+        rs.Process(frame, *resampled);
+        return front->Write(*resampled, u8_scale, fp_out);
+    }
     bytes.clear();
     rs.ProcessU8(frame, bytes, u8_scale);
     const size_t nb_write = fwrite(bytes.data(), 2, bytes.size() / 2, fp_out);
@@ -396,7 +440,8 @@ static int run_coded(const Args& args, FILE* fp_out) {
     auto resampler = make_resampler(args);
     const float u8_scale = (1.0f / 1536.0f * 4.0f) * 127.5f;
     auto wide = make_wideband(args, u8_scale, 1536);
-    std::vector<std::complex<float>> impaired((resampler || wide || interferer) ? S : 0), resampled;
+    auto front = make_front_end(args);
+    std::vector<std::complex<float>> impaired((resampler || wide || interferer || front) ? S : 0), resampled;
     int rc = 0;
     for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
         fibs.read(fib.data(), 360);
@@ -408,20 +453,24 @@ static int run_coded(const Args& args, FILE* fp_out) {
                 dabgpu_channel_stream now = cp;
                 now.start = cp.start + (k - 1) * (long long)S;             // window sample 0 = stream sample (k - 1) S
                 channel->SetParams(now);
-                if (resampler || wide || interferer) channel->Apply(impaired, window, false);
+                if (resampler || wide || interferer || front) channel->Apply(impaired, window, false);
                 else channel->ApplyU8(quantised, window, false, u8_scale);
-                if (interferer && (resampler || wide)) interferer->Apply(impaired, impaired);
+                if (interferer && (resampler || wide || front)) interferer->Apply(impaired, impaired);
                 else if (interferer) interferer->ApplyU8(quantised, impaired, u8_scale);
             }
         } else
         st = dabgpu_tx_bank_transmit_frames_host_sync(bank, fib.data(), pay.data(), 1, frequency_norm, quantised.data(), DABGPU_IQ_RAW_U8);
         if (st != DABGPU_OK) { fprintf(stderr, "Failed to create the OFDM frame: %s -- %s\n", dabgpu_strerror(st), dabgpu_last_error()); rc = 1; break; }
         if (wide) {
-            if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out)) break;
+            if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out, front.get())) break;
             continue;
         }
         if (resampler) {
-            if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
+            if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out, front.get(), &resampled)) break;
+            continue;
+        }
+        if (front) {                                                         // (--iq-imbalance makes the channel: `impaired` holds the frame)
+            if (!front->Write(impaired, u8_scale, fp_out)) break;
             continue;
         }
         const size_t nb_write = fwrite(quantised.data(), 2, DABGPU_NB_FRAME_SAMPLES, fp_out);
@@ -439,6 +488,7 @@ static void usage(const char* argv0) {
                     "          [--interferer tone:OFFSET_HZ:IS_DB|band:OFFSET_HZ:WIDTH_HZ:IS_DB|white:IS_DB]... [--interferer-gate PERIOD:ON[:OFFSET]]\n"
                     "          [--interferer-seed N] [--clock-ppm X] [--frac-delay D] [--output-rate HZ]\n"
                     "          [--wideband D] [--centre-offset-hz F] [--neighbour OFFSET_HZ:LEVEL_DB]...\n"
+                    "          [--iq-imbalance GAIN_DB:PHASE_DEG] [--dc-offset RE:IM]\n"
                     "Simulates an OFDM transmitter sending random data (8-bit IQ at 2.048 MHz; default output stdout);\n"
                     "with --subchannel / --fib-file / --payload-file / --seed the frames are channel coded (mode I) from that data;\n"
                     "with --snr-db / --cfo-hz / --timing-offset / --tap / --noise-seed the signal passes a channel on the device before it is\n"
@@ -490,6 +540,14 @@ static bool parse_args(int argc, char** argv, Args& args) {
         else if (a == "--output-rate") { args.output_rate = std::stod(value()); args.resample = true; }
         else if (a == "--wideband") { args.wideband = std::stoi(value()); have_wideband = true; }
         else if (a == "--centre-offset-hz") { args.centre_offset_hz = std::stod(value()); have_wide_option = true; }
+        else if (a == "--iq-imbalance" || a == "--dc-offset") {
+            const std::string v = value();
+            const size_t colon = v.find(':');
+            if (colon == std::string::npos) throw std::runtime_error(a + " expects two numbers, A:B: '" + v + "'");
+            const double first = std::stod(v.substr(0, colon)), second = std::stod(v.substr(colon + 1));
+            if (a == "--iq-imbalance") { args.iq_gain_db = first; args.iq_phase_deg = second; } else { args.dc_re = first; args.dc_im = second; }
+            args.front_end = true; args.channel = true;
+        }
         else if (a == "--neighbour") {
             const std::string v = value();
             const size_t colon = v.find(':');
@@ -522,6 +580,10 @@ static bool parse_args(int argc, char** argv, Args& args) {
         if (!(args.frac_delay >= 0.0 && args.frac_delay < 1.0)) throw std::runtime_error("--frac-delay is a fraction of a sample: 0 <= D < 1");
         if (!(args.output_rate >= 1.024e6 && args.output_rate <= 4.096e6)) throw std::runtime_error("--output-rate: 1024000 .. 4096000");
         if (!(std::fabs(args.clock_ppm) <= 1000.0)) throw std::runtime_error("--clock-ppm: -1000 .. 1000");
+    }
+    if (args.front_end) {
+        if (!(std::fabs(args.iq_gain_db) <= 20.0) || !(std::fabs(args.iq_phase_deg) <= 45.0)) throw std::runtime_error("--iq-imbalance: -20 .. 20 dB, -45 .. 45 degrees");
+        if (!std::isfinite(args.dc_re) || !std::isfinite(args.dc_im)) throw std::runtime_error("--dc-offset: two finite numbers");
     }
     if (!args.profile.empty() && !args.taps.empty()) throw std::runtime_error("--profile is not available with --tap");
     if (args.interferers.size() > DABGPU_INTERFERER_MAX) throw std::runtime_error("--interferer: at most 4 sources");
@@ -604,18 +666,25 @@ int main(int argc, char** argv) {
             auto interferer = make_interferer(args, cp, (int)params.nb_data_carriers);
             auto resampler = make_resampler(args);
             auto wide = make_wideband(args, u8_scale, (int)params.nb_data_carriers);
-            std::vector<std::complex<float>> impaired((resampler || wide || interferer) ? frame_size : 0), resampled;
+            auto front = make_front_end(args);
+            std::vector<std::complex<float>> impaired((resampler || wide || interferer || front) ? frame_size : 0), resampled;
             for (long long k = 0; args.frames < 0 || k < args.frames; k++) {
                 if (wide) {
                     channel.Apply(impaired, frame, true);
                     if (interferer) interferer->Apply(impaired, impaired);
-                    if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out)) break;
+                    if (!write_wideband(*wide, resampler.get(), impaired, resampled, fp_out, front.get())) break;
                     continue;
                 }
                 if (resampler) {
                     channel.Apply(impaired, frame, true);
                     if (interferer) interferer->Apply(impaired, impaired);
-                    if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out)) break;
+                    if (!write_resampled(*resampler, impaired, u8_scale, quantised, fp_out, front.get(), &resampled)) break;
+                    continue;
+                }
+                if (front) {
+                    channel.Apply(impaired, frame, true);
+                    if (interferer) interferer->Apply(impaired, impaired);
+                    if (!front->Write(impaired, u8_scale, fp_out)) break;
                     continue;
                 }
                 if (interferer) {

@@ -1506,6 +1506,102 @@ int dabgpu_blanker_bank_apply_host_sync(dabgpu_blanker_bank *bank, const float *
                                         void *h_out, size_t out_stride_bytes, uint32_t *h_mask, size_t mask_stride_words);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * IQ balance: the DC term and the mirror image of a zero-IF front end, in n_streams independent streams of complex float samples --
+ * made (the impairment behind the simulator's channel) and removed (blindly, ahead of resampler, channeliser and blanker) by one
+ * widely-linear map per sample.  The reference has nothing comparable; the definition is this library's own, written once in
+ * dab-radio_amd/csrc/iqbal_core.h for the kernels (iqbal.hip), for dabgpu_iqbal_solve_host and for the host model the tests build from
+ * the same header (tests/cpp/iqbal_host_model.cpp), pinned to an independent numpy model (tests/iqbal_model.py,
+ * tests/test_iqbal_model.py) and on the device bit for bit to the host model (tests/test_gpu_iqbal.py).  Derivation, bounds and
+ * measurements: DESIGN.md 4.32.
+ *
+ *   map     z = a y + b conj(y) + c, complex float a, b, c per stream; each component starts from c and takes the terms of a, then those
+ *           of b, one fmaf each (iqbal_core.h, iqb_map).  A stream of mode OFF copies its input bit for bit.
+ *   tile    1024 ABSOLUTE samples (the bank's 64-bit position + the sample's index in the call).  Its five float32 moments, of the RAW
+ *           input: sum re, sum im, sum |y|^2 = fmaf(im, im, re re), sum fmaf(-im, im, re re), sum (2 re) im, each a 10-level pairwise
+ *           tree over the sample index; the level order (index bits 0, 9, 1 .. 8) is iqbal_core.h's IQB_TREE_BITS.
+ *   fold    state N, S[5] per TRACK stream; for each tile of a MEASURE call in increasing order N = fmaf(forget, N, 1024),
+ *           S_k = fmaf(forget, S_k, m_k).  A tile with a moment that is not finite is skipped and counted (tiles_skipped).
+ *   solve   r = 1 / N, d = (S_0, S_1) r, P = S_2 r - |d|^2, Q = (S_3, S_4) r - d^2, C = Q (1 / P), w_0 = C / 2 and three steps
+ *           w = (C / 2)(1 + |w|^2) (the fixed point of C = 2 w / (1 + |w|^2), w = K2 / conj(K1)); a = 1, b = -w, c = -(d - w conj(d)).
+ *           Identity (a = 1, b = c = 0, valid = 0) while N < min_weight, or P is not a normal positive float, or |C|^2 >= 1.  The
+ *           residual complex gain K1 (1 - |w|^2) stays in the samples: DQPSK does not see it.
+ * dabgpu_iqbal_defaults: TRACK, a = 1, b = c = 0, forget = dabgpu_iqbal_forget(16 mode-I frames), min_weight 65536.
+ * dabgpu_iqbal_plan (host only): refused with DABGPU_ERR_INVALID_ARG, naming stream and field: n_streams outside 1..1048576, NULL
+ * params, a mode outside OFF / FIXED / TRACK, a coefficient that is not finite, forget outside (0, 1], min_weight not finite or below
+ * 1024 (one tile), max_samples_per_call not a multiple of 1024 in 1024..2^31.
+ *   tile_samples    1024
+ *   tiles_per_call  max_samples_per_call / 1024: the tiles a MEASURE call may hold
+ *   scratch_bytes   n_streams x tiles_per_call x 32: the bank's tile records
+ * dabgpu_iqbal_impairment: a FIXED stream for a front end with gain error gain_db (Q against I) and phase error phase_deg and DC
+ * dc_re + j dc_im: a = K1 = (1 + g e^{-j phi}) / 2, b = K2 = (1 - g e^{j phi}) / 2, c = DC, formed in double and rounded once.  Refused:
+ * |gain_db| > 20, |phase_deg| > 45, anything not finite.
+ * dabgpu_iqbal_forget: forget per tile for a time constant in samples, exp(-1024 / tau) rounded to float (1 for an infinite one); 0
+ * for a time constant that is not at least one tile.
+ * dabgpu_iqbal_solve_host: the solve above of the state in record->N, record->S with the stream's min_weight; fills the other fields of
+ * the record except the counters. */
+#define DABGPU_IQBAL_TILE 1024
+#define DABGPU_IQBAL_OFF 0
+#define DABGPU_IQBAL_FIXED 1
+#define DABGPU_IQBAL_TRACK 2
+#define DABGPU_IQBAL_MEASURE 1u                             /* flags of _apply */
+#define DABGPU_IQBAL_APPLY 2u
+#define DABGPU_IQBAL_MAX_POSITION ((uint64_t)1 << 62)
+typedef struct {
+    int32_t mode, reserved;
+    float a_re, a_im, b_re, b_im, c_re, c_im;   /* FIXED: the map's coefficients */
+    float forget, min_weight;                   /* TRACK */
+} dabgpu_iqbal_stream;
+typedef struct { uint32_t tile_samples, tiles_per_call; uint64_t scratch_bytes; } dabgpu_iqbal_geometry;
+typedef struct {
+    float N, S[5];                              /* the fold's state */
+    float d_re, d_im, P, C_re, C_im, w_re, w_im;
+    float a_re, a_im, b_re, b_im, c_re, c_im;   /* what the next APPLY maps a TRACK stream with */
+    uint32_t valid;                             /* 1: the coefficients are the solve's; 0: identity */
+    uint64_t tiles_used, tiles_skipped;
+    uint32_t calls_refused, reserved;           /* MEASURE calls that found the position off a tile edge (the device refuses them) */
+} dabgpu_iqbal_record;
+dabgpu_iqbal_stream dabgpu_iqbal_defaults(void);
+int dabgpu_iqbal_plan(const dabgpu_iqbal_stream *params, size_t n_streams, size_t max_samples_per_call, dabgpu_iqbal_geometry *out);
+int dabgpu_iqbal_impairment(double gain_db, double phase_deg, double dc_re, double dc_im, dabgpu_iqbal_stream *out);
+float dabgpu_iqbal_forget(double time_constant_samples);
+int dabgpu_iqbal_solve_host(const dabgpu_iqbal_stream *params, dabgpu_iqbal_record *record);
+
+/* IQ balance bank: the parameters and records of n_streams streams, their common position and the tile scratch on the device.
+ *   flags   DABGPU_IQBAL_MEASURE, DABGPU_IQBAL_APPLY or both.  Both is ONE pass: the output is mapped with the coefficients as they stood
+ *           before the call, then the call's tiles are folded and solved.  Priming: a MEASURE call, _seek back, an APPLY call.
+ *   d_in    stream s reads n complex float from d_in + s * in_stride_samples (0: one shared row; otherwise >= n and even), 16-byte aligned.
+ *   d_out   APPLY: stream s writes n samples from d_out + s * out_stride_bytes on (a multiple of 16 that holds n samples; 0 = the
+ *           default), 16-byte aligned, complex float or u8 pairs (ch_u8 with u8_scale).  d_out == d_in is allowed for complex float with
+ *           equal strides: the map is pointwise.  NULL without APPLY.
+ *   MEASURE needs n to be a multiple of 1024 up to the bank's max_samples_per_call (refused on the host) and the position to be a
+ *           multiple of 1024.  The position lives on the device, so that refusal is the device's: the call writes nothing, folds
+ *           nothing, leaves the position where it was and raises calls_refused of every record; the host form returns
+ *           DABGPU_ERR_INVALID_ARG then.  Frames of all four transmission modes are multiples of 1024.
+ *   APPLY alone takes any position and any n; partial tiles at either end are stored sample by sample.
+ * A call is up to three launches on `stream`: the work kernel (one 256-thread workgroup per stream and tile), with MEASURE the
+ * fold-and-solve kernel (one lane per stream, tiles in increasing order, no atomics), and the position advance.  No host state changes,
+ * so a call may be captured and its replays continue the stream.  _seek sets the position (<= 2^62), _set_params replaces all
+ * parameters and keeps the records, _reset returns the records to their first state (N = 0, identity, counters 0). */
+typedef struct dabgpu_iqbal_bank dabgpu_iqbal_bank;
+int dabgpu_iqbal_bank_create(dabgpu_ctx *ctx, size_t n_streams, const dabgpu_iqbal_stream *h_params, size_t max_samples_per_call,
+                             dabgpu_iqbal_bank **out);
+void dabgpu_iqbal_bank_destroy(dabgpu_iqbal_bank *bank);
+int dabgpu_iqbal_bank_set_params(dabgpu_iqbal_bank *bank, const dabgpu_iqbal_stream *h_params, void *stream);
+int dabgpu_iqbal_bank_seek(dabgpu_iqbal_bank *bank, uint64_t position, void *stream);
+int dabgpu_iqbal_bank_reset(dabgpu_iqbal_bank *bank, void *stream);
+int dabgpu_iqbal_bank_apply(dabgpu_iqbal_bank *bank, const float *d_in, size_t in_stride_samples, size_t n, void *d_out, int out_format,
+                            size_t out_stride_bytes, float u8_scale, uint32_t flags, void *stream);
+/* the same from and to host memory on the context's stream (rows of any length >= n, no alignment rule; h_out may be NULL without
+ * APPLY), as dabgpu_channel_bank_apply_host_sync */
+int dabgpu_iqbal_bank_apply_host_sync(dabgpu_iqbal_bank *bank, const float *h_in, size_t in_stride_samples, size_t n, void *h_out,
+                                      int out_format, size_t out_stride_bytes, float u8_scale, uint32_t flags);
+/* the n_streams records (waits for the context's stream) */
+int dabgpu_iqbal_bank_read_state_host_sync(dabgpu_iqbal_bank *bank, dabgpu_iqbal_record *h_records);
+/* the tile records of the last MEASURE call, n_tiles <= tiles_per_call of them per stream: h_moments[(s * n_tiles + j) * 8 + k], k < 5 the
+ * sums of the call's tile j, k >= 5 zero (waits for the context's stream) */
+int dabgpu_iqbal_bank_read_moments_host_sync(dabgpu_iqbal_bank *bank, size_t n_tiles, float *h_moments);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Resampler: arbitrary-ratio, fractional-delay resampling of n_streams independent streams of complex float samples -- a receiver's
  * sampling-clock error and fractional delay behind the channel model, and captures at 2.4, 2.56, 3.072 or 4.096 MS/s brought to the 2.048 MHz
  * grid in front of the demodulator.  The reference has nothing comparable; the definition is this library's own, written once in
