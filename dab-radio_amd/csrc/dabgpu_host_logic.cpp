@@ -7,6 +7,7 @@
 #include "noise_profile_core.h"
 #include "dd_profile_core.h"
 #include "sym_profile_core.h"
+#include "clock_core.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -312,6 +313,88 @@ int dabgpu_sym_profile_rows_host(const float* dqpsk, float* symbol_weight, float
     if (!dqpsk) return -1;
     return dabgpu::syp_frame(dqpsk, true, symbol_weight, symbol_noise, ref_noise) ? 1 : 0;
 }
+
+int dabgpu_clock_estimate_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const int64_t* d_slope_in,
+                               float gain, const int64_t* d_slope_out, const int64_t* d_residual, const float* d_corr, const uint32_t* d_valid,
+                               dabgpu_noise_geometry* out) {
+    if (!out) { dabgpu_set_error("clock_estimate_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("clock_estimate_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("clock_estimate_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_dqpsk) { dabgpu_set_error("clock_estimate_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("clock_estimate_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_slope_in | (uintptr_t)d_slope_out | (uintptr_t)d_residual) & 7) {
+        dabgpu_set_error("clock_estimate_plan: slope words must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (((uintptr_t)d_sync | (uintptr_t)d_corr | (uintptr_t)d_valid) & 3) {
+        dabgpu_set_error("clock_estimate_plan: records and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+    }
+    if (!dabgpu::clk_gain_ok(gain)) { dabgpu_set_error("clock_estimate_plan: gain %g outside (0, 1]", (double)gain); return DABGPU_ERR_INVALID_ARG; }
+    if (d_slope_in && d_slope_out && d_slope_in != d_slope_out) {
+        const uintptr_t a = (uintptr_t)d_slope_in, b = (uintptr_t)d_slope_out, bytes = (uintptr_t)n_frames * sizeof(int64_t);
+        if (a < b + bytes && b < a + bytes) {
+            dabgpu_set_error("clock_estimate_plan: d_slope_in and d_slope_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!d_slope_out && !d_residual && !d_corr && !d_valid) { dabgpu_set_error("clock_estimate_plan: no output at all"); return DABGPU_ERR_INVALID_ARG; }
+    out->grid = (uint32_t)n_frames;
+    out->threads = DABGPU_CLOCK_THREADS;
+    out->lds_bytes = DABGPU_CLOCK_ESTIMATE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_clock_derotate_plan(int transmission_mode, const float* d_dqpsk_in, const float* d_dqpsk_out, size_t n_frames, const dabgpu_sync_state* d_sync,
+                               const int64_t* d_slope, int symbols_per_block, dabgpu_diversity_geometry* out) {
+    if (!out) { dabgpu_set_error("clock_derotate_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
+    *out = dabgpu_diversity_geometry{};                       // a refusal leaves no geometry behind
+    if (transmission_mode != 1) { dabgpu_set_error("clock_derotate_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
+    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("clock_derotate_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
+    if (!d_dqpsk_in || !d_dqpsk_out) { dabgpu_set_error("clock_derotate_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
+    if (((uintptr_t)d_dqpsk_in | (uintptr_t)d_dqpsk_out) & 15) { dabgpu_set_error("clock_derotate_plan: products must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (d_dqpsk_in != d_dqpsk_out) {
+        const uintptr_t a = (uintptr_t)d_dqpsk_in, b = (uintptr_t)d_dqpsk_out;
+        const uintptr_t bytes = (uintptr_t)n_frames * dabgpu::CLK_SYMBOLS * dabgpu::CLK_CARRIERS * 2 * sizeof(float);
+        if (a < b + bytes && b < a + bytes) {
+            dabgpu_set_error("clock_derotate_plan: d_dqpsk_in and d_dqpsk_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!d_slope) { dabgpu_set_error("clock_derotate_plan: null slope words"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_slope & 7) { dabgpu_set_error("clock_derotate_plan: slope words must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_sync & 3) { dabgpu_set_error("clock_derotate_plan: records must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
+    if (symbols_per_block < 0 || symbols_per_block > dabgpu::CLK_SYMBOLS) {
+        dabgpu_set_error("clock_derotate_plan: symbols_per_block %d outside 0 .. 75", symbols_per_block); return DABGPU_ERR_INVALID_ARG;
+    }
+    const uint32_t spb = symbols_per_block ? (uint32_t)symbols_per_block : (uint32_t)dabgpu_host_small_batch_spb(n_frames);
+    out->symbols_per_block = spb;
+    out->runs_per_frame = (75u + spb - 1u) / spb;
+    out->grid = (uint32_t)n_frames * out->runs_per_frame;            // at most 2^24 x 75
+    out->threads = DABGPU_CLOCK_THREADS;
+    out->lds_bytes = DABGPU_CLOCK_DEROTATE_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+int dabgpu_clock_estimate_host(const float* dqpsk, int64_t slope_in, float gain, int64_t* slope_out, float* corr) {
+    if (!dqpsk || !dabgpu::clk_gain_ok(gain)) return -1;
+    const dabgpu::clk_update u = dabgpu::clk_estimate_frame(dqpsk, true, slope_in, gain, corr);
+    if (slope_out) *slope_out = u.slope;
+    return u.valid ? 1 : 0;
+}
+
+int dabgpu_clock_derotate_host(const float* dqpsk_in, float* dqpsk_out, int64_t slope_q64) {
+    if (!dqpsk_in || !dqpsk_out) return -1;
+    dabgpu::clk_derotate_frame(dqpsk_in, dqpsk_out, slope_q64);
+    return 0;
+}
+
+// slope = ppm * 1e-6 * 2552 / 2048 cycles per carrier, as Q0.64
+int64_t dabgpu_clock_slope_q64(double ppm) {
+    const double s = ppm * (2552.0 / 2048.0 * 1e-6) * 18446744073709551616.0;
+    if (s != s) return 0;
+    if (s < -9.2e18) return INT64_MIN;
+    if (s > 9.2e18) return INT64_MAX;
+    return (int64_t)llrint(s);
+}
+double dabgpu_clock_ppm(int64_t slope_q64) { return (double)slope_q64 * (1.0 / 18446744073709551616.0) * (2048.0 / 2552.0 * 1e6); }
 
 float dabgpu_diversity_band_mean_host(const float band_weight[128]) { return band_weight ? dabgpu::np_branch_weight(band_weight) : 0.0f; }
 

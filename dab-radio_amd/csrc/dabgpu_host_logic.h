@@ -259,6 +259,13 @@ int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout,
 #define DABGPU_SYM_PROFILE_THREADS 256u
 #define DABGPU_SYM_PROFILE_LDS_BYTES (3600u + 900u + 12u)
 
+// ---- sampling-clock tracker (clock.hip launches from dabgpu_clock_estimate_plan / _derotate_plan; include/dabgpu.h) ----
+// estimator: one 256-thread workgroup per frame; static LDS: 4 x 2 wave sums, 4 counts.  De-rotator: a workgroup per run of rows (the
+// combiner's symbols_per_block rule); static LDS: the frame's 1536 rotations
+#define DABGPU_CLOCK_THREADS 256u
+#define DABGPU_CLOCK_ESTIMATE_LDS_BYTES (32u + 16u)
+#define DABGPU_CLOCK_DEROTATE_LDS_BYTES (1536u * 8u)
+
 // ---- channel encoder planner (dab_encode.hip launches from it; include/dabgpu.h, dabgpu_tx_encode_plan) ----
 #define DABGPU_TX_TAIL_KEEP_MASK 0x00333333u        // PI_X: 2 of the 4 mother bits of each of the six tail steps
 struct dabgpu_tx_plan {

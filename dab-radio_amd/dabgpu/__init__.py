@@ -103,6 +103,9 @@ ABI_SYMBOLS = [
     "dabgpu_dd_profile_plan", "dabgpu_dd_profile_frames", "dabgpu_dd_profile_host_sync", "dabgpu_dd_profile_carriers_host",
     "dabgpu_sym_profile_plan", "dabgpu_sym_profile_frames", "dabgpu_sym_profile_host_sync", "dabgpu_sym_profile_rows_host",
     "dabgpu_diversity_plan_symbols", "dabgpu_diversity_combine_frames_symbols", "dabgpu_diversity_combine_symbols_host_sync",
+    "dabgpu_clock_estimate_plan", "dabgpu_clock_derotate_plan", "dabgpu_clock_estimate_frames", "dabgpu_clock_derotate_frames",
+    "dabgpu_clock_derotate_frames_split", "dabgpu_clock_track_host_sync", "dabgpu_clock_estimate_host", "dabgpu_clock_derotate_host",
+    "dabgpu_clock_slope_q64", "dabgpu_clock_ppm",
     "dabgpu_interferer_design", "dabgpu_interferer_plan", "dabgpu_interferer_bank_create", "dabgpu_interferer_bank_destroy",
     "dabgpu_interferer_bank_set_params", "dabgpu_interferer_bank_seek", "dabgpu_interferer_bank_apply", "dabgpu_interferer_bank_apply_host_sync",
     "dabgpu_blanker_defaults", "dabgpu_blanker_mask_words", "dabgpu_blanker_plan", "dabgpu_blanker_input_needed", "dabgpu_blanker_bank_create",
@@ -115,6 +118,8 @@ ABI_SYMBOLS = [
 ]
 NOISE_PROFILE_BANDS, NOISE_PROFILE_BAND_CARRIERS, NOISE_PROFILE_EXCLUDE_WORDS = 128, 12, 48      # noise profile (include/dabgpu.h)
 SYM_PROFILE_SYMBOLS = 75                  # symbol noise profile: product rows of a mode I frame
+CLOCK_LAG = 32                            # sampling-clock tracker (include/dabgpu.h): carriers between the two products of a lag product
+CLOCK_MAX_SLOPE = 22986372498099012       # the slope word of 1000 ppm
 SOFT_NORMALISED, SOFT_CSI = 0, 1          # dabgpu_soft_cfg.policy
 DIVERSITY_MAX_BRANCHES = 8                # receive diversity (include/dabgpu.h)
 NOISE_RECORD_DTYPE = [("noise_power", "<f4"), ("signal_power", "<f4"), ("weight", "<f4"), ("snr", "<f4"), ("valid", "<u4")]   # dabgpu_noise_record
@@ -509,6 +514,18 @@ def lib():
         L.dabgpu_sym_profile_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
         L.dabgpu_sym_profile_host_sync.argtypes = [C.c_void_p] * 6
         L.dabgpu_sym_profile_rows_host.argtypes = [C.c_void_p] * 4
+        L.dabgpu_clock_estimate_plan.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
+        L.dabgpu_clock_derotate_plan.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_clock_estimate_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
+        L.dabgpu_clock_derotate_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dabgpu_clock_derotate_frames_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.dabgpu_clock_track_host_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.dabgpu_clock_estimate_host.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+        L.dabgpu_clock_derotate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.dabgpu_clock_slope_q64.restype = C.c_int64
+        L.dabgpu_clock_slope_q64.argtypes = [C.c_double]
+        L.dabgpu_clock_ppm.restype = C.c_double
+        L.dabgpu_clock_ppm.argtypes = [C.c_int64]
         L.dabgpu_diversity_plan_symbols.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p]
         L.dabgpu_diversity_combine_frames_symbols.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
@@ -1120,6 +1137,33 @@ class Context:
         ref, ok = C.c_float(0.0), C.c_uint32(0)
         check(lib().dabgpu_sym_profile_host_sync(self._h, _ptr(x), _ptr(v), _ptr(q), C.byref(ref), C.byref(ok)), "dabgpu_sym_profile_host_sync")
         return v, q, ref.value, ok.value
+
+    def clock_estimate(self, dqpsk, n_frames, sync=None, slope_in=None, gain=1.0, slope_out=None, residual=None, corr=None, valid=None,
+                       stream=None):
+        """the sampling-clock estimator over n_frames frames (include/dabgpu.h, "Sampling-clock tracker"): dqpsk [n_frames][75][1536]
+        complex64 and sync the records of ofdm_sync_demod_frames_branch; slope_in [n_frames] int64 (None: zero), slope_out [n_frames]
+        int64 (may be slope_in itself: the state), residual [n_frames] int64, corr [n_frames][2] float32, valid [n_frames] uint32; every
+        output optional.  One kernel launch, no copy: capturable"""
+        check(lib().dabgpu_clock_estimate_frames(self._h, _ptr(dqpsk), n_frames, _ptr(sync), _ptr(slope_in), float(gain), _ptr(slope_out),
+                                                 _ptr(residual), _ptr(corr), _ptr(valid), self._stream(stream)), "dabgpu_clock_estimate_frames")
+
+    def clock_derotate(self, dqpsk_in, dqpsk_out, n_frames, slope, sync=None, symbols_per_block=0, stream=None):
+        """the products of n_frames frames with the ramp of slope [n_frames] int64 taken out; dqpsk_out may be dqpsk_in.  A frame of slope 0
+        is a copy (in place: untouched), a frame whose record in sync is not valid is neither read nor written.  symbols_per_block: the
+        rows a workgroup walks (0: the planner's choice; the bytes do not depend on it).  One kernel launch: capturable"""
+        check(lib().dabgpu_clock_derotate_frames_split(self._h, _ptr(dqpsk_in), _ptr(dqpsk_out), n_frames, _ptr(sync), _ptr(slope),
+                                                       int(symbols_per_block), self._stream(stream)), "dabgpu_clock_derotate_frames")
+
+    def clock_track_host(self, dqpsk, slope=0, gain=1.0, derotate=True):
+        """numpy convenience over dabgpu_clock_track_host_sync: one frame's products [75][1536] complex64 through the estimator and the
+        de-rotator -> (de-rotated products or None, new slope word, corr [2], valid)"""
+        import numpy as np
+        x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(75 * NB_CARRIERS)
+        out = np.zeros_like(x) if derotate else None
+        s, corr, ok = C.c_int64(int(slope)), np.zeros(2, np.float32), C.c_uint32(0)
+        check(lib().dabgpu_clock_track_host_sync(self._h, _ptr(x), _ptr(out), C.byref(s), float(gain), _ptr(corr), C.byref(ok)),
+              "dabgpu_clock_track_host_sync")
+        return (None if out is None else out.reshape(75, NB_CARRIERS)), s.value, corr, ok.value
 
     def noise_estimate_host(self, samples, null_offset_samples, freq_offset=0.0, fine_time_offset=0):
         """numpy convenience over dabgpu_noise_estimate_host_sync: one frame's NULL and phase reference symbol out of complex64 samples ->
@@ -2511,6 +2555,54 @@ def sym_profile_plan(dqpsk, n_frames, sync=None, symbol_weight=None, symbol_nois
     check(lib().dabgpu_sym_profile_plan(int(mode), _ptr(dqpsk), n_frames, _ptr(sync), _ptr(symbol_weight), _ptr(symbol_noise), _ptr(ref_noise),
                                         _ptr(valid), C.byref(g)), "dabgpu_sym_profile_plan")
     return g
+
+
+def clock_estimate_plan(dqpsk, n_frames, sync=None, slope_in=None, gain=1.0, slope_out=None, residual=None, corr=None, valid=None, mode=1):
+    """dabgpu_clock_estimate_plan (host only, nothing is dereferenced): the NoiseGeometry of a clock_estimate call with these arguments;
+    raises DabGpuError with the reason where that call would be refused"""
+    g = NoiseGeometry()
+    check(lib().dabgpu_clock_estimate_plan(int(mode), _ptr(dqpsk), n_frames, _ptr(sync), _ptr(slope_in), float(gain), _ptr(slope_out), _ptr(residual),
+                                           _ptr(corr), _ptr(valid), C.byref(g)), "dabgpu_clock_estimate_plan")
+    return g
+
+
+def clock_derotate_plan(dqpsk_in, dqpsk_out, n_frames, slope, sync=None, symbols_per_block=0, mode=1):
+    """dabgpu_clock_derotate_plan (host only, nothing is dereferenced): the DiversityGeometry (run length, runs per frame, grid) of a
+    clock_derotate call with these arguments; DabGpuError with the reason when refused"""
+    g = DiversityGeometry()
+    check(lib().dabgpu_clock_derotate_plan(int(mode), _ptr(dqpsk_in), _ptr(dqpsk_out), n_frames, _ptr(sync), _ptr(slope), int(symbols_per_block),
+                                           C.byref(g)), "dabgpu_clock_derotate_plan")
+    return g
+
+
+def clock_slope_q64(ppm):
+    """the slope word of a sampling-clock error of ppm: ppm * 1e-6 * 2552 / 2048 cycles per carrier as Q0.64"""
+    return lib().dabgpu_clock_slope_q64(float(ppm))
+
+
+def clock_ppm(slope_q64):
+    return lib().dabgpu_clock_ppm(int(slope_q64))
+
+
+def clock_estimate_host(dqpsk, slope_in=0, gain=1.0):
+    """the sampling-clock estimator on the host (no device): one frame's products [75][1536] complex64 -> (new slope word, corr [2], valid)"""
+    import numpy as np
+    x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(75 * NB_CARRIERS)
+    s, corr = C.c_int64(0), np.zeros(2, np.float32)
+    st = lib().dabgpu_clock_estimate_host(_ptr(x), int(slope_in), float(gain), C.byref(s), _ptr(corr))
+    if st < 0:
+        raise DabGpuError("dabgpu_clock_estimate_host: null products or a gain outside (0, 1]")
+    return s.value, corr, st
+
+
+def clock_derotate_host(dqpsk, slope_q64):
+    """the de-rotator on the host (no device): one frame's products [75][1536] complex64 -> the products without the ramp of slope_q64"""
+    import numpy as np
+    x = np.ascontiguousarray(dqpsk, dtype=np.complex64).reshape(75 * NB_CARRIERS)
+    out = np.zeros_like(x)
+    if lib().dabgpu_clock_derotate_host(_ptr(x), _ptr(out), int(slope_q64)) < 0:
+        raise DabGpuError("dabgpu_clock_derotate_host: null products")
+    return out.reshape(75, NB_CARRIERS)
 
 
 def sym_profile_rows_host(dqpsk):

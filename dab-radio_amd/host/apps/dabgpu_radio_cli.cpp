@@ -61,6 +61,15 @@
 // longer; FIC symbols under a burst stay lost.  Refused with --soft-bits normalised: that policy divides every product by its own
 // amplitude, which is what the weights act on.
 //
+// --track-clock [GAIN] [--clock-report] (include/dabgpu.h "Sampling-clock tracker"; with --soft-bits csi, banded or banded-dd): the delivered
+// frame's own products (GetFrameDataVec()) are copied and go through DAB_Clock_Tracker::Track (loop gain GAIN in (0, 1], default 1; taken
+// only where the next argument is a number), which estimates the ramp a sampling-clock error leaves over the carriers, carries the slope
+// from frame to frame (across resynchronisations too) and de-rotates the copy.  Everything else that reads products reads the copy: the
+// decision-directed and symbol profiles and the one-branch combiner, through which the frame then always goes -- under plain csi with
+// no table at all, as --symbol-weights does.  --clock-report prints one "clock frame=N ppm=X valid=V" line per frame, ppm in the sign of
+// dabgpu_simulate_transmitter --clock-ppm.  Refused with --soft-bits normalised: that path has no products to de-rotate, its soft bits
+// are made inside the demodulator.
+//
 // --blank [THRESHOLD] (not in the reference; include/dabgpu.h "Impulse blanker"): every block of samples at 2.048 MHz -- behind --input-rate
 // and --channel-offset-hz -- goes through a DAB_Stream_Blanker with dabgpu_blanker_defaults() (threshold 3 unless given) in front of
 // OFDM_Demod, which so runs 800 samples behind the input; the rest is flushed at the end of the input.  One "blank blocks=N of M" line
@@ -117,6 +126,7 @@
 #include "ofdm/tii_decoder.h"
 #include "ofdm/dab_noise_estimator.h"
 #include "ofdm/dab_dd_profile.h"
+#include "ofdm/dab_clock_tracker.h"
 #include "ofdm/dab_symbol_profile.h"
 #include "ofdm/dab_noise_profile.h"
 #include "ofdm/dab_diversity_combiner.h"
@@ -148,6 +158,8 @@ struct Args {
     bool soft_level_given = false;
     bool soft_banded = false;
     bool symbol_weights = false;                     // --symbol-weights: DAB_Symbol_Profile's weights into the one-branch combiner
+    bool track_clock = false, clock_report = false;  // --track-clock: DAB_Clock_Tracker in front of everything that reads the products
+    float clock_gain = 1.0f;
     bool soft_banded_dd = false;                     // (with soft_banded: the decision-directed profile in the NULL-based one's place)
     float alpha = 0.25f;
     bool alpha_given = false;
@@ -166,6 +178,7 @@ static void usage(const char* argv0) {
         "  [--radio-subchannel START,LENGTH,EEP_LEVEL(1-4),EEP_TYPE(A|B) | START,LENGTH,uep,UEP_INDEX]...\n"
         "  [--radio-msc-output PREFIX] [--tii] [--tii-frames N] [--snr] [--input-rate HZ] [--channel-offset-hz F] [--ber]\n"
         "  [--soft-bits normalised|csi|banded|banded-dd] [--soft-level 1..127] [--alpha A] [--symbol-weights] [--blank [THRESHOLD]]\n"
+        "  [--track-clock [GAIN]] [--clock-report]\n"
         "  [--iq-balance [TIME_CONSTANT_FRAMES]] [--iq-report]\n"
         "MODE: ", argv0);
     for (const auto& m : iq_read_modes) fprintf(stderr, "%s ", m.c_str());
@@ -240,6 +253,15 @@ static bool parse_args(int argc, char** argv, Args& args) {
             else throw std::runtime_error("unknown soft-bit policy '" + p + "' (normalised, csi, banded or banded-dd)");
         }
         else if (a == "--symbol-weights") args.symbol_weights = true;
+        else if (a == "--clock-report") args.clock_report = true;
+        else if (a == "--track-clock") {
+            args.track_clock = true;
+            char* end = nullptr;                                                  // the value is optional, as --blank's
+            if (i + 1 < argc) {
+                const float t = std::strtof(argv[i + 1], &end);
+                if (end != argv[i + 1] && *end == '\0') { args.clock_gain = t; i++; }
+            }
+        }
         else if (a == "--alpha") { args.alpha = std::stof(value()); args.alpha_given = true; }
         else if (a == "--soft-level") { args.soft_level = std::stof(value()); args.soft_level_given = true; }
         else if (a == "--iq-report") args.iq_report = true;
@@ -277,6 +299,11 @@ static bool parse_args(int argc, char** argv, Args& args) {
     if (args.symbol_weights && args.soft_policy != DABGPU_SOFT_CSI)
         throw std::runtime_error("--symbol-weights needs --soft-bits csi, banded or banded-dd: the normalised policy divides every product by its own amplitude, "
                                  "which is what the weights act on");
+    if (args.track_clock && args.soft_policy != DABGPU_SOFT_CSI)
+        throw std::runtime_error("--track-clock needs --soft-bits csi, banded or banded-dd: under the normalised policy the soft bits are made inside the "
+                                 "demodulator and there are no products to de-rotate");
+    if (args.track_clock && !(args.clock_gain > 0.0f && args.clock_gain <= 1.0f)) throw std::runtime_error("--track-clock: a gain above 0, up to 1");
+    if (args.clock_report && !args.track_clock) throw std::runtime_error("--clock-report needs --track-clock");
     if (args.alpha_given && !args.soft_banded) throw std::runtime_error("--alpha needs --soft-bits banded");
     if (!(args.alpha > 0.0f && args.alpha <= 1.0f)) throw std::runtime_error("--alpha: above 0, up to 1");
     if (args.soft_banded && args.ofdm_block_size > 196608 - 2656) throw std::runtime_error("--soft-bits banded: --ofdm-block-size may not exceed 193952");
@@ -461,7 +488,12 @@ static int run(const Args& args) {
         std::unique_ptr<DAB_Symbol_Profile> sym_profile;
         size_t sym_frames = 0, sym_kept = 0;
         if (args.symbol_weights) sym_profile = std::make_unique<DAB_Symbol_Profile>();
-        if (args.soft_banded || args.symbol_weights) {
+        // --track-clock: the frame's products are copied, de-rotated, and read from the copy by everything below
+        std::unique_ptr<DAB_Clock_Tracker> clock;
+        std::vector<std::complex<float>> clock_products;
+        size_t clock_frames = 0, clock_kept = 0;
+        if (args.track_clock) { clock = std::make_unique<DAB_Clock_Tracker>(args.clock_gain); clock_products.resize(DAB_Clock_Tracker::NB_PRODUCTS); }
+        if (args.soft_banded || args.symbol_weights || args.track_clock) {
             combiner = std::make_unique<DAB_Diversity_Combiner>(1);
             banded_bits.resize(DABGPU_NB_FRAME_BITS);
             demod->EnableDebugBuffers(true);                                         // the products of every frame, from the first
@@ -487,14 +519,21 @@ static int run(const Args& args) {
         };
         demod->On_OFDM_Frame().Attach([&](tcb::span<const viterbi_bit_t> demod_bits) {
             tcb::span<const viterbi_bit_t> bits = demod_bits;
-            if (profile || dd_profile || sym_profile) {
+            if (profile || dd_profile || sym_profile || clock) {
                 if ((profile || dd_profile) && demod->GetTotalFramesDesync() != banded_desync) {
                     banded_desync = demod->GetTotalFramesDesync();
                     if (profile) profile->Reset(); else dd_profile->Reset();
                 }
                 float w[DABGPU_NOISE_PROFILE_BANDS], v[DABGPU_SYM_PROFILE_SYMBOLS];
                 // (the buffer has the reference's size, 75 x 2048; the products are its first 75 x 1536)
-                const tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
+                tcb::span<const std::complex<float>> products[1] = {demod->GetFrameDataVec().first((size_t)75 * 1536)};
+                if (clock) {
+                    std::copy(products[0].begin(), products[0].end(), clock_products.begin());
+                    const bool tracked = clock->Track(clock_products);
+                    if (tracked) clock_frames++; else clock_kept++;
+                    if (args.clock_report) printf("clock frame=%d ppm=%.3f valid=%d\n", demod->GetTotalFramesRead(), clock->GetPpm(), tracked ? 1 : 0);
+                    products[0] = clock_products;
+                }
                 const bool banded = (profile || dd_profile) &&
                                     (profile ? (profile->Update(demod->GetCorrelationTimeBuffer().first(2656), 0, demod->GetNetFrequencyOffset(), w) && profile->IsValid())
                                              : (dd_profile->Update(products[0], w) && dd_profile->IsValid()));
@@ -509,6 +548,8 @@ static int run(const Args& args) {
                                                  symbol_weights, banded_bits);
                 else if (banded)
                     combined = combiner->Combine(products, scale, tcb::span<const float>(), band_weights, banded_bits);
+                else if (clock)
+                    combined = combiner->Combine(products, scale, tcb::span<const float>(), banded_bits);
                 if (combined) bits = banded_bits;
                 if (profile || dd_profile) { if (combined && banded) banded_frames++; else banded_kept++; }
                 if (sym_profile) { if (combined && weighted) sym_frames++; else sym_kept++; }
@@ -646,6 +687,7 @@ static int run(const Args& args) {
                 demod->GetTotalFramesDesync(), demod->GetCoarseFrequencyOffset(), demod->GetFineFrequencyOffset());
         if (profile || dd_profile) fprintf(stderr, "banded: frames_combined=%zu frames_kept_csi=%zu\n", banded_frames, banded_kept);
         if (sym_profile) fprintf(stderr, "symbols: frames_weighted=%zu frames_kept=%zu\n", sym_frames, sym_kept);
+        if (clock) fprintf(stderr, "clock: frames_tracked=%zu frames_kept=%zu ppm=%.3f\n", clock_frames, clock_kept, clock->GetPpm());
         if (blanker) fprintf(stderr, "blank blocks=%llu of %llu\n", (unsigned long long)blanker->BlankedBlocks(), (unsigned long long)blanker->TotalBlocks());
     } else {
         std::vector<viterbi_bit_t> bits(radio->frame_bits());                         // Basic_Radio_Block::run, app_radio_blocks.h:31-38

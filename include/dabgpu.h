@@ -2330,6 +2330,98 @@ int dabgpu_diversity_combine_symbols_host_sync(dabgpu_ctx *ctx, const float *con
                                                uint32_t *h_live_mask, const float *const *h_band_weight,
                                                const float *const *h_symbol_weight);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sampling-clock tracker: the slope of the phase ramp that a sampling-clock error leaves over the carriers of a frame's DQPSK products,
+ * and the products with that ramp taken out (mode I; batched, one kernel launch per call, no host state: both calls may be captured
+ * in a HIP graph; the tracking state is the caller's array).  A clock error eps moves the sampling instant by eps * 2552 samples from
+ * one OFDM symbol to the next.  A product of two neighbouring symbols keeps that as theta * k cycles at carrier number k,
+ * theta = eps * 2552 / 2048: 34 degrees at k = +-768 for 100 ppm, against a decision boundary at 45.  The synchroniser's time correction
+ * cannot see it (a constant window offset cancels in the product).  d_dqpsk holds X[s] * conj(X[s + 1]), the LATER symbol conjugated,
+ * so a positive clock error leaves the ramp -theta * k on it; steps 1 and 7 are written for that, and a positive slope word stands
+ * for a positive clock error.  The reference has no such code; this section is the definition.
+ * Carrier number: k(c) = c - 768 for c < 768, c - 767 from there on.
+ *   slope word    slope_q64: int64, cycles per carrier as Q0.64 in two's complement.  The ramp of carrier k is the exact product
+ *                 k * slope_q64 mod 2^64; its angle is the top 24 bits as cycles in [-0.5, 0.5), and (cos, sin) of it those of the channel
+ *                 model's oscillator (csrc/channel_core.h: ch_osc_cycles, ch_cos_sin).
+ * Estimator, per frame, from d_dqpsk [n_frames][75][1536] complex float in carrier order c:
+ *   1 lag         p[s][c] = d[s][c] * conj(d[s][c + L]), L = DABGPU_CLOCK_LAG = 32, for c in 0 .. 735 and 768 .. 1503 (1472 pairs a row:
+ *                 both carriers in one half of the block, so their numbers differ by exactly L); with lo = d[s][c], hi = d[s][c + L]:
+ *                 re = fma(lo.re, hi.re, lo.im * hi.im), im = fma(lo.im, hi.re, -(lo.re * hi.im)).  Channel, common phase and
+ *                 amplitude profile drop out: arg p = theta * L + a multiple of a quarter turn.
+ *   2 prior       with s_in = slope_in clamped to +-DABGPU_CLOCK_MAX_SLOPE: p is rotated by the frame's one constant
+ *                 (cos, -sin)(L * s_in), in the product order of step 7 -- what de-rotating every product by s_in would do to p.
+ *                 s_in = 0: no rotation.
+ *   3 fold        into the sector |arg| <= 45 degrees by sign and swap only: |re| >= |im|: p where re >= 0, else -p; otherwise -i p
+ *                 where im > 0, else i p.  A pair with a component that is not finite contributes nothing and is counted.
+ *   4 sum         A = the sum of the folded products, re and im apart.  Order: a row's 768 float4 positions j (carriers 2 j, 2 j + 1;
+ *                 position j pairs with j + 16; positions 368 .. 383 and 752 .. 767 have no partner) are dealt to owners t = 0 .. 255:
+ *                 owner t has j = t, t + 256, t + 512.  An owner chains from +0 over the rows s = 0 .. 74, in a row over its positions
+ *                 in that order, carrier 2 j before 2 j + 1.  Owners 64 w .. 64 w + 63 meet in the wavefront tree of "Noise profile"
+ *                 step 5; the four sums join as (p0 + p1) + (p2 + p3).  Independent of launch geometry.
+ *   5 angle       valid: re A a normal positive finite number, |im A| <= re A, and fewer than half of the 110400 pairs dropped.
+ *                 t = im A * (1 / re A), the reciprocal that of "Receive diversity"; residual = atan(t) / (2 pi) cycles by a fixed odd
+ *                 polynomial of degree 11 in fma Horner form (csrc/clock_core.h, clk_atan_cycles), within 2.5e-6 rad of atan on
+ *                 [-1, 1]: 0.01 ppm.
+ *   6 update      residual_q64 = rint(residual * 2^59): the residual over L as a slope word.  step = residual_q64 for gain = 1, else
+ *                 rint((gain * residual) * 2^59); slope_out = clamp(s_in + step, +-DABGPU_CLOCK_MAX_SLOPE), the slope of 1000 ppm.
+ *                 d_slope_out may be d_slope_in itself: the state is then the caller's array, and a zeroed array starts cleanly.
+ *   skipped       a frame whose record in d_sync (optional) has sync_valid = 0: its products are stale and none is read; or a frame
+ *                 that is not valid by step 5.  slope_out = slope_in as it came, 0 to d_residual and d_corr, d_valid cleared.
+ * De-rotator:
+ *   7 de-rotate   v[s][c] = d[s][c] * (cos, sin)(k(c) * slope), which takes the ramp -k * slope off: with (c, m) = (cos, sin),
+ *                 b0 = m * d.im, b1 = m * d.re, v = (fma(c, d.re, -b0), fma(c, d.im, b1)): the product order of the channel model.
+ *                 A frame whose slope word is 0 is a copy bit for bit (in place it is not touched at all); a frame skipped through
+ *                 d_sync is neither read nor written.  Out of place or in place (d_dqpsk_out == d_dqpsk_in); any other overlap is
+ *                 refused.
+ * ppm: slope = ppm * 1e-6 * 2552 / 2048 cycles per carrier.  The sign is that of dabgpu_simulate_transmitter --clock-ppm: a stream
+ * made with --clock-ppm X tracks to +X, and dabgpu_resample_step_q62(r, r, -X) ahead of the demodulator would undo it.
+ * Limits: the fold errs where noise turns a lag product past 45 degrees, so the estimate under-reads at low SNR and the loop needs more
+ * frames to settle; a residual beyond +-45 degrees over L carriers (1/256 cycle per carrier, 3135 ppm) aliases; a ramp that changes
+ * within a frame is averaged.
+ * Arithmetic: csrc/clock_core.h; the device equals dabgpu_clock_estimate_host / dabgpu_clock_derotate_host and the tests' host model
+ * bit for bit. */
+#define DABGPU_CLOCK_LAG 32
+#define DABGPU_CLOCK_MAX_SLOPE 22986372498099012LL     /* round(1000e-6 * 2552 / 2048 * 2^64) */
+/* What a dabgpu_clock_estimate_frames call with these arguments launches; needs no device (no address is dereferenced).
+ * DABGPU_ERR_INVALID_ARG, with the reason in dabgpu_last_error, for: a null result; a transmission_mode other than 1; n_frames of 0 or
+ * above 2^24; d_dqpsk null or not 16-byte aligned; d_slope_in, d_slope_out or d_residual not 8-byte aligned; d_sync, d_corr or d_valid
+ * not 4-byte aligned; gain outside (0, 1] (NaN included); d_slope_in and d_slope_out that overlap without being equal; no output at
+ * all. */
+int dabgpu_clock_estimate_plan(int transmission_mode, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                               const int64_t *d_slope_in, float gain, const int64_t *d_slope_out, const int64_t *d_residual,
+                               const float *d_corr, const uint32_t *d_valid, dabgpu_noise_geometry *out);
+/* What a dabgpu_clock_derotate_frames call launches (symbols_per_block = 0) or a _split call with that run length: as above, for a null
+ * result; a mode other than 1; n_frames of 0 or above 2^24; products null or not 16-byte aligned; in and out that overlap without being
+ * equal; d_slope null or not 8-byte aligned; d_sync not 4-byte aligned; symbols_per_block outside 0 .. 75.  symbols_per_block = 0: the
+ * planner chooses as dabgpu_diversity_plan does; the result never depends on it. */
+int dabgpu_clock_derotate_plan(int transmission_mode, const float *d_dqpsk_in, const float *d_dqpsk_out, size_t n_frames,
+                               const dabgpu_sync_state *d_sync, const int64_t *d_slope, int symbols_per_block,
+                               dabgpu_diversity_geometry *out);
+/* d_dqpsk and d_sync are dabgpu_ofdm_sync_demod_frames_branch's d_dqpsk and records.  d_slope_in [n_frames] may be NULL: zero.
+ * d_slope_out, d_residual [n_frames] int64, d_corr [n_frames][2] (A: re, im), d_valid [n_frames]: every output is optional.  One
+ * launch, one workgroup per frame. */
+int dabgpu_clock_estimate_frames(dabgpu_ctx *ctx, const float *d_dqpsk, size_t n_frames, const dabgpu_sync_state *d_sync,
+                                 const int64_t *d_slope_in, float gain, int64_t *d_slope_out, int64_t *d_residual, float *d_corr,
+                                 uint32_t *d_valid, void *stream);
+/* One launch.  _split: the same with the rows of a frame dealt to workgroups in runs of symbols_per_block (1 .. 75, 0 = the planner's
+ * choice); the bytes written do not depend on it. */
+int dabgpu_clock_derotate_frames(dabgpu_ctx *ctx, const float *d_dqpsk_in, float *d_dqpsk_out, size_t n_frames,
+                                 const dabgpu_sync_state *d_sync, const int64_t *d_slope, void *stream);
+int dabgpu_clock_derotate_frames_split(dabgpu_ctx *ctx, const float *d_dqpsk_in, float *d_dqpsk_out, size_t n_frames,
+                                       const dabgpu_sync_state *d_sync, const int64_t *d_slope, int symbols_per_block, void *stream);
+/* One frame from host memory through both kernels, synchronous, on the context's stream: h_dqpsk_in [75][1536] complex float; *slope is
+ * the state, read and written; the products de-rotated by the NEW slope go to h_dqpsk_out (may be h_dqpsk_in; NULL: estimate only).
+ * h_corr [2] may be NULL.  Returns DABGPU_OK with *h_valid (may be NULL) 1 or 0. */
+int dabgpu_clock_track_host_sync(dabgpu_ctx *ctx, const float *h_dqpsk_in, float *h_dqpsk_out, int64_t *slope, float gain, float *h_corr,
+                                 uint32_t *h_valid);
+/* the whole definition on the host (no device).  _estimate_host: one frame's products -> *slope_out, corr [2] (either may be NULL);
+ * 1 for a valid frame, 0 for a skipped one, -1 for null products or a gain outside (0, 1].  _derotate_host: step 7 of one frame,
+ * dqpsk_out may be dqpsk_in; 0, or -1 for a null argument. */
+int dabgpu_clock_estimate_host(const float *dqpsk, int64_t slope_in, float gain, int64_t *slope_out, float *corr);
+int dabgpu_clock_derotate_host(const float *dqpsk_in, float *dqpsk_out, int64_t slope_q64);
+int64_t dabgpu_clock_slope_q64(double ppm);
+double dabgpu_clock_ppm(int64_t slope_q64);
+
 #ifdef __cplusplus
 }
 #endif
