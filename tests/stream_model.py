@@ -2,6 +2,8 @@
 (reference: src/ofdm/ofdm_demodulator.cpp:235-358, :550-577, :922-950) composed from the CPU oracle's numeric
 functions, plus a synthetic DAB ensemble generator (FIC with CRC-valid FIBs, EEP sub-channels through the
 16-CIF time interleaver).  Used by the -m gpu tests as the expected-output side for the C++ mirror classes."""
+import collections
+import copy
 import os
 import platform
 
@@ -39,11 +41,33 @@ def l1_average(block):
     return F32(np.cumsum(t, dtype=F32)[-1] / F32(t.size))
 
 
+def l1_windows(block, k, stride):
+    """CalculateL1Average of the windows block[i:i + k], i = 0, stride, ... < block.size - k (the loops of :309 and :943), all at once:
+    every row is accumulated sequentially in float32 like l1_average"""
+    n_win = max(0, (block.size - k + stride - 1) // stride)
+    if n_win == 0:
+        return np.zeros(0, F32)
+    t = (np.abs(block.real).astype(F32) + np.abs(block.imag).astype(F32)).astype(F32)
+    if stride == k:
+        rows = t[:n_win * k].reshape(n_win, k)
+    else:
+        rows = t[(np.arange(n_win) * stride)[:, None] + np.arange(k)[None, :]]
+    return (np.cumsum(rows, axis=1, dtype=F32)[:, -1] / F32(k)).astype(F32)
+
+
+# OFDM_Demod_Config::signal_l1 and ::null_l1_search (ofdm_demodulator_config.h): update_beta, nb_samples (k), nb_decimate, thresh_null_start,
+# thresh_null_end
+L1Settings = collections.namedtuple("L1Settings", "beta k decimate start end", defaults=(0.95, 100, 5, 0.35, 0.75))
+
+
 class StreamModel:
     """states: 0 FINDING_NULL_POWER_DIP, 1 READING_NULL_AND_PRS, 2/3 sync, 4 READING_SYMBOLS"""
 
-    def __init__(self, oracle, mode=1):
+    def __init__(self, oracle, mode=1, l1=None):
         self.O = oracle
+        self.l1 = L1Settings() if l1 is None else L1Settings(*l1)
+        self.position = 0           # samples consumed since construction
+        self.events = []            # ("fill" | "frame", position after the sample that filled the correlation window / completed the frame)
         self.mode = mode
         self.g = oracle.geometry(mode)
         self.cfg = oracle.sync_cfg_default()
@@ -73,28 +97,41 @@ class StreamModel:
         self.sync = self.O.SyncState(0.0, 0.0, 0, 0, 0, 0)
         self.fine_time_offset = 0
 
+    def clone(self):
+        """an independent copy (the oracle and the mode's tables are shared)"""
+        c = copy.copy(self)
+        c.ring, c.corr, c.frame = self.ring.copy(), self.corr.copy(), self.frame.copy()
+        c.sync = self.O.SyncState.from_buffer_copy(self.sync)
+        c.cfg = type(self.cfg).from_buffer_copy(self.cfg)
+        c.out_frames, c.events = list(self.out_frames), list(self.events)
+        return c
+
     def update_signal_average(self, block):                      # :934-950
-        n, k = block.size, 100
+        n, k = block.size, self.l1.k
         if n < k:
             return
-        beta = F32(0.95)
-        for i in range(0, n - k, 500):
-            self.signal_avg = F32(beta * self.signal_avg + F32(F32(1.0) - beta) * l1_average(block[i:i + k]))
+        beta = F32(self.l1.beta)
+        for l1 in l1_windows(block, k, k * self.l1.decimate):    # i = 0, k * decimate, ... < n - k
+            self.signal_avg = F32(beta * self.signal_avg + F32(F32(1.0) - beta) * l1)
 
     def find_null(self, buf):                                    # :291-347
-        n, k = buf.size, 100
-        start_t = F32(self.signal_avg * F32(0.35))
-        end_t = F32(self.signal_avg * F32(0.75))
+        n, k = buf.size, self.l1.k
+        start_t = F32(self.signal_avg * F32(self.l1.start))
+        end_t = F32(self.signal_avg * F32(self.l1.end))
         nb_read = n
-        for i in range(0, n - k, k):
-            l1 = l1_average(buf[i:i + k])
-            if self.null_start:
-                if l1 > end_t:
-                    self.null_end = True
-                    nb_read = i + k
-                    break
-            elif l1 < start_t:
-                self.null_start = True
+        w, lo = 0, 0
+        while nb_read == n and lo < n - k:                       # i = 0, k, ... < n - k, a stretch of windows at a time
+            hi = min(n, lo + 4096 * k + k)
+            for l1 in l1_windows(buf[lo:hi], k, k):
+                if self.null_start:
+                    if l1 > end_t:
+                        self.null_end = True
+                        nb_read = w * k + k
+                        break
+                elif l1 < start_t:
+                    self.null_start = True
+                w += 1
+            lo = w * k
         cap = self.ring.size
         keep = min(nb_read, cap)                                 # sequential writes: only the last `cap` samples survive
         first = nb_read - keep
@@ -118,6 +155,7 @@ class StreamModel:
         self.corr_length += take
         if self.corr_length == self.corr.size:
             self.state = 2
+            self.events.append(("fill", self.position + take))
         return take
 
     def run_sync(self):                                          # :360-548
@@ -151,6 +189,7 @@ class StreamModel:
         r = O.demod_frame_mode(self.mode, self.frame, f, want_fft=True, m=self.mapper)
         self.sync.freq_fine = float(O.update_fine_freq_mode(self.mode, self.sync.freq_fine, r["total_phase"], 0.9))
         self.frames_read += 1
+        self.events.append(("frame", self.position + take))
         self.out_frames.append(dict(bits=r["bits"].copy(), coarse=F32(self.sync.freq_coarse), fine=F32(self.sync.freq_fine),
                                     offset=self.fine_time_offset, desync=self.frames_desync, fft=r["fft"].copy()))
         self.frame_length = 0
@@ -160,9 +199,10 @@ class StreamModel:
     def process(self, buf):                                      # :235-275
         buf = np.ascontiguousarray(buf, dtype=np.complex64)
         self.update_signal_average(buf)
-        pos = 0
+        pos, start = 0, self.position
         while pos < buf.size:
             rest = buf[pos:]
+            self.position = start + pos
             if self.state == 0:
                 pos += self.find_null(rest)
             elif self.state == 1:
@@ -171,6 +211,105 @@ class StreamModel:
                 self.run_sync()
             else:
                 pos += self.read_symbols(rest)
+        self.position = start + buf.size
+
+    def snapshot(self):
+        """(state, corr_length, frame_length, frames so far): what tells where a block ended"""
+        return (self.state, self.corr_length, self.frame_length, len(self.out_frames))
+
+
+def edge_schedule(model_factory, capture, targets, tiny, block=50000, align=100):
+    """Block lengths that make `capture` end blocks exactly on state boundaries of the model model_factory() builds, and the model's
+    snapshot() after every block.  The blocks: the `tiny` lengths at the very start (state 0) and what they lack to a multiple of `align`
+    (FindNullPowerDip's windows start with its block: the search that finds the first NULL then looks at the windows it looks at when the
+    capture comes as one block, and ends the NULL at the same sample); blocks of `block` samples, less what they have over a multiple
+    of `align`, until the first frame has completed (before the lock the level average, and with it the first NULL, depends on the cut;
+    while the lock holds, the positions of the events do not); then `targets` blocks that each end with the sample of the next event, found by running a clone of the model
+    ahead -- "fill" (the correlation window fills: state 2 with no sample left) and "frame" (a frame completes: state 1, corr_length =
+    the NULL period) in alternation, beginning with whichever comes first; the `tiny` lengths again right after the last "frame" target
+    (state 1) and, one `block` behind the last target, in the middle of a frame (state 4); blocks of `block` samples to the end."""
+    m = model_factory()
+    blocks, after = [], []
+    n = capture.size
+
+    def feed(length):
+        length = min(length, n - m.position)
+        if length <= 0:
+            return False
+        m.process(capture[m.position:m.position + length])
+        blocks.append(length)
+        after.append(m.snapshot())
+        return True
+
+    def look_ahead(c, kind):
+        seen = len(m.events)
+        while True:
+            for ev in c.events[seen:]:
+                if ev[1] > m.position and kind in (None, ev[0]):
+                    return ev
+            seen = len(c.events)
+            if c.position >= n:
+                return None
+            c.process(capture[c.position:c.position + block])
+
+    def next_event(kind):
+        ev = look_ahead(m.clone(), kind)
+        # a receiver that loses its lock on the way searches a NULL again, and where it finds it depends on the cut: the block up to
+        # the event is tried as ONE block, and the event taken from that run, until the block ends on it
+        for _ in range(8):
+            if ev is None:
+                return None
+            c = m.clone()
+            c.process(capture[m.position:ev[1]])
+            got = look_ahead(c, kind)
+            if got == ev:
+                return ev
+            ev = got
+        return None
+
+    for t in tiny:
+        feed(t)
+    feed(-m.position % align)
+    while not m.out_frames and feed(block - block % align):
+        pass
+    first = next_event(None)
+    kinds = []
+    if first is not None:
+        other = "frame" if first[0] == "fill" else "fill"
+        kinds = [first[0] if i % 2 == 0 else other for i in range(targets)]
+    last_frame = max([i for i, kd in enumerate(kinds) if kd == "frame"], default=-1)
+    for i, kd in enumerate(kinds):
+        ev = next_event(kd)
+        if ev is None:
+            break
+        feed(ev[1] - m.position)
+        if i == last_frame:
+            for t in tiny:
+                feed(t)
+    feed(block)
+    for t in tiny:
+        feed(t)
+    while feed(block):
+        pass
+    assert sum(blocks) == n and m.position == n
+    return blocks, after
+
+
+def edge_hits(g, blocks, after, k=100):
+    """what a schedule's blocks ended on, from the snapshot() after every block: the number of blocks that ended with the sample that
+    filled the correlation window ("fill"), with the sample that completed a frame ("frame"), and the blocks shorter than k consumed
+    wholly in state 0, 1, 4 ("tiny")"""
+    hits = dict(fill=0, frame=0, tiny={0: 0, 1: 0, 4: 0})
+    prev = (0, 0, 0, 0)
+    for length, now in zip(blocks, after):
+        if now[0] == 2 and now[1] == g.nb_null_period + g.nb_symbol_period:      # (a window that filled earlier in the block was synchronised)
+            hits["fill"] += 1
+        if now[0] == 1 and now[1] == g.nb_null_period and now[3] > prev[3]:
+            hits["frame"] += 1
+        if length < k and prev[0] == now[0] and now[0] in hits["tiny"]:
+            hits["tiny"][now[0]] += 1
+        prev = now
+    return hits
 
 
 def make_ensemble_stream(oracle, n_frames, subs, seed, cfo=1.8e-3, timing_pad=1234, noise=3.0, amplitude=1.0 / 39.2, payload=None, fib_data=None):
