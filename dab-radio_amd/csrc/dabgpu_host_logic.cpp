@@ -541,13 +541,21 @@ dabgpu_demod_plan dabgpu_host_plan_demod(int mode, const dabgpu_demod_facts& f) 
     // under the normalised policy, and a caller that hands descriptors without it is refused as before
     if (f.bank_soft && !f.desc) { dabgpu_set_error("ofdm_demod: bank_soft is a bank round's fact: it needs frame descriptors"); return p; }
     if (f.bank_soft && f.soft_policy == DABGPU_SOFT_NORMALISED) { dabgpu_set_error("ofdm_demod: bank_soft asks for DABGPU_SOFT_CSI, the policy is the normalised one"); return p; }
+    // bank_products is the bank's statement that the round also stores every frame's DQPSK products at the frame's bits slot: a round under
+    // the weighted policy (bank_soft and all it asks for), in the natural layout, without the display views (whose buffers are indexed by
+    // stream, not by slot)
+    if (f.bank_products && !f.bank_soft) { dabgpu_set_error("ofdm_demod: bank_products is a weighted bank round's fact: it needs bank_soft"); return p; }
+    if (f.bank_products && f.classed) { dabgpu_set_error("ofdm_demod: bank_products comes in the natural layout: classed is not available with it"); return p; }
+    if (f.bank_products && f.fft) { dabgpu_set_error("ofdm_demod: bank_products has no FFT view: fft is not available with it"); return p; }
+    if (f.bank_products && f.dqpsk) { dabgpu_set_error("ofdm_demod: bank_products stores the products by bits slot: dqpsk, the view by frame, is not available with it"); return p; }
     if (f.soft_policy != DABGPU_SOFT_NORMALISED) {
         if (f.soft_policy != DABGPU_SOFT_CSI) { dabgpu_set_error("ofdm_demod: no soft-decision policy %d", f.soft_policy); return p; }
         if (!mode1) { dabgpu_set_error("ofdm_demod: the weighted soft bits exist for the transmission mode I kernel only (mode %d)", mode); return p; }
         if (f.desc && !f.bank_soft) { dabgpu_set_error("ofdm_demod: the weighted soft bits have no stream-bank loader (frame descriptors)"); return p; }
         if (f.bank_soft && views) { dabgpu_set_error("ofdm_demod: a bank round has no display views under the weighted policy"); return p; }
         if (!dabgpu::sb_level_ok(f.soft_level)) { dabgpu_set_error("ofdm_demod: soft level %g outside [1, 127]", (double)f.soft_level); return p; }
-        p.variant = f.bank_soft ? DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST + f.src * 2 + (f.classed ? 1 : 0)
+        p.variant = f.bank_products ? DABGPU_DEMOD_MODE1_BANK_PRODUCTS_FIRST + f.src
+                    : f.bank_soft   ? DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST + f.src * 2 + (f.classed ? 1 : 0)
                                 : DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + f.src * 3 + (f.classed ? 2 : views ? 1 : 0);
     }
     if (!mode1) {

@@ -188,12 +188,17 @@ dabgpu_decode_slice dabgpu_host_decode_slice(const dabgpu_decode_plan& p, size_t
 // indexed by `variant`:
 //   mode I:        ((src * 2 + bank) * 3 + layout), layout 0 = soft bits, 1 = + display views, 2 = soft bits in class order;
 //                  weighted soft bits (DABGPU_SOFT_CSI) follow as 24 + src * 3 + layout for aligned frames, and behind those as
-//                  36 + src * 2 + (class order) for a bank round that states bank_soft (a bank round has no display views)
+//                  36 + src * 2 + (class order) for a bank round that states bank_soft (a bank round has no display views),
+//                  and last 44 + src for a bank round that states bank_products: the weighted soft bits plus the frame's DQPSK products
+//                  at the descriptor's bits slot (dabgpu_stream_bank_set_products)
 //   other families: 0 without descriptors (complex float only), 1 + src with them
 enum dabgpu_demod_family { DABGPU_DEMOD_MODE1, DABGPU_DEMOD_GENERIC, DABGPU_DEMOD_WAVE, DABGPU_DEMOD_WAVE3 };
 enum dabgpu_demod_tail { DABGPU_DEMOD_TAIL_NONE, DABGPU_DEMOD_TAIL_FUSED, DABGPU_DEMOD_TAIL_LAUNCH };
 constexpr int DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS = 4 * 2 * 3, DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS + 4 * 3,
               DABGPU_DEMOD_MODE1_VARIANTS = DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST + 4 * 2;
+// (DABGPU_DEMOD_MODE1_VARIANTS keeps its value, 44: tests/cpp/bank_soft_plan_driver.cpp pins it as the end of the bank_soft variants.  The four
+// variants of bank_products follow it, and the kernel table has DABGPU_DEMOD_MODE1_KERNELS entries)
+constexpr int DABGPU_DEMOD_MODE1_BANK_PRODUCTS_FIRST = DABGPU_DEMOD_MODE1_VARIANTS, DABGPU_DEMOD_MODE1_KERNELS = DABGPU_DEMOD_MODE1_BANK_PRODUCTS_FIRST + 4;
 constexpr int DABGPU_DEMOD_LOADER_VARIANTS = 1 + 4;
 // the facts of a call that are not addresses.  The views, class order, sync records, frame stride and phase outputs are the mode I kernel's:
 // the other families have none of them (the FFT view apart, which only the size-generic kernel writes) and do not look at these facts.
@@ -211,6 +216,7 @@ struct dabgpu_demod_facts {
     int soft_policy = DABGPU_SOFT_NORMALISED;   // DABGPU_SOFT_CSI: the mode I kernel without descriptors only
     float soft_level = 64.0f;               // [1, 127], looked at under DABGPU_SOFT_CSI
     bool bank_soft = false;                 // the bank round asks for the weighted policy: needs desc and DABGPU_SOFT_CSI, mode I, no display views
+    bool bank_products = false;             // the bank round also stores the frames' DQPSK products by bits slot: needs bank_soft; no class order, no display views
 };
 struct dabgpu_demod_plan {
     int status;                             // DABGPU_OK, or DABGPU_ERR_INVALID_ARG (reason in dabgpu_last_error): nothing else is set then

@@ -189,6 +189,10 @@ struct dabgpu_demod_call {
     float soft_level = 64.0f;
     float* d_soft_scale = nullptr;
     bool bank_soft = false;                     // a bank round under DABGPU_SOFT_CSI: d_soft_scale is indexed by the descriptors' bits slot (bank_process_impl only)
+    // ... that also stores every completed frame's DQPSK products [75][1536] complex float at d_bank_dqpsk + slot * 75 * 1536, slot = the
+    // descriptor's bits slot (dabgpu_stream_bank_set_products); not d_dqpsk, the display view, which is indexed by frame
+    bool bank_products = false;
+    float* d_bank_dqpsk = nullptr;
 };
 // plans the call (dabgpu_host_plan_demod) and launches the demodulation kernel of the mode's family, then the phase kernel if the plan asks for it;
 // what = how a HIP failure of the mode I launch is reported (the entry points' own wording)

@@ -168,8 +168,11 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
                        const dabgpu_frame_desc* __restrict__ desc, const void* __restrict__ tail, size_t tail_stride, demod_phase_tail pt,
                        const void* __restrict__ prev_tail, demod_frame_src fs, demod_soft soft)
 {
-    static_assert(!(CSI && BANK && VIEWS), "a bank round has no display views under the weighted policy");
-    f2* const fft_out = VIEWS ? fft_out_ : nullptr;
+    // BANK && CSI && VIEWS is the bank round that stores the frames' DQPSK products (dabgpu_stream_bank_set_products): the product store
+    // of the display views, indexed by the descriptor's bits slot; it has no FFT view and no class order
+    constexpr bool PRODUCTS = BANK && CSI && VIEWS;
+    static_assert(!(PRODUCTS && CLASSED), "a bank round stores its DQPSK products in the natural layout only");
+    f2* const fft_out = (VIEWS && !PRODUCTS) ? fft_out_ : nullptr;
     f2* const dqpsk_out = VIEWS ? dqpsk_out_ : nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // bufA: the radix-4 outputs, position-indexed, as four 512-element blocks (one per wave's 512-point problem) placed
@@ -507,7 +510,8 @@ void ofdm_demod_kernel(const void* __restrict__ iq, const float* __restrict__ fr
                 if (dqpsk_out != nullptr) {                              // GetFrameDataVec() view, natural carrier order
                     const int cbase[6] = {767, 1023, 1279, 0, 256, 512};
                     const int c = (k == 0 && Kb == 0) ? 1535 : (cbase[k] + Kb);
-                    dqpsk_out[((size_t)frame * (NB_FRAME_SYMBOLS - 1) + (i - 1)) * 1536 + c] = d;
+                    if constexpr (BANK && CSI && VIEWS) dqpsk_out[(out_frame * (NB_FRAME_SYMBOLS - 1) + (i - 1)) * 1536 + c] = d;      // by bits slot
+                    else dqpsk_out[((size_t)frame * (NB_FRAME_SYMBOLS - 1) + (i - 1)) * 1536 + c] = d;
                 }
             };
             if constexpr (CSI) {
@@ -616,31 +620,37 @@ namespace {
 using namespace dabgpu;
 // variant -> kernel, the planner's numbering (dabgpu_host_logic.h): ((loader * 2 + bank) * 3 + layout), layout 1 = display views, 2 = class order;
 // behind those, the weighted soft bits: 24 + loader * 3 + layout for aligned frames, then 36 + loader * 2 + (class order) for a bank round
-// (the bank launches soft bits and class order, never the display views)
+// (the bank launches soft bits and class order, never the display views); last, 44 + loader for a weighted bank round that stores its DQPSK
+// products by bits slot
 using demod_kernel_t = decltype(&ofdm_demod_kernel<SRC_C32, false>);
-constexpr int NORM_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS, BANK_SOFT_FIRST = DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST;
+constexpr int NORM_VARIANTS = DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS, BANK_SOFT_FIRST = DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST,
+              BANK_PRODUCTS_FIRST = DABGPU_DEMOD_MODE1_BANK_PRODUCTS_FIRST;
 template <int V>
 constexpr demod_kernel_t mode1_kernel() {
     if constexpr (V < NORM_VARIANTS) return ofdm_demod_kernel<V / 6, (V / 3) % 2 == 1, V % 3 == 1, V % 3 == 2, false>;
     else if constexpr (V < BANK_SOFT_FIRST) return ofdm_demod_kernel<(V - NORM_VARIANTS) / 3, false, V % 3 == 1, V % 3 == 2, true>;
-    else return ofdm_demod_kernel<(V - BANK_SOFT_FIRST) / 2, true, false, (V - BANK_SOFT_FIRST) % 2 == 1, true>;
+    else if constexpr (V < BANK_PRODUCTS_FIRST) return ofdm_demod_kernel<(V - BANK_SOFT_FIRST) / 2, true, false, (V - BANK_SOFT_FIRST) % 2 == 1, true>;
+    else return ofdm_demod_kernel<V - BANK_PRODUCTS_FIRST, true, true, false, true>;
 }
 template <int... V>
 constexpr std::array<demod_kernel_t, sizeof...(V)> mode1_kernels(std::integer_sequence<int, V...>) { return {{mode1_kernel<V>()...}}; }
-constexpr auto MODE1_KERNELS = mode1_kernels(std::make_integer_sequence<int, DABGPU_DEMOD_MODE1_VARIANTS>{});
+constexpr auto MODE1_KERNELS = mode1_kernels(std::make_integer_sequence<int, DABGPU_DEMOD_MODE1_KERNELS>{});
 static_assert(DABGPU_DEMOD_MODE1_NORMALISED_VARIANTS == 4 * 2 * 3 && DABGPU_DEMOD_MODE1_BANK_SOFT_FIRST == 4 * 2 * 3 + 4 * 3 &&
-              DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3 + 4 * 3 + 4 * 2 && NORM_VARIANTS % 3 == 0 && BANK_SOFT_FIRST % 3 == 0,
-              "the planner's variants are (loader, bank, layout), then (loader, layout) weighted, then (loader, class order) weighted in a bank round: "
-              "the formulas above instantiate nothing else");
+              DABGPU_DEMOD_MODE1_VARIANTS == 4 * 2 * 3 + 4 * 3 + 4 * 2 && DABGPU_DEMOD_MODE1_BANK_PRODUCTS_FIRST == 4 * 2 * 3 + 4 * 3 + 4 * 2 &&
+              DABGPU_DEMOD_MODE1_KERNELS == 4 * 2 * 3 + 4 * 3 + 4 * 2 + 4 &&
+              NORM_VARIANTS % 3 == 0 && BANK_SOFT_FIRST % 3 == 0,
+              "the planner's variants are (loader, bank, layout), then (loader, layout) weighted, then (loader, class order) weighted in a bank round, "
+              "then (loader) weighted with products in a bank round: the formulas above instantiate nothing else");
 static_assert(SRC_C32 == 0 && SRC_U8 == 1 && SRC_S8 == 2 && SRC_S16 == 3, "the planner's loader numbers");
 
 hipError_t enqueue_demod_mode1(const dabgpu_demod_plan& p, const dabgpu_demod_call& a, const float* d_tw, const dabgpu_mode_tables& t, hipStream_t stream) {
     const bool fuse = p.tail == DABGPU_DEMOD_TAIL_FUSED;
     float* const d_fine_freq = a.d_sync ? &a.d_sync->freq_fine : a.d_fine_freq;        // with sync records the fine-frequency words are theirs
     const demod_frame_src fs = {a.frame_stride_samples ? a.frame_stride_samples : (size_t)NB_FRAME_SAMPLES, a.d_sync, a.prs_offset};
+    const bool bank_products = p.variant >= BANK_PRODUCTS_FIRST;                       // the product store is the bank's buffer, by bits slot
     const demod_phase_tail pt = {fuse ? a.d_total_phase : nullptr, fuse ? d_fine_freq : nullptr, a.beta, p.fine_stride};
     hipLaunchKernelGGL(MODE1_KERNELS[p.variant], dim3(p.grid), dim3(p.threads), DEMOD_LDS_BYTES, stream, a.d_iq, a.d_freq, a.d_bits,
-                       reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<f2*>(a.d_fft), reinterpret_cast<f2*>(a.d_dqpsk), reinterpret_cast<const f2*>(d_tw),
+                       reinterpret_cast<f2*>(a.d_cp_corr), reinterpret_cast<f2*>(a.d_fft), reinterpret_cast<f2*>(bank_products ? a.d_bank_dqpsk : a.d_dqpsk), reinterpret_cast<const f2*>(d_tw),
                        t.inv_map16, a.n_frames, p.symbols_per_block, p.chunks, a.bits_frame_stride ? a.bits_frame_stride : (size_t)NB_FRAME_BITS, a.d_desc,
                        a.d_block, a.block_stride, pt, a.d_prev_block, fs, demod_soft{a.soft_level, a.d_soft_scale});
     hipError_t e = hipGetLastError();
@@ -660,6 +670,8 @@ int dabgpu_launch_demod(dabgpu_ctx* c, int mode, const dabgpu_demod_call& a, hip
     f.frame_stride = a.frame_stride_samples != 0; f.total_phase = a.d_total_phase != nullptr; f.fine_freq = a.d_fine_freq != nullptr;
     f.classed = a.classed != 0; f.symbols_per_block = a.symbols_per_block; f.n_frames = a.n_frames; f.generic_mode1 = a.generic_mode1;
     f.soft_policy = a.soft_policy; f.soft_level = a.soft_level; f.bank_soft = a.bank_soft;
+    f.bank_products = a.bank_products;
+    if (a.bank_products && a.d_bank_dqpsk == nullptr) { dabgpu_set_error("ofdm_demod: bank_products without a product buffer"); return DABGPU_ERR_INVALID_ARG; }
     // development switches of modes II-IV (the tests cross-check the kernels of a mode with them)
     f.switch_generic = mode != 1 && getenv("DABGPU_MODE_GENERIC");
     f.switch_mode3_single = mode == 3 && getenv("DABGPU_MODE3_SINGLE");

@@ -72,6 +72,7 @@ struct BankView {
     long long win_cap;
     int* not_done;                   // [2 lanes][8 rounds]: streams of the lane that need another round; round r counts in [r % 8] and
                                      // clears [(r + 1) % 8] (no memset between the rounds)
+    dabgpu_sync_state* records;      // the caller's, by bits slot (dabgpu_stream_bank_set_products); null = the bank stores no products
 };
 
 
@@ -309,6 +310,14 @@ void stream_advance_kernel(BankView B, int s0, int n_streams, const uint8_t* __r
                     d.tail_off = pos0 + (have & 1);
                     d.carry_dst = cd; d.carry_end = ce; d.carry_off = csrc - cd;
                     B.desc[s] = d;
+                    // the frame's record beside its products (dabgpu_stream_bank_set_products): the words the demodulator is handed, the
+                    // fine word before this frame's phase update
+                    if (B.records != nullptr) {
+                        dabgpu_sync_state r;
+                        r.freq_coarse = y.freq_coarse; r.freq_fine = y.freq_fine; r.is_found_coarse = y.is_found_coarse;
+                        r.fine_time_offset = S.fine_time_offset; r.sync_valid = 1; r.reserved = 0;
+                        B.records[d.slot] = r;
+                    }
                     S.carry_dst = 0; S.carry_end = 0; S.carry_src = 0;
                     // The demodulation of this frame runs in THIS round (the round's kernel order is advance, copy, demod, phase, sync),
                     // so the state machine does the frame's bookkeeping now (:563-576) and reads on into the next NULL + PRS window: one
@@ -425,6 +434,10 @@ struct dabgpu_stream_bank {
     dabgpu_soft_cfg soft = {DABGPU_SOFT_NORMALISED, 64.0f};
     float* d_soft_scale = nullptr;     // the caller's: scale of the frame in bits slot k at [k], soft_scale_cap floats
     size_t soft_scale_cap = 0;
+    // DQPSK products and sync records of the frames of the frames forms, by bits slot (dabgpu_stream_bank_set_products); survives a reset.
+    // The records' address is view.records: the state machine writes them
+    float* d_products = nullptr;       // the caller's: [products_cap][75][1536] complex float
+    size_t products_cap = 0;           // frames
 };
 
 // DABGPU_SOFT_CSI with a scale buffer: every bits slot of the call has its word (checked before a call launches anything)
@@ -433,6 +446,32 @@ static int bank_soft_scale_fits(const dabgpu_stream_bank* b, size_t slots_per_st
     dabgpu_set_error("stream_bank_process: %zu streams x %zu bits slots need more scale words than the %zu dabgpu_stream_bank_set_soft was given", b->n,
                      slots_per_stream, b->soft_scale_cap);
     return DABGPU_ERR_INVALID_ARG;
+}
+
+// products set (dabgpu_stream_bank_set_products): the call is a frames form under the weighted policy with a scale buffer, and every bits
+// slot of the call has its products and its record (checked before a call launches or converts anything)
+static int bank_products_fit(const dabgpu_stream_bank* b, size_t slots_per_stream, int ring_mode) {
+    if (b->d_products == nullptr) return DABGPU_OK;
+    if (ring_mode) {
+        dabgpu_set_error("stream_bank_process_ring: the ring forms store no DQPSK products (dabgpu_stream_bank_set_products is set: use a frames form, "
+                         "or switch the products off)");
+        return DABGPU_ERR_UNSUPPORTED;
+    }
+    if (b->soft.policy != DABGPU_SOFT_CSI) {
+        dabgpu_set_error("stream_bank_process: DQPSK products are set, their consumers need the frame's scale: the policy must be DABGPU_SOFT_CSI "
+                         "(dabgpu_stream_bank_set_soft), it is the normalised one");
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (b->d_soft_scale == nullptr) {
+        dabgpu_set_error("stream_bank_process: DQPSK products are set, their consumers need the frame's scale: dabgpu_stream_bank_set_soft was given no scale buffer");
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (slots_per_stream > b->products_cap / b->n) {
+        dabgpu_set_error("stream_bank_process: %zu streams x %zu bits slots need more product frames than the %zu dabgpu_stream_bank_set_products was given",
+                         b->n, slots_per_stream, b->products_cap);
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    return DABGPU_OK;
 }
 
 // n elements for *p, owned by `owner`
@@ -540,6 +579,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     }
     if (((uintptr_t)d_iq & (src_sample_bytes<SRC>::value - 1)) || ((uintptr_t)d_bits & 15)) { dabgpu_set_error("stream_bank_process: misaligned buffer"); return DABGPU_ERR_INVALID_ARG; }
     if (int fits = bank_soft_scale_fits(b, max_frames_per_stream)) return fits;
+    if (int fits = bank_products_fit(b, max_frames_per_stream, ring_mode)) return fits;
     dabgpu_ctx* c = b->ctx;
     DABGPU_BIND(c);
     hipStream_t s = (hipStream_t)stream;
@@ -586,6 +626,8 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
     // half's demodulation.  Same kernels, same per-stream order, same results.
     const int n_lanes = (G.mode == 1 && n >= 1024) ? 2 : 1;      // (each half must still fill the chip: 256 streams lost 10-30 % in two lanes)
     hipStream_t lane_stream[2] = {s, b->side.get()};
+    // products: a slot of this call without a frame has a zero record (sync_valid = 0), whatever an earlier call left there
+    if (b->view.records != nullptr) DABGPU_CK(hipMemsetAsync(b->view.records, 0, (size_t)n * max_frames_per_stream * sizeof(dabgpu_sync_state), s));
     const int lane_lo[3] = {0, (n_lanes == 2) ? n / 2 : n, n};
     if (n_lanes == 2) {
         DABGPU_CK(hipEventRecord(b->ev_fork.get(), s));
@@ -620,6 +662,7 @@ static int bank_process_impl(dabgpu_stream_bank* b, const void* d_iq, size_t str
             call.d_prev_block = prev_iq ? prev_iq + (size_t)s0 * stream_stride_samples * sb : nullptr;
             if (b->soft.policy == DABGPU_SOFT_CSI) {         // (mode I banks only: set_soft refuses the others)
                 call.bank_soft = true; call.soft_policy = DABGPU_SOFT_CSI; call.soft_level = b->soft.level; call.d_soft_scale = b->d_soft_scale;
+                if (b->d_products != nullptr) { call.bank_products = true; call.d_bank_dqpsk = b->d_products; }      // (both lanes: global slots)
             }
             CKS(dabgpu_launch_demod(c, G.mode, call, ls));
             CKL(dabgpu_launch_ofdm_phase(corr_l, cnt, b->cfg.sync.fine_freq_update_beta, nullptr, &b->view.sync[s0].freq_fine,
@@ -726,6 +769,7 @@ int dabgpu_stream_bank_process_raw(dabgpu_stream_bank* b, const void* d_raw, int
         dabgpu_set_error("stream_bank_process_raw: the byte stride between streams must be a multiple of 16"); return DABGPU_ERR_INVALID_ARG;
     }
     if (int fits = bank_soft_scale_fits(b, max_frames_per_stream)) return fits;          // (before the conversion is launched)
+    if (int fits = bank_products_fit(b, max_frames_per_stream, 0)) return fits;
     DABGPU_BIND(b->ctx);
     hipStream_t s = (hipStream_t)stream;
     const size_t padded = (n_samples + 1) & ~(size_t)1;                   // keeps every stream's converted block 16-byte aligned
@@ -746,6 +790,7 @@ int dabgpu_stream_bank_process_raw(dabgpu_stream_bank* b, const void* d_raw, int
 static int bank_process_ring_any(dabgpu_stream_bank* b, const void* d_raw, int format, size_t stream_stride_samples, size_t n_samples,
                                  int8_t* d_hist, int hist_frames, int32_t* d_newest_slot, int bits_layout, void* stream, const void* d_prev, int retain) {
     if (!b || !d_raw || !d_hist || !d_newest_slot) { dabgpu_set_error("stream_bank_process_ring: null argument"); return DABGPU_ERR_INVALID_ARG; }
+    if (int fits = bank_products_fit(b, (size_t)(hist_frames > 0 ? hist_frames : 0), 1)) return fits;
     if (hist_frames < 5) { dabgpu_set_error("stream_bank_process_ring: the ring needs at least 5 frames"); return DABGPU_ERR_INVALID_ARG; }
     const int st = dabgpu_check_bits_layout("stream_bank_process_ring", bits_layout);
     if (st) return st;
@@ -797,6 +842,36 @@ int dabgpu_stream_bank_set_soft(dabgpu_stream_bank* b, const dabgpu_soft_cfg* cf
 int dabgpu_stream_bank_get_soft(const dabgpu_stream_bank* b, dabgpu_soft_cfg* cfg) {
     if (!b || !cfg) { dabgpu_set_error("stream_bank_get_soft: null argument"); return DABGPU_ERR_INVALID_ARG; }
     *cfg = b->soft;
+    return DABGPU_OK;
+}
+
+int dabgpu_stream_bank_set_products(dabgpu_stream_bank* b, float* d_dqpsk, dabgpu_sync_state* d_records, size_t capacity_frames) {
+    if (!b) { dabgpu_set_error("stream_bank_set_products: null bank"); return DABGPU_ERR_INVALID_ARG; }
+    if ((d_dqpsk == nullptr) != (d_records == nullptr)) {
+        dabgpu_set_error("stream_bank_set_products: the products and the records go together (both, or both NULL to switch them off)");
+        return DABGPU_ERR_INVALID_ARG;
+    }
+    if (d_dqpsk != nullptr) {
+        if (b->view.g.mode != 1) {
+            dabgpu_set_error("stream_bank_set_products: the DQPSK products exist for transmission mode I banks only (mode %d)", b->view.g.mode);
+            return DABGPU_ERR_UNSUPPORTED;
+        }
+        if (((uintptr_t)d_dqpsk & 15) || ((uintptr_t)d_records & 3)) { dabgpu_set_error("stream_bank_set_products: misaligned buffer"); return DABGPU_ERR_INVALID_ARG; }
+        if (capacity_frames == 0 || capacity_frames > (size_t)0x7FFFFFFF) {
+            dabgpu_set_error("stream_bank_set_products: capacity_frames %zu outside 1 .. 2^31 - 1", capacity_frames); return DABGPU_ERR_INVALID_ARG;
+        }
+    }
+    b->d_products = d_dqpsk;
+    b->view.records = d_records;
+    b->products_cap = d_dqpsk ? capacity_frames : 0;
+    return DABGPU_OK;
+}
+
+int dabgpu_stream_bank_get_products(const dabgpu_stream_bank* b, float** d_dqpsk, dabgpu_sync_state** d_records, size_t* capacity_frames) {
+    if (!b) { dabgpu_set_error("stream_bank_get_products: null bank"); return DABGPU_ERR_INVALID_ARG; }
+    if (d_dqpsk) *d_dqpsk = b->d_products;
+    if (d_records) *d_records = b->view.records;
+    if (capacity_frames) *capacity_frames = b->products_cap;
     return DABGPU_OK;
 }
 

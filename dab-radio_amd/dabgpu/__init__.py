@@ -94,6 +94,7 @@ ABI_SYMBOLS = [
     "dabgpu_ber_plan", "dabgpu_ber_frames_layout", "dabgpu_ber_ring_layout", "dabgpu_ber_fib_group_host_sync", "dabgpu_ber_codeword_host_sync",
     "dabgpu_soft_cfg_default", "dabgpu_soft_scale_host", "dabgpu_ofdm_demod_frames_soft", "dabgpu_ofdm_sync_demod_frames_soft",
     "dabgpu_receiver_set_soft", "dabgpu_stream_bank_set_soft", "dabgpu_stream_bank_get_soft",
+    "dabgpu_stream_bank_set_products", "dabgpu_stream_bank_get_products",
     "dabgpu_diversity_plan", "dabgpu_diversity_combine_frames", "dabgpu_diversity_combine_host_sync", "dabgpu_diversity_scale_host",
     "dabgpu_ofdm_sync_demod_frames_branch", "dabgpu_receiver_frame_soft_scale",
     "dabgpu_noise_plan", "dabgpu_noise_estimate_frames", "dabgpu_noise_estimate_host_sync", "dabgpu_noise_unbias", "dabgpu_noise_floor_host",
@@ -580,6 +581,8 @@ def lib():
         L.dabgpu_stream_bank_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_stream_bank_set_soft.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dabgpu_stream_bank_get_soft.argtypes = [C.c_void_p, C.c_void_p]
+        L.dabgpu_stream_bank_set_products.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dabgpu_stream_bank_get_products.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dabgpu_dabplus_bank_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         L.dabgpu_dabplus_bank_destroy.argtypes = [C.c_void_p]
         L.dabgpu_dabplus_bank_reset.argtypes = [C.c_void_p, C.c_void_p]
@@ -1445,6 +1448,30 @@ class StreamBank(_Handle):
         soft = SoftCfg()
         check(lib().dabgpu_stream_bank_get_soft(self._h, C.byref(soft)), "dabgpu_stream_bank_get_soft")
         return soft
+
+    def set_products(self, dqpsk, records):
+        """the DQPSK products and sync records of every frame the frames forms complete from the next call on, by bits slot: dqpsk = a
+        device tensor of [capacity][75][1536] complex64 (or [...][2] float32), records = a device tensor of capacity SYNC_STATE_DTYPE
+        records (24 bytes each; any dtype).  With set_soft's soft_scale they are a diversity branch (dqpsk, soft_scale, None, records)
+        and the (dqpsk, sync) pair of dd_profile, sym_profile, clock_estimate and clock_derotate as they stand.  Both None switches the
+        feature off.  The bank keeps the addresses: the tensors are kept alive here (dabgpu_stream_bank_set_products)"""
+        cap = 0
+        if dqpsk is not None and records is not None:
+            cap = min(int(dqpsk.numel()) * int(dqpsk.element_size()) // (75 * NB_CARRIERS * 8), int(records.numel()) * int(records.element_size()) // 24)
+        check(lib().dabgpu_stream_bank_set_products(self._h, _ptr(dqpsk), _ptr(records), cap), "dabgpu_stream_bank_set_products")
+        self._products = (dqpsk, records)
+
+    def get_products(self):
+        """(dqpsk, records, capacity in frames): the tensors set_products was given (None, None, 0 when the feature is off); the addresses
+        and the capacity are read back from the bank (dabgpu_stream_bank_get_products)"""
+        d, r, cap = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib().dabgpu_stream_bank_get_products(self._h, C.byref(d), C.byref(r), C.byref(cap)), "dabgpu_stream_bank_get_products")
+        if not d.value:
+            return None, None, 0
+        dq, rec = getattr(self, "_products", (None, None))
+        if dq is None or dq.data_ptr() != d.value or rec.data_ptr() != r.value:          # (set through the C ABI directly)
+            return d.value, r.value, cap.value
+        return dq, rec, cap.value
 
     def status(self, stream=None):
         import numpy as np

@@ -766,6 +766,28 @@ int dabgpu_stream_bank_process_ring_retained(dabgpu_stream_bank *bank, const voi
  * frame position and no status field, only the bits. */
 int dabgpu_stream_bank_set_soft(dabgpu_stream_bank *bank, const dabgpu_soft_cfg *cfg, float *d_soft_scale, size_t scale_capacity);
 int dabgpu_stream_bank_get_soft(const dabgpu_stream_bank *bank, dabgpu_soft_cfg *cfg);
+/* The DQPSK products and a sync record of every frame the frames forms complete (dabgpu_stream_bank_process, _process_raw with the fused
+ * loaders and the converted path, _process_retained), beside its soft bits: what dabgpu_ofdm_sync_demod_frames_branch writes for frames in
+ * aligned slices, from unsynchronised streams.  d_dqpsk [capacity_frames][75][1536] complex float, 16-byte aligned, d_records
+ * [capacity_frames], 4-byte aligned; both together, both NULL switches the feature off.  Both are indexed by bits slot, the numbering of
+ * d_bits and of set_soft's d_soft_scale: the frame written to bits slot j of stream s is at s * max_frames_per_stream + j.  With the
+ * bank's d_soft_scale the three arrays are a dabgpu_diversity_branch as they stand (d_dqpsk, d_scale, d_sync), and d_dqpsk with d_records
+ * is the (d_dqpsk, d_sync) pair of dabgpu_dd_profile_frames, dabgpu_sym_profile_frames, dabgpu_clock_estimate_frames and
+ * dabgpu_clock_derotate_frames: no copy.
+ *   While products are set a frames-form call first zeroes the records of all its n_streams * max_frames_per_stream slots on the caller's
+ * stream (sync_valid = 0); every completed frame then writes its products -- bit for bit the d_dqpsk view of dabgpu_ofdm_demod_frames_soft
+ * on the assembled frame at the frequency the demodulator used -- and its record: sync_valid = 1, fine_time_offset, freq_coarse and
+ * is_found_coarse the stream's when the frame was handed to the demodulator, freq_fine the fine word BEFORE this frame's phase update
+ * (float(freq_coarse + freq_fine) is the word the demodulator used), reserved = 0.  A slot without a frame keeps its old products and has
+ * a zero record; a frame beyond the caller's capacity lands in the last slot, as the bits do: products, record, scale and bits of that
+ * slot belong to the same frame.  Bits, scale words, frame counts and every status field are those of the same bank without products.
+ *   Refused while products are set, before anything is launched or converted (no output is touched, no state moves): the ring forms
+ * (DABGPU_ERR_UNSUPPORTED); a process call under DABGPU_SOFT_NORMALISED, or without a scale buffer (the consumers need the frame's scale),
+ * or with n_streams * max_frames_per_stream > capacity_frames (DABGPU_ERR_INVALID_ARG).
+ *   Synchronises with nothing; the bank keeps the addresses; kept across dabgpu_stream_bank_reset.  Mode I banks: a bank of modes II-IV
+ * answers DABGPU_ERR_UNSUPPORTED and stays off. */
+int dabgpu_stream_bank_set_products(dabgpu_stream_bank *bank, float *d_dqpsk, dabgpu_sync_state *d_records, size_t capacity_frames);
+int dabgpu_stream_bank_get_products(const dabgpu_stream_bank *bank, float **d_dqpsk, dabgpu_sync_state **d_records, size_t *capacity_frames);
 /* snapshot of every stream's getters (GetState, GetSignalAverage, Get*FrequencyOffset, ...) into host memory; synchronous */
 int dabgpu_stream_bank_status(dabgpu_stream_bank *bank, dabgpu_stream_status *h_status, void *stream);
 
