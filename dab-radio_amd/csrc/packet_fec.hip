@@ -59,7 +59,7 @@ struct PkLds {
 };
 
 // Berlekamp-Massey for row i, then omega = S C mod x^16: rs::locator's algorithm with run-time trip counts over polynomials in LDS (the
-// shared body, unrolled for register arrays, costs this kernel its occupancy).  Checked by the GPU tests alone.
+// shared body, unrolled for register arrays, costs this kernel its occupancy).  No host build runs this copy: tests/test_gpu_rs_structured.py holds it to the reference's records.
 __device__ void pk_locator(PkLds& L, int i) {
     const uint8_t* S = &L.syn[i * PK_ROOTS];
     uint8_t *C = L.lam[i], *B = L.bm_b[i], *T = L.bm_t[i];

@@ -64,3 +64,14 @@ def corrupt(rng, sf, n_rs_errors_per_codeword):
         for j in rng.choice(120, k, replace=False):
             sf[i + int(j) * n_rs] ^= rng.integers(1, 256)
     return sf
+
+
+def apply_patterns(sf, patterns):
+    """XOR error pattern i (120 symbols, 0 = the code word's first data byte) onto RS codeword i of a super frame, codeword i = sf[i + j n_rs]:
+    patterns [n_rs][120] -> a damaged copy"""
+    sf = np.array(sf, np.uint8)
+    n_rs = sf.size // 120
+    patterns = np.asarray(patterns, np.uint8)
+    assert patterns.shape == (n_rs, 120)
+    sf[:120 * n_rs] ^= patterns.T.reshape(-1)
+    return sf

@@ -610,3 +610,15 @@ def parse_log(log):
         out.append((np.asarray(log[at + 5:at + 5 + n], np.uint8), bool(flag)))
         at += 5 + n
     return out
+
+
+def apply_patterns(frame, rows):
+    """XOR error patterns (204 symbols each, 0 = the row's first data byte) onto rows of a 2472-byte FEC frame: rows = {row: pattern} or a
+    list of 12 patterns (None: the row stays) -> a damaged copy"""
+    frame = np.array(frame, np.uint8)
+    items = rows.items() if isinstance(rows, dict) else [(y, p) for y, p in enumerate(rows) if p is not None]
+    for y, p in items:
+        p = np.asarray(p, np.uint8)
+        assert p.shape == (RS_N,)
+        frame[ROW_OFFSETS[y]] ^= p
+    return frame
