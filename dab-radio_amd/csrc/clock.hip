@@ -1,6 +1,7 @@
 // clock.hip -- the sampling-clock tracker on the device (include/dabgpu.h, "Sampling-clock tracker"): an estimator that turns one frame's
 // 75 x 1536 DQPSK products into the slope of their phase ramp over the carriers, and a de-rotator that takes the ramp out again.  The
-// arithmetic is clock_core.h's (shared with the host forms and the tests' host model).
+// arithmetic is clock_core.h's (shared with the host forms and the tests' host model).  The single-frame host form is
+// host_round_trip.h's: both launches are its launch callable, the de-rotated products its payload coming back.
 //
 // Estimator: one 256-thread workgroup per frame, one pass over the products (921,600 bytes a frame), a few words written.  Thread t owns
 // the float4 positions t, t + 256 and t + 512 of every row, as in sym_profile.hip; the lag partner of position j is position j + 16 of the
@@ -22,6 +23,7 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
+#include "host_round_trip.h"
 #include "ofdm_device.h"
 #include "clock_core.h"
 
@@ -202,33 +204,22 @@ int dabgpu_clock_track_host_sync(dabgpu_ctx* c, const float* h_dqpsk_in, float* 
     if (!c || !h_dqpsk_in || !slope) { dabgpu_set_error("clock_track_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (!clk_gain_ok(gain)) { dabgpu_set_error("clock_track_host_sync: gain %g outside (0, 1]", (double)gain); return DABGPU_ERR_INVALID_ARG; }
     if (h_valid) *h_valid = 0u;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st = DABGPU_OK;
-    hipStream_t s = c->stream;
-    // the frame's products (de-rotated in place), and one block of small words: the slope, the sum, valid
-    struct small_words { int64_t slope; float corr[2]; uint32_t valid, pad; };
-    const size_t dq_bytes = (size_t)CLK_SYMBOLS * CLK_CARRIERS * 2 * sizeof(float);
-    float* d_dq;
-    small_words *d_small, back;
-    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes, (void**)&d_dq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, sizeof(small_words), (void**)&d_small))) return st;
-    DABGPU_CK(hipMemcpyAsync(d_dq, h_dqpsk_in, dq_bytes, hipMemcpyHostToDevice, s));
-    DABGPU_CK(hipMemcpyAsync(&d_small->slope, slope, sizeof(int64_t), hipMemcpyHostToDevice, s));
-    if ((st = clk_launch_estimate(d_dq, 1, nullptr, &d_small->slope, gain, clk_est_out{&d_small->slope, nullptr, d_small->corr, &d_small->valid}, s)))
-        return st;
-    if (h_dqpsk_out) {
-        dabgpu_diversity_geometry g;
-        if ((st = dabgpu_clock_derotate_plan(1, d_dq, d_dq, 1, nullptr, &d_small->slope, 0, &g))) return st;
-        if ((st = clk_launch_derotate(d_dq, d_dq, g, nullptr, &d_small->slope, s))) return st;
-        DABGPU_CK(hipMemcpyAsync(h_dqpsk_out, d_dq, dq_bytes, hipMemcpyDeviceToHost, s));
-    }
-    DABGPU_CK(hipMemcpyAsync(&back, d_small, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    *slope = back.slope;
-    if (h_corr) { h_corr[0] = back.corr[0]; h_corr[1] = back.corr[1]; }
-    if (h_valid) *h_valid = back.valid;
-    return DABGPU_OK;
+    // the frame's products (de-rotated in place, and back when the caller wants them), and one block of small words: the slope (eight
+    // bytes, aligned), the sum, valid and a word that pads the block to whole slope words; all of it comes back behind the synchronise
+    constexpr size_t W_SLOPE = 0, W_CORR = W_SLOPE + 2, W_VALID = W_CORR + 2, W_PAD = W_VALID + 1, W_END = W_PAD + 1;
+    const HostField fields[] = {{W_SLOPE, 2, slope, HOST_IN | HOST_LATE}, {W_CORR, 2, h_corr, HOST_LATE}, {W_VALID, 1, h_valid, HOST_LATE},
+                                {W_PAD, 1, nullptr, HOST_LATE}};
+    return host_round_trip(c, "clock_track_host_sync",
+                           HostPayload{SCR_HOST_DQPSK, h_dqpsk_in, (size_t)CLK_SYMBOLS * CLK_CARRIERS * 2 * sizeof(float), h_dqpsk_out}, W_END, fields,
+                           [&](float* d_dq, float* d_small, hipStream_t s) {
+                               int64_t* const d_slope = reinterpret_cast<int64_t*>(d_small + W_SLOPE);
+                               int st = clk_launch_estimate(d_dq, 1, nullptr, d_slope, gain,
+                                                            clk_est_out{d_slope, nullptr, d_small + W_CORR, reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s);
+                               if (st || !h_dqpsk_out) return st;
+                               dabgpu_diversity_geometry g;
+                               if ((st = dabgpu_clock_derotate_plan(1, d_dq, d_dq, 1, nullptr, d_slope, 0, &g))) return st;
+                               return clk_launch_derotate(d_dq, d_dq, g, nullptr, d_slope, s);
+                           });
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "dd_profile_core.h"
 #include "sym_profile_core.h"
 #include "clock_core.h"
+#include "plan_prelude.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -163,68 +164,36 @@ int dabgpu_noise_floor_host(const float group_energy[192], float signal_power, d
     return dabgpu::noise_finish(dabgpu::noise_floor(group_energy), signal_power, out) ? 1 : 0;
 }
 
+using namespace dabgpu;           // (from here on: the planners below read as their rules)
+
 int dabgpu_noise_plan(int transmission_mode, const float* d_iq, size_t n_frames, size_t stream_stride_samples, size_t null_offset_samples,
                       const dabgpu_sync_state* d_states, const float* d_freq_offset, const float* d_noise_power, const float* d_signal_power,
                       const float* d_weight, const float* d_snr, const float* d_group_energy, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
-    if (!out) { dabgpu_set_error("noise_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("noise_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("noise_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_iq) { dabgpu_set_error("noise_plan: null samples"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("noise_plan: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_states | (uintptr_t)d_freq_offset | (uintptr_t)d_noise_power | (uintptr_t)d_signal_power | (uintptr_t)d_weight | (uintptr_t)d_snr |
-         (uintptr_t)d_group_energy | (uintptr_t)d_valid) & 3) {
-        dabgpu_set_error("noise_plan: records, offsets and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    const size_t reach = (size_t)dabgpu::NOISE_REACH + (d_states ? 1543u : 0u);
-    if (null_offset_samples > ((size_t)1 << 40) || stream_stride_samples > ((size_t)1 << 40) || stream_stride_samples < null_offset_samples + reach) {
-        dabgpu_set_error("noise_plan: stream_stride_samples %zu does not hold null_offset_samples %zu + %zu", stream_stride_samples, null_offset_samples,
-                         reach);
+    static const char who[] = "noise_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) || plan_input(who, plan_or(d_iq), 8, "samples", "d_iq") ||
+        plan_aligned(who, plan_or(d_states, d_freq_offset, d_noise_power, d_signal_power, d_weight, d_snr, d_group_energy, d_valid), 4,
+                     "records, offsets and outputs") ||
+        plan_null_reach(who, stream_stride_samples, null_offset_samples, NOISE_REACH, d_states != nullptr) ||
+        plan_any_output(who, plan_or(d_noise_power, d_signal_power, d_weight, d_snr, d_group_energy, d_valid)))
         return DABGPU_ERR_INVALID_ARG;
-    }
-    if (!d_noise_power && !d_signal_power && !d_weight && !d_snr && !d_group_energy && !d_valid) {
-        dabgpu_set_error("noise_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
-    }
-    out->grid = (uint32_t)n_frames;
-    out->threads = DABGPU_NOISE_THREADS;
-    out->lds_bytes = DABGPU_NOISE_LDS_BYTES;
-    return DABGPU_OK;
+    return plan_per_frame(out, n_frames, DABGPU_NOISE_THREADS, DABGPU_NOISE_LDS_BYTES);
 }
 
 int dabgpu_noise_profile_plan(int transmission_mode, const float* d_iq, size_t n_frames, size_t stream_stride_samples, size_t null_offset_samples,
                               const dabgpu_sync_state* d_states, const float* d_freq_offset, const uint32_t* d_exclude, const float* d_profile_in,
                               float alpha, const float* d_profile_out, const float* d_band_weight, const float* d_mean_noise,
                               const float* d_carrier_power, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
-    if (!out) { dabgpu_set_error("noise_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("noise_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("noise_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_iq) { dabgpu_set_error("noise_profile_plan: null samples"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("noise_profile_plan: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_states | (uintptr_t)d_freq_offset | (uintptr_t)d_exclude | (uintptr_t)d_profile_in | (uintptr_t)d_profile_out |
-         (uintptr_t)d_band_weight | (uintptr_t)d_mean_noise | (uintptr_t)d_carrier_power | (uintptr_t)d_valid) & 3) {
-        dabgpu_set_error("noise_profile_plan: records, offsets, tables and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    const size_t reach = (size_t)dabgpu::NP_NULL + (d_states ? 1543u : 0u);
-    if (null_offset_samples > ((size_t)1 << 40) || stream_stride_samples > ((size_t)1 << 40) || stream_stride_samples < null_offset_samples + reach) {
-        dabgpu_set_error("noise_profile_plan: stream_stride_samples %zu does not hold null_offset_samples %zu + %zu", stream_stride_samples,
-                         null_offset_samples, reach);
+    static const char who[] = "noise_profile_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) || plan_input(who, plan_or(d_iq), 8, "samples", "d_iq") ||
+        plan_aligned(who, plan_or(d_states, d_freq_offset, d_exclude, d_profile_in, d_profile_out, d_band_weight, d_mean_noise, d_carrier_power, d_valid), 4,
+                     "records, offsets, tables and outputs") ||
+        plan_null_reach(who, stream_stride_samples, null_offset_samples, NP_NULL, d_states != nullptr))
         return DABGPU_ERR_INVALID_ARG;
-    }
-    if (!dabgpu::np_alpha_ok(alpha)) { dabgpu_set_error("noise_profile_plan: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
-    if (d_profile_in && d_profile_out && d_profile_in != d_profile_out) {
-        const uintptr_t a = (uintptr_t)d_profile_in, b = (uintptr_t)d_profile_out, bytes = (uintptr_t)n_frames * dabgpu::NP_BANDS * sizeof(float);
-        if (a < b + bytes && b < a + bytes) {
-            dabgpu_set_error("noise_profile_plan: d_profile_in and d_profile_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (!d_profile_out && !d_band_weight && !d_mean_noise && !d_carrier_power && !d_valid) {
-        dabgpu_set_error("noise_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
-    }
-    out->grid = (uint32_t)n_frames;
-    out->threads = DABGPU_NOISE_PROFILE_THREADS;
-    out->lds_bytes = DABGPU_NOISE_PROFILE_LDS_BYTES;
-    return DABGPU_OK;
+    if (!np_alpha_ok(alpha)) { dabgpu_set_error("%s: alpha %g outside (0, 1]", who, (double)alpha); return DABGPU_ERR_INVALID_ARG; }
+    if (plan_in_place(who, d_profile_in, d_profile_out, (uintptr_t)n_frames * NP_BANDS * sizeof(float), "d_profile_in", "d_profile_out") ||
+        plan_any_output(who, plan_or(d_profile_out, d_band_weight, d_mean_noise, d_carrier_power, d_valid)))
+        return DABGPU_ERR_INVALID_ARG;
+    return plan_per_frame(out, n_frames, DABGPU_NOISE_PROFILE_THREADS, DABGPU_NOISE_PROFILE_LDS_BYTES);
 }
 
 int dabgpu_noise_profile_bands_host(const float carrier_power[1536], const uint32_t* exclude, const float* profile_in, float alpha,
@@ -254,33 +223,16 @@ int dabgpu_noise_profile_exclude_tii(const uint8_t* main_ids, const uint8_t* sub
 int dabgpu_dd_profile_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const uint32_t* d_exclude,
                            const float* d_profile_in, float alpha, const float* d_profile_out, const float* d_band_weight, const float* d_mean_noise,
                            const float* d_carrier_noise, const float* d_carrier_amplitude, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
-    if (!out) { dabgpu_set_error("dd_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("dd_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("dd_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_dqpsk) { dabgpu_set_error("dd_profile_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("dd_profile_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_sync | (uintptr_t)d_exclude | (uintptr_t)d_profile_in | (uintptr_t)d_profile_out | (uintptr_t)d_band_weight |
-         (uintptr_t)d_mean_noise | (uintptr_t)d_valid) & 3) {
-        dabgpu_set_error("dd_profile_plan: records, tables and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_carrier_noise | (uintptr_t)d_carrier_amplitude) & 7) {
-        dabgpu_set_error("dd_profile_plan: d_carrier_noise and d_carrier_amplitude must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (!dabgpu::np_alpha_ok(alpha)) { dabgpu_set_error("dd_profile_plan: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
-    if (d_profile_in && d_profile_out && d_profile_in != d_profile_out) {
-        const uintptr_t a = (uintptr_t)d_profile_in, b = (uintptr_t)d_profile_out, bytes = (uintptr_t)n_frames * dabgpu::NP_BANDS * sizeof(float);
-        if (a < b + bytes && b < a + bytes) {
-            dabgpu_set_error("dd_profile_plan: d_profile_in and d_profile_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (!d_profile_out && !d_band_weight && !d_mean_noise && !d_carrier_noise && !d_carrier_amplitude && !d_valid) {
-        dabgpu_set_error("dd_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
-    }
-    out->grid = (uint32_t)n_frames;
-    out->threads = DABGPU_DD_PROFILE_THREADS;
-    out->lds_bytes = DABGPU_DD_PROFILE_LDS_BYTES;
-    return DABGPU_OK;
+    static const char who[] = "dd_profile_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) || plan_input(who, plan_or(d_dqpsk), 16, "products", "d_dqpsk") ||
+        plan_aligned(who, plan_or(d_sync, d_exclude, d_profile_in, d_profile_out, d_band_weight, d_mean_noise, d_valid), 4, "records, tables and outputs") ||
+        plan_aligned(who, plan_or(d_carrier_noise, d_carrier_amplitude), 8, "d_carrier_noise and d_carrier_amplitude"))
+        return DABGPU_ERR_INVALID_ARG;
+    if (!np_alpha_ok(alpha)) { dabgpu_set_error("%s: alpha %g outside (0, 1]", who, (double)alpha); return DABGPU_ERR_INVALID_ARG; }
+    if (plan_in_place(who, d_profile_in, d_profile_out, (uintptr_t)n_frames * NP_BANDS * sizeof(float), "d_profile_in", "d_profile_out") ||
+        plan_any_output(who, plan_or(d_profile_out, d_band_weight, d_mean_noise, d_carrier_noise, d_carrier_amplitude, d_valid)))
+        return DABGPU_ERR_INVALID_ARG;
+    return plan_per_frame(out, n_frames, DABGPU_DD_PROFILE_THREADS, DABGPU_DD_PROFILE_LDS_BYTES);
 }
 
 int dabgpu_dd_profile_carriers_host(const float* dqpsk, float* carrier_noise, float* carrier_amplitude) {
@@ -291,22 +243,12 @@ int dabgpu_dd_profile_carriers_host(const float* dqpsk, float* carrier_noise, fl
 
 int dabgpu_sym_profile_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const float* d_symbol_weight,
                             const float* d_symbol_noise, const float* d_ref_noise, const uint32_t* d_valid, dabgpu_noise_geometry* out) {
-    if (!out) { dabgpu_set_error("sym_profile_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("sym_profile_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("sym_profile_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_dqpsk) { dabgpu_set_error("sym_profile_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("sym_profile_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_sync | (uintptr_t)d_symbol_weight | (uintptr_t)d_symbol_noise | (uintptr_t)d_ref_noise | (uintptr_t)d_valid) & 3) {
-        dabgpu_set_error("sym_profile_plan: records and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (!d_symbol_weight && !d_symbol_noise && !d_ref_noise && !d_valid) {
-        dabgpu_set_error("sym_profile_plan: no output at all"); return DABGPU_ERR_INVALID_ARG;
-    }
-    out->grid = (uint32_t)n_frames;
-    out->threads = DABGPU_SYM_PROFILE_THREADS;
-    out->lds_bytes = DABGPU_SYM_PROFILE_LDS_BYTES;
-    return DABGPU_OK;
+    static const char who[] = "sym_profile_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) || plan_input(who, plan_or(d_dqpsk), 16, "products", "d_dqpsk") ||
+        plan_aligned(who, plan_or(d_sync, d_symbol_weight, d_symbol_noise, d_ref_noise, d_valid), 4, "records and outputs") ||
+        plan_any_output(who, plan_or(d_symbol_weight, d_symbol_noise, d_ref_noise, d_valid)))
+        return DABGPU_ERR_INVALID_ARG;
+    return plan_per_frame(out, n_frames, DABGPU_SYM_PROFILE_THREADS, DABGPU_SYM_PROFILE_LDS_BYTES);
 }
 
 int dabgpu_sym_profile_rows_host(const float* dqpsk, float* symbol_weight, float* symbol_noise, float* ref_noise) {
@@ -317,52 +259,28 @@ int dabgpu_sym_profile_rows_host(const float* dqpsk, float* symbol_weight, float
 int dabgpu_clock_estimate_plan(int transmission_mode, const float* d_dqpsk, size_t n_frames, const dabgpu_sync_state* d_sync, const int64_t* d_slope_in,
                                float gain, const int64_t* d_slope_out, const int64_t* d_residual, const float* d_corr, const uint32_t* d_valid,
                                dabgpu_noise_geometry* out) {
-    if (!out) { dabgpu_set_error("clock_estimate_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_noise_geometry{};                           // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("clock_estimate_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("clock_estimate_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_dqpsk) { dabgpu_set_error("clock_estimate_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_dqpsk & 15) { dabgpu_set_error("clock_estimate_plan: d_dqpsk must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_slope_in | (uintptr_t)d_slope_out | (uintptr_t)d_residual) & 7) {
-        dabgpu_set_error("clock_estimate_plan: slope words must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (((uintptr_t)d_sync | (uintptr_t)d_corr | (uintptr_t)d_valid) & 3) {
-        dabgpu_set_error("clock_estimate_plan: records and outputs must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (!dabgpu::clk_gain_ok(gain)) { dabgpu_set_error("clock_estimate_plan: gain %g outside (0, 1]", (double)gain); return DABGPU_ERR_INVALID_ARG; }
-    if (d_slope_in && d_slope_out && d_slope_in != d_slope_out) {
-        const uintptr_t a = (uintptr_t)d_slope_in, b = (uintptr_t)d_slope_out, bytes = (uintptr_t)n_frames * sizeof(int64_t);
-        if (a < b + bytes && b < a + bytes) {
-            dabgpu_set_error("clock_estimate_plan: d_slope_in and d_slope_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (!d_slope_out && !d_residual && !d_corr && !d_valid) { dabgpu_set_error("clock_estimate_plan: no output at all"); return DABGPU_ERR_INVALID_ARG; }
-    out->grid = (uint32_t)n_frames;
-    out->threads = DABGPU_CLOCK_THREADS;
-    out->lds_bytes = DABGPU_CLOCK_ESTIMATE_LDS_BYTES;
-    return DABGPU_OK;
+    static const char who[] = "clock_estimate_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) || plan_input(who, plan_or(d_dqpsk), 16, "products", "d_dqpsk") ||
+        plan_aligned(who, plan_or(d_slope_in, d_slope_out, d_residual), 8, "slope words") ||
+        plan_aligned(who, plan_or(d_sync, d_corr, d_valid), 4, "records and outputs"))
+        return DABGPU_ERR_INVALID_ARG;
+    if (!clk_gain_ok(gain)) { dabgpu_set_error("%s: gain %g outside (0, 1]", who, (double)gain); return DABGPU_ERR_INVALID_ARG; }
+    if (plan_in_place(who, d_slope_in, d_slope_out, (uintptr_t)n_frames * sizeof(int64_t), "d_slope_in", "d_slope_out") ||
+        plan_any_output(who, plan_or(d_slope_out, d_residual, d_corr, d_valid)))
+        return DABGPU_ERR_INVALID_ARG;
+    return plan_per_frame(out, n_frames, DABGPU_CLOCK_THREADS, DABGPU_CLOCK_ESTIMATE_LDS_BYTES);
 }
 
 int dabgpu_clock_derotate_plan(int transmission_mode, const float* d_dqpsk_in, const float* d_dqpsk_out, size_t n_frames, const dabgpu_sync_state* d_sync,
                                const int64_t* d_slope, int symbols_per_block, dabgpu_diversity_geometry* out) {
-    if (!out) { dabgpu_set_error("clock_derotate_plan: null result"); return DABGPU_ERR_INVALID_ARG; }
-    *out = dabgpu_diversity_geometry{};                       // a refusal leaves no geometry behind
-    if (transmission_mode != 1) { dabgpu_set_error("clock_derotate_plan: transmission mode %d (mode I only)", transmission_mode); return DABGPU_ERR_INVALID_ARG; }
-    if (n_frames == 0 || n_frames > ((size_t)1 << 24)) { dabgpu_set_error("clock_derotate_plan: n_frames %zu outside 1 .. 16777216", n_frames); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_dqpsk_in || !d_dqpsk_out) { dabgpu_set_error("clock_derotate_plan: null products"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_dqpsk_in | (uintptr_t)d_dqpsk_out) & 15) { dabgpu_set_error("clock_derotate_plan: products must be 16-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (d_dqpsk_in != d_dqpsk_out) {
-        const uintptr_t a = (uintptr_t)d_dqpsk_in, b = (uintptr_t)d_dqpsk_out;
-        const uintptr_t bytes = (uintptr_t)n_frames * dabgpu::CLK_SYMBOLS * dabgpu::CLK_CARRIERS * 2 * sizeof(float);
-        if (a < b + bytes && b < a + bytes) {
-            dabgpu_set_error("clock_derotate_plan: d_dqpsk_in and d_dqpsk_out overlap without being the same buffer"); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (!d_slope) { dabgpu_set_error("clock_derotate_plan: null slope words"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_slope & 7) { dabgpu_set_error("clock_derotate_plan: slope words must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_sync & 3) { dabgpu_set_error("clock_derotate_plan: records must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    if (symbols_per_block < 0 || symbols_per_block > dabgpu::CLK_SYMBOLS) {
-        dabgpu_set_error("clock_derotate_plan: symbols_per_block %d outside 0 .. 75", symbols_per_block); return DABGPU_ERR_INVALID_ARG;
+    static const char who[] = "clock_derotate_plan";
+    if (plan_open(who, out, transmission_mode, n_frames) ||
+        plan_input(who, d_dqpsk_in && d_dqpsk_out ? plan_or(d_dqpsk_in, d_dqpsk_out) : 0, 16, "products", "products") ||
+        plan_in_place(who, d_dqpsk_in, d_dqpsk_out, (uintptr_t)n_frames * CLK_SYMBOLS * CLK_CARRIERS * 2 * sizeof(float), "d_dqpsk_in", "d_dqpsk_out") ||
+        plan_input(who, plan_or(d_slope), 8, "slope words", "slope words") || plan_aligned(who, plan_or(d_sync), 4, "records"))
+        return DABGPU_ERR_INVALID_ARG;
+    if (symbols_per_block < 0 || symbols_per_block > CLK_SYMBOLS) {
+        dabgpu_set_error("%s: symbols_per_block %d outside 0 .. 75", who, symbols_per_block); return DABGPU_ERR_INVALID_ARG;
     }
     const uint32_t spb = symbols_per_block ? (uint32_t)symbols_per_block : (uint32_t)dabgpu_host_small_batch_spb(n_frames);
     out->symbols_per_block = spb;

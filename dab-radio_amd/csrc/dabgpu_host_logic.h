@@ -242,6 +242,7 @@ int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg);
 int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout, int symbols_per_block, size_t bits_frame_stride,
                                dabgpu_diversity_geometry* out);
 
+// ---- the per-frame estimators: their planners (dabgpu_host_logic.cpp) are lists of plan_prelude.h's checks with each one's own rules ----
 // ---- noise estimator (noise.hip launches from dabgpu_noise_plan; include/dabgpu.h, "Noise estimate") ----
 // one 256-thread workgroup per frame; static LDS: the transform's patches, 2048 bin powers, 192 group energies, 24 floor shares, the four
 // wave sums of the frame power and the decision word

@@ -2,7 +2,8 @@
 // 75 x 1536 DQPSK products turned into a noise power per carrier (rms of the products minus their mean projected amplitude), that into
 // the noise power of 128 bands of 12 carriers, smoothed against the caller's previous profile, and the bands' maximal-ratio weights.
 // The carrier arithmetic is dd_profile_core.h's, everything behind it noise_profile_core.h's (both shared with the host forms and the
-// tests' host model).
+// tests' host model), on the device through noise_profile_device.h, the band tail shared with noise_profile.hip.  The single-frame host
+// form is host_round_trip.h's over this file's launch and layout of the small block.
 //
 // One 256-thread workgroup per frame; the call is one pass over the products (921,600 bytes a frame) and writes about 0.5 kB.  Thread t
 // owns the carrier pairs t, t + 256 and t + 512 (carriers 2 p, 2 p + 1; a pair never straddles a band): one 16-byte load per pair and
@@ -18,7 +19,8 @@
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
 #include "dd_profile_core.h"
-#include "ofdm_device.h"
+#include "host_round_trip.h"
+#include "noise_profile_device.h"
 
 namespace dabgpu {
 
@@ -31,20 +33,14 @@ struct ddp_out { float *profile, *band_weight, *mean_noise, *carrier_noise, *car
 
 // a skipped frame: zeros everywhere, the profile kept (keep: this thread's band's previous value, 0 without one)
 __device__ __forceinline__ void ddp_skip(const ddp_out& o, size_t k, int t, float keep) {
-    if (t < NP_BANDS) {
-        if (o.profile) o.profile[k * NP_BANDS + t] = keep;
-        if (o.band_weight) o.band_weight[k * NP_BANDS + t] = 0.0f;
-    }
+    np_band_skip(o, k, t, keep);
 #pragma unroll
     for (int j = 0; j < DDP_OWN; j++) {
         const size_t at = k * DDP_PAIRS + t + DDP_THREADS * j;
         if (o.carrier_noise) reinterpret_cast<ddp_f2*>(o.carrier_noise)[at] = ddp_f2{0.0f, 0.0f};
         if (o.carrier_amplitude) reinterpret_cast<ddp_f2*>(o.carrier_amplitude)[at] = ddp_f2{0.0f, 0.0f};
     }
-    if (t == 0) {
-        if (o.mean_noise) o.mean_noise[k] = 0.0f;
-        if (o.valid) o.valid[k] = 0u;
-    }
+    np_frame_store(o, k, t, 0.0f, 0u);
 }
 
 __global__ __launch_bounds__(256)
@@ -53,12 +49,9 @@ void dd_profile_kernel(const ddp_f4* __restrict__ dq, const dabgpu_sync_state* _
 {
     __shared__ __attribute__((aligned(8))) float Qs[DDP_CARRIERS];
     __shared__ float sumS[2];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const size_t k = blockIdx.x;
-
-    // the band's previous value (profile_in may be out.profile: read here, written at the end by the same thread)
-    const bool has_prev = profile_in != nullptr;
-    const float prev = (has_prev && t < NP_BANDS) ? profile_in[k * NP_BANDS + t] : 0.0f;
+    const float prev = np_band_prev(profile_in, k, t);
 
     // a frame the synchroniser refused left stale products behind: none is read (the same for the whole workgroup)
     if (sync && !sync[k].sync_valid) {
@@ -98,24 +91,10 @@ void dd_profile_kernel(const ddp_f4* __restrict__ dq, const dabgpu_sync_state* _
     __syncthreads();
 
     // steps 3 to 5: noise_profile_core.h over Q
-    float n = 0.0f;
-    if (t < NP_BANDS) {
-        const float m = np_band_measure([&](int c) { return Qs[c]; }, t, np_band_mask(exclude, t));
-        n = np_smooth(m, has_prev, prev, alpha);
-    }
-    if (wave < 2) {                                                                    // (uniform per wave)
-        const float s = wave_tree_sum(n, lane);
-        if (lane == 0) sumS[wave] = s;
-    }
-    __syncthreads();
-    const float M = np_mean_join(sumS[0], sumS[1]);
-    if (!np_mean_ok(M)) {                                                              // (uniform)
+    float M;
+    if (!np_band_finish([&](int c) { return Qs[c]; }, exclude, profile_in, prev, alpha, sumS, out, k, t, &M)) {                        // (uniform)
         ddp_skip(out, k, t, prev);
         return;
-    }
-    if (t < NP_BANDS) {
-        if (out.profile) out.profile[k * NP_BANDS + t] = n;
-        if (out.band_weight) out.band_weight[k * NP_BANDS + t] = np_weight(n, M);
     }
 #pragma unroll
     for (int j = 0; j < DDP_OWN; j++) {
@@ -123,10 +102,7 @@ void dd_profile_kernel(const ddp_f4* __restrict__ dq, const dabgpu_sync_state* _
         if (out.carrier_noise) reinterpret_cast<ddp_f2*>(out.carrier_noise)[at] = ddp_f2{Q[2 * j], Q[2 * j + 1]};
         if (out.carrier_amplitude) reinterpret_cast<ddp_f2*>(out.carrier_amplitude)[at] = ddp_f2{A[2 * j], A[2 * j + 1]};
     }
-    if (t == 0) {
-        if (out.mean_noise) out.mean_noise[k] = M;
-        if (out.valid) out.valid[k] = 1u;
-    }
+    np_frame_store(out, k, t, M, 1u);
 }
 
 }  // namespace dabgpu
@@ -160,35 +136,21 @@ int dabgpu_dd_profile_host_sync(dabgpu_ctx* c, const float* h_dqpsk, const uint3
     if (!c || !h_dqpsk) { dabgpu_set_error("dd_profile_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (h_valid) *h_valid = 0u;
     if (!np_alpha_ok(alpha)) { dabgpu_set_error("dd_profile_host_sync: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st = DABGPU_OK;
-    hipStream_t s = c->stream;
     // the frame's products, and one block of small words: exclusion, profile, weights, mean, valid, carrier noise, carrier amplitude
     constexpr size_t W_EX = 0, W_PROF = W_EX + NP_EXCLUDE_WORDS, W_BW = W_PROF + NP_BANDS, W_MEAN = W_BW + NP_BANDS, W_VALID = W_MEAN + 1,
                      W_Q = W_VALID + 1, W_A = W_Q + DDP_CARRIERS, W_END = W_A + DDP_CARRIERS;
     static_assert(W_Q % 2 == 0 && W_A % 2 == 0, "carrier outputs are stored in pairs");
-    const size_t dq_bytes = (size_t)DDP_SYMBOLS * DDP_CARRIERS * 2 * sizeof(float);
-    float *d_dq, *d_small;
-    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes, (void**)&d_dq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, W_END * 4, (void**)&d_small))) return st;
-    DABGPU_CK(hipMemcpyAsync(d_dq, h_dqpsk, dq_bytes, hipMemcpyHostToDevice, s));
-    if (h_exclude) DABGPU_CK(hipMemcpyAsync(d_small + W_EX, h_exclude, NP_EXCLUDE_WORDS * 4, hipMemcpyHostToDevice, s));
-    if (h_profile) DABGPU_CK(hipMemcpyAsync(d_small + W_PROF, h_profile, NP_BANDS * 4, hipMemcpyHostToDevice, s));
-    if ((st = ddp_launch(d_dq, 1, nullptr, h_exclude ? reinterpret_cast<const uint32_t*>(d_small + W_EX) : nullptr, h_profile ? d_small + W_PROF : nullptr,
-                         alpha, ddp_out{d_small + W_PROF, d_small + W_BW, d_small + W_MEAN, h_carrier_noise ? d_small + W_Q : nullptr,
-                                        h_carrier_amplitude ? d_small + W_A : nullptr, reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s)))
-        return st;
-    uint32_t back[2];
-    if (h_profile) DABGPU_CK(hipMemcpyAsync(h_profile, d_small + W_PROF, NP_BANDS * 4, hipMemcpyDeviceToHost, s));
-    if (h_band_weight) DABGPU_CK(hipMemcpyAsync(h_band_weight, d_small + W_BW, NP_BANDS * 4, hipMemcpyDeviceToHost, s));
-    if (h_carrier_noise) DABGPU_CK(hipMemcpyAsync(h_carrier_noise, d_small + W_Q, DDP_CARRIERS * 4, hipMemcpyDeviceToHost, s));
-    if (h_carrier_amplitude) DABGPU_CK(hipMemcpyAsync(h_carrier_amplitude, d_small + W_A, DDP_CARRIERS * 4, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipMemcpyAsync(back, d_small + W_MEAN, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    if (h_mean_noise) memcpy(h_mean_noise, &back[0], sizeof(float));
-    if (h_valid) *h_valid = back[1];
-    return DABGPU_OK;
+    const HostField fields[] = {{W_EX, NP_EXCLUDE_WORDS, const_cast<uint32_t*>(h_exclude), HOST_IN}, {W_PROF, NP_BANDS, h_profile, HOST_IN | HOST_OUT},
+                                {W_BW, NP_BANDS, h_band_weight, HOST_OUT},                         {W_Q, DDP_CARRIERS, h_carrier_noise, HOST_OUT},
+                                {W_A, DDP_CARRIERS, h_carrier_amplitude, HOST_OUT},                {W_MEAN, 1, h_mean_noise, HOST_LATE},
+                                {W_VALID, 1, h_valid, HOST_LATE}};
+    return host_round_trip(c, "dd_profile_host_sync", HostPayload{SCR_HOST_DQPSK, h_dqpsk, (size_t)DDP_SYMBOLS * DDP_CARRIERS * 2 * sizeof(float), nullptr},
+                           W_END, fields, [&](float* d_dq, float* d_small, hipStream_t s) {
+                               return ddp_launch(d_dq, 1, nullptr, h_exclude ? reinterpret_cast<const uint32_t*>(d_small + W_EX) : nullptr,
+                                                 h_profile ? d_small + W_PROF : nullptr, alpha,
+                                                 ddp_out{d_small + W_PROF, d_small + W_BW, d_small + W_MEAN, h_carrier_noise ? d_small + W_Q : nullptr,
+                                                         h_carrier_amplitude ? d_small + W_A : nullptr, reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s);
+                           });
 }
 
 }  // extern "C"

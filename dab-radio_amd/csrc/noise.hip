@@ -1,7 +1,8 @@
 // noise.hip -- the noise estimator on the device (include/dabgpu.h, "Noise estimate"): one frame's NULL window folded into 24 x 8 group
 // energies, their floor calibrated into a noise power, the frame power of the phase reference symbol behind it, and the maximal-ratio
-// weight of the two.  The arithmetic behind the transform is noise_core.h's (shared with the host forms and the tests' host model); window,
-// rotation, transform and powers are null_window.h's, the TII detector's front half.
+// weight of the two.  The arithmetic behind the transform is noise_core.h's (shared with the host forms and the tests' host model); the
+// window's place, rotation, transform and powers are null_window.h's, the TII detector's front half.  The single-frame host form is
+// host_round_trip.h's over this file's launch, its window check plan_prelude.h's.
 //
 // One 256-thread workgroup per frame.  Every thread first requests its eight samples of the phase reference symbol (sb_lane_sample order:
 // the same four 16-byte or eight 8-byte loads as the window's), so that they travel while the window is transformed; its chain of eight
@@ -14,8 +15,10 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
+#include "host_round_trip.h"
 #include "noise_core.h"
 #include "null_window.h"
+#include "plan_prelude.h"
 
 namespace dabgpu {
 
@@ -42,21 +45,13 @@ void noise_kernel(const f2* __restrict__ iq, size_t stride, long long null_offse
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const size_t k = blockIdx.x;
 
-    // where the frame is and how its window is rotated (the same for the whole workgroup)
     float f = freq_all;
     int fto = 0;
-    if (states) {
-        const dabgpu_sync_state st = states[k];
-        // refused (also a NULL that would begin in front of the frame's slice): none of its samples is read
-        if (!st.sync_valid || !tii_time_offset_ok(st.fine_time_offset) || null_offset + st.fine_time_offset < 0) {
-            if (t == 0) noise_store(out, k, dabgpu_noise_record{0.0f, 0.0f, 0.0f, 0.0f, 0u});
-            if (out.group_energy && t < TII_ACC) out.group_energy[k * TII_ACC + t] = 0.0f;
-            return;
-        }
-        fto = st.fine_time_offset;
-        f = st.freq_coarse + st.freq_fine;
+    if (!null_window_place(states, freq, k, null_offset, true, &f, &fto)) {             // refused: none of its samples is read
+        if (t == 0) noise_store(out, k, dabgpu_noise_record{0.0f, 0.0f, 0.0f, 0.0f, 0u});
+        if (out.group_energy && t < TII_ACC) out.group_energy[k * TII_ACC + t] = 0.0f;
+        return;
     }
-    if (freq) { const float fc = freq[k]; if (fc == fc) f = fc; }                     // a caller's offset (NaN: none for this frame)
     const f2* const null0 = iq + k * stride + (null_offset + fto);
     const Fft2048Tw w = fft2048_twiddles(tw);
 
@@ -129,30 +124,18 @@ int dabgpu_noise_estimate_host_sync(dabgpu_ctx* c, const float* h_iq, size_t n_s
                                     int fine_time_offset, dabgpu_noise_record* out) {
     if (!c || !h_iq || !out) { dabgpu_set_error("noise_estimate_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
     *out = dabgpu_noise_record{};
-    if (!tii_time_offset_ok(fine_time_offset)) {
-        dabgpu_set_error("noise_estimate_host_sync: fine_time_offset %d outside -504 .. 1543", fine_time_offset); return DABGPU_ERR_INVALID_ARG;
-    }
-    const long long first = (null_offset_samples > ((size_t)1 << 40)) ? -1 : (long long)null_offset_samples + fine_time_offset;
-    if (n_samples > ((size_t)1 << 40) || first < 0 || (size_t)first + NOISE_REACH > n_samples) {
-        dabgpu_set_error("noise_estimate_host_sync: NULL and phase reference symbol at null_offset_samples %zu + fine_time_offset %d leave the %zu samples",
-                         null_offset_samples, fine_time_offset, n_samples);
-        return DABGPU_ERR_INVALID_ARG;
-    }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st = DABGPU_OK;
-    hipStream_t s = c->stream;
-    // only the frame's NULL and phase reference symbol travel
-    float *d_iq, *d_rec;
-    if ((st = dabgpu_scratch(c, SCR_HOST_IQ, (size_t)NOISE_REACH * 8, (void**)&d_iq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, sizeof(dabgpu_noise_record), (void**)&d_rec))) return st;
-    DABGPU_CK(hipMemcpyAsync(d_iq, h_iq + 2 * (size_t)first, (size_t)NOISE_REACH * 8, hipMemcpyHostToDevice, s));
-    if ((st = noise_launch(c, d_iq, 1, NOISE_REACH, 0, nullptr, nullptr, freq_offset,
-                           noise_out{d_rec, d_rec + 1, d_rec + 2, d_rec + 3, nullptr, reinterpret_cast<uint32_t*>(d_rec + 4)}, s)))
-        return st;
-    DABGPU_CK(hipMemcpyAsync(out, d_rec, sizeof(dabgpu_noise_record), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    return DABGPU_OK;
+    const char* const who = "noise_estimate_host_sync";
+    const long long first = host_window_first(who, n_samples, null_offset_samples, fine_time_offset, true, 0, NOISE_REACH,
+                                              "NULL and phase reference symbol at", "leave");
+    if (first < 0) return DABGPU_ERR_INVALID_ARG;
+    // only the frame's NULL and phase reference symbol travel; the block of small words is the record
+    constexpr size_t W_END = sizeof(dabgpu_noise_record) / 4;
+    const HostField fields[] = {{0, W_END, out, HOST_OUT}};
+    return host_round_trip(c, who, HostPayload{SCR_HOST_IQ, h_iq + 2 * (size_t)first, (size_t)NOISE_REACH * 8, nullptr}, W_END, fields,
+                           [&](float* d_iq, float* d_rec, hipStream_t s) {
+                               return noise_launch(c, d_iq, 1, NOISE_REACH, 0, nullptr, nullptr, freq_offset,
+                                                   noise_out{d_rec, d_rec + 1, d_rec + 2, d_rec + 3, nullptr, reinterpret_cast<uint32_t*>(d_rec + 4)}, s);
+                           });
 }
 
 }  // extern "C"

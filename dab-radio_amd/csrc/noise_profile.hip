@@ -1,7 +1,9 @@
 // noise_profile.hip -- the noise profile on the device (include/dabgpu.h, "Noise profile"): one frame's NULL window turned into the noise
 // power of 128 bands of 12 carriers, smoothed against the caller's previous profile, and the bands' maximal-ratio weights.  The arithmetic
-// behind the transform is noise_profile_core.h's (shared with the host forms and the tests' host model); window, rotation, transform and
-// powers are null_window.h's, the TII detector's and the noise estimator's front half.
+// behind the transform is noise_profile_core.h's (shared with the host forms and the tests' host model); the window's place, rotation,
+// transform and powers are null_window.h's, the TII detector's and the noise estimator's front half; the band tail behind the powers is
+// noise_profile_device.h's, shared with dd_profile.hip.  The single-frame host form is host_round_trip.h's over this file's launch and
+// layout of the small block, its window check plan_prelude.h's.
 //
 // One 256-thread workgroup per frame.  Threads 0 .. 127 own one band each: they request the band's previous value before the window is
 // transformed, so that it travels meanwhile, chain the band's twelve powers out of LDS, smooth, and fold the 128 values in the
@@ -14,8 +16,10 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
-#include "noise_profile_core.h"
+#include "host_round_trip.h"
+#include "noise_profile_device.h"
 #include "null_window.h"
+#include "plan_prelude.h"
 
 namespace dabgpu {
 
@@ -23,18 +27,12 @@ struct profile_out { float *profile, *band_weight, *mean_noise, *carrier_power; 
 
 // a skipped frame: zeros everywhere, the profile kept (keep: this thread's band's previous value, 0 without one)
 __device__ __forceinline__ void profile_skip(const profile_out& o, size_t k, int t, float keep) {
-    if (t < NP_BANDS) {
-        if (o.profile) o.profile[k * NP_BANDS + t] = keep;
-        if (o.band_weight) o.band_weight[k * NP_BANDS + t] = 0.0f;
-    }
+    np_band_skip(o, k, t, keep);
     if (o.carrier_power) {
 #pragma unroll
         for (int j = 0; j < NP_CARRIERS / 256; j++) o.carrier_power[k * NP_CARRIERS + t + 256 * j] = 0.0f;
     }
-    if (t == 0) {
-        if (o.mean_noise) o.mean_noise[k] = 0.0f;
-        if (o.valid) o.valid[k] = 0u;
-    }
+    np_frame_store(o, k, t, 0.0f, 0u);
 }
 
 __global__ __launch_bounds__(256)
@@ -45,50 +43,25 @@ void noise_profile_kernel(const f2* __restrict__ iq, size_t stride, long long nu
     __shared__ __attribute__((aligned(16))) f2 A[4 * WAVE_PATCH];
     __shared__ float Pw[TII_FFT];
     __shared__ float sumS[2];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const size_t k = blockIdx.x;
+    const float prev = np_band_prev(profile_in, k, t);
 
-    // the band's previous value (profile_in may be out.profile: read here, written at the end by the same thread)
-    const bool has_prev = profile_in != nullptr;
-    const float prev = (has_prev && t < NP_BANDS) ? profile_in[k * NP_BANDS + t] : 0.0f;
-
-    // where the frame is and how its window is rotated (the same for the whole workgroup)
     float f = freq_all;
     int fto = 0;
-    if (states) {
-        const dabgpu_sync_state st = states[k];
-        // refused (also a NULL that would begin in front of the frame's slice): none of its samples is read
-        if (!st.sync_valid || !tii_time_offset_ok(st.fine_time_offset) || null_offset + st.fine_time_offset < 0) {
-            profile_skip(out, k, t, prev);
-            return;
-        }
-        fto = st.fine_time_offset;
-        f = st.freq_coarse + st.freq_fine;
+    if (!null_window_place(states, freq, k, null_offset, true, &f, &fto)) {             // refused: none of its samples is read
+        profile_skip(out, k, t, prev);
+        return;
     }
-    if (freq) { const float fc = freq[k]; if (fc == fc) f = fc; }                     // a caller's offset (NaN: none for this frame)
     const f2* const null0 = iq + k * stride + (null_offset + fto);
     const Fft2048Tw w = fft2048_twiddles(tw);
 
     null_window_powers(null0 + TII_PREFIX, f, w, A, Pw, t);
 
-    float n = 0.0f;
-    if (t < NP_BANDS) {
-        const float m = np_band_measure([&](int c) { return Pw[np_carrier_bin(c)]; }, t, np_band_mask(exclude, t));
-        n = np_smooth(m, has_prev, prev, alpha);
-    }
-    if (wave < 2) {                                                                    // (uniform per wave)
-        const float s = wave_tree_sum(n, lane);
-        if (lane == 0) sumS[wave] = s;
-    }
-    __syncthreads();
-    const float M = np_mean_join(sumS[0], sumS[1]);
-    if (!np_mean_ok(M)) {                                                              // (uniform)
+    float M;
+    if (!np_band_finish([&](int c) { return Pw[np_carrier_bin(c)]; }, exclude, profile_in, prev, alpha, sumS, out, k, t, &M)) {      // (uniform)
         profile_skip(out, k, t, prev);
         return;
-    }
-    if (t < NP_BANDS) {
-        if (out.profile) out.profile[k * NP_BANDS + t] = n;
-        if (out.band_weight) out.band_weight[k * NP_BANDS + t] = np_weight(n, M);
     }
     if (out.carrier_power) {
 #pragma unroll
@@ -97,10 +70,7 @@ void noise_profile_kernel(const f2* __restrict__ iq, size_t stride, long long nu
             out.carrier_power[k * NP_CARRIERS + c] = Pw[np_carrier_bin(c)];
         }
     }
-    if (t == 0) {
-        if (out.mean_noise) out.mean_noise[k] = M;
-        if (out.valid) out.valid[k] = 1u;
-    }
+    np_frame_store(out, k, t, M, 1u);
 }
 
 }  // namespace dabgpu
@@ -137,42 +107,23 @@ int dabgpu_noise_profile_host_sync(dabgpu_ctx* c, const float* h_iq, size_t n_sa
     if (!c || !h_iq) { dabgpu_set_error("noise_profile_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (h_valid) *h_valid = 0u;
     if (!np_alpha_ok(alpha)) { dabgpu_set_error("noise_profile_host_sync: alpha %g outside (0, 1]", (double)alpha); return DABGPU_ERR_INVALID_ARG; }
-    if (!tii_time_offset_ok(fine_time_offset)) {
-        dabgpu_set_error("noise_profile_host_sync: fine_time_offset %d outside -504 .. 1543", fine_time_offset); return DABGPU_ERR_INVALID_ARG;
-    }
-    const long long first = (null_offset_samples > ((size_t)1 << 40)) ? -1 : (long long)null_offset_samples + fine_time_offset;
-    if (n_samples > ((size_t)1 << 40) || first < 0 || (size_t)first + NP_NULL > n_samples) {
-        dabgpu_set_error("noise_profile_host_sync: the NULL at null_offset_samples %zu + fine_time_offset %d leaves the %zu samples",
-                         null_offset_samples, fine_time_offset, n_samples);
-        return DABGPU_ERR_INVALID_ARG;
-    }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st = DABGPU_OK;
-    hipStream_t s = c->stream;
+    const char* const who = "noise_profile_host_sync";
+    const long long first = host_window_first(who, n_samples, null_offset_samples, fine_time_offset, true, 0, NP_NULL, "the NULL at", "leaves");
+    if (first < 0) return DABGPU_ERR_INVALID_ARG;
     // only the frame's NULL travels; behind it one block of small words: exclusion, profile, weights, mean, valid, carrier powers
     constexpr size_t W_EX = 0, W_PROF = W_EX + NP_EXCLUDE_WORDS, W_BW = W_PROF + NP_BANDS, W_MEAN = W_BW + NP_BANDS, W_VALID = W_MEAN + 1,
                      W_CP = W_VALID + 1, W_END = W_CP + NP_CARRIERS;
-    float *d_iq, *d_small;
-    if ((st = dabgpu_scratch(c, SCR_HOST_IQ, (size_t)NP_NULL * 8, (void**)&d_iq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, W_END * 4, (void**)&d_small))) return st;
-    DABGPU_CK(hipMemcpyAsync(d_iq, h_iq + 2 * (size_t)first, (size_t)NP_NULL * 8, hipMemcpyHostToDevice, s));
-    if (h_exclude) DABGPU_CK(hipMemcpyAsync(d_small + W_EX, h_exclude, NP_EXCLUDE_WORDS * 4, hipMemcpyHostToDevice, s));
-    if (h_profile) DABGPU_CK(hipMemcpyAsync(d_small + W_PROF, h_profile, NP_BANDS * 4, hipMemcpyHostToDevice, s));
-    if ((st = profile_launch(c, d_iq, 1, NP_NULL, 0, nullptr, nullptr, freq_offset, h_exclude ? reinterpret_cast<const uint32_t*>(d_small + W_EX) : nullptr,
-                             h_profile ? d_small + W_PROF : nullptr, alpha,
-                             profile_out{d_small + W_PROF, d_small + W_BW, d_small + W_MEAN, h_carrier_power ? d_small + W_CP : nullptr,
-                                         reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s)))
-        return st;
-    uint32_t back[2];
-    if (h_profile) DABGPU_CK(hipMemcpyAsync(h_profile, d_small + W_PROF, NP_BANDS * 4, hipMemcpyDeviceToHost, s));
-    if (h_band_weight) DABGPU_CK(hipMemcpyAsync(h_band_weight, d_small + W_BW, NP_BANDS * 4, hipMemcpyDeviceToHost, s));
-    if (h_carrier_power) DABGPU_CK(hipMemcpyAsync(h_carrier_power, d_small + W_CP, NP_CARRIERS * 4, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipMemcpyAsync(back, d_small + W_MEAN, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    if (h_mean_noise) memcpy(h_mean_noise, &back[0], sizeof(float));
-    if (h_valid) *h_valid = back[1];
-    return DABGPU_OK;
+    const HostField fields[] = {{W_EX, NP_EXCLUDE_WORDS, const_cast<uint32_t*>(h_exclude), HOST_IN}, {W_PROF, NP_BANDS, h_profile, HOST_IN | HOST_OUT},
+                                {W_BW, NP_BANDS, h_band_weight, HOST_OUT},                         {W_CP, NP_CARRIERS, h_carrier_power, HOST_OUT},
+                                {W_MEAN, 1, h_mean_noise, HOST_LATE},                              {W_VALID, 1, h_valid, HOST_LATE}};
+    return host_round_trip(c, who, HostPayload{SCR_HOST_IQ, h_iq + 2 * (size_t)first, (size_t)NP_NULL * 8, nullptr}, W_END, fields,
+                           [&](float* d_iq, float* d_small, hipStream_t s) {
+                               return profile_launch(c, d_iq, 1, NP_NULL, 0, nullptr, nullptr, freq_offset,
+                                                     h_exclude ? reinterpret_cast<const uint32_t*>(d_small + W_EX) : nullptr,
+                                                     h_profile ? d_small + W_PROF : nullptr, alpha,
+                                                     profile_out{d_small + W_PROF, d_small + W_BW, d_small + W_MEAN, h_carrier_power ? d_small + W_CP : nullptr,
+                                                                 reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s);
+                           });
 }
 
 }  // extern "C"

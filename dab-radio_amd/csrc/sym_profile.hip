@@ -1,7 +1,7 @@
 // sym_profile.hip -- the symbol noise profile on the device (include/dabgpu.h, "Symbol noise profile"): one frame's 75 x 1536 DQPSK
 // products turned into one noise figure per product row (the quadrature spread across the decision diagonal, lifted by the row's excess
 // rms where decisions fail) and the rows' relative weights against the frame's median.  The arithmetic is sym_profile_core.h's (shared
-// with the host forms and the tests' host model).
+// with the host forms and the tests' host model).  The single-frame host form is host_round_trip.h's over this file's launch.
 //
 // One 256-thread workgroup per frame; the call is one pass over the products (921,600 bytes a frame) and writes about 0.6 kB.  Thread t
 // owns the carrier pairs t, t + 256 and t + 512 of every row, as in dd_profile.hip: one 16-byte load per pair and row, adjacent lanes
@@ -15,6 +15,7 @@
 
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
+#include "host_round_trip.h"
 #include "ofdm_device.h"
 #include "sym_profile_core.h"
 
@@ -148,27 +149,15 @@ int dabgpu_sym_profile_host_sync(dabgpu_ctx* c, const float* h_dqpsk, float* h_s
                                  uint32_t* h_valid) {
     if (!c || !h_dqpsk) { dabgpu_set_error("sym_profile_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
     if (h_valid) *h_valid = 0u;
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    int st = DABGPU_OK;
-    hipStream_t s = c->stream;
     // the frame's products, and one block of small words: weights, noise, reference, valid
     constexpr size_t W_V = 0, W_Q = W_V + SYP_SYMBOLS, W_REF = W_Q + SYP_SYMBOLS, W_VALID = W_REF + 1, W_END = W_VALID + 1;
-    const size_t dq_bytes = (size_t)SYP_SYMBOLS * SYP_CARRIERS * 2 * sizeof(float);
-    float *d_dq, *d_small;
-    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes, (void**)&d_dq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, W_END * 4, (void**)&d_small))) return st;
-    DABGPU_CK(hipMemcpyAsync(d_dq, h_dqpsk, dq_bytes, hipMemcpyHostToDevice, s));
-    if ((st = syp_launch(d_dq, 1, nullptr, syp_out{d_small + W_V, d_small + W_Q, d_small + W_REF, reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s)))
-        return st;
-    uint32_t back[2];
-    if (h_symbol_weight) DABGPU_CK(hipMemcpyAsync(h_symbol_weight, d_small + W_V, SYP_SYMBOLS * 4, hipMemcpyDeviceToHost, s));
-    if (h_symbol_noise) DABGPU_CK(hipMemcpyAsync(h_symbol_noise, d_small + W_Q, SYP_SYMBOLS * 4, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipMemcpyAsync(back, d_small + W_REF, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    if (h_ref_noise) memcpy(h_ref_noise, &back[0], sizeof(float));
-    if (h_valid) *h_valid = back[1];
-    return DABGPU_OK;
+    const HostField fields[] = {{W_V, SYP_SYMBOLS, h_symbol_weight, HOST_OUT}, {W_Q, SYP_SYMBOLS, h_symbol_noise, HOST_OUT},
+                                {W_REF, 1, h_ref_noise, HOST_LATE},            {W_VALID, 1, h_valid, HOST_LATE}};
+    return host_round_trip(c, "sym_profile_host_sync", HostPayload{SCR_HOST_DQPSK, h_dqpsk, (size_t)SYP_SYMBOLS * SYP_CARRIERS * 2 * sizeof(float), nullptr},
+                           W_END, fields, [&](float* d_dq, float* d_small, hipStream_t s) {
+                               return syp_launch(d_dq, 1, nullptr, syp_out{d_small + W_V, d_small + W_Q, d_small + W_REF,
+                                                                           reinterpret_cast<uint32_t*>(d_small + W_VALID)}, s);
+                           });
 }
 
 }  // extern "C"

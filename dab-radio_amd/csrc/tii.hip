@@ -2,8 +2,8 @@
 // 24 x 8 group energies per receiver, accumulated over frames and decided against a noise floor.  The arithmetic behind the transform is
 // tii_core.h's (shared with the tests' host model); the transform is ofdm_fft_lds.h's, the PLL ofdm_device.h's.
 //
-// One 256-thread workgroup per receiver.  Window, rotation, transform and the 2048 powers in LDS are null_window.h's (shared with the
-// noise estimator, noise.hip); threads 0 .. 191 own one (comb, group) each for the fold
+// One 256-thread workgroup per receiver.  The window's place, rotation, transform and the 2048 powers in LDS are null_window.h's (shared
+// with noise.hip and noise_profile.hip), the process call's window checks plan_prelude.h's (shared with their planners); threads 0 .. 191 own one (comb, group) each for the fold
 // and the accumulate; wave 0 decides: lane c < 24 sorts comb c in registers, the 24 floor shares meet in LDS and every lane sums them in
 // the same order, the active lanes compact their records in comb order through a ballot.  LDS: 18432 + 8192 + 768 + 96 bytes.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include "dabgpu.h"
 #include "dabgpu_internal.h"
 #include "null_window.h"
+#include "plan_prelude.h"
 
 namespace dabgpu {
 
@@ -27,16 +28,9 @@ void tii_kernel(const f2* __restrict__ iq, size_t stride, long long null_offset,
     const int t = threadIdx.x;
     const size_t rx = blockIdx.x;
 
-    // where the window is and how it is rotated (the same for the whole workgroup)
     float f = freq_all;
     int fto = time_all;
-    if (states) {
-        const dabgpu_sync_state st = states[rx];
-        if (!st.sync_valid || !tii_time_offset_ok(st.fine_time_offset)) return;      // receiver skipped: nothing of it is touched
-        fto = st.fine_time_offset;
-        f = st.freq_coarse + st.freq_fine;
-    }
-    if (freq) { const float fc = freq[rx]; if (fc == fc) f = fc; }                   // a caller's offset (NaN: none for this receiver)
+    if (!null_window_place(states, freq, rx, null_offset, false, &f, &fto)) return;  // receiver skipped: nothing of it is touched
     const f2* win = iq + rx * stride + (null_offset + fto + TII_PREFIX);
     const Fft2048Tw w = fft2048_twiddles(tw);
     null_window_powers(win, f, w, A, Pw, t);
@@ -134,17 +128,11 @@ int dabgpu_tii_bank_reset(dabgpu_tii_bank* b, void* stream) {
 int dabgpu_tii_bank_process(dabgpu_tii_bank* b, const float* d_iq, size_t stride, size_t null_offset, const dabgpu_sync_state* d_states,
                             const float* d_freq_offset, int decide, dabgpu_tii_record* d_results, uint32_t* d_counts, void* stream) {
     if (!b) { dabgpu_set_error("tii_bank_process: null bank"); return DABGPU_ERR_INVALID_ARG; }
-    if (!d_iq) { dabgpu_set_error("tii_bank_process: null samples"); return DABGPU_ERR_INVALID_ARG; }
-    if ((uintptr_t)d_iq & 7) { dabgpu_set_error("tii_bank_process: d_iq must be 8-byte aligned"); return DABGPU_ERR_INVALID_ARG; }
-    const size_t reach = (size_t)DABGPU_NB_NULL_PERIOD + (d_states ? 1543u : 0u);
-    if (null_offset > ((size_t)1 << 40) || stride > ((size_t)1 << 40) || stride < null_offset + reach) {
-        dabgpu_set_error("tii_bank_process: stream_stride_samples %zu does not hold null_offset_samples %zu + %zu", stride, null_offset, reach);
+    const char* const who = "tii_bank_process";
+    if (plan_input(who, plan_or(d_iq), 8, "samples", "d_iq") || plan_null_reach(who, stride, null_offset, DABGPU_NB_NULL_PERIOD, d_states != nullptr))
         return DABGPU_ERR_INVALID_ARG;
-    }
-    if (decide && (!d_results || !d_counts)) { dabgpu_set_error("tii_bank_process: a decision needs d_results and d_counts"); return DABGPU_ERR_INVALID_ARG; }
-    if (((uintptr_t)d_states | (uintptr_t)d_freq_offset | (uintptr_t)d_results | (uintptr_t)d_counts) & 3) {
-        dabgpu_set_error("tii_bank_process: records, offsets, results and counts must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
+    if (decide && (!d_results || !d_counts)) { dabgpu_set_error("%s: a decision needs d_results and d_counts", who); return DABGPU_ERR_INVALID_ARG; }
+    if (plan_aligned(who, plan_or(d_states, d_freq_offset, d_results, d_counts), 4, "records, offsets, results and counts")) return DABGPU_ERR_INVALID_ARG;
     DABGPU_BIND(b->ctx);
     return tii_launch(b, d_iq, stride, (long long)null_offset, d_states, d_freq_offset, 0.0f, 0, decide, d_results, d_counts, (hipStream_t)stream);
 }
@@ -157,12 +145,9 @@ int dabgpu_tii_bank_process_host_sync(dabgpu_tii_bank* b, const float* h_iq, siz
     if (decide && (!h_results || !h_count)) {
         dabgpu_set_error("tii_bank_process_host_sync: a decision needs h_results and h_count"); return DABGPU_ERR_INVALID_ARG;
     }
-    const long long first = (null_offset > ((size_t)1 << 40)) ? -1 : (long long)null_offset + fine_time_offset + TII_PREFIX;
-    if (n_samples > ((size_t)1 << 40) || first < 0 || (size_t)first + TII_FFT > n_samples) {
-        dabgpu_set_error("tii_bank_process_host_sync: the window at null_offset_samples %zu + fine_time_offset %d + 608 leaves the %zu samples",
-                         null_offset, fine_time_offset, n_samples);
-        return DABGPU_ERR_INVALID_ARG;
-    }
+    const long long first = host_window_first("tii_bank_process_host_sync", n_samples, null_offset, fine_time_offset, false, TII_PREFIX, TII_FFT,
+                                              "the window at", "+ 608 leaves");
+    if (first < 0) return DABGPU_ERR_INVALID_ARG;
     dabgpu_ctx* c = b->ctx;
     DABGPU_BIND(c);
     DABGPU_HOST_LOCK(c);

@@ -4,7 +4,8 @@ AddressSanitizer preset, CMakePresets.json:47-53):
  (a) the CPU ORACLE -- the checker that grades everything -- built with -fsanitize=address,undefined (oracle/Makefile SAN=1) runs its
      own CPU tests clean;
  (b) the DEVICE-FREE PART OF libdabgpu.so (dab-radio_amd/csrc/dabgpu_host_logic.cpp: protection-profile plans, codeword validation,
-     mapping cost model, the decode and demodulation planners, run-length rules, constant tables, capture-format and wav-header parsing), built on its own
+     mapping cost model, the decode and demodulation planners, run-length rules, constant tables, capture-format and wav-header parsing; the
+     frame estimators' planners there are lists of the checks in the header plan_prelude.h, compiled with it), built on its own
      under ASan + UBSan and fuzzed (tests/cpp/host_logic_fuzz.cpp): hostile sub-channel descriptors, decode plans of random multiplexes and a
      table of hand-worked ones, wav images with lying chunk sizes, truncations;
  (c) the C++ MIRROR CLASSES' host code (framing state machine, frame batcher with one session per demodulator, shared context,
