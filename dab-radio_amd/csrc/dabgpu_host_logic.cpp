@@ -319,42 +319,15 @@ float dabgpu_diversity_band_mean_host(const float band_weight[128]) { return ban
 int dabgpu_diversity_plan_banded(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
                                  size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
                                  dabgpu_diversity_geometry* out) {
-    const int st = dabgpu_diversity_plan(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, out);
-    if (st || !h_band_weight) return st;
-    bool any = false;
-    for (int b = 0; b < n_branches; b++) {
-        if (!h_band_weight[b]) continue;
-        any = true;
-        if ((uintptr_t)h_band_weight[b] & 3) {
-            *out = dabgpu_diversity_geometry{};
-            dabgpu_set_error("diversity_plan_banded: branch %d: band weights must be 4-byte aligned", b); return DABGPU_ERR_INVALID_ARG;
-        }
-        if (h_branches[b].d_weight) {
-            *out = dabgpu_diversity_geometry{};
-            dabgpu_set_error("diversity_plan_banded: branch %d has both a band table and d_weight", b); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (any) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;
-    return DABGPU_OK;
+    return dabgpu_host_plan_diversity_mode(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight,
+                                           nullptr, out, nullptr);
 }
 
 int dabgpu_diversity_plan_symbols(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
                                   size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
                                   const float* const* h_symbol_weight, dabgpu_diversity_geometry* out) {
-    const int st = dabgpu_diversity_plan_banded(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
-                                                h_band_weight, out);
-    if (st || !h_symbol_weight) return st;
-    bool any = false;
-    for (int b = 0; b < n_branches; b++) {
-        if (!h_symbol_weight[b]) continue;
-        any = true;
-        if ((uintptr_t)h_symbol_weight[b] & 3) {
-            *out = dabgpu_diversity_geometry{};
-            dabgpu_set_error("diversity_plan_symbols: branch %d: symbol weights must be 4-byte aligned", b); return DABGPU_ERR_INVALID_ARG;
-        }
-    }
-    if (any) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;      // the third instantiation keeps the banded one's LDS
-    return DABGPU_OK;
+    return dabgpu_host_plan_diversity_mode(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight,
+                                           h_symbol_weight, out, nullptr);
 }
 
 void dabgpu_stream_cfg_default(dabgpu_stream_cfg* c) {
@@ -438,6 +411,33 @@ int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout,
     out->grid = (uint32_t)n_frames * out->runs_per_frame;            // at most 2^24 x 75
     out->threads = DABGPU_DIVERSITY_THREADS;
     out->lds_bytes = DABGPU_DIVERSITY_LDS_BYTES;
+    return DABGPU_OK;
+}
+
+// an optional table per branch (band weights, symbol weights): every entry given 4-byte aligned and, where the table stands in for the
+// branch's weight, no d_weight beside it.  0: no entry at all, 1: at least one, -1: refused, the reason set
+static int dv_optional_tables(const char* who, const char* noun, const float* const* table, const dabgpu_diversity_branch* br, int n, bool for_weight) {
+    int any = 0;
+    for (int b = 0; table && b < n; b++) {
+        if (!table[b]) continue;
+        any = 1;
+        if ((uintptr_t)table[b] & 3) { dabgpu_set_error("%s: branch %d: %s weights must be 4-byte aligned", who, b, noun); return -1; }
+        if (for_weight && br[b].d_weight) { dabgpu_set_error("%s: branch %d has both a %s table and d_weight", who, b, noun); return -1; }
+    }
+    return any;
+}
+
+int dabgpu_host_plan_diversity_mode(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
+                                    size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
+                                    const float* const* h_symbol_weight, dabgpu_diversity_geometry* out, int* mode) {
+    if (mode) *mode = 0;
+    const int st = dabgpu_diversity_plan(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, out);
+    if (st) return st;
+    const int band = dv_optional_tables("diversity_plan_banded", "band", h_band_weight, h_branches, n_branches, true);
+    const int sym = band < 0 ? -1 : dv_optional_tables("diversity_plan_symbols", "symbol", h_symbol_weight, h_branches, n_branches, false);
+    if (sym < 0) { *out = dabgpu_diversity_geometry{}; return DABGPU_ERR_INVALID_ARG; }
+    if (band || sym) out->lds_bytes = DABGPU_DIVERSITY_BANDED_LDS_BYTES;      // the third instantiation keeps the banded one's LDS
+    if (mode) *mode = sym ? 2 : band;
     return DABGPU_OK;
 }
 

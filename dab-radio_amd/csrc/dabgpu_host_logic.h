@@ -241,6 +241,12 @@ int dabgpu_host_check_soft_cfg(const char* who, const dabgpu_soft_cfg* cfg);
 #define DABGPU_DIVERSITY_LDS_BYTES (2u * 3072u)        // two symbol rows of soft bits: scatter into one while the other is stored
 int dabgpu_host_plan_diversity(int n_branches, size_t n_frames, int bits_layout, int symbols_per_block, size_t bits_frame_stride,
                                dabgpu_diversity_geometry* out);
+// the planner of every diversity call (dabgpu_diversity_plan_banded and _plan_symbols are this one): dabgpu_diversity_plan's checks, then
+// the band tables', then the symbol tables' (either array may be null), each refusal under its own planner's name.  *mode (may be null)
+// receives the call's effective mode, diversity.hip's dv_mode: 2 where a symbol entry is given, else 1 where a band entry is, else 0
+int dabgpu_host_plan_diversity_mode(const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, const int8_t* d_bits,
+                                    size_t bits_frame_stride, int bits_layout, int symbols_per_block, const float* const* h_band_weight,
+                                    const float* const* h_symbol_weight, dabgpu_diversity_geometry* out, int* mode);
 
 // ---- the per-frame estimators: their planners (dabgpu_host_logic.cpp) are lists of plan_prelude.h's checks with each one's own rules ----
 // ---- noise estimator (noise.hip launches from dabgpu_noise_plan; include/dabgpu.h, "Noise estimate") ----

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
 
 #include "dabgpu_internal.h"
 #include "diversity_core.h"
@@ -176,148 +177,105 @@ void diversity_combine_kernel(const typename dv_table_of<MODE>::type tab, const 
 
 using namespace dabgpu;
 
-int dabgpu_diversity_combine_frames(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
-                                    size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale, uint32_t* d_live_mask,
-                                    void* stream) {
-    if (!c) { dabgpu_set_error("diversity_combine_frames: null context"); return DABGPU_ERR_INVALID_ARG; }
+namespace {
+
+constexpr int K = DABGPU_DIVERSITY_MAX_BRANCHES;
+// by dv_mode: the device entry point, its launch label, the host form
+const char* const DV_CALL[3] = {"diversity_combine_frames", "diversity_combine_frames_banded", "diversity_combine_frames_symbols"};
+const char* const DV_LABEL[3] = {"diversity_combine_kernel launch", "diversity_combine_kernel (banded) launch", "diversity_combine_kernel (symbols) launch"};
+const char* const DV_FORM[3] = {"diversity_combine_host_sync", "diversity_combine_banded_host_sync", "diversity_combine_symbols_host_sync"};
+
+const float* dv_entry(const float* const* table, int b) { return table ? table[b] : nullptr; }
+
+// The three device entry points: `who` is the one that was called and names itself in the null-context refusal only.  Everything behind
+// the plan goes by the call's EFFECTIVE mode -- symbols where a symbol entry is given, else banded where a band entry is, else scalar
+// (dabgpu_host_plan_diversity_mode): a call without a table of its kind is the narrower call, messages, label and instantiation included.
+int dv_combine_frames(const char* who, dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                      size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale, uint32_t* d_live_mask,
+                      const float* const* h_band_weight, const float* const* h_symbol_weight, void* stream) {
+    if (!c) { dabgpu_set_error("%s: null context", who); return DABGPU_ERR_INVALID_ARG; }
     dabgpu_diversity_geometry g;
-    int st = dabgpu_diversity_plan(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, &g);
+    int mode;
+    int st = dabgpu_host_plan_diversity_mode(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight,
+                                             h_symbol_weight, &g, &mode);
     if (st) return st;
     if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
-        dabgpu_set_error("diversity_combine_frames: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
+        dabgpu_set_error("%s: d_soft_scale and d_live_mask must be 4-byte aligned", DV_CALL[mode]); return DABGPU_ERR_INVALID_ARG;
     }
     if (n_frames == 0) return DABGPU_OK;
     DABGPU_BIND(c);
     const dabgpu_mode_tables* t;
-    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames"))) return st;
-    dv_table tab;
-    memset(&tab, 0, sizeof(tab));
-    for (int b = 0; b < n_branches; b++) tab.b[b] = h_branches[b];
-    hipLaunchKernelGGL(diversity_combine_kernel<DV_SCALAR>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
-                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
-                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
-    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel launch");
+    if ((st = dabgpu_mode_tables_of(c, 1, &t, DV_CALL[mode]))) return st;
+    const auto launch = [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        typename dv_table_of<MODE>::type tab;
+        memset(&tab, 0, sizeof(tab));
+        for (int b = 0; b < n_branches; b++) {
+            tab.b[b] = h_branches[b];
+            if constexpr (MODE != DV_SCALAR) tab.band[b] = dv_entry(h_band_weight, b);
+            if constexpr (MODE == DV_SYMBOLS) tab.sym[b] = dv_entry(h_symbol_weight, b);
+        }
+        hipLaunchKernelGGL(diversity_combine_kernel<MODE>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
+                           (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
+                           bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
+    };
+    if (mode == DV_SCALAR) launch(std::integral_constant<int, DV_SCALAR>{});
+    else if (mode == DV_BANDED) launch(std::integral_constant<int, DV_BANDED>{});
+    else launch(std::integral_constant<int, DV_SYMBOLS>{});
+    return dabgpu_check_hip(hipGetLastError(), DV_LABEL[mode]);
 }
 
-int dabgpu_diversity_combine_frames_banded(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
-                                           size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale,
-                                           uint32_t* d_live_mask, const float* const* h_band_weight, void* stream) {
-    if (!c) { dabgpu_set_error("diversity_combine_frames_banded: null context"); return DABGPU_ERR_INVALID_ARG; }
-    dabgpu_diversity_geometry g;
-    int st = dabgpu_diversity_plan_banded(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight, &g);
+// The three host forms.  The form, and with it the name in its own refusals and the device call it makes, follows the ARRAYS given: without
+// h_symbol_weight it is the banded form, without h_band_weight either the scalar one (an array of null entries keeps its form).  The block of
+// small words: K scales, K weights, k and the mask, K band tables, K symbol tables.
+int dv_combine_host(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight, const int* h_valid, int n_branches,
+                    int bits_layout, int8_t* h_bits, float* h_soft_scale, uint32_t* h_live_mask, const float* const* h_band_weight,
+                    const float* const* h_symbol_weight) {
+    const int form = h_symbol_weight ? DV_SYMBOLS : h_band_weight ? DV_BANDED : DV_SCALAR;
+    const char* const who = DV_FORM[form];
+    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("%s: null argument", who); return DABGPU_ERR_INVALID_ARG; }
+    if (n_branches < 1 || n_branches > K) { dabgpu_set_error("%s: n_branches %d outside 1 .. %d", who, n_branches, K); return DABGPU_ERR_INVALID_ARG; }
+    int st = dabgpu_check_bits_layout(who, bits_layout);
     if (st) return st;
-    // no table at all: the scalar call, exactly
-    if (g.lds_bytes != DABGPU_DIVERSITY_BANDED_LDS_BYTES)
-        return dabgpu_diversity_combine_frames(c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
-                                               d_soft_scale, d_live_mask, stream);
-    if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
-        dabgpu_set_error("diversity_combine_frames_banded: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (n_frames == 0) return DABGPU_OK;
-    DABGPU_BIND(c);
-    const dabgpu_mode_tables* t;
-    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames_banded"))) return st;
-    dv_table_banded tab;
-    memset(&tab, 0, sizeof(tab));
-    for (int b = 0; b < n_branches; b++) { tab.b[b] = h_branches[b]; tab.band[b] = h_band_weight[b]; }
-    hipLaunchKernelGGL(diversity_combine_kernel<DV_BANDED>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
-                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
-                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
-    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel (banded) launch");
-}
-
-int dabgpu_diversity_combine_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight, const int* h_valid,
-                                       int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale, uint32_t* h_live_mask) {
-    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
-        dabgpu_set_error("diversity_combine_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES); return DABGPU_ERR_INVALID_ARG;
-    }
-    int st = dabgpu_check_bits_layout("diversity_combine_host_sync", bits_layout);
-    if (st) return st;
-    // what the kernel will find live decides which products are uploaded: a branch the synchroniser refused travels as scale 0
-    float small[2 * DABGPU_DIVERSITY_MAX_BRANCHES];
+    // what the kernel will find live decides which products are uploaded: a branch the synchroniser refused travels as scale 0 (symbol
+    // weights have no say in that)
+    float small[2 * K] = {};
     for (int b = 0; b < n_branches; b++) {
-        const float w = h_weight ? h_weight[b] : 1.0f;
+        const float* const hb = dv_entry(h_band_weight, b);
+        const float w = hb ? np_branch_weight(hb) : (h_weight ? h_weight[b] : 1.0f);
         const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
-        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
-        small[b] = live ? h_scale[b] : 0.0f;
-        small[DABGPU_DIVERSITY_MAX_BRANCHES + b] = w;
-    }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
-    float *d_dq, *d_small; int8_t* d_bits;
-    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * DABGPU_DIVERSITY_MAX_BRANCHES + 2) * sizeof(float), (void**)&d_small))) return st;
-    hipStream_t s = c->stream;
-    dabgpu_diversity_branch br[DABGPU_DIVERSITY_MAX_BRANCHES];
-    for (int b = 0; b < n_branches; b++) {
-        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
-        br[b].d_scale = d_small + b;
-        br[b].d_weight = d_small + DABGPU_DIVERSITY_MAX_BRANCHES + b;
-        br[b].d_sync = nullptr;
-        if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
-    float* const d_k = d_small + 2 * DABGPU_DIVERSITY_MAX_BRANCHES;
-    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
-    if ((st = dabgpu_diversity_combine_frames(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, s))) return st;
-    uint32_t back[2];
-    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
-    if (h_live_mask) *h_live_mask = back[1];
-    return DABGPU_OK;
-}
-
-int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight,
-                                              const int* h_valid, int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale,
-                                              uint32_t* h_live_mask, const float* const* h_band_weight) {
-    if (!h_band_weight)
-        return dabgpu_diversity_combine_host_sync(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale, h_live_mask);
-    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_banded_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
-        dabgpu_set_error("diversity_combine_banded_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES);
-        return DABGPU_ERR_INVALID_ARG;
-    }
-    int st = dabgpu_check_bits_layout("diversity_combine_banded_host_sync", bits_layout);
-    if (st) return st;
-    // as the scalar form: what the kernel will find live decides which products are uploaded
-    constexpr int K = DABGPU_DIVERSITY_MAX_BRANCHES;
-    float small[2 * K];
-    for (int b = 0; b < n_branches; b++) {
-        const float w = h_band_weight[b] ? np_branch_weight(h_band_weight[b]) : (h_weight ? h_weight[b] : 1.0f);
-        const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
-        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_banded_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
+        if (live && !h_dqpsk[b]) { dabgpu_set_error("%s: live branch %d has no products", who, b); return DABGPU_ERR_INVALID_ARG; }
         small[b] = live ? h_scale[b] : 0.0f;
         small[K + b] = w;
     }
     DABGPU_BIND(c);
     DABGPU_HOST_LOCK(c);
-    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
+    const size_t dq_floats = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2, dq_bytes = dq_floats * sizeof(float);
     float *d_dq, *d_small; int8_t* d_bits;
     if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
     if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * K + 2 + K * NP_BANDS) * sizeof(float), (void**)&d_small))) return st;
+    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * K + 2 + K * NP_BANDS + K * DV_DATA_SYMBOLS) * sizeof(float), (void**)&d_small))) return st;
     hipStream_t s = c->stream;
+    float* const d_k = d_small + 2 * K;
+    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
+    float* const d_band = d_k + 2;
+    float* const d_sym = d_band + (size_t)K * NP_BANDS;
     dabgpu_diversity_branch br[K];
-    const float* band[K];
-    float* const d_band = d_small + 2 * K + 2;
+    const float *band[K], *sym[K];
     for (int b = 0; b < n_branches; b++) {
-        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
+        const float *const hb = dv_entry(h_band_weight, b), *const hs = dv_entry(h_symbol_weight, b);
+        br[b].d_dqpsk = d_dq + (size_t)b * dq_floats;
         br[b].d_scale = d_small + b;
-        br[b].d_weight = h_band_weight[b] ? nullptr : d_small + K + b;
+        br[b].d_weight = hb ? nullptr : d_small + K + b;
         br[b].d_sync = nullptr;
-        band[b] = h_band_weight[b] ? d_band + (size_t)b * NP_BANDS : nullptr;
-        if (h_band_weight[b]) DABGPU_CK(hipMemcpyAsync(d_band + (size_t)b * NP_BANDS, h_band_weight[b], NP_BANDS * sizeof(float), hipMemcpyHostToDevice, s));
+        band[b] = hb ? d_band + (size_t)b * NP_BANDS : nullptr;
+        sym[b] = hs ? d_sym + (size_t)b * DV_DATA_SYMBOLS : nullptr;
+        if (hb) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(band[b]), hb, NP_BANDS * sizeof(float), hipMemcpyHostToDevice, s));
+        if (hs) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(sym[b]), hs, DV_DATA_SYMBOLS * sizeof(float), hipMemcpyHostToDevice, s));
         if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
     }
     if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
-    float* const d_k = d_small + 2 * K;
-    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
-    if ((st = dabgpu_diversity_combine_frames_banded(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, s))) return st;
+    if ((st = dv_combine_frames(DV_CALL[form], c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, sym, s))) return st;
     uint32_t back[2];
     DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
     DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
@@ -325,101 +283,45 @@ int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx* c, const float* const*
     if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
     if (h_live_mask) *h_live_mask = back[1];
     return DABGPU_OK;
+}
+
+}  // namespace
+
+int dabgpu_diversity_combine_frames(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                                    size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale, uint32_t* d_live_mask,
+                                    void* stream) {
+    return dv_combine_frames(DV_CALL[DV_SCALAR], c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, d_soft_scale,
+                             d_live_mask, nullptr, nullptr, stream);
+}
+
+int dabgpu_diversity_combine_frames_banded(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
+                                           size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale,
+                                           uint32_t* d_live_mask, const float* const* h_band_weight, void* stream) {
+    return dv_combine_frames(DV_CALL[DV_BANDED], c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, d_soft_scale,
+                             d_live_mask, h_band_weight, nullptr, stream);
 }
 
 int dabgpu_diversity_combine_frames_symbols(dabgpu_ctx* c, const dabgpu_diversity_branch* h_branches, int n_branches, size_t n_frames, int8_t* d_bits,
                                             size_t bits_frame_stride, int bits_layout, int symbols_per_block, float* d_soft_scale,
                                             uint32_t* d_live_mask, const float* const* h_band_weight, const float* const* h_symbol_weight,
                                             void* stream) {
-    if (!c) { dabgpu_set_error("diversity_combine_frames_symbols: null context"); return DABGPU_ERR_INVALID_ARG; }
-    dabgpu_diversity_geometry g;
-    int st = dabgpu_diversity_plan_symbols(h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, h_band_weight,
-                                           h_symbol_weight, &g);
-    if (st) return st;
-    // no symbol table at all: the banded call, exactly
-    bool any = false;
-    for (int b = 0; h_symbol_weight && b < n_branches; b++) any = any || h_symbol_weight[b] != nullptr;
-    if (!any)
-        return dabgpu_diversity_combine_frames_banded(c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block,
-                                                      d_soft_scale, d_live_mask, h_band_weight, stream);
-    if ((((uintptr_t)d_soft_scale | (uintptr_t)d_live_mask) & 3)) {
-        dabgpu_set_error("diversity_combine_frames_symbols: d_soft_scale and d_live_mask must be 4-byte aligned"); return DABGPU_ERR_INVALID_ARG;
-    }
-    if (n_frames == 0) return DABGPU_OK;
-    DABGPU_BIND(c);
-    const dabgpu_mode_tables* t;
-    if ((st = dabgpu_mode_tables_of(c, 1, &t, "diversity_combine_frames_symbols"))) return st;
-    dv_table_symbols tab;
-    memset(&tab, 0, sizeof(tab));
-    for (int b = 0; b < n_branches; b++) {
-        tab.b[b] = h_branches[b];
-        tab.band[b] = h_band_weight ? h_band_weight[b] : nullptr;
-        tab.sym[b] = h_symbol_weight[b];
-    }
-    hipLaunchKernelGGL(diversity_combine_kernel<DV_SYMBOLS>, dim3(g.grid), dim3(g.threads), 0, (hipStream_t)stream, tab, n_branches, (int)n_frames,
-                       (int)g.symbols_per_block, (int)g.runs_per_frame, d_bits, bits_frame_stride ? bits_frame_stride : (size_t)DABGPU_NB_FRAME_BITS,
-                       bits_layout == DABGPU_BITS_MSC_CLASSED ? 1 : 0, t->inv_map16, d_soft_scale, d_live_mask);
-    return dabgpu_check_hip(hipGetLastError(), "diversity_combine_kernel (symbols) launch");
+    return dv_combine_frames(DV_CALL[DV_SYMBOLS], c, h_branches, n_branches, n_frames, d_bits, bits_frame_stride, bits_layout, symbols_per_block, d_soft_scale,
+                             d_live_mask, h_band_weight, h_symbol_weight, stream);
+}
+
+int dabgpu_diversity_combine_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight, const int* h_valid,
+                                       int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale, uint32_t* h_live_mask) {
+    return dv_combine_host(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale, h_live_mask, nullptr, nullptr);
+}
+
+int dabgpu_diversity_combine_banded_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight,
+                                              const int* h_valid, int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale,
+                                              uint32_t* h_live_mask, const float* const* h_band_weight) {
+    return dv_combine_host(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale, h_live_mask, h_band_weight, nullptr);
 }
 
 int dabgpu_diversity_combine_symbols_host_sync(dabgpu_ctx* c, const float* const* h_dqpsk, const float* h_scale, const float* h_weight,
                                                const int* h_valid, int n_branches, int bits_layout, int8_t* h_bits, float* h_soft_scale,
                                                uint32_t* h_live_mask, const float* const* h_band_weight, const float* const* h_symbol_weight) {
-    if (!h_symbol_weight)
-        return dabgpu_diversity_combine_banded_host_sync(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale,
-                                                         h_live_mask, h_band_weight);
-    if (!c || !h_dqpsk || !h_scale || !h_bits) { dabgpu_set_error("diversity_combine_symbols_host_sync: null argument"); return DABGPU_ERR_INVALID_ARG; }
-    if (n_branches < 1 || n_branches > DABGPU_DIVERSITY_MAX_BRANCHES) {
-        dabgpu_set_error("diversity_combine_symbols_host_sync: n_branches %d outside 1 .. %d", n_branches, DABGPU_DIVERSITY_MAX_BRANCHES);
-        return DABGPU_ERR_INVALID_ARG;
-    }
-    int st = dabgpu_check_bits_layout("diversity_combine_symbols_host_sync", bits_layout);
-    if (st) return st;
-    // as the banded form: what the kernel will find live decides which products are uploaded (symbol weights have no say in that)
-    constexpr int K = DABGPU_DIVERSITY_MAX_BRANCHES;
-    float small[2 * K];
-    for (int b = 0; b < n_branches; b++) {
-        const bool banded = h_band_weight && h_band_weight[b];
-        const float w = banded ? np_branch_weight(h_band_weight[b]) : (h_weight ? h_weight[b] : 1.0f);
-        const bool live = dv_branch_live(!h_valid || h_valid[b] != 0, h_scale[b], w);
-        if (live && !h_dqpsk[b]) { dabgpu_set_error("diversity_combine_symbols_host_sync: live branch %d has no products", b); return DABGPU_ERR_INVALID_ARG; }
-        small[b] = live ? h_scale[b] : 0.0f;
-        small[K + b] = w;
-    }
-    DABGPU_BIND(c);
-    DABGPU_HOST_LOCK(c);
-    const size_t dq_bytes = (size_t)DV_DATA_SYMBOLS * DV_CARRIERS * 2 * sizeof(float);
-    float *d_dq, *d_small; int8_t* d_bits;
-    if ((st = dabgpu_scratch(c, SCR_HOST_DQPSK, dq_bytes * (size_t)n_branches, (void**)&d_dq))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_BITS, (size_t)DABGPU_NB_FRAME_BITS, (void**)&d_bits))) return st;
-    if ((st = dabgpu_scratch(c, SCR_HOST_FREQ, (2 * K + 2 + K * NP_BANDS + K * DV_DATA_SYMBOLS) * sizeof(float), (void**)&d_small))) return st;
-    hipStream_t s = c->stream;
-    dabgpu_diversity_branch br[K];
-    const float *band[K], *sym[K];
-    float* const d_band = d_small + 2 * K + 2;
-    float* const d_sym = d_band + (size_t)K * NP_BANDS;
-    for (int b = 0; b < n_branches; b++) {
-        const bool banded = h_band_weight && h_band_weight[b];
-        br[b].d_dqpsk = d_dq + (size_t)b * (dq_bytes / sizeof(float));
-        br[b].d_scale = d_small + b;
-        br[b].d_weight = banded ? nullptr : d_small + K + b;
-        br[b].d_sync = nullptr;
-        band[b] = banded ? d_band + (size_t)b * NP_BANDS : nullptr;
-        sym[b] = h_symbol_weight[b] ? d_sym + (size_t)b * DV_DATA_SYMBOLS : nullptr;
-        if (banded) DABGPU_CK(hipMemcpyAsync(d_band + (size_t)b * NP_BANDS, h_band_weight[b], NP_BANDS * sizeof(float), hipMemcpyHostToDevice, s));
-        if (h_symbol_weight[b])
-            DABGPU_CK(hipMemcpyAsync(d_sym + (size_t)b * DV_DATA_SYMBOLS, h_symbol_weight[b], DV_DATA_SYMBOLS * sizeof(float), hipMemcpyHostToDevice, s));
-        if (small[b] != 0.0f) DABGPU_CK(hipMemcpyAsync(const_cast<float*>(br[b].d_dqpsk), h_dqpsk[b], dq_bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((st = dabgpu_stage_h2d(c, d_small, small, sizeof(small), s))) return st;
-    float* const d_k = d_small + 2 * K;
-    uint32_t* const d_mask = reinterpret_cast<uint32_t*>(d_k + 1);
-    if ((st = dabgpu_diversity_combine_frames_symbols(c, br, n_branches, 1, d_bits, 0, bits_layout, 0, d_k, d_mask, band, sym, s))) return st;
-    uint32_t back[2];
-    DABGPU_CK(hipMemcpyAsync(h_bits, d_bits, (size_t)DABGPU_NB_FRAME_BITS, hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipMemcpyAsync(back, d_k, sizeof(back), hipMemcpyDeviceToHost, s));
-    DABGPU_CK(hipStreamSynchronize(s));
-    if (h_soft_scale) memcpy(h_soft_scale, &back[0], sizeof(float));
-    if (h_live_mask) *h_live_mask = back[1];
-    return DABGPU_OK;
+    return dv_combine_host(c, h_dqpsk, h_scale, h_weight, h_valid, n_branches, bits_layout, h_bits, h_soft_scale, h_live_mask, h_band_weight, h_symbol_weight);
 }

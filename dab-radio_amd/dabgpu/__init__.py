@@ -993,22 +993,18 @@ class Context:
         symbol_weights = one entry per branch, a device buffer [n_frames][75] of symbol weights (Context.sym_profile's) or None:
         dabgpu_diversity_combine_frames_symbols"""
         table = diversity_table(branches)
+        args = [self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout), int(symbols_per_block), _ptr(soft_scale),
+                _ptr(live_mask)]
+        # the entry point follows the arguments given, not what they hold (the library itself goes by that)
+        name = "dabgpu_diversity_combine_frames"
         if symbol_weights is not None:
-            bands = None if band_weights is None else band_weight_table(band_weights, len(table))
-            syms = band_weight_table(symbol_weights, len(table), "symbol_weights")
-            check(lib().dabgpu_diversity_combine_frames_symbols(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
-                                                                int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), bands, syms,
-                                                                self._stream(stream)), "dabgpu_diversity_combine_frames_symbols")
-            return
-        if band_weights is not None:
-            bands = band_weight_table(band_weights, len(table))
-            check(lib().dabgpu_diversity_combine_frames_banded(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
-                                                               int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), bands,
-                                                               self._stream(stream)), "dabgpu_diversity_combine_frames_banded")
-            return
-        check(lib().dabgpu_diversity_combine_frames(self._h, table, len(table), n_frames, _ptr(bits), bits_frame_stride, int(bits_layout),
-                                                    int(symbols_per_block), _ptr(soft_scale), _ptr(live_mask), self._stream(stream)),
-              "dabgpu_diversity_combine_frames")
+            name += "_symbols"
+            args.append(None if band_weights is None else band_weight_table(band_weights, len(table)))
+            args.append(band_weight_table(symbol_weights, len(table), "symbol_weights"))
+        elif band_weights is not None:
+            name += "_banded"
+            args.append(band_weight_table(band_weights, len(table)))
+        check(getattr(lib(), name)(*args, self._stream(stream)), name)
 
     def diversity_combine_host(self, dqpsk, scales, weights=None, valid=None, bits_layout=BITS_NATURAL, band_weights=None, symbol_weights=None):
         """numpy convenience over dabgpu_diversity_combine_host_sync: one frame; dqpsk = a list of [75][1536] complex64 arrays (None where the
@@ -1017,48 +1013,33 @@ class Context:
         dabgpu_diversity_combine_symbols_host_sync"""
         import numpy as np
         n = len(dqpsk)
+        # the entry point follows the arguments given; its tables ride behind the common arguments
+        name, tables = "dabgpu_diversity_combine_host_sync", []
         if symbol_weights is not None:
             if len(symbol_weights) != n or (band_weights is not None and len(band_weights) != n):
                 raise ValueError("diversity_combine_host: one band_weights and one symbol_weights entry per branch")
-            keep_w = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(NOISE_PROFILE_BANDS) for x in (band_weights or [None] * n)]
-            keep_s = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(SYM_PROFILE_SYMBOLS) for x in symbol_weights]
-            bands = None if band_weights is None else (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_w])
-            syms = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_s])
-            keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
-            ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
-            k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
-            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
-            v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
-            bits = np.empty(NB_FRAME_BITS, np.int8)
-            out_k, out_m = C.c_float(0.0), C.c_uint32(0)
-            check(lib().dabgpu_diversity_combine_symbols_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits),
-                                                                   C.byref(out_k), C.byref(out_m), bands, syms),
-                  "dabgpu_diversity_combine_symbols_host_sync")
-            return bits, out_k.value, out_m.value
-        if band_weights is not None:
+            name, tables = "dabgpu_diversity_combine_symbols_host_sync", [(band_weights, NOISE_PROFILE_BANDS), (symbol_weights, SYM_PROFILE_SYMBOLS)]
+        elif band_weights is not None:
             if len(band_weights) != n:
                 raise ValueError("diversity_combine_host: one band_weights entry per branch")
-            keep_w = [None if x is None else np.ascontiguousarray(x, dtype=np.float32).reshape(NOISE_PROFILE_BANDS) for x in band_weights]
-            bands = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep_w])
-            keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
-            ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
-            k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
-            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
-            v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
-            bits = np.empty(NB_FRAME_BITS, np.int8)
-            out_k, out_m = C.c_float(0.0), C.c_uint32(0)
-            check(lib().dabgpu_diversity_combine_banded_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits),
-                                                                  C.byref(out_k), C.byref(out_m), bands), "dabgpu_diversity_combine_banded_host_sync")
-            return bits, out_k.value, out_m.value
-        keep = [None if d is None else np.ascontiguousarray(d, dtype=np.complex64).reshape(-1) for d in dqpsk]
-        ptrs = (C.c_void_p * n)(*[None if d is None else d.ctypes.data for d in keep])
+            name, tables = "dabgpu_diversity_combine_banded_host_sync", [(band_weights, NOISE_PROFILE_BANDS)]
+
+        def rows(arrays, dtype, size):
+            """(the addresses of the rows, null for a row that is None; what keeps them alive), or (None, None) for no array at all"""
+            if arrays is None:
+                return None, None
+            keep = [None if x is None else np.ascontiguousarray(x, dtype=dtype).reshape(size) for x in arrays]
+            return (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in keep]), keep
+
+        ptrs, keep = rows(dqpsk, np.complex64, -1)
         k = np.ascontiguousarray(scales, dtype=np.float32).reshape(n)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(n)
         v = None if valid is None else np.ascontiguousarray(valid, dtype=np.int32).reshape(n)
+        extra = [rows(t, np.float32, size) for t, size in tables]
         bits = np.empty(NB_FRAME_BITS, np.int8)
         out_k, out_m = C.c_float(0.0), C.c_uint32(0)
-        check(lib().dabgpu_diversity_combine_host_sync(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits), C.byref(out_k),
-                                                       C.byref(out_m)), "dabgpu_diversity_combine_host_sync")
+        check(getattr(lib(), name)(self._h, ptrs, _ptr(k), _ptr(w), _ptr(v), n, int(bits_layout), _ptr(bits), C.byref(out_k), C.byref(out_m),
+                                   *[e[0] for e in extra]), name)
         return bits, out_k.value, out_m.value
 
     def noise_estimate(self, iq, n_frames, stream_stride_samples, null_offset_samples, states=None, freq_offset=None, noise_power=None,

@@ -39,6 +39,10 @@ public:
     uint32_t GetLiveMask() const { return m_live_mask; }    // bit b: branch b took part in it
 
 private:
+    using Tables = tcb::span<const tcb::span<const float>>;
+    // the body of the three overloads; a null table: the overload has none, and the narrower entry point is the one called
+    bool CombineTables(tcb::span<const tcb::span<const std::complex<float>>> products, tcb::span<const float> scales, tcb::span<const float> weights,
+                       const Tables* band_weights, const Tables* symbol_weights, tcb::span<viterbi_bit_t> out_bits);
     dabgpu_ctx* m_ctx;
     int m_nb_branches;
     int m_layout = DABGPU_BITS_NATURAL;
