@@ -111,8 +111,8 @@ static bool uniform_batch(const dabgpu_codeword* h_cw, size_t n) {
         if (h_cw[i].n_steps != h_cw[0].n_steps || memcmp(h_cw[i].seg_pi, h_cw[0].seg_pi, sizeof(h_cw[0].seg_pi)) ||
             memcmp(h_cw[i].seg_steps, h_cw[0].seg_steps, sizeof(h_cw[0].seg_steps))) return false;
         // the lane mapping keeps ring offsets in 32 bits
-        if (h_cw[i].n_slots != 0 && (uint64_t)(h_cw[i].n_slots / h_cw[i].cifs_per_frame + 1) * h_cw[i].frame_stride +
-                                    (uint64_t)h_cw[i].cifs_per_frame * h_cw[i].cif_stride >= ((uint64_t)1 << 32)) return false;
+        if (h_cw[i].n_slots != 0 && !dabgpu_host_ring_fits_lanes(h_cw[i].n_slots, h_cw[i].cifs_per_frame, h_cw[i].frame_stride, h_cw[i].cif_stride))
+            return false;
     }
     return true;
 }

@@ -729,6 +729,19 @@ dabgpu_uniform_plan dabgpu_host_plan_uniform(size_t n_cw, uint32_t n_steps, cons
     return u;
 }
 
+// vit_prep_kernel forms, in uint32_t, aoff = frame * frame_stride + cif * cif_stride + class * (cif_stride / 16) with
+// frame <= (n_slots - 1) / cifs_per_frame, cif <= cifs_per_frame - 1, class <= 15 (class-order rows only; counted for both layouts), and
+// widens before it adds the bit's index inside the row.  So aoff alone has to stay below 2^32.  (The 4-CIF ring gathers of the decode
+// calls widen every term; they are held to the same rule so that one multiplex decodes by one rule whatever its alignment.)
+bool dabgpu_host_ring_fits_lanes(uint64_t n_slots, uint64_t cifs_per_frame, uint64_t frame_stride, uint64_t cif_stride) {
+    if (n_slots == 0 || cifs_per_frame == 0) return false;
+    uint64_t top, cif;
+    if (__builtin_mul_overflow((n_slots - 1) / cifs_per_frame, frame_stride, &top)) return false;
+    if (__builtin_mul_overflow(cifs_per_frame - 1, cif_stride, &cif) || __builtin_add_overflow(top, cif, &top)) return false;
+    if (__builtin_add_overflow(top, 15 * (cif_stride >> 4), &top)) return false;
+    return top < ((uint64_t)1 << 32);
+}
+
 // Which sub-channels go to the lane-per-codeword kernel?  The k longest can be left to viterbi_kernel and the rest given to vit_lanes_kernel in
 // the same call; AUTO only compares the pure choices k = 0 and k = n_sub -- a partial viterbi_kernel launch is a single lockstep round of
 // wavefronts and measured 2x its share of a full one, so hybrids did not pay (hybrid_k forces one, for the tests).  The lane mapping keeps
@@ -740,7 +753,8 @@ static void choose_lane_subchannels(dabgpu_decode_plan& p, int hist_frames, cons
     for (int j = 0; j < n_sub; j++) { order[j] = j; steps[j] = p.subs[(size_t)j].n_steps; }
     std::sort(order, order + n_sub, [&](int a, int b) { return steps[a] > steps[b]; });
     const int m = dabgpu_host_choose_msc_mapping(lim.forced_mapping, lim.n_simd, p.n_ens, steps, n_sub, p.model_us);
-    const bool lanes_allowed = (uint64_t)hist_frames * DABGPU_NB_FRAME_BITS < ((uint64_t)1 << 32) && lim.forced_mapping != DABGPU_VIT_MAP_WAVE;
+    const bool lanes_allowed = hist_frames > 0 && dabgpu_host_ring_fits_lanes((uint64_t)hist_frames * 4, 4, DABGPU_NB_FRAME_BITS, DABGPU_NB_CIF_BITS) &&
+                               lim.forced_mapping != DABGPU_VIT_MAP_WAVE;
     p.mapping = lanes_allowed ? m : DABGPU_VIT_MAP_WAVE;
     p.k_wave = p.mapping == DABGPU_VIT_MAP_WAVE ? n_sub : 0;
     p.octet = p.mapping == DABGPU_VIT_MAP_OCTET;

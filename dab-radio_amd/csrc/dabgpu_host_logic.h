@@ -103,6 +103,10 @@ int dabgpu_host_choose_msc_mapping(int forced_mapping, double n_simd, size_t n_e
 int dabgpu_host_build_msc_plans(const dabgpu_subchannel* subs, int n_sub, std::vector<dabgpu_msc_plan>& plans, uint32_t* cif_out_bytes,
                                 uint32_t* max_steps, uint32_t* max_out_bytes);
 void dabgpu_host_fill_vit_tables(dabgpu_vit_tables* T);
+// The lane and octet gathers keep a CIF ring's offsets in 32 bits (viterbi_lanes.hip, vit_prep_kernel): is the largest one they can form
+// -- last frame, last CIF of a frame, last time-interleaver class of a class-order row -- below 2^32?  The one rule behind the decode
+// planner (n_slots = 4 history frames of 230400 soft bits) and behind the generic batch's ring-form code words.
+bool dabgpu_host_ring_fits_lanes(uint64_t n_slots, uint64_t cifs_per_frame, uint64_t frame_stride, uint64_t cif_stride);
 
 // ---- decode planner: what a batch decode call will launch, from its arguments alone (no device address enters) ----
 // what the planner may not decide for itself: the device, the environment (read once per entry-point call), the context's setting
